@@ -2,7 +2,7 @@
 """bench.py -- forward+backward throughput of the few-bit activation hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c4_tensor] [--scaling weak|strong]
-                    [--digests] [--no-extras] [--no-cpu-baseline] [--no-pmc]
+                    [--digests] [--dump-outputs DIR] [--full [--no-extras] [--no-cpu-baseline] [--no-pmc]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--config c4]
 
@@ -34,7 +34,7 @@ A rank that raises writes its traceback to `<sync dir>/error.<rank>`; the parent
 strong-scaling test compares them with slices of the unsharded result (tests/test_gpu_bench.py).
 
 Timed region (the driver's contract): exactly W warm-up steps, barrier + synchronize, host clock, EXACTLY K steps,
-synchronize, host clock, barrier.  `value` / `ms_per_step` = wall time of those K steps, max over ranks.  A second,
+synchronize, host clock, barrier.  `value` / `ms_per_step` = wall time of those K steps, max over ranks.  With --full a second,
 identical K-step region between two HIP events gives the GPU-side time of such a region (`timing.event_ms_per_step`; it
 excludes the first launch's latency from an idle queue and the wake-up after the final synchronize, ~18 us = 4 % of a
 20-step region).
@@ -43,7 +43,14 @@ excludes the first launch's latency from an idle queue and the wake-up after the
 metric = algorithmic bytes / time; algorithmic bytes per element = 4*s + k/4 (fwd: read x, write y, write state;
 bwd: read gy, read state, write gx; s = element size, k = bits) -- SURVEY.md 8(d).
 
-Besides the contract fields the line carries (N = 1, unless --no-extras):
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints the line with the contract
+fields, the config and pct_of_hbm_roofline (both from the timed region alone).  Nothing else is measured or checked.
+`--dump-outputs DIR` writes what rank 0's timed path handed back in its last step -- y, gx and the packed state of the
+forward -- as float32 DIR/<name>.npy (a fixed, seeded sample of 2^21 elements of each; 24 MiB in all): the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+`--full` adds what takes runs of its own: the event-timed K-step region (`timing.event_*`), the settled per-kernel figures
+(`fwd_us`, `bwd_us`, `roofline`), and, with N = 1, these extras (unless --no-extras):
   roofline   dominant kernel (name from fewbit_hip_describe_*), its algorithmic GB/s against the 8 TB/s HBM peak; `traffic` =
              HBM bytes per launch from two rocprofv3 --pmc child runs of this very command (measure_traffic; --no-pmc skips them
              and the figure recorded under profiles/ is replayed, labelled so)
@@ -178,6 +185,24 @@ class Workload:
         _, y, _, gx, state = self.keep[0]
         return {name: hashlib.sha256(t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()).hexdigest()
                 for name, t in (('y', y), ('state', state), ('gx', gx))}
+
+
+DUMP_SAMPLE = 1 << 21         # elements per dumped output: a fixed, seeded sample of the larger ones (3 x 8 MiB of float32)
+
+
+def dump_outputs(w, directory):
+    """--dump-outputs: y (forward), gx (backward) and the packed state of buffer set 0 as they stand after the timed steps, as
+    float32 DIR/<name>.npy; an output of more than DUMP_SAMPLE elements is sampled at positions drawn from a fixed seed"""
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    torch.cuda.synchronize()
+    _, y, _, gx, state = w.keep[0]
+    for name, t in (('y', y), ('gx', gx), ('state', state)):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(0).choice(flat.numel(), size=DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+        np.save(out / f'{name}.npy', flat.float().cpu().numpy())
 
 
 def event_time_us(launches, rounds, preroll=1):
@@ -601,26 +626,31 @@ def run_rank(args, rank, local_rank, world, make_sync):
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     sync.barrier('stop')
-    # the same K steps once more between two HIP events on the launch stream: the GPU-side time of such a region (without
-    # the first launch's latency from an idle queue and the wake-up after the synchronize, ~18 us together)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    e1.record()
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(args.steps):
-        fwd()
-        bwd()
-    e1.record()
-    torch.cuda.synchronize()
-    event = e0.elapsed_time(e1) * 1e-3
-    wall_max, event_max = sync.max([wall, event])
-    res = {'rank': rank, 'device': device.index, 'n_devices': ndev, 'wall_s': wall_max, 'event_s': event_max,
-           'own_wall_s': wall, 'own_event_s': event, 'settle_steps': settle_steps, 'set_bytes': w.set_bytes,
-           'elements': w.n, 'span': [begin, end]}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(w, args.dump_outputs)
+    res = {'rank': rank, 'device': device.index, 'n_devices': ndev, 'own_wall_s': wall, 'settle_steps': settle_steps,
+           'set_bytes': w.set_bytes, 'elements': w.n, 'span': [begin, end]}
+    if not args.full:
+        res['wall_s'], = sync.max([wall])
+    else:
+        # the same K steps once more between two HIP events on the launch stream: the GPU-side time of such a region (without
+        # the first launch's latency from an idle queue and the wake-up after the synchronize, ~18 us together)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        e1.record()
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(args.steps):
+            fwd()
+            bwd()
+        e1.record()
+        torch.cuda.synchronize()
+        event = e0.elapsed_time(e1) * 1e-3
+        res['wall_s'], res['event_s'] = sync.max([wall, event])
+        res['own_event_s'] = event
     if args.digests:
         res['sha256'] = w.digests()
-    if rank == 0:
+    if rank == 0 and args.full:
         # Per-kernel figures for `roofline`, measured AFTER the contract's region and settled: a GPU that was idle boosts for
         # ~1.5 ms, then runs 8-12 % slower for ~10 ms, then settles (scratch/timeline.py), and a short timed region (the
         # driver's K = 20 is 0.5 ms) sits inside that transient.  ~40 ms of the same steps first, then: a long alternating
@@ -660,30 +690,9 @@ def build_line(args, world, res, per_rank=None, launcher='single process'):
     n_rank0 = res.get('elements', n)                     # rank 0 owns the largest slice (shard_range gives extras to low ranks)
     sb, _ = step_bytes(cfg)                              # whole config tensor
     _, fb = step_bytes(cfg, n_rank0)                     # what ONE forward launch of rank 0 moves
-    wall, event = res['wall_s'], res['event_s']
+    wall = res['wall_s']
     total = sb * args.steps * (1 if strong else world)
     value = total / wall / 2**30
-    event_step_us = event / args.steps * 1e6
-    fwd_us, bwd_us = res['fwd_us'], res['bwd_us']
-    # forward's duration inside a step: the GPU time of a step (HIP events on the launch stream around a long, settled
-    # fwd/bwd region -- see run_rank) split in the ratio of the two kernels' stand-alone durations; rocprofv3's per-dispatch
-    # average of the same command (profiles/) is the cross-check.  The same split of the contract's own K-step region is
-    # given beside it (frac_timed_region): with a short K it sits in the clock transient after idle.
-    steady = res['steady_step_us']
-    fwd_in_step_us = steady * fwd_us / (fwd_us + bwd_us)
-    achieved = fb / (fwd_in_step_us * 1e-6) / 1e9
-    fwd_in_timed_us = event_step_us * fwd_us / (fwd_us + bwd_us)
-    traffic, traffic_source = None, None
-    tf = ROOT / 'profiles' / 'traffic_forward.json'
-    if args.config == 'c2' and world == 1 and tf.exists():
-        try:
-            doc = json.loads(tf.read_text())
-            traffic = doc.get('hbm_bytes_per_launch')
-            traffic_source = (f"replayed from {doc.get('source', 'profiles/traffic_forward.json')}: rocprofv3 --pmc FETCH_SIZE / "
-                              "WRITE_SIZE passes over `bench.py --no-extras` (tools/profile_round.sh), NOT measured in this run")
-        except Exception:  # noqa: BLE001
-            traffic = None
-    kf, kb = res['kernels']
     shared = world > res['n_devices']
     devices_used = min(world, res['n_devices'])          # ranks sharing a GPU share its 8 TB/s too
     if per_rank:
@@ -710,15 +719,84 @@ def build_line(args, world, res, per_rank=None, launcher='single process'):
                                   if res['set_bytes'] < INFINITY_CACHE_BYTES else 'one buffer set, larger than the 256 MiB Infinity Cache'},
         'timing': {'method': 'host wall clock around exactly K steps, bracketed by barrier + synchronize on both sides; max over ranks '
                              '(value, ms_per_step)',
-                   'event_ms_per_step': round(event / args.steps * 1e3, 5),
-                   'event_GiB_s': round(total / event / 2**30, 2),
-                   'event_note': 'a second, identical K-step region right after the timed one, between two HIP events on the launch '
-                                 'stream: GPU-side time of such a region, without the first launch\'s latency from an idle queue and the '
-                                 'wake-up after the final synchronize (~18 us together, profiles/r03_wall_overhead.txt)',
                    'warmup_settle': (f'{res["settle_steps"]} extra untimed steps until the GPU had been busy {args.settle_ms:g} ms'
                                      if args.settle_ms > 0 else 'off: exactly W warm-up steps')},
         'pct_of_hbm_roofline': round(100.0 * (total / wall / 1e9) / (HBM_PEAK_GBS * devices_used), 2),
-        'pct_of_hbm_roofline_event_timed': round(100.0 * (total / event / 1e9) / (HBM_PEAK_GBS * devices_used), 2),
+    }
+    if args.full:
+        add_kernel_figures(line, args, world, res, total, fb, devices_used)
+    if strong and args.emulate_world:
+        m = args.emulate_world
+        line['emulated_world'] = m
+        line['projected'] = {'n_gpus': m, 'value_GiB_s': round(sb * args.steps / wall / 2**30, 2),
+                             'pct_of_hbm_roofline': round(100.0 * (sb * args.steps / wall / 1e9) / (HBM_PEAK_GBS * m), 2),
+                             'note': f'this GPU ran rank 0\'s slice ({n_rank0} of {n} elements) of a {m}-way cut ALONE; the path has no exchange step, so {m} '
+                                     f'separate GPUs each take this time for their slice: projected whole-tensor rate = {int(sb)} B / this time. '
+                                     'A projection from one device, not a measurement on several.'}
+        line['value'] = round(step_bytes(cfg, n_rank0)[0] * args.steps / wall / 2**30, 2)     # what THIS device did
+        line['pct_of_hbm_roofline'] = round(100.0 * (step_bytes(cfg, n_rank0)[0] * args.steps / wall / 1e9) / HBM_PEAK_GBS, 2)
+        line['config']['bytes_per_step_total'] = int(step_bytes(cfg, n_rank0)[0])
+    if args.full and strong and (world > 1 or args.emulate_world):
+        line['roofline']['note'] = (f'rank 0\'s slice ({n_rank0} elements, {int(fb)} B per forward launch): at this size a launch is bounded by the '
+                                    'dispatch boundary (an empty kernel is 2.5-2.7 us), not by HBM')
+    if shared:
+        line['shared_gpu'] = True
+        line['config']['parallelism'] += (f' -- {world} ranks on {res["n_devices"]} visible device(s): ranks SHARE a GPU (validation run; '
+                                          f'pct_of_hbm_roofline is against {devices_used} x 8 TB/s)')
+    if per_rank:
+        line['per_gpu_us_per_step'] = [round(r['own_wall_s'] / args.steps * 1e6, 2) for r in per_rank]
+        if args.full:
+            line['per_gpu_event_us_per_step'] = [round(r['own_event_s'] / args.steps * 1e6, 2) for r in per_rank]
+        line['per_gpu_device'] = [r['device'] for r in per_rank]
+        if all('elements' in r for r in per_rank):
+            line['per_gpu_elements'] = [r['elements'] for r in per_rank]
+        if all('sha256' in r for r in per_rank):
+            line['per_gpu_sha256'] = [r['sha256'] for r in per_rank]
+            line['per_gpu_span'] = [r['span'] for r in per_rank]
+    elif 'sha256' in res:
+        line['per_gpu_sha256'], line['per_gpu_span'] = [res['sha256']], [res['span']]
+    if args.full:
+        line['evidence'] = {'rocprofv3_kernel_stats': 'profiles/r04_bench_kernel_stats.csv (this command with --no-extras)',
+                            'pmc_traffic': 'profiles/r04_pmc_traffic.json', 'per_config_rocprofv3_and_pmc': 'profiles/r04_configs.json',
+                            'shape_sweeps': 'profiles/r03_shape_sweep_*.txt, profiles/r04_state_staging_ab.txt',
+                            'copy_floor_at_this_size': 'profiles/r04_stream_bench_32MiB.txt',
+                            'multi_rank_launch_paths': 'profiles/r04_bench_line_{4,8}ranks_*_shared.json, profiles/r04_strong_*',
+                            'regenerate': 'bash tools/profile_round.sh r04'}
+    return line
+
+
+def add_kernel_figures(line, args, world, res, total, fb, devices_used):
+    """--full: the event-timed K-step region and the settled per-kernel figures of rank 0 (run_rank) in the line"""
+    event = res['event_s']
+    event_step_us = event / args.steps * 1e6
+    fwd_us, bwd_us = res['fwd_us'], res['bwd_us']
+    # forward's duration inside a step: the GPU time of a step (HIP events on the launch stream around a long, settled
+    # fwd/bwd region -- see run_rank) split in the ratio of the two kernels' stand-alone durations; rocprofv3's per-dispatch
+    # average of the same command (profiles/) is the cross-check.  The same split of the contract's own K-step region is
+    # given beside it (frac_timed_region): with a short K it sits in the clock transient after idle.
+    steady = res['steady_step_us']
+    fwd_in_step_us = steady * fwd_us / (fwd_us + bwd_us)
+    achieved = fb / (fwd_in_step_us * 1e-6) / 1e9
+    fwd_in_timed_us = event_step_us * fwd_us / (fwd_us + bwd_us)
+    traffic, traffic_source = None, None
+    tf = ROOT / 'profiles' / 'traffic_forward.json'
+    if args.config == 'c2' and world == 1 and tf.exists():
+        try:
+            doc = json.loads(tf.read_text())
+            traffic = doc.get('hbm_bytes_per_launch')
+            traffic_source = (f"replayed from {doc.get('source', 'profiles/traffic_forward.json')}: rocprofv3 --pmc FETCH_SIZE / "
+                              "WRITE_SIZE passes over `bench.py --no-extras` (tools/profile_round.sh), NOT measured in this run")
+        except Exception:  # noqa: BLE001
+            traffic = None
+    kf, kb = res['kernels']
+    line['timing'].update({
+        'event_ms_per_step': round(event / args.steps * 1e3, 5),
+        'event_GiB_s': round(total / event / 2**30, 2),
+        'event_note': 'a second, identical K-step region right after the timed one, between two HIP events on the launch '
+                      'stream: GPU-side time of such a region, without the first launch\'s latency from an idle queue and the '
+                      'wake-up after the final synchronize (~18 us together, profiles/r03_wall_overhead.txt)'})
+    line['pct_of_hbm_roofline_event_timed'] = round(100.0 * (total / event / 1e9) / (HBM_PEAK_GBS * devices_used), 2)
+    line.update({
         'fwd_us': round(fwd_us, 2), 'bwd_us': round(bwd_us, 2), 'fwd_in_step_us': round(fwd_in_step_us, 2),
         'roofline': {'bound': 'hbm', 'kernel': kf['kernel'], 'launch_shape': {k: kf[k] for k in ('blocks', 'threads', 'blocks_per_cu', 'chunk', 'u')},
                      'other_kernel': kb['kernel'],
@@ -733,44 +811,7 @@ def build_line(args, world, res, per_rank=None, launcher='single process'):
                      'frac_timed_region': round(fb / (fwd_in_timed_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
                      'frac_timed_region_note': f'the same split applied to a {args.steps}-step region right after the contract\'s own (event-timed, timing.event_ms_per_step)',
                      'cache_state': 'warm (x and gy are served from the Infinity Cache; writes go to HBM); frac_cold is the figure '
-                                    'with nothing cached'},
-    }
-    if strong and args.emulate_world:
-        m = args.emulate_world
-        line['emulated_world'] = m
-        line['projected'] = {'n_gpus': m, 'value_GiB_s': round(sb * args.steps / wall / 2**30, 2),
-                             'pct_of_hbm_roofline': round(100.0 * (sb * args.steps / wall / 1e9) / (HBM_PEAK_GBS * m), 2),
-                             'note': f'this GPU ran rank 0\'s slice ({n_rank0} of {n} elements) of a {m}-way cut ALONE; the path has no exchange step, so {m} '
-                                     f'separate GPUs each take this time for their slice: projected whole-tensor rate = {int(sb)} B / this time. '
-                                     'A projection from one device, not a measurement on several.'}
-        line['value'] = round(step_bytes(cfg, n_rank0)[0] * args.steps / wall / 2**30, 2)     # what THIS device did
-        line['pct_of_hbm_roofline'] = round(100.0 * (step_bytes(cfg, n_rank0)[0] * args.steps / wall / 1e9) / HBM_PEAK_GBS, 2)
-        line['config']['bytes_per_step_total'] = int(step_bytes(cfg, n_rank0)[0])
-    if strong and (world > 1 or args.emulate_world):
-        line['roofline']['note'] = (f'rank 0\'s slice ({n_rank0} elements, {int(fb)} B per forward launch): at this size a launch is bounded by the '
-                                    'dispatch boundary (an empty kernel is 2.5-2.7 us), not by HBM')
-    if shared:
-        line['shared_gpu'] = True
-        line['config']['parallelism'] += (f' -- {world} ranks on {res["n_devices"]} visible device(s): ranks SHARE a GPU (validation run; '
-                                          f'pct_of_hbm_roofline is against {devices_used} x 8 TB/s)')
-    if per_rank:
-        line['per_gpu_us_per_step'] = [round(r['own_wall_s'] / args.steps * 1e6, 2) for r in per_rank]
-        line['per_gpu_event_us_per_step'] = [round(r['own_event_s'] / args.steps * 1e6, 2) for r in per_rank]
-        line['per_gpu_device'] = [r['device'] for r in per_rank]
-        if all('elements' in r for r in per_rank):
-            line['per_gpu_elements'] = [r['elements'] for r in per_rank]
-        if all('sha256' in r for r in per_rank):
-            line['per_gpu_sha256'] = [r['sha256'] for r in per_rank]
-            line['per_gpu_span'] = [r['span'] for r in per_rank]
-    elif 'sha256' in res:
-        line['per_gpu_sha256'], line['per_gpu_span'] = [res['sha256']], [res['span']]
-    line['evidence'] = {'rocprofv3_kernel_stats': 'profiles/r04_bench_kernel_stats.csv (this command with --no-extras)',
-                        'pmc_traffic': 'profiles/r04_pmc_traffic.json', 'per_config_rocprofv3_and_pmc': 'profiles/r04_configs.json',
-                        'shape_sweeps': 'profiles/r03_shape_sweep_*.txt, profiles/r04_state_staging_ab.txt',
-                        'copy_floor_at_this_size': 'profiles/r04_stream_bench_32MiB.txt',
-                        'multi_rank_launch_paths': 'profiles/r04_bench_line_{4,8}ranks_*_shared.json, profiles/r04_strong_*',
-                        'regenerate': 'bash tools/profile_round.sh r04'}
-    return line
+                                    'with nothing cached'}})
 
 
 def under_profiler():
@@ -781,7 +822,7 @@ def under_profiler():
 def measure_traffic(args, algorithmic, steps=50):
     """HBM bytes per launch of the forward (dominant) kernel from the PMC counters, measured by THIS run: two child processes,
     `rocprofv3 --pmc FETCH_SIZE --kernel-trace` and `--pmc WRITE_SIZE --kernel-trace` (separate passes, nothing else traced), each
-    over `bench.py --no-extras --no-cpu-baseline` of the same config; per-dispatch counter rows of the forward kernel averaged;
+    over `bench.py --full --no-extras --no-cpu-baseline` of the same config; per-dispatch counter rows of the forward kernel averaged;
     gfx950 correction of MI355X_MICROARCH.md's HBM section: FETCH_SIZE (KiB) counts half of a wide coalesced read -> doubled,
     WRITE_SIZE (KiB) as is.  The same passes run from tools/profile_round.sh are kept under profiles/ as the cross-check."""
     import csv
@@ -796,7 +837,7 @@ def measure_traffic(args, algorithmic, steps=50):
             out = os.path.join(tmp, name)
             cmd = [tool, '--pmc', name, '--kernel-trace', '--output-format', 'csv', '-d', out, '-o', 'pmc', '--',
                    sys.executable, str(Path(__file__).resolve()), '--config', args.config, '--steps', str(steps), '--warmup', '5',
-                   '--no-extras', '--no-cpu-baseline']
+                   '--full', '--no-extras', '--no-cpu-baseline']
             env = dict(os.environ, TMPDIR='/tmp')
             run = subprocess.run(cmd, cwd='/tmp', env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, timeout=240)
             if run.returncode != 0:
@@ -815,7 +856,7 @@ def measure_traffic(args, algorithmic, steps=50):
             'FETCH_SIZE_KiB_raw': round(means['FETCH_SIZE'], 1), 'WRITE_SIZE_KiB': round(means['WRITE_SIZE'], 1),
             'dispatches': counts['FETCH_SIZE'], 'over_algorithmic': round((fetch + write) / algorithmic, 4),
             'source': 'measured by this run: rocprofv3 --pmc FETCH_SIZE --kernel-trace / --pmc WRITE_SIZE --kernel-trace (two child '
-                      f'processes) over `bench.py --config {args.config} --steps {steps} --warmup 5 --no-extras --no-cpu-baseline`; FETCH_SIZE x2 '
+                      f'processes) over `bench.py --config {args.config} --steps {steps} --warmup 5 --full --no-extras --no-cpu-baseline`; FETCH_SIZE x2 '
                       '(gfx950), KiB units; per launch of the forward kernel'}
 
 
@@ -898,6 +939,10 @@ def parent_launch(args):
                 '--config', args.config, '--scaling', args.scaling, '--settle-ms', str(args.settle_ms), '--sync-dir', str(sync_dir)]
         if args.digests:
             base.append('--digests')
+        if args.full:
+            base.append('--full')
+        if args.dump_outputs:
+            base += ['--dump-outputs', args.dump_outputs]
         env = dict(os.environ)
         for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
             env.pop(k, None)
@@ -932,7 +977,8 @@ def parent_launch(args):
         per_rank = [json.loads((sync_dir / f'result.{r}.json').read_text()) for r in range(world)]
         res = dict(per_rank[0])
         res['wall_s'] = max(r['own_wall_s'] for r in per_rank)
-        res['event_s'] = max(r['own_event_s'] for r in per_rank)
+        if args.full:
+            res['event_s'] = max(r['own_event_s'] for r in per_rank)
         try:
             line = build_line(args, world, res, per_rank,
                               launcher=f'bench.py started {world} child processes itself (one per device, file barriers, no process group)')
@@ -959,9 +1005,15 @@ def main():
     ap.add_argument('--settle-ms', type=float, default=0.0,
                     help='optional: keep issuing untimed warm-up steps until the GPU has been busy this long (default 0 = exactly W '
                          'steps): MI355X drops its clocks 1.5-10 ms after load begins and recovers by ~15 ms (scratch/timeline.py)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='timed region only (what the rocprofv3 passes run)')
-    ap.add_argument('--no-pmc', action='store_true', help='skip the two rocprofv3 --pmc child runs behind roofline.traffic')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what rank 0\'s last step computed (y, gx, the packed state) as float32 DIR/<name>.npy '
+                         '(a fixed, seeded sample of 2^21 elements of each)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: the event-timed region, per-kernel and roofline figures and, with N = 1, '
+                         'the extras (cold, every config, op level, sketch estimators, live PMC traffic, CPU baselines)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: no extras, the per-kernel figures only (what the rocprofv3 passes run)')
+    ap.add_argument('--no-pmc', action='store_true', help='with --full: skip the two rocprofv3 --pmc child runs behind roofline.traffic')
     ap.add_argument('--worker-rank', type=int, default=None, help=argparse.SUPPRESS)     # set by parent_launch
     ap.add_argument('--sync-dir', default=None, help=argparse.SUPPRESS)
     ap.add_argument('--launch-timeout', type=float, default=900.0, help=argparse.SUPPRESS)
@@ -1011,8 +1063,9 @@ def main():
     res, sync, device, w = run_rank(args, 0, int(os.environ.get('LOCAL_RANK', 0)), 1, lambda device: NoSync())
     line = build_line(args, 1, res)
     del w
-    torch.cuda.empty_cache()
-    add_extras(line, args, device)
+    if args.full:
+        torch.cuda.empty_cache()
+        add_extras(line, args, device)
     print(json.dumps(line), flush=True)
 
 

@@ -5,6 +5,7 @@ Run from the repo root, only where /root/reference exists:
 
     make -C oracle ref && python tests/golden/gen_golden.py            (everything)
     python tests/golden/gen_golden.py fullsize                         (only the full-size digests)
+    python tests/golden/gen_golden.py codec_random                     (only codec_ref_random.npz)
 
 What is executed is the reference itself, where it lies:
   * oracle/_ref/libfewbit_ref.so  = fewbit/fewbit.cc + fewbit/cpu/gelu.cc + fewbit/cpu/codec.cc
@@ -135,6 +136,29 @@ def gen_codec():
     print('codec_ref.npz', len(out), 'arrays')
 
 
+def gen_codec_random():
+    """the reference's Deflate / Inflate on the draws of tests/test_oracle.py::test_codec_against_compiled_reference
+    (rng seed 3; widths 1..8; n in 1 .. 4093): codes, packed bytes, and the codes the reference unpacks from those bytes"""
+    L = ctypes.CDLL(str(ROOT / 'oracle/_ref/libcodec_ref.so'))
+    L.ref_deflate_u8.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int32]
+    L.ref_inflate_u8.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int32]
+    rng = np.random.default_rng(3)
+    out = {}
+    for k in range(1, 9):
+        for n in (1, 2, 3, 7, 8, 9, 15, 16, 17, 100, 4093):
+            codes = rng.integers(0, 1 << k, n).astype(np.int32)
+            nbytes = (k * n + 7) // 8
+            buf = np.zeros(nbytes + 2, np.uint8)
+            L.ref_deflate_u8(codes.ctypes.data, n, buf.ctypes.data, k)
+            back = np.zeros(n, np.int32)
+            L.ref_inflate_u8(back.ctypes.data, n, buf.ctypes.data, k)
+            out[f'k{k}_n{n}_codes'] = codes.astype(np.uint8)
+            out[f'k{k}_n{n}_bytes'] = buf[:nbytes].copy()
+            out[f'k{k}_n{n}_back'] = back.astype(np.uint8)
+    np.savez_compressed(OUT / 'codec_ref_random.npz', **out)
+    print('codec_ref_random.npz', len(out), 'arrays')
+
+
 def gen_api(tables):
     """Import the reference python package (symlink farm + the CPU op library) and record its surface."""
     tmp = Path(tempfile.mkdtemp(prefix='fbref_'))
@@ -260,8 +284,12 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == 'c4':
         gen_c4(tables)
         return
+    if len(sys.argv) > 1 and sys.argv[1] == 'codec_random':
+        gen_codec_random()
+        return
     gen_quantize(tables)
     gen_codec()
+    gen_codec_random()
     gen_api(tables)
     gen_fullsize(tables)
     gen_c4(tables)

@@ -23,7 +23,7 @@ STUB = textwrap.dedent('''
     for a in ('--gpus', '--steps', '--warmup', '--worker-rank'):
         ap.add_argument(a, type=int)
     ap.add_argument('--config'); ap.add_argument('--settle-ms'); ap.add_argument('--sync-dir'); ap.add_argument('--scaling')
-    ap.add_argument('--digests', action='store_true')
+    ap.add_argument('--digests', action='store_true'); ap.add_argument('--full', action='store_true'); ap.add_argument('--dump-outputs')
     args = ap.parse_args()
     mode = os.environ.get('STUB_MODE', 'ok')
     rank, world = args.worker_rank, args.gpus
@@ -105,7 +105,7 @@ def test_eight_children_weak(tmp_path):
 @pytest.mark.parametrize('gpus', (2, 4, 8))
 def test_strong_scaling_line_is_one_tensor_over_n_ranks(tmp_path, gpus):
     """--scaling strong: the bytes of ONE 4096x4096 tensor / the slowest rank; every rank reports its slice."""
-    r = _run(tmp_path, 'ok', gpus=gpus, steps=20, extra=('--scaling', 'strong'))
+    r = _run(tmp_path, 'ok', gpus=gpus, steps=20, extra=('--scaling', 'strong', '--full'))
     assert r.returncode == 0, r.stderr
     line = json.loads(r.stdout.strip())
     n = 4096 * 4096

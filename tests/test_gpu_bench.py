@@ -55,9 +55,51 @@ def _check_contract(line, n_gpus, steps, warmup, scaling='weak'):
 
 
 def test_single_gpu_line():
-    line = _bench('--steps', '5', '--warmup', '2', '--no-extras', '--no-cpu-baseline')
+    line = _bench('--steps', '5', '--warmup', '2', '--full', '--no-extras', '--no-cpu-baseline')
     _check_contract(line, 1, 5, 2)
     assert 'shared_gpu' not in line
+
+
+def test_plain_line_is_the_timed_region_only():
+    """without --full: the contract fields from the K timed steps, and none of what takes runs of its own"""
+    line = _bench('--steps', '5', '--warmup', '2')
+    for key in CONTRACT:
+        assert key in line, key
+    assert line['n_gpus'] == 1 and line['steps'] == 5 and line['warmup'] == 2 and line['unit'] == 'GiB/s'
+    assert line['higher_is_better'] is True and line['dtype'] == 'bf16'
+    total = line['config']['bytes_per_step_total']
+    assert line['value'] == pytest.approx(total / (line['ms_per_step'] * 1e-3) / 2**30, rel=2e-3)
+    assert 0.0 < line['pct_of_hbm_roofline'] < 100.0
+    for key in ('roofline', 'fwd_us', 'bwd_us', 'cold', 'configs', 'op_level', 'sketch', 'cpu_baseline', 'cpu_baseline_1thread'):
+        assert key not in line, key
+    assert 'event_ms_per_step' not in line['timing']
+
+
+def test_dump_outputs_are_the_last_steps_results(tmp_path):
+    """--dump-outputs: y, gx and the packed state of the timed path, float32, a seeded sample of each -- bit for bit what one
+    launch of each kernel gives on the same seeded 4096x4096 bf16 inputs (computed here through the same C-ABI)"""
+    import numpy as np
+    import torch
+    from fewbit_amd import cabi
+    import bench
+    line = _bench('--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path / 'out'))
+    assert line['steps'] == 3
+    files = sorted(p.name for p in (tmp_path / 'out').iterdir())
+    assert files == ['gx.npy', 'state.npy', 'y.npy']
+    assert sum(p.stat().st_size for p in (tmp_path / 'out').iterdir()) <= 64 * 2**20
+    cfg = bench.CONFIGS['c2']
+    n = cfg['rows'] * cfg['cols']
+    x = torch.randn(n, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16).cuda()
+    gy = torch.randn(n, generator=torch.Generator().manual_seed(1)).to(torch.bfloat16).cuda()
+    borders, levels = bench.load_tables(cfg, 'cuda')
+    y, state = cabi.quantize_forward('gelu', x, borders)
+    gx = cabi.quantize_backward(gy, state, levels)
+    for name, t in (('y', y), ('gx', gx), ('state', state)):
+        got = np.load(tmp_path / 'out' / f'{name}.npy')
+        assert got.dtype == np.float32 and got.shape == (bench.DUMP_SAMPLE,), (name, got.dtype, got.shape)
+        pos = np.sort(np.random.default_rng(0).choice(t.numel(), size=bench.DUMP_SAMPLE, replace=False))
+        want = t.reshape(-1)[torch.from_numpy(pos).cuda()].float().cpu().numpy()
+        assert np.array_equal(got, want), name
 
 
 def test_pmc_traffic_is_measured_by_the_run_itself():
@@ -127,7 +169,7 @@ def test_sketch_extra_quotes_the_reference_ratio_at_both_widths():
 
 
 def test_self_launched_ranks_line():
-    line = _bench('--gpus', '2', '--steps', '5', '--warmup', '2')
+    line = _bench('--gpus', '2', '--steps', '5', '--warmup', '2', '--full')
     _check_contract(line, 2, 5, 2)
     assert len(line['per_gpu_us_per_step']) == 2
     import torch
@@ -138,7 +180,7 @@ def test_self_launched_ranks_line():
 
 def test_eight_self_launched_ranks_line():
     """the launch path the 8-GPU lease will take (python bench.py --gpus 8): 8 children, file barriers, one line"""
-    line = _bench('--gpus', '8', '--steps', '5', '--warmup', '2')
+    line = _bench('--gpus', '8', '--steps', '5', '--warmup', '2', '--full')
     _check_contract(line, 8, 5, 2)
     assert len(line['per_gpu_us_per_step']) == 8 and len(line['per_gpu_device']) == 8
     import torch
@@ -171,7 +213,7 @@ def test_strong_scaling_bytes_are_slices_of_the_unsharded_result(gpus):
     from fewbit_amd import cabi
     from fewbit_amd.sharding import shard_range, state_range
     import bench
-    line = _bench('--gpus', str(gpus), '--steps', '5', '--warmup', '2', '--scaling', 'strong', '--digests', '--no-extras', '--no-cpu-baseline')
+    line = _bench('--gpus', str(gpus), '--steps', '5', '--warmup', '2', '--scaling', 'strong', '--digests', '--full', '--no-extras', '--no-cpu-baseline')
     _check_contract(line, gpus, 5, 2, scaling='strong')
     cfg = bench.CONFIGS['c2']
     n = cfg['rows'] * cfg['cols']
@@ -201,7 +243,7 @@ def test_the_drivers_torchrun_form_with_two_ranks():
         env.pop(k, None)
     base = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1']
     for port, extra, scaling in (('29531', (), 'weak'), ('29532', ('--scaling', 'strong', '--digests'), 'strong')):
-        r = subprocess.run(base + ['--master-port', port, str(ROOT / 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2', *extra],
+        r = subprocess.run(base + ['--master-port', port, str(ROOT / 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2', '--full', *extra],
                            env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [l for l in r.stdout.splitlines() if l.startswith('{')]

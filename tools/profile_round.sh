@@ -3,9 +3,9 @@
 # profiles/ after review).
 #   usage (through gpurun):  bash tools/profile_round.sh r02
 # Separate passes, as MI355X_MICROARCH.md prescribes (PMC never combined with other trace domains than --kernel-trace):
-#   1. python3 bench.py                                   -> <round>_bench_line.json  (the driver-visible line, all extras)
-#   2. rocprofv3 --kernel-trace --stats   bench.py --no-extras   -> kernel stats of the timed region's command (C2)
-#   3. rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE  bench.py --no-extras --steps 50   -> HBM traffic per launch (C2)
+#   1. python3 bench.py --full                            -> <round>_bench_line.json  (the driver-visible line, all extras)
+#   2. rocprofv3 --kernel-trace --stats   bench.py --full --no-extras  -> kernel stats of the timed region's command (C2)
+#   3. rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE  bench.py --full --no-extras --steps 50   -> HBM traffic per launch (C2)
 #   4. rocprofv3 --kernel-trace / --pmc FETCH_SIZE / --pmc WRITE_SIZE   tools/config_runs.py
 #      -> per-dispatch durations and traffic of EVERY config, warm and cold (split by tools/summarize_profiles.py)
 #   5. bench.py --config c4 / --steps 20 / 2 ranks on the one GPU (self-launched and under torch.distributed.run), stream
@@ -19,36 +19,36 @@ export TMPDIR=/tmp
 RAW=$ROOT/gpurun_out/prof_$R
 OUT=$ROOT/gpurun_out/profiles_$R
 rm -rf "$RAW"; mkdir -p "$RAW" "$OUT"
-python3 bench.py > "$OUT/${R}_bench_line.json" 2> "$RAW/bench.err"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$RAW/trace" -o bench -- python3 bench.py --no-extras --no-cpu-baseline > "$RAW/bench_under_trace.json" 2> "$RAW/trace.err"
-timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$RAW/fetch" -o bench -- python3 bench.py --steps 50 --warmup 5 --no-extras --no-cpu-baseline > /dev/null 2> "$RAW/fetch.err"
-timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$RAW/write" -o bench -- python3 bench.py --steps 50 --warmup 5 --no-extras --no-cpu-baseline > /dev/null 2> "$RAW/write.err"
+python3 bench.py --full > "$OUT/${R}_bench_line.json" 2> "$RAW/bench.err"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$RAW/trace" -o bench -- python3 bench.py --full --no-extras --no-cpu-baseline > "$RAW/bench_under_trace.json" 2> "$RAW/trace.err"
+timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$RAW/fetch" -o bench -- python3 bench.py --full --steps 50 --warmup 5 --no-extras --no-cpu-baseline > /dev/null 2> "$RAW/fetch.err"
+timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$RAW/write" -o bench -- python3 bench.py --full --steps 50 --warmup 5 --no-extras --no-cpu-baseline > /dev/null 2> "$RAW/write.err"
 timeout 900 rocprofv3 --kernel-trace --output-format csv -d "$RAW/cfg_trace" -o cfg -- python3 tools/config_runs.py "$RAW/cfg_trace/phases.json" 120 > /dev/null 2> "$RAW/cfg_trace.err"
 timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$RAW/cfg_fetch" -o cfg -- python3 tools/config_runs.py "$RAW/cfg_fetch/phases.json" 30 > /dev/null 2> "$RAW/cfg_fetch.err"
 timeout 900 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$RAW/cfg_write" -o cfg -- python3 tools/config_runs.py "$RAW/cfg_write/phases.json" 30 > /dev/null 2> "$RAW/cfg_write.err"
 python3 tools/summarize_profiles.py "$R" "$RAW" "$OUT"
 # 5. the other driver-visible lines and the side measurements DESIGN.md and EXPERIMENTS.md quote
-python3 bench.py --config c4 --no-cpu-baseline > "$OUT/${R}_bench_line_c4.json" 2>> "$RAW/bench.err"
-python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline > "$OUT/${R}_bench_line_k20.json" 2>> "$RAW/bench.err"
+python3 bench.py --full --config c4 --no-cpu-baseline > "$OUT/${R}_bench_line_c4.json" 2>> "$RAW/bench.err"
+python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline > "$OUT/${R}_bench_line_k20.json" 2>> "$RAW/bench.err"
 # N > 1 on the one GPU of this box (ranks SHARE it: validation of the launch paths, not a scaling point): bench.py starting
 # its own children, and the driver's torch.distributed.run form (gloo process group for the barrier and the max only)
-python3 bench.py --gpus 2 --steps 20 --warmup 5 > "$OUT/${R}_bench_line_2ranks_selflaunch_one_gpu.json" 2>> "$RAW/bench.err"
+python3 bench.py --full --gpus 2 --steps 20 --warmup 5 > "$OUT/${R}_bench_line_2ranks_selflaunch_one_gpu.json" 2>> "$RAW/bench.err"
 # the launch path an 8-GPU lease takes (8 / 4 self-launched ranks, here sharing the one GPU), weak (the driver's contract) ...
 for spec in "8 c2" "4 c2" "8 c4"; do set -- $spec
-    python3 bench.py --gpus $1 --config $2 --steps 20 --warmup 5 > "$OUT/${R}_bench_line_${1}ranks_${2}_shared.json" 2>> "$RAW/bench.err"
+    python3 bench.py --full --gpus $1 --config $2 --steps 20 --warmup 5 > "$OUT/${R}_bench_line_${1}ranks_${2}_shared.json" 2>> "$RAW/bench.err"
 done
 # ... and strong: ONE 4096x4096 (and one 16384x4096) tensor cut over N ranks; ranks sharing the GPU, and rank 0's slice of an
 # M-way cut ALONE on the GPU (--emulate-world: what each of M separate GPUs runs; the line carries the projected M-GPU figure)
 for n in 1 2 4 8; do
-    python3 bench.py --gpus $n --scaling strong --steps 200 --warmup 20 --no-extras --no-cpu-baseline > "$OUT/${R}_strong_c2_${n}ranks_one_gpu.json" 2>> "$RAW/bench.err"
-    python3 bench.py --gpus $n --config c4_tensor --scaling strong --steps 100 --warmup 20 --no-extras --no-cpu-baseline > "$OUT/${R}_strong_c4tensor_${n}ranks_one_gpu.json" 2>> "$RAW/bench.err"
+    python3 bench.py --full --gpus $n --scaling strong --steps 200 --warmup 20 --no-extras --no-cpu-baseline > "$OUT/${R}_strong_c2_${n}ranks_one_gpu.json" 2>> "$RAW/bench.err"
+    python3 bench.py --full --gpus $n --config c4_tensor --scaling strong --steps 100 --warmup 20 --no-extras --no-cpu-baseline > "$OUT/${R}_strong_c4tensor_${n}ranks_one_gpu.json" 2>> "$RAW/bench.err"
 done
 for m in 2 4 8; do
-    python3 bench.py --gpus 1 --scaling strong --emulate-world $m --steps 400 --warmup 50 --no-extras --no-cpu-baseline > "$OUT/${R}_strong_c2_emulated_world_$m.json" 2>> "$RAW/bench.err"
-    python3 bench.py --gpus 1 --config c4_tensor --scaling strong --emulate-world $m --steps 200 --warmup 50 --no-extras --no-cpu-baseline > "$OUT/${R}_strong_c4tensor_emulated_world_$m.json" 2>> "$RAW/bench.err"
+    python3 bench.py --full --gpus 1 --scaling strong --emulate-world $m --steps 400 --warmup 50 --no-extras --no-cpu-baseline > "$OUT/${R}_strong_c2_emulated_world_$m.json" 2>> "$RAW/bench.err"
+    python3 bench.py --full --gpus 1 --config c4_tensor --scaling strong --emulate-world $m --steps 200 --warmup 50 --no-extras --no-cpu-baseline > "$OUT/${R}_strong_c4tensor_emulated_world_$m.json" 2>> "$RAW/bench.err"
 done
 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 \
-    bench.py --gpus 2 --steps 200 --warmup 10 2>> "$RAW/bench.err" | tail -1 > "$OUT/${R}_bench_line_2ranks_torchrun_one_gpu.json"
+    bench.py --full --gpus 2 --steps 200 --warmup 10 2>> "$RAW/bench.err" | tail -1 > "$OUT/${R}_bench_line_2ranks_torchrun_one_gpu.json"
 # 6. BASELINE config 5: RoBERTa-base step, module route and the reference's raw-operator route, and the few-bit kernels' own
 #    durations INSIDE that step (rocprofv3 kernel trace; fp32 and bf16, both routes)
 for dt in fp32 bf16; do
