@@ -52,6 +52,7 @@
 #include <cstdio>
 #include <type_traits>
 
+#include "fewbit_fft4.h"
 #include "fewbit_hip.h"
 #include "fewbit_philox.h"
 
@@ -64,345 +65,7 @@ FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(pri
 
 namespace dct {
 
-constexpr int C = 32;                       // complex columns of a tile = 64 features
-constexpr int kFeatures = 2 * C;
-// Both passes: a 32 KiB tile + tables per 256-thread workgroup, four workgroups per CU, each in its own phase (loading, transforming,
-// storing): pass A one row of transforms x 32 complex columns; pass B the two rows of a residue pair x 16 complex columns
-constexpr int kThreadsA = 256, kRowsA = 1;
-constexpr int kThreadsB = 256, CB = C / 2;  // pass B: 16 complex columns x the two rows of a residue pair
-constexpr int kServeLanes = 4;              // pass B: lanes that write one sampled row (CB / kServeLanes complex columns each)
-
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-// complex product with two multiplies and two fused multiply-adds (the build has -ffp-contract=off: fusion is spelled out where wanted)
-__device__ __forceinline__ f32x2 cmul(f32x2 a, f32x2 b) {
-    return f32x2{__builtin_fmaf(a.x, b.x, -(a.y * b.y)), __builtin_fmaf(a.x, b.y, a.y * b.x)};
-}
-__device__ __forceinline__ f32x2 mul_mi(f32x2 a) { return f32x2{a.y, -a.x}; }                                   // a * (-i)
-// e^{-2 pi i num / den}: den a power of two (num / den is exact in fp32), or 3 x / 5 x a power of two (the angle in double, then rounded;
-// `den` is a template constant at every call site: the branch folds)
-__device__ __forceinline__ f32x2 unit(int num, int den) {
-    if ((den & (den - 1)) != 0) {
-        double s, c;
-        sincospi(-2.0 * static_cast<double>(num) / static_cast<double>(den), &s, &c);
-        return f32x2{static_cast<float>(c), static_cast<float>(s)};
-    }
-    float s, c;
-    sincospif(-2.0f * static_cast<float>(num) / static_cast<float>(den), &s, &c);
-    return f32x2{c, s};
-}
-
-// ---- small transforms in registers, natural order in and out: x[q] <- sum_j x[j] e^{-2 pi i j q / R} ------------------------------
-constexpr float kR2 = 0.70710678118654752f;                   // sqrt(1/2)
-constexpr float kC8 = 0.92387953251128674f, kS8 = 0.38268343236508977f;      // cos, sin of pi / 8
-__device__ __forceinline__ void dft2(f32x2 &a, f32x2 &b) {
-    const f32x2 s = a + b, d = a - b;
-    a = s;
-    b = d;
-}
-__device__ __forceinline__ void dft4(f32x2 &a0, f32x2 &a1, f32x2 &a2, f32x2 &a3) {
-    const f32x2 t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3, t3 = mul_mi(a1 - a3);
-    a0 = t0 + t2;
-    a1 = t1 + t3;
-    a2 = t0 - t2;
-    a3 = t1 - t3;
-}
-constexpr float kH3 = 0.86602540378443865f;                   // sqrt(3) / 2
-template <int R> __device__ __forceinline__ void dft(f32x2 (&x)[R]) {
-    if constexpr (R == 2) {
-        dft2(x[0], x[1]);
-    } else if constexpr (R == 3) {
-        // W3 = -1/2 - i sqrt(3)/2:  y1, y2 = x0 - (x1 + x2) / 2  +-  (-i) (sqrt(3) / 2) (x1 - x2)
-        const f32x2 t = x[1] + x[2], d = mul_mi(x[1] - x[2]) * kH3, m = x[0] - t * 0.5f;
-        x[0] = x[0] + t;
-        x[1] = m + d;
-        x[2] = m - d;
-    } else if constexpr (R == 4) {
-        dft4(x[0], x[1], x[2], x[3]);
-    } else if constexpr (R == 5) {
-        // W5^j = cos(2 pi j / 5) - i sin(2 pi j / 5):  y1, y4 = m1 -+ i n1,  y2, y3 = m2 -+ i n2
-        constexpr float c1 = 0.30901699437494742f, c2 = -0.80901699437494742f, s1 = 0.95105651629515357f, s2 = 0.58778525229247313f;
-        const f32x2 a1 = x[1] + x[4], a2 = x[2] + x[3], b1 = x[1] - x[4], b2 = x[2] - x[3];
-        const f32x2 m1 = x[0] + a1 * c1 + a2 * c2, m2 = x[0] + a1 * c2 + a2 * c1;
-        const f32x2 n1 = mul_mi(b1 * s1 + b2 * s2), n2 = mul_mi(b1 * s2 - b2 * s1);
-        x[0] = x[0] + a1 + a2;
-        x[1] = m1 + n1;
-        x[4] = m1 - n1;
-        x[2] = m2 + n2;
-        x[3] = m2 - n2;
-    } else if constexpr (R == 8) {
-        // j = 2a + b, q = p + 4 q':  y[p + 4 q'] = sum_b W8^{bp} (-1)^{b q'} sum_a x[2a + b] W4^{ap}
-        dft4(x[0], x[2], x[4], x[6]);
-        dft4(x[1], x[3], x[5], x[7]);
-        const f32x2 u1 = x[3], u2 = x[5], u3 = x[7];
-        const f32x2 t0 = x[1];
-        const f32x2 t1 = f32x2{(u1.x + u1.y) * kR2, (u1.y - u1.x) * kR2};             // * W8^1 = sqrt(1/2) (1 - i)
-        const f32x2 t2 = mul_mi(u2);                                                   // * W8^2
-        const f32x2 t3 = f32x2{(u3.y - u3.x) * kR2, -(u3.x + u3.y) * kR2};            // * W8^3 = -sqrt(1/2) (1 + i)
-        const f32x2 e0 = x[0], e1 = x[2], e2 = x[4], e3 = x[6];
-        x[0] = e0 + t0; x[4] = e0 - t0;
-        x[1] = e1 + t1; x[5] = e1 - t1;
-        x[2] = e2 + t2; x[6] = e2 - t2;
-        x[3] = e3 + t3; x[7] = e3 - t3;
-    } else {
-        static_assert(R == 16, "radix 2, 3, 4, 5, 8 or 16");
-        // j = 4a + b, q = p + 4 q':  y[p + 4 q'] = sum_b W16^{bp} W4^{b q'} sum_a x[4a + b] W4^{ap}
-        dft4(x[0], x[4], x[8], x[12]);
-        dft4(x[1], x[5], x[9], x[13]);
-        dft4(x[2], x[6], x[10], x[14]);
-        dft4(x[3], x[7], x[11], x[15]);
-        // u[b][p] = x[4p + b]; twiddle W16^{bp}
-        x[5] = cmul(x[5], f32x2{kC8, -kS8});                                           // b = 1, p = 1: W16^1
-        x[9] = f32x2{(x[9].x + x[9].y) * kR2, (x[9].y - x[9].x) * kR2};               // b = 1, p = 2: W16^2 = W8^1
-        x[13] = cmul(x[13], f32x2{kS8, -kC8});                                         // b = 1, p = 3: W16^3
-        x[6] = f32x2{(x[6].x + x[6].y) * kR2, (x[6].y - x[6].x) * kR2};               // b = 2, p = 1: W16^2
-        x[10] = mul_mi(x[10]);                                                         // b = 2, p = 2: W16^4 = -i
-        x[14] = f32x2{(x[14].y - x[14].x) * kR2, -(x[14].x + x[14].y) * kR2};         // b = 2, p = 3: W16^6 = W8^3
-        x[7] = cmul(x[7], f32x2{kS8, -kC8});                                           // b = 3, p = 1: W16^3
-        x[11] = f32x2{(x[11].y - x[11].x) * kR2, -(x[11].x + x[11].y) * kR2};         // b = 3, p = 2: W16^6
-        x[15] = cmul(x[15], f32x2{-kC8, kS8});                                         // b = 3, p = 3: W16^9
-        // outer transforms over b for each p; result q' of group p is output p + 4 q' -- which is where dft4 leaves it when the
-        // group is (x[4p], x[4p+1], x[4p+2], x[4p+3]) and the outputs are then transposed: y[p + 4q'] = group_p[q']
-        dft4(x[0], x[1], x[2], x[3]);
-        dft4(x[4], x[5], x[6], x[7]);
-        dft4(x[8], x[9], x[10], x[11]);
-        dft4(x[12], x[13], x[14], x[15]);
-        f32x2 y[16];
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) y[p + 4 * q] = x[4 * p + q];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) x[q] = y[q];
-    }
-}
-
-// radix of the first stage of a block of length `len`: 256 = 16 x 16, 128 = 16 x 8, 64 = 8 x 8, 32 = 8 x 4, 16 = 16; a factor 3
-// (48 = 3 x 16, 96 = 3 x 8 x 4, 192 = 3 x 8 x 8) or 5 (80 = 5 x 16, 160 = 5 x 8 x 4) goes first
-__host__ __device__ constexpr int first_radix(int len) {
-    return len % 3 == 0 ? 3 : len % 5 == 0 ? 5 : len >= 128 ? 16 : len == 64 ? 8 : len == 32 ? 8 : len == 16 ? 16 : len == 8 ? 8 : len == 4 ? 4 : 2;
-}
-
-// position P (after the in-place DIF stages) -> frequency k.  Stage i with radix r_i on blocks of length L_i leaves digit q_i
-// (k = q_1 + r_1 q_2 + r_1 r_2 q_3 + ...) in sub-block q_i: P = sum q_i L_i / r_i.
-template <int LEN> __host__ __device__ __forceinline__ int pos_to_freq(int p) {
-    if constexpr (LEN <= 1) {
-        return 0;
-    } else {
-        constexpr int r = first_radix(LEN), s = LEN / r;
-        return p / s + r * pos_to_freq<s>(p % s);
-    }
-}
-template <int LEN> __host__ __device__ __forceinline__ int freq_to_pos(int k) {
-    if constexpr (LEN <= 1) {
-        return 0;
-    } else {
-        constexpr int r = first_radix(LEN), s = LEN / r;
-        return (k % r) * s + freq_to_pos<s>(k / r);
-    }
-}
-
-// One stage of the in-place transform of the tile [TR][L][C] along its middle axis: blocks of length LEN, radix R, twiddles
-// tw[m] = W_L^m.  Thread (c = tid % 32, slot = tid / 32 of SLOTS) takes the butterflies slot, slot + SLOTS, ... of column c of all
-// TR rows; a butterfly is R loads, the transform in registers, the twiddles W_LEN^{ss q} (none in the last stage) and R stores.
-template <int L, int LEN, int R, int TR, int SLOTS> __device__ __forceinline__ void stage(f32x2 *tile, const f32x2 *tw, int c, int slot) {
-    constexpr int S = LEN / R, kPerRow = L / R;
-#pragma unroll
-    for (int bid0 = 0; bid0 < TR * kPerRow; bid0 += SLOTS) {
-        const int bid = bid0 + slot;
-        if (TR * kPerRow % SLOTS != 0 && bid >= TR * kPerRow) break;
-        const int row = bid / kPerRow, b = bid % kPerRow, block = b / S, ss = b % S;
-        f32x2 *p = tile + (row * L + block * LEN + ss) * C + c;
-        f32x2 x[R];
-#pragma unroll
-        for (int j = 0; j < R; ++j) x[j] = p[j * S * C];
-        dft<R>(x);
-        if constexpr (S > 1) {
-#pragma unroll
-            for (int q = 1; q < R; ++q) x[q] = cmul(x[q], tw[(L / LEN) * ss * q]);
-        }
-#pragma unroll
-        for (int q = 0; q < R; ++q) p[q * S * C] = x[q];
-    }
-    __syncthreads();
-}
-
-template <int L, int TR, int SLOTS, int LEN = L> __device__ __forceinline__ void fft_tile(f32x2 *tile, const f32x2 *tw, int c, int slot) {
-    if constexpr (LEN > 1) {
-        constexpr int R = first_radix(LEN);
-        stage<L, LEN, R, TR, SLOTS>(tile, tw, c, slot);
-        fft_tile<L, TR, SLOTS, LEN / R>(tile, tw, c, slot);
-    }
-}
-
-template <int DT> struct In {             // 16-byte piece of a row: 8 features of a 16-bit dtype, 4 of fp32
-    static constexpr int kPieceFeatures = DT == FEWBIT_F32 ? 4 : 8;
-    static constexpr int kPiecesPerSegment = kFeatures / kPieceFeatures;
-};
-
-__device__ __forceinline__ float half_to_float(uint32_t h, int dt) {
-    if (dt == FEWBIT_BF16) return __builtin_bit_cast(float, h << 16);
-    return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(h)));
-}
-
-// the piece `piece` of the 64-feature segment of row `row` that starts at feature f0, raw (16 bytes: 8 features of a 16-bit dtype or
-// 4 of fp32).  FULL: the whole tile lies inside the matrix (a workgroup-uniform fact): one unguarded 16-byte load -- a load under a
-// lane-divergent guard makes hipcc wait for it on the spot, which serialised the tile's loads; otherwise zeros beyond `features`,
-// element by element.  The conversion to fp32 happens when the piece is written to LDS (unpack), after the latency has been used.
-template <int DT, bool FULL> __device__ __forceinline__ u32x4 load_piece(const void *x, size_t row, size_t ld, size_t f0, int piece, size_t features) {
-    constexpr int PF = In<DT>::kPieceFeatures;
-    const size_t f = f0 + static_cast<size_t>(piece) * PF;
-    if constexpr (DT == FEWBIT_F32) {
-        const uint32_t *p = static_cast<const uint32_t *>(x) + row * ld + f;
-        if (FULL || f + PF <= features) {
-            typedef u32x4 __attribute__((aligned(4))) u32x4u;
-            return *reinterpret_cast<const u32x4u *>(p);
-        }
-        u32x4 q;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) q[e] = f + e < features ? p[e] : 0u;
-        return q;
-    } else {
-        const uint16_t *p = static_cast<const uint16_t *>(x) + row * ld + f;
-        if (FULL || f + PF <= features) {
-            typedef u32x4 __attribute__((aligned(2))) u32x4u;
-            return *reinterpret_cast<const u32x4u *>(p);
-        }
-        u32x4 q = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) q[e >> 1] |= (f + e < features ? static_cast<uint32_t>(p[e]) : 0u) << (16 * (e & 1));
-        return q;
-    }
-}
-template <int DT> __device__ __forceinline__ void unpack_piece(u32x4 q, float (&v)[In<DT>::kPieceFeatures]) {
-    if constexpr (DT == FEWBIT_F32) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const uint32_t w = q[e];              // (a scalar first: __builtin_bit_cast applied to the element expression q[e] itself
-            v[e] = __builtin_bit_cast(float, w);  //  reads the vector's first element for every e -- observed with hipcc 7.2)
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[2 * e] = half_to_float(q[e] & 0xffffu, DT);
-            v[2 * e + 1] = half_to_float(q[e] >> 16, DT);
-        }
-    }
-}
-
-constexpr int kFine = 128;                  // W_D^e = fine[e % 128] * coarse[e / 128] for e < N (coarse: N / 128 entries, at most 2048)
-constexpr int coarse_entries(int n) { return n / kFine > 0 ? n / kFine : 1; }
-__device__ __forceinline__ f32x2 table_unit(const f32x2 *fine, const f32x2 *coarse, int e, bool has_coarse) {
-    return has_coarse ? cmul(fine[e % kFine], coarse[e / kFine]) : fine[e % kFine];
-}
-
-// ---- the sampled rows ------------------------------------------------------------------------------------------------------------
-// Where they come from.  RowsInMemory: the caller's int64 array.  RowsOfSeed: a FUNCTION of a 64-bit seed,
-//     rows = 2^k:      idx[j] = 16-bit half j % 8 of the 128 bits of Philox4x32-10(counter = (j / 8, 0, 0, 3), key = seed)  mod  rows
-//                      (half h = bits 16 (h % 2) .. 16 (h % 2) + 15 of word h / 2)
-//     rows = 3 x 2^k:  idx[j] = (word j % 4 of Philox4x32-10(counter = (j / 4, 0, 0, 3), key = seed)  x  rows)  >>  32
-// (uniform -- in the second case up to rows / 2^32 --, with replacement, like the reference's T.multinomial of equal weights): no array, no
-// launch that draws one, nothing to keep for backward but the seed -- and, with the seed read from device memory, a recorded launch draws
-// fresh rows on every replay (fewbit_sketch.hip, same scheme).
-constexpr uint32_t kRowsDomain = 3u;        // counter word 3 (0 and 2: the dense sketches)
-__host__ __device__ constexpr bool power_of_two(size_t n) { return (n & (n - 1)) == 0; }
-// rows = 2^k <= 2^16: eight 16-bit halves per Philox call; any other row count (3 x 2^k, 5 x 2^k, 2^17, 2^18): four 32-bit words, word x rows >> 32
-__host__ __device__ constexpr bool draws_halves(size_t n) { return power_of_two(n) && n <= 65536; }
-__host__ __device__ constexpr int per_draw(bool halves) { return halves ? 8 : 4; }      // row numbers per Philox call
-// row number h of one Philox call (HALVES: not yet reduced mod rows -- the caller masks)
-template <bool HALVES> __host__ __device__ __forceinline__ int drawn_row(const uint32_t (&w)[4], int h, uint32_t rows) {
-    if constexpr (HALVES) return static_cast<int>((w[h / 2] >> (16 * (h % 2))) & 0xffffu);
-    else return static_cast<int>((static_cast<uint64_t>(w[h]) * rows) >> 32);
-}
-struct RowsInMemory {
-    static constexpr bool kSeeded = false;
-    const int64_t *idx;
-};
-struct RowsOfSeed {
-    static constexpr bool kSeeded = true;
-    sketch::Key value;
-    const sketch::Key *device;              // != nullptr: the key is read from there when the kernel runs
-};
-
-// Pass B's workgroup (u, t) writes the samples k with k % N1 in {u, N1 - u}.  So that its 24 .. 96 siblings (one per half tile) need
-// not each test all of idx -- a third of pass B's time when they did (profiles/r06_dct_variants.txt: "noenlist") -- ONE workgroup, pass
-// A's (0, 0) before it turns to its own tile, sorts the samples by u into the workspace:
-//     sorted[offsets[u] .. offsets[u + 1])  =  the samples (k, j) with min(k % N1, N1 - k % N1) = u,   u = 0 .. N1 / 2
-// A counting sort in LDS: histogram, prefix, placement.  The order inside a class is whatever the atomics give; no result depends on it
-// (every sample writes its own row of the output).
-struct Sample { int k, j; };                // frequency, row of the output
-constexpr size_t kOffsetsBytes = 2048;      // (N1 / 2 + 2 ints, N1 <= 512, rounded up)
-
-template <int N1, int N, typename ROWS>
-__device__ __forceinline__ void sort_rows(ROWS rows, size_t proj, int *__restrict__ offsets, Sample *__restrict__ sorted, int *lds, int tid) {
-    constexpr int U = N1 / 2 + 1, kThreads = kThreadsA;
-    constexpr bool kPow2 = power_of_two(N), kHalves = draws_halves(N);
-    constexpr int kPerDraw = per_draw(kHalves);
-    int *hist = lds, *cursor = lds + U + 1;
-    sketch::Key key{0u, 0u};
-    if constexpr (ROWS::kSeeded) {
-        key = rows.value;
-        if (rows.device != nullptr) key = *rows.device;               // (one scalar load)
-    }
-    auto bucket = [](int k) -> int {
-        const int k1 = k % N1;
-        return k1 <= N1 / 2 ? k1 : N1 - k1;
-    };
-    // every (k, j) this thread looks after: of an array j = tid, tid + 256, ...; of a seed the numbers of the Philox calls tid, tid + 256, ...
-    auto for_each = [&](auto &&f) __attribute__((always_inline)) {
-        if constexpr (ROWS::kSeeded) {
-            for (size_t q = tid; kPerDraw * q < proj; q += kThreads) {
-                uint32_t w[4];
-                sketch::philox4x32(static_cast<uint32_t>(q), static_cast<uint32_t>(q >> 32), 0u, kRowsDomain, key, w);
-#pragma unroll
-                for (int h = 0; h < kPerDraw; ++h) {
-                    const size_t j = kPerDraw * q + h;
-                    const int drawn = drawn_row<kHalves>(w, h, N);
-                    if (j < proj) f(kHalves ? drawn & (N - 1) : drawn, j);
-                }
-            }
-        } else {
-            // (the low dword of an int64 in [0, N) is the number; whatever else the array holds is reduced to [0, N))
-            // eight unconditional requests (a clamped index) before the first is looked at: eight latencies overlap instead of following one another
-            const int *lo = reinterpret_cast<const int *>(rows.idx);
-            for (size_t j0 = tid; j0 < proj; j0 += 8 * kThreads) {
-                int word[8];
-#pragma unroll
-                for (int a = 0; a < 8; ++a) {
-                    const size_t j = j0 + static_cast<size_t>(a) * kThreads;
-                    word[a] = lo[2 * (j < proj ? j : proj - 1)];
-                }
-#pragma unroll
-                for (int a = 0; a < 8; ++a) {
-                    const size_t j = j0 + static_cast<size_t>(a) * kThreads;
-                    if (j < proj) f(kPow2 ? word[a] & (N - 1) : static_cast<int>(static_cast<unsigned>(word[a]) % static_cast<unsigned>(N)), j);
-                }
-            }
-        }
-    };
-    for (int b = tid; b <= U; b += kThreads) hist[b] = 0;
-    __syncthreads();
-    for_each([&](int k, size_t) { atomicAdd(&hist[bucket(k)], 1); });
-    __syncthreads();
-    for (int mine = tid; mine <= U; mine += kThreads) {                // offsets[b] = the classes before b (every lane reads the same word: a broadcast)
-        int run = 0;
-#pragma unroll 8
-        for (int b = 0; b < U; ++b) {
-            const int n = hist[b];
-            run += b < mine ? n : 0;
-        }
-        cursor[mine] = run;
-        offsets[mine] = run;
-    }
-    __syncthreads();
-    for_each([&](int k, size_t j) {
-        const int pos = atomicAdd(&cursor[bucket(k)], 1);
-        sorted[pos] = Sample{k, static_cast<int>(j)};
-    });
-    __syncthreads();                                                   // (the tile takes this LDS over)
-}
+// (tiles, small transforms, row loads, tables, the rows of a seed and their sort, split_rows: fewbit_fft4.h)
 
 // ---- pass A -----------------------------------------------------------------------------------------------------------------
 // grid (N2, column tiles): workgroup (b, t) transforms the rows n = N2 n1 + b of column tile t.  inter: [half tile][k1][n2][16] complex fp32.
@@ -602,37 +265,6 @@ __global__ __launch_bounds__(kThreadsB, (N2 > 128 ? 2 : 4)) void dct_pass_b_kern
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
-struct Split { int n1, n2; };
-// rows = N1 x N2.  2^8 .. 2^18: 16 <= N2 <= N1 <= 512, both powers of two (2^17 = 512 x 256 and 2^18 = 512 x 512: 128 KiB tiles, one
-// workgroup per CU).  3 x 2^8 .. 3 x 2^14 (768 .. 49152) and 5 x 2^8 .. 5 x 2^13 (1280 .. 40960): the odd factor goes to the second pass,
-// N2 = 48 / 96 / 192 or 80 / 160 (N1 stays a power of two: residues and digit maps of pass A, the k % N1 of pass B)
-inline bool split_rows(size_t rows, Split &s) {
-    if (rows < 256 || rows > 262144) return false;
-    const bool three = rows % 3 == 0, five = !three && rows % 5 == 0;
-    const size_t two = three ? rows / 3 : five ? rows / 5 : rows;
-    if (!power_of_two(two) || (three && (two < 256 || two > 16384)) || (five && (two < 256 || two > 8192))) return false;
-    int bits = 0;
-    while ((static_cast<size_t>(1) << bits) < two) ++bits;
-    if (!three && !five) {
-        s.n1 = 1 << ((bits + 1) / 2);
-        s.n2 = 1 << (bits / 2);
-        return true;
-    }
-    // 3 x 2^bits, bits = 8 .. 14:  16 x 48, 32 x 48, 32 x 96, 64 x 96, 128 x 96, 128 x 192, 256 x 192
-    // 5 x 2^bits, bits = 8 .. 13:  16 x 80, 32 x 80, 64 x 80, 64 x 160, 128 x 160, 256 x 160
-    static const int n1_of_3[7] = {16, 32, 32, 64, 128, 128, 256}, n1_of_5[6] = {16, 32, 64, 64, 128, 256};
-    s.n1 = three ? n1_of_3[bits - 8] : n1_of_5[bits - 8];
-    s.n2 = static_cast<int>(rows / static_cast<size_t>(s.n1));
-    return true;
-}
-inline size_t tiles_of(size_t features) { return (features + kFeatures - 1) / kFeatures; }
-inline size_t inter_bytes(size_t rows, size_t features) { return tiles_of(features) * rows * C * sizeof(f32x2); }
-// workspace: [the intermediate | offsets of the sorted samples (2 KiB) | the sorted samples, 8 bytes each]
-inline size_t workspace_bytes_of(size_t rows, size_t features, size_t proj) { return inter_bytes(rows, features) + kOffsetsBytes + ((proj * sizeof(Sample) + 15) & ~static_cast<size_t>(15)); }
-
-template <int L> constexpr size_t lds_bytes_a(int n) { return (kRowsA * L * C + L + kFine + coarse_entries(n)) * sizeof(f32x2); }
-template <int L> constexpr size_t lds_bytes_b(int n) { return (2 * L * CB + L + kFine + coarse_entries(n)) * sizeof(f32x2); }
-
 template <typename K> int opt_in(K kern, size_t lds, std::atomic<unsigned long long> &done) {
     if (lds <= 65536) return FEWBIT_OK;
     int dev = 0;

@@ -1,0 +1,417 @@
+// fewbit_dft.hip -- the sampled Fourier transform of the randomized linear layers (the reference's 'dft' estimator) on gfx950, the
+// kernels of the companion library libfewbit_hipx.so (include/fewbit_hipx.h):
+//
+//     out[0][j][c] + i out[1][j][c] = scale * (1 / sqrt(N)) * sum_n M[n][c] e^{-2 pi i n idx[j] / N}     M: rows x features (bf16 / fp16 / fp32)
+//
+// = torch.fft.fft(M, dim=0, norm='ortho')[idx] * scale, as two planes (real, imaginary) of proj x features.  What it replaces: the
+// layer's torch.fft formulation, which materialises the whole complex rows x features transform (for a 16-bit input after a cast to fp32)
+// and gathers the sampled rows afterwards -- 209 / 846 us for 16384 x 768 / 3072 bf16 at p = 3276 (profiles/r06_sketch_bench.json).
+//
+// The machine is the sampled DCT's (fewbit_dct.hip; shared code: fewbit_fft4.h): features (2c, 2c + 1) of a row are one complex number,
+// Z = DFT_N of that column is a four-step FFT (pass A along n1 with the twiddle W_N^{n2 k1}, pass B along n2), and the pass-B workgroup of
+// the residue pair (u, N1 - u) holds Z[k] and Z[N - k] of every sampled k of its two classes.  Two differences:
+//   pass A   loads row n = N2 n1 + b itself (no Makhoul reordering);
+//   pass B   splits the packed pair, X_2c[k] = (Z[k] + conj Z[N-k]) / 2 and X_2c+1[k] = (Z[k] - conj Z[N-k]) / 2i, and writes both parts
+//            times scale / sqrt(N) (no e^{-i pi k / 2N} twiddle, so no W_4N tables; no sqrt(2) at k = 0).
+// Exact by construction: at k = 0 and k = N / 2 the pair is one LDS entry read twice (imaginary parts 0), and a sampled pair k, N - k
+// reads the same two entries swapped (exact conjugates).  Same row counts, tiles, rows of a seed and workspace as the DCT.
+// Traffic: M once + 2 x rows x features x 4 B of intermediate + 2 planes of p rows.
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <type_traits>
+
+#include "fewbit_fft4.h"
+#include "fewbit_hipx.h"
+
+#define FEWBIT_HIDDEN __attribute__((visibility("hidden")))
+
+namespace fewbit_hip {
+namespace dft {
+
+using namespace dct;
+
+FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// ---- pass A: dct_pass_a_kernel (fewbit_dct.hip) line for line, except the row each n1 loads -------------------------------------
+// (a copy, not a shared body: the DCT's kernels stay bit for bit the machine code they were measured as; routing them through a
+// common inline function changed the instruction schedule of 44 of them)
+// grid (N2, column tiles): workgroup (b, t) transforms the rows n = N2 n1 + b of column tile t (of M itself).  inter: [half tile][k1][n2][16] complex fp32.
+template <int DT, int N1, int N2, typename ROWS>
+__global__ __launch_bounds__(kThreadsA, (N1 > 128 ? 2 : 4)) void dft_pass_a_kernel(const void *__restrict__ x, size_t features, size_t ld, f32x2 *__restrict__ inter, ROWS rows,
+                                                                  size_t proj, int *__restrict__ offsets, Sample *__restrict__ sorted) {
+    constexpr int N = N1 * N2, kCoarse = coarse_entries(N), kThreads = kThreadsA, kSlots = kThreads / C;
+    static_assert(kRowsA == 1, "one n2 per workgroup");
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    f32x2 *tile = reinterpret_cast<f32x2 *>(lds_raw);                 // [N1][C]
+    f32x2 *tw = tile + N1 * C;                                        // W_N1^m, m < N1
+    f32x2 *fine = tw + N1, *coarse = fine + kFine;                    // W_N^m (m < 128), W_N^{128 m}
+    const int tid = threadIdx.x, c = tid % C, slot = tid / C;
+    const int b = blockIdx.x;
+    const size_t t = blockIdx.y, f0 = t * kFeatures;
+    // one workgroup of the launch sorts the sampled rows for pass B first (~2 us of its own time; the launch takes 16)
+    if (blockIdx.x == 0 && blockIdx.y == 0) sort_rows<N1, N, ROWS>(rows, proj, offsets, sorted, reinterpret_cast<int *>(lds_raw), tid);
+
+    // ---- loads first (all in flight), tables while they travel, then registers -> LDS
+    constexpr int PF = In<DT>::kPieceFeatures, PPS = In<DT>::kPiecesPerSegment, kTotal = N1 * PPS, kPieces = (kTotal + kThreads - 1) / kThreads;
+    // (one body per case, FULL tile or edge tile, each with its own registers from the loads to the LDS writes: were the two
+    // cases to meet in one set of registers in between, the copies at the join would wait for the loads right behind their issue)
+    auto fill_tile = [&](auto full) __attribute__((always_inline)) {
+        u32x4 raw[kPieces];
+#pragma unroll
+        for (int i = 0; i < kPieces; ++i) {
+            const int pid = tid + kThreads * i, n1 = pid / PPS, piece = pid % PPS;
+            if (kTotal % kThreads != 0 && pid >= kTotal) break;
+            const size_t row = static_cast<size_t>(N2 * n1 + b);                 // (the DCT loads row 2n or 2 (N - 1 - n) + 1 here)
+            raw[i] = load_piece<DT, decltype(full)::value>(x, row, ld, f0, piece, features);
+        }
+        for (int m = tid; m < N1; m += kThreads) tw[m] = unit(m, N1);
+        for (int m = tid; m < kFine; m += kThreads) fine[m] = unit(m, N);
+        for (int m = tid; m < kCoarse; m += kThreads) coarse[m] = unit(m * kFine, N);
+#pragma unroll
+        for (int i = 0; i < kPieces; ++i) {
+            const int pid = tid + kThreads * i, n1 = pid / PPS, piece = pid % PPS;
+            if (kTotal % kThreads != 0 && pid >= kTotal) break;
+            float v[PF];
+            unpack_piece<DT>(raw[i], v);
+            f32x4 *dst = reinterpret_cast<f32x4 *>(tile + n1 * C + piece * (PF / 2));
+#pragma unroll
+            for (int e = 0; e < PF / 4; ++e) dst[e] = f32x4{v[4 * e], v[4 * e + 1], v[4 * e + 2], v[4 * e + 3]};
+        }
+    };
+    if (f0 + kFeatures <= features) fill_tile(std::true_type{});       // (workgroup-uniform)
+    else fill_tile(std::false_type{});
+    __syncthreads();
+
+    fft_tile<N1, kRowsA, kSlots>(tile, tw, c, slot);
+
+    // ---- twiddle + store: unit = two complex columns (16 B) of one position P; 16 consecutive lanes = the 256 contiguous bytes of one k1
+    constexpr int kUnitsTotal = N1 * (C / 2), kUnits = (kUnitsTotal + kThreads - 1) / kThreads;
+#pragma unroll
+    for (int i = 0; i < kUnits; ++i) {
+        const int uid = tid + kThreads * i, c2 = uid % (C / 2), p = uid / (C / 2);
+        if (kUnitsTotal % kThreads != 0 && uid >= kUnitsTotal) break;
+        const int k1 = pos_to_freq<N1>(p), e = b * k1;
+        const f32x2 w = table_unit(fine, coarse, e, kCoarse > 1);
+        const f32x4 z = *reinterpret_cast<const f32x4 *>(tile + p * C + 2 * c2);
+        const f32x2 a = cmul(f32x2{z[0], z[1]}, w), bb = cmul(f32x2{z[2], z[3]}, w);
+        // (the intermediate is kept per HALF tile of 16 complex columns -- what one pass-B workgroup reads: 128 contiguous bytes here)
+        f32x4 *dst = reinterpret_cast<f32x4 *>(inter + (((2 * t + c2 / (CB / 2)) * N1 + k1) * N2 + b) * CB + 2 * (c2 % (CB / 2)));
+        *dst = f32x4{a.x, a.y, bb.x, bb.y};
+    }
+}
+
+// 2 E values of one plane at element `at` (features fa .. fa + 2 E of a row): the DCT's vector stores
+template <int ODT, int E>
+__device__ __forceinline__ void store_values(void *out, size_t at, const float (&y)[2 * E], size_t fa, size_t features) {
+    if constexpr (ODT == FEWBIT_F32) {
+        float *o = static_cast<float *>(out) + at;
+        if (fa + 2 * E <= features) {
+            if constexpr (E == 1) {
+                *reinterpret_cast<f32x2 *>(o) = f32x2{y[0], y[1]};
+            } else {
+                typedef f32x4 __attribute__((aligned(4))) f32x4u;
+#pragma unroll
+                for (int e = 0; e < E; e += 2) *reinterpret_cast<f32x4u *>(o + 2 * e) = f32x4{y[2 * e], y[2 * e + 1], y[2 * e + 2], y[2 * e + 3]};
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 2 * E; ++e) if (fa + e < features) o[e] = y[e];
+        }
+    } else {
+        uint16_t *o = static_cast<uint16_t *>(out) + at;
+        uint16_t h[2 * E];
+#pragma unroll
+        for (int e = 0; e < 2 * E; ++e) {
+            if constexpr (ODT == FEWBIT_BF16) h[e] = __builtin_bit_cast(uint16_t, static_cast<__bf16>(y[e]));
+            else h[e] = __builtin_bit_cast(uint16_t, static_cast<_Float16>(y[e]));
+        }
+        if (fa + 2 * E <= features) {
+            typedef uint32_t __attribute__((aligned(2))) u32u;
+            typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+            typedef u32x2 __attribute__((aligned(2))) u32x2u;
+            typedef u32x4 __attribute__((aligned(2))) u32x4u;
+            auto pair = [&](int e) -> uint32_t { return static_cast<uint32_t>(h[2 * e]) | (static_cast<uint32_t>(h[2 * e + 1]) << 16); };
+            if constexpr (E == 1) *reinterpret_cast<u32u *>(o) = pair(0);
+            else if constexpr (E == 2) *reinterpret_cast<u32x2u *>(o) = u32x2{pair(0), pair(1)};
+            else *reinterpret_cast<u32x4u *>(o) = u32x4{pair(0), pair(1), pair(2), pair(3)};
+        } else {
+#pragma unroll
+            for (int e = 0; e < 2 * E; ++e) if (fa + e < features) o[e] = h[e];
+        }
+    }
+}
+
+// ---- pass B: the DCT's, with the Fourier epilogue -----------------------------------------------------------------------------
+// grid (N1 / 2 + 1, half tiles of 16 complex columns): residues k1 = u and (N1 - u) % N1; LDS tile [N2][2][16] (fewbit_dct.hip).
+// out: [2][proj][features] in ODT (real plane, imaginary plane); factor = scale / sqrt(N).
+template <int ODT, int N1, int N2>
+__global__ __launch_bounds__(kThreadsB, (N2 > 128 ? 2 : 4)) void dft_pass_b_kernel(const f32x2 *__restrict__ inter, const int *__restrict__ offsets, const Sample *__restrict__ sorted,
+                                                                  size_t proj, size_t features, float factor, void *__restrict__ out) {
+    constexpr int kThreads = kThreadsB, kSlots = kThreads / C;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    f32x2 *tile = reinterpret_cast<f32x2 *>(lds_raw);                 // [N2][2][CB]
+    f32x2 *tw = tile + N2 * 2 * CB;                                   // W_N2^m
+    const int tid = threadIdx.x;
+    const int u = blockIdx.x, k1a = u, k1b = (N1 - u) % N1;
+    const size_t t = blockIdx.y, f0 = t * (2 * CB);
+    constexpr int kLanes = kServeLanes, E = CB / kLanes, kSGroups = kThreads / kLanes;       // lanes per sample, complex columns per lane
+    const int lane = tid % kLanes, sgroup = tid / kLanes;
+
+    // this workgroup's samples first (vmcnt counts in order), unconditionally (a clamped index), as in the DCT
+    const int begin = offsets[u], count = offsets[u + 1] - begin;
+    constexpr int kPre = 2;
+    Sample pre[kPre];
+#pragma unroll
+    for (int i = 0; i < kPre; ++i) {
+        const size_t e = static_cast<size_t>(begin) + sgroup + i * kSGroups;
+        pre[i] = sorted[e < proj ? e : proj - 1];
+    }
+    constexpr int kPerRow = N2 * (CB / 2), kTotal = 2 * kPerRow, kPieces = (kTotal + kThreads - 1) / kThreads;     // 16-byte pieces (two complex)
+    f32x4 v[kPieces];
+#pragma unroll
+    for (int i = 0; i < kPieces; ++i) {
+        const int pid = tid + kThreads * i, r = pid / kPerRow, rest = pid % kPerRow;
+        if (kTotal % kThreads != 0 && pid >= kTotal) break;
+        const f32x2 *src = inter + (t * N1 + (r == 0 ? k1a : k1b)) * static_cast<size_t>(N2) * CB;
+        v[i] = reinterpret_cast<const f32x4 *>(src)[rest];
+    }
+    for (int m = tid; m < N2; m += kThreads) tw[m] = unit(m, N2);
+#pragma unroll
+    for (int i = 0; i < kPieces; ++i) {
+        const int pid = tid + kThreads * i, r = pid / kPerRow, rest = pid % kPerRow, n2 = rest / (CB / 2), c2 = rest % (CB / 2);
+        if (kTotal % kThreads != 0 && pid >= kTotal) break;
+        *reinterpret_cast<f32x4 *>(tile + (n2 * 2 + r) * CB + 2 * c2) = v[i];
+    }
+    __syncthreads();
+    fft_tile<N2, 1, kSlots>(tile, tw, tid % C, tid / C);               // (ends with a barrier)
+
+    const float half = 0.5f * factor;
+    const size_t plane = proj * features;
+    auto write_row = [&](int km, size_t j) __attribute__((always_inline)) {
+        const int k1 = km % N1, k2 = km / N1;
+        const int r = k1 == k1a ? 0 : 1;
+        const int k2m = k1 == 0 ? (N2 - k2) % N2 : N2 - 1 - k2;         // N - k = (N1 - k1) + N1 k2m
+        const f32x2 *pk = tile + (freq_to_pos<N2>(k2) * 2 + r) * CB + E * lane;
+        const f32x2 *pm = tile + (freq_to_pos<N2>(k2m) * 2 + (1 - r)) * CB + E * lane;
+        f32x2 zk[E], zm[E];
+        if constexpr (E >= 2) {
+#pragma unroll
+            for (int e = 0; e < E; e += 2) {
+                const f32x4 a4 = *reinterpret_cast<const f32x4 *>(pk + e), b4 = *reinterpret_cast<const f32x4 *>(pm + e);
+                zk[e] = f32x2{a4[0], a4[1]}; zk[e + 1] = f32x2{a4[2], a4[3]};
+                zm[e] = f32x2{b4[0], b4[1]}; zm[e + 1] = f32x2{b4[2], b4[3]};
+            }
+        } else {
+            zk[0] = pk[0]; zm[0] = pm[0];
+        }
+        // a = Z[k], b = Z[N - k]:  X_2c = (a + conj b) / 2,  X_2c+1 = (a - conj b) / 2i = ((a.y + b.y) + i (b.x - a.x)) / 2
+        float re[2 * E], im[2 * E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const f32x2 a = zk[e], b = zm[e];
+            re[2 * e] = (a.x + b.x) * half;
+            im[2 * e] = (a.y - b.y) * half;
+            re[2 * e + 1] = (a.y + b.y) * half;
+            im[2 * e + 1] = (b.x - a.x) * half;
+        }
+        const size_t fa = f0 + 2 * E * lane, at = j * features + fa;
+        store_values<ODT, E>(out, at, re, fa, features);
+        store_values<ODT, E>(out, plane + at, im, fa, features);
+    };
+#pragma unroll
+    for (int i = 0; i < kPre; ++i)
+        if (sgroup + i * kSGroups < count) write_row(pre[i].k, static_cast<size_t>(pre[i].j));
+    for (int e = sgroup + kPre * kSGroups; e < count; e += kSGroups) {
+        const Sample smp = sorted[static_cast<size_t>(begin) + e];
+        write_row(smp.k, static_cast<size_t>(smp.j));
+    }
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------
+template <int L> constexpr size_t lds_bytes_b_dft() { return (2 * L * CB + L) * sizeof(f32x2); }
+
+// the splits of split_rows (fewbit_fft4.h)
+#define FB_DFT_SPLITS(X)                                                                                                      \
+    X(16, 16) X(32, 16) X(32, 32) X(64, 32) X(64, 64) X(128, 64) X(128, 128) X(256, 128) X(256, 256) X(512, 256) X(512, 512) \
+    X(16, 48) X(32, 48) X(32, 96) X(64, 96) X(128, 96) X(128, 192) X(256, 192)                                                \
+    X(16, 80) X(32, 80) X(64, 80) X(64, 160) X(128, 160) X(256, 160)
+
+template <typename K> int reserve_lds(K kern, size_t lds) {
+    if (lds <= 65536) return FEWBIT_OK;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FEWBIT_ERR_LAUNCH, "sampled_dft: cannot reserve %zu bytes of LDS", lds);
+    }
+    return FEWBIT_OK;
+}
+
+// The LDS opt-in of EVERY kernel of dtype DT whose tile exceeds 64 KiB (pass A reading DT, pass B writing DT), once per device at the
+// first call that uses DT -- not per instantiation at its own first launch: after one eager call of a dtype, a hipGraph capture of any
+// other row count of that dtype makes no attribute call.
+template <int DT> int opt_in_dtype() {
+    static std::atomic<unsigned long long> done{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_relaxed) & bit) return FEWBIT_OK;
+    int rc = FEWBIT_OK;
+#define FB_DFT_OPT_IN(A, B)                                                                                               \
+    if (rc == FEWBIT_OK) rc = reserve_lds(dft_pass_a_kernel<DT, A, B, RowsInMemory>, lds_bytes_a<A>(A * B));             \
+    if (rc == FEWBIT_OK) rc = reserve_lds(dft_pass_a_kernel<DT, A, B, RowsOfSeed>, lds_bytes_a<A>(A * B));               \
+    if (rc == FEWBIT_OK) rc = reserve_lds(dft_pass_b_kernel<DT, A, B>, lds_bytes_b_dft<B>());
+    FB_DFT_SPLITS(FB_DFT_OPT_IN)
+#undef FB_DFT_OPT_IN
+    if (rc == FEWBIT_OK) done.fetch_or(bit, std::memory_order_relaxed);
+    return rc;
+}
+
+template <int DT, typename ROWS>
+int launch_a(Split sp, const void *m, size_t features, size_t ld, ROWS idx, size_t proj, f32x2 *inter, int *offsets, Sample *sorted, hipStream_t s) {
+    const unsigned tiles = static_cast<unsigned>(tiles_of(features));
+#define FB_DFT_CASE_A(A, B)                                                                                                          \
+    if (sp.n1 == A && sp.n2 == B) {                                                                                                  \
+        hipLaunchKernelGGL((dft_pass_a_kernel<DT, A, B, ROWS>), dim3(B, tiles), dim3(kThreadsA), lds_bytes_a<A>(A * B), s, m, features, ld, \
+                           inter, idx, proj, offsets, sorted);                                                                       \
+        return FEWBIT_OK;                                                                                                            \
+    }
+    FB_DFT_SPLITS(FB_DFT_CASE_A)
+#undef FB_DFT_CASE_A
+    return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dft: no kernel for %d x %d rows", sp.n1, sp.n2);
+}
+
+template <int ODT>
+int launch_b(Split sp, const f32x2 *inter, const int *offsets, const Sample *sorted, size_t proj, size_t features, float factor, void *out, hipStream_t s) {
+    const unsigned half_tiles = static_cast<unsigned>((features + 2 * CB - 1) / (2 * CB));
+#define FB_DFT_CASE_B(A, B)                                                                                                          \
+    if (sp.n1 == A && sp.n2 == B) {                                                                                                  \
+        hipLaunchKernelGGL((dft_pass_b_kernel<ODT, A, B>), dim3(A / 2 + 1, half_tiles), dim3(kThreadsB), lds_bytes_b_dft<B>(), s, inter, \
+                           offsets, sorted, proj, features, factor, out);                                                            \
+        return FEWBIT_OK;                                                                                                            \
+    }
+    FB_DFT_SPLITS(FB_DFT_CASE_B)
+#undef FB_DFT_CASE_B
+    return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dft: no kernel for %d x %d rows", sp.n1, sp.n2);
+}
+
+// Three translation units, one per dtype (-DFEWBIT_DFT_TU=0 / 1 / 2 = FEWBIT_F32 / F16 / BF16): pass A reading that dtype, pass B writing
+// it and its opt-in; the C entry points with unit 0.  Without the define everything is one unit.
+#ifndef FEWBIT_DFT_TU
+#define FEWBIT_DFT_TU -1
+#endif
+#define FB_DFT_UNIT(KEYWORD, DT)                                                                                                      \
+    KEYWORD template int opt_in_dtype<DT>();                                                                                         \
+    KEYWORD template int launch_a<DT, RowsInMemory>(Split, const void *, size_t, size_t, RowsInMemory, size_t, f32x2 *, int *, Sample *, hipStream_t); \
+    KEYWORD template int launch_a<DT, RowsOfSeed>(Split, const void *, size_t, size_t, RowsOfSeed, size_t, f32x2 *, int *, Sample *, hipStream_t); \
+    KEYWORD template int launch_b<DT>(Split, const f32x2 *, const int *, const Sample *, size_t, size_t, float, void *, hipStream_t);
+#if FEWBIT_DFT_TU >= 0
+FB_DFT_UNIT(, FEWBIT_DFT_TU)
+#endif
+#if FEWBIT_DFT_TU == 0
+FB_DFT_UNIT(extern, FEWBIT_F16)
+FB_DFT_UNIT(extern, FEWBIT_BF16)
+#endif
+#undef FB_DFT_UNIT
+
+#if FEWBIT_DFT_TU <= 0
+thread_local char g_last_error[256] = "";
+
+int fail(int code, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_last_error, sizeof g_last_error, fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+inline bool known_dtype(int dtype) { return dtype == FEWBIT_F32 || dtype == FEWBIT_F16 || dtype == FEWBIT_BF16; }
+
+inline int opt_in(int dtype) {
+    switch (dtype) {
+    case FEWBIT_F32: return opt_in_dtype<FEWBIT_F32>();
+    case FEWBIT_F16: return opt_in_dtype<FEWBIT_F16>();
+    default: return opt_in_dtype<FEWBIT_BF16>();
+    }
+}
+
+template <typename ROWS>
+int run(int dtype, const void *m, size_t rows, size_t features, size_t ld, ROWS idx, size_t proj, double scale, int out_dtype, void *out, void *workspace,
+        size_t workspace_bytes, void *stream) {
+    if (!known_dtype(dtype)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dft: unknown dtype %d", dtype);
+    if (out_dtype != FEWBIT_F32 && out_dtype != dtype) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dft: out_dtype %d is neither F32 nor the dtype of m", out_dtype);
+    if (proj == 0 || features == 0) return FEWBIT_OK;
+    Split sp;
+    if (!split_rows(rows, sp)) return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dft: rows = %zu is none of 2^k (256 .. 262144), 3 x 2^k (768 .. 49152), 5 x 2^k (1280 .. 40960)", rows);
+    bool null = m == nullptr || out == nullptr;
+    if constexpr (!ROWS::kSeeded) null = null || idx.idx == nullptr;
+    if (null) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dft: null pointer");
+    if (ld < features) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dft: leading dimension %zu < features %zu", ld, features);
+    const size_t need = workspace_bytes_of(rows, features, proj);
+    if (workspace == nullptr || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dft: a 16-byte aligned workspace of %zu bytes is needed (fewbit_hipx_sampled_dft_workspace), got %zu", need, workspace_bytes);
+    if (tiles_of(features) > 32767) return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dft: more than 32767 column tiles");
+    if (proj > 0x7fffffffull) return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dft: more than 2^31 - 1 samples");
+    if (const int rc = opt_in(dtype)) return rc;
+    if (out_dtype != dtype)
+        if (const int rc = opt_in(out_dtype)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    f32x2 *inter = static_cast<f32x2 *>(workspace);
+    int *offsets = reinterpret_cast<int *>(static_cast<uint8_t *>(workspace) + inter_bytes(rows, features));
+    Sample *sorted = reinterpret_cast<Sample *>(reinterpret_cast<uint8_t *>(offsets) + kOffsetsBytes);
+    int rc;
+    switch (dtype) {
+    case FEWBIT_F32: rc = launch_a<FEWBIT_F32, ROWS>(sp, m, features, ld, idx, proj, inter, offsets, sorted, s); break;
+    case FEWBIT_F16: rc = launch_a<FEWBIT_F16, ROWS>(sp, m, features, ld, idx, proj, inter, offsets, sorted, s); break;
+    default: rc = launch_a<FEWBIT_BF16, ROWS>(sp, m, features, ld, idx, proj, inter, offsets, sorted, s); break;
+    }
+    if (rc != FEWBIT_OK) return rc;
+    const float factor = static_cast<float>(scale / std::sqrt(static_cast<double>(rows)));
+    switch (out_dtype) {
+    case FEWBIT_F32: rc = launch_b<FEWBIT_F32>(sp, inter, offsets, sorted, proj, features, factor, out, s); break;
+    case FEWBIT_F16: rc = launch_b<FEWBIT_F16>(sp, inter, offsets, sorted, proj, features, factor, out, s); break;
+    default: rc = launch_b<FEWBIT_BF16>(sp, inter, offsets, sorted, proj, features, factor, out, s); break;
+    }
+    if (rc != FEWBIT_OK) return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(FEWBIT_ERR_LAUNCH, "sampled_dft: %s", hipGetErrorString(e));
+    return FEWBIT_OK;
+}
+#endif  // FEWBIT_DFT_TU <= 0
+
+}  // namespace dft
+}  // namespace fewbit_hip
+
+#if FEWBIT_DFT_TU <= 0
+using namespace fewbit_hip;
+using namespace fewbit_hip::dft;
+
+extern "C" {
+
+int fewbit_hipx_abi_version(void) { return FEWBIT_HIPX_ABI_VERSION; }
+
+const char *fewbit_hipx_last_error(void) { return g_last_error; }
+
+size_t fewbit_hipx_sampled_dft_workspace(int dtype, size_t rows, size_t features, size_t proj) {
+    Split sp;
+    if (!known_dtype(dtype) || features == 0 || proj == 0 || !split_rows(rows, sp)) return 0;
+    return workspace_bytes_of(rows, features, proj);
+}
+
+int fewbit_hipx_sampled_dft(int dtype, const void *m, size_t rows, size_t features, size_t ld, const int64_t *idx, size_t proj, double scale, int out_dtype,
+                            void *out, void *workspace, size_t workspace_bytes, void *stream) {
+    return run(dtype, m, rows, features, ld, RowsInMemory{idx}, proj, scale, out_dtype, out, workspace, workspace_bytes, stream);
+}
+
+int fewbit_hipx_sampled_dft_seeded(int dtype, const void *m, size_t rows, size_t features, size_t ld, uint64_t seed, const uint64_t *seed_device, size_t proj,
+                                   double scale, int out_dtype, void *out, void *workspace, size_t workspace_bytes, void *stream) {
+    if ((reinterpret_cast<uintptr_t>(seed_device) & 7) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dft: the seed word in device memory must be 8-byte aligned");
+    const RowsOfSeed of{sketch::Key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)}, reinterpret_cast<const sketch::Key *>(seed_device)};
+    return run(dtype, m, rows, features, ld, of, proj, scale, out_dtype, out, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"
+#endif  // FEWBIT_DFT_TU <= 0

@@ -33,18 +33,21 @@ constructor / call signatures; the implementation is this repository's own:
   way into the matrix pipe (accumulation is fp32): a zero-mean relative perturbation of 2^-9 per element under an estimator
   whose own relative noise is ~ sqrt(rows / p).  ``use_native_sketch(False)`` (or ``FEWBIT_SKETCH_NATIVE=0``) selects
   the PyTorch formulation (randn / randint + matmul) instead, and so does an EXPLICIT ``sketch_dtype=torch.float32`` /
-  ``float64`` (a request for products of that precision); host tensors, float64 and 'dft' always take it;
+  ``float64`` (a request for products of that precision); host tensors and float64 always take it;
 * the native path can be captured into a hipGraph (``torch.cuda.graph``) after one eager warm-up call per device: while
   the stream is capturing, the seed is a device word that a recorded one-thread kernel re-derives on every replay
   (``_sketch_seed``), so a replayed training step draws a fresh ``S`` each time -- a seed recorded by value would repeat
   one matrix for ever.  (The reference reads the generator state back in forward and cannot be captured.)
 
-The sampled transforms: 'dct' on 2-D GPU tensors of 2^8 .. 2^18, 3 x 2^8 .. 3 x 2^14 or 5 x 2^8 .. 5 x 2^13 rows runs on this package's kernel pair (``fewbit_hip_sampled_dct``,
-``fewbit_amd/csrc/fewbit_dct.hip``: a four-step fp32 FFT in LDS that writes only the sampled rows -- the torch.fft formulation costs
-110-120 x the bytes of the result, profiles/r06_sketch_bench.json); other shapes and 'dft' are PyTorch-level code.  Inside the layer the
-sampled rows are, like ``S``, a function of the call's 64-bit seed that the kernel evaluates itself (``fewbit_hip_sampled_dct_seeded``;
-``cabi.sampled_rows(seed, rows, p)`` is the same function on the host): no ``randint`` launch, no saved RNG state, and the layer can be
-captured into a hipGraph.  ``use_native_sketch(False)`` selects torch.fft + randint.  SURVEY section 8f, row 4.
+The sampled transforms: 'dct' and 'dft' on 2-D GPU tensors of 2^8 .. 2^18, 3 x 2^8 .. 3 x 2^14 or 5 x 2^8 .. 5 x 2^13 rows run on this
+package's kernel pairs (``fewbit_hip_sampled_dct``, ``fewbit_amd/csrc/fewbit_dct.hip``; ``fewbit_hipx_sampled_dft`` of the companion
+library, ``fewbit_amd/csrc/fewbit_dft.hip``): one four-step fp32 FFT in LDS that writes only the sampled rows -- the torch.fft formulation
+costs 110-120 x the bytes of the result, profiles/r06_sketch_bench.json.  'dft' keeps its real and imaginary parts as two planes in the
+layer's dtype (two ``p x features`` views of one buffer; for a 16-bit layer half the bytes of torch.fft's complex64), and its weight
+gradient ``Gr^T Xr + Gi^T Xi`` is two accumulating GEMMs in the planes' dtype.  Other shapes are PyTorch-level code.  Inside the layer the
+sampled rows are, like ``S``, a function of the call's 64-bit seed that the kernel evaluates itself (``fewbit_hip_sampled_dct_seeded``,
+``fewbit_hipx_sampled_dft_seeded``; ``cabi.sampled_rows(seed, rows, p)`` is the same function on the host): no ``randint`` launch, no saved
+RNG state, and the layer can be captured into a hipGraph.  ``use_native_sketch(False)`` selects torch.fft + randint.  SURVEY section 8f, row 4.
 """
 import contextlib
 import os
@@ -105,8 +108,9 @@ _NATIVE_SKETCH = os.environ.get('FEWBIT_SKETCH_NATIVE', '1') not in ('0', 'no', 
 
 
 def use_native_sketch(on: Optional[bool] = None) -> bool:
-    """Query / set whether GPU tensors take the Philox-in-register MFMA kernel for 'gaussian' / 'rademacher' sketches
-    (default) or the PyTorch formulation.  Returns the previous setting."""
+    """Query / set whether GPU tensors take this package's kernels -- the Philox-in-register MFMA kernel for 'gaussian' /
+    'rademacher' sketches, the sampled-transform kernel pairs for 'dct' and 'dft' (default) -- or the PyTorch formulation
+    (randn / randint + matmul, torch.fft).  Returns the previous setting."""
     global _NATIVE_SKETCH
     prev = _NATIVE_SKETCH
     if on is not None:
@@ -208,6 +212,15 @@ def _native_dct(mat: torch.Tensor, p: int, seed, scale: float) -> torch.Tensor:
     return cabi.sampled_dct_seeded(mat, p, seed, scale)
 
 
+def _native_dft(mat: torch.Tensor, p: int, seed, scale: float, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``scale * torch.fft.fft(mat, dim=0, norm='ortho')[rows(seed)]`` on this package's kernel pair, as a ``(2, p, features)`` tensor of
+    ``out_dtype`` (default: the dtype of ``mat``): ``[0]`` the real part, ``[1]`` the imaginary part"""
+    from . import cabi_x
+    if mat.stride(1) != 1 or mat.stride(0) < mat.shape[1]:
+        mat = mat.contiguous()
+    return cabi_x.sampled_dft_seeded(mat, p, seed, scale, out_dtype)
+
+
 _INJECTED: Optional[torch.Tensor] = None
 
 
@@ -261,18 +274,43 @@ def _dct_rows_supported(rows: int) -> bool:
     return 256 <= two <= (16384 if three else 8192 if five else 262144) and two & (two - 1) == 0
 
 
+_DFT_ROWS = {}
+
+
+def _native_dft_applies(mat: torch.Tensor) -> bool:
+    """The gfx950 sampled-DFT kernel pair (fewbit_amd/csrc/fewbit_dft.hip) takes 2-D fp32 / fp16 / bf16 GPU tensors of the row counts the
+    library has a kernel for (those of the DCT pair), as it says itself: ``sampled_dft_workspace_bytes(rows, 1, 1) != 0``, asked once per
+    row count; everything else keeps the torch.fft formulation."""
+    if not (_NATIVE_SKETCH and mat.device.type == 'cuda' and mat.dim() == 2 and mat.dtype in (torch.float32, torch.float16, torch.bfloat16)
+            and mat.shape[1] > 0):
+        return False
+    rows = mat.shape[0]
+    ok = _DFT_ROWS.get(rows)
+    if ok is None:
+        from . import cabi_x
+        ok = _DFT_ROWS[rows] = cabi_x.sampled_dft_workspace_bytes(rows, 1, 1, torch.float32) != 0
+    return ok
+
+
 def sampled_transform_path(kind: str, mat: torch.Tensor) -> str:
     """Which code computes the sampled transform ``kind`` ('dct' / 'dft') of ``mat`` (what bench.py prints beside its time)."""
     if kind == 'dct' and _native_dct_applies(mat):
         return 'gfx950 kernel pair fewbit_hip_sampled_dct (four-step fp32 FFT in LDS, only the sampled rows are written; in the layer: rows of a seed)'
+    if kind == 'dft' and _native_dft_applies(mat):
+        return ('gfx950 kernel pair fewbit_hipx_sampled_dft (four-step fp32 FFT in LDS, only the sampled rows are written, real and imaginary '
+                'planes; in the layer: rows of a seed)')
     return 'torch.fft (rocFFT on the GPU): full transform along dim 0 in fp32, then the gather of the sampled rows'
 
 
 def sampled_transform(kind: str, mat: torch.Tensor, p: int, gen: torch.Generator, seed: int = 1234, scale: float = 1.0) -> torch.Tensor:
     """One estimator product of the layer, ``scale * transform(mat)[p sampled rows]``, on the path ``linear_grp`` takes for this
-    ``kind`` and ``mat`` (what bench.py and tools/ time): the kernel pair with rows of ``seed``, or torch.fft + randint from ``gen``."""
+    ``kind`` and ``mat`` (what bench.py and tools/ time): the kernel pair with rows of ``seed``, or torch.fft + randint from ``gen``.
+    'dft' returns a complex64 ``(p, features)`` tensor on either path (on the kernel pair: built from its fp32 planes)."""
     if kind == 'dct' and _native_dct_applies(mat):
         return _native_dct(mat, p, seed, scale)
+    if kind == 'dft' and _native_dft_applies(mat):
+        planes = _native_dft(mat, p, seed, scale, torch.float32)
+        return torch.complex(planes[0], planes[1])
     return _sketch(kind, mat, p, gen, scale=scale)
 
 
@@ -325,6 +363,15 @@ class _LinearGRP(torch.autograd.Function):
             ctx.p, ctx.kind = p, kind
             ctx.has_bias = bias is not None
             return F.linear(input, weight, bias)
+        if kind == 'dft' and _native_dft_applies(flat):
+            # the same on the Fourier pair: kept are the real and imaginary planes in the layer's dtype (two p x features views of one buffer)
+            ctx.native_seed = _sketch_seed(generator, flat.device)
+            ctx.low = None
+            planes = _native_dft(flat.detach(), p, ctx.native_seed, rows / p)
+            ctx.save_for_backward(planes[0], planes[1], weight)
+            ctx.p, ctx.kind = p, kind
+            ctx.has_bias = bias is not None
+            return F.linear(input, weight, bias)
         token, gen = _capture_rng(generator, input.device)
         scale = 1.0 / p if kind in ('gaussian', 'rademacher') else rows / p
         draw_dtype = sketch_dtype or flat.dtype
@@ -336,7 +383,8 @@ class _LinearGRP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        sketch, weight = ctx.saved_tensors
+        saved = ctx.saved_tensors                       # (sketch, weight); 'dft' on the kernel pair: (real plane, imaginary plane, weight)
+        sketch, weight = saved[0], saved[-1]
         grad_input = grad_weight = grad_bias = None
         if ctx.needs_input_grad[0]:
             grad_input = grad_output @ weight
@@ -347,11 +395,17 @@ class _LinearGRP(torch.autograd.Function):
             g2 = flat if flat.dtype in (torch.float32, torch.float16, torch.bfloat16) else flat.float()
             if ctx.low is not None:
                 g2 = g2.to(ctx.low)
-            if ctx.kind == 'dct':
-                proj = _native_dct(g2, ctx.p, ctx.native_seed, 1.0)
+            if ctx.kind == 'dft':
+                # Re((F G)^H (F X)) = Gr^T Xr + Gi^T Xi: two accumulating GEMMs in the dtype of the planes
+                xr, xi = saved[0], saved[1]
+                g = _native_dft(g2, ctx.p, ctx.native_seed, 1.0).to(xr.dtype)
+                grad_weight = torch.addmm(g[0].T @ xr, g[1].T, xi).to(weight.dtype)
             else:
-                proj = _native_sketch(ctx.kind, g2, ctx.p, ctx.native_seed, 1.0)
-            grad_weight = (proj.to(sketch.dtype).T @ sketch).to(weight.dtype)
+                if ctx.kind == 'dct':
+                    proj = _native_dct(g2, ctx.p, ctx.native_seed, 1.0)
+                else:
+                    proj = _native_sketch(ctx.kind, g2, ctx.p, ctx.native_seed, 1.0)
+                grad_weight = (proj.to(sketch.dtype).T @ sketch).to(weight.dtype)
         elif ctx.needs_input_grad[1]:
             proj = _sketch(ctx.kind, flat, ctx.p, _replay_rng(ctx.token), ctx.sketch_dtype, ctx.draw_dtype)
             if proj.is_complex():                                               # Re((F G)^H (F X))
