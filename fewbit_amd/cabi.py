@@ -6,7 +6,7 @@ every call raises (the product never computes this path on the CPU).
 """
 import ctypes
 from pathlib import Path
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -178,6 +178,37 @@ def _same_device(first: torch.Tensor, *others: torch.Tensor):
     for t in others:
         if t.device != first.device:
             raise FewbitHipError(f'tensors live on different devices ({first.device} and {t.device})')
+
+
+def _matrix(m: torch.Tensor) -> Tuple[int, int, int]:
+    """(rows, features, leading dimension) of a rows x features matrix on the GPU: 2-D, unit stride along the features, a dtype of DTYPES"""
+    if m.device.type != 'cuda':
+        raise FewbitHipError(f'm must live on the GPU (got {m.device})')
+    if m.dim() != 2 or (m.shape[1] > 1 and m.stride(1) != 1):
+        raise FewbitHipError('m must be 2-D with unit stride along its last dimension')
+    if m.dtype not in DTYPES:
+        raise FewbitHipError(f'unsupported dtype {m.dtype}')
+    rows, features = m.shape
+    return rows, features, m.stride(0) if rows > 1 else features
+
+
+def _buffers(m: torch.Tensor, others, out: Optional[torch.Tensor], shape, dtype: torch.dtype, what: str,
+             workspace: Optional[torch.Tensor], need: int):
+    """-> (out, workspace) on the device of ``m`` (current): ``out`` allocated, or checked to be a contiguous ``shape`` tensor of ``dtype``
+    (``what`` names it); ``workspace`` allocated when ``need`` bytes are needed and it is missing or smaller"""
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=m.device)
+    elif out.shape != shape or out.dtype != dtype or not out.is_contiguous():
+        raise FewbitHipError(f'out must be a contiguous {what}')
+    if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
+        workspace = torch.empty(need, dtype=torch.uint8, device=m.device)
+    _same_device(m, out, *others, *(() if workspace is None else (workspace, )))
+    return out, workspace
+
+
+def _span(workspace: Optional[torch.Tensor]) -> Tuple[int, int]:
+    """(pointer, bytes) of a workspace, (0, 0) without one"""
+    return (0, 0) if workspace is None else (workspace.data_ptr(), workspace.numel() * workspace.element_size())
 
 
 def bitwidth(nlevels: int) -> int:
@@ -389,25 +420,11 @@ def sketch(dist: str, m: torch.Tensor, proj: int, seed, scale: float = 1.0, out:
     workspace as MFMA fragments and read back).  ``m``: 2-D, rows x features, unit stride along the features (any row stride).
     ``workspace``: ``sketch_workspace_bytes(...)`` bytes of scratch, allocated here when not given.  ``seed``: an int, or a
     one-element int64 tensor on the device of ``m`` whose value is read when the kernel runs (``next_sketch_seed``)."""
-    if m.device.type != 'cuda':
-        raise FewbitHipError(f'm must live on the GPU (got {m.device})')
-    if m.dim() != 2 or (m.shape[1] > 1 and m.stride(1) != 1):
-        raise FewbitHipError('m must be 2-D with unit stride along its last dimension')
-    if m.dtype not in DTYPES:
-        raise FewbitHipError(f'unsupported dtype {m.dtype}')
-    rows, features = m.shape
-    ld = m.stride(0) if rows > 1 else features
+    rows, features, ld = _matrix(m)
     with _on(m.device):
-        if out is None:
-            out = torch.empty((proj, features), dtype=m.dtype, device=m.device)
-        elif out.shape != (proj, features) or out.dtype != m.dtype or not out.is_contiguous():
-            raise FewbitHipError('out must be a contiguous proj x features tensor of the dtype of m')
         need = sketch_workspace_bytes(dist, rows, features, proj, m.dtype)
-        if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
-            workspace = torch.empty(need, dtype=torch.uint8, device=m.device)
-        _same_device(m, out, *(() if workspace is None else (workspace, )))
-        tail = (scale, out.data_ptr(), 0 if workspace is None else workspace.data_ptr(),
-                0 if workspace is None else workspace.numel() * workspace.element_size(), _stream(stream, m.device))
+        out, workspace = _buffers(m, (), out, (proj, features), m.dtype, 'proj x features tensor of the dtype of m', workspace, need)
+        tail = (scale, out.data_ptr(), *_span(workspace), _stream(stream, m.device))
         if isinstance(seed, torch.Tensor):
             _seed_word(seed, 'seed')
             _same_device(m, seed)
@@ -490,42 +507,41 @@ def tune_sketch_materialise(materialise: int) -> None:
 
 
 # ---- sampled cosine transform (fewbit_amd/csrc/fewbit_dct.hip): out = scale * dct(m, dim=0, norm='ortho')[idx] -------------------
+# the row counts of the sampled transforms (fewbit_fft4.h: split_rows); 'dft' (cabi_x) has the same
+SAMPLED_ROWS = '2^k in [256, 262144], 3 x 2^k in [768, 49152] or 5 x 2^k in [1280, 40960]'
+
+
 def sampled_dct_workspace_bytes(rows: int, features: int, proj: int, dtype: torch.dtype = torch.bfloat16) -> int:
-    """bytes of scratch a ``sampled_dct`` call needs; 0 = this shape has no kernel (rows none of 2^k in [256, 262144], 3 x 2^k in [768, 49152], 5 x 2^k in [1280, 40960])"""
+    """bytes of scratch a ``sampled_dct`` call needs; 0 = this shape has no kernel (rows not of SAMPLED_ROWS)"""
     if dtype not in DTYPES:
         return 0
     return lib().fewbit_hip_sampled_dct_workspace(DTYPES[dtype], rows, features, proj)
 
 
-def _sampled_dct_call(m: torch.Tensor, proj: int, out: Optional[torch.Tensor], workspace: Optional[torch.Tensor], others, launch) -> torch.Tensor:
-    if m.device.type != 'cuda':
-        raise FewbitHipError(f'm must live on the GPU (got {m.device})')
-    if m.dim() != 2 or (m.shape[1] > 1 and m.stride(1) != 1):
-        raise FewbitHipError('m must be 2-D with unit stride along its last dimension')
-    if m.dtype not in DTYPES:
-        raise FewbitHipError(f'unsupported dtype {m.dtype}')
-    rows, features = m.shape
-    ld = m.stride(0) if rows > 1 else features
-    need = sampled_dct_workspace_bytes(rows, features, proj, m.dtype)
+def _sampled_call(name: str, workspace_bytes, check, m: torch.Tensor, proj: int, planes: tuple, out_dtype: torch.dtype, what: str,
+                  out: Optional[torch.Tensor], workspace: Optional[torch.Tensor], others, launch) -> torch.Tensor:
+    """A call of a sampled-transform kernel pair (``sampled_dct*`` here, ``cabi_x.sampled_dft*``): ``m`` checked, a row count without a
+    kernel refused by name, ``out`` (``planes + (proj, features)`` of ``out_dtype``) and the workspace allocated or checked, then
+    ``check(launch(dtype, m, rows, features, ld, out, workspace, workspace bytes))``."""
+    rows, features, ld = _matrix(m)
+    need = workspace_bytes(rows, features, proj, m.dtype)
     if need == 0 and proj and features:
-        raise FewbitHipError(f'sampled_dct: no kernel for {rows} rows (2^k in [256, 262144], 3 x 2^k in [768, 49152] or 5 x 2^k in [1280, 40960] is needed)')
+        raise FewbitHipError(f'{name}: no kernel for {rows} rows ({SAMPLED_ROWS} is needed)')
     with _on(m.device):
-        if out is None:
-            out = torch.empty((proj, features), dtype=m.dtype, device=m.device)
-        elif out.shape != (proj, features) or out.dtype != m.dtype or not out.is_contiguous():
-            raise FewbitHipError('out must be a contiguous proj x features tensor of the dtype of m')
-        if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
-            workspace = torch.empty(need, dtype=torch.uint8, device=m.device)
-        _same_device(m, out, *others, *(() if workspace is None else (workspace, )))
-        _check(launch(DTYPES[m.dtype], m.data_ptr(), rows, features, ld, out.data_ptr(), 0 if workspace is None else workspace.data_ptr(),
-                      0 if workspace is None else workspace.numel() * workspace.element_size()))
+        out, workspace = _buffers(m, others, out, (*planes, proj, features), out_dtype, what, workspace, need)
+        check(launch(DTYPES[m.dtype], m.data_ptr(), rows, features, ld, out.data_ptr(), *_span(workspace)))
     return out
+
+
+def _sampled_dct_call(m: torch.Tensor, proj: int, out: Optional[torch.Tensor], workspace: Optional[torch.Tensor], others, launch) -> torch.Tensor:
+    return _sampled_call('sampled_dct', sampled_dct_workspace_bytes, _check, m, proj, (), m.dtype, 'proj x features tensor of the dtype of m', out,
+                         workspace, others, launch)
 
 
 def sampled_dct(m: torch.Tensor, idx: torch.Tensor, scale: float = 1.0, out: Optional[torch.Tensor] = None,
                 workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
     """``scale * dct(m, dim=0, norm='ortho')[idx]`` (DCT-II along the rows, orthonormal; the reference's 'dct' sketch) for a 2-D
-    ``m`` (rows x features, unit stride along the features) whose row count is 2^k in [256, 262144], 3 x 2^k in [768, 49152] or 5 x 2^k in [1280, 40960]; ``idx``: int64 row
+    ``m`` (rows x features, unit stride along the features) whose row count is one of SAMPLED_ROWS; ``idx``: int64 row
     numbers on the device of ``m``.  fp32 arithmetic, result in the dtype of ``m``."""
     if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != m.device or not idx.is_contiguous():
         raise FewbitHipError('idx must be a contiguous 1-D int64 tensor on the device of m')

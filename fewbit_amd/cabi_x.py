@@ -9,7 +9,7 @@ from typing import Optional
 
 import torch
 
-from .cabi import DTYPES, FewbitHipError, _on, _same_device, _seed_word, _stream
+from .cabi import DTYPES, FewbitHipError, _sampled_call, _seed_word, _stream
 
 __all__ = ['LIB_PATH', 'ABI_VERSION', 'SYMBOLS', 'lib', 'sampled_dft', 'sampled_dft_seeded', 'sampled_dft_workspace_bytes']
 
@@ -56,7 +56,7 @@ def _check(rc: int):
 # ---- sampled Fourier transform (fewbit_amd/csrc/fewbit_dft.hip): out = scale * fft(m, dim=0, norm='ortho')[idx] as two planes -----
 def sampled_dft_workspace_bytes(rows: int, features: int, proj: int, dtype: torch.dtype = torch.bfloat16) -> int:
     """bytes of scratch a ``sampled_dft`` call needs (the formula of ``cabi.sampled_dct_workspace_bytes``); 0 = this shape has no kernel
-    (rows none of 2^k in [256, 262144], 3 x 2^k in [768, 49152], 5 x 2^k in [1280, 40960], or a dtype other than fp32 / fp16 / bf16)"""
+    (rows not of ``cabi.SAMPLED_ROWS``, or a dtype other than fp32 / fp16 / bf16)"""
     if dtype not in DTYPES:
         return 0
     return lib().fewbit_hipx_sampled_dft_workspace(DTYPES[dtype], rows, features, proj)
@@ -64,43 +64,23 @@ def sampled_dft_workspace_bytes(rows: int, features: int, proj: int, dtype: torc
 
 def _sampled_dft_call(m: torch.Tensor, proj: int, out_dtype: Optional[torch.dtype], out: Optional[torch.Tensor], workspace: Optional[torch.Tensor],
                       others, launch) -> torch.Tensor:
-    if m.device.type != 'cuda':
-        raise FewbitHipError(f'm must live on the GPU (got {m.device})')
-    if m.dim() != 2 or (m.shape[1] > 1 and m.stride(1) != 1):
-        raise FewbitHipError('m must be 2-D with unit stride along its last dimension')
-    if m.dtype not in DTYPES:
-        raise FewbitHipError(f'unsupported dtype {m.dtype}')
     out_dtype = m.dtype if out_dtype is None else out_dtype
     if out_dtype not in (torch.float32, m.dtype):
         raise FewbitHipError(f'out_dtype must be torch.float32 or the dtype of m (got {out_dtype})')
-    rows, features = m.shape
-    ld = m.stride(0) if rows > 1 else features
-    need = sampled_dft_workspace_bytes(rows, features, proj, m.dtype)
-    if need == 0 and proj and features:
-        raise FewbitHipError(f'sampled_dft: no kernel for {rows} rows (2^k in [256, 262144], 3 x 2^k in [768, 49152] or 5 x 2^k in [1280, 40960] is needed)')
-    with _on(m.device):
-        if out is None:
-            out = torch.empty((2, proj, features), dtype=out_dtype, device=m.device)
-        elif out.shape != (2, proj, features) or out.dtype != out_dtype or not out.is_contiguous():
-            raise FewbitHipError('out must be a contiguous 2 x proj x features tensor of out_dtype')
-        if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
-            workspace = torch.empty(need, dtype=torch.uint8, device=m.device)
-        _same_device(m, out, *others, *(() if workspace is None else (workspace, )))
-        _check(launch(DTYPES[m.dtype], m.data_ptr(), rows, features, ld, DTYPES[out_dtype], out.data_ptr(),
-                      0 if workspace is None else workspace.data_ptr(), 0 if workspace is None else workspace.numel() * workspace.element_size()))
-    return out
+    return _sampled_call('sampled_dft', sampled_dft_workspace_bytes, _check, m, proj, (2, ), out_dtype, '2 x proj x features tensor of out_dtype', out,
+                         workspace, others, lambda dt, *rest: launch(dt, DTYPES[out_dtype], *rest))
 
 
 def sampled_dft(m: torch.Tensor, idx: torch.Tensor, scale: float = 1.0, out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None,
                 workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
     """``scale * torch.fft.fft(m, dim=0, norm='ortho')[idx]`` for a 2-D ``m`` (rows x features, unit stride along the features) whose row
-    count is 2^k in [256, 262144], 3 x 2^k in [768, 49152] or 5 x 2^k in [1280, 40960]; ``idx``: int64 row numbers on the device of ``m``.
+    count is one of ``cabi.SAMPLED_ROWS``; ``idx``: int64 row numbers on the device of ``m``.
     fp32 arithmetic.  Returns a ``(2, proj, features)`` tensor of ``out_dtype`` (torch.float32 or the dtype of ``m``, the default):
     ``[0]`` the real part, ``[1]`` the imaginary part."""
     if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != m.device or not idx.is_contiguous():
         raise FewbitHipError('idx must be a contiguous 1-D int64 tensor on the device of m')
     proj = idx.numel()
-    return _sampled_dft_call(m, proj, out_dtype, out, workspace, (idx, ), lambda dt, mp, rows, features, ld, odt, op, wp, wb: lib().fewbit_hipx_sampled_dft(
+    return _sampled_dft_call(m, proj, out_dtype, out, workspace, (idx, ), lambda dt, odt, mp, rows, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dft(
         dt, mp, rows, features, ld, idx.data_ptr(), proj, scale, odt, op, wp, wb, _stream(stream, m.device)))
 
 
@@ -115,5 +95,5 @@ def sampled_dft_seeded(m: torch.Tensor, proj: int, seed, scale: float = 1.0, out
         value, word, others = 0, seed.data_ptr(), (seed, )
     else:
         value, word, others = seed & 0xffffffffffffffff, 0, ()
-    return _sampled_dft_call(m, proj, out_dtype, out, workspace, others, lambda dt, mp, rows, features, ld, odt, op, wp, wb: lib().fewbit_hipx_sampled_dft_seeded(
+    return _sampled_dft_call(m, proj, out_dtype, out, workspace, others, lambda dt, odt, mp, rows, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dft_seeded(
         dt, mp, rows, features, ld, value, word, proj, scale, odt, op, wp, wb, _stream(stream, m.device)))

@@ -19,7 +19,7 @@
 //          pass A   for every n2:  A[k1][n2] = W_N^{n2 k1} * sum_{n1} z[N2 n1 + n2] W_N1^{n1 k1}        (length-N1 DFTs over rows N2 apart)
 //          pass B   for every k1:  Z[k1 + N1 k2] = sum_{n2} A[k1][n2] W_N2^{n2 k2}                       (length-N2 DFTs, contiguous)
 //      Pass B never writes Z: the workgroup that owns the residues k1 and N1 - k1 holds Z[k] AND Z[N-k] for every k of those
-//      two classes in LDS, scans idx for the samples that fall into them and writes just those rows of the result.
+//      two classes in LDS, reads the samples of those classes (sorted by class in pass A) and writes just those rows of the result.
 //
 // ---- tiling ------------------------------------------------------------------------------------------------------------------
 //   tile        L points x 32 complex fp32 entries = 32 KiB of LDS at L = 128 (+ 3-7 KiB of tables): FOUR 256-thread workgroups per CU
@@ -47,7 +47,6 @@
 // Roofline class: HBM / Infinity Cache bandwidth (5 N log2 N flops per column: 0.9 GFLOP for 16384 x 768).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <type_traits>
@@ -65,7 +64,7 @@ FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(pri
 
 namespace dct {
 
-// (tiles, small transforms, row loads, tables, the rows of a seed and their sort, split_rows: fewbit_fft4.h)
+// (tiles, small transforms, row loads, tables, the rows of a seed and their sort, split_rows, the host side: fewbit_fft4.h)
 
 // ---- pass A -----------------------------------------------------------------------------------------------------------------
 // grid (N2, column tiles): workgroup (b, t) transforms the rows n = N2 n1 + b of column tile t.  inter: [half tile][k1][n2][16] complex fp32.
@@ -264,49 +263,16 @@ __global__ __launch_bounds__(kThreadsB, (N2 > 128 ? 2 : 4)) void dct_pass_b_kern
     }
 }
 
-// ---- host side --------------------------------------------------------------------------------------------------------------
-template <typename K> int opt_in(K kern, size_t lds, std::atomic<unsigned long long> &done) {
-    if (lds <= 65536) return FEWBIT_OK;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_relaxed) & bit)) {                 // (once per kernel and device)
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(FEWBIT_ERR_LAUNCH, "sampled_dct: cannot reserve %zu bytes of LDS", lds);
-        }
-        done.fetch_or(bit, std::memory_order_relaxed);
-    }
-    return FEWBIT_OK;
-}
-
-template <int DT, int N1, int N2, typename ROWS>
-int launch(const void *m, size_t features, size_t ld, ROWS idx, size_t proj, float scale, void *out, f32x2 *inter, int *offsets, Sample *sorted, hipStream_t s) {
-    static std::atomic<unsigned long long> done_a{0}, done_b{0};
-    constexpr size_t la = lds_bytes_a<N1>(N1 * N2), lb = lds_bytes_b<N2>(N1 * N2);
-    static_assert(la >= 2 * (N1 / 2 + 2) * sizeof(int) && (N1 / 2 + 2) * sizeof(int) <= kOffsetsBytes, "the sort's counters fit pass A's LDS and the offsets their slot");
-    if (const int rc = opt_in(dct_pass_a_kernel<DT, N1, N2, ROWS>, la, done_a)) return rc;
-    if (const int rc = opt_in(dct_pass_b_kernel<DT, N1, N2>, lb, done_b)) return rc;
-    const unsigned tiles = static_cast<unsigned>(tiles_of(features));
-    hipLaunchKernelGGL((dct_pass_a_kernel<DT, N1, N2, ROWS>), dim3(N2, tiles), dim3(kThreadsA), la, s, m, features, ld, inter, idx, proj, offsets, sorted);
-    const unsigned half_tiles = static_cast<unsigned>((features + 2 * CB - 1) / (2 * CB));
-    hipLaunchKernelGGL((dct_pass_b_kernel<DT, N1, N2>), dim3(N1 / 2 + 1, half_tiles), dim3(kThreadsB), lb, s, inter, offsets, sorted, proj, features, scale, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FEWBIT_ERR_LAUNCH, "sampled_dct: %s", hipGetErrorString(e));
-    return FEWBIT_OK;
-}
-
-template <int DT, typename ROWS>
-int launch_rows(Split sp, const void *m, size_t features, size_t ld, ROWS idx, size_t proj, float scale, void *out, f32x2 *inter, int *offsets, Sample *sorted, hipStream_t s) {
-#define FB_DCT_CASE(A, B) \
-    if (sp.n1 == A && sp.n2 == B) return launch<DT, A, B, ROWS>(m, features, ld, idx, proj, scale, out, inter, offsets, sorted, s);
-    FB_DCT_CASE(16, 16) FB_DCT_CASE(32, 16) FB_DCT_CASE(32, 32) FB_DCT_CASE(64, 32) FB_DCT_CASE(64, 64) FB_DCT_CASE(128, 64) FB_DCT_CASE(128, 128)
-    FB_DCT_CASE(256, 128) FB_DCT_CASE(256, 256) FB_DCT_CASE(512, 256) FB_DCT_CASE(512, 512)
-    FB_DCT_CASE(16, 48) FB_DCT_CASE(32, 48) FB_DCT_CASE(32, 96) FB_DCT_CASE(64, 96) FB_DCT_CASE(128, 96) FB_DCT_CASE(128, 192) FB_DCT_CASE(256, 192)
-    FB_DCT_CASE(16, 80) FB_DCT_CASE(32, 80) FB_DCT_CASE(64, 80) FB_DCT_CASE(64, 160) FB_DCT_CASE(128, 160) FB_DCT_CASE(256, 160)
-#undef FB_DCT_CASE
-    return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dct: no kernel for %d x %d rows", sp.n1, sp.n2);
-}
+// ---- host side (fewbit_fft4.h: the checks, the dispatch and the LDS opt-in of both pairs) ------------------------------------------
+struct Dct {
+    static constexpr const char *kName = "sampled_dct", *kWorkspace = "fewbit_hip_sampled_dct_workspace";
+    static constexpr int (*fail)(int, const char *, ...) = fewbit_hip::fail;
+    static constexpr bool kSeededLast = true;
+    template <int DT, int N1, int N2, typename ROWS> static constexpr auto pass_a() { return &dct_pass_a_kernel<DT, N1, N2, ROWS>; }
+    template <int DT, int N1, int N2> static constexpr auto pass_b() { return &dct_pass_b_kernel<DT, N1, N2>; }
+    template <int N1, int N2> static constexpr size_t lds_b() { return lds_bytes_b<N2>(N1 * N2); }
+    static float factor(double scale, size_t) { return static_cast<float>(scale); }
+};
 
 // The file is compiled as three translation units in parallel, one per dtype (-DFEWBIT_DCT_TU=0 / 1 / 2 = FEWBIT_F32 / F16 / BF16: 54
 // kernels each; the C entry points with unit 0), and linked into the one library -- 50 s instead of 2.5 min; without the define everything
@@ -314,43 +280,13 @@ int launch_rows(Split sp, const void *m, size_t features, size_t ld, ROWS idx, s
 #ifndef FEWBIT_DCT_TU
 #define FEWBIT_DCT_TU -1
 #endif
-#define FB_DCT_LAUNCH_ROWS(KEYWORD, DT, ROWS) \
-    KEYWORD template int launch_rows<DT, ROWS>(Split, const void *, size_t, size_t, ROWS, size_t, float, void *, f32x2 *, int *, Sample *, hipStream_t);
 #if FEWBIT_DCT_TU >= 0
-FB_DCT_LAUNCH_ROWS(, FEWBIT_DCT_TU, RowsInMemory) FB_DCT_LAUNCH_ROWS(, FEWBIT_DCT_TU, RowsOfSeed)
+FB_FFT4_UNIT(, Dct, FEWBIT_DCT_TU)
 #endif
 #if FEWBIT_DCT_TU == 0
-FB_DCT_LAUNCH_ROWS(extern, FEWBIT_F16, RowsInMemory) FB_DCT_LAUNCH_ROWS(extern, FEWBIT_F16, RowsOfSeed)
-FB_DCT_LAUNCH_ROWS(extern, FEWBIT_BF16, RowsInMemory) FB_DCT_LAUNCH_ROWS(extern, FEWBIT_BF16, RowsOfSeed)
+FB_FFT4_UNIT(extern, Dct, FEWBIT_F16)
+FB_FFT4_UNIT(extern, Dct, FEWBIT_BF16)
 #endif
-#undef FB_DCT_LAUNCH_ROWS
-
-#if FEWBIT_DCT_TU <= 0
-template <typename ROWS>
-int run(int dtype, const void *m, size_t rows, size_t features, size_t ld, ROWS idx, size_t proj, double scale, void *out, void *workspace,
-                       size_t workspace_bytes, void *stream) {
-    Split sp;
-    if (!split_rows(rows, sp)) return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dct: rows = %zu is none of 2^k (256 .. 262144), 3 x 2^k (768 .. 49152), 5 x 2^k (1280 .. 40960)", rows);
-    if (m == nullptr || out == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dct: null pointer");
-    if (ld < features) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dct: leading dimension %zu < features %zu", ld, features);
-    const size_t need = workspace_bytes_of(rows, features, proj);
-    if (workspace == nullptr || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dct: a 16-byte aligned workspace of %zu bytes is needed (fewbit_hip_sampled_dct_workspace), got %zu", need, workspace_bytes);
-    if (tiles_of(features) > 32767) return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dct: more than 32767 column tiles");
-    if (proj > 0x7fffffffull) return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dct: more than 2^31 - 1 samples");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    f32x2 *inter = static_cast<f32x2 *>(workspace);
-    int *offsets = reinterpret_cast<int *>(static_cast<uint8_t *>(workspace) + inter_bytes(rows, features));
-    Sample *sorted = reinterpret_cast<Sample *>(reinterpret_cast<uint8_t *>(offsets) + kOffsetsBytes);
-    const float fs = static_cast<float>(scale);
-    switch (dtype) {
-    case FEWBIT_F32: return launch_rows<FEWBIT_F32, ROWS>(sp, m, features, ld, idx, proj, fs, out, inter, offsets, sorted, s);
-    case FEWBIT_F16: return launch_rows<FEWBIT_F16, ROWS>(sp, m, features, ld, idx, proj, fs, out, inter, offsets, sorted, s);
-    default: return launch_rows<FEWBIT_BF16, ROWS>(sp, m, features, ld, idx, proj, fs, out, inter, offsets, sorted, s);
-    }
-}
-
-#endif  // FEWBIT_DCT_TU <= 0
 
 }  // namespace dct
 }  // namespace fewbit_hip
@@ -370,24 +306,17 @@ size_t fewbit_hip_sampled_dct_workspace(int dtype, size_t rows, size_t features,
 
 int fewbit_hip_sampled_dct(int dtype, const void *m, size_t rows, size_t features, size_t ld, const int64_t *idx, size_t proj, double scale, void *out,
                            void *workspace, size_t workspace_bytes, void *stream) {
-    if (dtype != FEWBIT_F32 && dtype != FEWBIT_F16 && dtype != FEWBIT_BF16) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dct: unknown dtype %d", dtype);
-    if (proj == 0 || features == 0) return FEWBIT_OK;
-    if (idx == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dct: null pointer");
-    return run(dtype, m, rows, features, ld, RowsInMemory{idx}, proj, scale, out, workspace, workspace_bytes, stream);
+    return run<Dct>(dtype, dtype, m, rows, features, ld, RowsInMemory{idx}, proj, scale, out, workspace, workspace_bytes, stream);
 }
 
 int fewbit_hip_sampled_dct_seeded(int dtype, const void *m, size_t rows, size_t features, size_t ld, uint64_t seed, const uint64_t *seed_device, size_t proj,
                                   double scale, void *out, void *workspace, size_t workspace_bytes, void *stream) {
-    if (dtype != FEWBIT_F32 && dtype != FEWBIT_F16 && dtype != FEWBIT_BF16) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dct: unknown dtype %d", dtype);
-    if (proj == 0 || features == 0) return FEWBIT_OK;
-    if ((reinterpret_cast<uintptr_t>(seed_device) & 7) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dct: the seed word in device memory must be 8-byte aligned");
-    const RowsOfSeed of{sketch::Key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)}, reinterpret_cast<const sketch::Key *>(seed_device)};
-    return run(dtype, m, rows, features, ld, of, proj, scale, out, workspace, workspace_bytes, stream);
+    return run<Dct>(dtype, dtype, m, rows, features, ld, rows_of_seed(seed, seed_device), proj, scale, out, workspace, workspace_bytes, stream);
 }
 
 int fewbit_hip_sampled_rows(uint64_t seed, size_t rows, size_t proj, int64_t *idx) {
     Split sp;
-    if (!split_rows(rows, sp)) return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_rows: rows = %zu is none of 2^k (256 .. 262144), 3 x 2^k (768 .. 49152), 5 x 2^k (1280 .. 40960)", rows);
+    if (!split_rows(rows, sp)) return refuse_rows<Dct>("sampled_rows", rows);
     if (proj > 0 && idx == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_rows: null pointer");
     const sketch::Key key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)};
     const bool pow2 = draws_halves(rows);

@@ -18,7 +18,6 @@
 // Traffic: M once + 2 x rows x features x 4 B of intermediate + 2 planes of p rows.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
@@ -232,91 +231,20 @@ __global__ __launch_bounds__(kThreadsB, (N2 > 128 ? 2 : 4)) void dft_pass_b_kern
     }
 }
 
-// ---- host side --------------------------------------------------------------------------------------------------------------
-template <int L> constexpr size_t lds_bytes_b_dft() { return (2 * L * CB + L) * sizeof(f32x2); }
+// ---- host side (fewbit_fft4.h: the checks, the dispatch and the LDS opt-in of both pairs) ------------------------------------------
+struct Dft {
+    static constexpr const char *kName = "sampled_dft", *kWorkspace = "fewbit_hipx_sampled_dft_workspace";
+    static constexpr int (*fail)(int, const char *, ...) = dft::fail;
+    static constexpr bool kSeededLast = false;
+    template <int DT, int N1, int N2, typename ROWS> static constexpr auto pass_a() { return &dft_pass_a_kernel<DT, N1, N2, ROWS>; }
+    template <int ODT, int N1, int N2> static constexpr auto pass_b() { return &dft_pass_b_kernel<ODT, N1, N2>; }
+    template <int N1, int N2> static constexpr size_t lds_b() { return (2 * N2 * CB + N2) * sizeof(f32x2); }      // (no W_4N tables)
+    static float factor(double scale, size_t rows) { return static_cast<float>(scale / std::sqrt(static_cast<double>(rows))); }
+};
 
-// the splits of split_rows (fewbit_fft4.h)
-#define FB_DFT_SPLITS(X)                                                                                                      \
-    X(16, 16) X(32, 16) X(32, 32) X(64, 32) X(64, 64) X(128, 64) X(128, 128) X(256, 128) X(256, 256) X(512, 256) X(512, 512) \
-    X(16, 48) X(32, 48) X(32, 96) X(64, 96) X(128, 96) X(128, 192) X(256, 192)                                                \
-    X(16, 80) X(32, 80) X(64, 80) X(64, 160) X(128, 160) X(256, 160)
-
-template <typename K> int reserve_lds(K kern, size_t lds) {
-    if (lds <= 65536) return FEWBIT_OK;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FEWBIT_ERR_LAUNCH, "sampled_dft: cannot reserve %zu bytes of LDS", lds);
-    }
-    return FEWBIT_OK;
-}
-
-// The LDS opt-in of EVERY kernel of dtype DT whose tile exceeds 64 KiB (pass A reading DT, pass B writing DT), once per device at the
-// first call that uses DT -- not per instantiation at its own first launch: after one eager call of a dtype, a hipGraph capture of any
-// other row count of that dtype makes no attribute call.
-template <int DT> int opt_in_dtype() {
-    static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_relaxed) & bit) return FEWBIT_OK;
-    int rc = FEWBIT_OK;
-#define FB_DFT_OPT_IN(A, B)                                                                                               \
-    if (rc == FEWBIT_OK) rc = reserve_lds(dft_pass_a_kernel<DT, A, B, RowsInMemory>, lds_bytes_a<A>(A * B));             \
-    if (rc == FEWBIT_OK) rc = reserve_lds(dft_pass_a_kernel<DT, A, B, RowsOfSeed>, lds_bytes_a<A>(A * B));               \
-    if (rc == FEWBIT_OK) rc = reserve_lds(dft_pass_b_kernel<DT, A, B>, lds_bytes_b_dft<B>());
-    FB_DFT_SPLITS(FB_DFT_OPT_IN)
-#undef FB_DFT_OPT_IN
-    if (rc == FEWBIT_OK) done.fetch_or(bit, std::memory_order_relaxed);
-    return rc;
-}
-
-template <int DT, typename ROWS>
-int launch_a(Split sp, const void *m, size_t features, size_t ld, ROWS idx, size_t proj, f32x2 *inter, int *offsets, Sample *sorted, hipStream_t s) {
-    const unsigned tiles = static_cast<unsigned>(tiles_of(features));
-#define FB_DFT_CASE_A(A, B)                                                                                                          \
-    if (sp.n1 == A && sp.n2 == B) {                                                                                                  \
-        hipLaunchKernelGGL((dft_pass_a_kernel<DT, A, B, ROWS>), dim3(B, tiles), dim3(kThreadsA), lds_bytes_a<A>(A * B), s, m, features, ld, \
-                           inter, idx, proj, offsets, sorted);                                                                       \
-        return FEWBIT_OK;                                                                                                            \
-    }
-    FB_DFT_SPLITS(FB_DFT_CASE_A)
-#undef FB_DFT_CASE_A
-    return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dft: no kernel for %d x %d rows", sp.n1, sp.n2);
-}
-
-template <int ODT>
-int launch_b(Split sp, const f32x2 *inter, const int *offsets, const Sample *sorted, size_t proj, size_t features, float factor, void *out, hipStream_t s) {
-    const unsigned half_tiles = static_cast<unsigned>((features + 2 * CB - 1) / (2 * CB));
-#define FB_DFT_CASE_B(A, B)                                                                                                          \
-    if (sp.n1 == A && sp.n2 == B) {                                                                                                  \
-        hipLaunchKernelGGL((dft_pass_b_kernel<ODT, A, B>), dim3(A / 2 + 1, half_tiles), dim3(kThreadsB), lds_bytes_b_dft<B>(), s, inter, \
-                           offsets, sorted, proj, features, factor, out);                                                            \
-        return FEWBIT_OK;                                                                                                            \
-    }
-    FB_DFT_SPLITS(FB_DFT_CASE_B)
-#undef FB_DFT_CASE_B
-    return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dft: no kernel for %d x %d rows", sp.n1, sp.n2);
-}
-
-// Three translation units, one per dtype (-DFEWBIT_DFT_TU=0 / 1 / 2 = FEWBIT_F32 / F16 / BF16): pass A reading that dtype, pass B writing
-// it and its opt-in; the C entry points with unit 0.  Without the define everything is one unit.
 #ifndef FEWBIT_DFT_TU
 #define FEWBIT_DFT_TU -1
 #endif
-#define FB_DFT_UNIT(KEYWORD, DT)                                                                                                      \
-    KEYWORD template int opt_in_dtype<DT>();                                                                                         \
-    KEYWORD template int launch_a<DT, RowsInMemory>(Split, const void *, size_t, size_t, RowsInMemory, size_t, f32x2 *, int *, Sample *, hipStream_t); \
-    KEYWORD template int launch_a<DT, RowsOfSeed>(Split, const void *, size_t, size_t, RowsOfSeed, size_t, f32x2 *, int *, Sample *, hipStream_t); \
-    KEYWORD template int launch_b<DT>(Split, const f32x2 *, const int *, const Sample *, size_t, size_t, float, void *, hipStream_t);
-#if FEWBIT_DFT_TU >= 0
-FB_DFT_UNIT(, FEWBIT_DFT_TU)
-#endif
-#if FEWBIT_DFT_TU == 0
-FB_DFT_UNIT(extern, FEWBIT_F16)
-FB_DFT_UNIT(extern, FEWBIT_BF16)
-#endif
-#undef FB_DFT_UNIT
-
 #if FEWBIT_DFT_TU <= 0
 thread_local char g_last_error[256] = "";
 
@@ -327,62 +255,20 @@ int fail(int code, const char *fmt, ...) {
     va_end(ap);
     return code;
 }
-
-inline bool known_dtype(int dtype) { return dtype == FEWBIT_F32 || dtype == FEWBIT_F16 || dtype == FEWBIT_BF16; }
-
-inline int opt_in(int dtype) {
-    switch (dtype) {
-    case FEWBIT_F32: return opt_in_dtype<FEWBIT_F32>();
-    case FEWBIT_F16: return opt_in_dtype<FEWBIT_F16>();
-    default: return opt_in_dtype<FEWBIT_BF16>();
-    }
-}
-
-template <typename ROWS>
-int run(int dtype, const void *m, size_t rows, size_t features, size_t ld, ROWS idx, size_t proj, double scale, int out_dtype, void *out, void *workspace,
-        size_t workspace_bytes, void *stream) {
-    if (!known_dtype(dtype)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dft: unknown dtype %d", dtype);
-    if (out_dtype != FEWBIT_F32 && out_dtype != dtype) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dft: out_dtype %d is neither F32 nor the dtype of m", out_dtype);
-    if (proj == 0 || features == 0) return FEWBIT_OK;
-    Split sp;
-    if (!split_rows(rows, sp)) return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dft: rows = %zu is none of 2^k (256 .. 262144), 3 x 2^k (768 .. 49152), 5 x 2^k (1280 .. 40960)", rows);
-    bool null = m == nullptr || out == nullptr;
-    if constexpr (!ROWS::kSeeded) null = null || idx.idx == nullptr;
-    if (null) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dft: null pointer");
-    if (ld < features) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dft: leading dimension %zu < features %zu", ld, features);
-    const size_t need = workspace_bytes_of(rows, features, proj);
-    if (workspace == nullptr || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dft: a 16-byte aligned workspace of %zu bytes is needed (fewbit_hipx_sampled_dft_workspace), got %zu", need, workspace_bytes);
-    if (tiles_of(features) > 32767) return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dft: more than 32767 column tiles");
-    if (proj > 0x7fffffffull) return fail(FEWBIT_ERR_UNSUPPORTED, "sampled_dft: more than 2^31 - 1 samples");
-    if (const int rc = opt_in(dtype)) return rc;
-    if (out_dtype != dtype)
-        if (const int rc = opt_in(out_dtype)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    f32x2 *inter = static_cast<f32x2 *>(workspace);
-    int *offsets = reinterpret_cast<int *>(static_cast<uint8_t *>(workspace) + inter_bytes(rows, features));
-    Sample *sorted = reinterpret_cast<Sample *>(reinterpret_cast<uint8_t *>(offsets) + kOffsetsBytes);
-    int rc;
-    switch (dtype) {
-    case FEWBIT_F32: rc = launch_a<FEWBIT_F32, ROWS>(sp, m, features, ld, idx, proj, inter, offsets, sorted, s); break;
-    case FEWBIT_F16: rc = launch_a<FEWBIT_F16, ROWS>(sp, m, features, ld, idx, proj, inter, offsets, sorted, s); break;
-    default: rc = launch_a<FEWBIT_BF16, ROWS>(sp, m, features, ld, idx, proj, inter, offsets, sorted, s); break;
-    }
-    if (rc != FEWBIT_OK) return rc;
-    const float factor = static_cast<float>(scale / std::sqrt(static_cast<double>(rows)));
-    switch (out_dtype) {
-    case FEWBIT_F32: rc = launch_b<FEWBIT_F32>(sp, inter, offsets, sorted, proj, features, factor, out, s); break;
-    case FEWBIT_F16: rc = launch_b<FEWBIT_F16>(sp, inter, offsets, sorted, proj, features, factor, out, s); break;
-    default: rc = launch_b<FEWBIT_BF16>(sp, inter, offsets, sorted, proj, features, factor, out, s); break;
-    }
-    if (rc != FEWBIT_OK) return rc;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FEWBIT_ERR_LAUNCH, "sampled_dft: %s", hipGetErrorString(e));
-    return FEWBIT_OK;
-}
 #endif  // FEWBIT_DFT_TU <= 0
 
 }  // namespace dft
+
+// Three translation units, one per dtype (-DFEWBIT_DFT_TU=0 / 1 / 2 = FEWBIT_F32 / F16 / BF16): pass A reading that dtype, pass B writing
+// it and its opt-in; the C entry points with unit 0.  Without the define everything is one unit.
+#if FEWBIT_DFT_TU >= 0
+FB_FFT4_UNIT(, dft::Dft, FEWBIT_DFT_TU)
+#endif
+#if FEWBIT_DFT_TU == 0
+FB_FFT4_UNIT(extern, dft::Dft, FEWBIT_F16)
+FB_FFT4_UNIT(extern, dft::Dft, FEWBIT_BF16)
+#endif
+
 }  // namespace fewbit_hip
 
 #if FEWBIT_DFT_TU <= 0
@@ -403,14 +289,12 @@ size_t fewbit_hipx_sampled_dft_workspace(int dtype, size_t rows, size_t features
 
 int fewbit_hipx_sampled_dft(int dtype, const void *m, size_t rows, size_t features, size_t ld, const int64_t *idx, size_t proj, double scale, int out_dtype,
                             void *out, void *workspace, size_t workspace_bytes, void *stream) {
-    return run(dtype, m, rows, features, ld, RowsInMemory{idx}, proj, scale, out_dtype, out, workspace, workspace_bytes, stream);
+    return run<Dft>(dtype, out_dtype, m, rows, features, ld, RowsInMemory{idx}, proj, scale, out, workspace, workspace_bytes, stream);
 }
 
 int fewbit_hipx_sampled_dft_seeded(int dtype, const void *m, size_t rows, size_t features, size_t ld, uint64_t seed, const uint64_t *seed_device, size_t proj,
                                    double scale, int out_dtype, void *out, void *workspace, size_t workspace_bytes, void *stream) {
-    if ((reinterpret_cast<uintptr_t>(seed_device) & 7) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_dft: the seed word in device memory must be 8-byte aligned");
-    const RowsOfSeed of{sketch::Key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)}, reinterpret_cast<const sketch::Key *>(seed_device)};
-    return run(dtype, m, rows, features, ld, of, proj, scale, out_dtype, out, workspace, workspace_bytes, stream);
+    return run<Dft>(dtype, out_dtype, m, rows, features, ld, rows_of_seed(seed, seed_device), proj, scale, out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

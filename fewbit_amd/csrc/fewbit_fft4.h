@@ -1,11 +1,13 @@
 // fewbit_fft4.h -- the four-step fp32 FFT of the sampled transforms, shared by fewbit_dct.hip (sampled DCT-II) and fewbit_dft.hip
 // (sampled DFT): tile constants, the small transforms in registers, the in-place LDS stages and their digit maps, the 16-byte row
 // loads, the twiddle tables, the rows of a seed (RowsInMemory / RowsOfSeed) and their sort by residue class (sort_rows), the row
-// split N = N1 x N2 (split_rows) and the workspace formula.  The algorithm and the tiling are described in fewbit_dct.hip's header;
-// the two files differ only in how pass A orders the rows it loads and in pass B's epilogue.
+// split N = N1 x N2 (split_rows, FB_FFT4_SPLITS), the workspace formula and the host side of a call (run: checks, LDS opt-in,
+// dispatch).  The algorithm and the tiling are described in fewbit_dct.hip's header; the two files differ only in how pass A orders
+// the rows it loads and in pass B's epilogue.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <type_traits>
 
@@ -378,6 +380,14 @@ inline bool split_rows(size_t rows, Split &s) {
     s.n2 = static_cast<int>(rows / static_cast<size_t>(s.n1));
     return true;
 }
+// the (N1, N2) split_rows returns: the cases of the launches and of the LDS opt-in
+#define FB_FFT4_SPLITS(X)                                                                                                     \
+    X(16, 16) X(32, 16) X(32, 32) X(64, 32) X(64, 64) X(128, 64) X(128, 128) X(256, 128) X(256, 256) X(512, 256) X(512, 512) \
+    X(16, 48) X(32, 48) X(32, 96) X(64, 96) X(128, 96) X(128, 192) X(256, 192)                                                \
+    X(16, 80) X(32, 80) X(64, 80) X(64, 160) X(128, 160) X(256, 160)
+// the row counts split_rows takes, as every refusal names them
+constexpr char kRowFamilies[] = "2^k (256 .. 262144), 3 x 2^k (768 .. 49152), 5 x 2^k (1280 .. 40960)";
+
 inline size_t tiles_of(size_t features) { return (features + kFeatures - 1) / kFeatures; }
 inline size_t inter_bytes(size_t rows, size_t features) { return tiles_of(features) * rows * C * sizeof(f32x2); }
 // workspace: [the intermediate | offsets of the sorted samples (2 KiB) | the sorted samples, 8 bytes each]
@@ -385,6 +395,141 @@ inline size_t workspace_bytes_of(size_t rows, size_t features, size_t proj) { re
 
 template <int L> constexpr size_t lds_bytes_a(int n) { return (kRowsA * L * C + L + kFine + coarse_entries(n)) * sizeof(f32x2); }
 template <int L> constexpr size_t lds_bytes_b(int n) { return (2 * L * CB + L + kFine + coarse_entries(n)) * sizeof(f32x2); }
+
+inline bool known_dtype(int dtype) { return dtype == FEWBIT_F32 || dtype == FEWBIT_F16 || dtype == FEWBIT_BF16; }
+inline RowsOfSeed rows_of_seed(uint64_t seed, const uint64_t *device) {
+    return RowsOfSeed{sketch::Key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)}, reinterpret_cast<const sketch::Key *>(device)};
+}
+
+// ---- the host side of both kernel pairs --------------------------------------------------------------------------------------
+// PAIR (fewbit_dct.hip: Dct, fewbit_dft.hip: Dft) holds what differs between them: its kernels (pass_a<DT, N1, N2, ROWS>() and
+// pass_b<ODT, N1, N2>()), pass B's LDS (lds_b<N1, N2>()), the factor pass B applies (factor(scale, rows)), the prefix of its messages
+// (kName), its workspace query (kWorkspace), its error reporter (fail: each library keeps its own last error) and kSeededLast (below).
+template <typename PAIR> int refuse_rows(const char *what, size_t rows) {
+    return PAIR::fail(FEWBIT_ERR_UNSUPPORTED, "%s: rows = %zu is none of %s", what, rows, kRowFamilies);
+}
+
+template <typename PAIR, typename K> int reserve_lds(K kern, size_t lds) {
+    if (lds <= 65536) return FEWBIT_OK;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) {
+        (void)hipGetLastError();
+        return PAIR::fail(FEWBIT_ERR_LAUNCH, "%s: cannot reserve %zu bytes of LDS", PAIR::kName, lds);
+    }
+    return FEWBIT_OK;
+}
+
+// The LDS opt-in of EVERY kernel of dtype DT whose tile exceeds 64 KiB (pass A reading DT, for both kinds of rows, and pass B writing
+// DT), once per device at the first call that uses DT -- not per instantiation at its own first launch: after one eager call of a
+// dtype, a hipGraph capture of any other row count of that dtype makes no attribute call.
+template <typename PAIR, int DT> int opt_in_dtype() {
+    static std::atomic<unsigned long long> done{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_relaxed) & bit) return FEWBIT_OK;
+    int rc = FEWBIT_OK;
+    // (the order in which a unit first names its kernels is their order in the device module, and the code generated for the last
+    // split depends on it: each pair names them in the order of its former host code -- the DCT's seeded pass A after all others)
+#define FB_FFT4_OPT_IN(A, B)                                                                                                  \
+    if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_a<DT, A, B, RowsInMemory>(), lds_bytes_a<A>(A * B));   \
+    if constexpr (!PAIR::kSeededLast) FB_FFT4_OPT_IN_SEEDED(A, B)                                                             \
+    if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_b<DT, A, B>(), PAIR::template lds_b<A, B>());
+#define FB_FFT4_OPT_IN_SEEDED(A, B) \
+    if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_a<DT, A, B, RowsOfSeed>(), lds_bytes_a<A>(A * B));
+    FB_FFT4_SPLITS(FB_FFT4_OPT_IN)
+    if constexpr (PAIR::kSeededLast) { FB_FFT4_SPLITS(FB_FFT4_OPT_IN_SEEDED) }
+#undef FB_FFT4_OPT_IN
+#undef FB_FFT4_OPT_IN_SEEDED
+    if (rc == FEWBIT_OK) done.fetch_or(bit, std::memory_order_relaxed);
+    return rc;
+}
+
+template <typename PAIR, int DT, typename ROWS>
+int launch_a(Split sp, const void *m, size_t features, size_t ld, ROWS idx, size_t proj, f32x2 *inter, int *offsets, Sample *sorted, hipStream_t s) {
+    const unsigned tiles = static_cast<unsigned>(tiles_of(features));
+#define FB_FFT4_CASE_A(A, B)                                                                                                   \
+    if (sp.n1 == A && sp.n2 == B) {                                                                                            \
+        static_assert(lds_bytes_a<A>(A * B) >= 2 * (A / 2 + 2) * sizeof(int) && (A / 2 + 2) * sizeof(int) <= kOffsetsBytes,    \
+                      "the sort's counters fit pass A's LDS and the offsets their slot");                                      \
+        constexpr auto kern = PAIR::template pass_a<DT, A, B, ROWS>();                                                         \
+        hipLaunchKernelGGL(kern, dim3(B, tiles), dim3(kThreadsA), lds_bytes_a<A>(A * B), s, m, features, ld, inter, idx, proj, offsets, sorted); \
+        return FEWBIT_OK;                                                                                                      \
+    }
+    FB_FFT4_SPLITS(FB_FFT4_CASE_A)
+#undef FB_FFT4_CASE_A
+    return PAIR::fail(FEWBIT_ERR_UNSUPPORTED, "%s: no kernel for %d x %d rows", PAIR::kName, sp.n1, sp.n2);
+}
+
+template <typename PAIR, int ODT>
+int launch_b(Split sp, const f32x2 *inter, const int *offsets, const Sample *sorted, size_t proj, size_t features, float factor, void *out, hipStream_t s) {
+    const unsigned half_tiles = static_cast<unsigned>((features + 2 * CB - 1) / (2 * CB));
+#define FB_FFT4_CASE_B(A, B)                                                                                                   \
+    if (sp.n1 == A && sp.n2 == B) {                                                                                            \
+        constexpr auto kern = PAIR::template pass_b<ODT, A, B>();                                                              \
+        hipLaunchKernelGGL(kern, dim3(A / 2 + 1, half_tiles), dim3(kThreadsB), (PAIR::template lds_b<A, B>()), s, inter, offsets, sorted, proj, features, factor, out); \
+        return FEWBIT_OK;                                                                                                      \
+    }
+    FB_FFT4_SPLITS(FB_FFT4_CASE_B)
+#undef FB_FFT4_CASE_B
+    return PAIR::fail(FEWBIT_ERR_UNSUPPORTED, "%s: no kernel for %d x %d rows", PAIR::kName, sp.n1, sp.n2);
+}
+
+// the host functions of dtype DT: a pair is compiled as three translation units, one per dtype, each instantiating its own (KEYWORD
+// empty); the unit with the C entry points declares the other two (KEYWORD extern).  Used in namespace fewbit_hip or fewbit_hip::dct.
+#define FB_FFT4_UNIT(KEYWORD, PAIR, DT)                                                                                        \
+    KEYWORD template int dct::opt_in_dtype<PAIR, DT>();                                                                        \
+    KEYWORD template int dct::launch_a<PAIR, DT, dct::RowsInMemory>(dct::Split, const void *, size_t, size_t, dct::RowsInMemory, size_t, dct::f32x2 *, int *, dct::Sample *, hipStream_t); \
+    KEYWORD template int dct::launch_a<PAIR, DT, dct::RowsOfSeed>(dct::Split, const void *, size_t, size_t, dct::RowsOfSeed, size_t, dct::f32x2 *, int *, dct::Sample *, hipStream_t); \
+    KEYWORD template int dct::launch_b<PAIR, DT>(dct::Split, const dct::f32x2 *, const int *, const dct::Sample *, size_t, size_t, float, void *, hipStream_t);
+
+// calls f(std::integral_constant<int, DT>) for the run-time dtype (one of known_dtype)
+template <typename F> int with_dtype(int dtype, F &&f) {
+    switch (dtype) {
+    case FEWBIT_F32: return f(std::integral_constant<int, FEWBIT_F32>{});
+    case FEWBIT_F16: return f(std::integral_constant<int, FEWBIT_F16>{});
+    default: return f(std::integral_constant<int, FEWBIT_BF16>{});
+    }
+}
+
+// One call of a pair: the argument checks, the LDS opt-in of the dtypes involved, the workspace carved into [inter | offsets | sorted],
+// pass A reading `dtype`, pass B writing `out_dtype` (the DCT's is its dtype), and the launch error.
+template <typename PAIR, typename ROWS>
+int run(int dtype, int out_dtype, const void *m, size_t rows, size_t features, size_t ld, ROWS idx, size_t proj, double scale, void *out,
+        void *workspace, size_t workspace_bytes, void *stream) {
+    const char *name = PAIR::kName;
+    if (!known_dtype(dtype)) return PAIR::fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: unknown dtype %d", name, dtype);
+    if (out_dtype != FEWBIT_F32 && out_dtype != dtype) return PAIR::fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: out_dtype %d is neither F32 nor the dtype of m", name, out_dtype);
+    if (proj == 0 || features == 0) return FEWBIT_OK;
+    if constexpr (ROWS::kSeeded)
+        if ((reinterpret_cast<uintptr_t>(idx.device) & 7) != 0) return PAIR::fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the seed word in device memory must be 8-byte aligned", name);
+    Split sp;
+    if (!split_rows(rows, sp)) return refuse_rows<PAIR>(name, rows);
+    bool null = m == nullptr || out == nullptr;
+    if constexpr (!ROWS::kSeeded) null = null || idx.idx == nullptr;
+    if (null) return PAIR::fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer", name);
+    if (ld < features) return PAIR::fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: leading dimension %zu < features %zu", name, ld, features);
+    const size_t need = workspace_bytes_of(rows, features, proj);
+    if (workspace == nullptr || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
+        return PAIR::fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: a 16-byte aligned workspace of %zu bytes is needed (%s), got %zu", name, need, PAIR::kWorkspace, workspace_bytes);
+    if (tiles_of(features) > 32767) return PAIR::fail(FEWBIT_ERR_UNSUPPORTED, "%s: more than 32767 column tiles", name);
+    if (proj > 0x7fffffffull) return PAIR::fail(FEWBIT_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 samples", name);
+    auto opt_in = [](auto dt) { return opt_in_dtype<PAIR, decltype(dt)::value>(); };
+    if (const int rc = with_dtype(dtype, opt_in)) return rc;
+    if (out_dtype != dtype)
+        if (const int rc = with_dtype(out_dtype, opt_in)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    f32x2 *inter = static_cast<f32x2 *>(workspace);
+    int *offsets = reinterpret_cast<int *>(static_cast<uint8_t *>(workspace) + inter_bytes(rows, features));
+    Sample *sorted = reinterpret_cast<Sample *>(reinterpret_cast<uint8_t *>(offsets) + kOffsetsBytes);
+    if (const int rc = with_dtype(dtype, [&](auto dt) { return launch_a<PAIR, decltype(dt)::value, ROWS>(sp, m, features, ld, idx, proj, inter, offsets, sorted, s); }))
+        return rc;
+    const float factor = PAIR::factor(scale, rows);
+    if (const int rc = with_dtype(out_dtype, [&](auto dt) { return launch_b<PAIR, decltype(dt)::value>(sp, inter, offsets, sorted, proj, features, factor, out, s); }))
+        return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return PAIR::fail(FEWBIT_ERR_LAUNCH, "%s: %s", name, hipGetErrorString(e));
+    return FEWBIT_OK;
+}
 
 }  // namespace dct
 }  // namespace fewbit_hip

@@ -196,29 +196,27 @@ def _sketch_seed(generator: Optional[torch.Generator], device: torch.device):
     return cabi.next_sketch_seed(counter, _draw_seed(generator))
 
 
+def _unit_stride(mat: torch.Tensor) -> torch.Tensor:
+    """``mat``, or a contiguous copy when its rows are not unit-stride rows at least ``features`` apart (e.g. the expanded gradient of a
+    sum: strides (0, 0)) -- what the kernels take"""
+    return mat if mat.stride(1) == 1 and mat.stride(0) >= mat.shape[1] else mat.contiguous()
+
+
 def _native_sketch(kind: str, mat: torch.Tensor, p: int, seed, scale: float) -> torch.Tensor:
     from . import cabi
-    if mat.stride(1) != 1 or mat.stride(0) < mat.shape[1]:      # (e.g. the expanded gradient of a sum: strides (0, 0))
-        mat = mat.contiguous()
-    return cabi.sketch(kind, mat, p, seed, scale)
+    return cabi.sketch(kind, _unit_stride(mat), p, seed, scale)
 
 
-def _native_dct(mat: torch.Tensor, p: int, seed, scale: float) -> torch.Tensor:
-    """``scale * dct(mat, dim=0, norm='ortho')[rows(seed)]`` on this package's kernel pair: M is read once, one fp32 intermediate goes
-    out and back, only the p sampled rows are written (the torch formulation materialises the whole transform in fp32 first)"""
-    from . import cabi
-    if mat.stride(1) != 1 or mat.stride(0) < mat.shape[1]:
-        mat = mat.contiguous()
-    return cabi.sampled_dct_seeded(mat, p, seed, scale)
-
-
-def _native_dft(mat: torch.Tensor, p: int, seed, scale: float, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
-    """``scale * torch.fft.fft(mat, dim=0, norm='ortho')[rows(seed)]`` on this package's kernel pair, as a ``(2, p, features)`` tensor of
-    ``out_dtype`` (default: the dtype of ``mat``): ``[0]`` the real part, ``[1]`` the imaginary part"""
+def _native_transform(kind: str, mat: torch.Tensor, p: int, seed, scale: float, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``scale * transform(mat, dim=0, norm='ortho')[rows(seed)]`` on this package's kernel pair: M is read once, one fp32 intermediate goes
+    out and back, only the p sampled rows are written (the torch formulation materialises the whole transform in fp32 first).  'dct': a
+    ``(p, features)`` tensor of the dtype of ``mat``; 'dft': a ``(2, p, features)`` tensor of ``out_dtype`` (default: the dtype of ``mat``),
+    ``[0]`` the real part, ``[1]`` the imaginary part"""
+    if kind == 'dct':
+        from . import cabi
+        return cabi.sampled_dct_seeded(_unit_stride(mat), p, seed, scale)
     from . import cabi_x
-    if mat.stride(1) != 1 or mat.stride(0) < mat.shape[1]:
-        mat = mat.contiguous()
-    return cabi_x.sampled_dft_seeded(mat, p, seed, scale, out_dtype)
+    return cabi_x.sampled_dft_seeded(_unit_stride(mat), p, seed, scale, out_dtype)
 
 
 _INJECTED: Optional[torch.Tensor] = None
@@ -256,49 +254,44 @@ def _sampled_rows(p: int, rows: int, like: torch.Tensor, gen: torch.Generator) -
     return torch.randint(0, rows, (p, ), generator=gen, device=gen.device).to(like.device)
 
 
-def _native_dct_applies(mat: torch.Tensor) -> bool:
-    """The gfx950 sampled-DCT kernel pair (fewbit_amd/csrc/fewbit_dct.hip) takes 2-D fp32 / fp16 / bf16 GPU tensors whose row count is
-    2^k in [256, 262144] (RoBERTa's 128 x 128 tokens = 16384) or 3 x 2^k in [768, 49152] (32 sequences of 384 tokens = 12288) or 5 x 2^k in [1280, 40960]; everything
-    else keeps the torch.fft formulation."""
-    if not (_NATIVE_SKETCH and mat.device.type == 'cuda' and mat.dim() == 2 and mat.dtype in (torch.float32, torch.float16, torch.bfloat16)):
-        return False
-    rows = mat.shape[0]
-    return _dct_rows_supported(rows) and mat.shape[1] > 0
+_TRANSFORM_ROWS = {}
 
 
-def _dct_rows_supported(rows: int) -> bool:
-    """2^k rows, k = 8 .. 18, 3 x 2^k rows, k = 8 .. 14, or 5 x 2^k rows, k = 8 .. 13 (fewbit_dct.hip::split_rows)"""
-    three = rows % 3 == 0
-    five = not three and rows % 5 == 0
-    two = rows // 3 if three else rows // 5 if five else rows
-    return 256 <= two <= (16384 if three else 8192 if five else 262144) and two & (two - 1) == 0
-
-
-_DFT_ROWS = {}
-
-
-def _native_dft_applies(mat: torch.Tensor) -> bool:
-    """The gfx950 sampled-DFT kernel pair (fewbit_amd/csrc/fewbit_dft.hip) takes 2-D fp32 / fp16 / bf16 GPU tensors of the row counts the
-    library has a kernel for (those of the DCT pair), as it says itself: ``sampled_dft_workspace_bytes(rows, 1, 1) != 0``, asked once per
-    row count; everything else keeps the torch.fft formulation."""
-    if not (_NATIVE_SKETCH and mat.device.type == 'cuda' and mat.dim() == 2 and mat.dtype in (torch.float32, torch.float16, torch.bfloat16)
-            and mat.shape[1] > 0):
-        return False
-    rows = mat.shape[0]
-    ok = _DFT_ROWS.get(rows)
+def _transform_rows(kind: str, rows: int) -> bool:
+    """Whether the library that owns the sampled transform ``kind`` has a kernel for ``rows`` rows, as it says itself: its workspace query
+    at (rows, 1, 1) is non-zero ('dct': libfewbit_hip.so, 'dft': libfewbit_hipx.so -- a 'dct' question never loads the companion library);
+    asked once per kind and row count."""
+    ok = _TRANSFORM_ROWS.get((kind, rows))
     if ok is None:
-        from . import cabi_x
-        ok = _DFT_ROWS[rows] = cabi_x.sampled_dft_workspace_bytes(rows, 1, 1, torch.float32) != 0
+        if kind == 'dct':
+            from . import cabi
+            ok = cabi.sampled_dct_workspace_bytes(rows, 1, 1, torch.float32) != 0
+        else:
+            from . import cabi_x
+            ok = cabi_x.sampled_dft_workspace_bytes(rows, 1, 1, torch.float32) != 0
+        _TRANSFORM_ROWS[(kind, rows)] = ok
     return ok
+
+
+def _native_transform_applies(kind: str, mat: torch.Tensor) -> bool:
+    """The gfx950 sampled-transform kernel pairs (fewbit_amd/csrc/fewbit_dct.hip, fewbit_dft.hip) take 2-D fp32 / fp16 / bf16 GPU tensors
+    of the row counts their library has a kernel for (_transform_rows; e.g. RoBERTa's 128 x 128 tokens = 16384, 32 sequences of 384 tokens
+    = 12288 = 3 x 2^12); everything else keeps the torch.fft formulation."""
+    return (_NATIVE_SKETCH and kind in ('dct', 'dft') and mat.device.type == 'cuda' and mat.dim() == 2
+            and mat.dtype in (torch.float32, torch.float16, torch.bfloat16) and mat.shape[1] > 0 and _transform_rows(kind, mat.shape[0]))
+
+
+_TRANSFORM_PATHS = {
+    'dct': 'gfx950 kernel pair fewbit_hip_sampled_dct (four-step fp32 FFT in LDS, only the sampled rows are written; in the layer: rows of a seed)',
+    'dft': ('gfx950 kernel pair fewbit_hipx_sampled_dft (four-step fp32 FFT in LDS, only the sampled rows are written, real and imaginary '
+            'planes; in the layer: rows of a seed)'),
+}
 
 
 def sampled_transform_path(kind: str, mat: torch.Tensor) -> str:
     """Which code computes the sampled transform ``kind`` ('dct' / 'dft') of ``mat`` (what bench.py prints beside its time)."""
-    if kind == 'dct' and _native_dct_applies(mat):
-        return 'gfx950 kernel pair fewbit_hip_sampled_dct (four-step fp32 FFT in LDS, only the sampled rows are written; in the layer: rows of a seed)'
-    if kind == 'dft' and _native_dft_applies(mat):
-        return ('gfx950 kernel pair fewbit_hipx_sampled_dft (four-step fp32 FFT in LDS, only the sampled rows are written, real and imaginary '
-                'planes; in the layer: rows of a seed)')
+    if _native_transform_applies(kind, mat):
+        return _TRANSFORM_PATHS[kind]
     return 'torch.fft (rocFFT on the GPU): full transform along dim 0 in fp32, then the gather of the sampled rows'
 
 
@@ -306,12 +299,12 @@ def sampled_transform(kind: str, mat: torch.Tensor, p: int, gen: torch.Generator
     """One estimator product of the layer, ``scale * transform(mat)[p sampled rows]``, on the path ``linear_grp`` takes for this
     ``kind`` and ``mat`` (what bench.py and tools/ time): the kernel pair with rows of ``seed``, or torch.fft + randint from ``gen``.
     'dft' returns a complex64 ``(p, features)`` tensor on either path (on the kernel pair: built from its fp32 planes)."""
-    if kind == 'dct' and _native_dct_applies(mat):
-        return _native_dct(mat, p, seed, scale)
-    if kind == 'dft' and _native_dft_applies(mat):
-        planes = _native_dft(mat, p, seed, scale, torch.float32)
-        return torch.complex(planes[0], planes[1])
-    return _sketch(kind, mat, p, gen, scale=scale)
+    if not _native_transform_applies(kind, mat):
+        return _sketch(kind, mat, p, gen, scale=scale)
+    if kind == 'dct':
+        return _native_transform(kind, mat, p, seed, scale)
+    planes = _native_transform(kind, mat, p, seed, scale, torch.float32)
+    return torch.complex(planes[0], planes[1])
 
 
 def _sketch(kind: str, mat: torch.Tensor, p: int, gen: torch.Generator, sketch_dtype=None, draw_dtype=None, scale: float = 1.0) -> torch.Tensor:
@@ -340,45 +333,34 @@ class _LinearGRP(torch.autograd.Function):
         flat = input.reshape(-1, input.shape[-1])
         rows = flat.shape[0]
         ctx.native_seed = None
-        if _native_sketch_applies(kind, flat, sketch_dtype):
-            # S lives nowhere: the projection and the seed are all that is kept
+        ctx.p, ctx.kind = p, kind
+        ctx.has_bias = bias is not None
+        dense = _native_sketch_applies(kind, flat, sketch_dtype)
+        if dense or _native_transform_applies(kind, flat):
+            # S -- or the sampled rows -- lives nowhere: a function of the seed that the kernel evaluates itself; the projection and the
+            # seed are all that is kept (no randint launch, no RNG state to save and replay; while a graph is being captured the seed is
+            # a device word)
             ctx.native_seed = _sketch_seed(generator, flat.device)
-            # sketch_dtype (16-bit) for a wider input: the projection is computed from, and KEPT in, that dtype -- half the
-            # saved bytes of an fp32 layer, and the small GEMM of backward runs on the 16-bit matrix pipe as well
-            low = sketch_dtype if sketch_dtype is not None and sketch_dtype != flat.dtype else None
-            ctx.low = low
+            # sketch_dtype (16-bit) for a wider input: a dense projection is computed from, and KEPT in, that dtype -- half the saved bytes
+            # of an fp32 layer, and the small GEMM of backward runs on the 16-bit matrix pipe as well
+            ctx.low = sketch_dtype if dense and sketch_dtype is not None and sketch_dtype != flat.dtype else None
+            x = flat.detach() if ctx.low is None else flat.detach().to(ctx.low)
             # (the sketch before or after the layer's own GEMM: no difference, profiles/r05_roberta_ab_order.txt)
-            sketch = _native_sketch(kind, flat.detach() if low is None else flat.detach().to(low), p, ctx.native_seed, 1.0 / p)
-            ctx.save_for_backward(sketch, weight)
-            ctx.p, ctx.kind = p, kind
-            ctx.has_bias = bias is not None
-            return F.linear(input, weight, bias)
-        if kind == 'dct' and _native_dct_applies(flat):
-            # the sampled rows live nowhere either: a function of the seed that the kernel evaluates itself (no randint launch, no
-            # RNG state to save and replay; while a graph is being captured the seed is a device word, like the dense sketches')
-            ctx.native_seed = _sketch_seed(generator, flat.device)
-            ctx.low = None
-            sketch = _native_dct(flat.detach(), p, ctx.native_seed, rows / p)
-            ctx.save_for_backward(sketch, weight)
-            ctx.p, ctx.kind = p, kind
-            ctx.has_bias = bias is not None
-            return F.linear(input, weight, bias)
-        if kind == 'dft' and _native_dft_applies(flat):
-            # the same on the Fourier pair: kept are the real and imaginary planes in the layer's dtype (two p x features views of one buffer)
-            ctx.native_seed = _sketch_seed(generator, flat.device)
-            ctx.low = None
-            planes = _native_dft(flat.detach(), p, ctx.native_seed, rows / p)
-            ctx.save_for_backward(planes[0], planes[1], weight)
-            ctx.p, ctx.kind = p, kind
-            ctx.has_bias = bias is not None
+            if dense:
+                kept = (_native_sketch(kind, x, p, ctx.native_seed, 1.0 / p), )
+            elif kind == 'dct':
+                kept = (_native_transform(kind, x, p, ctx.native_seed, rows / p), )
+            else:                                       # 'dft': the real and imaginary planes in the layer's dtype, two views of one buffer
+                planes = _native_transform(kind, x, p, ctx.native_seed, rows / p)
+                kept = (planes[0], planes[1])
+            ctx.save_for_backward(*kept, weight)
             return F.linear(input, weight, bias)
         token, gen = _capture_rng(generator, input.device)
         scale = 1.0 / p if kind in ('gaussian', 'rademacher') else rows / p
         draw_dtype = sketch_dtype or flat.dtype
         sketch = _sketch(kind, flat.detach(), p, gen, sketch_dtype, draw_dtype, scale)
         ctx.save_for_backward(sketch, weight)
-        ctx.token, ctx.p, ctx.kind, ctx.sketch_dtype, ctx.draw_dtype = token, p, kind, sketch_dtype, draw_dtype
-        ctx.has_bias = bias is not None
+        ctx.token, ctx.sketch_dtype, ctx.draw_dtype = token, sketch_dtype, draw_dtype
         return F.linear(input, weight, bias)
 
     @staticmethod
@@ -398,13 +380,11 @@ class _LinearGRP(torch.autograd.Function):
             if ctx.kind == 'dft':
                 # Re((F G)^H (F X)) = Gr^T Xr + Gi^T Xi: two accumulating GEMMs in the dtype of the planes
                 xr, xi = saved[0], saved[1]
-                g = _native_dft(g2, ctx.p, ctx.native_seed, 1.0).to(xr.dtype)
+                g = _native_transform('dft', g2, ctx.p, ctx.native_seed, 1.0).to(xr.dtype)
                 grad_weight = torch.addmm(g[0].T @ xr, g[1].T, xi).to(weight.dtype)
             else:
-                if ctx.kind == 'dct':
-                    proj = _native_dct(g2, ctx.p, ctx.native_seed, 1.0)
-                else:
-                    proj = _native_sketch(ctx.kind, g2, ctx.p, ctx.native_seed, 1.0)
+                native = _native_transform if ctx.kind == 'dct' else _native_sketch
+                proj = native(ctx.kind, g2, ctx.p, ctx.native_seed, 1.0)
                 grad_weight = (proj.to(sketch.dtype).T @ sketch).to(weight.dtype)
         elif ctx.needs_input_grad[1]:
             proj = _sketch(ctx.kind, flat, ctx.p, _replay_rng(ctx.token), ctx.sketch_dtype, ctx.draw_dtype)

@@ -223,7 +223,9 @@ int fewbit_hip_sketch_describe(int dist, int dtype, size_t rows, size_t features
  *   out  proj x features, contiguous, the dtype of m (fully written)
  *   workspace  fewbit_hip_sampled_dct_workspace(...) = ceil(features / 64) * rows * 256 (the fp32 intermediate) + 2048 + 8 * proj rounded up to
  *              16 (the samples sorted by residue class) bytes, 16-byte aligned; contents are scratch
- * Two launches on `stream` (fewbit_amd/csrc/fewbit_dct.hip); deterministic. */
+ * Two launches on `stream` (fewbit_amd/csrc/fewbit_dct.hip); deterministic.  Tiles at 32768 rows and more need more than 64 KiB of LDS:
+ * the first call of a dtype on a device reserves it for every row count of that dtype, so one eager call per dtype and device precedes
+ * a hipGraph capture of any row count of it. */
 size_t fewbit_hip_sampled_dct_workspace(int dtype, size_t rows, size_t features, size_t proj);
 int fewbit_hip_sampled_dct(int dtype, const void *m, size_t rows, size_t features, size_t ld, const int64_t *idx, size_t proj, double scale,
                            void *out, void *workspace, size_t workspace_bytes, void *stream);

@@ -1,4 +1,6 @@
-"""Shared helpers for the parity tests (bit-exact views, fixture decoding, ULP distance)."""
+"""Shared helpers for the parity tests (bit-exact views, fixture decoding, ULP distance, captured steps of the sampled transforms)."""
+import subprocess
+import sys
 from pathlib import Path
 
 import numpy as np
@@ -169,3 +171,63 @@ def sha256_of(t: torch.Tensor) -> str:
     import hashlib
     t = t.detach().cpu().contiguous()
     return hashlib.sha256(t.view(torch.uint8).numpy().tobytes()).hexdigest()
+
+
+# ---- the layer's sampled transforms ('dct', 'dft') inside a hipGraph (tests/test_gpu_dct.py, tests/test_gpu_dft.py) -------------------
+BASE = 0x7654321                     # the host draw the recorded seed kernel starts from (linear._draw_seed pinned to it)
+
+
+def captured_step_replays_fresh_rows(kind, rows, features, p, dtype, warm_rows, dev='cuda:0'):
+    """warm up the layer (matmul=kind) eagerly at `warm_rows`, capture one fwd + bwd step at `rows`, replay it three times; every replay must
+    equal the explicit product on the rows of its seed, and replays must differ.  The caller pins linear._draw_seed to BASE."""
+    import fewbit
+    from fewbit_amd import cabi, cabi_x, linear
+    lin = fewbit.RandomizedLinear(features, 32, proj_dim=p, matmul=kind, bias=False, device=dev, dtype=dtype)
+    x = torch.randn(rows, features, device=dev, dtype=dtype, requires_grad=True)
+    wgt = torch.randn(rows, 32, device=dev, dtype=dtype)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        xw = torch.randn(warm_rows, features, device=dev, dtype=dtype, requires_grad=True)
+        torch.autograd.grad((lin(xw) * torch.randn(warm_rows, 32, device=dev, dtype=dtype)).sum(), lin.weight)
+    torch.cuda.current_stream().wait_stream(side)
+    counter = linear._replay_counter(torch.device(dev))
+    c0 = int(counter)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        gw, = torch.autograd.grad((lin(x) * wgt).sum(), lin.weight)
+    seen = []
+    for r in range(3):
+        g.replay()
+        torch.cuda.synchronize()
+        assert int(counter) == c0 + r + 1
+        idx = cabi.sampled_rows(cabi.mix_sketch_seed(BASE, c0 + r), rows, p).to(dev)
+        if kind == 'dct':
+            want = cabi.sampled_dct(wgt, idx).T @ cabi.sampled_dct(x.detach(), idx, rows / p)
+        else:
+            gr, gi = cabi_x.sampled_dft(wgt, idx)
+            xr, xi = cabi_x.sampled_dft(x.detach(), idx, rows / p)
+            want = gr.T @ xr + gi.T @ xi
+        assert torch.allclose(gw, want, rtol=1e-4, atol=1e-3), (r, float((gw - want).abs().max()))
+        seen.append(gw.clone())
+    assert not torch.equal(seen[0], seen[1]) and not torch.equal(seen[1], seen[2])
+
+
+CAPTURE_CHILD = '''
+import sys
+sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+import torch
+from fewbit_amd import linear
+import helpers
+torch.manual_seed(0)
+linear._draw_seed = lambda generator: helpers.BASE
+helpers.captured_step_replays_fresh_rows({kind!r}, 32768, 64, 3276, torch.float32, 512)
+print('captured 32768-row step ok')
+'''
+
+
+def large_tile_capture_in_a_fresh_process(kind):
+    """32768 rows (LDS tiles above 64 KiB) captured in a fresh process whose only eager call was at 512 rows"""
+    code = CAPTURE_CHILD.format(root=str(ROOT), tests=str(ROOT / 'tests'), kind=kind)
+    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and 'captured 32768-row step ok' in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]

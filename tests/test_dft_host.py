@@ -3,6 +3,7 @@ reports version 1, and its workspace is a host-side formula (the sampled DCT's);
 import ctypes
 import re
 import subprocess
+import sys
 
 import pytest
 import torch
@@ -81,3 +82,19 @@ def test_calls_are_refused_by_name_before_anything_is_launched():
     assert b'8-byte aligned' in L.fewbit_hipx_last_error()
     # proj = 0: nothing to do, whatever the rows
     assert L.fewbit_hipx_sampled_dft(0, None, 3000, 8, 8, None, 0, 1.0, 0, None, None, 0, None) == 0
+
+
+def test_the_layer_asks_the_library_of_each_kind_which_row_counts_have_a_kernel():
+    """linear's row predicate for 'dct' / 'dft' is "that library's workspace query is non-zero": every supported row count, its neighbours,
+    7 x 2^k, 0 and counts past 262144; a 'dct' question does not load the companion library"""
+    from fewbit_amd import linear
+    sweep = sorted({0, 1, 262145, 393216, 524288, 1 << 20} | {r + d for r in SUPPORTED for d in (-1, 0, 1)} | {7 << k for k in range(16)})
+    for kind, workspace in (('dct', cabi.sampled_dct_workspace_bytes), ('dft', cabi_x.sampled_dft_workspace_bytes)):
+        assert all(linear._transform_rows(kind, rows) for rows in SUPPORTED), kind
+        for rows in sweep:
+            assert linear._transform_rows(kind, rows) == (workspace(rows, 1, 1) != 0), (kind, rows)
+    code = ('import sys; sys.path.insert(0, %r)\n'
+            'from fewbit_amd import cabi_x, linear\n'
+            'assert linear._transform_rows("dct", 16384) and not linear._transform_rows("dct", 3000) and cabi_x._lib is None' % str(ROOT))
+    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]

@@ -12,7 +12,7 @@ import torch
 
 import fewbit
 from fewbit_amd import cabi
-from helpers import GOLDEN
+from helpers import BASE, GOLDEN, captured_step_replays_fresh_rows, large_tile_capture_in_a_fresh_process
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -148,31 +148,14 @@ def test_a_captured_dct_layer_step_samples_fresh_rows_on_every_replay(monkeypatc
     seed kernel derives the seed of replay r from (the host draw made at capture time, the device counter); the replayed weight gradient
     equals the explicit product on cabi.sampled_rows of that seed, backward meets forward's rows, replays differ"""
     from fewbit_amd import linear
-    lin = fewbit.RandomizedLinear(64, 32, proj_dim=96, matmul='dct', bias=False, device=DEV)
-    x = torch.randn(512, 64, device=DEV, requires_grad=True)
-    wgt = torch.randn(512, 32, device=DEV)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        torch.autograd.grad((lin(x) * wgt).sum(), lin.weight)
-    torch.cuda.current_stream().wait_stream(side)
-    base = 0x7654321
-    monkeypatch.setattr(linear, '_draw_seed', lambda generator: base)
-    counter = linear._replay_counter(torch.device(DEV))
-    c0 = int(counter)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        gw, = torch.autograd.grad((lin(x) * wgt).sum(), lin.weight)
-    seen = []
-    for r in range(3):
-        g.replay()
-        torch.cuda.synchronize()
-        assert int(counter) == c0 + r + 1
-        idx = cabi.sampled_rows(cabi.mix_sketch_seed(base, c0 + r), 512, 96).to(DEV)
-        want = cabi.sampled_dct(wgt, idx).T @ cabi.sampled_dct(x.detach(), idx, 512 / 96)
-        assert torch.allclose(gw, want, rtol=1e-4, atol=1e-3), (r, float((gw - want).abs().max()))
-        seen.append(gw.clone())
-    assert not torch.equal(seen[0], seen[1]) and not torch.equal(seen[1], seen[2])
+    monkeypatch.setattr(linear, '_draw_seed', lambda generator: BASE)
+    captured_step_replays_fresh_rows('dct', 512, 64, 96, torch.float32, 512)
+
+
+def test_a_large_tile_shape_captures_after_a_warm_up_of_another_row_count():
+    """32768 rows (LDS tiles above 64 KiB) captured in a fresh process whose only eager call was at 512 rows: the first call of a dtype
+    reserves the LDS of every large-tile kernel of that dtype, so no attribute call falls inside the capture"""
+    large_tile_capture_in_a_fresh_process('dct')
 
 
 def _fuzz_cases(n, seed):

@@ -9,16 +9,13 @@ Against numpy's float64 FFT of the same data on the host, `fft(m, axis=0, norm='
 
 The inputs are multiples of 1/16 below 4 in magnitude: exact in all three dtypes, so one float64 reference serves every dtype.
 """
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
 import fewbit
 from fewbit_amd import cabi, cabi_x, linear
-from helpers import ROOT
+from helpers import BASE, captured_step_replays_fresh_rows, large_tile_capture_in_a_fresh_process
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -217,67 +214,18 @@ def test_the_seeded_dft_estimator_has_the_mean_and_spread_of_the_formulation_wit
         assert abs(msd[True] / msd[False] - 1.0) <= 0.05, (rows, msd)
 
 
-BASE = 0x7654321                     # the host draw the recorded seed kernel starts from (linear._draw_seed pinned to it)
-
-
-def _captured_step_replays_fresh_rows(rows, features, p, dtype, warm_rows):
-    """warm up the layer eagerly at `warm_rows`, capture one fwd + bwd step at `rows`, replay it three times; every replay must equal the
-    explicit product on the rows of its seed, and replays must differ.  The caller pins linear._draw_seed to BASE."""
-    lin = fewbit.RandomizedLinear(features, 32, proj_dim=p, matmul='dft', bias=False, device=DEV, dtype=dtype)
-    x = torch.randn(rows, features, device=DEV, dtype=dtype, requires_grad=True)
-    wgt = torch.randn(rows, 32, device=DEV, dtype=dtype)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        xw = torch.randn(warm_rows, features, device=DEV, dtype=dtype, requires_grad=True)
-        torch.autograd.grad((lin(xw) * torch.randn(warm_rows, 32, device=DEV, dtype=dtype)).sum(), lin.weight)
-    torch.cuda.current_stream().wait_stream(side)
-    counter = linear._replay_counter(torch.device(DEV))
-    c0 = int(counter)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        gw, = torch.autograd.grad((lin(x) * wgt).sum(), lin.weight)
-    seen = []
-    for r in range(3):
-        g.replay()
-        torch.cuda.synchronize()
-        assert int(counter) == c0 + r + 1
-        idx = cabi.sampled_rows(cabi.mix_sketch_seed(BASE, c0 + r), rows, p).to(DEV)
-        gr, gi = cabi_x.sampled_dft(wgt, idx)
-        xr, xi = cabi_x.sampled_dft(x.detach(), idx, rows / p)
-        want = gr.T @ xr + gi.T @ xi
-        assert torch.allclose(gw, want, rtol=1e-4, atol=1e-3), (r, float((gw - want).abs().max()))
-        seen.append(gw.clone())
-    assert not torch.equal(seen[0], seen[1]) and not torch.equal(seen[1], seen[2])
-
-
 def test_a_captured_dft_layer_step_samples_fresh_rows_on_every_replay(monkeypatch):
     """The layer with matmul='dft' inside a hipGraph: the recorded seed kernel derives the seed of replay r from (the host draw made at capture
     time, the device counter); the replayed weight gradient equals the explicit product on cabi.sampled_rows of that seed, backward meets
     forward's rows, replays differ"""
     monkeypatch.setattr(linear, '_draw_seed', lambda generator: BASE)
-    _captured_step_replays_fresh_rows(512, 64, 96, torch.float32, 512)
-
-
-CHILD = '''
-import sys
-sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
-import torch
-from fewbit_amd import linear
-import test_gpu_dft as t
-torch.manual_seed(0)
-linear._draw_seed = lambda generator: t.BASE
-t._captured_step_replays_fresh_rows(32768, 64, 3276, torch.float32, 512)
-print('captured 32768-row step ok')
-'''
+    captured_step_replays_fresh_rows('dft', 512, 64, 96, torch.float32, 512)
 
 
 def test_a_large_tile_shape_captures_after_a_warm_up_of_another_row_count():
     """32768 rows (LDS tiles above 64 KiB) captured in a fresh process whose only eager call was at 512 rows: the first call of a dtype
     reserves the LDS of every large-tile kernel of that dtype, so no attribute call falls inside the capture"""
-    code = CHILD.format(root=str(ROOT), tests=str(ROOT / 'tests'))
-    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and 'captured 32768-row step ok' in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    large_tile_capture_in_a_fresh_process('dft')
 
 
 def test_the_layer_keeps_two_bf16_planes_and_its_forward_peak_is_workspace_plus_planes():
