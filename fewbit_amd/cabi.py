@@ -542,7 +542,11 @@ def sampled_dct(m: torch.Tensor, idx: torch.Tensor, scale: float = 1.0, out: Opt
                 workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
     """``scale * dct(m, dim=0, norm='ortho')[idx]`` (DCT-II along the rows, orthonormal; the reference's 'dct' sketch) for a 2-D
     ``m`` (rows x features, unit stride along the features) whose row count is one of SAMPLED_ROWS; ``idx``: int64 row
-    numbers on the device of ``m``.  fp32 arithmetic, result in the dtype of ``m``."""
+    numbers on the device of ``m``.  fp32 arithmetic, result in the dtype of ``m``.
+
+    Features ``(2c, 2c + 1)`` are transformed as one complex column: the rounding error of column ``c`` scales with the RMS of the pair
+    ``(c, c ^ 1)``, and a NaN or Inf in one column makes its partner non-finite too (other columns stay bit for bit as they are).
+    torch.fft keeps every column apart."""
     if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != m.device or not idx.is_contiguous():
         raise FewbitHipError('idx must be a contiguous 1-D int64 tensor on the device of m')
     proj = idx.numel()
@@ -554,7 +558,8 @@ def sampled_dct_seeded(m: torch.Tensor, proj: int, seed, scale: float = 1.0, out
                        workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
     """``sampled_dct(m, sampled_rows(seed, rows, proj))`` without the array of row numbers: the rows are a function of ``seed`` that the
     kernel evaluates itself.  ``seed``: an int, or a one-element int64 tensor on the device of ``m`` whose value is read when the kernel
-    runs (``next_sketch_seed``: a launch recorded into a hipGraph then samples fresh rows on every replay)."""
+    runs (``next_sketch_seed``: a launch recorded into a hipGraph then samples fresh rows on every replay).  The pair contract of
+    ``sampled_dct`` holds: column ``c``'s error scales with the RMS of the pair ``(c, c ^ 1)``, a non-finite value reaches the partner."""
     if isinstance(seed, torch.Tensor):
         _seed_word(seed, 'seed')
         value, word, others = 0, seed.data_ptr(), (seed, )

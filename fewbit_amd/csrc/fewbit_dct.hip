@@ -15,6 +15,9 @@
 //      V = DFT_N(v):  DCT-II(x)[k] = Re(2 e^{-i pi k / 2N} V[k]).
 //   2. Two real columns per complex transform: M is row-major, so features (2c, 2c+1) of a row ARE a complex number in memory;
 //      Z = DFT_N(v_2c + i v_2c+1) gives V_2c[k] = (Z[k] + conj Z[N-k]) / 2 and V_2c+1[k] = (Z[k] - conj Z[N-k]) / 2i.
+//      The pair contract: the rounding error of column c scales with the RMS of the pair (c, c ^ 1), not with its own, and a NaN or Inf
+//      in one column makes its partner non-finite too; other columns, the padding behind ld and the memory around out are untouched.
+//      torch.fft (the reference, the layer's fallback) keeps every column apart (tests/test_gpu_transform_columns.py).
 //   3. Four-step DFT, N = N1 x N2 (each 16 .. 512; 16384 = 128 x 128, 262144 = 512 x 512; 12288 = 128 x 96: a factor 3 goes to N2), n = N2 n1 + n2, k = k1 + N1 k2:
 //          pass A   for every n2:  A[k1][n2] = W_N^{n2 k1} * sum_{n1} z[N2 n1 + n2] W_N1^{n1 k1}        (length-N1 DFTs over rows N2 apart)
 //          pass B   for every k1:  Z[k1 + N1 k2] = sum_{n2} A[k1][n2] W_N2^{n2 k2}                       (length-N2 DFTs, contiguous)

@@ -15,6 +15,9 @@
 //            times scale / sqrt(N) (no e^{-i pi k / 2N} twiddle, so no W_4N tables; no sqrt(2) at k = 0).
 // Exact by construction: at k = 0 and k = N / 2 the pair is one LDS entry read twice (imaginary parts 0), and a sampled pair k, N - k
 // reads the same two entries swapped (exact conjugates).  Same row counts, tiles, rows of a seed and workspace as the DCT.
+// The pair contract (the DCT's): the rounding error of column c scales with the RMS of the pair (c, c ^ 1), and a NaN or Inf in one
+// column makes its partner non-finite too; other columns, the padding behind ld and the memory around out are untouched.  torch.fft
+// (the reference, the layer's fallback) keeps every column apart (tests/test_gpu_transform_columns.py).
 // Traffic: M once + 2 x rows x features x 4 B of intermediate + 2 planes of p rows.
 #include <hip/hip_runtime.h>
 

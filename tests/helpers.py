@@ -1,4 +1,6 @@
-"""Shared helpers for the parity tests (bit-exact views, fixture decoding, ULP distance, captured steps of the sampled transforms)."""
+"""Shared helpers for the parity tests (bit-exact views, fixture decoding, ULP distance, captured steps of the sampled transforms, the
+per-column error measure of the sampled transforms and their structured inputs)."""
+import math
 import subprocess
 import sys
 from pathlib import Path
@@ -211,6 +213,116 @@ def captured_step_replays_fresh_rows(kind, rows, features, p, dtype, warm_rows, 
         assert torch.allclose(gw, want, rtol=1e-4, atol=1e-3), (r, float((gw - want).abs().max()))
         seen.append(gw.clone())
     assert not torch.equal(seen[0], seen[1]) and not torch.equal(seen[1], seen[2])
+
+
+# ---- the sampled transforms per feature column (tests/test_gpu_transform_columns.py, tests/test_transform_error_model.py) ----------------
+# Both kernel pairs transform the features (2c, 2c + 1) as ONE complex column, so the error of column c scales with the RMS of the pair
+# (c, c ^ 1).  The error of an entry is measured against the RMS of its own input column (= the RMS of its output column: the transforms are
+# orthonormal); the pair measure divides by the larger RMS of the two columns of its pair.
+U_F32 = 2.0**-24
+ERROR_FACTOR = 4.0                   # bound = 4 x max(E_ref, u log2 N): a correct packed four-step stays within 1.3 x the fp32 reference
+TRANSFORM_FAMILIES = ('white noise', 'mean 1000 sigma', 'random walk', 'single spike', 'pure tone', 'alternating', 'scales per pair')
+
+
+def column_rms(x: torch.Tensor) -> torch.Tensor:
+    """RMS of every column of a (rows, features) matrix, float64"""
+    return x.double().pow(2).mean(0).sqrt()
+
+
+def pair_rms(x: torch.Tensor) -> torch.Tensor:
+    """per column c: the larger RMS of the columns c and c ^ 1 (a last column without a partner: its own)"""
+    r = column_rms(x)
+    mate = torch.arange(r.numel(), device=r.device) ^ 1
+    mate = torch.where(mate < r.numel(), mate, torch.arange(r.numel(), device=r.device))
+    return torch.maximum(r, r[mate])
+
+
+def _planes(t: torch.Tensor) -> torch.Tensor:
+    """a complex (p, features) result as the kernel's (2, p, features) planes; a real one as it is; float64"""
+    return torch.stack([t.real, t.imag]).double() if t.is_complex() else t.double()
+
+
+def normalised_error(got: torch.Tensor, want: torch.Tensor, x: torch.Tensor, pair: bool = False) -> torch.Tensor:
+    """|got - want| / RMS of the input column of each entry (pair: / the larger RMS of the columns 2c, 2c + 1).  `got`, `want`: sampled
+    rows (p, features) or planes (2, p, features), complex allowed; `x`: the input (rows, features), already rounded to the kernel's dtype.
+    An entry of an all-zero column (pair) counts 0 when exact, inf otherwise."""
+    got, want = _planes(got), _planes(want).to(got.device)
+    rms = (pair_rms(x) if pair else column_rms(x)).to(got.device)
+    err = (got - want).abs()
+    return torch.where(rms > 0, err / torch.where(rms > 0, rms, torch.ones_like(rms)), torch.where(err == 0, 0.0, float('inf')))
+
+
+def reference_error(ref32: torch.Tensor, want: torch.Tensor, x: torch.Tensor, pair: bool = False) -> float:
+    """E_ref: the largest normalised error of the fp32 reference on the same data (over the same sampled rows)"""
+    return float(normalised_error(ref32, want, x, pair).max())
+
+
+def transform_error_check(got, want, x, e_ref: float, rel: float, pair: bool = False, floor: float = 0.0):
+    """The per-entry criterion of the sampled transforms:
+
+        |err| <= rel |want| + 4 max(E_ref, u log2 N) RMS_c + floor
+
+    rel: one rounding of the fp32 result to the output dtype (0 for fp32 results); floor: 2^-24 for fp16 results (subnormal steps);
+    RMS_c: the column's (pair: the pair's).  -> (ok, worst |err| / bound, kernel-to-reference ratio = the largest normalised error left
+    after the output rounding, / max(E_ref, u log2 N): the criterion is this ratio <= 4, with every entry finite)"""
+    rows = x.shape[0]
+    unit = max(e_ref, U_F32 * math.log2(rows))
+    got, want = _planes(got), _planes(want).to(got.device)
+    rms = (pair_rms(x) if pair else column_rms(x)).to(got.device)
+    err = (got - want).abs()
+    tol = rel * want.abs() + ERROR_FACTOR * unit * rms + floor
+    ok = bool((err <= tol).all()) and bool(torch.isfinite(got).all())
+    left = (err - rel * want.abs() - floor).clamp_min(0.0)
+    excess = torch.where(rms > 0, left / torch.where(rms > 0, rms, torch.ones_like(rms)), torch.where(left == 0, 0.0, float('inf')))
+    return ok, float((err / tol.clamp_min(1e-300)).max()), float(excess.max()) / unit
+
+
+def transform_input(family: str, kind: str, rows: int, features: int, dtype: torch.dtype, seed: int):
+    """(x, k0): a host (rows, features) matrix of `family` (TRANSFORM_FAMILIES, or 'partners': columns 2c and 2c + 1 2^20 apart -- 2^6 for
+    fp16 --, the larger one alternating between the two, and the pair (2, 3) all zero), rounded to `dtype` and returned as float64; k0:
+    the bin of the pure tone (of the DCT-II basis for kind 'dct', of the DFT for 'dft').  Amplitudes and scales differ between pairs and
+    are equal within one: the coupling inside a pair is the 'partners' family's.  Every exact output stays finite in `dtype`:
+    the fp16 mean is 100 sigma (1000 sigma x sqrt(2^18) is beyond fp16), the walk is divided by sqrt(rows)."""
+    g = torch.Generator().manual_seed(seed)
+    n = torch.arange(rows, dtype=torch.float64)[:, None]
+    col = torch.arange(features)
+    amp = (1.0 + (col // 2) % 5).double()                                  # equal within a pair (unequal pairs: 'partners')
+    k0 = rows // 3 + 7
+    fp16 = dtype == torch.float16
+    if family == 'white noise':
+        x = torch.randn(rows, features, generator=g, dtype=torch.float64)
+    elif family == 'mean 1000 sigma':
+        x = torch.randn(rows, features, generator=g, dtype=torch.float64) + (100.0 if fp16 else 1000.0)
+    elif family == 'random walk':
+        x = torch.randn(rows, features, generator=g, dtype=torch.float64).cumsum(0) / math.sqrt(rows)
+    elif family == 'single spike':
+        x = torch.zeros(rows, features, dtype=torch.float64)
+        x[torch.randint(0, rows, (features, ), generator=g), col] = amp
+    elif family == 'pure tone':
+        if kind == 'dct':
+            x = torch.cos(math.pi * (2 * n + 1) * k0 / (2 * rows)) * amp
+        else:
+            phase = torch.rand(features, generator=g, dtype=torch.float64) * 2 * math.pi
+            x = torch.cos(2 * math.pi * ((n * k0) % rows) / rows + phase) * amp
+    elif family == 'alternating':
+        x = (1.0 - 2.0 * (n % 2)) * amp
+    elif family == 'scales per pair':
+        s = torch.tensor((2.0**-6, 1.0, 2.0**6) if fp16 else (2.0**-30, 1.0, 2.0**30), dtype=torch.float64)
+        x = torch.randn(rows, features, generator=g, dtype=torch.float64) * s[(col // 2) % 3]
+    elif family == 'partners':
+        big = 2.0**6 if fp16 else 2.0**20
+        s = torch.where((col % 2) == ((col // 2) % 2), big, 1.0).double()
+        x = torch.randn(rows, features, generator=g, dtype=torch.float64) * s
+        x[:, 2:4] = 0.0
+    else:
+        raise ValueError(family)
+    return x.to(dtype).double(), k0
+
+
+def transform_rows(rows: int, k0: int, draws: int, seed: int) -> torch.Tensor:
+    """the sampled rows of a structured case: the corners 0, N/2, N-1, the tone's bins k0, N-k0, and `draws` random rows (host int64)"""
+    g = torch.Generator().manual_seed(seed)
+    return torch.cat([torch.tensor([0, rows // 2, rows - 1, k0, rows - k0]), torch.randint(0, rows, (draws, ), generator=g)])
 
 
 CAPTURE_CHILD = '''
