@@ -5,20 +5,23 @@ torch's current stream on the tensors' device, no fallback -- a missing library 
 import ctypes
 import os
 from pathlib import Path
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
-from .cabi import DTYPES, FewbitHipError, _sampled_call, _seed_word, _stream
+from .cabi import DTYPES, FewbitHipError, _buffers, _matrix, _on, _sampled_call, _seed_word, _span, _stream
 
-__all__ = ['LIB_PATH', 'ABI_VERSION', 'SYMBOLS', 'lib', 'sampled_dft', 'sampled_dft_seeded', 'sampled_dft_workspace_bytes']
+__all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft', 'sampled_dft_seeded', 'sampled_dft_workspace_bytes', 'crs_columns',
+           'crs_count', 'crs_workspace_bytes', 'crs_gather', 'crs_scatter']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
+REVISION = 2                                   # FEWBIT_HIPX_REVISION: additions inside ABI version 1 (2: the crs entry points)
 
 # every symbol include/fewbit_hipx.h declares
 SYMBOLS = ('fewbit_hipx_abi_version', 'fewbit_hipx_last_error', 'fewbit_hipx_sampled_dft_workspace', 'fewbit_hipx_sampled_dft',
-           'fewbit_hipx_sampled_dft_seeded')
+           'fewbit_hipx_sampled_dft_seeded', 'fewbit_hipx_revision', 'fewbit_hipx_crs_columns', 'fewbit_hipx_crs_workspace', 'fewbit_hipx_crs_gather',
+           'fewbit_hipx_crs_scatter')
 
 _lib = None
 
@@ -31,11 +34,18 @@ def lib() -> ctypes.CDLL:
                                  '(or `python -c "import __graft_entry__ as g; g.build()"`)')
         L = ctypes.CDLL(str(LIB_PATH))
         vp, sz, i32, dbl, u64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double, ctypes.c_uint64
+        missing = [name for name in SYMBOLS if not hasattr(L, name)]
+        if missing:
+            raise FewbitHipError(f'{LIB_PATH} lacks {", ".join(missing)} (an older revision of the library): rebuild it (make -C fewbit_amd/csrc)')
         L.fewbit_hipx_abi_version.restype = i32
         L.fewbit_hipx_abi_version.argtypes = []
         have = L.fewbit_hipx_abi_version()
         if have < ABI_VERSION:
             raise FewbitHipError(f'{LIB_PATH} has ABI version {have}, this binding needs {ABI_VERSION}: rebuild it (make -C fewbit_amd/csrc)')
+        L.fewbit_hipx_revision.restype = i32
+        L.fewbit_hipx_revision.argtypes = []
+        if L.fewbit_hipx_revision() < REVISION:
+            raise FewbitHipError(f'{LIB_PATH} has revision {L.fewbit_hipx_revision()}, this binding needs {REVISION}: rebuild it (make -C fewbit_amd/csrc)')
         L.fewbit_hipx_last_error.restype = ctypes.c_char_p
         L.fewbit_hipx_last_error.argtypes = []
         L.fewbit_hipx_sampled_dft_workspace.restype = sz
@@ -44,6 +54,14 @@ def lib() -> ctypes.CDLL:
         L.fewbit_hipx_sampled_dft.argtypes = [i32, vp, sz, sz, sz, vp, sz, dbl, i32, vp, vp, sz, vp]
         L.fewbit_hipx_sampled_dft_seeded.restype = i32
         L.fewbit_hipx_sampled_dft_seeded.argtypes = [i32, vp, sz, sz, sz, u64, vp, sz, dbl, i32, vp, vp, sz, vp]
+        L.fewbit_hipx_crs_columns.restype = i32
+        L.fewbit_hipx_crs_columns.argtypes = [u64, sz, sz, vp, vp, ctypes.POINTER(sz)]
+        L.fewbit_hipx_crs_workspace.restype = sz
+        L.fewbit_hipx_crs_workspace.argtypes = [i32, sz, sz, sz]
+        L.fewbit_hipx_crs_gather.restype = i32
+        L.fewbit_hipx_crs_gather.argtypes = [i32, vp, sz, sz, sz, u64, vp, sz, sz, vp, vp, sz, vp]
+        L.fewbit_hipx_crs_scatter.restype = i32
+        L.fewbit_hipx_crs_scatter.argtypes = [i32, vp, sz, sz, u64, vp, sz, sz, vp, vp, sz, vp]
         _lib = L
     return _lib
 
@@ -102,3 +120,76 @@ def sampled_dft_seeded(m: torch.Tensor, proj: int, seed, scale: float = 1.0, out
         value, word, others = seed & 0xffffffffffffffff, 0, ()
     return _sampled_dft_call(m, proj, out_dtype, out, workspace, others, lambda dt, odt, mp, rows, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dft_seeded(
         dt, mp, rows, features, ld, value, word, proj, scale, odt, op, wp, wb, _stream(stream, m.device)))
+
+
+# ---- column sampling of LinearCRS (fewbit_amd/csrc/fewbit_crs.hip): the columns of a seed, the gather of forward, the scatter of backward ----
+def crs_count(seed: int, in_features: int, nopairs: int) -> int:
+    """``m``, the number of distinct columns among the ``nopairs`` draws of ``seed`` (evaluated on the host; no GPU needed)"""
+    m = ctypes.c_size_t(0)
+    _check(lib().fewbit_hipx_crs_columns(seed & 0xffffffffffffffff, in_features, nopairs, None, None, ctypes.byref(m)))
+    return m.value
+
+
+def crs_columns(seed: int, in_features: int, nopairs: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The columns ``crs_gather`` keeps for ``seed``: (``cols``, ascending distinct column numbers as a host int64 tensor; ``count``, how often
+    each was drawn, int32; ``count.sum() == nopairs``).  The definition is include/fewbit_hipx.h's; evaluated on the host, no GPU needed."""
+    room = min(nopairs, in_features)
+    cols, count, m = torch.empty(room, dtype=torch.int64), torch.empty(room, dtype=torch.int32), ctypes.c_size_t(0)
+    _check(lib().fewbit_hipx_crs_columns(seed & 0xffffffffffffffff, in_features, nopairs, cols.data_ptr(), count.data_ptr(), ctypes.byref(m)))
+    return cols[:m.value], count[:m.value]
+
+
+def crs_workspace_bytes(rows: int, in_features: int, nopairs: int, dtype: torch.dtype = torch.bfloat16) -> int:
+    """bytes of scratch a ``crs_gather`` / ``crs_scatter`` call needs; 0 = no kernel (a dtype other than fp32 / fp16 / bf16, no rows, or
+    ``in_features`` / ``nopairs`` outside the range include/fewbit_hipx.h states)"""
+    if dtype not in DTYPES:
+        return 0
+    return lib().fewbit_hipx_crs_workspace(DTYPES[dtype], rows, in_features, nopairs)
+
+
+def _crs_seed(seed):
+    """-> (value, device word pointer, tensors to keep on the device of the call)"""
+    if isinstance(seed, torch.Tensor):
+        _seed_word(seed, 'seed')
+        return 0, seed.data_ptr(), (seed, )
+    return seed & 0xffffffffffffffff, 0, ()
+
+
+def _crs_call(name: str, src: torch.Tensor, seed, in_features: int, nopairs: int, shape, out: Optional[torch.Tensor], workspace: Optional[torch.Tensor],
+              launch) -> torch.Tensor:
+    rows = src.shape[0]
+    need = crs_workspace_bytes(rows, in_features, nopairs, src.dtype)
+    if need == 0:
+        raise FewbitHipError(f'{name}: no kernel for {rows} rows, in_features = {in_features}, nopairs = {nopairs} of {src.dtype}')
+    value, word, others = _crs_seed(seed)
+    with _on(src.device):
+        out, workspace = _buffers(src, others, out, shape, src.dtype, f'{" x ".join(map(str, shape))} tensor of the dtype of the input', workspace, need)
+        _check(launch(DTYPES[src.dtype], src.data_ptr(), value, word, out.data_ptr(), *_span(workspace), _stream(None, src.device)))
+    return out
+
+
+def crs_gather(x: torch.Tensor, seed, nopairs: int, cap: Optional[int] = None, out: Optional[torch.Tensor] = None,
+               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``(x.float()[:, cols] * scale).to(x.dtype)`` padded with zero columns to ``cap`` columns, for the columns of ``seed`` (``crs_columns``;
+    ``scale = count * in_features / nopairs``) and a 2-D ``x`` (rows x in_features, unit stride along the features).  ``seed``: an int -- then
+    ``cap`` defaults to ``m``, the number of distinct columns, evaluated on the host -- or a one-element int64 tensor on the device of ``x``
+    that is read when the kernel runs (``cabi.next_sketch_seed``; a launch recorded into a hipGraph draws fresh columns on every replay) --
+    then ``cap`` defaults to ``min(nopairs, in_features)``, which no draw exceeds.  Nothing is read back from the device."""
+    rows, in_features, ld = _matrix(x)
+    if cap is None:
+        cap = min(nopairs, in_features) if isinstance(seed, torch.Tensor) else crs_count(seed, in_features, nopairs)
+    return _crs_call('crs_gather', x, seed, in_features, nopairs, (rows, cap), out, workspace, lambda dt, xp, value, word, op, wp, wb, st: lib().fewbit_hipx_crs_gather(
+        dt, xp, rows, in_features, ld, value, word, nopairs, cap, op, wp, wb, st))
+
+
+def crs_scatter(t: torch.Tensor, seed, in_features: int, nopairs: int, out: Optional[torch.Tensor] = None,
+                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The ``out_features x in_features`` weight gradient of the columns of ``seed`` from ``t`` (``out_features x cap``, contiguous; the product
+    ``G^T kept`` of a ``crs_gather`` result of the same ``seed`` and ``nopairs``): column ``cols[j]`` is ``t[:, j]``, every other entry is +0.
+    All of the result is written in one pass."""
+    if t.dim() != 2 or not t.is_contiguous():
+        raise FewbitHipError('t must be a contiguous 2-D tensor')
+    _matrix(t)
+    out_features, cap = t.shape
+    return _crs_call('crs_scatter', t, seed, in_features, nopairs, (out_features, in_features), out, workspace,
+                     lambda dt, tp, value, word, op, wp, wb, st: lib().fewbit_hipx_crs_scatter(dt, tp, out_features, cap, value, word, in_features, nopairs, op, wp, wb, st))

@@ -48,6 +48,13 @@ gradient ``Gr^T Xr + Gi^T Xi`` is two accumulating GEMMs in the planes' dtype.  
 sampled rows are, like ``S``, a function of the call's 64-bit seed that the kernel evaluates itself (``fewbit_hip_sampled_dct_seeded``,
 ``fewbit_hipx_sampled_dft_seeded``; ``cabi.sampled_rows(seed, rows, p)`` is the same function on the host): no ``randint`` launch, no saved
 RNG state, and the layer can be captured into a hipGraph.  ``use_native_sketch(False)`` selects torch.fft + randint.  SURVEY section 8f, row 4.
+
+Column sampling: ``linear_crs`` / ``LinearCRS`` on fp32 / fp16 / bf16 GPU tensors follows the same contract on the kernels of
+``fewbit_amd/csrc/fewbit_crs.hip`` (companion library: ``fewbit_hipx_crs_gather``, ``fewbit_hipx_crs_scatter``): the drawn columns are a function
+of the call's seed (``cabi_x.crs_columns(seed, in_features, nopairs)`` on the host), forward is one gather-and-scale call, backward one GEMM and
+one call that writes the whole weight gradient; the layer keeps its ``rows x m`` projection and one integer, reads nothing back and can be
+captured into a hipGraph (a captured layer keeps ``min(nopairs, in_features)`` columns, the unused ones zero).  ``use_native_sketch(False)``
+selects randint + bincount + nonzero, with its read-back.
 """
 import contextlib
 import os
@@ -109,8 +116,9 @@ _NATIVE_SKETCH = os.environ.get('FEWBIT_SKETCH_NATIVE', '1') not in ('0', 'no', 
 
 def use_native_sketch(on: Optional[bool] = None) -> bool:
     """Query / set whether GPU tensors take this package's kernels -- the Philox-in-register MFMA kernel for 'gaussian' /
-    'rademacher' sketches, the sampled-transform kernel pairs for 'dct' and 'dft' (default) -- or the PyTorch formulation
-    (randn / randint + matmul, torch.fft).  Returns the previous setting."""
+    'rademacher' sketches, the sampled-transform kernel pairs for 'dct' and 'dft', the column-sampling kernels of ``linear_crs`` / ``LinearCRS``
+    (default) -- or the PyTorch formulation (randn / randint + matmul, torch.fft; for ``linear_crs`` randint + bincount + nonzero, which
+    reads back from the device).  Returns the previous setting."""
     global _NATIVE_SKETCH
     prev = _NATIVE_SKETCH
     if on is not None:
@@ -419,33 +427,73 @@ def linear_grp(input: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
 linear_randomized = linear_grp
 
 
+_CRS_SHAPES = {}
+
+
+def _native_crs_applies(flat: torch.Tensor, weight: torch.Tensor, nopairs: int) -> bool:
+    """The gfx950 column-sampling kernels (fewbit_amd/csrc/fewbit_crs.hip) take fp32 / fp16 / bf16 GPU tensors of the shapes the companion
+    library says it has a kernel for (its workspace query is non-zero; asked once per shape); everything else keeps the PyTorch formulation."""
+    if not (_NATIVE_SKETCH and flat.device.type == 'cuda' and flat.dtype in (torch.float32, torch.float16, torch.bfloat16)
+            and weight.dtype == flat.dtype and weight.device == flat.device):
+        return False
+    key = (flat.dtype, flat.shape[0], flat.shape[1], nopairs)
+    ok = _CRS_SHAPES.get(key)
+    if ok is None:
+        from . import cabi_x
+        ok = _CRS_SHAPES[key] = cabi_x.crs_workspace_bytes(flat.shape[0], flat.shape[1], nopairs, flat.dtype) != 0
+    return ok
+
+
 class _LinearCRS(torch.autograd.Function):
     """Column sampling of the weight gradient: ``nopairs`` draws (with replacement) from the ``in_features`` columns;
     only the drawn columns of the input are kept, each scaled by ``count / (nopairs / in_features)`` so that the
-    estimate is unbiased (behaviour of fewbit/functional/linear.py:28-62)."""
+    estimate is unbiased (behaviour of fewbit/functional/linear.py:28-62).
+
+    On the GPU (fp32 / fp16 / bf16, ``use_native_sketch()`` on) the drawn columns are, like the sampled rows of 'dct' / 'dft', a function of
+    the call's 64-bit seed (``_sketch_seed``: the host default generator, so ``torch.manual_seed`` reproduces a run) that the kernels of
+    ``fewbit_amd/csrc/fewbit_crs.hip`` evaluate themselves (``cabi_x.crs_columns`` is the same function on the host): forward is ONE call that
+    gathers and scales the drawn columns (the scale is applied in fp32, the result rounded once to the layer's dtype), backward is the
+    library GEMM ``G^T kept`` and ONE call that writes all of ``dL/dW``.  Kept for backward: the ``rows x m`` projection (``m`` distinct
+    columns, known from the host evaluation of the seed) and one integer -- no column list, no randint / bincount / nonzero, no read-back
+    and no stream synchronisation.  While the stream is being captured into a hipGraph the seed is a device word the host cannot evaluate:
+    the projection then has ``cap = min(nopairs, in_features)`` columns, the ``cap - m`` unused ones exactly zero, and every replay draws
+    fresh columns.  Host tensors, float64, ``use_native_sketch(False)`` and shapes the library has no kernel for take the PyTorch
+    formulation below, whose ``nonzero`` reads the number of hit columns back from the device (and cannot be captured)."""
 
     @staticmethod
     def forward(ctx, input, weight, bias, nopairs: int):
         in_features = weight.shape[1]
+        ctx.has_bias = bias is not None
+        ctx.native_seed = None
+        flat = input.detach().reshape(-1, in_features)
+        if _native_crs_applies(flat, weight, nopairs):
+            from . import cabi_x
+            ctx.native_seed, ctx.nopairs = _sketch_seed(None, flat.device), nopairs
+            ctx.save_for_backward(cabi_x.crs_gather(_unit_stride(flat), ctx.native_seed, nopairs), weight)
+            return F.linear(input, weight, bias)
         draws = torch.randint(0, in_features, (nopairs, ), device=input.device)
         counts = torch.bincount(draws, minlength=in_features)
         scale = counts.to(input.dtype) * (in_features / nopairs)
-        flat = input.detach().reshape(-1, in_features)
         # a dense (rows x in_features) product with a mostly-zero scale would save nothing: keep the hit columns only.
-        # nonzero() has a data-dependent size and therefore reads back from the device -- inherent to this estimator.
+        # nonzero() has a data-dependent size and therefore reads back from the device -- the price of drawing the columns on the device with
+        # torch's generator; the kernels above avoid it by making the columns a function of a seed that the host can evaluate as well.
         cols = torch.nonzero(counts, as_tuple=True)[0]
         ctx.save_for_backward(flat[:, cols] * scale[cols], weight, cols)
-        ctx.has_bias = bias is not None
         return F.linear(input, weight, bias)
 
     @staticmethod
     def backward(ctx, grad_output):
-        kept, weight, cols = ctx.saved_tensors
+        kept, weight = ctx.saved_tensors[:2]
         grad_input = grad_weight = grad_bias = None
         if ctx.needs_input_grad[0]:
             grad_input = grad_output @ weight
         flat = grad_output.reshape(-1, grad_output.shape[-1])
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and ctx.native_seed is not None:
+            from . import cabi_x
+            t = (flat.T @ kept).to(weight.dtype)
+            grad_weight = cabi_x.crs_scatter(t.contiguous(), ctx.native_seed, weight.shape[1], ctx.nopairs)
+        elif ctx.needs_input_grad[1]:
+            cols = ctx.saved_tensors[2]
             grad_weight = torch.zeros_like(weight)
             grad_weight[:, cols] = (flat.T @ kept).to(weight.dtype)
         if ctx.has_bias and ctx.needs_input_grad[2]:

@@ -23,10 +23,15 @@ extern "C" {
 
 /* Version history.  Bindings check it and refuse an older library by name.
  *   1: fewbit_hipx_sampled_dft, _seeded, _workspace (the reference's 'dft' estimator).
- * What is declared below is what a binding needs (tests/test_dft_host.py pins the exported symbol list). */
+ * What is declared below is what a binding needs (tests/test_dft_host.py pins the exported symbol list).
+ * Additions that leave every version-1 entry point as it was do not move the version; they move the REVISION:
+ *   revision 1: the version-1 library as first released (it has no fewbit_hipx_revision symbol).
+ *   revision 2: fewbit_hipx_revision; the column sampling of LinearCRS: fewbit_hipx_crs_columns, _crs_workspace, _crs_gather, _crs_scatter. */
 #define FEWBIT_HIPX_ABI_VERSION 1
+#define FEWBIT_HIPX_REVISION 2
 
 int fewbit_hipx_abi_version(void);
+int fewbit_hipx_revision(void);
 const char *fewbit_hipx_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------------------------
@@ -56,6 +61,48 @@ int fewbit_hipx_sampled_dft(int dtype, const void *m, size_t rows, size_t featur
  * replay, fed by fewbit_hip_sketch_next_seed. */
 int fewbit_hipx_sampled_dft_seeded(int dtype, const void *m, size_t rows, size_t features, size_t ld, uint64_t seed, const uint64_t *seed_device,
                                    size_t proj, double scale, int out_dtype, void *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Column sampling of the weight gradient (LinearCRS; the reference's linear_crs, fewbit/functional/linear.py:27-43): `nopairs`
+ * draws with replacement from the in_features columns of the layer's input; the drawn columns are kept, each scaled by
+ * count * in_features / nopairs, which makes G^T kept an unbiased estimate of the drawn columns of dL/dW.
+ *
+ * The columns of a seed.  The draws are a pure function of (seed, in_features, nopairs):
+ *     block q = Philox4x32-10(counter = (q, 0, 0, 4), key = (low 32 bits of seed, high 32 bits of seed))      (fewbit_philox.h;
+ *               counter word 3 = 4 is this domain's own: 0 and 2 are the dense sketches', 3 the sampled rows')
+ *     draw i  = (uint64(word i % 4 of block i / 4) * in_features) >> 32,    i = 0 .. nopairs - 1
+ *     cols[0 .. m)  the distinct drawn columns in ASCENDING order,  count[j] = how often cols[j] was drawn  (sum of count = nopairs)
+ *     scale[j] = (float)((double)count[j] * in_features / nopairs)
+ *     pos[c]   = j if cols[j] == c, else -1,    c = 0 .. in_features - 1
+ * Supported: in_features in [1, 2^20], nopairs in [1, 2^22], dtype F32 / F16 / BF16, at least one row; anything else has no kernel
+ * (the workspace query returns 0, the entry points FEWBIT_ERR_UNSUPPORTED or FEWBIT_ERR_INVALID_ARGUMENT).
+ *
+ * fewbit_hipx_crs_columns evaluates the definition on the HOST, with HOST pointers (the counterpart of fewbit_hip_sampled_rows): *m
+ * is set, and with cols_host != NULL (then count_host != NULL too, room for min(nopairs, in_features) entries each) the columns and
+ * their counts are written.  No device is touched.
+ *
+ * fewbit_hipx_crs_workspace: bytes of scratch of the two calls below (16-byte aligned; 16 + 4 in_features + 8 min(nopairs, in_features),
+ * each part rounded up to 16), 0 = no kernel.  The kernels leave m, pos, cols and scale there; the layout is private.
+ *
+ * fewbit_hipx_crs_gather: out[r][j] = round_to_dtype(float(x[r][cols[j]]) * scale[j]) for j < m and exactly 0 for m <= j < cap.
+ *   x    rows x in_features, row-major with leading dimension `ld` (elements)
+ *   seed, seed_device   as in fewbit_hipx_sampled_dft_seeded: seed_device != NULL is an 8-byte aligned DEVICE word read when the
+ *        kernel runs (`seed` is ignored), so a launch recorded in a hipGraph draws fresh columns on every replay
+ *   cap  columns of `out`, 1 <= cap <= min(nopairs, in_features).  A caller that knows m (from fewbit_hipx_crs_columns) passes it;
+ *        one that cannot (the seed is a device word) passes min(nopairs, in_features) >= m.  m is never read back.  (cap < m: only
+ *        the first cap columns are written.)
+ *   out  rows x cap, contiguous, fully written
+ * fewbit_hipx_crs_scatter: gw[o][c] = pos[c] >= 0 ? t[o][pos[c]] : +0 -- ALL of gw (out_features x in_features, contiguous) in one
+ * pass, the bits of t copied.  t: the out_features x cap product G^T kept, contiguous; (seed, in_features, nopairs) those of the gather
+ * (columns at positions >= cap read as 0).
+ * Each call is two launches on `stream` (fewbit_amd/csrc/fewbit_crs.hip): one workgroup that evaluates the definition into the
+ * workspace, and the pass over the rows.  The same arguments give the same bits. */
+int fewbit_hipx_crs_columns(uint64_t seed, size_t in_features, size_t nopairs, int64_t *cols_host, int32_t *count_host, size_t *m);
+size_t fewbit_hipx_crs_workspace(int dtype, size_t rows, size_t in_features, size_t nopairs);
+int fewbit_hipx_crs_gather(int dtype, const void *x, size_t rows, size_t in_features, size_t ld, uint64_t seed, const uint64_t *seed_device, size_t nopairs,
+                           size_t cap, void *out, void *workspace, size_t workspace_bytes, void *stream);
+int fewbit_hipx_crs_scatter(int dtype, const void *t, size_t out_features, size_t cap, uint64_t seed, const uint64_t *seed_device, size_t in_features,
+                            size_t nopairs, void *gw, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

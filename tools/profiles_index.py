@@ -40,6 +40,7 @@ ROWS = [
     ('r06_dct_serve_lanes.txt', 'pass B writing a sampled row with 16 / 8 / 4 lanes: 4 shipped (pass B -8 %)', f'{D} 7.5'),
     ('r06_dct_rounds.txt', 'both DCT passes against the number of workgroups (features swept): a fixed 7-9 us plus 7.5 ns per workgroup', f'{D} 7.5'),
     ('r07_transform_columns.txt', 'both sampled-transform kernel pairs per feature column on structured inputs: kernel / fp32 reference error ratios (tests/test_gpu_transform_columns.py)', f'{D} 6'),
+    ('crs_bench.json', 'tools/sketch_bench.py (CRS=1): LinearCRS forward extra and weight-gradient part on the kernels against the torch formulation; rocprofv3 kernel times, gather byte-floor fraction', f'{E} 8.2'),
     ('r06_dct_stagger.txt|r06_dct_fused_upper_bound.txt|r06_dct_inter16.txt', 'DCT experiments not kept: staggered starts, both passes in one launch (timing only), a bf16 intermediate', 'EXPERIMENTS.md'),
     ('r0?_roberta_table_*.json', "tools/roberta_bench.py --table: the reference README's RoBERTa table per dtype and estimator", f'{D} 7.4'),
     ('r0?_roberta_ab_fp32.txt|r0?_roberta_ab_bf16.txt|r0?_roberta_randomized_insitu*.json', 'the randomized RoBERTa step, arms interleaved in one process; its GPU time by kernel class', f'{D} 7.4'),

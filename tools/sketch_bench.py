@@ -57,7 +57,63 @@ def sampled_transforms(m, proj):
     return rec
 
 
+def crs_rows():
+    """LinearCRS at RoBERTa-base's layer shapes (nopairs = in_features / 2): what the layer adds to F.linear in forward (the columns of a seed,
+    the gather and the scaling) and the weight-gradient part of backward (G^T kept and the spread over dL/dW), on the gfx950 kernels and on
+    the PyTorch formulation (use_native_sketch(False): randint + bincount + nonzero + indexed gather / zeros_like + indexed assignment), in
+    one process.  byte floor of the gather: rows x in_features in + rows x m out."""
+    from fewbit_amd import cabi_x, linear
+    recs = []
+    for dtype, rows, in_features, out_features in ((torch.bfloat16, 16384, 768, 3072), (torch.bfloat16, 16384, 3072, 768), (torch.float32, 16384, 768, 3072)):
+        nopairs = in_features // 2
+        x = torch.randn(rows, in_features, device=DEV).to(dtype)
+        gy = torch.randn(rows, out_features, device=DEV).to(dtype)
+        w = torch.randn(out_features, in_features, device=DEV).to(dtype)
+        seed = 1234
+        m = cabi_x.crs_count(seed, in_features, nopairs)
+        rec = {'crs': True, 'dtype': str(dtype).split('.')[-1], 'rows': rows, 'in_features': in_features, 'out_features': out_features, 'nopairs': nopairs,
+               'm': m, 'gather_byte_floor_bytes': rows * (in_features + m) * x.element_size()}
+        rec['gather_byte_floor_us_at_8TBs'] = round(rec['gather_byte_floor_bytes'] / 8e6, 2)
+
+        def native_forward():
+            return cabi_x.crs_gather(x, linear._draw_seed(None), nopairs)
+
+        def torch_forward():
+            draws = torch.randint(0, in_features, (nopairs, ), device=DEV)
+            counts = torch.bincount(draws, minlength=in_features)
+            scale = counts.to(dtype) * (in_features / nopairs)
+            cols = torch.nonzero(counts, as_tuple=True)[0]
+            return x[:, cols] * scale[cols], cols
+
+        kept = cabi_x.crs_gather(x, seed, nopairs)
+        kept_t, cols_t = torch_forward()
+
+        def native_backward():
+            return cabi_x.crs_scatter(gy.T @ kept, seed, in_features, nopairs)
+
+        def torch_backward():
+            gw = torch.zeros_like(w)
+            gw[:, cols_t] = gy.T @ kept_t
+            return gw
+
+        # alternating, so that both see the same state of the machine
+        for name, native, formulation in (('forward_extra', native_forward, torch_forward), ('weight_gradient', native_backward, torch_backward)):
+            a = [timed(native, reps=50), timed(formulation, reps=50), timed(native, reps=50), timed(formulation, reps=50)]
+            rec[name] = {'native_us': round(min(a[0], a[2]), 1), 'torch_us': round(min(a[1], a[3]), 1), 'native_runs_us': [round(a[0], 1), round(a[2], 1)],
+                         'torch_runs_us': [round(a[1], 1), round(a[3], 1)]}
+            rec[name]['speedup'] = round(rec[name]['torch_us'] / rec[name]['native_us'], 2)
+        rec['weight_gradient']['gemm_only_us'] = round(timed(lambda: gy.T @ kept, reps=50), 1)
+        print(json.dumps(rec), flush=True)
+        recs.append(rec)
+        del x, gy, w, kept, kept_t
+        torch.cuda.empty_cache()
+    return recs
+
+
 def main():
+    if os.environ.get('CRS'):                   # CRS=1: the LinearCRS rows only, one JSON line each on stdout
+        crs_rows()
+        return
     out = []
     slices = [int(s) for s in os.environ.get('SLICES', '-1').split(',')]
     shapes = [(16384, 768, 1638), (16384, 3072, 1638), (16384, 768, 3276), (16384, 3072, 3276), (16384, 3072, 8192), (65536, 4096, 4096)]
@@ -107,6 +163,7 @@ def main():
             out.append(rec)
             del m, S, mo
             torch.cuda.empty_cache()
+    out.extend(crs_rows())
     os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
     json.dump(out, open(os.path.join(ROOT, 'gpurun_out', 'sketch_bench.json'), 'w'), indent=1)
 
