@@ -508,7 +508,8 @@ def tune_sketch_materialise(materialise: int) -> None:
 
 # ---- sampled cosine transform (fewbit_amd/csrc/fewbit_dct.hip): out = scale * dct(m, dim=0, norm='ortho')[idx] -------------------
 # the row counts of the sampled transforms (fewbit_fft4.h: split_rows); 'dft' (cabi_x) has the same
-SAMPLED_ROWS = '2^k in [256, 262144], 3 x 2^k in [768, 49152] or 5 x 2^k in [1280, 40960]'
+SAMPLED_ROWS = ('2^k in [256, 262144], 3 x 2^k in [768, 49152], 5 x 2^k in [1280, 40960], 7 x 2^k in [3584, 57344], 9 x 2^k in [2304, 36864] '
+                'or 15 x 2^k in [3840, 30720]')
 
 
 def sampled_dct_workspace_bytes(rows: int, features: int, proj: int, dtype: torch.dtype = torch.bfloat16) -> int:

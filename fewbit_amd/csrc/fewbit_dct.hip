@@ -1,7 +1,7 @@
 // fewbit_dct.hip -- the sampled cosine transform of the randomized linear layers (the reference's 'dct' estimator)
 // on gfx950:
 //
-//     out[j][:] = scale * DCT-II_ortho(M, along the rows)[idx[j]][:]        M: rows x features (bf16 / fp16 / fp32), rows = 2^m, 3 x 2^m or 5 x 2^m
+//     out[j][:] = scale * DCT-II_ortho(M, along the rows)[idx[j]][:]        M: rows x features (bf16 / fp16 / fp32), rows = 2^m or 3, 5, 7, 9, 15 x 2^m
 //
 // What it replaces in the reference (skolai/fewbit): `dct(input_view, dim=0, norm='ortho')[proj, ...]` in LinearGRPFunc.forward
 // (fewbit/functional/linear.py:113-122) and the same on the gradient in .backward (:174-183); dct = fewbit/fft.py:10-43 (shuffle,
@@ -18,7 +18,7 @@
 //      The pair contract: the rounding error of column c scales with the RMS of the pair (c, c ^ 1), not with its own, and a NaN or Inf
 //      in one column makes its partner non-finite too; other columns, the padding behind ld and the memory around out are untouched.
 //      torch.fft (the reference, the layer's fallback) keeps every column apart (tests/test_gpu_transform_columns.py).
-//   3. Four-step DFT, N = N1 x N2 (each 16 .. 512; 16384 = 128 x 128, 262144 = 512 x 512; 12288 = 128 x 96: a factor 3 goes to N2), n = N2 n1 + n2, k = k1 + N1 k2:
+//   3. Four-step DFT, N = N1 x N2 (each 16 .. 512; 16384 = 128 x 128, 262144 = 512 x 512; 12288 = 128 x 96: the odd factor 3, 5, 7, 9 or 15 goes to N2), n = N2 n1 + n2, k = k1 + N1 k2:
 //          pass A   for every n2:  A[k1][n2] = W_N^{n2 k1} * sum_{n1} z[N2 n1 + n2] W_N1^{n1 k1}        (length-N1 DFTs over rows N2 apart)
 //          pass B   for every k1:  Z[k1 + N1 k2] = sum_{n2} A[k1][n2] W_N2^{n2 k2}                       (length-N2 DFTs, contiguous)
 //      Pass B never writes Z: the workgroup that owns the residues k1 and N1 - k1 holds Z[k] AND Z[N-k] for every k of those
@@ -30,7 +30,7 @@
 //               Lanes run along the 32 entries of a point: every LDS access of a half-wave is 256 contiguous bytes (all 64 banks once,
 //               ds_read/write_b64: conflict-free), every twiddle is half-wave-uniform (an LDS broadcast).
 //   FFT         in place, decimation in frequency, TWO stages at L = 128 (radix 16 then radix 8, each butterfly entirely in the
-//               registers of one thread; 64 = 8 x 8, 32 = 8 x 4, 16 = 16; 96 = 3 x 8 x 4, 192 = 3 x 8 x 8, 48 = 3 x 16), one barrier per stage; the result stands in digit-reversed
+//               registers of one thread; 64 = 8 x 8, 32 = 8 x 4, 16 = 16; 96 = 3 x 8 x 4, 192 = 3 x 8 x 8, 48 = 3 x 16, 112 = 7 x 16, 144 = 3 x 3 x 16, 240 = 3 x 5 x 16), one barrier per stage; the result stands in digit-reversed
 //               positions (pos_to_freq / freq_to_pos), which costs nothing: both passes address their outputs through the map.
 //   pass A      workgroup (b, t): the rows n = N2 n1 + b of column tile t (32 complex columns = 64 features).  Loads N1 row segments
 //               (128 B of bf16: full cache lines, 16 B per lane, issued back to back), converts to fp32, transforms along n1,
@@ -277,7 +277,7 @@ struct Dct {
     static float factor(double scale, size_t) { return static_cast<float>(scale); }
 };
 
-// The file is compiled as three translation units in parallel, one per dtype (-DFEWBIT_DCT_TU=0 / 1 / 2 = FEWBIT_F32 / F16 / BF16: 54
+// The file is compiled as three translation units in parallel, one per dtype (-DFEWBIT_DCT_TU=0 / 1 / 2 = FEWBIT_F32 / F16 / BF16: 114
 // kernels each; the C entry points with unit 0), and linked into the one library -- 50 s instead of 2.5 min; without the define everything
 // is one unit (make variant).
 #ifndef FEWBIT_DCT_TU

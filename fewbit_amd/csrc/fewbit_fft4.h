@@ -33,7 +33,7 @@ __device__ __forceinline__ f32x2 cmul(f32x2 a, f32x2 b) {
     return f32x2{__builtin_fmaf(a.x, b.x, -(a.y * b.y)), __builtin_fmaf(a.x, b.y, a.y * b.x)};
 }
 __device__ __forceinline__ f32x2 mul_mi(f32x2 a) { return f32x2{a.y, -a.x}; }                                   // a * (-i)
-// e^{-2 pi i num / den}: den a power of two (num / den is exact in fp32), or 3 x / 5 x a power of two (the angle in double, then rounded;
+// e^{-2 pi i num / den}: den a power of two (num / den is exact in fp32), or 3, 5, 7, 9, 15 x a power of two (the angle in double, then rounded;
 // `den` is a template constant at every call site: the branch folds)
 __device__ __forceinline__ f32x2 unit(int num, int den) {
     if ((den & (den - 1)) != 0) {
@@ -84,6 +84,21 @@ template <int R> __device__ __forceinline__ void dft(f32x2 (&x)[R]) {
         x[4] = m1 - n1;
         x[2] = m2 + n2;
         x[3] = m2 - n2;
+    } else if constexpr (R == 7) {
+        // W7^j = cos(2 pi j / 7) - i sin(2 pi j / 7), a_j = x_j + x_{7-j}, b_j = x_j - x_{7-j}:  y_q, y_{7-q} = m_q -+ i n_q,
+        // m_q = x0 + sum_j cos(2 pi j q / 7) a_j,  n_q = sum_j sin(2 pi j q / 7) b_j
+        constexpr float c1 = 0.62348980185873353f, c2 = -0.22252093395631440f, c3 = -0.90096886790241913f;
+        constexpr float s1 = 0.78183148246802981f, s2 = 0.97492791218182361f, s3 = 0.43388373911755812f;
+        const f32x2 a1 = x[1] + x[6], a2 = x[2] + x[5], a3 = x[3] + x[4], b1 = x[1] - x[6], b2 = x[2] - x[5], b3 = x[3] - x[4];
+        const f32x2 m1 = x[0] + a1 * c1 + a2 * c2 + a3 * c3, m2 = x[0] + a1 * c2 + a2 * c3 + a3 * c1, m3 = x[0] + a1 * c3 + a2 * c1 + a3 * c2;
+        const f32x2 n1 = mul_mi(b1 * s1 + b2 * s2 + b3 * s3), n2 = mul_mi(b1 * s2 - b2 * s3 - b3 * s1), n3 = mul_mi(b1 * s3 - b2 * s1 + b3 * s2);
+        x[0] = x[0] + a1 + a2 + a3;
+        x[1] = m1 + n1;
+        x[6] = m1 - n1;
+        x[2] = m2 + n2;
+        x[5] = m2 - n2;
+        x[3] = m3 + n3;
+        x[4] = m3 - n3;
     } else if constexpr (R == 8) {
         // j = 2a + b, q = p + 4 q':  y[p + 4 q'] = sum_b W8^{bp} (-1)^{b q'} sum_a x[2a + b] W4^{ap}
         dft4(x[0], x[2], x[4], x[6]);
@@ -99,7 +114,7 @@ template <int R> __device__ __forceinline__ void dft(f32x2 (&x)[R]) {
         x[2] = e2 + t2; x[6] = e2 - t2;
         x[3] = e3 + t3; x[7] = e3 - t3;
     } else {
-        static_assert(R == 16, "radix 2, 3, 4, 5, 8 or 16");
+        static_assert(R == 16, "radix 2, 3, 4, 5, 7, 8 or 16");
         // j = 4a + b, q = p + 4 q':  y[p + 4 q'] = sum_b W16^{bp} W4^{b q'} sum_a x[4a + b] W4^{ap}
         dft4(x[0], x[4], x[8], x[12]);
         dft4(x[1], x[5], x[9], x[13]);
@@ -132,9 +147,10 @@ template <int R> __device__ __forceinline__ void dft(f32x2 (&x)[R]) {
 }
 
 // radix of the first stage of a block of length `len`: 256 = 16 x 16, 128 = 16 x 8, 64 = 8 x 8, 32 = 8 x 4, 16 = 16; a factor 3
-// (48 = 3 x 16, 96 = 3 x 8 x 4, 192 = 3 x 8 x 8) or 5 (80 = 5 x 16, 160 = 5 x 8 x 4) goes first
+// (48 = 3 x 16, 96 = 3 x 8 x 4, 192 = 3 x 8 x 8), 5 (80 = 5 x 16, 160 = 5 x 8 x 4) or 7 (112 = 7 x 16, 224 = 7 x 8 x 4) goes first, threes
+// before a five (144 = 3 x 3 x 16, 288 = 3 x 3 x 8 x 4, 240 = 3 x 5 x 16)
 __host__ __device__ constexpr int first_radix(int len) {
-    return len % 3 == 0 ? 3 : len % 5 == 0 ? 5 : len >= 128 ? 16 : len == 64 ? 8 : len == 32 ? 8 : len == 16 ? 16 : len == 8 ? 8 : len == 4 ? 4 : 2;
+    return len % 3 == 0 ? 3 : len % 5 == 0 ? 5 : len % 7 == 0 ? 7 : len >= 128 ? 16 : len == 64 ? 8 : len == 32 ? 8 : len == 16 ? 16 : len == 8 ? 8 : len == 4 ? 4 : 2;
 }
 
 // position P (after the in-place DIF stages) -> frequency k.  Stage i with radix r_i on blocks of length L_i leaves digit q_i
@@ -254,13 +270,13 @@ __device__ __forceinline__ f32x2 table_unit(const f32x2 *fine, const f32x2 *coar
 // Where they come from.  RowsInMemory: the caller's int64 array.  RowsOfSeed: a FUNCTION of a 64-bit seed,
 //     rows = 2^k:      idx[j] = 16-bit half j % 8 of the 128 bits of Philox4x32-10(counter = (j / 8, 0, 0, 3), key = seed)  mod  rows
 //                      (half h = bits 16 (h % 2) .. 16 (h % 2) + 15 of word h / 2)
-//     rows = 3 x 2^k:  idx[j] = (word j % 4 of Philox4x32-10(counter = (j / 4, 0, 0, 3), key = seed)  x  rows)  >>  32
+//     any other rows:  idx[j] = (word j % 4 of Philox4x32-10(counter = (j / 4, 0, 0, 3), key = seed)  x  rows)  >>  32
 // (uniform -- in the second case up to rows / 2^32 --, with replacement, like the reference's T.multinomial of equal weights): no array, no
 // launch that draws one, nothing to keep for backward but the seed -- and, with the seed read from device memory, a recorded launch draws
 // fresh rows on every replay (fewbit_sketch.hip, same scheme).
 constexpr uint32_t kRowsDomain = 3u;        // counter word 3 (0 and 2: the dense sketches)
 __host__ __device__ constexpr bool power_of_two(size_t n) { return (n & (n - 1)) == 0; }
-// rows = 2^k <= 2^16: eight 16-bit halves per Philox call; any other row count (3 x 2^k, 5 x 2^k, 2^17, 2^18): four 32-bit words, word x rows >> 32
+// rows = 2^k <= 2^16: eight 16-bit halves per Philox call; any other row count (3, 5, 7, 9, 15 x 2^k, 2^17, 2^18): four 32-bit words, word x rows >> 32
 __host__ __device__ constexpr bool draws_halves(size_t n) { return power_of_two(n) && n <= 65536; }
 __host__ __device__ constexpr int per_draw(bool halves) { return halves ? 8 : 4; }      // row numbers per Philox call
 // row number h of one Philox call (HALVES: not yet reduced mod rows -- the caller masks)
@@ -359,24 +375,39 @@ __device__ __forceinline__ void sort_rows(ROWS rows, size_t proj, int *__restric
 // ---- host side --------------------------------------------------------------------------------------------------------------
 struct Split { int n1, n2; };
 // rows = N1 x N2.  2^8 .. 2^18: 16 <= N2 <= N1 <= 512, both powers of two (2^17 = 512 x 256 and 2^18 = 512 x 512: 128 KiB tiles, one
-// workgroup per CU).  3 x 2^8 .. 3 x 2^14 (768 .. 49152) and 5 x 2^8 .. 5 x 2^13 (1280 .. 40960): the odd factor goes to the second pass,
-// N2 = 48 / 96 / 192 or 80 / 160 (N1 stays a power of two: residues and digit maps of pass A, the k % N1 of pass B)
+// workgroup per CU).  3 x 2^8 .. 3 x 2^14 (768 .. 49152), 5 x 2^8 .. 5 x 2^13 (1280 .. 40960), 7 x 2^9 .. 7 x 2^13 (3584 .. 57344),
+// 9 x 2^8 .. 9 x 2^12 (2304 .. 36864) and 15 x 2^8 .. 15 x 2^11 (3840 .. 30720): the odd factor goes to the second pass, N2 = 48 / 96 /
+// 192, 80 / 160, 112 / 224, 144 / 288 or 240 (N1 stays a power of two: residues and digit maps of pass A, the k % N1 of pass B).  Pass
+// B's tile is 256 N2 bytes + tables: at most 78 KiB (N2 = 288), two workgroups in the 160 KiB of a CU
+struct RowFamily { int odd, low, high, n1[7]; };       // rows = odd x 2^bits, low <= bits <= high; n1[bits - low]
 inline bool split_rows(size_t rows, Split &s) {
     if (rows < 256 || rows > 262144) return false;
-    const bool three = rows % 3 == 0, five = !three && rows % 5 == 0;
-    const size_t two = three ? rows / 3 : five ? rows / 5 : rows;
-    if (!power_of_two(two) || (three && (two < 256 || two > 16384)) || (five && (two < 256 || two > 8192))) return false;
+    // N1 grows with the rows up to 128 (four pass-A workgroups per CU) before N2 doubles, and reaches 256 last:
+    //  3 x 2^bits, bits = 8 .. 14:  16 x 48, 32 x 48, 32 x 96, 64 x 96, 128 x 96, 128 x 192, 256 x 192
+    //  5 x 2^bits, bits = 8 .. 13:  16 x 80, 32 x 80, 64 x 80, 64 x 160, 128 x 160, 256 x 160
+    //  7 x 2^bits, bits = 9 .. 13:  32 x 112 (3584), 64 x 112 (7168), 128 x 112 (14336), 128 x 224 (28672), 256 x 224 (57344)
+    //  9 x 2^bits, bits = 8 .. 12:  16 x 144 (2304), 32 x 144 (4608), 64 x 144 (9216), 128 x 144 (18432), 128 x 288 (36864)
+    // 15 x 2^bits, bits = 8 .. 11:  16 x 240 (3840), 32 x 240 (7680), 64 x 240 (15360), 128 x 240 (30720)
+    // (15 and 9 before 5 and 3: a multiple of 15 is one of 3 and of 5)
+    static const RowFamily families[5] = {{15, 8, 11, {16, 32, 64, 128}},
+                                          {9, 8, 12, {16, 32, 64, 128, 128}},
+                                          {7, 9, 13, {32, 64, 128, 128, 256}},
+                                          {5, 8, 13, {16, 32, 64, 64, 128, 256}},
+                                          {3, 8, 14, {16, 32, 32, 64, 128, 128, 256}}};
+    const RowFamily *family = nullptr;
+    for (const RowFamily &f : families)
+        if (family == nullptr && rows % static_cast<size_t>(f.odd) == 0) family = &f;
+    const size_t two = family != nullptr ? rows / static_cast<size_t>(family->odd) : rows;
+    if (!power_of_two(two)) return false;
     int bits = 0;
     while ((static_cast<size_t>(1) << bits) < two) ++bits;
-    if (!three && !five) {
+    if (family == nullptr) {
         s.n1 = 1 << ((bits + 1) / 2);
         s.n2 = 1 << (bits / 2);
         return true;
     }
-    // 3 x 2^bits, bits = 8 .. 14:  16 x 48, 32 x 48, 32 x 96, 64 x 96, 128 x 96, 128 x 192, 256 x 192
-    // 5 x 2^bits, bits = 8 .. 13:  16 x 80, 32 x 80, 64 x 80, 64 x 160, 128 x 160, 256 x 160
-    static const int n1_of_3[7] = {16, 32, 32, 64, 128, 128, 256}, n1_of_5[6] = {16, 32, 64, 64, 128, 256};
-    s.n1 = three ? n1_of_3[bits - 8] : n1_of_5[bits - 8];
+    if (bits < family->low || bits > family->high) return false;
+    s.n1 = family->n1[bits - family->low];
     s.n2 = static_cast<int>(rows / static_cast<size_t>(s.n1));
     return true;
 }
@@ -384,9 +415,13 @@ inline bool split_rows(size_t rows, Split &s) {
 #define FB_FFT4_SPLITS(X)                                                                                                     \
     X(16, 16) X(32, 16) X(32, 32) X(64, 32) X(64, 64) X(128, 64) X(128, 128) X(256, 128) X(256, 256) X(512, 256) X(512, 512) \
     X(16, 48) X(32, 48) X(32, 96) X(64, 96) X(128, 96) X(128, 192) X(256, 192)                                                \
-    X(16, 80) X(32, 80) X(64, 80) X(64, 160) X(128, 160) X(256, 160)
+    X(16, 80) X(32, 80) X(64, 80) X(64, 160) X(128, 160) X(256, 160)                                                          \
+    X(32, 112) X(64, 112) X(128, 112) X(128, 224) X(256, 224)                                                                 \
+    X(16, 144) X(32, 144) X(64, 144) X(128, 144) X(128, 288)                                                                  \
+    X(16, 240) X(32, 240) X(64, 240) X(128, 240)
 // the row counts split_rows takes, as every refusal names them
-constexpr char kRowFamilies[] = "2^k (256 .. 262144), 3 x 2^k (768 .. 49152), 5 x 2^k (1280 .. 40960)";
+constexpr char kRowFamilies[] = "2^k (256 .. 262144), 3 x 2^k (768 .. 49152), 5 x 2^k (1280 .. 40960), 7 x 2^k (3584 .. 57344), 9 x 2^k (2304 .. 36864), "
+                              "15 x 2^k (3840 .. 30720)";
 
 inline size_t tiles_of(size_t features) { return (features + kFeatures - 1) / kFeatures; }
 inline size_t inter_bytes(size_t rows, size_t features) { return tiles_of(features) * rows * C * sizeof(f32x2); }

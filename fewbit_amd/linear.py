@@ -39,7 +39,8 @@ constructor / call signatures; the implementation is this repository's own:
   (``_sketch_seed``), so a replayed training step draws a fresh ``S`` each time -- a seed recorded by value would repeat
   one matrix for ever.  (The reference reads the generator state back in forward and cannot be captured.)
 
-The sampled transforms: 'dct' and 'dft' on 2-D GPU tensors of 2^8 .. 2^18, 3 x 2^8 .. 3 x 2^14 or 5 x 2^8 .. 5 x 2^13 rows run on this
+The sampled transforms: 'dct' and 'dft' on 2-D GPU tensors of 2^8 .. 2^18, 3 x 2^8 .. 3 x 2^14, 5 x 2^8 .. 5 x 2^13, 7 x 2^9 .. 7 x 2^13,
+9 x 2^8 .. 9 x 2^12 or 15 x 2^8 .. 15 x 2^11 rows (``cabi.SAMPLED_ROWS``) run on this
 package's kernel pairs (``fewbit_hip_sampled_dct``, ``fewbit_amd/csrc/fewbit_dct.hip``; ``fewbit_hipx_sampled_dft`` of the companion
 library, ``fewbit_amd/csrc/fewbit_dft.hip``): one four-step fp32 FFT in LDS that writes only the sampled rows -- the torch.fft formulation
 costs 110-120 x the bytes of the result, profiles/r06_sketch_bench.json.  'dft' keeps its real and imaginary parts as two planes in the
@@ -284,7 +285,7 @@ def _transform_rows(kind: str, rows: int) -> bool:
 def _native_transform_applies(kind: str, mat: torch.Tensor) -> bool:
     """The gfx950 sampled-transform kernel pairs (fewbit_amd/csrc/fewbit_dct.hip, fewbit_dft.hip) take 2-D fp32 / fp16 / bf16 GPU tensors
     of the row counts their library has a kernel for (_transform_rows; e.g. RoBERTa's 128 x 128 tokens = 16384, 32 sequences of 384 tokens
-    = 12288 = 3 x 2^12); everything else keeps the torch.fft formulation."""
+    = 12288 = 3 x 2^12, 28 sequences of 128 tokens = 3584 = 7 x 2^9); everything else keeps the torch.fft formulation."""
     return (_NATIVE_SKETCH and kind in ('dct', 'dft') and mat.device.type == 'cuda' and mat.dim() == 2
             and mat.dtype in (torch.float32, torch.float16, torch.bfloat16) and mat.shape[1] > 0 and _transform_rows(kind, mat.shape[0]))
 

@@ -40,7 +40,8 @@ const char *fewbit_hipx_last_error(void);
  *   = torch.fft.fft(m, dim=0, norm='ortho')[idx] * scale, the layer's torch.fft formulation, which builds the whole complex
  *     rows x features transform before it gathers the sampled rows
  *   m    rows x features, row-major with leading dimension `ld` (elements), dtype F32 / F16 / BF16; rows = 2^k in [256, 262144],
- *        3 x 2^k in [768, 49152] or 5 x 2^k in [1280, 40960], the row counts of fewbit_hip_sampled_dct (anything else:
+ *        3 x 2^k in [768, 49152], 5 x 2^k in [1280, 40960], 7 x 2^k in [3584, 57344], 9 x 2^k in [2304, 36864] or 15 x 2^k in
+ *        [3840, 30720], the row counts of fewbit_hip_sampled_dct (anything else:
  *        FEWBIT_ERR_UNSUPPORTED, and fewbit_hipx_sampled_dft_workspace returns 0); arithmetic and the intermediate are fp32
  *   idx  proj row numbers in [0, rows) as int64 in DEVICE memory (drawn with replacement: duplicates are served one by one; as in
  *        fewbit_hip_sampled_dct, the low 32 bits of an entry are reduced to [0, rows))

@@ -35,6 +35,7 @@ ROWS = [
     ('r06_dct_rows_big.txt', 'the kernel pair and the torch.fft formulation at 2^17 and 2^18 rows (512-point tiles)', f'{D} 7.3'),
     ('r06_dct_rows_5x.txt', 'the kernel pair and the torch.fft formulation at 5 x 2^k rows (1280 .. 40960)', f'{D} 7.3'),
     ('r06_dct_rows_3x.txt', 'the kernel pair and the torch.fft formulation at 3 x 2^k rows (768 .. 49152)', f'{D} 7.3'),
+    ('transform_rows_odd.txt', 'tools/transform_rows_bench.py: both kernel pairs at 7 x 2^k, 9 x 2^k and 15 x 2^k rows against the torch.fft formulation and against the next power of two', f'{E} 8.3'),
     ('r06_dct_variants.txt', 'the sampled-DCT variants measured in round 6, phases compiled out, per-workgroup timeline', f'{D} 7.5'),
     ('r06_dct_sorted_samples.txt', 'the samples sorted by residue class once, in pass A, instead of tested by every pass-B workgroup: pass B 17.3 -> 12.7 us', f'{D} 5'),
     ('r06_dct_serve_lanes.txt', 'pass B writing a sampled row with 16 / 8 / 4 lanes: 4 shipped (pass B -8 %)', f'{D} 7.5'),
