@@ -230,7 +230,7 @@ __global__ __launch_bounds__(kSpreadThreads) void crs_spread_kernel(const void *
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 inline int launch_prep(uint64_t seed, const uint64_t *seed_device, size_t in_features, size_t nopairs, const Workspace &ws, hipStream_t s) {
-    const Key key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)};
+    const Key key = sketch::key_of(seed);
     const Key *device = reinterpret_cast<const Key *>(seed_device);
     const uint32_t in = static_cast<uint32_t>(in_features), np = static_cast<uint32_t>(nopairs);
     if (in_features <= static_cast<size_t>(kLdsCols))
@@ -297,7 +297,7 @@ int fewbit_hipx_crs_columns(uint64_t seed, size_t in_features, size_t nopairs, i
         return fail(FEWBIT_ERR_UNSUPPORTED, "crs_columns: in_features = %zu, nopairs = %zu is out of range (1 .. %zu columns, 1 .. %zu pairs)", in_features, nopairs,
                     kMaxCols, kMaxPairs);
     if (m == nullptr || (cols_host == nullptr) != (count_host == nullptr)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "crs_columns: null pointer");
-    const Key key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)};
+    const Key key = sketch::key_of(seed);
     std::vector<int32_t> count(in_features, 0);
     for (size_t q = 0; 4 * q < nopairs; ++q) {
         uint32_t w[4];

@@ -321,7 +321,7 @@ int fewbit_hip_sampled_rows(uint64_t seed, size_t rows, size_t proj, int64_t *id
     Split sp;
     if (!split_rows(rows, sp)) return refuse_rows<Dct>("sampled_rows", rows);
     if (proj > 0 && idx == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sampled_rows: null pointer");
-    const sketch::Key key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)};
+    const sketch::Key key = sketch::key_of(seed);
     const bool pow2 = draws_halves(rows);
     const size_t per = per_draw(pow2);
     for (size_t q = 0; per * q < proj; ++q) {

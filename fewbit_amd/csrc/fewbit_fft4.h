@@ -433,7 +433,7 @@ template <int L> constexpr size_t lds_bytes_b(int n) { return (2 * L * CB + L + 
 
 inline bool known_dtype(int dtype) { return dtype == FEWBIT_F32 || dtype == FEWBIT_F16 || dtype == FEWBIT_BF16; }
 inline RowsOfSeed rows_of_seed(uint64_t seed, const uint64_t *device) {
-    return RowsOfSeed{sketch::Key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)}, reinterpret_cast<const sketch::Key *>(device)};
+    return RowsOfSeed{sketch::key_of(seed), reinterpret_cast<const sketch::Key *>(device)};
 }
 
 // ---- the host side of both kernel pairs --------------------------------------------------------------------------------------

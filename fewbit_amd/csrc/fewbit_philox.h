@@ -13,6 +13,9 @@ namespace sketch {
 constexpr int kPhiloxRounds = 10;
 
 struct Key { uint32_t k0, k1; };
+// (a seed that lives in device memory is read through a `const Key *`)
+static_assert(sizeof(Key) == sizeof(uint64_t), "a Key is the two halves of the 64-bit seed, low word first");
+__host__ __device__ inline Key key_of(uint64_t seed) { return Key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)}; }
 
 template <int ROUNDS = kPhiloxRounds>
 __host__ __device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, Key key, uint32_t (&out)[4]) {

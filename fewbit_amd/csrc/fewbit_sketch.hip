@@ -847,9 +847,34 @@ __global__ void next_seed_kernel(uint64_t *counter, uint64_t base, uint64_t *see
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
-struct Plan { unsigned gx, gy, gz; size_t kslice; int waves, halves; };
+// Everything about one call is decided ONCE, by make_plan: what the product kernel is handed (S generated or read, M as it is or
+// rounded to bf16 first), its tile and grid, how the slices' sums reach the result, the parts of the workspace.  The entry points
+// get a Plan and size (fewbit_hip_sketch_workspace), launch (sketch_entry -> launch ... launch_kernel, reduce) or
+// print (fewbit_hip_sketch_describe) from it; nothing below make_plan looks at a tuning value or repeats a policy.
 struct Seed { Key value; const Key *device; };       // `device` != nullptr: the key is read from there when the kernel runs
 struct Frags { const void *data; size_t steps; };    // A fragments in memory (kFromMemory): `steps` MFMA steps per 32-row block of S
+enum Partial { kDirect = 0, kPartialF32 = 1, kPartialBf16 = 2 };       // the kernel's PARTIAL: the result itself, or one slice's sums in fp32 / bf16
+struct Part { size_t off, bytes; };                  // of the workspace
+struct Plan {
+    int dist;                                        // the kernel's DIST: FEWBIT_SKETCH_RADEMACHER / _GAUSSIAN (fused), kFromMemory
+    int operand_dtype;                               // the kernel's DT: the dtype of M, FEWBIT_BF16 when `converted`
+    bool converted;                                  // fp32 M is rounded to bf16 in one pass first (into `copy`)
+    int waves, halves;                               // Tile<waves, halves>
+    unsigned gx, gy, gz;                             // column tiles, row tiles of S, row slices of `kslice` rows of M
+    size_t kslice;
+    Partial partial;
+    Part partials, copy, frags;                      // the workspace: [partial sums][bf16 copy of an fp32 M][A fragments of S],
+    size_t total;                                    // each part aligned to kWorkspaceAlign
+    int lds_bytes;
+};
+// the six keys of fewbit_hip_tune that belong to this unit (sketch_tune): -1 = the built-in policy.  A call reads them once.
+FEWBIT_HIDDEN std::atomic<long long> g_forced_slices{-1}, g_forced_waves{-1}, g_forced_halves{-1}, g_forced_convert{-1}, g_forced_partial16{-1},
+    g_forced_materialise{-1};
+struct Tuning { long long slices, waves, halves, convert, partial16, materialise; };
+Tuning tuning_now() {
+    auto get = [](const std::atomic<long long> &v) { return v.load(std::memory_order_relaxed); };
+    return Tuning{get(g_forced_slices), get(g_forced_waves), get(g_forced_halves), get(g_forced_convert), get(g_forced_partial16), get(g_forced_materialise)};
+}
 
 int device_cus() {
     static std::atomic<int> cached[64];
@@ -863,7 +888,8 @@ int device_cus() {
     return v;
 }
 
-FEWBIT_HIDDEN std::atomic<long long> g_forced_slices{-1}, g_forced_waves{-1}, g_forced_halves{-1};
+constexpr size_t kWorkspaceAlign = 256;
+size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // K slices: the tile grid of a sketch is small (proj x features) and K = rows is long, so the rows are cut into `gz` slices
 // when that fills the chip better.  cost(z) = (rounds of the CU array with z x tiles workgroups) / z, plus 4 % per extra
@@ -885,186 +911,13 @@ double plan_slices(size_t tiles, size_t slots, size_t rows, long long forced, si
     return best_cost;
 }
 
-Plan make_plan(int dist, int dtype, size_t rows, size_t features, size_t proj, bool one_half = false) {
-    const long long forced_z = g_forced_slices.load(std::memory_order_relaxed), forced_w = g_forced_waves.load(std::memory_order_relaxed);
-    const long long forced_h = g_forced_halves.load(std::memory_order_relaxed);
-    const size_t cus = static_cast<size_t>(device_cus());
-    Plan p;
-    // the Gaussian sketch is bound by the generator (instruction issue): the 128 x 512 tile generates every element of S once per
-    // 512 columns instead of once per 256 (two column halves share their A fragments through LDS).  Measured (16384 rows,
-    // bf16): 3072 features +11-16 % at p = 1638 / 3276 / 8192; 768 features (one and a half wide tiles) -8 %; fp32 input no gain
-    // (its staging registers already spill) -- so: 16-bit input, and a feature count the 512-wide tile divides or >= 2048
-    bool wide = dist == FEWBIT_SKETCH_GAUSSIAN && dtype != FEWBIT_F32 && features >= 1024 && (features % (2 * BN) == 0 || features >= 2048);
-    if (forced_h == 1) wide = false;
-    if (forced_h == 2) wide = true;
-    if (one_half) wide = false;                      // (fragments from memory: the product kernel has the one-half tiles only)
-    if (wide) {
-        p.waves = 8;
-        p.halves = 2;
-        p.gx = static_cast<unsigned>((features + 2 * BN - 1) / (2 * BN));
-        p.gy = static_cast<unsigned>((proj + 127) / 128);
-        size_t z = 1;
-        plan_slices(static_cast<size_t>(p.gx) * p.gy, cus, rows, forced_z, z);
-        size_t kslice = (rows + z - 1) / z;
-        kslice = (kslice + 255) / 256 * 256;
-        p.kslice = kslice;
-        p.gz = static_cast<unsigned>((rows + kslice - 1) / kslice);
-        if (p.gz < 1) p.gz = 1;
-        return p;
-    }
-    p.halves = 1;
-    p.gx = static_cast<unsigned>((features + BN - 1) / BN);
-    // tile height: 256 rows of S (8 waves) when that does not waste more of the last row tile than 128 rows (4 waves) would
-    // cost in staging
-    size_t z4 = 1, z8 = 1;
-    const size_t t4 = static_cast<size_t>(p.gx) * ((proj + 127) / 128), t8 = static_cast<size_t>(p.gx) * ((proj + 255) / 256);
-    // (a round of 2 x CUs short tiles and a round of CUs tall tiles are the same MFMA work per CU; measured, the tall tile runs
-    // 3-10 % faster per MFMA: half the staging work and L2 reads)
-    const double c4 = plan_slices(t4, 2 * cus, rows, forced_z, z4);
-    const double c8 = plan_slices(t8, cus, rows, forced_z, z8) * 0.93;
-    bool tall = c8 <= c4;
-    if (forced_w == 4) tall = false;
-    if (forced_w == 8) tall = true;
-    p.waves = tall ? 8 : 4;
-    p.gy = static_cast<unsigned>((proj + (tall ? 255 : 127)) / (tall ? 256 : 128));
-    const size_t z = tall ? z8 : z4;
-    size_t kslice = (rows + z - 1) / z;
-    kslice = (kslice + 255) / 256 * 256;
-    p.kslice = kslice;
-    p.gz = static_cast<unsigned>((rows + kslice - 1) / kslice);
-    if (p.gz < 1) p.gz = 1;
-    return p;
-}
-
-template <int DIST, int DT, int PARTIAL, int W, int NH = 1>
-int launch_kernel(const Plan &p, bool ragged, const void *m, size_t rows, size_t features, size_t ld, size_t proj, Seed key, float scale, void *out,
-                  Frags frags, hipStream_t s) {
-    const dim3 grid(p.gx, p.gy, p.gz), block(Tile<W, NH>::kThreads);
-    constexpr size_t lds = Tile<W, NH>::kLdsBytes;
-    auto go = [&](auto kern) -> int {
-        if (lds > 65536) {                           // (more than the default limit of a workgroup: opt in once per kernel and device)
-            // (one flag word per KERNEL: the ragged and the plain variant have the same function type, hence share this lambda's
-            // instantiation -- they are told apart by index)
-            static std::atomic<unsigned long long> done_flags[2];
-            std::atomic<unsigned long long> &done = done_flags[ragged ? 1 : 0];
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            const unsigned long long bit = 1ull << (dev & 63);
-            if (!(done.load(std::memory_order_relaxed) & bit)) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return fail(FEWBIT_ERR_LAUNCH, "sketch: cannot reserve %zu bytes of LDS", lds);
-                }
-                done.fetch_or(bit, std::memory_order_relaxed);
-            }
-        }
-        hipLaunchKernelGGL(kern, grid, block, lds, s, m, rows, features, ld, proj, key.value, key.device, scale, out, p.kslice, frags.data, frags.steps);
-        return FEWBIT_OK;
-    };
-    return ragged ? go(sketch_kernel<DIST, DT, PARTIAL, true, W, NH>) : go(sketch_kernel<DIST, DT, PARTIAL, false, W, NH>);
-}
-
-// bf16 partial sums: when the rows are sliced and the operands are bf16, the slices' round trip through memory (written by
-// the product kernel, read back by the reduce kernel -- 2 x gz x proj x features x 4 bytes, the K-independent part of a 768-wide
-// product's time) is made in bf16: each slice's sum is rounded once, the slices are added in fp32 in the same fixed order.
-//   * bf16 result: its error grows from one bf16 rounding to about sqrt(2) of one (gz roundings of sums sqrt(gz) times smaller);
-//   * fp32 result of an fp32 input that was rounded to bf16 first: the sums already carry the operands' rounding (2^-9 per
-//     element of M -- and of a Gaussian S --: ~0.6-0.8 x 2^-9 of a slice's sum in its standard deviation); rounding the slice's sum to
-//     bf16 adds ~0.4 x 2^-9 of it, +12 % on that error, under an estimator whose own relative noise is sqrt(rows / p).
-// fp16 keeps fp32 partial sums (range).  tune: 0 never, 2 for bf16 results only, 1 / -1 this policy.
-FEWBIT_HIDDEN std::atomic<long long> g_forced_partial16{-1};
-bool partial16(int dtype, int out_dtype, unsigned gz) {
-    if (dtype != FEWBIT_BF16 || gz <= 1 || (out_dtype != FEWBIT_BF16 && out_dtype != FEWBIT_F32)) return false;
-    const long long forced = g_forced_partial16.load(std::memory_order_relaxed);
-    return forced != 0 && !(forced == 2 && out_dtype != FEWBIT_BF16);
-}
-
-template <int DIST, int DT, int PARTIAL>
-int launch_tile(const Plan &p, bool ragged, const void *m, size_t rows, size_t features, size_t ld, size_t proj, Seed key, float scale, void *out,
-                Frags frags, hipStream_t s) {
-    if constexpr (DIST != kFromMemory) {
-        if (p.halves == 2) return launch_kernel<DIST, DT, PARTIAL, 8, 2>(p, ragged, m, rows, features, ld, proj, key, scale, out, frags, s);
-    }
-    return p.waves == 8 ? launch_kernel<DIST, DT, PARTIAL, 8>(p, ragged, m, rows, features, ld, proj, key, scale, out, frags, s)
-                        : launch_kernel<DIST, DT, PARTIAL, 4>(p, ragged, m, rows, features, ld, proj, key, scale, out, frags, s);
-}
-
-template <int DIST, int DT>
-int launch(const void *m, size_t rows, size_t features, size_t ld, size_t proj, Seed key, float scale, void *out, int out_dtype, void *workspace,
-           size_t workspace_bytes, Frags frags, hipStream_t s) {
-    const Plan p = make_plan(DIST == kFromMemory ? static_cast<int>(FEWBIT_SKETCH_RADEMACHER) : DIST, DT, rows, features, proj, DIST == kFromMemory);
-    const bool ragged = (features % 8) != 0;
-    int rc;
-    if (p.gz == 1 && out_dtype == DT) {
-        rc = launch_tile<DIST, DT, 0>(p, ragged, m, rows, features, ld, proj, key, scale, out, frags, s);
-        if (rc != FEWBIT_OK) return rc;
-    } else {                                         // partial sums, then one pass: sum, scale, round to the result's dtype
-        const bool p16 = partial16(DT, out_dtype, p.gz);
-        const size_t n = proj * features;
-        const size_t need = static_cast<size_t>(p.gz) * n * (p16 ? sizeof(uint16_t) : sizeof(float));
-        if (workspace == nullptr || workspace_bytes < need)
-            return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sketch: workspace of %zu bytes needed (fewbit_hip_sketch_workspace), got %zu", need, workspace_bytes);
-        const int z = static_cast<int>(p.gz);
-        if constexpr (DT == FEWBIT_BF16) {
-            if (p16) {
-                rc = launch_tile<DIST, DT, 2>(p, ragged, m, rows, features, ld, proj, key, scale, workspace, frags, s);
-                if (rc != FEWBIT_OK) return rc;
-                const uint16_t *ws = static_cast<const uint16_t *>(workspace);
-                const bool vec = n % 8 == 0 && (reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
-                const dim3 grid(static_cast<unsigned>(((vec ? n / 8 : n) + 255) / 256));
-                if (out_dtype == FEWBIT_F32) {
-                    if (vec) hipLaunchKernelGGL((sketch_reduce_bf16_kernel<true, true>), grid, dim3(256), 0, s, ws, n, z, scale, out);
-                    else hipLaunchKernelGGL((sketch_reduce_bf16_kernel<false, true>), grid, dim3(256), 0, s, ws, n, z, scale, out);
-                } else {
-                    if (vec) hipLaunchKernelGGL((sketch_reduce_bf16_kernel<true, false>), grid, dim3(256), 0, s, ws, n, z, scale, out);
-                    else hipLaunchKernelGGL((sketch_reduce_bf16_kernel<false, false>), grid, dim3(256), 0, s, ws, n, z, scale, out);
-                }
-                const hipError_t e = hipGetLastError();
-                if (e != hipSuccess) return fail(FEWBIT_ERR_LAUNCH, "sketch: %s", hipGetErrorString(e));
-                return FEWBIT_OK;
-            }
-        }
-        rc = launch_tile<DIST, DT, 1>(p, ragged, m, rows, features, ld, proj, key, scale, workspace, frags, s);
-        if (rc != FEWBIT_OK) return rc;
-        const float *ws = static_cast<const float *>(workspace);
-        const bool vec = n % 4 == 0 && (reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
-        auto reduce = [&](auto tag) {
-            constexpr int ODT = decltype(tag)::value;
-            if (vec) hipLaunchKernelGGL((sketch_reduce4_kernel<ODT>), dim3(static_cast<unsigned>((n / 4 + 255) / 256)), dim3(256), 0, s, ws, n / 4, z, scale, out);
-            else hipLaunchKernelGGL((sketch_reduce_kernel<ODT>), dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s, ws, n, z, scale, out);
-        };
-        if (out_dtype == FEWBIT_F32) reduce(std::integral_constant<int, FEWBIT_F32>{});
-        else reduce(std::integral_constant<int, DT>{});
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FEWBIT_ERR_LAUNCH, "sketch: %s", hipGetErrorString(e));
-    return FEWBIT_OK;
-}
-
-template <int DIST>
-int launch_dtype(int dtype, const void *m, size_t rows, size_t features, size_t ld, size_t proj, Seed key, float scale, void *out, int out_dtype,
-                 void *workspace, size_t workspace_bytes, Frags frags, hipStream_t s) {
-    switch (dtype) {
-    case FEWBIT_F32:
-        if constexpr (DIST == kFromMemory) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sketch: fragments from memory need a 16-bit operand");
-        else return launch<DIST, FEWBIT_F32>(m, rows, features, ld, proj, key, scale, out, out_dtype, workspace, workspace_bytes, frags, s);
-    case FEWBIT_F16: return launch<DIST, FEWBIT_F16>(m, rows, features, ld, proj, key, scale, out, out_dtype, workspace, workspace_bytes, frags, s);
-    case FEWBIT_BF16: return launch<DIST, FEWBIT_BF16>(m, rows, features, ld, proj, key, scale, out, out_dtype, workspace, workspace_bytes, frags, s);
-    default: return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sketch: unknown dtype %d", dtype);
-    }
-}
-
 // fp32 input: convert first?  From 6 row tiles of 256 on (p > 1280) -- below that M is read too few times for the extra pass
 // (read 4 + write 2 + read 2 bytes per element) to pay.  tune: 0 never, 1 always, -1 this policy.
-FEWBIT_HIDDEN std::atomic<long long> g_forced_convert{-1};
-bool converts_first(int dtype, size_t rows, size_t proj) {
+bool converts_first(const Tuning &t, int dtype, size_t rows, size_t proj) {
     if (dtype != FEWBIT_F32 || rows == 0) return false;
-    const long long forced = g_forced_convert.load(std::memory_order_relaxed);
-    if (forced >= 0) return forced != 0;
+    if (t.convert >= 0) return t.convert != 0;
     return proj > 1280;
 }
-constexpr size_t kWorkspaceAlign = 256;
-size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // S in memory first?  The Gaussian sketch (a fragment costs ~100 issue slots; Rademacher's 8 are not worth a byte of traffic) when
 // at least two column tiles would otherwise regenerate it (features > 256) and its fragments (bf16, rows of S padded to 256, rows
@@ -1075,34 +928,178 @@ size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // tune "sketch_materialise": 0 never, -1 this policy, 1 the policy without the width rule of fp32 input (the caps stay).
 constexpr size_t kWideLayer = 2048;
 constexpr size_t kMaxFragmentBytes = 1ull << 30;
-FEWBIT_HIDDEN std::atomic<long long> g_forced_materialise{-1};
 size_t fragment_blocks(size_t rows) { return (rows + 255) / 256; }                  // 256-row blocks of M = 16 MFMA steps each
 size_t fragment_row_blocks(size_t proj) { return (proj + 255) / 256 * 8; }          // 32-row blocks of S, padded to whole 256-row tiles
 size_t fragment_bytes(size_t rows, size_t proj) { return (fragment_row_blocks(proj) * fragment_blocks(rows) * 16 + kFragAhead) * 1024; }
-bool materialises(int dist, int operand_dtype, bool converted, size_t rows, size_t features, size_t proj) {
+bool materialises(const Tuning &t, int dist, int operand_dtype, bool converted, size_t rows, size_t features, size_t proj) {
     if (dist != FEWBIT_SKETCH_GAUSSIAN || operand_dtype == FEWBIT_F32 || rows == 0) return false;
-    const long long forced = g_forced_materialise.load(std::memory_order_relaxed);
-    if (forced == 0 || fragment_row_blocks(proj) > 65535) return false;
+    if (t.materialise == 0 || fragment_row_blocks(proj) > 65535) return false;
     if (features <= BN || fragment_bytes(rows, proj) > kMaxFragmentBytes) return false;      // (also when forced: the path exists to SAVE time and memory)
-    return forced == 1 || !converted || features >= kWideLayer;
+    return t.materialise == 1 || !converted || features >= kWideLayer;
 }
 
-// the workspace of one call: [partial sums][bf16 copy of an fp32 M][A fragments of S], each part aligned to kWorkspaceAlign
-struct Layout { int operand_dtype, plan_dist; bool converted, materialised; size_t partial_bytes, copy_off, copy_bytes, frag_off, frag_bytes, total; };
-Layout layout(int dist, int dtype, size_t rows, size_t features, size_t proj) {
-    Layout L{};
-    L.converted = converts_first(dtype, rows, proj);
-    L.operand_dtype = L.converted ? static_cast<int>(FEWBIT_BF16) : dtype;
-    L.materialised = materialises(dist, L.operand_dtype, L.converted, rows, features, proj);
-    L.plan_dist = L.materialised ? static_cast<int>(FEWBIT_SKETCH_RADEMACHER) : dist;      // (fragments from memory: the one-half tiles' plan)
-    const Plan p = make_plan(L.plan_dist, L.operand_dtype, rows, features, proj, L.materialised);
-    L.partial_bytes = (p.gz > 1 || dtype != L.operand_dtype)
-                          ? static_cast<size_t>(p.gz) * proj * features * (partial16(L.operand_dtype, dtype, p.gz) ? sizeof(uint16_t) : sizeof(float)) : 0;
-    size_t end = L.partial_bytes;
-    if (L.converted) { L.copy_off = round_up(end, kWorkspaceAlign); L.copy_bytes = rows * features * sizeof(uint16_t); end = L.copy_off + L.copy_bytes; }
-    if (L.materialised) { L.frag_off = round_up(end, kWorkspaceAlign); L.frag_bytes = fragment_bytes(rows, proj); end = L.frag_off + L.frag_bytes; }
-    L.total = end;
-    return L;
+// How the sums reach the result: written by the product kernel itself when one slice holds all rows and the operands have the
+// result's dtype; otherwise every slice writes its partial sums and one more pass adds them, scales and rounds to the result's dtype.
+// bf16 partial sums: when the rows are sliced and the operands are bf16, the slices' round trip through memory (written by
+// the product kernel, read back by the reduce kernel -- 2 x gz x proj x features x 4 bytes, the K-independent part of a 768-wide
+// product's time) is made in bf16: each slice's sum is rounded once, the slices are added in fp32 in the same fixed order.
+//   * bf16 result: its error grows from one bf16 rounding to about sqrt(2) of one (gz roundings of sums sqrt(gz) times smaller);
+//   * fp32 result of an fp32 input that was rounded to bf16 first: the sums already carry the operands' rounding (2^-9 per
+//     element of M -- and of a Gaussian S --: ~0.6-0.8 x 2^-9 of a slice's sum in its standard deviation); rounding the slice's sum to
+//     bf16 adds ~0.4 x 2^-9 of it, +12 % on that error, under an estimator whose own relative noise is sqrt(rows / p).
+// fp16 keeps fp32 partial sums (range).  tune: 0 never, 2 for bf16 results only, 1 / -1 this policy.
+Partial partial_sums(const Tuning &t, int operand_dtype, int out_dtype, unsigned gz) {
+    if (gz == 1 && out_dtype == operand_dtype) return kDirect;
+    if (operand_dtype != FEWBIT_BF16 || gz <= 1 || (out_dtype != FEWBIT_BF16 && out_dtype != FEWBIT_F32)) return kPartialF32;
+    return t.partial16 != 0 && !(t.partial16 == 2 && out_dtype != FEWBIT_BF16) ? kPartialBf16 : kPartialF32;
+}
+
+Plan make_plan(int dist, int dtype, size_t rows, size_t features, size_t proj) {
+    const Tuning t = tuning_now();
+    const size_t cus = static_cast<size_t>(device_cus());
+    Plan p{};
+    p.converted = converts_first(t, dtype, rows, proj);
+    p.operand_dtype = p.converted ? static_cast<int>(FEWBIT_BF16) : dtype;
+    const bool from_memory = materialises(t, dist, p.operand_dtype, p.converted, rows, features, proj);
+    p.dist = from_memory ? kFromMemory : dist;
+    // the Gaussian sketch is bound by the generator (instruction issue): the 128 x 512 tile generates every element of S once per
+    // 512 columns instead of once per 256 (two column halves share their A fragments through LDS).  Measured (16384 rows,
+    // bf16): 3072 features +11-16 % at p = 1638 / 3276 / 8192; 768 features (one and a half wide tiles) -8 %; fp32 input no gain
+    // (its staging registers already spill) -- so: 16-bit input, and a feature count the 512-wide tile divides or >= 2048
+    bool wide = dist == FEWBIT_SKETCH_GAUSSIAN && p.operand_dtype != FEWBIT_F32 && features >= 1024 && (features % (2 * BN) == 0 || features >= 2048);
+    if (t.halves == 1) wide = false;
+    if (t.halves == 2) wide = true;
+    if (from_memory) wide = false;                   // (the product kernel that reads its fragments has the one-half tiles only)
+    size_t z = 1;
+    if (wide) {
+        p.waves = 8;
+        p.halves = 2;
+        p.gx = static_cast<unsigned>((features + 2 * BN - 1) / (2 * BN));
+        p.gy = static_cast<unsigned>((proj + 127) / 128);
+        plan_slices(static_cast<size_t>(p.gx) * p.gy, cus, rows, t.slices, z);
+    } else {
+        p.halves = 1;
+        p.gx = static_cast<unsigned>((features + BN - 1) / BN);
+        // tile height: 256 rows of S (8 waves) when that does not waste more of the last row tile than 128 rows (4 waves) would
+        // cost in staging
+        size_t z4 = 1, z8 = 1;
+        const size_t t4 = static_cast<size_t>(p.gx) * ((proj + 127) / 128), t8 = static_cast<size_t>(p.gx) * ((proj + 255) / 256);
+        // (a round of 2 x CUs short tiles and a round of CUs tall tiles are the same MFMA work per CU; measured, the tall tile runs
+        // 3-10 % faster per MFMA: half the staging work and L2 reads)
+        const double c4 = plan_slices(t4, 2 * cus, rows, t.slices, z4);
+        const double c8 = plan_slices(t8, cus, rows, t.slices, z8) * 0.93;
+        bool tall = c8 <= c4;
+        if (t.waves == 4) tall = false;
+        if (t.waves == 8) tall = true;
+        p.waves = tall ? 8 : 4;
+        p.gy = static_cast<unsigned>((proj + (tall ? 255 : 127)) / (tall ? 256 : 128));
+        z = tall ? z8 : z4;
+    }
+    p.lds_bytes = p.halves == 2 ? Tile<8, 2>::kLdsBytes : p.waves == 8 ? Tile<8>::kLdsBytes : Tile<4>::kLdsBytes;
+    // z slices of whole 256-row blocks (no rows: one empty slice)
+    p.kslice = rows == 0 ? 256 : round_up((rows + z - 1) / z, 256);
+    p.gz = rows == 0 ? 1 : static_cast<unsigned>((rows + p.kslice - 1) / p.kslice);
+    p.partial = partial_sums(t, p.operand_dtype, dtype, p.gz);
+    size_t end = 0;
+    auto part = [&end](size_t bytes) { const Part q{round_up(end, kWorkspaceAlign), bytes}; end = q.off + bytes; return q; };
+    if (p.partial != kDirect) p.partials = part(static_cast<size_t>(p.gz) * proj * features * (p.partial == kPartialBf16 ? sizeof(uint16_t) : sizeof(float)));
+    if (p.converted) p.copy = part(rows * features * sizeof(uint16_t));
+    if (from_memory) p.frags = part(fragment_bytes(rows, proj));
+    p.total = end;
+    return p;
+}
+
+// the arguments of one call as the product kernel gets them (M: the bf16 copy when the plan converts first)
+struct Call { const void *m; size_t rows, features, ld, proj; Seed key; float scale; void *out; int out_dtype; Frags frags; hipStream_t s; };
+
+int launched() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "sketch: %s", hipGetErrorString(e));
+}
+
+// more LDS than the default limit of a workgroup: opt in once per kernel and device (one flag word per kernel, a bit per device)
+template <auto Kern> int reserve_lds(size_t lds) {
+    static std::atomic<unsigned long long> done{0};
+    if (lds <= 65536) return FEWBIT_OK;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_relaxed) & bit) return FEWBIT_OK;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FEWBIT_ERR_LAUNCH, "sketch: cannot reserve %zu bytes of LDS", lds);
+    }
+    done.fetch_or(bit, std::memory_order_relaxed);
+    return FEWBIT_OK;
+}
+
+// ---- from the plan's run-time values to the kernel's template arguments: DIST (launch), DT (launch_dtype), PARTIAL (launch_partial),
+// W / NH (launch_tile), RAGGED (launch_kernel).  kFromMemory has no fp32 operand and no two-half tile; bf16 partial sums have bf16 operands.
+template <int DIST, int DT, int PARTIAL, int W, int NH = 1> int launch_kernel(const Plan &p, const Call &c, void *sums) {
+    using T = Tile<W, NH>;
+    auto go = [&](auto ragged) -> int {
+        constexpr auto kern = sketch_kernel<DIST, DT, PARTIAL, decltype(ragged)::value, W, NH>;
+        const int rc = reserve_lds<kern>(T::kLdsBytes);
+        if (rc != FEWBIT_OK) return rc;
+        hipLaunchKernelGGL(kern, dim3(p.gx, p.gy, p.gz), dim3(T::kThreads), T::kLdsBytes, c.s, c.m, c.rows, c.features, c.ld, c.proj, c.key.value, c.key.device,
+                           c.scale, sums, p.kslice, c.frags.data, c.frags.steps);
+        return FEWBIT_OK;
+    };
+    return c.features % 8 != 0 ? go(std::true_type{}) : go(std::false_type{});
+}
+
+template <int DIST, int DT, int PARTIAL> int launch_tile(const Plan &p, const Call &c, void *sums) {
+    if constexpr (DIST != kFromMemory) {
+        if (p.halves == 2) return launch_kernel<DIST, DT, PARTIAL, 8, 2>(p, c, sums);
+    }
+    return p.waves == 8 ? launch_kernel<DIST, DT, PARTIAL, 8>(p, c, sums) : launch_kernel<DIST, DT, PARTIAL, 4>(p, c, sums);
+}
+
+template <int DIST, int DT> int launch_partial(const Plan &p, const Call &c, void *sums) {
+    if constexpr (DT == FEWBIT_BF16) {
+        if (p.partial == kPartialBf16) return launch_tile<DIST, DT, kPartialBf16>(p, c, sums);
+    }
+    return p.partial == kDirect ? launch_tile<DIST, DT, kDirect>(p, c, sums) : launch_tile<DIST, DT, kPartialF32>(p, c, sums);
+}
+
+template <int DIST> int launch_dtype(const Plan &p, const Call &c, void *sums) {
+    switch (p.operand_dtype) {
+    case FEWBIT_F32:
+        if constexpr (DIST == kFromMemory) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sketch: fragments from memory need a 16-bit operand");
+        else return launch_partial<DIST, FEWBIT_F32>(p, c, sums);
+    case FEWBIT_F16: return launch_partial<DIST, FEWBIT_F16>(p, c, sums);
+    case FEWBIT_BF16: return launch_partial<DIST, FEWBIT_BF16>(p, c, sums);
+    default: return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sketch: unknown dtype %d", p.operand_dtype);
+    }
+}
+
+// the slices' partial sums -> the result: added in slice order, scaled, rounded to the result's dtype.  Sixteen bytes of sums per
+// thread (8 bf16 / 4 fp32) where the element count and both pointers allow, else element by element.
+int reduce(const Plan &p, const Call &c, const void *sums) {
+    const size_t n = c.proj * c.features, per = p.partial == kPartialBf16 ? 8 : 4;
+    const bool vec = n % per == 0 && (reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(c.out)) % 16 == 0;
+    const dim3 grid(static_cast<unsigned>(((vec ? n / per : n) + 255) / 256));
+    auto go = [&](auto kern, auto *src, size_t count) { hipLaunchKernelGGL(kern, grid, dim3(256), 0, c.s, src, count, static_cast<int>(p.gz), c.scale, c.out); };
+    if (p.partial == kPartialBf16) {
+        const uint16_t *src = static_cast<const uint16_t *>(sums);
+        if (c.out_dtype == FEWBIT_F32) vec ? go(sketch_reduce_bf16_kernel<true, true>, src, n) : go(sketch_reduce_bf16_kernel<false, true>, src, n);
+        else vec ? go(sketch_reduce_bf16_kernel<true, false>, src, n) : go(sketch_reduce_bf16_kernel<false, false>, src, n);
+    } else {
+        const float *src = static_cast<const float *>(sums);
+        auto to = [&](auto odt) { vec ? go(sketch_reduce4_kernel<decltype(odt)::value>, src, n / 4) : go(sketch_reduce_kernel<decltype(odt)::value>, src, n); };
+        if (c.out_dtype == FEWBIT_F32) to(std::integral_constant<int, FEWBIT_F32>{});
+        else if (c.out_dtype == FEWBIT_F16) to(std::integral_constant<int, FEWBIT_F16>{});
+        else to(std::integral_constant<int, FEWBIT_BF16>{});
+    }
+    return launched();
+}
+
+int launch(const Plan &p, const Call &c, uint8_t *workspace) {
+    void *sums = p.partial == kDirect ? c.out : workspace + p.partials.off;
+    const int rc = p.dist == kFromMemory ? launch_dtype<kFromMemory>(p, c, sums)
+                   : p.dist == FEWBIT_SKETCH_RADEMACHER ? launch_dtype<FEWBIT_SKETCH_RADEMACHER>(p, c, sums) : launch_dtype<FEWBIT_SKETCH_GAUSSIAN>(p, c, sums);
+    if (rc != FEWBIT_OK) return rc;
+    return p.partial == kDirect ? launched() : reduce(p, c, sums);
 }
 
 }  // namespace sketch
@@ -1140,7 +1137,7 @@ extern "C" {
 
 size_t fewbit_hip_sketch_workspace(int dist, int dtype, size_t rows, size_t features, size_t proj) {
     if (rows == 0 || features == 0 || proj == 0) return 0;
-    return layout(dist, dtype, rows, features, proj).total;
+    return make_plan(dist, dtype, rows, features, proj).total;
 }
 
 static int sketch_entry(int dist, int dtype, const void *m, size_t rows, size_t features, size_t ld, size_t proj, Seed key, double scale,
@@ -1157,48 +1154,40 @@ static int sketch_entry(int dist, int dtype, const void *m, size_t rows, size_t 
         if (hipMemsetAsync(out, 0, proj * features * es, s) != hipSuccess) return fail(FEWBIT_ERR_LAUNCH, "sketch: memset failed");
         return FEWBIT_OK;
     }
-    const Layout L = layout(dist, dtype, rows, features, proj);
-    if (L.total != 0 && (workspace == nullptr || workspace_bytes < L.total))
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sketch: workspace of %zu bytes needed (fewbit_hip_sketch_workspace), got %zu", L.total, workspace_bytes);
+    const Plan p = make_plan(dist, dtype, rows, features, proj);
+    if (p.total != 0 && (workspace == nullptr || workspace_bytes < p.total))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sketch: workspace of %zu bytes needed (fewbit_hip_sketch_workspace), got %zu", p.total, workspace_bytes);
     uint8_t *ws = static_cast<uint8_t *>(workspace);
-    auto launch_fragments = [&]() {
-        const size_t nblocks = fragment_blocks(rows);
-        const dim3 grid(static_cast<unsigned>((nblocks + 3) / 4), static_cast<unsigned>(fragment_row_blocks(proj)));
-        u32x4 *frag = reinterpret_cast<u32x4 *>(ws + L.frag_off);
-        if (L.operand_dtype == FEWBIT_F16) hipLaunchKernelGGL((sketch_fragments_kernel<FEWBIT_SKETCH_GAUSSIAN, FEWBIT_F16>), grid, dim3(256), 0, s, key.value, key.device, nblocks, frag);
-        else hipLaunchKernelGGL((sketch_fragments_kernel<FEWBIT_SKETCH_GAUSSIAN, FEWBIT_BF16>), grid, dim3(256), 0, s, key.value, key.device, nblocks, frag);
-    };
-    if (L.converted) {                                // fp32 input, many row tiles: rounded to bf16 once
-        uint16_t *copy = reinterpret_cast<uint16_t *>(ws + L.copy_off);
+    Call c{m, rows, features, ld, proj, key, static_cast<float>(scale), out, dtype, Frags{nullptr, 0}, s};
+    if (p.converted) {                                // fp32 input, many row tiles: rounded to bf16 once
+        uint16_t *copy = reinterpret_cast<uint16_t *>(ws + p.copy.off);
         const size_t pieces = rows * ((features + 7) / 8);
         hipLaunchKernelGGL(to_bf16_kernel, dim3(static_cast<unsigned>((pieces + 255) / 256)), dim3(256), 0, s, static_cast<const float *>(m), rows, features, ld, copy);
-        m = copy;
-        ld = features;
+        c.m = copy;
+        c.ld = features;
     }
-    const float fscale = static_cast<float>(scale);
-    if (L.materialised) {                             // S once, as A fragments; then the product kernel that reads them
+    if (p.dist == kFromMemory) {                      // S once, as A fragments, for the product kernel to read
+        // (behind the conversion pass of an fp32 input: in front of it measured the same)
         const size_t nblocks = fragment_blocks(rows);
-        u32x4 *frag = reinterpret_cast<u32x4 *>(ws + L.frag_off);
-        launch_fragments();       // (behind the conversion pass of an fp32 input: in front of it measured the same)
+        const dim3 grid(static_cast<unsigned>((nblocks + 3) / 4), static_cast<unsigned>(fragment_row_blocks(proj)));
+        u32x4 *frag = reinterpret_cast<u32x4 *>(ws + p.frags.off);
+        if (p.operand_dtype == FEWBIT_F16) hipLaunchKernelGGL((sketch_fragments_kernel<FEWBIT_SKETCH_GAUSSIAN, FEWBIT_F16>), grid, dim3(256), 0, s, key.value, key.device, nblocks, frag);
+        else hipLaunchKernelGGL((sketch_fragments_kernel<FEWBIT_SKETCH_GAUSSIAN, FEWBIT_BF16>), grid, dim3(256), 0, s, key.value, key.device, nblocks, frag);
         // (the kFragAhead steps of padding behind the last fragment are read, never used: any bytes will do)
-        return launch_dtype<kFromMemory>(L.operand_dtype, m, rows, features, ld, proj, key, fscale, out, dtype, workspace, L.partial_bytes, Frags{frag, nblocks * 16}, s);
+        c.frags = Frags{frag, nblocks * 16};
     }
-    if (dist == FEWBIT_SKETCH_RADEMACHER)
-        return launch_dtype<FEWBIT_SKETCH_RADEMACHER>(L.operand_dtype, m, rows, features, ld, proj, key, fscale, out, dtype, workspace, L.partial_bytes, Frags{nullptr, 0}, s);
-    return launch_dtype<FEWBIT_SKETCH_GAUSSIAN>(L.operand_dtype, m, rows, features, ld, proj, key, fscale, out, dtype, workspace, L.partial_bytes, Frags{nullptr, 0}, s);
+    return launch(p, c, ws);
 }
 
 int fewbit_hip_sketch(int dist, int dtype, const void *m, size_t rows, size_t features, size_t ld, size_t proj, uint64_t seed, double scale,
                       void *out, void *workspace, size_t workspace_bytes, void *stream) {
-    const Seed key{Key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)}, nullptr};
-    return sketch_entry(dist, dtype, m, rows, features, ld, proj, key, scale, out, workspace, workspace_bytes, stream);
+    return sketch_entry(dist, dtype, m, rows, features, ld, proj, Seed{key_of(seed), nullptr}, scale, out, workspace, workspace_bytes, stream);
 }
 
 int fewbit_hip_sketch_device_seed(int dist, int dtype, const void *m, size_t rows, size_t features, size_t ld, size_t proj,
                                   const uint64_t *seed_device, double scale, void *out, void *workspace, size_t workspace_bytes, void *stream) {
     if (seed_device == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sketch: null seed pointer");
-    static_assert(sizeof(Key) == sizeof(uint64_t), "a Key is the two halves of the 64-bit seed, low word first");
-    const Seed key{Key{0u, 0u}, reinterpret_cast<const Key *>(seed_device)};
+    const Seed key{Key{0u, 0u}, reinterpret_cast<const Key *>(seed_device)};      // (a Key is the seed's two words: fewbit_philox.h)
     return sketch_entry(dist, dtype, m, rows, features, ld, proj, key, scale, out, workspace, workspace_bytes, stream);
 }
 
@@ -1216,7 +1205,7 @@ int fewbit_hip_sketch_matrix(int dist, int dtype, uint64_t seed, size_t row0, si
     if (dist != FEWBIT_SKETCH_RADEMACHER && dist != FEWBIT_SKETCH_GAUSSIAN) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sketch: unknown distribution %d", dist);
     if (nrows == 0 || ncols == 0) return FEWBIT_OK;
     if (out == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sketch: null pointer");
-    const Key key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)};
+    const Key key = key_of(seed);
     const size_t n = nrows * ncols;
     const dim3 grid(static_cast<unsigned>((n + 255) / 256));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1229,15 +1218,13 @@ int fewbit_hip_sketch_matrix(int dist, int dtype, uint64_t seed, size_t row0, si
 
 int fewbit_hip_sketch_describe(int dist, int dtype, size_t rows, size_t features, size_t proj, char *buf, size_t len) {
     if (buf == nullptr || len == 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sketch_describe: no buffer");
-    const Layout L = layout(dist, dtype, rows, features, proj);
-    const Plan p = make_plan(L.plan_dist, L.operand_dtype, rows, features, proj, L.materialised);
-    const char *partials = (p.gz > 1 || L.operand_dtype != dtype) ? (partial16(L.operand_dtype, dtype, p.gz) ? "\"bf16\"" : "\"fp32\"") : "null";
+    const Plan p = make_plan(dist, dtype, rows, features, proj);
+    static const char *const partials[] = {"null", "\"fp32\"", "\"bf16\""};
     snprintf(buf, len, "{\"kernel\": \"sketch_kernel (%dx%d tile, K stage %d, v_mfma_f32_32x32x16%s)\", \"grid\": [%u, %u, %u], \"threads\": %d, "
                        "\"k_slice\": %zu, \"lds_bytes\": %d, \"workspace_bytes\": %zu, \"converted_to_bf16_first\": %s, \"partial_sums\": %s, "
                        "\"s_fragment_bytes\": %zu}",
-             32 * p.waves / p.halves, 256 * p.halves, 16 * p.waves / p.halves, L.materialised ? ", A fragments of S from memory" : "", p.gx, p.gy, p.gz,
-             64 * p.waves, p.kslice, p.halves == 2 ? Tile<8, 2>::kLdsBytes : 2 * 16 * p.waves * BN * 2, rows == 0 ? 0 : L.total,
-             L.converted ? "true" : "false", partials, L.frag_bytes);
+             32 * p.waves / p.halves, 256 * p.halves, 16 * p.waves / p.halves, p.dist == kFromMemory ? ", A fragments of S from memory" : "", p.gx, p.gy, p.gz,
+             64 * p.waves, p.kslice, p.lds_bytes, p.total, p.converted ? "true" : "false", partials[p.partial], p.frags.bytes);
     return FEWBIT_OK;
 }
 
