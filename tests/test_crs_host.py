@@ -42,6 +42,20 @@ def test_the_host_function_is_the_definition(in_features):
             assert cabi_x.crs_count(seed, in_features, nopairs) == len(want_cols) <= min(nopairs, in_features)
 
 
+@pytest.mark.parametrize('in_features', (1023, 1025, 8191, 8193))
+def test_the_host_function_is_the_definition_around_the_prep_kernels_boundaries(in_features):
+    """the widths on either side of the prep kernel's 1024 threads and of its 8192 LDS counters, at one draw and at one draw past a full
+    pass of its draw loop (4 x 1024 + 1): what tests/test_gpu_crs_edges.py holds the device's evaluation against"""
+    for nopairs in (1, 4097):
+        for seed in (1, 0xfedcba9876543210):
+            cols, count = cabi_x.crs_columns(seed, in_features, nopairs)
+            want_cols, want_count, want_scale = columns_of_seed(seed, in_features, nopairs)
+            assert cols.tolist() == want_cols and count.tolist() == want_count, (seed, in_features, nopairs)
+            assert int(count.sum()) == nopairs and cabi_x.crs_count(seed, in_features, nopairs) == len(want_cols) <= min(nopairs, in_features)
+            scale = (count.double() * in_features / nopairs).float()
+            assert scale.tolist() == [float(s) for s in want_scale]
+
+
 def test_the_column_domain_is_not_the_rows_or_a_sketch_domain():
     """one seed used for a sketch, for sampled rows and for columns: three different Philox blocks"""
     header = (ROOT / 'include' / 'fewbit_hipx.h').read_text()
