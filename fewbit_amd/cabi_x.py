@@ -9,10 +9,11 @@ from typing import Optional, Tuple
 
 import torch
 
-from .cabi import DTYPES, FewbitHipError, _buffers, _matrix, _on, _sampled_call, _seed_word, _span, _stream
+from .cabi import DTYPES, SAMPLED_ROWS, FewbitHipError, _buffers, _matrix, _on, _sampled_call, _seed_word, _span, _stream
 
 __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft', 'sampled_dft_seeded', 'sampled_dft_workspace_bytes', 'crs_columns',
-           'crs_count', 'crs_workspace_bytes', 'crs_gather', 'crs_scatter']
+           'crs_count', 'crs_workspace_bytes', 'crs_gather', 'crs_scatter', 'sampled_rows_ceil', 'sampled_dct_zext', 'sampled_dct_zext_seeded',
+           'sampled_dft_zext', 'sampled_dft_zext_seeded']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -21,7 +22,8 @@ REVISION = 2                                   # FEWBIT_HIPX_REVISION: additions
 # every symbol include/fewbit_hipx.h declares
 SYMBOLS = ('fewbit_hipx_abi_version', 'fewbit_hipx_last_error', 'fewbit_hipx_sampled_dft_workspace', 'fewbit_hipx_sampled_dft',
            'fewbit_hipx_sampled_dft_seeded', 'fewbit_hipx_revision', 'fewbit_hipx_crs_columns', 'fewbit_hipx_crs_workspace', 'fewbit_hipx_crs_gather',
-           'fewbit_hipx_crs_scatter')
+           'fewbit_hipx_crs_scatter', 'fewbit_hipx_sampled_rows_ceil', 'fewbit_hipx_sampled_dct_zext', 'fewbit_hipx_sampled_dct_zext_seeded',
+           'fewbit_hipx_sampled_dft_zext', 'fewbit_hipx_sampled_dft_zext_seeded')
 
 _lib = None
 
@@ -62,6 +64,17 @@ def lib() -> ctypes.CDLL:
         L.fewbit_hipx_crs_gather.argtypes = [i32, vp, sz, sz, sz, u64, vp, sz, sz, vp, vp, sz, vp]
         L.fewbit_hipx_crs_scatter.restype = i32
         L.fewbit_hipx_crs_scatter.argtypes = [i32, vp, sz, sz, u64, vp, sz, sz, vp, vp, sz, vp]
+        # the zero-extended sampled transforms: inside revision 2, recognised by their symbols (checked above with every other name)
+        L.fewbit_hipx_sampled_rows_ceil.restype = sz
+        L.fewbit_hipx_sampled_rows_ceil.argtypes = [sz]
+        L.fewbit_hipx_sampled_dct_zext.restype = i32
+        L.fewbit_hipx_sampled_dct_zext.argtypes = [i32, vp, sz, sz, sz, sz, vp, sz, dbl, vp, vp, sz, vp]
+        L.fewbit_hipx_sampled_dct_zext_seeded.restype = i32
+        L.fewbit_hipx_sampled_dct_zext_seeded.argtypes = [i32, vp, sz, sz, sz, sz, u64, vp, sz, dbl, vp, vp, sz, vp]
+        L.fewbit_hipx_sampled_dft_zext.restype = i32
+        L.fewbit_hipx_sampled_dft_zext.argtypes = [i32, vp, sz, sz, sz, sz, vp, sz, dbl, i32, vp, vp, sz, vp]
+        L.fewbit_hipx_sampled_dft_zext_seeded.restype = i32
+        L.fewbit_hipx_sampled_dft_zext_seeded.argtypes = [i32, vp, sz, sz, sz, sz, u64, vp, sz, dbl, i32, vp, vp, sz, vp]
         _lib = L
     return _lib
 
@@ -120,6 +133,97 @@ def sampled_dft_seeded(m: torch.Tensor, proj: int, seed, scale: float = 1.0, out
         value, word, others = seed & 0xffffffffffffffff, 0, ()
     return _sampled_dft_call(m, proj, out_dtype, out, workspace, others, lambda dt, odt, mp, rows, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dft_seeded(
         dt, mp, rows, features, ld, value, word, proj, scale, odt, op, wp, wb, _stream(stream, m.device)))
+
+
+# ---- the sampled transforms at any row count: x is transformed as if zero rows followed it, up to a supported row count -------------------
+def sampled_rows_ceil(rows: int) -> int:
+    """The smallest row count of ``cabi.SAMPLED_ROWS`` that is ``>= rows`` (256 for 1 .. 256); 0 for ``rows = 0`` and beyond 262144.
+    Evaluated on the host from the table the kernels are dispatched by; no GPU needed."""
+    if rows < 0:
+        raise FewbitHipError(f'rows must not be negative (got {rows})')
+    return lib().fewbit_hipx_sampled_rows_ceil(rows)
+
+
+def _zext_call(name: str, x: torch.Tensor, rows: int, proj: int, planes: tuple, out_dtype: torch.dtype, what: str, out: Optional[torch.Tensor],
+               workspace: Optional[torch.Tensor], others, launch) -> torch.Tensor:
+    """A zero-extended call: ``x`` checked (``valid_rows = x.shape[0]`` of them, 1 .. ``rows``), ``rows`` without a kernel refused by name,
+    ``out`` and the workspace (the plain formula at ``rows``) allocated or checked, then
+    ``launch(dtype, x, rows, valid_rows, features, ld, out, workspace, workspace bytes)``"""
+    valid, features, ld = _matrix(x)
+    need = sampled_dft_workspace_bytes(rows, features, proj, x.dtype)
+    if sampled_dft_workspace_bytes(rows, 1, 1, x.dtype) == 0:
+        raise FewbitHipError(f'{name}: no kernel for {rows} rows ({SAMPLED_ROWS} is needed; sampled_rows_ceil gives the next one)')
+    if not 1 <= valid <= rows:
+        raise FewbitHipError(f'{name}: x has {valid} rows, 1 .. rows = {rows} are needed')
+    with _on(x.device):
+        out, workspace = _buffers(x, others, out, (*planes, proj, features), out_dtype, what, workspace, need)
+        _check(launch(DTYPES[x.dtype], x.data_ptr(), rows, valid, features, ld, out.data_ptr(), *_span(workspace)))
+    return out
+
+
+def _seed_arguments(seed):
+    """-> (value, device word pointer, tensors to keep on the device of the call)"""
+    if isinstance(seed, torch.Tensor):
+        _seed_word(seed, 'seed')
+        return 0, seed.data_ptr(), (seed, )
+    return seed & 0xffffffffffffffff, 0, ()
+
+
+def _row_numbers(idx: torch.Tensor, x: torch.Tensor) -> int:
+    if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != x.device or not idx.is_contiguous():
+        raise FewbitHipError('idx must be a contiguous 1-D int64 tensor on the device of x')
+    return idx.numel()
+
+
+def sampled_dct_zext(x: torch.Tensor, rows: int, idx: torch.Tensor, scale: float = 1.0, out: Optional[torch.Tensor] = None,
+                     workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+    """``scale * dct(cat(x, zeros), dim=0, norm='ortho')[idx]`` at length ``rows`` (a row count of ``cabi.SAMPLED_ROWS``, e.g.
+    ``sampled_rows_ceil(x.shape[0])``) for a 2-D ``x`` of 1 .. ``rows`` rows, without the padded copy: the missing rows are zeros the kernel
+    never loads, and nothing behind the last row of ``x`` is read.  ``idx``: int64 row numbers in ``[0, rows)`` on the device of ``x``.  Bit
+    for bit ``cabi.sampled_dct`` of the zero-filled copy; the pair contract of ``cabi.sampled_dct`` holds.
+
+    With rows drawn uniformly from ``[0, rows)`` and ``scale = sqrt(rows / p)`` this is a sketch ``S x`` with ``E[S^T S] = I`` over the rows of
+    ``x`` (include/fewbit_hipx.h) -- unbiased like the layer's own, but not the reference's ``dct(x)[idx]`` at length ``x.shape[0]``."""
+    proj = _row_numbers(idx, x)
+    return _zext_call('sampled_dct_zext', x, rows, proj, (), x.dtype, 'proj x features tensor of the dtype of x', out, workspace, (idx, ),
+                      lambda dt, xp, n, valid, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dct_zext(
+                          dt, xp, n, valid, features, ld, idx.data_ptr(), proj, scale, op, wp, wb, _stream(stream, x.device)))
+
+
+def sampled_dct_zext_seeded(x: torch.Tensor, rows: int, p: int, seed, scale: float = 1.0, out: Optional[torch.Tensor] = None,
+                            workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+    """``sampled_dct_zext(x, rows, cabi.sampled_rows(seed, rows, p))`` without the array of row numbers (``seed``: an int, or a one-element
+    int64 tensor on the device of ``x`` that is read when the kernel runs, as in ``cabi.sampled_dct_seeded``)"""
+    value, word, others = _seed_arguments(seed)
+    return _zext_call('sampled_dct_zext', x, rows, p, (), x.dtype, 'proj x features tensor of the dtype of x', out, workspace, others,
+                      lambda dt, xp, n, valid, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dct_zext_seeded(
+                          dt, xp, n, valid, features, ld, value, word, p, scale, op, wp, wb, _stream(stream, x.device)))
+
+
+def _dft_out_dtype(x: torch.Tensor, out_dtype: Optional[torch.dtype]) -> torch.dtype:
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, x.dtype):
+        raise FewbitHipError(f'out_dtype must be torch.float32 or the dtype of x (got {out_dtype})')
+    return out_dtype
+
+
+def sampled_dft_zext(x: torch.Tensor, rows: int, idx: torch.Tensor, scale: float = 1.0, out_dtype: Optional[torch.dtype] = None,
+                     out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+    """``scale * torch.fft.fft(cat(x, zeros), dim=0, norm='ortho')[idx]`` at length ``rows`` as a ``(2, proj, features)`` tensor (real plane,
+    imaginary plane) of ``out_dtype``: ``sampled_dft`` of the zero-filled copy, bit for bit, without the copy (see ``sampled_dct_zext``)"""
+    proj, odt = _row_numbers(idx, x), _dft_out_dtype(x, out_dtype)
+    return _zext_call('sampled_dft_zext', x, rows, proj, (2, ), odt, '2 x proj x features tensor of out_dtype', out, workspace, (idx, ),
+                      lambda dt, xp, n, valid, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dft_zext(
+                          dt, xp, n, valid, features, ld, idx.data_ptr(), proj, scale, DTYPES[odt], op, wp, wb, _stream(stream, x.device)))
+
+
+def sampled_dft_zext_seeded(x: torch.Tensor, rows: int, p: int, seed, scale: float = 1.0, out_dtype: Optional[torch.dtype] = None,
+                            out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+    """``sampled_dft_zext(x, rows, cabi.sampled_rows(seed, rows, p))`` without the array of row numbers (``seed`` as in ``sampled_dft_seeded``)"""
+    (value, word, others), odt = _seed_arguments(seed), _dft_out_dtype(x, out_dtype)
+    return _zext_call('sampled_dft_zext', x, rows, p, (2, ), odt, '2 x proj x features tensor of out_dtype', out, workspace, others,
+                      lambda dt, xp, n, valid, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dft_zext_seeded(
+                          dt, xp, n, valid, features, ld, value, word, p, scale, DTYPES[odt], op, wp, wb, _stream(stream, x.device)))
 
 
 # ---- column sampling of LinearCRS (fewbit_amd/csrc/fewbit_crs.hip): the columns of a seed, the gather of forward, the scatter of backward ----

@@ -58,6 +58,16 @@
 #include "fewbit_hip.h"
 #include "fewbit_philox.h"
 
+// Units 0 .. 2 (and the single-unit build) are libfewbit_hip.so's.  Units 3 .. 5 (-DFEWBIT_DCT_TU=3 / 4 / 5 = FEWBIT_F32 / F16 / BF16 + 3) are
+// the companion library's: the zero-extended DCT (fewbit_hipx_sampled_dct_zext, include/fewbit_hipx.h) -- pass A is fewbit_fft4.h's
+// pass_a_zext_kernel in Makhoul's order, pass B is this file's, compiled a second time under a name of its own.
+#ifndef FEWBIT_DCT_TU
+#define FEWBIT_DCT_TU -1
+#endif
+#if FEWBIT_DCT_TU >= 3
+#include "fewbit_hipx.h"
+#endif
+
 #define FEWBIT_HIDDEN __attribute__((visibility("hidden")))
 
 namespace fewbit_hip {
@@ -137,6 +147,9 @@ __global__ __launch_bounds__(kThreadsA, (N1 > 128 ? 2 : 4)) void dct_pass_a_kern
 }
 
 // ---- pass B -----------------------------------------------------------------------------------------------------------------
+#if FEWBIT_DCT_TU >= 3
+inline namespace companion {                // (the companion library's copies: symbols of their own)
+#endif
 // grid (N1 / 2 + 1, half tiles of 16 complex columns): residues k1 = u and (N1 - u) % N1.  The LDS tile is [N2][2][16]: the two
 // residue rows sit side by side, so that a half-wave still touches 256 contiguous bytes per position and one butterfly serves
 // both rows -- to the transform it is one row of 32 columns.
@@ -266,11 +279,17 @@ __global__ __launch_bounds__(kThreadsB, (N2 > 128 ? 2 : 4)) void dct_pass_b_kern
     }
 }
 
+#if FEWBIT_DCT_TU >= 3
+}  // namespace companion
+#endif
+
 // ---- host side (fewbit_fft4.h: the checks, the dispatch and the LDS opt-in of both pairs) ------------------------------------------
+#if FEWBIT_DCT_TU < 3
 struct Dct {
     static constexpr const char *kName = "sampled_dct", *kWorkspace = "fewbit_hip_sampled_dct_workspace";
     static constexpr int (*fail)(int, const char *, ...) = fewbit_hip::fail;
-    static constexpr bool kSeededLast = true;
+    static constexpr bool kSeededLast = true, kZext = false;
+    using PassB = Dct;
     template <int DT, int N1, int N2, typename ROWS> static constexpr auto pass_a() { return &dct_pass_a_kernel<DT, N1, N2, ROWS>; }
     template <int DT, int N1, int N2> static constexpr auto pass_b() { return &dct_pass_b_kernel<DT, N1, N2>; }
     template <int N1, int N2> static constexpr size_t lds_b() { return lds_bytes_b<N2>(N1 * N2); }
@@ -280,9 +299,6 @@ struct Dct {
 // The file is compiled as three translation units in parallel, one per dtype (-DFEWBIT_DCT_TU=0 / 1 / 2 = FEWBIT_F32 / F16 / BF16: 114
 // kernels each; the C entry points with unit 0), and linked into the one library -- 50 s instead of 2.5 min; without the define everything
 // is one unit (make variant).
-#ifndef FEWBIT_DCT_TU
-#define FEWBIT_DCT_TU -1
-#endif
 #if FEWBIT_DCT_TU >= 0
 FB_FFT4_UNIT(, Dct, FEWBIT_DCT_TU)
 #endif
@@ -290,6 +306,31 @@ FB_FFT4_UNIT(, Dct, FEWBIT_DCT_TU)
 FB_FFT4_UNIT(extern, Dct, FEWBIT_F16)
 FB_FFT4_UNIT(extern, Dct, FEWBIT_BF16)
 #endif
+#else  // FEWBIT_DCT_TU >= 3: the zero-extended pair of the companion library (its error text: fewbit_hipx_last_error)
+}  // namespace dct
+namespace dft {
+FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+}
+namespace dct {
+struct DctZext {
+    static constexpr const char *kName = "sampled_dct_zext", *kWorkspace = "fewbit_hipx_sampled_dft_workspace";
+    static constexpr int (*fail)(int, const char *, ...) = dft::fail;
+    static constexpr bool kSeededLast = false, kZext = true;
+    using PassB = DctZext;
+    template <int DT, int N1, int N2, typename ROWS> static constexpr auto pass_a() { return &pass_a_zext_kernel<RowsMakhoul, DT, N1, N2, ROWS>; }
+    template <int DT, int N1, int N2> static constexpr auto pass_b() { return &dct_pass_b_kernel<DT, N1, N2>; }
+    template <int N1, int N2> static constexpr size_t lds_b() { return lds_bytes_b<N2>(N1 * N2); }
+    template <int DT> static int opt_in_b() { return opt_in_pass_b<DctZext, DT>(); }
+    static float factor(double scale, size_t) { return static_cast<float>(scale); }
+};
+
+// three units, one per dtype: 76 pass A and 38 pass B kernels each; the C entry points with unit 3
+FB_FFT4_UNIT(, DctZext, FEWBIT_DCT_TU - 3)
+#if FEWBIT_DCT_TU == 3
+FB_FFT4_UNIT(extern, DctZext, FEWBIT_F16)
+FB_FFT4_UNIT(extern, DctZext, FEWBIT_BF16)
+#endif
+#endif  // FEWBIT_DCT_TU < 3
 
 }  // namespace dct
 }  // namespace fewbit_hip
@@ -309,12 +350,12 @@ size_t fewbit_hip_sampled_dct_workspace(int dtype, size_t rows, size_t features,
 
 int fewbit_hip_sampled_dct(int dtype, const void *m, size_t rows, size_t features, size_t ld, const int64_t *idx, size_t proj, double scale, void *out,
                            void *workspace, size_t workspace_bytes, void *stream) {
-    return run<Dct>(dtype, dtype, m, rows, features, ld, RowsInMemory{idx}, proj, scale, out, workspace, workspace_bytes, stream);
+    return run<Dct>(dtype, dtype, m, rows, rows, features, ld, RowsInMemory{idx}, proj, scale, out, workspace, workspace_bytes, stream);
 }
 
 int fewbit_hip_sampled_dct_seeded(int dtype, const void *m, size_t rows, size_t features, size_t ld, uint64_t seed, const uint64_t *seed_device, size_t proj,
                                   double scale, void *out, void *workspace, size_t workspace_bytes, void *stream) {
-    return run<Dct>(dtype, dtype, m, rows, features, ld, rows_of_seed(seed, seed_device), proj, scale, out, workspace, workspace_bytes, stream);
+    return run<Dct>(dtype, dtype, m, rows, rows, features, ld, rows_of_seed(seed, seed_device), proj, scale, out, workspace, workspace_bytes, stream);
 }
 
 int fewbit_hip_sampled_rows(uint64_t seed, size_t rows, size_t proj, int64_t *idx) {
@@ -336,3 +377,23 @@ int fewbit_hip_sampled_rows(uint64_t seed, size_t rows, size_t proj, int64_t *id
 
 }  // extern "C"
 #endif  // FEWBIT_DCT_TU <= 0
+
+#if FEWBIT_DCT_TU == 3
+using namespace fewbit_hip;
+using namespace fewbit_hip::dct;
+
+extern "C" {
+
+int fewbit_hipx_sampled_dct_zext(int dtype, const void *m, size_t rows, size_t valid_rows, size_t features, size_t ld, const int64_t *idx, size_t proj,
+                                 double scale, void *out, void *workspace, size_t workspace_bytes, void *stream) {
+    return run<DctZext>(dtype, dtype, m, rows, valid_rows, features, ld, RowsInMemory{idx}, proj, scale, out, workspace, workspace_bytes, stream);
+}
+
+int fewbit_hipx_sampled_dct_zext_seeded(int dtype, const void *m, size_t rows, size_t valid_rows, size_t features, size_t ld, uint64_t seed,
+                                        const uint64_t *seed_device, size_t proj, double scale, void *out, void *workspace, size_t workspace_bytes,
+                                        void *stream) {
+    return run<DctZext>(dtype, dtype, m, rows, valid_rows, features, ld, rows_of_seed(seed, seed_device), proj, scale, out, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"
+#endif  // FEWBIT_DCT_TU == 3

@@ -238,11 +238,23 @@ __global__ __launch_bounds__(kThreadsB, (N2 > 128 ? 2 : 4)) void dft_pass_b_kern
 struct Dft {
     static constexpr const char *kName = "sampled_dft", *kWorkspace = "fewbit_hipx_sampled_dft_workspace";
     static constexpr int (*fail)(int, const char *, ...) = dft::fail;
-    static constexpr bool kSeededLast = false;
+    static constexpr bool kSeededLast = false, kZext = false;
+    using PassB = Dft;
+    template <int DT> static int opt_in_b() { return opt_in_dtype<Dft, DT>(); }                // (of both passes: the pair has one opt-in)
     template <int DT, int N1, int N2, typename ROWS> static constexpr auto pass_a() { return &dft_pass_a_kernel<DT, N1, N2, ROWS>; }
     template <int ODT, int N1, int N2> static constexpr auto pass_b() { return &dft_pass_b_kernel<ODT, N1, N2>; }
     template <int N1, int N2> static constexpr size_t lds_b() { return (2 * N2 * CB + N2) * sizeof(f32x2); }      // (no W_4N tables)
     static float factor(double scale, size_t rows) { return static_cast<float>(scale / std::sqrt(static_cast<double>(rows))); }
+};
+
+// The zero-extended pair (fewbit_hipx_sampled_dft_zext): fewbit_fft4.h's pass_a_zext_kernel on the rows in their order, and Dft's pass B
+struct DftZext {
+    static constexpr const char *kName = "sampled_dft_zext", *kWorkspace = "fewbit_hipx_sampled_dft_workspace";
+    static constexpr int (*fail)(int, const char *, ...) = dft::fail;
+    static constexpr bool kSeededLast = false, kZext = true;
+    using PassB = Dft;
+    template <int DT, int N1, int N2, typename ROWS> static constexpr auto pass_a() { return &pass_a_zext_kernel<RowsInOrder, DT, N1, N2, ROWS>; }
+    static float factor(double scale, size_t rows) { return Dft::factor(scale, rows); }
 };
 
 #ifndef FEWBIT_DFT_TU
@@ -263,13 +275,26 @@ int fail(int code, const char *fmt, ...) {
 }  // namespace dft
 
 // Three translation units, one per dtype (-DFEWBIT_DFT_TU=0 / 1 / 2 = FEWBIT_F32 / F16 / BF16): pass A reading that dtype, pass B writing
-// it and its opt-in; the C entry points with unit 0.  Without the define everything is one unit.
-#if FEWBIT_DFT_TU >= 0
+// it and its opt-in; the C entry points with unit 0.  Units 3 / 4 / 5: pass A of the zero-extended pair reading F32 / F16 / BF16 and its
+// opt-in (pass B is the plain pair's, of units 0 .. 2).  Without the define everything is one unit.
+#if FEWBIT_DFT_TU >= 0 && FEWBIT_DFT_TU < 3
 FB_FFT4_UNIT(, dft::Dft, FEWBIT_DFT_TU)
 #endif
 #if FEWBIT_DFT_TU == 0
 FB_FFT4_UNIT(extern, dft::Dft, FEWBIT_F16)
 FB_FFT4_UNIT(extern, dft::Dft, FEWBIT_BF16)
+FB_FFT4_UNIT_A(extern, dft::DftZext, FEWBIT_F32)
+FB_FFT4_UNIT_A(extern, dft::DftZext, FEWBIT_F16)
+FB_FFT4_UNIT_A(extern, dft::DftZext, FEWBIT_BF16)
+#endif
+#if FEWBIT_DFT_TU >= 3
+extern template int dct::opt_in_dtype<dft::Dft, FEWBIT_DFT_TU - 3>();
+FB_FFT4_UNIT_A(, dft::DftZext, FEWBIT_DFT_TU - 3)
+#endif
+#if FEWBIT_DFT_TU < 0
+FB_FFT4_UNIT_A(, dft::DftZext, FEWBIT_F32)
+FB_FFT4_UNIT_A(, dft::DftZext, FEWBIT_F16)
+FB_FFT4_UNIT_A(, dft::DftZext, FEWBIT_BF16)
 #endif
 
 }  // namespace fewbit_hip
@@ -292,12 +317,25 @@ size_t fewbit_hipx_sampled_dft_workspace(int dtype, size_t rows, size_t features
 
 int fewbit_hipx_sampled_dft(int dtype, const void *m, size_t rows, size_t features, size_t ld, const int64_t *idx, size_t proj, double scale, int out_dtype,
                             void *out, void *workspace, size_t workspace_bytes, void *stream) {
-    return run<Dft>(dtype, out_dtype, m, rows, features, ld, RowsInMemory{idx}, proj, scale, out, workspace, workspace_bytes, stream);
+    return run<Dft>(dtype, out_dtype, m, rows, rows, features, ld, RowsInMemory{idx}, proj, scale, out, workspace, workspace_bytes, stream);
 }
 
 int fewbit_hipx_sampled_dft_seeded(int dtype, const void *m, size_t rows, size_t features, size_t ld, uint64_t seed, const uint64_t *seed_device, size_t proj,
                                    double scale, int out_dtype, void *out, void *workspace, size_t workspace_bytes, void *stream) {
-    return run<Dft>(dtype, out_dtype, m, rows, features, ld, rows_of_seed(seed, seed_device), proj, scale, out, workspace, workspace_bytes, stream);
+    return run<Dft>(dtype, out_dtype, m, rows, rows, features, ld, rows_of_seed(seed, seed_device), proj, scale, out, workspace, workspace_bytes, stream);
+}
+
+size_t fewbit_hipx_sampled_rows_ceil(size_t rows) { return rows_ceil(rows); }
+
+int fewbit_hipx_sampled_dft_zext(int dtype, const void *m, size_t rows, size_t valid_rows, size_t features, size_t ld, const int64_t *idx, size_t proj,
+                                 double scale, int out_dtype, void *out, void *workspace, size_t workspace_bytes, void *stream) {
+    return run<DftZext>(dtype, out_dtype, m, rows, valid_rows, features, ld, RowsInMemory{idx}, proj, scale, out, workspace, workspace_bytes, stream);
+}
+
+int fewbit_hipx_sampled_dft_zext_seeded(int dtype, const void *m, size_t rows, size_t valid_rows, size_t features, size_t ld, uint64_t seed,
+                                        const uint64_t *seed_device, size_t proj, double scale, int out_dtype, void *out, void *workspace,
+                                        size_t workspace_bytes, void *stream) {
+    return run<DftZext>(dtype, out_dtype, m, rows, valid_rows, features, ld, rows_of_seed(seed, seed_device), proj, scale, out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -372,6 +372,103 @@ __device__ __forceinline__ void sort_rows(ROWS rows, size_t proj, int *__restric
     __syncthreads();                                                   // (the tile takes this LDS over)
 }
 
+// ---- pass A of a zero-extended call ---------------------------------------------------------------------------------------------
+// The matrix has valid_rows <= N rows in memory and counts as N rows, the missing ones zero.  ORDER says which row of it the point n of
+// the transformed sequence is: the DFT's is row n, the DCT's Makhoul's reordering (fewbit_dct.hip, step 1).
+struct RowsInOrder {
+    template <int N> static __device__ __forceinline__ size_t row(int n) { return static_cast<size_t>(n); }
+};
+struct RowsMakhoul {
+    template <int N> static __device__ __forceinline__ size_t row(int n) { return n < N / 2 ? 2 * static_cast<size_t>(n) : 2 * static_cast<size_t>(N - 1 - n) + 1; }
+};
+// dct_pass_a_kernel / dft_pass_a_kernel (fewbit_dct.hip, fewbit_dft.hip: the algorithm, the tile, the intermediate) with ONE difference: a
+// 16-byte piece whose row is >= valid_rows is zeros in registers and no memory request is made for it, so nothing at or beyond row
+// valid_rows of x is read and the pass moves valid_rows / N of the bytes.  Everything after the tile is filled is the same arithmetic on
+// the same values as the plain kernel's on a zero-filled copy: the same bits.  One template for both orders (the plain kernels are two
+// copies to keep the machine code they were measured as; these are new).
+// WHICH COPY LEADS.  Pass A now exists three times: dct_pass_a_kernel, dft_pass_a_kernel and this one.  The plain kernels are the
+// authoritative text: a change to pass A is made there first and then repeated here line by line (the bit-equality test of
+// tests/test_gpu_transform_zext.py fails when this copy is left behind).  Once a change of the plain kernels' machine code is acceptable,
+// both can be pass_a_zext_kernel<ORDER> with valid_rows = N and the three become one.
+// How a piece is left out.  A load under a lane-divergent `if (row < valid_rows)` makes hipcc wait for each load where the branches join
+// (the tile's loads then follow one another: seen in the assembly of this kernel written that way).  So the pieces of a full tile are
+// buffer loads through a descriptor of the valid_rows x ld elements of x: a piece of a missing row is given the offset kBeyondZext, which
+// the hardware's range check (offset >= the descriptor's bytes) answers with zeros without a memory access -- no branch, all loads in
+// flight at once as in the plain kernel.  The descriptor's size is 32 bits: valid_rows x ld elements must be below 4 GiB (zext_span_ok;
+// the host refuses more).  The edge tile (features % 64 != 0), loaded element by element as in the plain kernel, keeps the `if`.
+constexpr uint32_t kBeyondZext = 0xfffffff0u;
+inline bool zext_span_ok(size_t valid_rows, size_t ld, int dtype) {
+    const size_t row_bytes = ld * (dtype == FEWBIT_F32 ? 4 : 2);
+    return row_bytes == 0 || valid_rows <= static_cast<size_t>(kBeyondZext) / row_bytes;
+}
+template <typename ORDER, int DT, int N1, int N2, typename ROWS>
+__global__ __launch_bounds__(kThreadsA, (N1 > 128 ? 2 : 4)) void pass_a_zext_kernel(const void *__restrict__ x, size_t valid_rows, size_t features, size_t ld,
+                                                                   f32x2 *__restrict__ inter, ROWS rows, size_t proj, int *__restrict__ offsets,
+                                                                   Sample *__restrict__ sorted) {
+    constexpr int N = N1 * N2, kCoarse = coarse_entries(N), kThreads = kThreadsA, kSlots = kThreads / C;
+    static_assert(kRowsA == 1, "one n2 per workgroup");
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    f32x2 *tile = reinterpret_cast<f32x2 *>(lds_raw);                 // [N1][C]
+    f32x2 *tw = tile + N1 * C;                                        // W_N1^m, m < N1
+    f32x2 *fine = tw + N1, *coarse = fine + kFine;                    // W_N^m (m < 128), W_N^{128 m}
+    const int tid = threadIdx.x, c = tid % C, slot = tid / C;
+    const int b = blockIdx.x;
+    const size_t t = blockIdx.y, f0 = t * kFeatures;
+    if (blockIdx.x == 0 && blockIdx.y == 0) sort_rows<N1, N, ROWS>(rows, proj, offsets, sorted, reinterpret_cast<int *>(lds_raw), tid);
+
+    constexpr int PF = In<DT>::kPieceFeatures, PPS = In<DT>::kPiecesPerSegment, kTotal = N1 * PPS, kPieces = (kTotal + kThreads - 1) / kThreads;
+    constexpr size_t kElementBytes = DT == FEWBIT_F32 ? 4 : 2;
+    // the rows of x that exist (built from kernel arguments only: uniform)
+    const __amdgpu_buffer_rsrc_t held = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(x), 0, static_cast<int>(static_cast<uint32_t>(valid_rows * ld * kElementBytes)), 0x00020000);
+    auto fill_tile = [&](auto full) __attribute__((always_inline)) {
+        u32x4 raw[kPieces];
+#pragma unroll
+        for (int i = 0; i < kPieces; ++i) {
+            const int pid = tid + kThreads * i, n1 = pid / PPS, piece = pid % PPS;
+            if (kTotal % kThreads != 0 && pid >= kTotal) break;
+            const size_t row = ORDER::template row<N>(N2 * n1 + b);
+            if constexpr (decltype(full)::value) {
+                const size_t at = (row * ld + f0 + static_cast<size_t>(piece) * PF) * kElementBytes;
+                raw[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(held, row < valid_rows ? static_cast<uint32_t>(at) : kBeyondZext, 0, 0));
+            } else {
+                raw[i] = u32x4{0u, 0u, 0u, 0u};
+                if (row < valid_rows) raw[i] = load_piece<DT, false>(x, row, ld, f0, piece, features);
+            }
+        }
+        for (int m = tid; m < N1; m += kThreads) tw[m] = unit(m, N1);
+        for (int m = tid; m < kFine; m += kThreads) fine[m] = unit(m, N);
+        for (int m = tid; m < kCoarse; m += kThreads) coarse[m] = unit(m * kFine, N);
+#pragma unroll
+        for (int i = 0; i < kPieces; ++i) {
+            const int pid = tid + kThreads * i, n1 = pid / PPS, piece = pid % PPS;
+            if (kTotal % kThreads != 0 && pid >= kTotal) break;
+            float v[PF];
+            unpack_piece<DT>(raw[i], v);
+            f32x4 *dst = reinterpret_cast<f32x4 *>(tile + n1 * C + piece * (PF / 2));
+#pragma unroll
+            for (int e = 0; e < PF / 4; ++e) dst[e] = f32x4{v[4 * e], v[4 * e + 1], v[4 * e + 2], v[4 * e + 3]};
+        }
+    };
+    if (f0 + kFeatures <= features) fill_tile(std::true_type{});       // (workgroup-uniform)
+    else fill_tile(std::false_type{});
+    __syncthreads();
+
+    fft_tile<N1, kRowsA, kSlots>(tile, tw, c, slot);
+
+    constexpr int kUnitsTotal = N1 * (C / 2), kUnits = (kUnitsTotal + kThreads - 1) / kThreads;
+#pragma unroll
+    for (int i = 0; i < kUnits; ++i) {
+        const int uid = tid + kThreads * i, c2 = uid % (C / 2), p = uid / (C / 2);
+        if (kUnitsTotal % kThreads != 0 && uid >= kUnitsTotal) break;
+        const int k1 = pos_to_freq<N1>(p), e = b * k1;
+        const f32x2 w = table_unit(fine, coarse, e, kCoarse > 1);
+        const f32x4 z = *reinterpret_cast<const f32x4 *>(tile + p * C + 2 * c2);
+        const f32x2 a = cmul(f32x2{z[0], z[1]}, w), bb = cmul(f32x2{z[2], z[3]}, w);
+        f32x4 *dst = reinterpret_cast<f32x4 *>(inter + (((2 * t + c2 / (CB / 2)) * N1 + k1) * N2 + b) * CB + 2 * (c2 % (CB / 2)));
+        *dst = f32x4{a.x, a.y, bb.x, bb.y};
+    }
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------------
 struct Split { int n1, n2; };
 // rows = N1 x N2.  2^8 .. 2^18: 16 <= N2 <= N1 <= 512, both powers of two (2^17 = 512 x 256 and 2^18 = 512 x 512: 128 KiB tiles, one
@@ -380,23 +477,29 @@ struct Split { int n1, n2; };
 // 192, 80 / 160, 112 / 224, 144 / 288 or 240 (N1 stays a power of two: residues and digit maps of pass A, the k % N1 of pass B).  Pass
 // B's tile is 256 N2 bytes + tables: at most 78 KiB (N2 = 288), two workgroups in the 160 KiB of a CU
 struct RowFamily { int odd, low, high, n1[7]; };       // rows = odd x 2^bits, low <= bits <= high; n1[bits - low]
+constexpr int kLowBits = 8, kHighBits = 18;            // rows = 2^bits: 256 .. 262144
+// N1 grows with the rows up to 128 (four pass-A workgroups per CU) before N2 doubles, and reaches 256 last:
+//  3 x 2^bits, bits = 8 .. 14:  16 x 48, 32 x 48, 32 x 96, 64 x 96, 128 x 96, 128 x 192, 256 x 192
+//  5 x 2^bits, bits = 8 .. 13:  16 x 80, 32 x 80, 64 x 80, 64 x 160, 128 x 160, 256 x 160
+//  7 x 2^bits, bits = 9 .. 13:  32 x 112 (3584), 64 x 112 (7168), 128 x 112 (14336), 128 x 224 (28672), 256 x 224 (57344)
+//  9 x 2^bits, bits = 8 .. 12:  16 x 144 (2304), 32 x 144 (4608), 64 x 144 (9216), 128 x 144 (18432), 128 x 288 (36864)
+// 15 x 2^bits, bits = 8 .. 11:  16 x 240 (3840), 32 x 240 (7680), 64 x 240 (15360), 128 x 240 (30720)
+// (15 and 9 before 5 and 3: a multiple of 15 is one of 3 and of 5)
+constexpr int kRowFamilyCount = 5;
+inline const RowFamily *row_families() {
+    static const RowFamily families[kRowFamilyCount] = {{15, 8, 11, {16, 32, 64, 128}},
+                                                        {9, 8, 12, {16, 32, 64, 128, 128}},
+                                                        {7, 9, 13, {32, 64, 128, 128, 256}},
+                                                        {5, 8, 13, {16, 32, 64, 64, 128, 256}},
+                                                        {3, 8, 14, {16, 32, 32, 64, 128, 128, 256}}};
+    return families;
+}
 inline bool split_rows(size_t rows, Split &s) {
-    if (rows < 256 || rows > 262144) return false;
-    // N1 grows with the rows up to 128 (four pass-A workgroups per CU) before N2 doubles, and reaches 256 last:
-    //  3 x 2^bits, bits = 8 .. 14:  16 x 48, 32 x 48, 32 x 96, 64 x 96, 128 x 96, 128 x 192, 256 x 192
-    //  5 x 2^bits, bits = 8 .. 13:  16 x 80, 32 x 80, 64 x 80, 64 x 160, 128 x 160, 256 x 160
-    //  7 x 2^bits, bits = 9 .. 13:  32 x 112 (3584), 64 x 112 (7168), 128 x 112 (14336), 128 x 224 (28672), 256 x 224 (57344)
-    //  9 x 2^bits, bits = 8 .. 12:  16 x 144 (2304), 32 x 144 (4608), 64 x 144 (9216), 128 x 144 (18432), 128 x 288 (36864)
-    // 15 x 2^bits, bits = 8 .. 11:  16 x 240 (3840), 32 x 240 (7680), 64 x 240 (15360), 128 x 240 (30720)
-    // (15 and 9 before 5 and 3: a multiple of 15 is one of 3 and of 5)
-    static const RowFamily families[5] = {{15, 8, 11, {16, 32, 64, 128}},
-                                          {9, 8, 12, {16, 32, 64, 128, 128}},
-                                          {7, 9, 13, {32, 64, 128, 128, 256}},
-                                          {5, 8, 13, {16, 32, 64, 64, 128, 256}},
-                                          {3, 8, 14, {16, 32, 32, 64, 128, 128, 256}}};
+    if (rows < (static_cast<size_t>(1) << kLowBits) || rows > (static_cast<size_t>(1) << kHighBits)) return false;
+    const RowFamily *families = row_families();
     const RowFamily *family = nullptr;
-    for (const RowFamily &f : families)
-        if (family == nullptr && rows % static_cast<size_t>(f.odd) == 0) family = &f;
+    for (int i = 0; i < kRowFamilyCount; ++i)
+        if (family == nullptr && rows % static_cast<size_t>(families[i].odd) == 0) family = &families[i];
     const size_t two = family != nullptr ? rows / static_cast<size_t>(family->odd) : rows;
     if (!power_of_two(two)) return false;
     int bits = 0;
@@ -410,6 +513,24 @@ inline bool split_rows(size_t rows, Split &s) {
     s.n1 = family->n1[bits - family->low];
     s.n2 = static_cast<int>(rows / static_cast<size_t>(s.n1));
     return true;
+}
+// the smallest row count split_rows takes that is >= rows, from the same table: of 2^bits and of every family the first member that
+// reaches `rows`, and of those the least; 0 for rows = 0 and beyond the largest (what a zero-extended call runs at)
+inline size_t rows_ceil(size_t rows) {
+    if (rows == 0 || rows > (static_cast<size_t>(1) << kHighBits)) return 0;
+    size_t best = 0;
+    auto offer = [&](size_t odd, int low, int high) {
+        for (int bits = low; bits <= high; ++bits) {
+            const size_t n = odd << bits;
+            if (n < rows) continue;
+            if (best == 0 || n < best) best = n;
+            return;
+        }
+    };
+    offer(1, kLowBits, kHighBits);
+    const RowFamily *families = row_families();
+    for (int i = 0; i < kRowFamilyCount; ++i) offer(static_cast<size_t>(families[i].odd), families[i].low, families[i].high);
+    return best;
 }
 // the (N1, N2) split_rows returns: the cases of the launches and of the LDS opt-in
 #define FB_FFT4_SPLITS(X)                                                                                                     \
@@ -439,7 +560,9 @@ inline RowsOfSeed rows_of_seed(uint64_t seed, const uint64_t *device) {
 // ---- the host side of both kernel pairs --------------------------------------------------------------------------------------
 // PAIR (fewbit_dct.hip: Dct, fewbit_dft.hip: Dft) holds what differs between them: its kernels (pass_a<DT, N1, N2, ROWS>() and
 // pass_b<ODT, N1, N2>()), pass B's LDS (lds_b<N1, N2>()), the factor pass B applies (factor(scale, rows)), the prefix of its messages
-// (kName), its workspace query (kWorkspace), its error reporter (fail: each library keeps its own last error) and kSeededLast (below).
+// (kName), its workspace query (kWorkspace), its error reporter (fail: each library keeps its own last error), kSeededLast (below), and
+// what a zero-extended pair differs in: kZext (its pass A is a pass_a_zext_kernel and takes valid_rows) and PassB, the pair whose pass B
+// it runs (a plain pair: itself) -- whose opt_in_b<DT>() reserves the LDS of those kernels.
 template <typename PAIR> int refuse_rows(const char *what, size_t rows) {
     return PAIR::fail(FEWBIT_ERR_UNSUPPORTED, "%s: rows = %zu is none of %s", what, rows, kRowFamilies);
 }
@@ -463,12 +586,14 @@ template <typename PAIR, int DT> int opt_in_dtype() {
     const unsigned long long bit = 1ull << (dev & 63);
     if (done.load(std::memory_order_relaxed) & bit) return FEWBIT_OK;
     int rc = FEWBIT_OK;
+    if constexpr (PAIR::kZext) rc = PAIR::PassB::template opt_in_b<DT>();      // (pass B is another pair's, or has an opt-in of its own)
     // (the order in which a unit first names its kernels is their order in the device module, and the code generated for the last
     // split depends on it: each pair names them in the order of its former host code -- the DCT's seeded pass A after all others)
 #define FB_FFT4_OPT_IN(A, B)                                                                                                  \
     if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_a<DT, A, B, RowsInMemory>(), lds_bytes_a<A>(A * B));   \
     if constexpr (!PAIR::kSeededLast) FB_FFT4_OPT_IN_SEEDED(A, B)                                                             \
-    if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_b<DT, A, B>(), PAIR::template lds_b<A, B>());
+    if constexpr (!PAIR::kZext)                                                                                               \
+        if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_b<DT, A, B>(), PAIR::template lds_b<A, B>());
 #define FB_FFT4_OPT_IN_SEEDED(A, B) \
     if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_a<DT, A, B, RowsOfSeed>(), lds_bytes_a<A>(A * B));
     FB_FFT4_SPLITS(FB_FFT4_OPT_IN)
@@ -479,15 +604,35 @@ template <typename PAIR, int DT> int opt_in_dtype() {
     return rc;
 }
 
+// the LDS opt-in of every pass B of PAIR that writes DT alone: a pair whose pass A is zero-extended only (the DCT's in the companion library)
+template <typename PAIR, int DT> int opt_in_pass_b() {
+    static std::atomic<unsigned long long> done{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_relaxed) & bit) return FEWBIT_OK;
+    int rc = FEWBIT_OK;
+#define FB_FFT4_OPT_IN_B(A, B) \
+    if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_b<DT, A, B>(), PAIR::template lds_b<A, B>());
+    FB_FFT4_SPLITS(FB_FFT4_OPT_IN_B)
+#undef FB_FFT4_OPT_IN_B
+    if (rc == FEWBIT_OK) done.fetch_or(bit, std::memory_order_relaxed);
+    return rc;
+}
+
+// (valid_rows: the rows of m in memory, for a zero-extended pair; a plain pair's kernels do not take it)
 template <typename PAIR, int DT, typename ROWS>
-int launch_a(Split sp, const void *m, size_t features, size_t ld, ROWS idx, size_t proj, f32x2 *inter, int *offsets, Sample *sorted, hipStream_t s) {
+int launch_a(Split sp, const void *m, size_t valid_rows, size_t features, size_t ld, ROWS idx, size_t proj, f32x2 *inter, int *offsets, Sample *sorted, hipStream_t s) {
     const unsigned tiles = static_cast<unsigned>(tiles_of(features));
 #define FB_FFT4_CASE_A(A, B)                                                                                                   \
     if (sp.n1 == A && sp.n2 == B) {                                                                                            \
         static_assert(lds_bytes_a<A>(A * B) >= 2 * (A / 2 + 2) * sizeof(int) && (A / 2 + 2) * sizeof(int) <= kOffsetsBytes,    \
                       "the sort's counters fit pass A's LDS and the offsets their slot");                                      \
         constexpr auto kern = PAIR::template pass_a<DT, A, B, ROWS>();                                                         \
-        hipLaunchKernelGGL(kern, dim3(B, tiles), dim3(kThreadsA), lds_bytes_a<A>(A * B), s, m, features, ld, inter, idx, proj, offsets, sorted); \
+        if constexpr (PAIR::kZext)                                                                                             \
+            hipLaunchKernelGGL(kern, dim3(B, tiles), dim3(kThreadsA), lds_bytes_a<A>(A * B), s, m, valid_rows, features, ld, inter, idx, proj, offsets, sorted); \
+        else                                                                                                                   \
+            hipLaunchKernelGGL(kern, dim3(B, tiles), dim3(kThreadsA), lds_bytes_a<A>(A * B), s, m, features, ld, inter, idx, proj, offsets, sorted); \
         return FEWBIT_OK;                                                                                                      \
     }
     FB_FFT4_SPLITS(FB_FFT4_CASE_A)
@@ -511,11 +656,14 @@ int launch_b(Split sp, const f32x2 *inter, const int *offsets, const Sample *sor
 
 // the host functions of dtype DT: a pair is compiled as three translation units, one per dtype, each instantiating its own (KEYWORD
 // empty); the unit with the C entry points declares the other two (KEYWORD extern).  Used in namespace fewbit_hip or fewbit_hip::dct.
-#define FB_FFT4_UNIT(KEYWORD, PAIR, DT)                                                                                        \
+#define FB_FFT4_UNIT_A(KEYWORD, PAIR, DT)                                                                                      \
     KEYWORD template int dct::opt_in_dtype<PAIR, DT>();                                                                        \
-    KEYWORD template int dct::launch_a<PAIR, DT, dct::RowsInMemory>(dct::Split, const void *, size_t, size_t, dct::RowsInMemory, size_t, dct::f32x2 *, int *, dct::Sample *, hipStream_t); \
-    KEYWORD template int dct::launch_a<PAIR, DT, dct::RowsOfSeed>(dct::Split, const void *, size_t, size_t, dct::RowsOfSeed, size_t, dct::f32x2 *, int *, dct::Sample *, hipStream_t); \
+    KEYWORD template int dct::launch_a<PAIR, DT, dct::RowsInMemory>(dct::Split, const void *, size_t, size_t, size_t, dct::RowsInMemory, size_t, dct::f32x2 *, int *, dct::Sample *, hipStream_t); \
+    KEYWORD template int dct::launch_a<PAIR, DT, dct::RowsOfSeed>(dct::Split, const void *, size_t, size_t, size_t, dct::RowsOfSeed, size_t, dct::f32x2 *, int *, dct::Sample *, hipStream_t);
+#define FB_FFT4_UNIT_B(KEYWORD, PAIR, DT) \
     KEYWORD template int dct::launch_b<PAIR, DT>(dct::Split, const dct::f32x2 *, const int *, const dct::Sample *, size_t, size_t, float, void *, hipStream_t);
+#define FB_FFT4_UNIT(KEYWORD, PAIR, DT) FB_FFT4_UNIT_A(KEYWORD, PAIR, DT) FB_FFT4_UNIT_B(KEYWORD, PAIR, DT)
+// (a zero-extended pair whose pass B is another pair's has a unit of pass A alone: FB_FFT4_UNIT_A)
 
 // calls f(std::integral_constant<int, DT>) for the run-time dtype (one of known_dtype)
 template <typename F> int with_dtype(int dtype, F &&f) {
@@ -527,9 +675,10 @@ template <typename F> int with_dtype(int dtype, F &&f) {
 }
 
 // One call of a pair: the argument checks, the LDS opt-in of the dtypes involved, the workspace carved into [inter | offsets | sorted],
-// pass A reading `dtype`, pass B writing `out_dtype` (the DCT's is its dtype), and the launch error.
+// pass A reading `dtype`, pass B writing `out_dtype` (the DCT's is its dtype), and the launch error.  valid_rows: the rows m holds, of a
+// zero-extended pair (a plain pair: rows).
 template <typename PAIR, typename ROWS>
-int run(int dtype, int out_dtype, const void *m, size_t rows, size_t features, size_t ld, ROWS idx, size_t proj, double scale, void *out,
+int run(int dtype, int out_dtype, const void *m, size_t rows, size_t valid_rows, size_t features, size_t ld, ROWS idx, size_t proj, double scale, void *out,
         void *workspace, size_t workspace_bytes, void *stream) {
     const char *name = PAIR::kName;
     if (!known_dtype(dtype)) return PAIR::fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: unknown dtype %d", name, dtype);
@@ -539,6 +688,9 @@ int run(int dtype, int out_dtype, const void *m, size_t rows, size_t features, s
         if ((reinterpret_cast<uintptr_t>(idx.device) & 7) != 0) return PAIR::fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the seed word in device memory must be 8-byte aligned", name);
     Split sp;
     if (!split_rows(rows, sp)) return refuse_rows<PAIR>(name, rows);
+    if (valid_rows == 0 || valid_rows > rows) return PAIR::fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: valid_rows = %zu is not in 1 .. rows = %zu", name, valid_rows, rows);
+    if constexpr (PAIR::kZext)
+        if (!zext_span_ok(valid_rows, ld, dtype)) return PAIR::fail(FEWBIT_ERR_UNSUPPORTED, "%s: valid_rows x ld = %zu x %zu elements span 4 GiB or more", name, valid_rows, ld);
     bool null = m == nullptr || out == nullptr;
     if constexpr (!ROWS::kSeeded) null = null || idx.idx == nullptr;
     if (null) return PAIR::fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer", name);
@@ -556,10 +708,10 @@ int run(int dtype, int out_dtype, const void *m, size_t rows, size_t features, s
     f32x2 *inter = static_cast<f32x2 *>(workspace);
     int *offsets = reinterpret_cast<int *>(static_cast<uint8_t *>(workspace) + inter_bytes(rows, features));
     Sample *sorted = reinterpret_cast<Sample *>(reinterpret_cast<uint8_t *>(offsets) + kOffsetsBytes);
-    if (const int rc = with_dtype(dtype, [&](auto dt) { return launch_a<PAIR, decltype(dt)::value, ROWS>(sp, m, features, ld, idx, proj, inter, offsets, sorted, s); }))
+    if (const int rc = with_dtype(dtype, [&](auto dt) { return launch_a<PAIR, decltype(dt)::value, ROWS>(sp, m, valid_rows, features, ld, idx, proj, inter, offsets, sorted, s); }))
         return rc;
     const float factor = PAIR::factor(scale, rows);
-    if (const int rc = with_dtype(out_dtype, [&](auto dt) { return launch_b<PAIR, decltype(dt)::value>(sp, inter, offsets, sorted, proj, features, factor, out, s); }))
+    if (const int rc = with_dtype(out_dtype, [&](auto dt) { return launch_b<typename PAIR::PassB, decltype(dt)::value>(sp, inter, offsets, sorted, proj, features, factor, out, s); }))
         return rc;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return PAIR::fail(FEWBIT_ERR_LAUNCH, "%s: %s", name, hipGetErrorString(e));

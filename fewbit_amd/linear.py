@@ -50,6 +50,14 @@ sampled rows are, like ``S``, a function of the call's 64-bit seed that the kern
 ``fewbit_hipx_sampled_dft_seeded``; ``cabi.sampled_rows(seed, rows, p)`` is the same function on the host): no ``randint`` launch, no saved
 RNG state, and the layer can be captured into a hipGraph.  ``use_native_sketch(False)`` selects torch.fft + randint.  SURVEY section 8f, row 4.
 
+Any other row count (100 or 50 sequences, the short last batch of an epoch): torch.fft by default; with ``use_row_extension(True)`` (or
+``FEWBIT_EXTEND_ROWS=1``) the kernel pairs at the next supported row count N' (``cabi_x.sampled_rows_ceil``) by zero extension
+(``fewbit_hipx_sampled_dct_zext_seeded`` / ``_dft_zext_seeded``: the missing rows are zeros pass A never loads, there is no padded copy).
+With R sampling p of N' rows uniformly with replacement, C' the orthonormal transform of length N' and P the N' x N matrix that appends
+the zero rows, S = sqrt(N' / p) R C' P has E[S^T S] = (N' / p) P^T C'^T (p / N') C' P = P^T P = I_N, so ``(S G)^T (S X)`` with the same R in
+forward (scale N' / p) and backward (scale 1) is an unbiased estimate of ``G^T X``.  It is an estimator of the same kind as the layer's own
+but NOT the reference's ``dct(X)[idx]`` at length N -- another random variable with the same mean -- which is why it is opt-in.
+
 Column sampling: ``linear_crs`` / ``LinearCRS`` on fp32 / fp16 / bf16 GPU tensors follows the same contract on the kernels of
 ``fewbit_amd/csrc/fewbit_crs.hip`` (companion library: ``fewbit_hipx_crs_gather``, ``fewbit_hipx_crs_scatter``): the drawn columns are a function
 of the call's seed (``cabi_x.crs_columns(seed, in_features, nopairs)`` on the host), forward is one gather-and-scale call, backward one GEMM and
@@ -67,7 +75,7 @@ import torch.nn.functional as F
 from .fft import dct
 
 __all__ = ('MATMUL_TYPES', 'projection_dim', 'linear_crs', 'linear_grp', 'linear_randomized', 'LinearCRS', 'LinearGRP',
-           'RandomizedLinear', 'use_native_sketch', 'sampled_transform', 'sampled_transform_path')
+           'RandomizedLinear', 'use_native_sketch', 'use_row_extension', 'sampled_transform', 'sampled_transform_path')
 
 MATMUL_TYPES = ('dct', 'dft', 'gaussian', 'rademacher')
 
@@ -124,6 +132,22 @@ def use_native_sketch(on: Optional[bool] = None) -> bool:
     prev = _NATIVE_SKETCH
     if on is not None:
         _NATIVE_SKETCH = bool(on)
+    return prev
+
+
+_EXTEND_ROWS = os.environ.get('FEWBIT_EXTEND_ROWS', '0') in ('1', 'yes', 'true')
+
+
+def use_row_extension(on: Optional[bool] = None) -> bool:
+    """Query / set whether 'dct' / 'dft' on a 2-D fp32 / fp16 / bf16 GPU tensor whose row count N has no kernel run on the kernel pairs at
+    the next supported count N' by zero extension (``cabi_x.sampled_*_zext_seeded``) instead of torch.fft.  Off by default (environment:
+    ``FEWBIT_EXTEND_ROWS=1`` turns it on): the zero-extended estimator is unbiased (module docstring) but is not the reference's
+    ``dct(X)[idx]`` at length N.  Needs ``use_native_sketch()`` on; row counts with a kernel, and those above 262144, are not affected.
+    Returns the previous setting."""
+    global _EXTEND_ROWS
+    prev = _EXTEND_ROWS
+    if on is not None:
+        _EXTEND_ROWS = bool(on)
     return prev
 
 
@@ -216,11 +240,17 @@ def _native_sketch(kind: str, mat: torch.Tensor, p: int, seed, scale: float) -> 
     return cabi.sketch(kind, _unit_stride(mat), p, seed, scale)
 
 
-def _native_transform(kind: str, mat: torch.Tensor, p: int, seed, scale: float, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+def _native_transform(kind: str, mat: torch.Tensor, p: int, seed, scale: float, out_dtype: Optional[torch.dtype] = None, rows: Optional[int] = None) -> torch.Tensor:
     """``scale * transform(mat, dim=0, norm='ortho')[rows(seed)]`` on this package's kernel pair: M is read once, one fp32 intermediate goes
     out and back, only the p sampled rows are written (the torch formulation materialises the whole transform in fp32 first).  'dct': a
     ``(p, features)`` tensor of the dtype of ``mat``; 'dft': a ``(2, p, features)`` tensor of ``out_dtype`` (default: the dtype of ``mat``),
-    ``[0]`` the real part, ``[1]`` the imaginary part"""
+    ``[0]`` the real part, ``[1]`` the imaginary part.  ``rows`` other than the rows of ``mat``: the transform of that length of ``mat``
+    followed by zero rows (the zero-extended pair; the sampled rows are those of ``seed`` in ``[0, rows)``)"""
+    if rows is not None and rows != mat.shape[0]:
+        from . import cabi_x
+        if kind == 'dct':
+            return cabi_x.sampled_dct_zext_seeded(_unit_stride(mat), rows, p, seed, scale)
+        return cabi_x.sampled_dft_zext_seeded(_unit_stride(mat), rows, p, seed, scale, out_dtype)
     if kind == 'dct':
         from . import cabi
         return cabi.sampled_dct_seeded(_unit_stride(mat), p, seed, scale)
@@ -282,12 +312,36 @@ def _transform_rows(kind: str, rows: int) -> bool:
     return ok
 
 
+def _zext_span_ok(rows: int, ld: int, itemsize: int) -> bool:
+    """Whether ``rows x ld`` elements lie in the span the zero-extended pass A addresses (its buffer descriptor is 32 bits wide:
+    fewbit_fft4.h::zext_span_ok, the same bound)"""
+    return rows * ld * itemsize <= 0xfffffff0
+
+
+def _native_transform_rows(kind: str, mat: torch.Tensor) -> int:
+    """The row count at which the gfx950 sampled-transform kernel pairs (fewbit_amd/csrc/fewbit_dct.hip, fewbit_dft.hip) run ``mat``; 0: they
+    do not.  They take 2-D fp32 / fp16 / bf16 GPU tensors of the row counts their library has a kernel for (_transform_rows; e.g. RoBERTa's
+    128 x 128 tokens = 16384, 32 sequences of 384 tokens = 12288 = 3 x 2^12, 28 sequences of 128 tokens = 3584 = 7 x 2^9): the rows of
+    ``mat``.  With ``use_row_extension()`` on, any other row count up to 262144 runs zero-extended at the next supported one
+    (``cabi_x.sampled_rows_ceil``) -- unless the matrix spans 4 GiB or more, which the zero-extended pass A does not address.  Everything
+    else keeps the torch.fft formulation."""
+    if not (_NATIVE_SKETCH and kind in ('dct', 'dft') and mat.device.type == 'cuda' and mat.dim() == 2
+            and mat.dtype in (torch.float32, torch.float16, torch.bfloat16) and mat.shape[1] > 0):
+        return 0
+    rows = mat.shape[0]
+    if _transform_rows(kind, rows):
+        return rows
+    if not _EXTEND_ROWS or rows < 1:
+        return 0
+    ld = mat.stride(0) if mat.stride(1) == 1 and mat.stride(0) >= mat.shape[1] else mat.shape[1]      # (what _unit_stride hands the kernels)
+    if not _zext_span_ok(rows, ld, mat.element_size()):
+        return 0
+    from . import cabi_x
+    return cabi_x.sampled_rows_ceil(rows)
+
+
 def _native_transform_applies(kind: str, mat: torch.Tensor) -> bool:
-    """The gfx950 sampled-transform kernel pairs (fewbit_amd/csrc/fewbit_dct.hip, fewbit_dft.hip) take 2-D fp32 / fp16 / bf16 GPU tensors
-    of the row counts their library has a kernel for (_transform_rows; e.g. RoBERTa's 128 x 128 tokens = 16384, 32 sequences of 384 tokens
-    = 12288 = 3 x 2^12, 28 sequences of 128 tokens = 3584 = 7 x 2^9); everything else keeps the torch.fft formulation."""
-    return (_NATIVE_SKETCH and kind in ('dct', 'dft') and mat.device.type == 'cuda' and mat.dim() == 2
-            and mat.dtype in (torch.float32, torch.float16, torch.bfloat16) and mat.shape[1] > 0 and _transform_rows(kind, mat.shape[0]))
+    return _native_transform_rows(kind, mat) != 0
 
 
 _TRANSFORM_PATHS = {
@@ -299,8 +353,14 @@ _TRANSFORM_PATHS = {
 
 def sampled_transform_path(kind: str, mat: torch.Tensor) -> str:
     """Which code computes the sampled transform ``kind`` ('dct' / 'dft') of ``mat`` (what bench.py prints beside its time)."""
-    if _native_transform_applies(kind, mat):
+    rows = _native_transform_rows(kind, mat)
+    if rows == mat.shape[0] and rows:
         return _TRANSFORM_PATHS[kind]
+    if rows:
+        planes = '' if kind == 'dct' else ', real and imaginary planes'
+        return (f'gfx950 kernel pair fewbit_hipx_sampled_{kind}_zext, zero-extended to {rows} rows (four-step fp32 FFT in LDS, the missing rows are '
+                f'never loaded, only the sampled rows are written{planes}; in the layer: rows of a seed; an unbiased estimator, not the '
+                "reference's transform at the true length)")
     return 'torch.fft (rocFFT on the GPU): full transform along dim 0 in fp32, then the gather of the sampled rows'
 
 
@@ -308,11 +368,12 @@ def sampled_transform(kind: str, mat: torch.Tensor, p: int, gen: torch.Generator
     """One estimator product of the layer, ``scale * transform(mat)[p sampled rows]``, on the path ``linear_grp`` takes for this
     ``kind`` and ``mat`` (what bench.py and tools/ time): the kernel pair with rows of ``seed``, or torch.fft + randint from ``gen``.
     'dft' returns a complex64 ``(p, features)`` tensor on either path (on the kernel pair: built from its fp32 planes)."""
-    if not _native_transform_applies(kind, mat):
+    rows = _native_transform_rows(kind, mat)                  # (other than the rows of mat: the zero-extended pair, rows of seed in [0, rows))
+    if not rows:
         return _sketch(kind, mat, p, gen, scale=scale)
     if kind == 'dct':
-        return _native_transform(kind, mat, p, seed, scale)
-    planes = _native_transform(kind, mat, p, seed, scale, torch.float32)
+        return _native_transform(kind, mat, p, seed, scale, rows=rows)
+    planes = _native_transform(kind, mat, p, seed, scale, torch.float32, rows)
     return torch.complex(planes[0], planes[1])
 
 
@@ -345,7 +406,10 @@ class _LinearGRP(torch.autograd.Function):
         ctx.p, ctx.kind = p, kind
         ctx.has_bias = bias is not None
         dense = _native_sketch_applies(kind, flat, sketch_dtype)
-        if dense or _native_transform_applies(kind, flat):
+        # the row count the sampled-transform pair runs at: the rows of flat, or with use_row_extension() the next supported count N' (flat
+        # zero-extended; the rows of the seed are drawn from [0, N'), the scale is N' / p, and backward runs on the same N' and seed)
+        ctx.transform_rows = 0 if dense else _native_transform_rows(kind, flat)
+        if dense or ctx.transform_rows:
             # S -- or the sampled rows -- lives nowhere: a function of the seed that the kernel evaluates itself; the projection and the
             # seed are all that is kept (no randint launch, no RNG state to save and replay; while a graph is being captured the seed is
             # a device word)
@@ -358,9 +422,9 @@ class _LinearGRP(torch.autograd.Function):
             if dense:
                 kept = (_native_sketch(kind, x, p, ctx.native_seed, 1.0 / p), )
             elif kind == 'dct':
-                kept = (_native_transform(kind, x, p, ctx.native_seed, rows / p), )
+                kept = (_native_transform(kind, x, p, ctx.native_seed, ctx.transform_rows / p, rows=ctx.transform_rows), )
             else:                                       # 'dft': the real and imaginary planes in the layer's dtype, two views of one buffer
-                planes = _native_transform(kind, x, p, ctx.native_seed, rows / p)
+                planes = _native_transform(kind, x, p, ctx.native_seed, ctx.transform_rows / p, rows=ctx.transform_rows)
                 kept = (planes[0], planes[1])
             ctx.save_for_backward(*kept, weight)
             return F.linear(input, weight, bias)
@@ -389,11 +453,13 @@ class _LinearGRP(torch.autograd.Function):
             if ctx.kind == 'dft':
                 # Re((F G)^H (F X)) = Gr^T Xr + Gi^T Xi: two accumulating GEMMs in the dtype of the planes
                 xr, xi = saved[0], saved[1]
-                g = _native_transform('dft', g2, ctx.p, ctx.native_seed, 1.0).to(xr.dtype)
+                g = _native_transform('dft', g2, ctx.p, ctx.native_seed, 1.0, rows=ctx.transform_rows).to(xr.dtype)
                 grad_weight = torch.addmm(g[0].T @ xr, g[1].T, xi).to(weight.dtype)
             else:
-                native = _native_transform if ctx.kind == 'dct' else _native_sketch
-                proj = native(ctx.kind, g2, ctx.p, ctx.native_seed, 1.0)
+                if ctx.kind == 'dct':
+                    proj = _native_transform('dct', g2, ctx.p, ctx.native_seed, 1.0, rows=ctx.transform_rows)
+                else:
+                    proj = _native_sketch(ctx.kind, g2, ctx.p, ctx.native_seed, 1.0)
                 grad_weight = (proj.to(sketch.dtype).T @ sketch).to(weight.dtype)
         elif ctx.needs_input_grad[1]:
             proj = _sketch(ctx.kind, flat, ctx.p, _replay_rng(ctx.token), ctx.sketch_dtype, ctx.draw_dtype)

@@ -26,7 +26,9 @@ extern "C" {
  * What is declared below is what a binding needs (tests/test_dft_host.py pins the exported symbol list).
  * Additions that leave every version-1 entry point as it was do not move the version; they move the REVISION:
  *   revision 1: the version-1 library as first released (it has no fewbit_hipx_revision symbol).
- *   revision 2: fewbit_hipx_revision; the column sampling of LinearCRS: fewbit_hipx_crs_columns, _crs_workspace, _crs_gather, _crs_scatter. */
+ *   revision 2: fewbit_hipx_revision; the column sampling of LinearCRS: fewbit_hipx_crs_columns, _crs_workspace, _crs_gather, _crs_scatter.
+ * The zero-extended sampled transforms (fewbit_hipx_sampled_rows_ceil, _sampled_dct_zext, _sampled_dft_zext and their _seeded forms) were
+ * added inside revision 2: a binding recognises them by the presence of the symbols and refuses by name a library that lacks them. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -62,6 +64,37 @@ int fewbit_hipx_sampled_dft(int dtype, const void *m, size_t rows, size_t featur
  * replay, fed by fewbit_hip_sketch_next_seed. */
 int fewbit_hipx_sampled_dft_seeded(int dtype, const void *m, size_t rows, size_t features, size_t ld, uint64_t seed, const uint64_t *seed_device,
                                    size_t proj, double scale, int out_dtype, void *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The sampled transforms at ANY row count, by zero extension.  m holds valid_rows rows and is transformed as if it had `rows` rows, the
+ * missing ones zero:
+ *     out = scale * transform_of_length_rows([m; 0])[idx]          transform: the orthonormal DCT-II (fewbit_hip_sampled_dct) or the DFT above
+ *   rows        a supported row count (the list above) -- fewbit_hipx_sampled_rows_ceil(n): the smallest one >= n, 256 for n = 1 .. 256,
+ *               0 for n = 0 and n > 262144 (from the table the kernels are dispatched by)
+ *   valid_rows  1 <= valid_rows <= rows (else FEWBIT_ERR_INVALID_ARGUMENT).  m: valid_rows x features with leading dimension ld; no
+ *               address at or beyond m + valid_rows * ld elements is read -- the missing rows are zeros that are never loaded, there is no
+ *               padded copy.  valid_rows * ld elements must span less than 4 GiB (else FEWBIT_ERR_UNSUPPORTED)
+ *   idx / seed  row numbers in [0, rows) -- of the seed: fewbit_hip_sampled_rows(seed, rows, proj) -- by the rules of the plain entry points
+ *   out, out_dtype, scale, stream, the seed word   as in fewbit_hip_sampled_dct[_seeded] (the DCT: no out_dtype, one plane in the dtype of m)
+ *               and fewbit_hipx_sampled_dft[_seeded]
+ *   workspace   fewbit_hipx_sampled_dft_workspace(dtype, rows, features, proj) bytes (the one formula of all sampled transforms, at `rows`)
+ * The result is bit for bit that of the plain entry point on a rows x features copy of m filled up with zeros (valid_rows = rows: on m itself).
+ * What it is for: with R sampling p of `rows` rows uniformly with replacement, C the orthonormal transform of length `rows` and P the
+ * rows x valid_rows matrix that appends the zero rows, S = sqrt(rows / p) R C P has E[S^T S] = P^T C^T C P = P^T P = I, so (S G)^T (S X)
+ * with the same R is an unbiased estimate of G^T X for matrices of valid_rows rows -- an estimator of the same kind as the layer's, but
+ * NOT the reference's dct(X)[idx] at length valid_rows: another random variable with the same mean.
+ * Pass A skips the missing rows (fewbit_amd/csrc/fewbit_fft4.h: pass_a_zext_kernel); pass B and the LDS note above are the plain pair's. */
+size_t fewbit_hipx_sampled_rows_ceil(size_t rows);
+int fewbit_hipx_sampled_dct_zext(int dtype, const void *m, size_t rows, size_t valid_rows, size_t features, size_t ld, const int64_t *idx, size_t proj,
+                                 double scale, void *out, void *workspace, size_t workspace_bytes, void *stream);
+int fewbit_hipx_sampled_dct_zext_seeded(int dtype, const void *m, size_t rows, size_t valid_rows, size_t features, size_t ld, uint64_t seed,
+                                        const uint64_t *seed_device, size_t proj, double scale, void *out, void *workspace, size_t workspace_bytes,
+                                        void *stream);
+int fewbit_hipx_sampled_dft_zext(int dtype, const void *m, size_t rows, size_t valid_rows, size_t features, size_t ld, const int64_t *idx, size_t proj,
+                                 double scale, int out_dtype, void *out, void *workspace, size_t workspace_bytes, void *stream);
+int fewbit_hipx_sampled_dft_zext_seeded(int dtype, const void *m, size_t rows, size_t valid_rows, size_t features, size_t ld, uint64_t seed,
+                                        const uint64_t *seed_device, size_t proj, double scale, int out_dtype, void *out, void *workspace,
+                                        size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Column sampling of the weight gradient (LinearCRS; the reference's linear_crs, fewbit/functional/linear.py:27-43): `nopairs`

@@ -36,6 +36,7 @@ ROWS = [
     ('r06_dct_rows_5x.txt', 'the kernel pair and the torch.fft formulation at 5 x 2^k rows (1280 .. 40960)', f'{D} 7.3'),
     ('r06_dct_rows_3x.txt', 'the kernel pair and the torch.fft formulation at 3 x 2^k rows (768 .. 49152)', f'{D} 7.3'),
     ('transform_rows_odd.txt', 'tools/transform_rows_bench.py: both kernel pairs at 7 x 2^k, 9 x 2^k and 15 x 2^k rows against the torch.fft formulation and against the next power of two', f'{E} 8.3'),
+    ('transform_zext.txt', "tools/transform_zext_bench.py: the zero-extended kernel pairs at 12800 and 51200 rows against F.pad + the plain call, the plain call on N' real rows and the torch.fft formulation", f'{E} 8.6'),
     ('r06_dct_variants.txt', 'the sampled-DCT variants measured in round 6, phases compiled out, per-workgroup timeline', f'{D} 7.5'),
     ('r06_dct_sorted_samples.txt', 'the samples sorted by residue class once, in pass A, instead of tested by every pass-B workgroup: pass B 17.3 -> 12.7 us', f'{D} 5'),
     ('r06_dct_serve_lanes.txt', 'pass B writing a sampled row with 16 / 8 / 4 lanes: 4 shipped (pass B -8 %)', f'{D} 7.5'),
@@ -47,6 +48,7 @@ ROWS = [
     ('r0?_roberta_ab_fp32.txt|r0?_roberta_ab_bf16.txt|r0?_roberta_randomized_insitu*.json', 'the randomized RoBERTa step, arms interleaved in one process; its GPU time by kernel class', f'{D} 7.4'),
     ('r06_roberta_overlap_ab.txt', 'the estimators on a side stream beside the layer GEMMs: slower, not kept', f'{E} round 6'),
     ('r06_isa_identity.txt', 'tools/isa_digest.py: machine code of all 628 device functions before / after the round-6 source clean-up', f'{D} 9'),
+    ('transform_zext_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1320 device functions before / after the zero-extended pairs were added (570 new)', f'{E} 8.6'),
     # ---- experiments (kept as records; the design quotes only their conclusions)
     ('r02_launch_shape_sweep_*.txt|r03_*shape_sweep*.txt|r03_backward_size_crossover.txt', 'launch shape, groups per lane and size crossovers of the activation kernels', f'{D} 3.1'),
     ('r03_ablation_*.txt|r03_kernels_r02_vs_r03_ab.txt|r03_inplace_stores.txt|r04_inplace_*.txt', 'one stage compiled out at a time; in-place stores; round-to-round A/B', f'{D} 7.1; {E} 6'),
