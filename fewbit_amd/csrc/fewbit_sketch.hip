@@ -145,6 +145,15 @@ template <> struct Operand<FEWBIT_F16> {
     }
 };
 
+// sum * scale as an fp32 number of its own.  Left to itself hipcc folds `(_Float16)(v * scale)` into v_fma_mixlo_f16, which rounds the exact
+// product ONCE to fp16, while the packed conversions (v_cvt_pk_f16_f32) round the fp32 product: the element-wise tails and the scalar reduce
+// kernel then differed from the vector paths in the last fp16 bit of ~0.25 % of the results.  The empty asm keeps the product in a register.
+__device__ __forceinline__ float scaled(float v, float scale) {
+    float p = v * scale;
+    asm volatile("" : "+v"(p));
+    return p;
+}
+
 // ---- S as a function -----------------------------------------------------------------------------------------------------
 // Rademacher: the 8 signs of MFMA step s (0..15) of the 256-row block whose 128 bits are `w`, as 4 packed operand dwords:
 // dword q = (+-1, +-1) with the sign bits taken from bits 15 - sh and 31 - sh of word s/4, sh = 4*(s%4) + q
@@ -610,7 +619,7 @@ __global__ __launch_bounds__(64 * W, 2) void sketch_kernel(const void *__restric
             uint16_t *p = static_cast<uint16_t *>(out) + i * features + f;
             u32x4 o;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = Operand<DT>::pack(v[2 * e] * scale, v[2 * e + 1] * scale);
+            for (int e = 0; e < 4; ++e) o[e] = Operand<DT>::pack(scaled(v[2 * e], scale), scaled(v[2 * e + 1], scale));
             if (f + 8 <= features) {
                 typedef u32x4 __attribute__((aligned(2))) u32x4u;
                 *reinterpret_cast<u32x4u *>(p) = o;
@@ -627,7 +636,7 @@ template <int DT> __global__ __launch_bounds__(256) void sketch_reduce_kernel(co
     if (i >= n) return;
     float s = ws[i];
     for (int z = 1; z < slices; ++z) s += ws[static_cast<size_t>(z) * n + i];
-    s *= scale;
+    s = scaled(s, scale);
     if constexpr (DT == FEWBIT_F32) static_cast<float *>(out)[i] = s;
     else if constexpr (DT == FEWBIT_F16) static_cast<_Float16 *>(out)[i] = static_cast<_Float16>(s);
     else static_cast<__bf16 *>(out)[i] = static_cast<__bf16>(s);
@@ -663,7 +672,7 @@ template <int DT> __global__ __launch_bounds__(256) void sketch_reduce4_kernel(c
 #pragma unroll
         for (int k = 0; k < 3; ++k) if (z + k < slices) s += v[k];      // (no `+ 0`: -0.0 stays -0.0, as in the scalar kernel)
     }
-    s *= scale;
+    s = f32x4{scaled(s.x, scale), scaled(s.y, scale), scaled(s.z, scale), scaled(s.w, scale)};
     if constexpr (DT == FEWBIT_F32) reinterpret_cast<f32x4 *>(out)[i] = s;
     else {
         typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
@@ -738,18 +747,18 @@ template <int DIST> __global__ __launch_bounds__(256) void sketch_matrix_kernel(
         philox4x32(static_cast<uint32_t>(i), static_cast<uint32_t>(2 * (r >> 8) + h), 0u, 0u, key, w);
         v = ((w[s >> 2] >> (((j & 1) ? 31 : 15) - (4 * (s & 3) + (j >> 1)))) & 1u) ? -1.0f : 1.0f;
     } else {
-        float z0, z1;
         // element j of step s of block r / 256 for octet parity h: word 2 s + (q & 1) of stream q / 2, q = j / 2
         const int s = static_cast<int>((r & 255) >> 4), h = static_cast<int>((r >> 3) & 1), q = j >> 1;
         uint32_t st[4];
         philox4x32<kGaussianRounds>(static_cast<uint32_t>(i), static_cast<uint32_t>(2 * (r >> 8) + h), static_cast<uint32_t>(q >> 1), 2u, key, st);
         uint32_t w = 0;
         for (int k = 0; k <= 2 * s + (q & 1); ++k) w = xoshiro128pp(st);
-        box_muller(w, z0, z1);
-        v = (j & 1) ? z1 : z0;
-        // rounded as the product kernel rounds its operand
-        if (dtype == FEWBIT_F16) v = static_cast<float>(static_cast<_Float16>(v));
-        else v = static_cast<float>(static_cast<__bf16>(v));
+        // the operand dword exactly as the product kernels form it (gaussian_pair: the same Box-Muller, the same packed conversion), then
+        // the half this element sits in
+        const uint32_t pair = dtype == FEWBIT_F16 ? gaussian_pair<FEWBIT_F16>(w) : gaussian_pair<FEWBIT_BF16>(w);
+        const uint32_t half = (j & 1) ? pair >> 16 : pair & 0xffffu;
+        if (dtype == FEWBIT_F16) v = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(half)));
+        else v = __builtin_bit_cast(float, half << 16);
     }
     out[idx] = v;
 }

@@ -99,3 +99,115 @@ def matrix(dist: str, seed: int, nrows: int, ncols: int, dtype: torch.dtype = to
     if dist == 'rademacher':
         return rademacher(seed, nrows, ncols, row0, col0)
     return gaussian(seed, nrows, ncols, dtype, row0, col0)
+
+
+# ---- one-term sums: the exact tests of the product kernels (tests/test_gpu_sketch_exact.py, tests/test_sketch_exact_host.py) ----------
+# If every column of M has exactly ONE nonzero entry, every output is a sum of one product and zeros: bit-exact whatever the stage order,
+# the slicing or the association of the fp32 sums -- the result names the row, the column, the sign and every rounding.
+ONE_TERM_STEP = 277             # prime, and coprime to both row counts below: f -> 277 f mod rows visits every row
+ONE_TERM_ROWS = 645             # 2 * 256 + 128 + 5: a last stage with 5 valid rows (most of its octets lie wholly outside)
+ONE_TERM_ROWS_SLICED = 3717     # 3072 + 645: the library cuts rows into slices of at least 1024 (645 rows are one slice whatever is asked for);
+#                                 three slices of 1280 rows, the last one 4 * 256 + 128 + 5 rows long
+ONE_TERM_FEATURES = (264, 261, 520)     # a second column tile of one chunk; the ragged path; 512 + one chunk (the 128 x 512 tile)
+ONE_TERM_PROJ = (130, 257)
+ONE_TERM_SCALES = (1.0, -0.5, None)     # None: 1 / proj
+
+
+def one_term_phases(rows: int, features: int) -> int:
+    """calls after which every row of M has been the nonzero row of some column (at least three: one per scale)"""
+    return max(3, -(-rows // features))
+
+
+def one_term_rows(rows: int, features: int, phase: int) -> np.ndarray:
+    """the nonzero row of every column in call number `phase`: column f -> 277 (f + features * phase) mod rows"""
+    return (ONE_TERM_STEP * (np.arange(features, dtype=np.int64) + features * phase)) % rows
+
+
+def one_term_values(features: int, dtype: torch.dtype, seed: int) -> torch.Tensor:
+    """randn scaled by a power of two per column, 2^-20 ... 2^20 (fp16: 2^-6 ... 2^6), in `dtype`"""
+    g = torch.Generator().manual_seed(seed)
+    span = 6 if dtype == torch.float16 else 20
+    e = torch.randint(-span, span + 1, (features, ), generator=g)
+    return (torch.randn(features, generator=g) * torch.exp2(e.float())).to(dtype)
+
+
+def operand(m: torch.Tensor) -> torch.Tensor:
+    """M as the matrix pipe gets it, in float32: fp32 rounded to bf16 (to nearest even), 16-bit input as it is"""
+    op = torch.float16 if m.dtype == torch.float16 else torch.bfloat16
+    return m.to(op).to(torch.float32)
+
+
+def one_term_expected(S: torch.Tensor, r, values: torch.Tensor, scale: float, bf16_partials: bool = False) -> torch.Tensor:
+    """out[i, f] of a call whose column f holds values[f] at row r[f] and zeros elsewhere, in float32 arithmetic throughout:
+    S[i, r] * op(m), rounded to bf16 when the slices exchange bf16 partial sums, times float32(scale), one rounding to the dtype of M"""
+    S = S.to(torch.float32).cpu()
+    v = S[:, torch.as_tensor(r, dtype=torch.int64)] * operand(values.cpu())[None, :]
+    if bf16_partials:
+        v = v.to(torch.bfloat16).to(torch.float32)
+    return (v * torch.tensor(scale, dtype=torch.float32)).to(values.dtype)
+
+
+def _bits(t: torch.Tensor) -> torch.Tensor:
+    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+
+
+def exact_mismatches(got: torch.Tensor, want: torch.Tensor, allowance=None) -> torch.Tensor:
+    """mask of the entries that differ: bit for bit, except that NaN matches NaN (payloads are not compared) and zeros are compared by
+    value; `allowance` (broadcastable, absolute, 0 where nothing is allowed) is for Gaussian products among the fp32 subnormals"""
+    got, want = got.detach().cpu(), want.detach().cpu()
+    assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape, got.dtype, want.dtype)
+    ok = (_bits(got) == _bits(want)) | (torch.isnan(got) & torch.isnan(want)) | ((got == 0) & (want == 0))
+    if allowance is not None:
+        ok |= (allowance > 0) & ((got.double() - want.double()).abs() <= allowance)
+    return ~ok
+
+
+def subnormal_allowance(values: torch.Tensor, scale: float) -> torch.Tensor:
+    """Gaussian S only: |m| < 2^-100 puts s * m among the fp32 subnormals, where it need not be exact -- 2^-149 |scale| there, 0 elsewhere"""
+    tiny = operand(values.cpu()).abs() < 2.0**-100
+    return torch.where(tiny, torch.tensor(2.0**-149 * abs(scale), dtype=torch.float64), torch.tensor(0.0, dtype=torch.float64))[None, :]
+
+
+# The settings of the one-term sweep: `tune` values (keys of cabi.tune_sketch_*; a key not named is -1, the policy), the distributions
+# and dtypes they are run with.  sketch_convert only acts on fp32 input, sketch_materialise only on the Gaussian sketch.
+# tests/test_sketch_exact_host.py checks that, per distribution and dtype, every kernel variant appears in the plans of this list.
+_ALL = ('rademacher', 'gaussian')
+_F32, _F16, _BF16 = torch.float32, torch.float16, torch.bfloat16
+EXACT_SETTINGS = (
+    (dict(waves=4, halves=1, materialise=0), _ALL, (_F32, _F16, _BF16)),                                   # fused, 128 x 256 tile
+    (dict(waves=8, halves=1, materialise=0), _ALL, (_F32, _F16, _BF16)),                                   # fused, 256 x 256 tile
+    (dict(halves=2, materialise=0), _ALL, (_F32, _F16, _BF16)),                                            # 128 x 512 tile
+    (dict(waves=4, halves=1, materialise=1), ('gaussian', ), (_F16, _BF16)),                               # S from memory
+    (dict(waves=8, halves=1, slices=3, partials=0, materialise=0), _ALL, (_F32, _F16, _BF16)),             # sliced, fp32 partial sums
+    (dict(waves=4, halves=1, slices=3, partials=1, materialise=0), _ALL, (_F16, _BF16)),                   # sliced, bf16 partial sums (bf16)
+    (dict(halves=2, slices=3, partials=1, materialise=0), _ALL, (_F16, _BF16)),                            # the same on the 128 x 512 tile
+    (dict(waves=8, halves=1, slices=3, partials=1, materialise=1), ('gaussian', ), (_F16, _BF16)),         # S from memory, sliced
+    (dict(waves=4, halves=1, convert=1, materialise=0), _ALL, (_F32, )),                                   # fp32 rounded to bf16 first
+    (dict(waves=8, halves=1, convert=1, materialise=1), ('gaussian', ), (_F32, )),                         # ... S from memory
+    (dict(halves=2, convert=1, slices=3, partials=1, materialise=0), _ALL, (_F32, )),                      # ... 128 x 512, bf16 partial sums
+    (dict(waves=8, halves=1, convert=1, slices=3, partials=0, materialise=0), _ALL, (_F32, )),             # ... fp32 partial sums
+    (dict(waves=4, halves=1, convert=1, slices=3, partials=1, materialise=1), ('gaussian', ), (_F32, )),   # ... S from memory, bf16 partial sums
+    (dict(waves=4, halves=1, convert=0, slices=3, materialise=0), _ALL, (_F32, )),                         # fp32 staged in the kernel, sliced
+)
+TUNE_KEYS = ('slices', 'waves', 'halves', 'convert', 'partials', 'materialise')
+
+
+def exact_cases():
+    """(distribution, dtype, tune dict) of every case of the sweep"""
+    return [(dist, dtype, tune) for tune, dists, dtypes in EXACT_SETTINGS for dist in dists for dtype in dtypes]
+
+
+def expected_plan(dist: str, dtype: torch.dtype, tune: dict, rows: int) -> dict:
+    """what a setting of EXACT_SETTINGS asks for (every feature count of the sweep is wider than one column tile): the fields the GPU
+    test asserts on describe_sketch before it trusts a case to have run the kernel variant it is named after"""
+    converted = dtype == torch.float32 and tune.get('convert', -1) == 1
+    operand_bf16 = dtype == torch.bfloat16 or converted
+    gz = 3 if tune.get('slices', -1) == 3 and rows >= 3072 else 1
+    if gz == 1:
+        partial = 'fp32' if converted else None
+    else:
+        partial = 'bf16' if operand_bf16 and tune.get('partials', -1) == 1 and dtype != torch.float16 else 'fp32'
+    return {'wide': tune.get('halves', -1) == 2,
+            'tile': '128x512' if tune.get('halves', -1) == 2 else '128x256' if tune['waves'] == 4 else '256x256',
+            'from_memory': dist == 'gaussian' and tune.get('materialise', -1) == 1 and (dtype != torch.float32 or converted),
+            'converted': converted, 'gz': gz, 'partial_sums': partial}
