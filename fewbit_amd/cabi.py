@@ -425,20 +425,28 @@ def sketch(dist: str, m: torch.Tensor, proj: int, seed, scale: float = 1.0, out:
         need = sketch_workspace_bytes(dist, rows, features, proj, m.dtype)
         out, workspace = _buffers(m, (), out, (proj, features), m.dtype, 'proj x features tensor of the dtype of m', workspace, need)
         tail = (scale, out.data_ptr(), *_span(workspace), _stream(stream, m.device))
-        if isinstance(seed, torch.Tensor):
-            _seed_word(seed, 'seed')
-            _same_device(m, seed)
-            _check(lib().fewbit_hip_sketch_device_seed(SKETCH_DISTS.index(dist), DTYPES[m.dtype], m.data_ptr(), rows, features, ld,
-                                                       proj, seed.data_ptr(), *tail))
+        value, word, others = _seed_arguments(seed)
+        head = (SKETCH_DISTS.index(dist), DTYPES[m.dtype], m.data_ptr(), rows, features, ld, proj)
+        if others:
+            _same_device(m, *others)
+            _check(lib().fewbit_hip_sketch_device_seed(*head, word, *tail))
         else:
-            _check(lib().fewbit_hip_sketch(SKETCH_DISTS.index(dist), DTYPES[m.dtype], m.data_ptr(), rows, features, ld, proj,
-                                           seed & 0xffffffffffffffff, *tail))
+            _check(lib().fewbit_hip_sketch(*head, value, *tail))
     return out
 
 
 def _seed_word(t: torch.Tensor, what: str) -> None:
     if t.device.type != 'cuda' or t.dtype != torch.int64 or t.numel() != 1:
         raise FewbitHipError(f'{what} must be a one-element int64 tensor on the GPU')
+
+
+def _seed_arguments(seed):
+    """A seed -- an int, or a one-element int64 device tensor that is read when the kernel runs -- as (value, device word pointer, the tensors
+    to keep on the device of the call)"""
+    if isinstance(seed, torch.Tensor):
+        _seed_word(seed, 'seed')
+        return 0, seed.data_ptr(), (seed, )
+    return seed & 0xffffffffffffffff, 0, ()
 
 
 def next_sketch_seed(counter: torch.Tensor, base: int, out: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
@@ -519,24 +527,51 @@ def sampled_dct_workspace_bytes(rows: int, features: int, proj: int, dtype: torc
     return lib().fewbit_hip_sampled_dct_workspace(DTYPES[dtype], rows, features, proj)
 
 
-def _sampled_call(name: str, workspace_bytes, check, m: torch.Tensor, proj: int, planes: tuple, out_dtype: torch.dtype, what: str,
-                  out: Optional[torch.Tensor], workspace: Optional[torch.Tensor], others, launch) -> torch.Tensor:
-    """A call of a sampled-transform kernel pair (``sampled_dct*`` here, ``cabi_x.sampled_dft*``): ``m`` checked, a row count without a
-    kernel refused by name, ``out`` (``planes + (proj, features)`` of ``out_dtype``) and the workspace allocated or checked, then
-    ``check(launch(dtype, m, rows, features, ld, out, workspace, workspace bytes))``."""
+def _row_numbers(idx: torch.Tensor, m: torch.Tensor, who: str = 'm') -> int:
+    """the number of row numbers in ``idx``, checked to be a contiguous 1-D int64 tensor on the device of the matrix (``who`` names it)"""
+    if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != m.device or not idx.is_contiguous():
+        raise FewbitHipError(f'idx must be a contiguous 1-D int64 tensor on the device of {who}')
+    return idx.numel()
+
+
+def _planes_dtype(m: torch.Tensor, out_dtype: Optional[torch.dtype], who: str = 'm') -> torch.dtype:
+    """the dtype of the planes of a sampled Fourier transform: torch.float32 or the dtype of the matrix, the default"""
+    out_dtype = m.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, m.dtype):
+        raise FewbitHipError(f'out_dtype must be torch.float32 or the dtype of {who} (got {out_dtype})')
+    return out_dtype
+
+
+def _sampled_call(pair: tuple, m: torch.Tensor, proj: int, out_dtype: torch.dtype, out: Optional[torch.Tensor], workspace: Optional[torch.Tensor],
+                  others, stream: Optional[int], launch, length: Optional[int] = None) -> torch.Tensor:
+    """A call of a sampled-transform kernel pair (``sampled_dct*`` here, ``cabi_x.sampled_*``).  ``pair``: (the name in messages, the
+    workspace query, the error check of the library, the planes in front of ``(proj, features)``, what ``out`` is called).  ``m`` is checked,
+    a row count without a kernel refused by name, ``out`` (of ``out_dtype``) and the workspace allocated or checked, then
+    ``check(launch(head, tail))`` with ``head = (dtype, m, rows, features, ld)`` and ``tail = (out, workspace, workspace bytes, stream)``.
+    With a ``length`` the transform has that many rows, of which ``m`` holds the first 1 .. ``length`` (the zero-extended pairs:
+    ``head = (dtype, m, length, rows, features, ld)``); such a call is refused even when it is empty, a plain one is left to C, which
+    answers an empty call before it looks at the rows."""
+    name, workspace_bytes, check, planes, what = pair
     rows, features, ld = _matrix(m)
-    need = workspace_bytes(rows, features, proj, m.dtype)
-    if need == 0 and proj and features:
-        raise FewbitHipError(f'{name}: no kernel for {rows} rows ({SAMPLED_ROWS} is needed)')
+    if length is None:
+        need = workspace_bytes(rows, features, proj, m.dtype)
+        if need == 0 and proj and features:
+            raise FewbitHipError(f'{name}: no kernel for {rows} rows ({SAMPLED_ROWS} is needed)')
+        lead = (rows, )
+    else:
+        need = workspace_bytes(length, features, proj, m.dtype)
+        if workspace_bytes(length, 1, 1, m.dtype) == 0:
+            raise FewbitHipError(f'{name}: no kernel for {length} rows ({SAMPLED_ROWS} is needed; sampled_rows_ceil gives the next one)')
+        if not 1 <= rows <= length:
+            raise FewbitHipError(f'{name}: x has {rows} rows, 1 .. rows = {length} are needed')
+        lead = (length, rows)
     with _on(m.device):
         out, workspace = _buffers(m, others, out, (*planes, proj, features), out_dtype, what, workspace, need)
-        check(launch(DTYPES[m.dtype], m.data_ptr(), rows, features, ld, out.data_ptr(), *_span(workspace)))
+        check(launch((DTYPES[m.dtype], m.data_ptr(), *lead, features, ld), (out.data_ptr(), *_span(workspace), _stream(stream, m.device))))
     return out
 
 
-def _sampled_dct_call(m: torch.Tensor, proj: int, out: Optional[torch.Tensor], workspace: Optional[torch.Tensor], others, launch) -> torch.Tensor:
-    return _sampled_call('sampled_dct', sampled_dct_workspace_bytes, _check, m, proj, (), m.dtype, 'proj x features tensor of the dtype of m', out,
-                         workspace, others, launch)
+_DCT = ('sampled_dct', sampled_dct_workspace_bytes, _check, (), 'proj x features tensor of the dtype of m')
 
 
 def sampled_dct(m: torch.Tensor, idx: torch.Tensor, scale: float = 1.0, out: Optional[torch.Tensor] = None,
@@ -548,11 +583,9 @@ def sampled_dct(m: torch.Tensor, idx: torch.Tensor, scale: float = 1.0, out: Opt
     Features ``(2c, 2c + 1)`` are transformed as one complex column: the rounding error of column ``c`` scales with the RMS of the pair
     ``(c, c ^ 1)``, and a NaN or Inf in one column makes its partner non-finite too (other columns stay bit for bit as they are).
     torch.fft keeps every column apart."""
-    if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != m.device or not idx.is_contiguous():
-        raise FewbitHipError('idx must be a contiguous 1-D int64 tensor on the device of m')
-    proj = idx.numel()
-    return _sampled_dct_call(m, proj, out, workspace, (idx, ), lambda dt, mp, rows, features, ld, op, wp, wb: lib().fewbit_hip_sampled_dct(
-        dt, mp, rows, features, ld, idx.data_ptr(), proj, scale, op, wp, wb, _stream(stream, m.device)))
+    proj = _row_numbers(idx, m)
+    return _sampled_call(_DCT, m, proj, m.dtype, out, workspace, (idx, ), stream,
+                         lambda head, tail: lib().fewbit_hip_sampled_dct(*head, idx.data_ptr(), proj, scale, *tail))
 
 
 def sampled_dct_seeded(m: torch.Tensor, proj: int, seed, scale: float = 1.0, out: Optional[torch.Tensor] = None,
@@ -561,13 +594,9 @@ def sampled_dct_seeded(m: torch.Tensor, proj: int, seed, scale: float = 1.0, out
     kernel evaluates itself.  ``seed``: an int, or a one-element int64 tensor on the device of ``m`` whose value is read when the kernel
     runs (``next_sketch_seed``: a launch recorded into a hipGraph then samples fresh rows on every replay).  The pair contract of
     ``sampled_dct`` holds: column ``c``'s error scales with the RMS of the pair ``(c, c ^ 1)``, a non-finite value reaches the partner."""
-    if isinstance(seed, torch.Tensor):
-        _seed_word(seed, 'seed')
-        value, word, others = 0, seed.data_ptr(), (seed, )
-    else:
-        value, word, others = seed & 0xffffffffffffffff, 0, ()
-    return _sampled_dct_call(m, proj, out, workspace, others, lambda dt, mp, rows, features, ld, op, wp, wb: lib().fewbit_hip_sampled_dct_seeded(
-        dt, mp, rows, features, ld, value, word, proj, scale, op, wp, wb, _stream(stream, m.device)))
+    value, word, others = _seed_arguments(seed)
+    return _sampled_call(_DCT, m, proj, m.dtype, out, workspace, others, stream,
+                         lambda head, tail: lib().fewbit_hip_sampled_dct_seeded(*head, value, word, proj, scale, *tail))
 
 
 def sampled_rows(seed: int, rows: int, proj: int) -> torch.Tensor:

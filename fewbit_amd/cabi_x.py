@@ -9,7 +9,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from .cabi import DTYPES, SAMPLED_ROWS, FewbitHipError, _buffers, _matrix, _on, _sampled_call, _seed_word, _span, _stream
+from .cabi import DTYPES, FewbitHipError, _buffers, _matrix, _on, _planes_dtype, _row_numbers, _sampled_call, _seed_arguments, _span, _stream
 
 __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft', 'sampled_dft_seeded', 'sampled_dft_workspace_bytes', 'crs_columns',
            'crs_count', 'crs_workspace_bytes', 'crs_gather', 'crs_scatter', 'sampled_rows_ceil', 'sampled_dct_zext', 'sampled_dct_zext_seeded',
@@ -93,13 +93,7 @@ def sampled_dft_workspace_bytes(rows: int, features: int, proj: int, dtype: torc
     return lib().fewbit_hipx_sampled_dft_workspace(DTYPES[dtype], rows, features, proj)
 
 
-def _sampled_dft_call(m: torch.Tensor, proj: int, out_dtype: Optional[torch.dtype], out: Optional[torch.Tensor], workspace: Optional[torch.Tensor],
-                      others, launch) -> torch.Tensor:
-    out_dtype = m.dtype if out_dtype is None else out_dtype
-    if out_dtype not in (torch.float32, m.dtype):
-        raise FewbitHipError(f'out_dtype must be torch.float32 or the dtype of m (got {out_dtype})')
-    return _sampled_call('sampled_dft', sampled_dft_workspace_bytes, _check, m, proj, (2, ), out_dtype, '2 x proj x features tensor of out_dtype', out,
-                         workspace, others, lambda dt, *rest: launch(dt, DTYPES[out_dtype], *rest))
+_DFT = ('sampled_dft', sampled_dft_workspace_bytes, _check, (2, ), '2 x proj x features tensor of out_dtype')
 
 
 def sampled_dft(m: torch.Tensor, idx: torch.Tensor, scale: float = 1.0, out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None,
@@ -112,11 +106,9 @@ def sampled_dft(m: torch.Tensor, idx: torch.Tensor, scale: float = 1.0, out_dtyp
     Features ``(2c, 2c + 1)`` are transformed as one complex column: the rounding error of column ``c`` scales with the RMS of the pair
     ``(c, c ^ 1)``, and a NaN or Inf in one column makes its partner non-finite too (other columns stay bit for bit as they are).
     torch.fft keeps every column apart."""
-    if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != m.device or not idx.is_contiguous():
-        raise FewbitHipError('idx must be a contiguous 1-D int64 tensor on the device of m')
-    proj = idx.numel()
-    return _sampled_dft_call(m, proj, out_dtype, out, workspace, (idx, ), lambda dt, odt, mp, rows, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dft(
-        dt, mp, rows, features, ld, idx.data_ptr(), proj, scale, odt, op, wp, wb, _stream(stream, m.device)))
+    proj, odt = _row_numbers(idx, m), _planes_dtype(m, out_dtype)
+    return _sampled_call(_DFT, m, proj, odt, out, workspace, (idx, ), stream,
+                         lambda head, tail: lib().fewbit_hipx_sampled_dft(*head, idx.data_ptr(), proj, scale, DTYPES[odt], *tail))
 
 
 def sampled_dft_seeded(m: torch.Tensor, proj: int, seed, scale: float = 1.0, out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None,
@@ -126,13 +118,9 @@ def sampled_dft_seeded(m: torch.Tensor, proj: int, seed, scale: float = 1.0, out
     ``m`` whose value is read when the kernel runs (``cabi.next_sketch_seed``: a launch recorded into a hipGraph then samples fresh rows on
     every replay).  The pair contract of ``sampled_dft`` holds: column ``c``'s error scales with the RMS of the pair ``(c, c ^ 1)``, a
     non-finite value reaches the partner."""
-    if isinstance(seed, torch.Tensor):
-        _seed_word(seed, 'seed')
-        value, word, others = 0, seed.data_ptr(), (seed, )
-    else:
-        value, word, others = seed & 0xffffffffffffffff, 0, ()
-    return _sampled_dft_call(m, proj, out_dtype, out, workspace, others, lambda dt, odt, mp, rows, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dft_seeded(
-        dt, mp, rows, features, ld, value, word, proj, scale, odt, op, wp, wb, _stream(stream, m.device)))
+    (value, word, others), odt = _seed_arguments(seed), _planes_dtype(m, out_dtype)
+    return _sampled_call(_DFT, m, proj, odt, out, workspace, others, stream,
+                         lambda head, tail: lib().fewbit_hipx_sampled_dft_seeded(*head, value, word, proj, scale, DTYPES[odt], *tail))
 
 
 # ---- the sampled transforms at any row count: x is transformed as if zero rows followed it, up to a supported row count -------------------
@@ -144,35 +132,9 @@ def sampled_rows_ceil(rows: int) -> int:
     return lib().fewbit_hipx_sampled_rows_ceil(rows)
 
 
-def _zext_call(name: str, x: torch.Tensor, rows: int, proj: int, planes: tuple, out_dtype: torch.dtype, what: str, out: Optional[torch.Tensor],
-               workspace: Optional[torch.Tensor], others, launch) -> torch.Tensor:
-    """A zero-extended call: ``x`` checked (``valid_rows = x.shape[0]`` of them, 1 .. ``rows``), ``rows`` without a kernel refused by name,
-    ``out`` and the workspace (the plain formula at ``rows``) allocated or checked, then
-    ``launch(dtype, x, rows, valid_rows, features, ld, out, workspace, workspace bytes)``"""
-    valid, features, ld = _matrix(x)
-    need = sampled_dft_workspace_bytes(rows, features, proj, x.dtype)
-    if sampled_dft_workspace_bytes(rows, 1, 1, x.dtype) == 0:
-        raise FewbitHipError(f'{name}: no kernel for {rows} rows ({SAMPLED_ROWS} is needed; sampled_rows_ceil gives the next one)')
-    if not 1 <= valid <= rows:
-        raise FewbitHipError(f'{name}: x has {valid} rows, 1 .. rows = {rows} are needed')
-    with _on(x.device):
-        out, workspace = _buffers(x, others, out, (*planes, proj, features), out_dtype, what, workspace, need)
-        _check(launch(DTYPES[x.dtype], x.data_ptr(), rows, valid, features, ld, out.data_ptr(), *_span(workspace)))
-    return out
-
-
-def _seed_arguments(seed):
-    """-> (value, device word pointer, tensors to keep on the device of the call)"""
-    if isinstance(seed, torch.Tensor):
-        _seed_word(seed, 'seed')
-        return 0, seed.data_ptr(), (seed, )
-    return seed & 0xffffffffffffffff, 0, ()
-
-
-def _row_numbers(idx: torch.Tensor, x: torch.Tensor) -> int:
-    if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != x.device or not idx.is_contiguous():
-        raise FewbitHipError('idx must be a contiguous 1-D int64 tensor on the device of x')
-    return idx.numel()
+# (the workspace of a zero-extended call is the plain formula at ``rows``; the DCT's is asked of this library too, which owns its kernels)
+_DCT_ZEXT = ('sampled_dct_zext', sampled_dft_workspace_bytes, _check, (), 'proj x features tensor of the dtype of x')
+_DFT_ZEXT = ('sampled_dft_zext', sampled_dft_workspace_bytes, _check, (2, ), '2 x proj x features tensor of out_dtype')
 
 
 def sampled_dct_zext(x: torch.Tensor, rows: int, idx: torch.Tensor, scale: float = 1.0, out: Optional[torch.Tensor] = None,
@@ -184,10 +146,9 @@ def sampled_dct_zext(x: torch.Tensor, rows: int, idx: torch.Tensor, scale: float
 
     With rows drawn uniformly from ``[0, rows)`` and ``scale = sqrt(rows / p)`` this is a sketch ``S x`` with ``E[S^T S] = I`` over the rows of
     ``x`` (include/fewbit_hipx.h) -- unbiased like the layer's own, but not the reference's ``dct(x)[idx]`` at length ``x.shape[0]``."""
-    proj = _row_numbers(idx, x)
-    return _zext_call('sampled_dct_zext', x, rows, proj, (), x.dtype, 'proj x features tensor of the dtype of x', out, workspace, (idx, ),
-                      lambda dt, xp, n, valid, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dct_zext(
-                          dt, xp, n, valid, features, ld, idx.data_ptr(), proj, scale, op, wp, wb, _stream(stream, x.device)))
+    proj = _row_numbers(idx, x, 'x')
+    return _sampled_call(_DCT_ZEXT, x, proj, x.dtype, out, workspace, (idx, ), stream,
+                         lambda head, tail: lib().fewbit_hipx_sampled_dct_zext(*head, idx.data_ptr(), proj, scale, *tail), rows)
 
 
 def sampled_dct_zext_seeded(x: torch.Tensor, rows: int, p: int, seed, scale: float = 1.0, out: Optional[torch.Tensor] = None,
@@ -195,35 +156,25 @@ def sampled_dct_zext_seeded(x: torch.Tensor, rows: int, p: int, seed, scale: flo
     """``sampled_dct_zext(x, rows, cabi.sampled_rows(seed, rows, p))`` without the array of row numbers (``seed``: an int, or a one-element
     int64 tensor on the device of ``x`` that is read when the kernel runs, as in ``cabi.sampled_dct_seeded``)"""
     value, word, others = _seed_arguments(seed)
-    return _zext_call('sampled_dct_zext', x, rows, p, (), x.dtype, 'proj x features tensor of the dtype of x', out, workspace, others,
-                      lambda dt, xp, n, valid, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dct_zext_seeded(
-                          dt, xp, n, valid, features, ld, value, word, p, scale, op, wp, wb, _stream(stream, x.device)))
-
-
-def _dft_out_dtype(x: torch.Tensor, out_dtype: Optional[torch.dtype]) -> torch.dtype:
-    out_dtype = x.dtype if out_dtype is None else out_dtype
-    if out_dtype not in (torch.float32, x.dtype):
-        raise FewbitHipError(f'out_dtype must be torch.float32 or the dtype of x (got {out_dtype})')
-    return out_dtype
+    return _sampled_call(_DCT_ZEXT, x, p, x.dtype, out, workspace, others, stream,
+                         lambda head, tail: lib().fewbit_hipx_sampled_dct_zext_seeded(*head, value, word, p, scale, *tail), rows)
 
 
 def sampled_dft_zext(x: torch.Tensor, rows: int, idx: torch.Tensor, scale: float = 1.0, out_dtype: Optional[torch.dtype] = None,
                      out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
     """``scale * torch.fft.fft(cat(x, zeros), dim=0, norm='ortho')[idx]`` at length ``rows`` as a ``(2, proj, features)`` tensor (real plane,
     imaginary plane) of ``out_dtype``: ``sampled_dft`` of the zero-filled copy, bit for bit, without the copy (see ``sampled_dct_zext``)"""
-    proj, odt = _row_numbers(idx, x), _dft_out_dtype(x, out_dtype)
-    return _zext_call('sampled_dft_zext', x, rows, proj, (2, ), odt, '2 x proj x features tensor of out_dtype', out, workspace, (idx, ),
-                      lambda dt, xp, n, valid, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dft_zext(
-                          dt, xp, n, valid, features, ld, idx.data_ptr(), proj, scale, DTYPES[odt], op, wp, wb, _stream(stream, x.device)))
+    proj, odt = _row_numbers(idx, x, 'x'), _planes_dtype(x, out_dtype, 'x')
+    return _sampled_call(_DFT_ZEXT, x, proj, odt, out, workspace, (idx, ), stream,
+                         lambda head, tail: lib().fewbit_hipx_sampled_dft_zext(*head, idx.data_ptr(), proj, scale, DTYPES[odt], *tail), rows)
 
 
 def sampled_dft_zext_seeded(x: torch.Tensor, rows: int, p: int, seed, scale: float = 1.0, out_dtype: Optional[torch.dtype] = None,
                             out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
     """``sampled_dft_zext(x, rows, cabi.sampled_rows(seed, rows, p))`` without the array of row numbers (``seed`` as in ``sampled_dft_seeded``)"""
-    (value, word, others), odt = _seed_arguments(seed), _dft_out_dtype(x, out_dtype)
-    return _zext_call('sampled_dft_zext', x, rows, p, (2, ), odt, '2 x proj x features tensor of out_dtype', out, workspace, others,
-                      lambda dt, xp, n, valid, features, ld, op, wp, wb: lib().fewbit_hipx_sampled_dft_zext_seeded(
-                          dt, xp, n, valid, features, ld, value, word, p, scale, DTYPES[odt], op, wp, wb, _stream(stream, x.device)))
+    (value, word, others), odt = _seed_arguments(seed), _planes_dtype(x, out_dtype, 'x')
+    return _sampled_call(_DFT_ZEXT, x, p, odt, out, workspace, others, stream,
+                         lambda head, tail: lib().fewbit_hipx_sampled_dft_zext_seeded(*head, value, word, p, scale, DTYPES[odt], *tail), rows)
 
 
 # ---- column sampling of LinearCRS (fewbit_amd/csrc/fewbit_crs.hip): the columns of a seed, the gather of forward, the scatter of backward ----
@@ -251,21 +202,13 @@ def crs_workspace_bytes(rows: int, in_features: int, nopairs: int, dtype: torch.
     return lib().fewbit_hipx_crs_workspace(DTYPES[dtype], rows, in_features, nopairs)
 
 
-def _crs_seed(seed):
-    """-> (value, device word pointer, tensors to keep on the device of the call)"""
-    if isinstance(seed, torch.Tensor):
-        _seed_word(seed, 'seed')
-        return 0, seed.data_ptr(), (seed, )
-    return seed & 0xffffffffffffffff, 0, ()
-
-
 def _crs_call(name: str, src: torch.Tensor, seed, in_features: int, nopairs: int, shape, out: Optional[torch.Tensor], workspace: Optional[torch.Tensor],
               launch) -> torch.Tensor:
     rows = src.shape[0]
     need = crs_workspace_bytes(rows, in_features, nopairs, src.dtype)
     if need == 0:
         raise FewbitHipError(f'{name}: no kernel for {rows} rows, in_features = {in_features}, nopairs = {nopairs} of {src.dtype}')
-    value, word, others = _crs_seed(seed)
+    value, word, others = _seed_arguments(seed)
     with _on(src.device):
         out, workspace = _buffers(src, others, out, shape, src.dtype, f'{" x ".join(map(str, shape))} tensor of the dtype of the input', workspace, need)
         _check(launch(DTYPES[src.dtype], src.data_ptr(), value, word, out.data_ptr(), *_span(workspace), _stream(None, src.device)))

@@ -232,42 +232,7 @@ __global__ __launch_bounds__(kThreadsB, (N2 > 128 ? 2 : 4)) void dct_pass_b_kern
             y[2 * e + 1] = (w.x * vb.x - w.y * vb.y) * f;
         }
         const size_t fa = f0 + 2 * E * lane;
-        if constexpr (DT == FEWBIT_F32) {
-            float *o = static_cast<float *>(out) + j * features + fa;
-            if (fa + 2 * E <= features) {
-                if constexpr (E == 1) {
-                    *reinterpret_cast<f32x2 *>(o) = f32x2{y[0], y[1]};
-                } else {
-                    typedef f32x4 __attribute__((aligned(4))) f32x4u;
-#pragma unroll
-                    for (int e = 0; e < E; e += 2) *reinterpret_cast<f32x4u *>(o + 2 * e) = f32x4{y[2 * e], y[2 * e + 1], y[2 * e + 2], y[2 * e + 3]};
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 2 * E; ++e) if (fa + e < features) o[e] = y[e];
-            }
-        } else {
-            uint16_t *o = static_cast<uint16_t *>(out) + j * features + fa;
-            uint16_t h[2 * E];
-#pragma unroll
-            for (int e = 0; e < 2 * E; ++e) {
-                if constexpr (DT == FEWBIT_BF16) h[e] = __builtin_bit_cast(uint16_t, static_cast<__bf16>(y[e]));
-                else h[e] = __builtin_bit_cast(uint16_t, static_cast<_Float16>(y[e]));
-            }
-            if (fa + 2 * E <= features) {
-                typedef uint32_t __attribute__((aligned(2))) u32u;
-                typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-                typedef u32x2 __attribute__((aligned(2))) u32x2u;
-                typedef u32x4 __attribute__((aligned(2))) u32x4u;
-                auto pair = [&](int e) -> uint32_t { return static_cast<uint32_t>(h[2 * e]) | (static_cast<uint32_t>(h[2 * e + 1]) << 16); };
-                if constexpr (E == 1) *reinterpret_cast<u32u *>(o) = pair(0);
-                else if constexpr (E == 2) *reinterpret_cast<u32x2u *>(o) = u32x2{pair(0), pair(1)};
-                else *reinterpret_cast<u32x4u *>(o) = u32x4{pair(0), pair(1), pair(2), pair(3)};
-            } else {
-#pragma unroll
-                for (int e = 0; e < 2 * E; ++e) if (fa + e < features) o[e] = h[e];
-            }
-        }
+        store_values<DT, E>(out, j * features + fa, y, fa, features);
     };
 #pragma unroll
     for (int i = 0; i < kPre; ++i)

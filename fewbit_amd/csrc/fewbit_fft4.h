@@ -260,6 +260,48 @@ template <int DT> __device__ __forceinline__ void unpack_piece(u32x4 q, float (&
     }
 }
 
+// 2 E values of a result row (or of one plane of it) at element `at` of `out` (features fa .. fa + 2 E of the row): pass B's vector stores,
+// element by element where the row ends inside them
+template <int ODT, int E>
+__device__ __forceinline__ void store_values(void *out, size_t at, const float (&y)[2 * E], size_t fa, size_t features) {
+    if constexpr (ODT == FEWBIT_F32) {
+        float *o = static_cast<float *>(out) + at;
+        if (fa + 2 * E <= features) {
+            if constexpr (E == 1) {
+                *reinterpret_cast<f32x2 *>(o) = f32x2{y[0], y[1]};
+            } else {
+                typedef f32x4 __attribute__((aligned(4))) f32x4u;
+#pragma unroll
+                for (int e = 0; e < E; e += 2) *reinterpret_cast<f32x4u *>(o + 2 * e) = f32x4{y[2 * e], y[2 * e + 1], y[2 * e + 2], y[2 * e + 3]};
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 2 * E; ++e) if (fa + e < features) o[e] = y[e];
+        }
+    } else {
+        uint16_t *o = static_cast<uint16_t *>(out) + at;
+        uint16_t h[2 * E];
+#pragma unroll
+        for (int e = 0; e < 2 * E; ++e) {
+            if constexpr (ODT == FEWBIT_BF16) h[e] = __builtin_bit_cast(uint16_t, static_cast<__bf16>(y[e]));
+            else h[e] = __builtin_bit_cast(uint16_t, static_cast<_Float16>(y[e]));
+        }
+        if (fa + 2 * E <= features) {
+            typedef uint32_t __attribute__((aligned(2))) u32u;
+            typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+            typedef u32x2 __attribute__((aligned(2))) u32x2u;
+            typedef u32x4 __attribute__((aligned(2))) u32x4u;
+            auto pair = [&](int e) -> uint32_t { return static_cast<uint32_t>(h[2 * e]) | (static_cast<uint32_t>(h[2 * e + 1]) << 16); };
+            if constexpr (E == 1) *reinterpret_cast<u32u *>(o) = pair(0);
+            else if constexpr (E == 2) *reinterpret_cast<u32x2u *>(o) = u32x2{pair(0), pair(1)};
+            else *reinterpret_cast<u32x4u *>(o) = u32x4{pair(0), pair(1), pair(2), pair(3)};
+        } else {
+#pragma unroll
+            for (int e = 0; e < 2 * E; ++e) if (fa + e < features) o[e] = h[e];
+        }
+    }
+}
+
 constexpr int kFine = 128;                  // W_D^e = fine[e % 128] * coarse[e / 128] for e < N (coarse: N / 128 entries, at most 2048)
 constexpr int coarse_entries(int n) { return n / kFine > 0 ? n / kFine : 1; }
 __device__ __forceinline__ f32x2 table_unit(const f32x2 *fine, const f32x2 *coarse, int e, bool has_coarse) {

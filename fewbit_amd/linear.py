@@ -229,33 +229,42 @@ def _sketch_seed(generator: Optional[torch.Generator], device: torch.device):
     return cabi.next_sketch_seed(counter, _draw_seed(generator))
 
 
+def _kernel_rows(mat: torch.Tensor) -> bool:
+    """whether the rows of ``mat`` are unit-stride rows at least ``features`` apart: what the kernels take as it is"""
+    return mat.stride(1) == 1 and mat.stride(0) >= mat.shape[1]
+
+
 def _unit_stride(mat: torch.Tensor) -> torch.Tensor:
-    """``mat``, or a contiguous copy when its rows are not unit-stride rows at least ``features`` apart (e.g. the expanded gradient of a
-    sum: strides (0, 0)) -- what the kernels take"""
-    return mat if mat.stride(1) == 1 and mat.stride(0) >= mat.shape[1] else mat.contiguous()
+    """``mat``, or a contiguous copy when the kernels do not take its rows (e.g. the expanded gradient of a sum: strides (0, 0))"""
+    return mat if _kernel_rows(mat) else mat.contiguous()
 
 
 def _native_sketch(kind: str, mat: torch.Tensor, p: int, seed, scale: float) -> torch.Tensor:
+    """the dense leg of _native_project (a seam of its own: tests count the dense products of a step through it)"""
     from . import cabi
     return cabi.sketch(kind, _unit_stride(mat), p, seed, scale)
 
 
-def _native_transform(kind: str, mat: torch.Tensor, p: int, seed, scale: float, out_dtype: Optional[torch.dtype] = None, rows: Optional[int] = None) -> torch.Tensor:
-    """``scale * transform(mat, dim=0, norm='ortho')[rows(seed)]`` on this package's kernel pair: M is read once, one fp32 intermediate goes
+def _native_project(kind: str, mat: torch.Tensor, p: int, seed, scale: float, rows: int = 0, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """One estimator product on this package's kernels, the only place that picks the binding.  'gaussian' / 'rademacher': ``scale * S(seed) @ mat``.
+    'dct' / 'dft': ``scale * transform(mat, dim=0, norm='ortho')[rows(seed)]`` on the kernel pair: M is read once, one fp32 intermediate goes
     out and back, only the p sampled rows are written (the torch formulation materialises the whole transform in fp32 first).  'dct': a
     ``(p, features)`` tensor of the dtype of ``mat``; 'dft': a ``(2, p, features)`` tensor of ``out_dtype`` (default: the dtype of ``mat``),
-    ``[0]`` the real part, ``[1]`` the imaginary part.  ``rows`` other than the rows of ``mat``: the transform of that length of ``mat``
+    ``[0]`` the real part, ``[1]`` the imaginary part.  ``rows`` other than 0 and the rows of ``mat``: the transform of that length of ``mat``
     followed by zero rows (the zero-extended pair; the sampled rows are those of ``seed`` in ``[0, rows)``)"""
-    if rows is not None and rows != mat.shape[0]:
+    if kind in ('gaussian', 'rademacher'):
+        return _native_sketch(kind, mat, p, seed, scale)
+    mat = _unit_stride(mat)
+    if rows and rows != mat.shape[0]:
         from . import cabi_x
         if kind == 'dct':
-            return cabi_x.sampled_dct_zext_seeded(_unit_stride(mat), rows, p, seed, scale)
-        return cabi_x.sampled_dft_zext_seeded(_unit_stride(mat), rows, p, seed, scale, out_dtype)
+            return cabi_x.sampled_dct_zext_seeded(mat, rows, p, seed, scale)
+        return cabi_x.sampled_dft_zext_seeded(mat, rows, p, seed, scale, out_dtype)
     if kind == 'dct':
         from . import cabi
-        return cabi.sampled_dct_seeded(_unit_stride(mat), p, seed, scale)
+        return cabi.sampled_dct_seeded(mat, p, seed, scale)
     from . import cabi_x
-    return cabi_x.sampled_dft_seeded(_unit_stride(mat), p, seed, scale, out_dtype)
+    return cabi_x.sampled_dft_seeded(mat, p, seed, scale, out_dtype)
 
 
 _INJECTED: Optional[torch.Tensor] = None
@@ -333,15 +342,11 @@ def _native_transform_rows(kind: str, mat: torch.Tensor) -> int:
         return rows
     if not _EXTEND_ROWS or rows < 1:
         return 0
-    ld = mat.stride(0) if mat.stride(1) == 1 and mat.stride(0) >= mat.shape[1] else mat.shape[1]      # (what _unit_stride hands the kernels)
+    ld = mat.stride(0) if _kernel_rows(mat) else mat.shape[1]      # (what _unit_stride hands the kernels)
     if not _zext_span_ok(rows, ld, mat.element_size()):
         return 0
     from . import cabi_x
     return cabi_x.sampled_rows_ceil(rows)
-
-
-def _native_transform_applies(kind: str, mat: torch.Tensor) -> bool:
-    return _native_transform_rows(kind, mat) != 0
 
 
 _TRANSFORM_PATHS = {
@@ -372,8 +377,8 @@ def sampled_transform(kind: str, mat: torch.Tensor, p: int, gen: torch.Generator
     if not rows:
         return _sketch(kind, mat, p, gen, scale=scale)
     if kind == 'dct':
-        return _native_transform(kind, mat, p, seed, scale, rows=rows)
-    planes = _native_transform(kind, mat, p, seed, scale, torch.float32, rows)
+        return _native_project(kind, mat, p, seed, scale, rows)
+    planes = _native_project(kind, mat, p, seed, scale, rows, torch.float32)
     return torch.complex(planes[0], planes[1])
 
 
@@ -402,14 +407,14 @@ class _LinearGRP(torch.autograd.Function):
     def forward(ctx, input, weight, bias, p: int, kind: str, generator, sketch_dtype=None):
         flat = input.reshape(-1, input.shape[-1])
         rows = flat.shape[0]
-        ctx.native_seed = None
         ctx.p, ctx.kind = p, kind
         ctx.has_bias = bias is not None
+        # the route, decided here once: None -- the PyTorch formulation; 0 -- the dense kernel; N' -- the sampled-transform pair at N' rows: the
+        # rows of flat, or with use_row_extension() the next supported count (flat zero-extended; the rows of the seed are drawn from [0, N'),
+        # the scale is N' / p, and backward runs on the same N' and seed)
         dense = _native_sketch_applies(kind, flat, sketch_dtype)
-        # the row count the sampled-transform pair runs at: the rows of flat, or with use_row_extension() the next supported count N' (flat
-        # zero-extended; the rows of the seed are drawn from [0, N'), the scale is N' / p, and backward runs on the same N' and seed)
-        ctx.transform_rows = 0 if dense else _native_transform_rows(kind, flat)
-        if dense or ctx.transform_rows:
+        ctx.route = 0 if dense else _native_transform_rows(kind, flat) or None
+        if ctx.route is not None:
             # S -- or the sampled rows -- lives nowhere: a function of the seed that the kernel evaluates itself; the projection and the
             # seed are all that is kept (no randint launch, no RNG state to save and replay; while a graph is being captured the seed is
             # a device word)
@@ -419,14 +424,9 @@ class _LinearGRP(torch.autograd.Function):
             ctx.low = sketch_dtype if dense and sketch_dtype is not None and sketch_dtype != flat.dtype else None
             x = flat.detach() if ctx.low is None else flat.detach().to(ctx.low)
             # (the sketch before or after the layer's own GEMM: no difference, profiles/r05_roberta_ab_order.txt)
-            if dense:
-                kept = (_native_sketch(kind, x, p, ctx.native_seed, 1.0 / p), )
-            elif kind == 'dct':
-                kept = (_native_transform(kind, x, p, ctx.native_seed, ctx.transform_rows / p, rows=ctx.transform_rows), )
-            else:                                       # 'dft': the real and imaginary planes in the layer's dtype, two views of one buffer
-                planes = _native_transform(kind, x, p, ctx.native_seed, ctx.transform_rows / p, rows=ctx.transform_rows)
-                kept = (planes[0], planes[1])
-            ctx.save_for_backward(*kept, weight)
+            kept = _native_project(kind, x, p, ctx.native_seed, (ctx.route or 1) / p, ctx.route)
+            # ('dft': the real and imaginary planes in the layer's dtype, two views of one buffer)
+            ctx.save_for_backward(*((kept[0], kept[1]) if kind == 'dft' else (kept, )), weight)
             return F.linear(input, weight, bias)
         token, gen = _capture_rng(generator, input.device)
         scale = 1.0 / p if kind in ('gaussian', 'rademacher') else rows / p
@@ -444,23 +444,17 @@ class _LinearGRP(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             grad_input = grad_output @ weight
         flat = grad_output.reshape(-1, grad_output.shape[-1])
-        if ctx.needs_input_grad[1] and ctx.native_seed is not None:
+        if ctx.needs_input_grad[1] and ctx.route is not None:
             # the same S again, from the same seed (a grad_output of another dtype than the forward's input -- autocast --
             # still meets the same matrix: S does not depend on the operand dtype beyond its final rounding)
             g2 = flat if flat.dtype in (torch.float32, torch.float16, torch.bfloat16) else flat.float()
             if ctx.low is not None:
                 g2 = g2.to(ctx.low)
-            if ctx.kind == 'dft':
-                # Re((F G)^H (F X)) = Gr^T Xr + Gi^T Xi: two accumulating GEMMs in the dtype of the planes
-                xr, xi = saved[0], saved[1]
-                g = _native_transform('dft', g2, ctx.p, ctx.native_seed, 1.0, rows=ctx.transform_rows).to(xr.dtype)
-                grad_weight = torch.addmm(g[0].T @ xr, g[1].T, xi).to(weight.dtype)
+            proj = _native_project(ctx.kind, g2, ctx.p, ctx.native_seed, 1.0, ctx.route).to(sketch.dtype)
+            if len(saved) == 3:                         # Re((F G)^H (F X)) = Gr^T Xr + Gi^T Xi: two accumulating GEMMs in the dtype of the planes
+                grad_weight = torch.addmm(proj[0].T @ saved[0], proj[1].T, saved[1]).to(weight.dtype)
             else:
-                if ctx.kind == 'dct':
-                    proj = _native_transform('dct', g2, ctx.p, ctx.native_seed, 1.0, rows=ctx.transform_rows)
-                else:
-                    proj = _native_sketch(ctx.kind, g2, ctx.p, ctx.native_seed, 1.0)
-                grad_weight = (proj.to(sketch.dtype).T @ sketch).to(weight.dtype)
+                grad_weight = (proj.T @ sketch).to(weight.dtype)
         elif ctx.needs_input_grad[1]:
             proj = _sketch(ctx.kind, flat, ctx.p, _replay_rng(ctx.token), ctx.sketch_dtype, ctx.draw_dtype)
             if proj.is_complex():                                               # Re((F G)^H (F X))
