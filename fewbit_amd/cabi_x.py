@@ -13,7 +13,7 @@ from .cabi import DTYPES, FewbitHipError, _buffers, _matrix, _on, _planes_dtype,
 
 __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft', 'sampled_dft_seeded', 'sampled_dft_workspace_bytes', 'crs_columns',
            'crs_count', 'crs_workspace_bytes', 'crs_gather', 'crs_scatter', 'sampled_rows_ceil', 'sampled_dct_zext', 'sampled_dct_zext_seeded',
-           'sampled_dft_zext', 'sampled_dft_zext_seeded']
+           'sampled_dft_zext', 'sampled_dft_zext_seeded', 'moments_workspace_bytes', 'row_moments', 'sum_squares']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -23,7 +23,8 @@ REVISION = 2                                   # FEWBIT_HIPX_REVISION: additions
 SYMBOLS = ('fewbit_hipx_abi_version', 'fewbit_hipx_last_error', 'fewbit_hipx_sampled_dft_workspace', 'fewbit_hipx_sampled_dft',
            'fewbit_hipx_sampled_dft_seeded', 'fewbit_hipx_revision', 'fewbit_hipx_crs_columns', 'fewbit_hipx_crs_workspace', 'fewbit_hipx_crs_gather',
            'fewbit_hipx_crs_scatter', 'fewbit_hipx_sampled_rows_ceil', 'fewbit_hipx_sampled_dct_zext', 'fewbit_hipx_sampled_dct_zext_seeded',
-           'fewbit_hipx_sampled_dft_zext', 'fewbit_hipx_sampled_dft_zext_seeded')
+           'fewbit_hipx_sampled_dft_zext', 'fewbit_hipx_sampled_dft_zext_seeded', 'fewbit_hipx_moments_workspace', 'fewbit_hipx_row_moments',
+           'fewbit_hipx_sum_squares')
 
 _lib = None
 
@@ -75,6 +76,13 @@ def lib() -> ctypes.CDLL:
         L.fewbit_hipx_sampled_dft_zext.argtypes = [i32, vp, sz, sz, sz, sz, vp, sz, dbl, i32, vp, vp, sz, vp]
         L.fewbit_hipx_sampled_dft_zext_seeded.restype = i32
         L.fewbit_hipx_sampled_dft_zext_seeded.argtypes = [i32, vp, sz, sz, sz, sz, u64, vp, sz, dbl, i32, vp, vp, sz, vp]
+        # the moments of the variance estimator: inside revision 2 as well, recognised by their symbols
+        L.fewbit_hipx_moments_workspace.restype = sz
+        L.fewbit_hipx_moments_workspace.argtypes = [sz, sz, sz]
+        L.fewbit_hipx_row_moments.restype = i32
+        L.fewbit_hipx_row_moments.argtypes = [i32, vp, sz, sz, i32, vp, sz, sz, sz, vp, vp, sz, vp]
+        L.fewbit_hipx_sum_squares.restype = i32
+        L.fewbit_hipx_sum_squares.argtypes = [i32, vp, sz, vp, vp, sz, vp]
         _lib = L
     return _lib
 
@@ -240,3 +248,58 @@ def crs_scatter(t: torch.Tensor, seed, in_features: int, nopairs: int, out: Opti
     out_features, cap = t.shape
     return _crs_call('crs_scatter', t, seed, in_features, nopairs, (out_features, in_features), out, workspace,
                      lambda dt, tp, value, word, op, wp, wb, st: lib().fewbit_hipx_crs_scatter(dt, tp, out_features, cap, value, word, in_features, nopairs, op, wp, wb, st))
+
+
+# ---- the moments of the variance estimator (fewbit_amd/csrc/fewbit_moments.hip): sums of squares in fp64, one read of every element ----------
+def moments_workspace_bytes(rows: int, n: int = 1, m: int = 1) -> int:
+    """bytes of scratch a ``row_moments`` call on ``rows`` rows of ``n`` and ``m`` columns needs -- and a ``sum_squares`` call on ``rows``
+    elements, with ``n = m = 1``; 0 = no kernel (an extent of 0 or beyond the caps include/fewbit_hipx.h states)"""
+    if min(rows, n, m) < 0:
+        return 0
+    return lib().fewbit_hipx_moments_workspace(rows, n, m)
+
+
+def _rows_of(t: torch.Tensor, what: str) -> torch.Tensor:
+    """``t`` as the kernels take it: unit stride along the columns and a row stride that skips no row backwards; anything else as a copy"""
+    if t.dim() != 2:
+        raise FewbitHipError(f'{what} must be 2-D (got {t.dim()} dimensions)')
+    ok = (t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])
+    return t if ok else t.contiguous()
+
+
+def _moments_call(first: torch.Tensor, others, count: int, out: Optional[torch.Tensor], workspace: Optional[torch.Tensor], rows: int, n: int,
+                  m: int, launch) -> torch.Tensor:
+    need = moments_workspace_bytes(rows, n, m)
+    with _on(first.device):
+        out, workspace = _buffers(first, others, out, (count, ), torch.float64, f'float64 tensor of {count} element{"s" if count > 1 else ""}', workspace, need)
+        if workspace is None:                                   # (need == 0: the library names the offending extent)
+            workspace = torch.empty(0, dtype=torch.uint8, device=first.device)
+        _check(launch(out.data_ptr(), *_span(workspace), _stream(None, first.device)))
+    return out
+
+
+def row_moments(x: torch.Tensor, g: torch.Tensor, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``(sx, sg, sxg) = (sum_b |x_b|^2, sum_b |g_b|^2, sum_b |x_b|^2 |g_b|^2)`` of the rows of ``x`` (B x n) and ``g`` (B x m) as a float64
+    tensor of 3 elements on their device.  The dtypes (fp32 / fp16 / bf16) are independent.  Every element is read once and squared exactly,
+    every sum is fp64 in a fixed order: the same arguments give the same bits, each result is within ``B * max(n, m) * 2^-53`` relative
+    of the exact value.  Rows may be strided (``stride(1) == 1``, ``stride(0) >= columns``: no padding element is read); any other layout is
+    made contiguous first.  Enqueued on torch's current stream of that device; nothing is read back."""
+    x, g = _rows_of(x, 'x'), _rows_of(g, 'g')
+    (rows, n, ldx), (rows_g, m, ldg) = _matrix(x), _matrix(g)
+    if rows_g != rows:
+        raise FewbitHipError(f'x and g must have the same number of rows (got {rows} and {rows_g})')
+    return _moments_call(x, (g, ), 3, out, workspace, rows, n, m, lambda op, wp, wb, st: lib().fewbit_hipx_row_moments(
+        DTYPES[x.dtype], x.data_ptr(), n, ldx, DTYPES[g.dtype], g.data_ptr(), m, ldg, rows, op, wp, wb, st))
+
+
+def sum_squares(t: torch.Tensor, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``sum(t^2)`` over all elements of ``t`` (fp32 / fp16 / bf16, any shape; made contiguous if it is not) as a float64 tensor of 1 element
+    on its device: the arithmetic, the fixed order and the workspace of ``row_moments`` (within ``t.numel() * 2^-53`` relative)."""
+    if t.device.type != 'cuda':
+        raise FewbitHipError(f't must live on the GPU (got {t.device})')
+    if t.dtype not in DTYPES:
+        raise FewbitHipError(f'unsupported dtype {t.dtype}')
+    t = t if t.is_contiguous() else t.contiguous()
+    count = t.numel()
+    return _moments_call(t, (), 1, out, workspace, count, 1, 1,
+                         lambda op, wp, wb, st: lib().fewbit_hipx_sum_squares(DTYPES[t.dtype], t.data_ptr(), count, op, wp, wb, st))

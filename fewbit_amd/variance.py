@@ -10,15 +10,28 @@ module reports, per backward pass,
 * ``var_rmm  = (||X||_F^2 ||G||_F^2 - ||X^T G||_F^2) / B_proj``                   (added by the random projection)
 
 (definitions of fewbit/modules/variance.py:17-46; arXiv:2201.13195, section 3).
+
+All three are functions of four numbers, ``gradient_moments``:
+
+    sx = ||X||_F^2      sg = ||G||_F^2      sxg = sum_b ||x_b||^2 ||g_b||^2      cross = ||X^T G||_F^2
+    corr = cross / (sx sg)      var_sgd = B/(B-1) sxg - cross/(B-1)      var_rmm = (sx sg - cross) / B_proj
+
+On the GPU (fp32 / fp16 / bf16 operands, ``use_native_sketch()`` on) the first three come from ONE pass over X and G in their own dtypes
+(``cabi_x.row_moments``: exact squares, fp64 sums in a fixed order) and the fourth from ONE GEMM in the operands' dtype with fp32
+accumulation (``_cross_product``) followed by ``cabi_x.sum_squares`` -- no fp32 copies of the operands, nothing read back from the device,
+so an estimator without a callback can be captured into a hipGraph together with its layer (after one eager step).  Operands of
+different dtypes (autocast: fp32 input, bf16 gradient) are multiplied in the narrower one, the precision the layer's own exact
+weight-gradient GEMM has there; fp16 with bf16 multiplies in bf16.  ``sx``, ``sg`` and ``sxg`` are always those of the operands as they are.
 """
 from typing import Callable, Optional
 
 import torch
 
+from . import linear as _linear
 from .linear import projection_dim
 
 __all__ = ('GradientStorage', 'catch_gradients', 'VarianceEstimator', 'estimate_correlation', 'estimate_variance_sgd',
-           'estimate_variance_rmm')
+           'estimate_variance_rmm', 'gradient_moments', 'variance_path')
 
 
 class GradientStorage:
@@ -75,6 +88,55 @@ def estimate_variance_rmm(input: torch.Tensor, output: torch.Tensor, bs_proj: Op
     return (torch.linalg.norm(input)**2 * torch.linalg.norm(output)**2 - cross) / bs_proj
 
 
+_KERNEL_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _native_moments_apply(x: torch.Tensor, g: torch.Tensor) -> bool:
+    return (_linear.use_native_sketch() and x.device.type == 'cuda' and g.device == x.device and x.dtype in _KERNEL_DTYPES
+            and g.dtype in _KERNEL_DTYPES and x.dim() == 2 and g.dim() == 2 and x.shape[0] == g.shape[0] and min(x.shape + g.shape) > 0)
+
+
+def _cross_product(x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """``G^T X`` as an fp32 matrix from ONE GEMM in the operands' dtype (fp32 accumulation).  Operands of different dtypes are rounded to
+    the narrower one first (fp32 with a 16-bit dtype: that dtype; fp16 with bf16: bf16) -- the seam the tests count calls of."""
+    if x.dtype != g.dtype:
+        narrow = torch.bfloat16 if torch.bfloat16 in (x.dtype, g.dtype) else torch.float16
+        x, g = x.to(narrow), g.to(narrow)
+    if x.dtype == torch.float32:
+        return torch.mm(g.T, x)
+    return torch.mm(g.T, x, out_dtype=torch.float32)
+
+
+def gradient_moments(input: torch.Tensor, grad_output: torch.Tensor) -> torch.Tensor:
+    """``(sx, sg, sxg, cross)`` of a linear layer's input rows and output-gradient rows (leading dimensions are flattened) as a float64
+    tensor of 4 elements on the operands' device (module docstring).  GPU operands take the gfx950 kernels and one GEMM; host tensors,
+    float64 and ``use_native_sketch(False)`` take float64 PyTorch arithmetic.  Nothing is read back from the device."""
+    x = input.reshape(-1, input.shape[-1])
+    g = grad_output.reshape(-1, grad_output.shape[-1])
+    if _native_moments_apply(x, g):
+        from . import cabi_x
+        out = torch.empty(4, dtype=torch.float64, device=x.device)
+        workspace = torch.empty(cabi_x.moments_workspace_bytes(x.shape[0], x.shape[1], g.shape[1]), dtype=torch.uint8, device=x.device)
+        cabi_x.row_moments(x, g, out=out[:3], workspace=workspace)
+        cabi_x.sum_squares(_cross_product(x, g), out=out[3:], workspace=workspace)
+        return out
+    x, g = x.double(), g.double()
+    xx, gg = (x * x).sum(dim=1), (g * g).sum(dim=1)
+    product = x.T @ g
+    return torch.stack((xx.sum(), gg.sum(), xx @ gg, (product * product).sum()))
+
+
+def variance_path(input: torch.Tensor, grad_output: torch.Tensor) -> str:
+    """Which code computes ``gradient_moments(input, grad_output)`` (what tools/variance_bench.py prints beside its times)."""
+    x = input.reshape(-1, input.shape[-1])
+    g = grad_output.reshape(-1, grad_output.shape[-1])
+    if _native_moments_apply(x, g):
+        gemm = str(x.dtype if x.dtype == g.dtype else (torch.bfloat16 if torch.bfloat16 in (x.dtype, g.dtype) else torch.float16)).replace('torch.', '')
+        return (f'gfx950 kernels fewbit_hipx_row_moments (one pass over X and G, fp64 sums) + one {gemm} GEMM with fp32 accumulation + '
+                'fewbit_hipx_sum_squares on its fp32 product')
+    return 'float64 PyTorch arithmetic (fp64 copies of X and G, one fp64 GEMM)'
+
+
 class _VarianceState(GradientStorage):
 
     def __init__(self, callback: Optional[Callable] = None):
@@ -88,11 +150,13 @@ class _VarianceState(GradientStorage):
     def postprocess(self) -> None:
         if self.input is None or self.grad_output is None:
             return
-        x = self.input.reshape(-1, self.input.shape[-1]).float()
-        g = self.grad_output.reshape(-1, self.grad_output.shape[-1]).float()
-        corr = estimate_correlation(x, g)
-        var_sgd = estimate_variance_sgd(x, g, self.bs)
-        var_rmm = estimate_variance_rmm(x, g, self.bs_proj)
+        sx, sg, sxg, cross = gradient_moments(self.input, self.grad_output).unbind(0)
+        bs = self.bs or self.input.numel() // self.input.shape[-1]
+        bs_proj = self.bs_proj or bs
+        # (0-d float64 arithmetic on the operands' device; stored as float32, the dtype the three have always had)
+        corr = (cross / (sx * sg)).float()
+        var_sgd = (sxg * (bs / (bs - 1)) - cross / (bs - 1)).float()
+        var_rmm = ((sx * sg - cross) / bs_proj).float()
         if callable(self.callback):
             self.callback(corr, var_sgd, var_rmm, self.step)
         self.step += 1

@@ -28,7 +28,9 @@ extern "C" {
  *   revision 1: the version-1 library as first released (it has no fewbit_hipx_revision symbol).
  *   revision 2: fewbit_hipx_revision; the column sampling of LinearCRS: fewbit_hipx_crs_columns, _crs_workspace, _crs_gather, _crs_scatter.
  * The zero-extended sampled transforms (fewbit_hipx_sampled_rows_ceil, _sampled_dct_zext, _sampled_dft_zext and their _seeded forms) were
- * added inside revision 2: a binding recognises them by the presence of the symbols and refuses by name a library that lacks them. */
+ * added inside revision 2: a binding recognises them by the presence of the symbols and refuses by name a library that lacks them.
+ * So were the moments of the variance estimator (fewbit_hipx_moments_workspace, _row_moments, _sum_squares): inside revision 2, recognised
+ * by the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -137,6 +139,37 @@ int fewbit_hipx_crs_gather(int dtype, const void *x, size_t rows, size_t in_feat
                            size_t cap, void *out, void *workspace, size_t workspace_bytes, void *stream);
 int fewbit_hipx_crs_scatter(int dtype, const void *t, size_t out_features, size_t cap, uint64_t seed, const uint64_t *seed_device, size_t in_features,
                             size_t nopairs, void *gw, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The moments of the variance estimator (fewbit_amd/variance.py; arXiv:2201.13195, section 3).  For a linear layer's input rows X
+ * (rows x n) and output-gradient rows G (rows x m):
+ *     fewbit_hipx_row_moments   out3[0] = sx  = sum_b |x_b|^2      out3[1] = sg = sum_b |g_b|^2      out3[2] = sxg = sum_b |x_b|^2 |g_b|^2
+ *     fewbit_hipx_sum_squares   out1[0] = sum_i t[i]^2             (on the fp32 product X^T G: cross = |X^T G|_F^2)
+ * from which corr = cross / (sx sg), var_sgd = rows / (rows - 1) sxg - cross / (rows - 1), var_rmm = (sx sg - cross) / proj.
+ *   x, g   row-major with leading dimensions ldx >= n, ldg >= m (elements); dtype_x and dtype_g are INDEPENDENT, each F32 / F16 / BF16
+ *          (under autocast the gradient's dtype differs from the input's); pointers aligned to their element size, nothing more
+ *   t      `count` contiguous elements of `dtype`
+ *   out3 / out1   3 / 1 doubles in DEVICE memory, 8-byte aligned, written by the second launch
+ *   workspace     fewbit_hipx_moments_workspace(rows, n, m) bytes, 16-byte aligned -- for fewbit_hipx_sum_squares:
+ *          fewbit_hipx_moments_workspace(count, 1, 1); 24576 today, whatever the extents.  Contents are scratch and need no initialisation
+ *   Supported: rows, count, ldx, ldg in [1, 2^31], n and m in [1, 2^24].  A zero or larger extent and ld < n: FEWBIT_ERR_UNSUPPORTED with the
+ *          offending value in the message (the workspace query returns 0); an unknown dtype, a null or misaligned pointer and a short
+ *          workspace: FEWBIT_ERR_INVALID_ARGUMENT.
+ * Arithmetic: every element is widened to fp64 and squared exactly; every sum -- over a row, the product of the two row sums, over the
+ * rows -- is accumulated in fp64.  Nothing overflows for finite input (bf16 3e38 included); each output is within (terms added) x 2^-53
+ * relative of the exact value and exact whenever every partial sum is representable; NaN and Inf propagate to the outputs they belong to.
+ * Order: rows are dealt to waves, a wave reduces a row in a fixed lane order, a workgroup writes its three sums to the workspace, and a
+ * second launch of one workgroup adds those partials in a fixed order (lane l the partials l, l + 64, .. ascending, then a fixed
+ * butterfly).  There are no floating-point atomics: the same arguments give the same bits.  The plan is a pure function of the row count:
+ * rows per workgroup = max(16, ceil(rows / 1024)), at most 1024 workgroups (sum_squares: pieces of 1024 elements as rows, at least 4 per
+ * workgroup).
+ * Reads: each element of X, G and t once, 16 bytes at a time wherever a row's 16-byte aligned interior allows and element by element at
+ * its head and tail; no address at or beyond x + rows * ldx or g + rows * ldg and no element of a row's padding [n, ldx) is read.
+ * Two launches per call on `stream` (fewbit_amd/csrc/fewbit_moments.hip), no synchronisation: both calls can be captured into a hipGraph. */
+size_t fewbit_hipx_moments_workspace(size_t rows, size_t n, size_t m);
+int fewbit_hipx_row_moments(int dtype_x, const void *x, size_t n, size_t ldx, int dtype_g, const void *g, size_t m, size_t ldg, size_t rows, double *out3,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int fewbit_hipx_sum_squares(int dtype, const void *t, size_t count, double *out1, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

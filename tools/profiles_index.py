@@ -43,6 +43,8 @@ ROWS = [
     ('r06_dct_rounds.txt', 'both DCT passes against the number of workgroups (features swept): a fixed 7-9 us plus 7.5 ns per workgroup', f'{D} 7.5'),
     ('r07_transform_columns.txt', 'both sampled-transform kernel pairs per feature column on structured inputs: kernel / fp32 reference error ratios (tests/test_gpu_transform_columns.py)', f'{D} 6'),
     ('crs_bench.json', 'tools/sketch_bench.py (CRS=1): LinearCRS forward extra and weight-gradient part on the kernels against the torch formulation; rocprofv3 kernel times, gather byte-floor fraction', f'{E} 8.2'),
+    ('variance_bench.json', "tools/variance_bench.py: the variance estimator's postprocess on the kernels (row_moments + one GEMM + sum_squares) against the fp32 formulation it replaced and the float64 fallback; row_moments against two vector_norm calls, byte-floor fraction", f'{E} 8.9'),
+    ('moments_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1890 device functions before / after fewbit_moments.hip was added (13 new)', f'{E} 8.9'),
     ('r06_dct_stagger.txt|r06_dct_fused_upper_bound.txt|r06_dct_inter16.txt', 'DCT experiments not kept: staggered starts, both passes in one launch (timing only), a bf16 intermediate', 'EXPERIMENTS.md'),
     ('r0?_roberta_table_*.json', "tools/roberta_bench.py --table: the reference README's RoBERTa table per dtype and estimator", f'{D} 7.4'),
     ('r0?_roberta_ab_fp32.txt|r0?_roberta_ab_bf16.txt|r0?_roberta_randomized_insitu*.json', 'the randomized RoBERTa step, arms interleaved in one process; its GPU time by kernel class', f'{D} 7.4'),
