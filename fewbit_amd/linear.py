@@ -38,6 +38,9 @@ constructor / call signatures; the implementation is this repository's own:
   the stream is capturing, the seed is a device word that a recorded one-thread kernel re-derives on every replay
   (``_sketch_seed``), so a replayed training step draws a fresh ``S`` each time -- a seed recorded by value would repeat
   one matrix for ever.  (The reference reads the generator state back in forward and cannot be captured.)
+* inside training wrappers: backward runs under the autocast state its forward saw (``backward()`` may follow the ``autocast`` block); with
+  grad mode off, a frozen weight or no rows the layers are ``F.linear`` and nothing else (``_plain_linear``); backward reads its saved
+  tensors once (non-re-entrant checkpointing) and works on a contiguous ``grad_output`` (one gradient, one result, whatever its strides).
 
 The sampled transforms: 'dct' and 'dft' on 2-D GPU tensors of 2^8 .. 2^18, 3 x 2^8 .. 3 x 2^14, 5 x 2^8 .. 5 x 2^13, 7 x 2^9 .. 7 x 2^13,
 9 x 2^8 .. 9 x 2^12 or 15 x 2^8 .. 15 x 2^11 rows (``cabi.SAMPLED_ROWS``) run on this
@@ -401,6 +404,37 @@ def _sketch(kind: str, mat: torch.Tensor, p: int, gen: torch.Generator, sketch_d
     return out if scale == 1.0 else out * scale
 
 
+def _autocast_seen(device_type: str):
+    """the autocast state of the calling thread for ``device_type``, as a forward records it for its backward"""
+    enabled = torch.is_autocast_enabled(device_type)
+    return device_type, enabled, torch.get_autocast_dtype(device_type) if enabled else None
+
+
+def _autocast_as(seen):
+    """Context in which a backward runs under the autocast state its forward saw (what ``torch.amp.custom_bwd`` does; one Function serves
+    host and GPU tensors here, so the device type is the input's, recorded by the forward).  A plain ``autograd.Function``'s backward runs
+    under the state of the thread that calls ``backward()``: after the ``autocast`` block is left -- the ordinary AMP pattern -- a bf16
+    ``grad_output`` would meet the fp32 weight uncast.  No autocast in forward: disabled in backward, whatever the caller's state."""
+    device_type, enabled, dtype = seen
+    if torch.is_autocast_enabled(device_type) == enabled and (not enabled or torch.get_autocast_dtype(device_type) == dtype):
+        return contextlib.nullcontext()
+    return torch.autocast(device_type, dtype=dtype, enabled=enabled)
+
+
+def _dense_rows(grad_output: torch.Tensor) -> torch.Tensor:
+    """``grad_output`` as backward works on it: itself when contiguous (the usual case, no copy), else a contiguous copy -- the expanded
+    gradient of a ``sum()``, a transposed tensor.  The order in which ``sum(dim=0)`` and the library GEMMs add depends on the strides of
+    their operands, so without it one gradient in two layouts gave two results that differ in their last bits."""
+    return grad_output if grad_output.is_contiguous() else grad_output.contiguous()
+
+
+def _plain_linear(input: torch.Tensor, weight: torch.Tensor) -> bool:
+    """Whether a call is ``F.linear`` and nothing else: no weight gradient can follow (grad mode is off -- ``no_grad``, ``inference_mode``,
+    the first pass of a re-entrant checkpoint -- or the weight is frozen; ``ctx.needs_input_grad`` does not show grad mode), or there are no
+    rows to sketch (the weight gradient of ``F.linear`` is then exactly zero).  No seed is drawn, nothing is launched, nothing is saved."""
+    return not torch.is_grad_enabled() or not weight.requires_grad or input.numel() == 0
+
+
 class _LinearGRP(torch.autograd.Function):
 
     @staticmethod
@@ -408,6 +442,7 @@ class _LinearGRP(torch.autograd.Function):
         flat = input.reshape(-1, input.shape[-1])
         rows = flat.shape[0]
         ctx.p, ctx.kind = p, kind
+        ctx.autocast = _autocast_seen(input.device.type)
         ctx.has_bias = bias is not None
         # the route, decided here once: None -- the PyTorch formulation; 0 -- the dense kernel; N' -- the sampled-transform pair at N' rows: the
         # rows of flat, or with use_row_extension() the next supported count (flat zero-extended; the rows of the seed are drawn from [0, N'),
@@ -438,6 +473,11 @@ class _LinearGRP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_output):
+        with _autocast_as(ctx.autocast):
+            return _LinearGRP._backward(ctx, _dense_rows(grad_output))
+
+    @staticmethod
+    def _backward(ctx, grad_output):
         saved = ctx.saved_tensors                       # (sketch, weight); 'dft' on the kernel pair: (real plane, imaginary plane, weight)
         sketch, weight = saved[0], saved[-1]
         grad_input = grad_weight = grad_bias = None
@@ -480,7 +520,9 @@ def linear_grp(input: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
         raise ValueError('Param proj_dim_min should be not greater than param proj_dim_max.')
     if matmul not in MATMUL_TYPES:
         raise ValueError(f'Unexpected matmul type: {matmul}.')
-    rows = input.numel() // input.shape[-1] if input.numel() else 0
+    if _plain_linear(input, weight):
+        return F.linear(input, weight, bias)
+    rows = input.numel() // input.shape[-1]
     p = projection_dim(rows, proj_dim_ratio, proj_dim, proj_dim_max, proj_dim_min)
     return _LinearGRP.apply(input, weight, bias, p, matmul, generator, sketch_dtype)
 
@@ -526,6 +568,7 @@ class _LinearCRS(torch.autograd.Function):
         in_features = weight.shape[1]
         ctx.has_bias = bias is not None
         ctx.native_seed = None
+        ctx.autocast = _autocast_seen(input.device.type)
         flat = input.detach().reshape(-1, in_features)
         if _native_crs_applies(flat, weight, nopairs):
             from . import cabi_x
@@ -544,7 +587,13 @@ class _LinearCRS(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        kept, weight = ctx.saved_tensors[:2]
+        with _autocast_as(ctx.autocast):
+            return _LinearCRS._backward(ctx, _dense_rows(grad_output))
+
+    @staticmethod
+    def _backward(ctx, grad_output):
+        saved = ctx.saved_tensors                       # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
+        kept, weight = saved[:2]
         grad_input = grad_weight = grad_bias = None
         if ctx.needs_input_grad[0]:
             grad_input = grad_output @ weight
@@ -554,7 +603,7 @@ class _LinearCRS(torch.autograd.Function):
             t = (flat.T @ kept).to(weight.dtype)
             grad_weight = cabi_x.crs_scatter(t.contiguous(), ctx.native_seed, weight.shape[1], ctx.nopairs)
         elif ctx.needs_input_grad[1]:
-            cols = ctx.saved_tensors[2]
+            cols = saved[2]
             grad_weight = torch.zeros_like(weight)
             grad_weight[:, cols] = (flat.T @ kept).to(weight.dtype)
         if ctx.has_bias and ctx.needs_input_grad[2]:
@@ -566,6 +615,8 @@ def linear_crs(input: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
     """``F.linear`` with a column-sampled weight gradient (reference: ``linear_crs``, fewbit/functional/linear.py:65)."""
     if nopairs < 1:
         raise ValueError('Number of sampled pairs should be strictly positive.')
+    if _plain_linear(input, weight):
+        return F.linear(input, weight, bias)
     return _LinearCRS.apply(input, weight, bias, int(nopairs))
 
 
