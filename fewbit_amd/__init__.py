@@ -81,6 +81,7 @@ from . import modules  # noqa: E402,F401
 from . import approx, cli, compat, fft, linear, variance  # noqa: E402,F401
 from .modules import *  # noqa: E402,F401,F403
 from .linear import LinearCRS, LinearGRP, RandomizedLinear  # noqa: E402,F401
+from .dropout import Dropout, dropout, dropout_add  # noqa: E402,F401  (fewbit_amd.dropout is the function from here on; the module: sys.modules['fewbit_amd.dropout'])
 from .util import map_module, memory_usage_hooks  # noqa: E402,F401
 
 __version__ = '0.2.0'

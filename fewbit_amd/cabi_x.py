@@ -13,7 +13,8 @@ from .cabi import DTYPES, FewbitHipError, _buffers, _matrix, _on, _planes_dtype,
 
 __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft', 'sampled_dft_seeded', 'sampled_dft_workspace_bytes', 'crs_columns',
            'crs_count', 'crs_workspace_bytes', 'crs_gather', 'crs_scatter', 'sampled_rows_ceil', 'sampled_dct_zext', 'sampled_dct_zext_seeded',
-           'sampled_dft_zext', 'sampled_dft_zext_seeded', 'moments_workspace_bytes', 'row_moments', 'sum_squares']
+           'sampled_dft_zext', 'sampled_dft_zext_seeded', 'moments_workspace_bytes', 'row_moments', 'sum_squares',
+           'DROPOUT_SWEEP', 'dropout_threshold', 'dropout_keep', 'dropout_apply']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -24,7 +25,7 @@ SYMBOLS = ('fewbit_hipx_abi_version', 'fewbit_hipx_last_error', 'fewbit_hipx_sam
            'fewbit_hipx_sampled_dft_seeded', 'fewbit_hipx_revision', 'fewbit_hipx_crs_columns', 'fewbit_hipx_crs_workspace', 'fewbit_hipx_crs_gather',
            'fewbit_hipx_crs_scatter', 'fewbit_hipx_sampled_rows_ceil', 'fewbit_hipx_sampled_dct_zext', 'fewbit_hipx_sampled_dct_zext_seeded',
            'fewbit_hipx_sampled_dft_zext', 'fewbit_hipx_sampled_dft_zext_seeded', 'fewbit_hipx_moments_workspace', 'fewbit_hipx_row_moments',
-           'fewbit_hipx_sum_squares')
+           'fewbit_hipx_sum_squares', 'fewbit_hipx_dropout_threshold', 'fewbit_hipx_dropout_keep', 'fewbit_hipx_dropout')
 
 _lib = None
 
@@ -83,6 +84,13 @@ def lib() -> ctypes.CDLL:
         L.fewbit_hipx_row_moments.argtypes = [i32, vp, sz, sz, i32, vp, sz, sz, sz, vp, vp, sz, vp]
         L.fewbit_hipx_sum_squares.restype = i32
         L.fewbit_hipx_sum_squares.argtypes = [i32, vp, sz, vp, vp, sz, vp]
+        # the dropout of a seed: inside revision 2 as well, recognised by its symbols
+        L.fewbit_hipx_dropout_threshold.restype = i32
+        L.fewbit_hipx_dropout_threshold.argtypes = [dbl]
+        L.fewbit_hipx_dropout_keep.restype = i32
+        L.fewbit_hipx_dropout_keep.argtypes = [u64, ctypes.c_uint32, u64, sz, vp]
+        L.fewbit_hipx_dropout.restype = i32
+        L.fewbit_hipx_dropout.argtypes = [i32, vp, vp, vp, sz, u64, u64, vp, ctypes.c_uint32, vp]
         _lib = L
     return _lib
 
@@ -303,3 +311,50 @@ def sum_squares(t: torch.Tensor, out: Optional[torch.Tensor] = None, workspace: 
     count = t.numel()
     return _moments_call(t, (), 1, out, workspace, count, 1, 1,
                          lambda op, wp, wb, st: lib().fewbit_hipx_sum_squares(DTYPES[t.dtype], t.data_ptr(), count, op, wp, wb, st))
+
+
+# ---- dropout whose mask is a function of a seed (fewbit_amd/csrc/fewbit_dropout.hip): nothing is kept for backward but the seed -------------
+DROPOUT_SWEEP = 1 << 22                         # elements one sweep of the launch plan covers (2048 workgroups x 256 lanes x 8); beyond it lanes loop
+
+
+def dropout_threshold(p: float) -> int:
+    """``T``, the threshold of drop probability ``p``: the nearest integer to ``p * 65536`` (ties to even).  An element is dropped with
+    probability ``T / 65536`` exactly.  ``p`` outside [0, 1] (NaN included) is refused.  Evaluated on the host; no GPU needed."""
+    t = lib().fewbit_hipx_dropout_threshold(float(p))
+    if t < 0:
+        raise FewbitHipError(f'dropout probability has to be between 0 and 1, but got {p}')
+    return t
+
+
+def dropout_keep(seed: int, n: int, p: float, first: int = 0) -> torch.Tensor:
+    """The mask ``dropout_apply`` uses for ``seed``: ``keep(first + j)`` for ``j < n`` as a host bool tensor (True: the element is kept).  The
+    definition is include/fewbit_hipx.h's ("the mask of a seed"); evaluated on the host, no GPU needed; ``first`` may be any index."""
+    keep = torch.empty(n, dtype=torch.uint8)
+    _check(lib().fewbit_hipx_dropout_keep(seed & 0xffffffffffffffff, dropout_threshold(p), first, n, keep.data_ptr()))
+    return keep.bool()
+
+
+def dropout_apply(src: torch.Tensor, seed, p: float, addend: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, first: int = 0,
+                  stream: Optional[int] = None) -> torch.Tensor:
+    """``where(keep, (src.float() * scale [+ addend.float()]).to(dtype), addend or 0)`` for the mask of ``seed`` (``dropout_keep``) in ONE
+    launch: ``scale = float32(65536 / (65536 - T))`` with ``T = dropout_threshold(p)``.  Forward (``src = x``) and backward (``src = gy``, no
+    addend) of a dropout that keeps only its seed.  ``src``, ``addend`` and ``out``: contiguous fp32 / fp16 / bf16 GPU tensors of one shape and
+    dtype; ``out`` may BE ``src`` or ``addend`` (the same memory exactly).  ``seed``: an int, or a one-element int64 tensor on the device of
+    ``src`` that is read when the kernel runs (``cabi.next_sketch_seed``: a launch recorded into a hipGraph draws a fresh mask on every
+    replay).  ``first``: the flat index of ``src``'s first element in the logical tensor whose mask is drawn, a multiple of 8 (a shard of a
+    tensor passes its offset).  A dropped element is +0 (the addend's bits with an addend) even where ``src`` holds inf or NaN."""
+    if src.device.type != 'cuda':
+        raise FewbitHipError(f'src must live on the GPU (got {src.device})')
+    if src.dtype not in DTYPES:
+        raise FewbitHipError(f'unsupported dtype {src.dtype}')
+    if not src.is_contiguous():
+        raise FewbitHipError('src must be contiguous')
+    if addend is not None and (addend.shape != src.shape or addend.dtype != src.dtype or not addend.is_contiguous()):
+        raise FewbitHipError('addend must be a contiguous tensor of the shape and dtype of src')
+    threshold = dropout_threshold(p)
+    value, word, others = _seed_arguments(seed)
+    with _on(src.device):
+        out, _ = _buffers(src, others + (() if addend is None else (addend, )), out, src.shape, src.dtype, 'tensor of the shape and dtype of src', None, 0)
+        _check(lib().fewbit_hipx_dropout(DTYPES[src.dtype], src.data_ptr(), None if addend is None else addend.data_ptr(), out.data_ptr(), src.numel(), first,
+                                         value, word, threshold, _stream(stream, src.device)))
+    return out

@@ -254,3 +254,4 @@ del _name
 # (fewbit/functional/__init__.py:14-18).
 from .linear import linear_crs, linear_grp, linear_randomized  # noqa: E402,F401
 from .variance import GradientStorage, catch_gradients  # noqa: E402,F401
+from .dropout import dropout, dropout_add  # noqa: E402,F401

@@ -30,7 +30,9 @@ extern "C" {
  * The zero-extended sampled transforms (fewbit_hipx_sampled_rows_ceil, _sampled_dct_zext, _sampled_dft_zext and their _seeded forms) were
  * added inside revision 2: a binding recognises them by the presence of the symbols and refuses by name a library that lacks them.
  * So were the moments of the variance estimator (fewbit_hipx_moments_workspace, _row_moments, _sum_squares): inside revision 2, recognised
- * by the presence of the symbols. */
+ * by the presence of the symbols.
+ * So was the dropout whose mask is a function of a seed (fewbit_hipx_dropout_threshold, _dropout_keep, _dropout): inside revision 2,
+ * recognised by the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -170,6 +172,47 @@ size_t fewbit_hipx_moments_workspace(size_t rows, size_t n, size_t m);
 int fewbit_hipx_row_moments(int dtype_x, const void *x, size_t n, size_t ldx, int dtype_g, const void *g, size_t m, size_t ldg, size_t rows, double *out3,
                             void *workspace, size_t workspace_bytes, void *stream);
 int fewbit_hipx_sum_squares(int dtype, const void *t, size_t count, double *out1, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Dropout that keeps nothing for backward: the mask is a pure function of (seed, threshold, element index), evaluated alike by the
+ * host function and the kernel, so backward regenerates it from the seed.
+ *
+ * The mask of a seed.  For the element at flat index i of a logical contiguous tensor:
+ *     q       = i >> 3
+ *     w[0..3] = Philox4x32-10(counter = (low 32 bits of q, high 32 bits of q, 0, 5), key = (low 32 bits of seed, high 32 bits of seed))
+ *               (fewbit_philox.h; counter word 3 = 5 is this domain's own: 0 and 2 are the dense sketches', 3 the sampled rows', 4 the
+ *               CRS columns')
+ *     u(i)    = 16 bits of the block: word (i & 7) >> 1, its LOW half for even i, its HIGH half for odd i
+ *     T       = the threshold: the nearest integer to p * 65536 (ties to even), 0 <= T <= 65536
+ *     keep(i) = u(i) >= T                                   P(drop) = T / 65536 exactly
+ *     scale   = (float)(65536.0 / (65536 - T))              (T = 65536: everything is dropped, the scale is not used)
+ *     out[i]  = keep(i) ? round_to_dtype(float(src[i]) * scale [+ float(addend[i])]) : (addend ? addend[i] : +0)
+ * The product and the sum are separate fp32 operations and the result is rounded once to the dtype.  A dropped element is exactly +0 (with an
+ * addend: the addend's bits) whatever src holds -- an inf or NaN there has no influence on the result.  The scale is that of the realized
+ * probability T / 65536, so E[out] = src [+ addend] exactly; |p - T / 65536| <= 2^-17.
+ *
+ * fewbit_hipx_dropout_threshold: T of p on the host, -1 for p outside [0, 1] or NaN.
+ * fewbit_hipx_dropout_keep: keep(first + j) for j < count as bytes of 0 / 1 at a HOST pointer; no device is touched; any `first`
+ *   (threshold > 65536: FEWBIT_ERR_INVALID_ARGUMENT).
+ * fewbit_hipx_dropout: ONE launch on `stream` (fewbit_amd/csrc/fewbit_dropout.hip); forward (src = x) and backward (src = gy, addend = NULL) alike.
+ *   dtype        F32 / F16 / BF16, of src, addend and out; n elements each, contiguous
+ *   first        the flat index of src[0] in the logical tensor, a multiple of 8: a shard of a tensor draws the mask of the whole tensor
+ *   addend       may be NULL; given, out = addend + dropout(src) in the same pass
+ *   out          may alias src exactly, or addend exactly (any other overlap is undefined)
+ *   seed, seed_device   as in fewbit_hipx_crs_gather: seed_device != NULL is an 8-byte aligned DEVICE word read when the kernel runs (`seed`
+ *                is ignored), so a launch recorded in a hipGraph draws a fresh mask on every replay
+ *   threshold    T, 0 .. 65536
+ * Pointers need only the alignment of their element.  With src, addend and out all 16-byte aligned one Philox call serves eight elements
+ * moved by 16-byte loads and stores (one per lane for the 16-bit types, two for fp32); otherwise the elements are moved one by one and the
+ * bytes are the same.  No address at or beyond n elements is read or written.  No LDS, no workspace, no atomics: the same arguments give the
+ * same bits.  The plan is a pure function of n: lanes take blocks of 8 elements, 256 lanes to a workgroup, at most 2048 workgroups (2^22
+ * elements), beyond which each lane sweeps on by the width of the grid.
+ * Refused before anything is launched (FEWBIT_ERR_INVALID_ARGUMENT): an unknown dtype, threshold > 65536, first not a multiple of 8, a
+ * misaligned seed word, a null src or out, a pointer not aligned to its element.  n = 0: FEWBIT_OK, no launch. */
+int fewbit_hipx_dropout_threshold(double p);
+int fewbit_hipx_dropout_keep(uint64_t seed, uint32_t threshold, uint64_t first, size_t count, uint8_t *keep_host);
+int fewbit_hipx_dropout(int dtype, const void *src, const void *addend, void *out, size_t n, uint64_t first, uint64_t seed, const uint64_t *seed_device,
+                        uint32_t threshold, void *stream);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,9 @@ ROWS = [
     ('r07_transform_columns.txt', 'both sampled-transform kernel pairs per feature column on structured inputs: kernel / fp32 reference error ratios (tests/test_gpu_transform_columns.py)', f'{D} 6'),
     ('crs_bench.json', 'tools/sketch_bench.py (CRS=1): LinearCRS forward extra and weight-gradient part on the kernels against the torch formulation; rocprofv3 kernel times, gather byte-floor fraction', f'{E} 8.2'),
     ('variance_bench.json', "tools/variance_bench.py: the variance estimator's postprocess on the kernels (row_moments + one GEMM + sum_squares) against the fp32 formulation it replaced and the float64 fallback; row_moments against two vector_norm calls, byte-floor fraction", f'{E} 8.9'),
+    ('dropout_bench.json', "tools/dropout_bench.py: fewbit.functional.dropout / dropout_add forward + backward against torch's dropout at 16384 x 768 / 3072, bf16 and fp32; bytes saved for backward; the kernel alone against its byte floor", f'{E} 8.11'),
+    ('dropout_kernel_times.txt', 'rocprofv3 --kernel-trace over tools/dropout_bench.py: per-dispatch durations of the dropout kernel and of torch\'s forward / backward dropout kernels, per shape', f'{E} 8.11'),
+    ('roberta_dropout_bf16.json', 'tools/roberta_bench.py --dtype bf16 --dropout fewbit: RoBERTa-base b128 x s128 with every nn.Dropout swapped, alone and with the GELU swap', f'{E} 8.11'),
     ('moments_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1890 device functions before / after fewbit_moments.hip was added (13 new)', f'{E} 8.9'),
     ('r06_dct_stagger.txt|r06_dct_fused_upper_bound.txt|r06_dct_inter16.txt', 'DCT experiments not kept: staggered starts, both passes in one launch (timing only), a bf16 intermediate', 'EXPERIMENTS.md'),
     ('r0?_roberta_table_*.json', "tools/roberta_bench.py --table: the reference README's RoBERTa table per dtype and estimator", f'{D} 7.4'),

@@ -11,6 +11,9 @@ Two routes to the same kernels:
                             reference's monkey patch of `transformers.activations.ACT2FN['gelu']` amounts to (:139-147);
   --route both              module and op side by side (adds `op` and `op_vs_module` to the line).
     python tools/roberta_bench.py [--dtype fp32|bf16] [--steps 10] [--bits 3] [--route module|op|both]
+  --dropout fewbit          every `nn.Dropout` of the model is swapped for `fewbit.Dropout` (the mask of a seed: nothing saved for backward) in
+                            the fewbit / op variants and in every non-vanilla row of --table; the line gains a `dropout` entry: the vanilla
+                            model with ONLY the dropouts swapped, its peak memory and step time against the vanilla model.
 Prints one JSON line.
 """
 import argparse
@@ -69,6 +72,20 @@ def patch_gelu_with_raw_op(model, dtype, device):
         layer.intermediate.intermediate_act_fn = gelu3bit
         n += 1
     return n
+
+
+def swap_dropout(model):
+    """Every nn.Dropout -> fewbit.Dropout (the README's recipe)"""
+    n = [0]
+
+    def fn(mod, path):
+        if type(mod) is torch.nn.Dropout:
+            n[0] += 1
+            return fewbit.Dropout(mod.p, mod.inplace)
+        return mod
+
+    fewbit.map_module(model, fn)
+    return n[0]
 
 
 def swap_linear(model, ratio, sketch_dtype=None, matmul='gaussian'):
@@ -134,6 +151,7 @@ def main():
     ap.add_argument('--torch-sketch', action='store_true',
                     help='draw S with torch.randn / randint and multiply with torch.matmul (what round 3 measured) instead of the '
                          'gfx950 sketch kernels (fewbit_amd/csrc/fewbit_sketch.hip)')
+    ap.add_argument('--dropout', default='torch', choices=('torch', 'fewbit'), help="'fewbit': swap every nn.Dropout for fewbit.Dropout (module docstring)")
     args = ap.parse_args()
     dtype = {'fp32': torch.float32, 'bf16': torch.bfloat16}[args.dtype]
     dev = torch.device('cuda:0')
@@ -152,9 +170,10 @@ def main():
             model = build(dtype, dev)
             ng = swap_gelu(model, args.bits) if gelu else 0
             nl = swap_linear(model, args.linear_ratio, torch.bfloat16 if args.sketch_bf16 else None, args.matmul) if linear else 0
+            nd = swap_dropout(model) if args.dropout == 'fewbit' and (gelu or linear) else 0
             r = run(model, ids, labels, args.steps)
             rows.append({'gelu': f'{args.bits}-bit' if gelu else 'vanilla', 'linear': 'randomized' if linear else 'vanilla',
-                         'gelu_modules_swapped': ng, 'linear_modules_swapped': nl, 'ms_per_step': round(r['ms_per_step'], 2),
+                         'gelu_modules_swapped': ng, 'linear_modules_swapped': nl, 'dropout_modules_swapped': nd, 'ms_per_step': round(r['ms_per_step'], 2),
                          'peak_gib': round(r['peak_bytes'] / 2**30, 3), 'loss': r['loss']})
             del model
             torch.cuda.empty_cache()
@@ -171,6 +190,8 @@ def main():
 
     res = {}
     names = ('vanilla', 'fewbit') + (('op', ) if args.route in ('op', 'both') or args.only == 'op' else ())
+    if args.dropout == 'fewbit' and not args.only:
+        names += ('dropout', )
     for name in names:
         if args.only and name != args.only:
             continue
@@ -181,8 +202,9 @@ def main():
             swapped = patch_gelu_with_raw_op(model, dtype, dev)
         else:
             swapped = swap_gelu(model, args.bits) if name == 'fewbit' else 0
+        dropouts = swap_dropout(model) if args.dropout == 'fewbit' and name != 'vanilla' else 0
         res[name] = run(model, ids, labels, args.steps)
-        res[name]['gelu_modules_swapped'] = swapped
+        res[name]['gelu_modules_swapped'], res[name]['dropout_modules_swapped'] = swapped, dropouts
         del model
         torch.cuda.empty_cache()
     if args.only:
@@ -207,6 +229,12 @@ def main():
         out['peak_saving_bytes'] = out['summary']['peak_saving_bytes']
         out['saved_tensor_saving_bytes'] = out['summary']['saved_tensor_saving_bytes']
         out['step_time_ratio'] = out['summary']['step_time_ratio']
+    if 'dropout' in res:      # the dropouts alone
+        out['dropout'] = res['dropout']
+        out['dropout_summary'] = {'route': 'fewbit.Dropout in place of every nn.Dropout, nothing else swapped',
+                                  'peak_saving_bytes': res['vanilla']['peak_bytes'] - res['dropout']['peak_bytes'],
+                                  'saved_tensor_saving_bytes': res['vanilla']['saved_for_backward_bytes'] - res['dropout']['saved_for_backward_bytes'],
+                                  'step_time_ratio': res['dropout']['ms_per_step'] / res['vanilla']['ms_per_step']}
     if 'fewbit' in res and 'op' in res:
         out['op_vs_module'] = {'step_time_ratio': res['op']['ms_per_step'] / res['fewbit']['ms_per_step'],
                                'saved_bytes_difference': res['op']['saved_for_backward_bytes'] - res['fewbit']['saved_for_backward_bytes'],
