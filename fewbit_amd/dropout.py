@@ -15,7 +15,15 @@ regenerates the mask from the seed with the kernel that made it in forward (``fe
   recorded backward reads the same word as its forward.  (One eager call on the device precedes a capture, as for the randomized linears.)
 * The kernel serves fp32 / fp16 / bf16 GPU tensors with at least one element while ``linear.use_native_sketch()`` is on.  Host tensors,
   float64 and ``use_native_sketch(False)`` take ``torch.nn.functional.dropout`` unchanged.
-* Not differentiable twice (``once_differentiable``).
+* Not differentiable twice (``once_differentiable``); ``torch.func.grad`` / ``torch.vmap`` refuse the node (it has no ``setup_context``).
+* Inside training wrappers (tests/test_dropout_training.py, tests/test_gpu_dropout_training.py): under ``torch.autocast`` a 16-bit input stays
+  16-bit and ``backward()`` may follow the block; under ``torch.utils.checkpoint`` in both modes the recomputation draws the forward's seed
+  again, so output and gradients are the plain run's bit for bit -- PROVIDED the seed comes from a default generator (``generator=None``,
+  ``torch.default_generator``, ``torch.cuda.default_generators[i]``): checkpoint saves and restores only those.  With any other generator
+  the recomputation draws a SECOND seed: in non-reentrant mode the node keeps the forward's seed while the layers behind it receive
+  activations recomputed under another mask; in reentrant mode every gradient belongs to another mask than the output.  Nothing raises.
+* With grad mode off (``no_grad``, ``inference_mode``) a call still drops and builds no node; ``inplace=True`` then writes through the binding
+  and returns the input object itself, as torch does -- a leaf that requires grad keeps requiring it.
 """
 from typing import Optional
 
@@ -71,7 +79,9 @@ def dropout(input: torch.Tensor, p: float = 0.5, training: bool = True, inplace:
     """``torch.nn.functional.dropout`` whose backward needs no mask: on the kernel path (module docstring) the node saves no tensor, the mask
     is regenerated from the call's seed.  ``generator``: where the seed is drawn from (default: the host default generator).  Not training,
     or a threshold of 0: the input itself -- no launch, no node, no seed drawn.  A non-contiguous input gives a contiguous output; with
-    ``inplace=True`` the result is written into the input.  A dropped element is +0 even where the input is inf or NaN."""
+    ``inplace=True`` the result is written into the input (with grad mode off the input object itself is returned).  A dropped element is +0
+    even where the input is inf or NaN.  Inside ``torch.utils.checkpoint`` ``generator`` must be a default one (``None`` included): checkpoint
+    restores only those, and the recomputation must draw the forward's seed again (module docstring)."""
     _check_p(p)
     if not training or p == 0.0:
         return input
@@ -82,6 +92,16 @@ def dropout(input: torch.Tensor, p: float = 0.5, training: bool = True, inplace:
         return input
     if inplace and input.requires_grad and input.is_leaf and torch.is_grad_enabled():         # (before anything is written, as in torch)
         raise RuntimeError('a leaf Variable that requires grad is being used in an in-place operation.')
+    if inplace and not torch.is_grad_enabled():
+        # no node to build: written through the binding, and the caller gets its own tensor back (``Function.apply`` with grad mode off
+        # returns another tensor object that no longer requires grad, which ``x = drop(x)`` would silently keep)
+        src = input if input.is_contiguous() else input.contiguous()
+        cabi_x.dropout_apply(src, linear._sketch_seed(generator, input.device), float(p), out=src)
+        if src is input:
+            torch.autograd.graph.increment_version(input)             # (the write went through a pointer: autograd is told, as mark_dirty tells it)
+        else:
+            input.copy_(src)
+        return input
     return _SeededDropout.apply(input, None, float(p), inplace, generator)
 
 
@@ -108,7 +128,10 @@ class Dropout(torch.nn.Dropout):
         fewbit.map_module(model, lambda m, path: fewbit.Dropout(m.p, m.inplace) if type(m) is torch.nn.Dropout else m)
 
     The seed of a call is a draw from the host generator (``generator``, default: torch's default one), so ``torch.manual_seed`` reproduces a
-    run, and a model's other random streams move by one host draw per call relative to ``nn.Dropout``."""
+    run, and a model's other random streams move by one host draw per call relative to ``nn.Dropout``.  Inside ``torch.utils.checkpoint`` the
+    generator must be a default one (``None``, ``torch.default_generator``, ``torch.cuda.default_generators[i]``): checkpoint saves and
+    restores only those, so a generator of the caller's own draws a second seed in the recomputation and the gradients no longer belong to
+    the mask of the output (module docstring)."""
 
     def __init__(self, p: float = 0.5, inplace: bool = False, generator: Optional[torch.Generator] = None):
         super().__init__(p, inplace)

@@ -659,7 +659,11 @@ class LinearGRP(torch.nn.Linear):
     matmul : {'dct', 'dft', 'gaussian', 'rademacher'}, default='gaussian'
         Kind of random projection.
     generator : torch.Generator, optional
-        Source of randomness; without it the host default generator seeds every call.
+        Source of randomness; without it the host default generator seeds every call.  Inside ``torch.utils.checkpoint`` it must be a
+        DEFAULT generator (``None``, ``torch.default_generator`` or ``torch.cuda.default_generators[i]``): checkpoint saves and restores
+        only those, so with any other generator the recomputation draws a second seed -- in non-reentrant mode the layers behind this one
+        then receive activations recomputed under another sketch than the one this layer's backward uses, in reentrant mode every
+        gradient belongs to another sketch than the output.  With a default generator both modes give the plain run's bits.
     sketch_dtype : torch.dtype, optional
         dtype of the dense sketch products (extension; e.g. ``torch.bfloat16`` for an fp32 layer on the GPU).
 

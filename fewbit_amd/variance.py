@@ -70,6 +70,25 @@ def catch_gradients(input: torch.Tensor, storage: GradientStorage) -> torch.Tens
     return _Catch.apply(input, storage)
 
 
+class _CatchPair(torch.autograd.Function):
+    """``catch_gradients`` for ONE call of a module that may be called several times before a backward: the copy of the call's input and its
+    two row counts travel in the node (the copy as a saved tensor, so a checkpointed region releases it and recomputes it), and the storage
+    receives the complete pair -- input, ``bs``, ``bs_proj``, then ``backward(grad_output)`` -- when the gradient of THIS call arrives."""
+
+    @staticmethod
+    def forward(ctx, output: torch.Tensor, kept: torch.Tensor, storage: GradientStorage, bs: int, bs_proj: int) -> torch.Tensor:
+        ctx.storage, ctx.bs, ctx.bs_proj = storage, bs, bs_proj
+        ctx.save_for_backward(kept)
+        return output.view_as(output)
+
+    @staticmethod
+    def backward(ctx, grad_output: torch.Tensor):
+        storage = ctx.storage
+        (storage.input, ), storage.bs, storage.bs_proj = ctx.saved_tensors, ctx.bs, ctx.bs_proj
+        storage.backward(grad_output)
+        return grad_output, None, None, None, None
+
+
 def estimate_correlation(input: torch.Tensor, output: torch.Tensor) -> torch.Tensor:
     cross = torch.linalg.norm(input.T @ output)
     return (cross / (torch.linalg.norm(input) * torch.linalg.norm(output)))**2
@@ -167,7 +186,14 @@ class VarianceEstimator(torch.nn.Module):
     """Wraps a randomized linear layer (anything with ``proj_dim*`` attributes) and evaluates the three quantities
     above on every backward pass; ``callback(corr, var_sgd, var_rmm, step)`` receives them, ``.variance`` keeps the
     last triple.  (The reference stores ``var_sgd`` twice in ``.variance``, fewbit/modules/variance.py:77; here the
-    third entry is ``var_rmm``.)"""
+    third entry is ``var_rmm``.)
+
+    The copy of a call's input and its row counts travel with that call (``_CatchPair``): a wrapped layer that is called several times
+    before one ``backward()`` -- tied weights, a layer applied per segment, a siamese pair -- reports one triple per call, in backward
+    order, each of its own (input, gradient) pair; ``state.input`` / ``.grad_output`` / ``.bs`` / ``.bs_proj`` are filled when a pair is
+    complete and describe the last backward.  Inside ``torch.utils.checkpoint`` (both modes) a step reports once.  A call that cannot
+    reach a backward -- ``no_grad``, ``inference_mode``, nothing requiring grad -- is the wrapped model's call and nothing else: no copy,
+    and the state keeps describing the last step that had a gradient."""
 
     def __init__(self, model: torch.nn.Module, callback: Optional[Callable] = None):
         super().__init__()
@@ -179,14 +205,19 @@ class VarianceEstimator(torch.nn.Module):
         return self.state.variance
 
     def forward(self, input: torch.Tensor, *args, **kwargs):
+        # a call that cannot reach a backward (grad mode off, nothing requiring grad) is the model's and nothing else: no copy of the input,
+        # and the state keeps describing the last step that had a gradient
+        if not (torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in self.model.parameters()))):
+            return self.model(input, *args, **kwargs)
         rows = input.numel() // input.shape[-1]
-        self.state.bs = rows
-        self.state.bs_proj = projection_dim(rows, getattr(self.model, 'proj_dim_ratio', None),
-                                            getattr(self.model, 'proj_dim', None),
-                                            getattr(self.model, 'proj_dim_max', None),
-                                            getattr(self.model, 'proj_dim_min', None))
-        self.state.forward(input)
+        bs_proj = projection_dim(rows, getattr(self.model, 'proj_dim_ratio', None), getattr(self.model, 'proj_dim', None),
+                                 getattr(self.model, 'proj_dim_max', None), getattr(self.model, 'proj_dim_min', None))
+        kept = input.detach().clone()
         output = self.model(input, *args, **kwargs)
-        if isinstance(output, tuple):
-            return (catch_gradients(output[0], self.state), ) + tuple(output[1:])
-        return catch_gradients(output, self.state)
+        first = output[0] if isinstance(output, tuple) else output
+        if not first.requires_grad:
+            return output
+        # the pair of a call is completed by that call's own node: one module called twice in a step reports two triples, each of its own
+        # (input, gradient), in backward order; ``state.input`` / ``.grad_output`` / ``.bs`` / ``.bs_proj`` are those of the last backward
+        caught = _CatchPair.apply(first, kept, self.state, rows, bs_proj)
+        return (caught, ) + tuple(output[1:]) if isinstance(output, tuple) else caught
