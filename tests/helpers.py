@@ -325,6 +325,31 @@ def transform_rows(rows: int, k0: int, draws: int, seed: int) -> torch.Tensor:
     return torch.cat([torch.tensor([0, rows // 2, rows - 1, k0, rows - k0]), torch.randint(0, rows, (draws, ), generator=g)])
 
 
+# ---- the sampled transforms against their float64 rows (tests/test_gpu_transform_splits.py; shown to have teeth in tests/test_transform_rows_host.py) ----
+TRANSFORM_EPS = 3e-6                 # the fp32 four-step FFT stays within 3e-6 max|y| of the float64 transform
+ROUNDING = {torch.float32: 0.0, torch.float16: 2.0**-11, torch.bfloat16: 2.0**-8}      # one rounding of the fp32 result to the result's dtype
+
+
+def sampled_rows_check(got, want, rel: float = 0.0):
+    """The criterion every sampled-transform test states, per entry:
+
+        |got - want| <= rel |want| + 3e-6 max|want|
+
+    `got`: the kernel's (p, features) rows, or the (2, p, features) planes of the DFT (any float dtype, host or device); `want`: the
+    float64 rows of the same shape (numpy or torch), complex (p, features) for the planes; `rel`: ROUNDING of the result's dtype.
+    -> (ok, the worst |err| / bound).  A result of another shape or with a non-finite entry is not ok."""
+    want = torch.as_tensor(np.asarray(want))
+    want = torch.stack([want.real, want.imag]).double() if want.is_complex() else want.double()
+    got = got.detach().cpu().double()
+    if got.shape != want.shape:
+        return False, float('inf')
+    if not bool(torch.isfinite(got).all()):
+        return False, float('inf')
+    err = (got - want).abs()
+    tol = rel * want.abs() + TRANSFORM_EPS * float(want.abs().max())
+    return bool((err <= tol).all()), float((err / tol.clamp_min(1e-300)).max())
+
+
 CAPTURE_CHILD = '''
 import sys
 sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})

@@ -11,7 +11,9 @@ from helpers import BASE, GOLDEN
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 DTYPES = (torch.float32, torch.float16, torch.bfloat16)
-# (N', valid): each tile shape of pass A once, even and odd bounds for Makhoul's map; 131072 = 512 x 256: the tile above 64 KiB
+# (N', valid): the smallest row count of every family, even and odd bounds for Makhoul's map.  Their pass A tiles are N1 = 16 (256, 768, 1280,
+# 2304, 3840) and N1 = 32 (3584) only; the first test adds 131072 = 512 x 256 (the tile above 64 KiB) outside this tuple.  N1 = 64, 128 and 256,
+# and every other row count, are pinned bit for bit by tests/test_gpu_transform_splits.py, which runs all 38 counts of the dispatch table.
 PAIRS = ((256, 1), (256, 2), (256, 129), (256, 255), (256, 256), (768, 700), (1280, 1025), (2304, 2100), (3584, 3101), (3840, 3700))
 
 
