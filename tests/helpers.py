@@ -368,3 +368,89 @@ def large_tile_capture_in_a_fresh_process(kind):
     code = CAPTURE_CHILD.format(root=str(ROOT), tests=str(ROOT / 'tests'), kind=kind)
     r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'captured 32768-row step ok' in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+# ---- the same input through a kernel's tile body and through its element-wise tail (tests/test_gpu_tail_body.py, tests/test_gpu_step1_exhaustive.py) ----
+# A streaming activation kernel computes an element in a whole tile (64 x U groups, vectorised) or, where the tensor does not fill one, in the
+# element-wise tail of the last wave: separate code, separate conversions.  BODY_N = 65 x 1024 elements has no tail at U = 1 and at U = 2, and the wide
+# backward (one group of slack) still covers its first BODY_COVERED elements with tiles; a call of at most TAIL_N = 511 elements (63 full groups and
+# a ragged one of 7) has no tile at all.
+BODY_N, BODY_COVERED, TAIL_N = 66560, 66048, 511
+STREAM_TUNE_KEYS = ('waves_per_cu', 'chunk', 'lut_chunk', 'lut_blocks_per_cu', 'lut_min', 'u_fwd', 'u_bwd', 'u_step1')
+
+
+# the parameter sets of the 1-bit family: values the 16-bit dtypes hold exactly and values they do not (0.3, 1/3, 0.01, 0.1)
+STEP1_CASES = [('hardshrink', (0.5, )), ('hardshrink', (0.3, )), ('hardshrink', (1 / 3, )), ('hardsigmoid', ()), ('hardtanh', (-1.0, 1.0)),
+               ('hardtanh', (-0.3, 0.7)), ('leaky_relu', (0.01, )), ('leaky_relu', (0.1, )), ('leaky_relu', (0.3, )), ('leaky_relu', (0.5, )), ('relu', ()),
+               ('relu6', ()), ('softshrink', (0.5, )), ('softshrink', (0.3, )), ('softshrink', (1 / 3, )), ('threshold', (1.0, 3.0)), ('threshold', (0.3, -0.1))]
+GEOMETRIES = (('body', 1), ('body', 2), ('tail', 1), ('tail', 2))          # (where every element is computed, groups per lane per stage)
+
+
+def case_id(v) -> str:
+    """pytest id of a function name or of its parameter tuple"""
+    return v if isinstance(v, str) else '-'.join(f'{q:.3g}' for q in v)
+
+
+def kinks(p) -> tuple:
+    """0, +-p0, p1, +-3 and 6: the kink values of the 1-bit family, whose fp32 neighbours every fp32 probe includes"""
+    p0, p1 = (tuple(p) + (0.0, 0.0))[:2]
+    return (0.0, p0, -p0, p1, 3.0, -3.0, 6.0)
+
+
+def set_groups_per_lane(u: int) -> None:
+    """force U of every streaming kernel that is built with more than one (fewbit_hip_tune)"""
+    from fewbit_amd import cabi
+    cabi.tune(u_fwd=u, u_bwd=u, u_step1=u)
+
+
+def run_geometry(where: str, op, *inputs):
+    return (run_body if where == 'body' else run_tail)(op, *inputs)
+
+
+def all_16bit(dtype: torch.dtype) -> torch.Tensor:
+    """every pattern of a 16-bit dtype, 0x8000 .. 0xffff then 0x0000 .. 0x7fff"""
+    return torch.arange(-32768, 32768, dtype=torch.int32).to(torch.int16).view(dtype)
+
+
+def fp32_neighbours(values) -> torch.Tensor:
+    """float32(v) and its +-1 and +-2 ulp neighbours, for every v"""
+    v = torch.tensor(list(values), dtype=torch.float32).view(torch.int32)
+    return torch.cat([v + d for d in (-2, -1, 0, 1, 2)]).view(torch.float32)
+
+
+def probe_patterns(dtype: torch.dtype, kinks=()) -> torch.Tensor:
+    """The inputs of a tail-against-body case: every pattern of a 16-bit dtype; for fp32 the 65 536 patterns k * 65537 mod 2^32 (every exponent, both
+    signs), +-0, +-inf, NaN of both signs and the +-1 / +-2 ulp neighbours of every value of `kinks`."""
+    if dtype != torch.float32:
+        return all_16bit(dtype)
+    spread = ((torch.arange(65536, dtype=torch.int64) * 65537) & 0xffffffff).to(torch.int32).view(torch.float32)
+    special = torch.tensor([0, -0x80000000, 0x7f800000, -0x00800000, 0x7fc00000, -0x00400000], dtype=torch.int64).to(torch.int32).view(torch.float32)
+    x = torch.cat([spread, special, fp32_neighbours(kinks)])
+    assert x.numel() <= BODY_COVERED
+    return x
+
+
+def run_body(op, *inputs, dev='cuda:0'):
+    """op(*device tensors of BODY_N elements) -> tuple of per-element device tensors, on the inputs extended to BODY_N with their own first elements:
+    every input element lies in a whole tile.  -> the outputs of the inputs' own elements, on the host"""
+    n = inputs[0].numel()
+    assert BODY_N - 1024 <= n <= BODY_COVERED and all(t.numel() == n for t in inputs)
+    outs = op(*(torch.cat([t, t[:BODY_N - n]]).to(dev) for t in inputs))
+    return tuple(o[:n].cpu() for o in outs)
+
+
+def run_tail(op, *inputs, dev='cuda:0'):
+    """the same through calls of at most TAIL_N elements: every element is computed by the element-wise tail"""
+    n = inputs[0].numel()
+    on_dev = [t.to(dev) for t in inputs]
+    outs = [op(*(d[i:i + TAIL_N] for d in on_dev)) for i in range(0, n, TAIL_N)]
+    return tuple(torch.cat(col).cpu() for col in zip(*outs))
+
+
+def differing(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """positions whose bits differ, two NaNs counting as equal (host tensors of one dtype and shape)"""
+    assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
+    neq = bits(a) != bits(b)
+    if a.is_floating_point():
+        neq &= ~(torch.isnan(a) & torch.isnan(b))
+    return neq

@@ -56,6 +56,7 @@ ROWS = [
     ('transform_zext_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1320 device functions before / after the zero-extended pairs were added (570 new)', f'{E} 8.6'),
     ('store_values_isa_identity.txt', "tools/isa_digest.py --diff: machine code of all 1890 device functions before / after pass B's vector store became one function of fewbit_fft4.h", f'{E} 8.8'),
     ('linear_routes_bit_identity.txt', 'sha256 of the output, the kept tensors and the gradients of every route of linear_grp / linear_crs: two runs of the parent and one of the tree with one call path, side by side', f'{E} 8.8'),
+    ('tail_body_isa_identity.txt', "tools/isa_digest.py --diff and --where: the 168 fp16 activation kernels before / after the register barrier of Elem<FEWBIT_F16>::store -- 159 differ only behind their tile loop, 7 have the same loop with registers renumbered, 2 (threshold forward) a rescheduled address add", f'{E} 8.14'),
     # ---- experiments (kept as records; the design quotes only their conclusions)
     ('r02_launch_shape_sweep_*.txt|r03_*shape_sweep*.txt|r03_backward_size_crossover.txt', 'launch shape, groups per lane and size crossovers of the activation kernels', f'{D} 3.1'),
     ('r03_ablation_*.txt|r03_kernels_r02_vs_r03_ab.txt|r03_inplace_stores.txt|r04_inplace_*.txt', 'one stage compiled out at a time; in-place stores; round-to-round A/B', f'{D} 7.1; {E} 6'),
