@@ -13,7 +13,7 @@ from .cabi import DTYPES, FewbitHipError, _buffers, _matrix, _on, _planes_dtype,
 
 __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft', 'sampled_dft_seeded', 'sampled_dft_workspace_bytes', 'crs_columns',
            'crs_count', 'crs_workspace_bytes', 'crs_gather', 'crs_scatter', 'sampled_rows_ceil', 'sampled_dct_zext', 'sampled_dct_zext_seeded',
-           'sampled_dft_zext', 'sampled_dft_zext_seeded', 'moments_workspace_bytes', 'row_moments', 'sum_squares',
+           'sampled_dft_zext', 'sampled_dft_zext_seeded', 'sampled_signs', 'sampled_dct_signed', 'sampled_dft_signed', 'moments_workspace_bytes', 'row_moments', 'sum_squares',
            'DROPOUT_SWEEP', 'dropout_threshold', 'dropout_keep', 'dropout_apply']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
@@ -25,7 +25,8 @@ SYMBOLS = ('fewbit_hipx_abi_version', 'fewbit_hipx_last_error', 'fewbit_hipx_sam
            'fewbit_hipx_sampled_dft_seeded', 'fewbit_hipx_revision', 'fewbit_hipx_crs_columns', 'fewbit_hipx_crs_workspace', 'fewbit_hipx_crs_gather',
            'fewbit_hipx_crs_scatter', 'fewbit_hipx_sampled_rows_ceil', 'fewbit_hipx_sampled_dct_zext', 'fewbit_hipx_sampled_dct_zext_seeded',
            'fewbit_hipx_sampled_dft_zext', 'fewbit_hipx_sampled_dft_zext_seeded', 'fewbit_hipx_moments_workspace', 'fewbit_hipx_row_moments',
-           'fewbit_hipx_sum_squares', 'fewbit_hipx_dropout_threshold', 'fewbit_hipx_dropout_keep', 'fewbit_hipx_dropout')
+           'fewbit_hipx_sum_squares', 'fewbit_hipx_dropout_threshold', 'fewbit_hipx_dropout_keep', 'fewbit_hipx_dropout', 'fewbit_hipx_sampled_signs',
+           'fewbit_hipx_sampled_dct_signed', 'fewbit_hipx_sampled_dft_signed')
 
 _lib = None
 
@@ -91,6 +92,13 @@ def lib() -> ctypes.CDLL:
         L.fewbit_hipx_dropout_keep.argtypes = [u64, ctypes.c_uint32, u64, sz, vp]
         L.fewbit_hipx_dropout.restype = i32
         L.fewbit_hipx_dropout.argtypes = [i32, vp, vp, vp, sz, u64, u64, vp, ctypes.c_uint32, vp]
+        # the sampled transforms with the signs of a seed: inside revision 2 as well, recognised by their symbols
+        L.fewbit_hipx_sampled_signs.restype = i32
+        L.fewbit_hipx_sampled_signs.argtypes = [u64, u64, sz, vp]
+        L.fewbit_hipx_sampled_dct_signed.restype = i32
+        L.fewbit_hipx_sampled_dct_signed.argtypes = [i32, vp, sz, sz, sz, sz, u64, vp, sz, dbl, vp, vp, sz, vp]
+        L.fewbit_hipx_sampled_dft_signed.restype = i32
+        L.fewbit_hipx_sampled_dft_signed.argtypes = [i32, vp, sz, sz, sz, sz, u64, vp, sz, dbl, i32, vp, vp, sz, vp]
         _lib = L
     return _lib
 
@@ -191,6 +199,43 @@ def sampled_dft_zext_seeded(x: torch.Tensor, rows: int, p: int, seed, scale: flo
     (value, word, others), odt = _seed_arguments(seed), _planes_dtype(x, out_dtype, 'x')
     return _sampled_call(_DFT_ZEXT, x, p, odt, out, workspace, others, stream,
                          lambda head, tail: lib().fewbit_hipx_sampled_dft_zext_seeded(*head, value, word, p, scale, DTYPES[odt], *tail), rows)
+
+
+# ---- the sampled transforms behind a random sign per row (fewbit_amd/csrc/fewbit_signed.hip): scale * T(D x)[rows of the seed] -----------------
+_DCT_SIGNED = ('sampled_dct_signed', sampled_dft_workspace_bytes, _check, (), 'proj x features tensor of the dtype of x')
+_DFT_SIGNED = ('sampled_dft_signed', sampled_dft_workspace_bytes, _check, (2, ), '2 x proj x features tensor of out_dtype')
+
+
+def sampled_signs(seed: int, rows: int, first: int = 0) -> torch.Tensor:
+    """The signs ``sampled_dct_signed`` / ``sampled_dft_signed`` give the rows ``first .. first + rows`` of their input for ``seed``: a host
+    bool tensor, True where the row is negated.  The definition is include/fewbit_hipx.h's ("the signs of a seed"); evaluated on the host,
+    no GPU needed; ``first`` may be any row number below 2^64."""
+    if rows < 0 or first < 0:
+        raise FewbitHipError(f'rows and first must not be negative (got {rows}, {first})')
+    flip = torch.empty(rows, dtype=torch.uint8)
+    _check(lib().fewbit_hipx_sampled_signs(seed & 0xffffffffffffffff, first & 0xffffffffffffffff, rows, flip.data_ptr()))
+    return flip.bool()
+
+
+def sampled_dct_signed(x: torch.Tensor, rows: int, p: int, seed, scale: float = 1.0, out: Optional[torch.Tensor] = None,
+                       workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+    """``sampled_dct_zext_seeded`` of ``x`` with the rows of ``sampled_signs(seed, x.shape[0])`` negated, bit for bit, without the negated
+    copy: the kernel evaluates the signs itself and flips the sign bits of the rows it has just loaded.  ``rows``: the length of the
+    transform, a row count of ``cabi.SAMPLED_ROWS`` (``x.shape[0]`` itself where it is one).  ``seed``: an int, or a one-element int64 tensor
+    on the device of ``x`` that is read when the kernel runs -- for the sampled rows and the signs alike, so a launch recorded into a hipGraph
+    draws both afresh on every replay."""
+    value, word, others = _seed_arguments(seed)
+    return _sampled_call(_DCT_SIGNED, x, p, x.dtype, out, workspace, others, stream,
+                         lambda head, tail: lib().fewbit_hipx_sampled_dct_signed(*head, value, word, p, scale, *tail), rows)
+
+
+def sampled_dft_signed(x: torch.Tensor, rows: int, p: int, seed, scale: float = 1.0, out_dtype: Optional[torch.dtype] = None,
+                       out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+    """``sampled_dft_zext_seeded`` of ``x`` with the rows of ``sampled_signs(seed, x.shape[0])`` negated, bit for bit (see
+    ``sampled_dct_signed``); a ``(2, p, features)`` tensor of ``out_dtype``"""
+    (value, word, others), odt = _seed_arguments(seed), _planes_dtype(x, out_dtype, 'x')
+    return _sampled_call(_DFT_SIGNED, x, p, odt, out, workspace, others, stream,
+                         lambda head, tail: lib().fewbit_hipx_sampled_dft_signed(*head, value, word, p, scale, DTYPES[odt], *tail), rows)
 
 
 # ---- column sampling of LinearCRS (fewbit_amd/csrc/fewbit_crs.hip): the columns of a seed, the gather of forward, the scatter of backward ----

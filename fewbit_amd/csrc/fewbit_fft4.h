@@ -327,14 +327,31 @@ template <bool HALVES> __host__ __device__ __forceinline__ int drawn_row(const u
     else return static_cast<int>((static_cast<uint64_t>(w[h]) * rows) >> 32);
 }
 struct RowsInMemory {
-    static constexpr bool kSeeded = false;
+    static constexpr bool kSeeded = false, kSigned = false;
     const int64_t *idx;
 };
 struct RowsOfSeed {
-    static constexpr bool kSeeded = true;
+    static constexpr bool kSeeded = true, kSigned = false;
     sketch::Key value;
     const sketch::Key *device;              // != nullptr: the key is read from there when the kernel runs
 };
+// The rows of a seed AND its signs: the matrix is transformed as D m, D = diag(+-1) a function of the same seed (the random diagonal of
+// a subsampled randomized Fourier transform: it flattens the row energies of T D m whatever the rows of m share).
+//     w[0..3] = Philox4x32-10(counter = (low 32 bits of r >> 7, high 32 bits of r >> 7, 0, 6), key = seed)
+//     flip(r) = bit (r & 31) of w[(r >> 5) & 3]          1: row r of m (as it lies in memory) is negated
+// Only pass_a_zext_kernel knows it (ROWS::kSigned); the sampled rows and their sort are RowsOfSeed's.  The flag is a constant of the ROWS
+// type and not a template parameter of the kernel: a sixth parameter would rename every existing instantiation, and the kernels keep their
+// names and their machine code (tools/isa_digest.py --diff: profiles/signed_transform_isa_identity.txt).
+constexpr uint32_t kSignsDomain = 6u;       // counter word 3 (4: the CRS columns, 5: dropout)
+struct SignedRowsOfSeed : RowsOfSeed {
+    static constexpr bool kSigned = true;
+};
+__host__ __device__ __forceinline__ bool row_flipped(sketch::Key key, uint64_t r) {
+    const uint64_t q = r >> 7;
+    uint32_t w[4];
+    sketch::philox4x32(static_cast<uint32_t>(q), static_cast<uint32_t>(q >> 32), 0u, kSignsDomain, key, w);
+    return ((w[(r >> 5) & 3] >> (r & 31)) & 1u) != 0u;
+}
 
 // Pass B's workgroup (u, t) writes the samples k with k % N1 in {u, N1 - u}.  So that its 24 .. 96 siblings (one per half tile) need
 // not each test all of idx -- a third of pass B's time when they did (profiles/r06_dct_variants.txt: "noenlist") -- ONE workgroup, pass
@@ -438,7 +455,30 @@ struct RowsMakhoul {
 // the hardware's range check (offset >= the descriptor's bytes) answers with zeros without a memory access -- no branch, all loads in
 // flight at once as in the plain kernel.  The descriptor's size is 32 bits: valid_rows x ld elements must be below 4 GiB (zext_span_ok;
 // the host refuses more).  The edge tile (features % 64 != 0), loaded element by element as in the plain kernel, keeps the `if`.
+// The signs of a seed (ROWS = SignedRowsOfSeed; every other ROWS compiles to the code it was).  While its loads travel, the workgroup
+// evaluates flip(row) of the N1 rows it touches ONCE (at most two Philox calls per thread) into a table at the start of the tile's LDS,
+// every thread takes the entries of its own pieces into registers, and the tile is filled as before with ONE difference: the raw piece
+// is XORed with the sign bits of its elements (0x80008000 / 0x80000000 per dword) before it is unpacked -- exact in all three dtypes, the
+// bits of a matrix negated in memory.  Only what was loaded is flipped: a missing row and the zeros behind `features` in the edge tile
+// stay +0, so the result is bit for bit the unsigned kernel's on m with the flipped rows negated.  No branch around a load; the two
+// barriers stand between the loads' issue and their first use.
 constexpr uint32_t kBeyondZext = 0xfffffff0u;
+// the sign bits of the elements of a 16-byte piece that starts at feature f and lie inside the row (the whole piece in a full tile)
+template <int DT, bool FULL> __device__ __forceinline__ u32x4 sign_bits(size_t f, size_t features) {
+    if constexpr (DT == FEWBIT_F32) {
+        if (FULL || f + 4 <= features) return u32x4{0x80000000u, 0x80000000u, 0x80000000u, 0x80000000u};
+        u32x4 q;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q[e] = f + e < features ? 0x80000000u : 0u;
+        return q;
+    } else {
+        if (FULL || f + 8 <= features) return u32x4{0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u};
+        u32x4 q;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q[e] = (f + 2 * e < features ? 0x8000u : 0u) | (f + 2 * e + 1 < features ? 0x80000000u : 0u);
+        return q;
+    }
+}
 inline bool zext_span_ok(size_t valid_rows, size_t ld, int dtype) {
     const size_t row_bytes = ld * (dtype == FEWBIT_F32 ? 4 : 2);
     return row_bytes == 0 || valid_rows <= static_cast<size_t>(kBeyondZext) / row_bytes;
@@ -477,6 +517,24 @@ __global__ __launch_bounds__(kThreadsA, (N1 > 128 ? 2 : 4)) void pass_a_zext_ker
                 if (row < valid_rows) raw[i] = load_piece<DT, false>(x, row, ld, f0, piece, features);
             }
         }
+        uint32_t flip[kPieces];                                        // all ones: the piece's row is negated (kSigned alone)
+        if constexpr (ROWS::kSigned) {
+            uint32_t *flips = reinterpret_cast<uint32_t *>(lds_raw);   // [N1], where the tile will be
+            sketch::Key key = rows.value;
+            if (rows.device != nullptr) key = *rows.device;            // (one scalar load)
+            for (int m = tid; m < N1; m += kThreads) {
+                const size_t row = ORDER::template row<N>(N2 * m + b);
+                flips[m] = row < valid_rows && row_flipped(key, row) ? 0xffffffffu : 0u;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < kPieces; ++i) {
+                const int pid = tid + kThreads * i;
+                if (kTotal % kThreads != 0 && pid >= kTotal) break;
+                flip[i] = flips[pid / PPS];
+            }
+            __syncthreads();                                           // (the tables and the tile take this LDS over)
+        }
         for (int m = tid; m < N1; m += kThreads) tw[m] = unit(m, N1);
         for (int m = tid; m < kFine; m += kThreads) fine[m] = unit(m, N);
         for (int m = tid; m < kCoarse; m += kThreads) coarse[m] = unit(m * kFine, N);
@@ -485,6 +543,7 @@ __global__ __launch_bounds__(kThreadsA, (N1 > 128 ? 2 : 4)) void pass_a_zext_ker
             const int pid = tid + kThreads * i, n1 = pid / PPS, piece = pid % PPS;
             if (kTotal % kThreads != 0 && pid >= kTotal) break;
             float v[PF];
+            if constexpr (ROWS::kSigned) raw[i] ^= sign_bits<DT, decltype(full)::value>(f0 + static_cast<size_t>(piece) * PF, features) & flip[i];
             unpack_piece<DT>(raw[i], v);
             f32x4 *dst = reinterpret_cast<f32x4 *>(tile + n1 * C + piece * (PF / 2));
 #pragma unroll
@@ -662,6 +721,23 @@ template <typename PAIR, int DT> int opt_in_pass_b() {
     return rc;
 }
 
+// the LDS opt-in of a pair whose pass A takes the signs of the seed (fewbit_signed.hip): that of the zero-extended pair whose pass B it
+// runs (PAIR::opt_in_unsigned) and its own pass A reading DT -- once per device at the first signed call of DT, like opt_in_dtype
+template <typename PAIR, int DT> int opt_in_signed() {
+    static std::atomic<unsigned long long> done{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_relaxed) & bit) return FEWBIT_OK;
+    int rc = PAIR::template opt_in_unsigned<DT>();
+#define FB_FFT4_OPT_IN_SIGNED(A, B) \
+    if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_a<DT, A, B, SignedRowsOfSeed>(), lds_bytes_a<A>(A * B));
+    FB_FFT4_SPLITS(FB_FFT4_OPT_IN_SIGNED)
+#undef FB_FFT4_OPT_IN_SIGNED
+    if (rc == FEWBIT_OK) done.fetch_or(bit, std::memory_order_relaxed);
+    return rc;
+}
+
 // (valid_rows: the rows of m in memory, for a zero-extended pair; a plain pair's kernels do not take it)
 template <typename PAIR, int DT, typename ROWS>
 int launch_a(Split sp, const void *m, size_t valid_rows, size_t features, size_t ld, ROWS idx, size_t proj, f32x2 *inter, int *offsets, Sample *sorted, hipStream_t s) {
@@ -705,6 +781,10 @@ int launch_b(Split sp, const f32x2 *inter, const int *offsets, const Sample *sor
 #define FB_FFT4_UNIT_B(KEYWORD, PAIR, DT) \
     KEYWORD template int dct::launch_b<PAIR, DT>(dct::Split, const dct::f32x2 *, const int *, const dct::Sample *, size_t, size_t, float, void *, hipStream_t);
 #define FB_FFT4_UNIT(KEYWORD, PAIR, DT) FB_FFT4_UNIT_A(KEYWORD, PAIR, DT) FB_FFT4_UNIT_B(KEYWORD, PAIR, DT)
+// (a pair with the signs of the seed has a unit of that pass A alone)
+#define FB_FFT4_UNIT_SIGNED(KEYWORD, PAIR, DT)                                                                                 \
+    KEYWORD template int dct::opt_in_signed<PAIR, DT>();                                                                       \
+    KEYWORD template int dct::launch_a<PAIR, DT, dct::SignedRowsOfSeed>(dct::Split, const void *, size_t, size_t, size_t, dct::SignedRowsOfSeed, size_t, dct::f32x2 *, int *, dct::Sample *, hipStream_t);
 // (a zero-extended pair whose pass B is another pair's has a unit of pass A alone: FB_FFT4_UNIT_A)
 
 // calls f(std::integral_constant<int, DT>) for the run-time dtype (one of known_dtype)
@@ -742,7 +822,10 @@ int run(int dtype, int out_dtype, const void *m, size_t rows, size_t valid_rows,
         return PAIR::fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: a 16-byte aligned workspace of %zu bytes is needed (%s), got %zu", name, need, PAIR::kWorkspace, workspace_bytes);
     if (tiles_of(features) > 32767) return PAIR::fail(FEWBIT_ERR_UNSUPPORTED, "%s: more than 32767 column tiles", name);
     if (proj > 0x7fffffffull) return PAIR::fail(FEWBIT_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 samples", name);
-    auto opt_in = [](auto dt) { return opt_in_dtype<PAIR, decltype(dt)::value>(); };
+    auto opt_in = [](auto dt) {
+        if constexpr (ROWS::kSigned) return opt_in_signed<PAIR, decltype(dt)::value>();
+        else return opt_in_dtype<PAIR, decltype(dt)::value>();
+    };
     if (const int rc = with_dtype(dtype, opt_in)) return rc;
     if (out_dtype != dtype)
         if (const int rc = with_dtype(out_dtype, opt_in)) return rc;

@@ -61,6 +61,16 @@ the zero rows, S = sqrt(N' / p) R C' P has E[S^T S] = (N' / p) P^T C'^T (p / N')
 forward (scale N' / p) and backward (scale 1) is an unbiased estimate of ``G^T X``.  It is an estimator of the same kind as the layer's own
 but NOT the reference's ``dct(X)[idx]`` at length N -- another random variable with the same mean -- which is why it is opt-in.
 
+Random signs in front of the transform: with ``use_sign_flips(True)`` (or ``FEWBIT_SIGN_FLIPS=1``; off by default) 'dct' and 'dft' use
+``S = sqrt(N / p) R T D`` with ``D = diag(+-1)``, the subsampled RANDOMIZED transform.  ``E[S^T S] = D T^H T D = I`` for every ``D``, so the
+estimate stays unbiased; what ``D`` buys is the variance: without it a component many rows share (a mean activation, a repeated token) lands in
+a few rows of ``T X`` that the ``p`` samples hit or miss, and the variance grows like ``N`` times the dense sketches' level; with it the level
+``VarianceEstimator``'s ``var_rmm`` assumes holds.  On the kernel pairs the signs are, like the rows, a function of the call's seed
+(``cabi_x.sampled_signs(seed, rows)`` on the host) that pass A evaluates itself and XORs into the rows it has just loaded
+(``fewbit_hipx_sampled_dct_signed`` / ``_dft_signed``, zero-extended with ``use_row_extension()``): still one integer kept for backward, no
+read-back, capturable after one eager call, and autocast, checkpoint and ``no_grad`` behave as above.  The PyTorch formulation draws ``D``
+from the call's generator before the rows.  The autograd node records whether its forward flipped; backward follows the record.
+
 Column sampling: ``linear_crs`` / ``LinearCRS`` on fp32 / fp16 / bf16 GPU tensors follows the same contract on the kernels of
 ``fewbit_amd/csrc/fewbit_crs.hip`` (companion library: ``fewbit_hipx_crs_gather``, ``fewbit_hipx_crs_scatter``): the drawn columns are a function
 of the call's seed (``cabi_x.crs_columns(seed, in_features, nopairs)`` on the host), forward is one gather-and-scale call, backward one GEMM and
@@ -78,7 +88,7 @@ import torch.nn.functional as F
 from .fft import dct
 
 __all__ = ('MATMUL_TYPES', 'projection_dim', 'linear_crs', 'linear_grp', 'linear_randomized', 'LinearCRS', 'LinearGRP',
-           'RandomizedLinear', 'use_native_sketch', 'use_row_extension', 'sampled_transform', 'sampled_transform_path')
+           'RandomizedLinear', 'use_native_sketch', 'use_row_extension', 'use_sign_flips', 'sampled_transform', 'sampled_transform_path')
 
 MATMUL_TYPES = ('dct', 'dft', 'gaussian', 'rademacher')
 
@@ -151,6 +161,21 @@ def use_row_extension(on: Optional[bool] = None) -> bool:
     prev = _EXTEND_ROWS
     if on is not None:
         _EXTEND_ROWS = bool(on)
+    return prev
+
+
+_SIGN_FLIPS = os.environ.get('FEWBIT_SIGN_FLIPS', '0') in ('1', 'yes', 'true')
+
+
+def use_sign_flips(on: Optional[bool] = None) -> bool:
+    """Query / set whether 'dct' and 'dft' (``linear_grp`` / ``LinearGRP`` / ``RandomizedLinear``, ``sampled_transform``) negate a random
+    half of the rows before the transform: ``S = sqrt(N / p) R T D``, ``D = diag(+-1)`` (module docstring).  Off by default (environment:
+    ``FEWBIT_SIGN_FLIPS=1`` turns it on); off, nothing changes.  A backward follows what its forward did, not this switch.  Returns the
+    previous setting."""
+    global _SIGN_FLIPS
+    prev = _SIGN_FLIPS
+    if on is not None:
+        _SIGN_FLIPS = bool(on)
     return prev
 
 
@@ -248,16 +273,23 @@ def _native_sketch(kind: str, mat: torch.Tensor, p: int, seed, scale: float) -> 
     return cabi.sketch(kind, _unit_stride(mat), p, seed, scale)
 
 
-def _native_project(kind: str, mat: torch.Tensor, p: int, seed, scale: float, rows: int = 0, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+def _native_project(kind: str, mat: torch.Tensor, p: int, seed, scale: float, rows: int = 0, out_dtype: Optional[torch.dtype] = None,
+                    signed: bool = False) -> torch.Tensor:
     """One estimator product on this package's kernels, the only place that picks the binding.  'gaussian' / 'rademacher': ``scale * S(seed) @ mat``.
     'dct' / 'dft': ``scale * transform(mat, dim=0, norm='ortho')[rows(seed)]`` on the kernel pair: M is read once, one fp32 intermediate goes
     out and back, only the p sampled rows are written (the torch formulation materialises the whole transform in fp32 first).  'dct': a
     ``(p, features)`` tensor of the dtype of ``mat``; 'dft': a ``(2, p, features)`` tensor of ``out_dtype`` (default: the dtype of ``mat``),
     ``[0]`` the real part, ``[1]`` the imaginary part.  ``rows`` other than 0 and the rows of ``mat``: the transform of that length of ``mat``
-    followed by zero rows (the zero-extended pair; the sampled rows are those of ``seed`` in ``[0, rows)``)"""
+    followed by zero rows (the zero-extended pair; the sampled rows are those of ``seed`` in ``[0, rows)``).  ``signed``: 'dct' / 'dft' of
+    ``mat`` with the rows of ``cabi_x.sampled_signs(seed, mat.shape[0])`` negated (the signed pair, at either length)"""
     if kind in ('gaussian', 'rademacher'):
         return _native_sketch(kind, mat, p, seed, scale)
     mat = _unit_stride(mat)
+    if signed:
+        from . import cabi_x
+        if kind == 'dct':
+            return cabi_x.sampled_dct_signed(mat, rows or mat.shape[0], p, seed, scale)
+        return cabi_x.sampled_dft_signed(mat, rows or mat.shape[0], p, seed, scale, out_dtype)
     if rows and rows != mat.shape[0]:
         from . import cabi_x
         if kind == 'dct':
@@ -299,6 +331,12 @@ def _dense_sketch(kind: str, p: int, rows: int, like: torch.Tensor, gen: torch.G
         return torch.randn((p, rows), generator=gen, device=gen.device, dtype=draw_dtype or like.dtype).to(like.device, like.dtype)
     signs = torch.randint(0, 2, (p, rows), generator=gen, device=gen.device, dtype=torch.int8).to(like.device)
     return (signs.to(like.dtype) * 2) - 1                                       # Rademacher: +-1
+
+
+def _flipped_rows(mat: torch.Tensor, gen: torch.Generator) -> torch.Tensor:
+    """``D mat`` for a ``D = diag(+-1)`` drawn from ``gen`` (one draw of ``rows`` bits; negation is exact in every dtype)"""
+    flip = torch.randint(0, 2, (mat.shape[0], ), generator=gen, device=gen.device, dtype=torch.int8).to(mat.device).bool()
+    return torch.where(flip.unsqueeze(1), -mat, mat)
 
 
 def _sampled_rows(p: int, rows: int, like: torch.Tensor, gen: torch.Generator) -> torch.Tensor:
@@ -362,6 +400,11 @@ _TRANSFORM_PATHS = {
 def sampled_transform_path(kind: str, mat: torch.Tensor) -> str:
     """Which code computes the sampled transform ``kind`` ('dct' / 'dft') of ``mat`` (what bench.py prints beside its time)."""
     rows = _native_transform_rows(kind, mat)
+    if rows and _SIGN_FLIPS:
+        planes = '' if kind == 'dct' else ', real and imaginary planes'
+        length = '' if rows == mat.shape[0] else f', zero-extended to {rows} rows'
+        return (f'gfx950 kernel pair fewbit_hipx_sampled_{kind}_signed{length} (rows negated by the signs of the seed as pass A loads them, '
+                f'four-step fp32 FFT in LDS, only the sampled rows are written{planes}; in the layer: rows and signs of one seed)')
     if rows == mat.shape[0] and rows:
         return _TRANSFORM_PATHS[kind]
     if rows:
@@ -369,24 +412,28 @@ def sampled_transform_path(kind: str, mat: torch.Tensor) -> str:
         return (f'gfx950 kernel pair fewbit_hipx_sampled_{kind}_zext, zero-extended to {rows} rows (four-step fp32 FFT in LDS, the missing rows are '
                 f'never loaded, only the sampled rows are written{planes}; in the layer: rows of a seed; an unbiased estimator, not the '
                 "reference's transform at the true length)")
-    return 'torch.fft (rocFFT on the GPU): full transform along dim 0 in fp32, then the gather of the sampled rows'
+    signs = 'rows negated by random signs of the generator, then ' if _SIGN_FLIPS else ''
+    return f'torch.fft (rocFFT on the GPU): {signs}full transform along dim 0 in fp32, then the gather of the sampled rows'
 
 
 def sampled_transform(kind: str, mat: torch.Tensor, p: int, gen: torch.Generator, seed: int = 1234, scale: float = 1.0) -> torch.Tensor:
     """One estimator product of the layer, ``scale * transform(mat)[p sampled rows]``, on the path ``linear_grp`` takes for this
     ``kind`` and ``mat`` (what bench.py and tools/ time): the kernel pair with rows of ``seed``, or torch.fft + randint from ``gen``.
-    'dft' returns a complex64 ``(p, features)`` tensor on either path (on the kernel pair: built from its fp32 planes)."""
+    'dft' returns a complex64 ``(p, features)`` tensor on either path (on the kernel pair: built from its fp32 planes).  With
+    ``use_sign_flips()`` on, the rows are negated by the signs of ``seed`` (kernel pair) or of ``gen`` (torch.fft) first."""
     rows = _native_transform_rows(kind, mat)                  # (other than the rows of mat: the zero-extended pair, rows of seed in [0, rows))
     if not rows:
-        return _sketch(kind, mat, p, gen, scale=scale)
+        return _sketch(kind, mat, p, gen, scale=scale, signed=_SIGN_FLIPS)
     if kind == 'dct':
-        return _native_project(kind, mat, p, seed, scale, rows)
-    planes = _native_project(kind, mat, p, seed, scale, rows, torch.float32)
+        return _native_project(kind, mat, p, seed, scale, rows, signed=_SIGN_FLIPS)
+    planes = _native_project(kind, mat, p, seed, scale, rows, torch.float32, signed=_SIGN_FLIPS)
     return torch.complex(planes[0], planes[1])
 
 
-def _sketch(kind: str, mat: torch.Tensor, p: int, gen: torch.Generator, sketch_dtype=None, draw_dtype=None, scale: float = 1.0) -> torch.Tensor:
-    """``scale * S @ mat`` (``E[S^T S] = p * I`` for the dense sketches, ``(p / rows) * I`` for the sampled transforms)."""
+def _sketch(kind: str, mat: torch.Tensor, p: int, gen: torch.Generator, sketch_dtype=None, draw_dtype=None, scale: float = 1.0,
+            signed: bool = False) -> torch.Tensor:
+    """``scale * S @ mat`` (``E[S^T S] = p * I`` for the dense sketches, ``(p / rows) * I`` for the sampled transforms).  ``signed``: the
+    sampled transforms of ``D mat``, ``D = diag(+-1)`` drawn from ``gen`` BEFORE the rows (a replay draws in the same order)."""
     rows = mat.shape[0]
     if kind in ('gaussian', 'rademacher'):
         if sketch_dtype is not None and sketch_dtype != mat.dtype:
@@ -395,6 +442,8 @@ def _sketch(kind: str, mat: torch.Tensor, p: int, gen: torch.Generator, sketch_d
         else:
             out = _dense_sketch(kind, p, rows, mat, gen, draw_dtype) @ mat
         return out if scale == 1.0 else out * scale
+    if signed:
+        mat = _flipped_rows(mat, gen)
     idx = _sampled_rows(p, rows, mat, gen)
     if kind == 'dct':
         out = dct(mat, dim=0, norm='ortho')[idx]
@@ -449,6 +498,7 @@ class _LinearGRP(torch.autograd.Function):
         # the scale is N' / p, and backward runs on the same N' and seed)
         dense = _native_sketch_applies(kind, flat, sketch_dtype)
         ctx.route = 0 if dense else _native_transform_rows(kind, flat) or None
+        ctx.signed = _SIGN_FLIPS and kind in ('dct', 'dft')                # (recorded: backward flips iff forward did, whatever the switch says then)
         if ctx.route is not None:
             # S -- or the sampled rows -- lives nowhere: a function of the seed that the kernel evaluates itself; the projection and the
             # seed are all that is kept (no randint launch, no RNG state to save and replay; while a graph is being captured the seed is
@@ -459,14 +509,14 @@ class _LinearGRP(torch.autograd.Function):
             ctx.low = sketch_dtype if dense and sketch_dtype is not None and sketch_dtype != flat.dtype else None
             x = flat.detach() if ctx.low is None else flat.detach().to(ctx.low)
             # (the sketch before or after the layer's own GEMM: no difference, profiles/r05_roberta_ab_order.txt)
-            kept = _native_project(kind, x, p, ctx.native_seed, (ctx.route or 1) / p, ctx.route)
+            kept = _native_project(kind, x, p, ctx.native_seed, (ctx.route or 1) / p, ctx.route, signed=ctx.signed)
             # ('dft': the real and imaginary planes in the layer's dtype, two views of one buffer)
             ctx.save_for_backward(*((kept[0], kept[1]) if kind == 'dft' else (kept, )), weight)
             return F.linear(input, weight, bias)
         token, gen = _capture_rng(generator, input.device)
         scale = 1.0 / p if kind in ('gaussian', 'rademacher') else rows / p
         draw_dtype = sketch_dtype or flat.dtype
-        sketch = _sketch(kind, flat.detach(), p, gen, sketch_dtype, draw_dtype, scale)
+        sketch = _sketch(kind, flat.detach(), p, gen, sketch_dtype, draw_dtype, scale, ctx.signed)
         ctx.save_for_backward(sketch, weight)
         ctx.token, ctx.sketch_dtype, ctx.draw_dtype = token, sketch_dtype, draw_dtype
         return F.linear(input, weight, bias)
@@ -490,13 +540,13 @@ class _LinearGRP(torch.autograd.Function):
             g2 = flat if flat.dtype in (torch.float32, torch.float16, torch.bfloat16) else flat.float()
             if ctx.low is not None:
                 g2 = g2.to(ctx.low)
-            proj = _native_project(ctx.kind, g2, ctx.p, ctx.native_seed, 1.0, ctx.route).to(sketch.dtype)
+            proj = _native_project(ctx.kind, g2, ctx.p, ctx.native_seed, 1.0, ctx.route, signed=ctx.signed).to(sketch.dtype)
             if len(saved) == 3:                         # Re((F G)^H (F X)) = Gr^T Xr + Gi^T Xi: two accumulating GEMMs in the dtype of the planes
                 grad_weight = torch.addmm(proj[0].T @ saved[0], proj[1].T, saved[1]).to(weight.dtype)
             else:
                 grad_weight = (proj.T @ sketch).to(weight.dtype)
         elif ctx.needs_input_grad[1]:
-            proj = _sketch(ctx.kind, flat, ctx.p, _replay_rng(ctx.token), ctx.sketch_dtype, ctx.draw_dtype)
+            proj = _sketch(ctx.kind, flat, ctx.p, _replay_rng(ctx.token), ctx.sketch_dtype, ctx.draw_dtype, signed=ctx.signed)
             if proj.is_complex():                                               # Re((F G)^H (F X))
                 grad_weight = (proj.real.T @ sketch.real + proj.imag.T @ sketch.imag).to(weight.dtype)
             else:

@@ -32,7 +32,9 @@ extern "C" {
  * So were the moments of the variance estimator (fewbit_hipx_moments_workspace, _row_moments, _sum_squares): inside revision 2, recognised
  * by the presence of the symbols.
  * So was the dropout whose mask is a function of a seed (fewbit_hipx_dropout_threshold, _dropout_keep, _dropout): inside revision 2,
- * recognised by the presence of the symbols. */
+ * recognised by the presence of the symbols.
+ * So were the sampled transforms with the signs of a seed (fewbit_hipx_sampled_signs, _sampled_dct_signed, _sampled_dft_signed): inside
+ * revision 2, recognised by the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -99,6 +101,41 @@ int fewbit_hipx_sampled_dft_zext(int dtype, const void *m, size_t rows, size_t v
 int fewbit_hipx_sampled_dft_zext_seeded(int dtype, const void *m, size_t rows, size_t valid_rows, size_t features, size_t ld, uint64_t seed,
                                         const uint64_t *seed_device, size_t proj, double scale, int out_dtype, void *out, void *workspace,
                                         size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The sampled transforms behind a random sign per row: the subsampled RANDOMIZED transform.
+ *     out = scale * transform_of_length_rows([D m; 0])[rows of the seed]          D = diag(+-1), valid_rows x valid_rows, of the same seed
+ *
+ * The signs of a seed.  The sign of matrix row r (the row of m in memory, before any reordering) is a pure function of (seed, r):
+ *     w[0..3] = Philox4x32-10(counter = (low 32 bits of r >> 7, high 32 bits of r >> 7, 0, 6), key = (low 32 bits of seed, high 32 bits of seed))
+ *               (fewbit_philox.h; counter word 3 = 6 is this domain's own: 0 and 2 are the dense sketches', 3 the sampled rows', 4 the CRS
+ *               columns', 5 the dropout's)
+ *     flip(r) = bit (r & 31) of w[(r >> 5) & 3]                  1: the row is negated
+ * The sampled rows stay fewbit_hip_sampled_rows(seed, rows, proj): one seed serves both.
+ *
+ * Why.  With R sampling p of `rows` rows uniformly and T the orthonormal transform, S = sqrt(rows / p) R T D has E[S^T S] = D T^H T D = I
+ * for EVERY D: the estimate (S G)^T (S X) stays unbiased.  Its variance, summed over entries, is
+ * (1 / p) [rows * sum_k |(T D G)_k|^2 |(T D X)_k|^2 - |G^T X|_F^2]: without D whatever many rows of X share (a mean activation, a repeated
+ * token) lands in a few rows of T X and the first term grows like `rows` times |G|^2 |X|^2; with D it stays within a small constant of it
+ * (at most 3 for a rank-one input under the real transform, 2 under the complex one), the level fewbit_amd.VarianceEstimator's var_rmm assumes.
+ *
+ * fewbit_hipx_sampled_signs: flip(first + i) for i < count as bytes of 0 / 1 at a HOST pointer; no device is touched; any `first`.
+ * fewbit_hipx_sampled_dct_signed / _dft_signed: the arguments, the refusals (with these names in the message) and the workspace of
+ *   fewbit_hipx_sampled_dct_zext_seeded / _dft_zext_seeded; valid_rows == rows is the plain case.  seed_device != NULL: the seed word is read
+ *   when the kernel runs, for the rows and the signs alike -- a launch recorded in a hipGraph draws fresh rows AND fresh signs on every
+ *   replay.  Seeded only: there is no form with an array of row numbers.
+ * The result is bit for bit that of the _zext_seeded entry point on a copy of m whose flipped rows are negated (negation is exact in all
+ * three dtypes): pass A XORs the sign bits into the 16-byte pieces it has just loaded, before they are widened to fp32 (fewbit_fft4.h:
+ * pass_a_zext_kernel with the signs of the seed; fewbit_amd/csrc/fewbit_signed.hip).  Rows that are not loaded, and the zeros a ragged last
+ * column tile is filled up with, stay +0.  Pass B, the workspace layout and the LDS note of the plain pair are unchanged; the first signed
+ * call of a dtype on a device reserves the LDS of its kernels (one eager call per dtype and device before a hipGraph capture). */
+int fewbit_hipx_sampled_signs(uint64_t seed, uint64_t first, size_t count, uint8_t *flip_host);
+int fewbit_hipx_sampled_dct_signed(int dtype, const void *m, size_t rows, size_t valid_rows, size_t features, size_t ld, uint64_t seed,
+                                   const uint64_t *seed_device, size_t proj, double scale, void *out, void *workspace, size_t workspace_bytes,
+                                   void *stream);
+int fewbit_hipx_sampled_dft_signed(int dtype, const void *m, size_t rows, size_t valid_rows, size_t features, size_t ld, uint64_t seed,
+                                   const uint64_t *seed_device, size_t proj, double scale, int out_dtype, void *out, void *workspace,
+                                   size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Column sampling of the weight gradient (LinearCRS; the reference's linear_crs, fewbit/functional/linear.py:27-43): `nopairs`

@@ -47,6 +47,11 @@ ROWS = [
     ('dropout_bench.json', "tools/dropout_bench.py: fewbit.functional.dropout / dropout_add forward + backward against torch's dropout at 16384 x 768 / 3072, bf16 and fp32; bytes saved for backward; the kernel alone against its byte floor", f'{E} 8.11'),
     ('dropout_kernel_times.txt', 'rocprofv3 --kernel-trace over tools/dropout_bench.py: per-dispatch durations of the dropout kernel and of torch\'s forward / backward dropout kernels, per shape', f'{E} 8.11'),
     ('roberta_dropout_bf16.json', 'tools/roberta_bench.py --dtype bf16 --dropout fewbit: RoBERTa-base b128 x s128 with every nn.Dropout swapped, alone and with the GELU swap', f'{E} 8.11'),
+    ('signed_transform_bench.json', 'tools/signed_transform_bench.py: the sampled DCT / DFT with the signs of the seed against the unsigned _zext_seeded calls at 16384 x 768 / 3072, p = 3276, bf16 and fp32: HIP events per call and rocprofv3 per pass', f'{E} 8.15'),
+    ('signed_transform_kernel_stats.csv', 'rocprofv3 --kernel-trace --stats over tools/signed_transform_bench.py --trace: every kernel of the signed and unsigned calls', f'{E} 8.15'),
+    ('roberta_signed_dct_*.json', 'tools/roberta_bench.py --table --matmul dct, use_sign_flips off and on: RoBERTa-base b128 x s128 step time and peak memory, bf16 and fp32', f'{E} 8.15'),
+    ('convergence_demo_signed_*.txt', "tools/convergence_demo.py with the signed-DCT arm: bf16 at the usual step size and at SGD lr 1.0, where the unsigned DCT arm diverges", f'{D} 7.4'),
+    ('signed_transform_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1915 device functions before / after the signed pass A was added (228 new)', f'{E} 8.15'),
     ('moments_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1890 device functions before / after fewbit_moments.hip was added (13 new)', f'{E} 8.9'),
     ('r06_dct_stagger.txt|r06_dct_fused_upper_bound.txt|r06_dct_inter16.txt', 'DCT experiments not kept: staggered starts, both passes in one launch (timing only), a bf16 intermediate', 'EXPERIMENTS.md'),
     ('r0?_roberta_table_*.json', "tools/roberta_bench.py --table: the reference README's RoBERTa table per dtype and estimator", f'{D} 7.4'),

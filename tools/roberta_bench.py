@@ -14,6 +14,8 @@ Two routes to the same kernels:
   --dropout fewbit          every `nn.Dropout` of the model is swapped for `fewbit.Dropout` (the mask of a seed: nothing saved for backward) in
                             the fewbit / op variants and in every non-vanilla row of --table; the line gains a `dropout` entry: the vanilla
                             model with ONLY the dropouts swapped, its peak memory and step time against the vanilla model.
+  --sign-flips              `fewbit_amd.linear.use_sign_flips(True)`: with --table --matmul dct / dft the randomized layers negate a random half of
+                            the rows in front of the transform (S = sqrt(N / p) R T D; the signs of the call's seed, evaluated in pass A)
 Prints one JSON line.
 """
 import argparse
@@ -152,6 +154,7 @@ def main():
                     help='draw S with torch.randn / randint and multiply with torch.matmul (what round 3 measured) instead of the '
                          'gfx950 sketch kernels (fewbit_amd/csrc/fewbit_sketch.hip)')
     ap.add_argument('--dropout', default='torch', choices=('torch', 'fewbit'), help="'fewbit': swap every nn.Dropout for fewbit.Dropout (module docstring)")
+    ap.add_argument('--sign-flips', action='store_true', help="random row signs in front of the 'dct' / 'dft' sketches (fewbit_amd.linear.use_sign_flips)")
     args = ap.parse_args()
     dtype = {'fp32': torch.float32, 'bf16': torch.bfloat16}[args.dtype]
     dev = torch.device('cuda:0')
@@ -162,6 +165,7 @@ def main():
     import fewbit_amd.linear
     if args.torch_sketch:
         fewbit_amd.linear.use_native_sketch(False)
+    fewbit_amd.linear.use_sign_flips(args.sign_flips)
     if args.table:
         rows = []
         for i, (gelu, linear) in enumerate(((False, False), (True, False), (False, True), (True, True))):
