@@ -60,7 +60,7 @@
 
 // Units 0 .. 2 (and the single-unit build) are libfewbit_hip.so's.  Units 3 .. 5 (-DFEWBIT_DCT_TU=3 / 4 / 5 = FEWBIT_F32 / F16 / BF16 + 3) are
 // the companion library's: the zero-extended DCT (fewbit_hipx_sampled_dct_zext, include/fewbit_hipx.h) -- pass A is fewbit_fft4.h's
-// pass_a_zext_kernel in Makhoul's order, pass B is this file's, compiled a second time under a name of its own.
+// pass_a_zext_kernel in Makhoul's order, pass B is the DCT's, compiled a second time under a name of its own (CosineRows<CompanionLibrary>).
 #ifndef FEWBIT_DCT_TU
 #define FEWBIT_DCT_TU -1
 #endif
@@ -77,176 +77,8 @@ FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(pri
 
 namespace dct {
 
-// (tiles, small transforms, row loads, tables, the rows of a seed and their sort, split_rows, the host side: fewbit_fft4.h)
-
-// ---- pass A -----------------------------------------------------------------------------------------------------------------
-// grid (N2, column tiles): workgroup (b, t) transforms the rows n = N2 n1 + b of column tile t.  inter: [half tile][k1][n2][16] complex fp32.
-template <int DT, int N1, int N2, typename ROWS>
-__global__ __launch_bounds__(kThreadsA, (N1 > 128 ? 2 : 4)) void dct_pass_a_kernel(const void *__restrict__ x, size_t features, size_t ld, f32x2 *__restrict__ inter, ROWS rows,
-                                                                  size_t proj, int *__restrict__ offsets, Sample *__restrict__ sorted) {
-    constexpr int N = N1 * N2, kCoarse = coarse_entries(N), kThreads = kThreadsA, kSlots = kThreads / C;
-    static_assert(kRowsA == 1, "one n2 per workgroup");
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-    f32x2 *tile = reinterpret_cast<f32x2 *>(lds_raw);                 // [N1][C]
-    f32x2 *tw = tile + N1 * C;                                        // W_N1^m, m < N1
-    f32x2 *fine = tw + N1, *coarse = fine + kFine;                    // W_N^m (m < 128), W_N^{128 m}
-    const int tid = threadIdx.x, c = tid % C, slot = tid / C;
-    const int b = blockIdx.x;
-    const size_t t = blockIdx.y, f0 = t * kFeatures;
-    // one workgroup of the launch sorts the sampled rows for pass B first (~2 us of its own time; the launch takes 16)
-    if (blockIdx.x == 0 && blockIdx.y == 0) sort_rows<N1, N, ROWS>(rows, proj, offsets, sorted, reinterpret_cast<int *>(lds_raw), tid);
-
-    // ---- loads first (all in flight), tables while they travel, then registers -> LDS
-    constexpr int PF = In<DT>::kPieceFeatures, PPS = In<DT>::kPiecesPerSegment, kTotal = N1 * PPS, kPieces = (kTotal + kThreads - 1) / kThreads;
-    // (one body per case, FULL tile or edge tile, each with its own registers from the loads to the LDS writes: were the two
-    // cases to meet in one set of registers in between, the copies at the join would wait for the loads right behind their issue)
-    auto fill_tile = [&](auto full) __attribute__((always_inline)) {
-        u32x4 raw[kPieces];
-#pragma unroll
-        for (int i = 0; i < kPieces; ++i) {
-            const int pid = tid + kThreads * i, n1 = pid / PPS, piece = pid % PPS;
-            if (kTotal % kThreads != 0 && pid >= kTotal) break;
-            const int n = N2 * n1 + b;                                  // index into the reordered sequence v
-            const size_t row = n < N / 2 ? 2 * static_cast<size_t>(n) : 2 * static_cast<size_t>(N - 1 - n) + 1;
-            raw[i] = load_piece<DT, decltype(full)::value>(x, row, ld, f0, piece, features);
-        }
-        for (int m = tid; m < N1; m += kThreads) tw[m] = unit(m, N1);
-        for (int m = tid; m < kFine; m += kThreads) fine[m] = unit(m, N);
-        for (int m = tid; m < kCoarse; m += kThreads) coarse[m] = unit(m * kFine, N);
-#pragma unroll
-        for (int i = 0; i < kPieces; ++i) {
-            const int pid = tid + kThreads * i, n1 = pid / PPS, piece = pid % PPS;
-            if (kTotal % kThreads != 0 && pid >= kTotal) break;
-            float v[PF];
-            unpack_piece<DT>(raw[i], v);
-            f32x4 *dst = reinterpret_cast<f32x4 *>(tile + n1 * C + piece * (PF / 2));
-#pragma unroll
-            for (int e = 0; e < PF / 4; ++e) dst[e] = f32x4{v[4 * e], v[4 * e + 1], v[4 * e + 2], v[4 * e + 3]};
-        }
-    };
-    if (f0 + kFeatures <= features) fill_tile(std::true_type{});       // (workgroup-uniform)
-    else fill_tile(std::false_type{});
-    __syncthreads();
-
-    fft_tile<N1, kRowsA, kSlots>(tile, tw, c, slot);
-
-    // ---- twiddle + store: unit = two complex columns (16 B) of one position P; 16 consecutive lanes = the 256 contiguous bytes of one k1
-    constexpr int kUnitsTotal = N1 * (C / 2), kUnits = (kUnitsTotal + kThreads - 1) / kThreads;
-#pragma unroll
-    for (int i = 0; i < kUnits; ++i) {
-        const int uid = tid + kThreads * i, c2 = uid % (C / 2), p = uid / (C / 2);
-        if (kUnitsTotal % kThreads != 0 && uid >= kUnitsTotal) break;
-        const int k1 = pos_to_freq<N1>(p), e = b * k1;
-        const f32x2 w = table_unit(fine, coarse, e, kCoarse > 1);
-        const f32x4 z = *reinterpret_cast<const f32x4 *>(tile + p * C + 2 * c2);
-        const f32x2 a = cmul(f32x2{z[0], z[1]}, w), bb = cmul(f32x2{z[2], z[3]}, w);
-        // (the intermediate is kept per HALF tile of 16 complex columns -- what one pass-B workgroup reads: 128 contiguous bytes here)
-        f32x4 *dst = reinterpret_cast<f32x4 *>(inter + (((2 * t + c2 / (CB / 2)) * N1 + k1) * N2 + b) * CB + 2 * (c2 % (CB / 2)));
-        *dst = f32x4{a.x, a.y, bb.x, bb.y};
-    }
-}
-
-// ---- pass B -----------------------------------------------------------------------------------------------------------------
-#if FEWBIT_DCT_TU >= 3
-inline namespace companion {                // (the companion library's copies: symbols of their own)
-#endif
-// grid (N1 / 2 + 1, half tiles of 16 complex columns): residues k1 = u and (N1 - u) % N1.  The LDS tile is [N2][2][16]: the two
-// residue rows sit side by side, so that a half-wave still touches 256 contiguous bytes per position and one butterfly serves
-// both rows -- to the transform it is one row of 32 columns.
-template <int DT, int N1, int N2>
-__global__ __launch_bounds__(kThreadsB, (N2 > 128 ? 2 : 4)) void dct_pass_b_kernel(const f32x2 *__restrict__ inter, const int *__restrict__ offsets, const Sample *__restrict__ sorted,
-                                                                  size_t proj, size_t features, float scale, void *__restrict__ out) {
-    constexpr int N = N1 * N2, kCoarse = coarse_entries(N), kThreads = kThreadsB, kSlots = kThreads / C;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-    f32x2 *tile = reinterpret_cast<f32x2 *>(lds_raw);                 // [N2][2][CB]
-    f32x2 *tw = tile + N2 * 2 * CB;                                   // W_N2^m
-    f32x2 *fine = tw + N2, *coarse = fine + kFine;                    // W_4N^m (m < 128), W_4N^{128 m}: e^{-i pi k / 2N} = W_4N^k
-    const int tid = threadIdx.x;
-    const int u = blockIdx.x, k1a = u, k1b = (N1 - u) % N1;
-    const size_t t = blockIdx.y, f0 = t * (2 * CB);
-    // four lanes write one sampled row, four complex columns each: 64 rows at a time -- all of a typical workgroup's in one step (with 16
-    // lanes per row the four dependent steps of sample -> tile -> table -> store cost 1.5 us of a 18.8 us launch, profiles/r06_dct_serve_lanes.txt)
-    constexpr int kLanes = kServeLanes, E = CB / kLanes, kSGroups = kThreads / kLanes;       // lanes per sample, complex columns per lane
-    const int lane = tid % kLanes, sgroup = tid / kLanes;
-
-    // this workgroup's samples (pass A's workgroup (0, 0) sorted them): the first two of every group of lanes are requested FIRST (vmcnt
-    // counts in order: looking at them after the transform does not wait for anything), unconditionally (a clamped index: hipcc gives a
-    // load under a lane-divergent guard its own wait)
-    const int begin = offsets[u], count = offsets[u + 1] - begin;      // (scalar loads)
-    constexpr int kPre = 2;
-    Sample pre[kPre];
-#pragma unroll
-    for (int i = 0; i < kPre; ++i) {
-        const size_t e = static_cast<size_t>(begin) + sgroup + i * kSGroups;
-        pre[i] = sorted[e < proj ? e : proj - 1];
-    }
-    constexpr int kPerRow = N2 * (CB / 2), kTotal = 2 * kPerRow, kPieces = (kTotal + kThreads - 1) / kThreads;     // 16-byte pieces (two complex)
-    f32x4 v[kPieces];
-#pragma unroll
-    for (int i = 0; i < kPieces; ++i) {
-        const int pid = tid + kThreads * i, r = pid / kPerRow, rest = pid % kPerRow;
-        if (kTotal % kThreads != 0 && pid >= kTotal) break;
-        const f32x2 *src = inter + (t * N1 + (r == 0 ? k1a : k1b)) * static_cast<size_t>(N2) * CB;
-        v[i] = reinterpret_cast<const f32x4 *>(src)[rest];
-    }
-    for (int m = tid; m < N2; m += kThreads) tw[m] = unit(m, N2);
-    for (int m = tid; m < kFine; m += kThreads) fine[m] = unit(m, 4 * N);
-    for (int m = tid; m < kCoarse; m += kThreads) coarse[m] = unit(m * kFine, 4 * N);
-#pragma unroll
-    for (int i = 0; i < kPieces; ++i) {
-        const int pid = tid + kThreads * i, r = pid / kPerRow, rest = pid % kPerRow, n2 = rest / (CB / 2), c2 = rest % (CB / 2);
-        if (kTotal % kThreads != 0 && pid >= kTotal) break;
-        *reinterpret_cast<f32x4 *>(tile + (n2 * 2 + r) * CB + 2 * c2) = v[i];
-    }
-    __syncthreads();
-    fft_tile<N2, 1, kSlots>(tile, tw, tid % C, tid / C);               // (ends with a barrier)
-
-    // ---- the sampled rows of this workgroup's two residue classes: one per group of kServeLanes lanes at a time, lanes along the columns
-    const float base = scale * __builtin_sqrtf(0.5f / static_cast<float>(N));          // ortho: sqrt(1 / 2N) (k > 0), sqrt(1 / 4N) (k = 0)
-    auto write_row = [&](int km, size_t j) __attribute__((always_inline)) {
-        const int k1 = km % N1, k2 = km / N1;
-        const int r = k1 == k1a ? 0 : 1;
-        const int k2m = k1 == 0 ? (N2 - k2) % N2 : N2 - 1 - k2;         // N - k = (N1 - k1) + N1 k2m
-        const f32x2 *pk = tile + (freq_to_pos<N2>(k2) * 2 + r) * CB + E * lane;
-        const f32x2 *pm = tile + (freq_to_pos<N2>(k2m) * 2 + (1 - r)) * CB + E * lane;
-        f32x2 zk[E], zm[E];
-        if constexpr (E >= 2) {
-#pragma unroll
-            for (int e = 0; e < E; e += 2) {
-                const f32x4 a4 = *reinterpret_cast<const f32x4 *>(pk + e), b4 = *reinterpret_cast<const f32x4 *>(pm + e);
-                zk[e] = f32x2{a4[0], a4[1]}; zk[e + 1] = f32x2{a4[2], a4[3]};
-                zm[e] = f32x2{b4[0], b4[1]}; zm[e + 1] = f32x2{b4[2], b4[3]};
-            }
-        } else {
-            zk[0] = pk[0]; zm[0] = pm[0];
-        }
-        const f32x2 w = table_unit(fine, coarse, km, kCoarse > 1);      // e^{-i pi k / 2N}
-        const float f = (km == 0 ? kR2 : 1.0f) * 2.0f * base;
-        float y[2 * E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            f32x2 m = zm[e];
-            m.y = -m.y;                                                 // conj Z[N - k]
-            const f32x2 va = (zk[e] + m) * 0.5f, d = (zk[e] - m) * 0.5f, vb = mul_mi(d);
-            y[2 * e] = (w.x * va.x - w.y * va.y) * f;                   // Re(w V)
-            y[2 * e + 1] = (w.x * vb.x - w.y * vb.y) * f;
-        }
-        const size_t fa = f0 + 2 * E * lane;
-        store_values<DT, E>(out, j * features + fa, y, fa, features);
-    };
-#pragma unroll
-    for (int i = 0; i < kPre; ++i)
-        if (sgroup + i * kSGroups < count) write_row(pre[i].k, static_cast<size_t>(pre[i].j));
-    // (more than 128 samples in these two classes: p beyond ~8000, or a skewed idx)
-    for (int e = sgroup + kPre * kSGroups; e < count; e += kSGroups) {
-        const Sample smp = sorted[static_cast<size_t>(begin) + e];
-        write_row(smp.k, static_cast<size_t>(smp.j));
-    }
-}
-
-#if FEWBIT_DCT_TU >= 3
-}  // namespace companion
-#endif
+// (tiles, small transforms, row loads, tables, the rows of a seed and their sort, both passes -- pass_a_kernel / pass_a_zext_kernel in
+// Makhoul's order, pass_b_kernel with the epilogue CosineRows --, split_rows, the host side: fewbit_fft4.h)
 
 // ---- host side (fewbit_fft4.h: the checks, the dispatch and the LDS opt-in of both pairs) ------------------------------------------
 #if FEWBIT_DCT_TU < 3
@@ -254,11 +86,9 @@ struct Dct {
     static constexpr const char *kName = "sampled_dct", *kWorkspace = "fewbit_hip_sampled_dct_workspace";
     static constexpr int (*fail)(int, const char *, ...) = fewbit_hip::fail;
     static constexpr bool kSeededLast = true, kZext = false;
+    using Order = RowsMakhoul;
+    using Epilogue = CosineRows<CoreLibrary>;
     using PassB = Dct;
-    template <int DT, int N1, int N2, typename ROWS> static constexpr auto pass_a() { return &dct_pass_a_kernel<DT, N1, N2, ROWS>; }
-    template <int DT, int N1, int N2> static constexpr auto pass_b() { return &dct_pass_b_kernel<DT, N1, N2>; }
-    template <int N1, int N2> static constexpr size_t lds_b() { return lds_bytes_b<N2>(N1 * N2); }
-    static float factor(double scale, size_t) { return static_cast<float>(scale); }
 };
 
 // The file is compiled as three translation units in parallel, one per dtype (-DFEWBIT_DCT_TU=0 / 1 / 2 = FEWBIT_F32 / F16 / BF16: 114
@@ -281,12 +111,9 @@ struct DctZext {
     static constexpr const char *kName = "sampled_dct_zext", *kWorkspace = "fewbit_hipx_sampled_dft_workspace";
     static constexpr int (*fail)(int, const char *, ...) = dft::fail;
     static constexpr bool kSeededLast = false, kZext = true;
+    using Order = RowsMakhoul;
+    using Epilogue = CosineRows<CompanionLibrary>;
     using PassB = DctZext;
-    template <int DT, int N1, int N2, typename ROWS> static constexpr auto pass_a() { return &pass_a_zext_kernel<RowsMakhoul, DT, N1, N2, ROWS>; }
-    template <int DT, int N1, int N2> static constexpr auto pass_b() { return &dct_pass_b_kernel<DT, N1, N2>; }
-    template <int N1, int N2> static constexpr size_t lds_b() { return lds_bytes_b<N2>(N1 * N2); }
-    template <int DT> static int opt_in_b() { return opt_in_pass_b<DctZext, DT>(); }
-    static float factor(double scale, size_t) { return static_cast<float>(scale); }
 };
 
 // three units, one per dtype: 76 pass A and 38 pass B kernels each; the C entry points with unit 3

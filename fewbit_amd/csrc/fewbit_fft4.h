@@ -1,13 +1,15 @@
 // fewbit_fft4.h -- the four-step fp32 FFT of the sampled transforms, shared by fewbit_dct.hip (sampled DCT-II) and fewbit_dft.hip
 // (sampled DFT): tile constants, the small transforms in registers, the in-place LDS stages and their digit maps, the 16-byte row
 // loads, the twiddle tables, the rows of a seed (RowsInMemory / RowsOfSeed) and their sort by residue class (sort_rows), the row
-// split N = N1 x N2 (split_rows, FB_FFT4_SPLITS), the workspace formula and the host side of a call (run: checks, LDS opt-in,
-// dispatch).  The algorithm and the tiling are described in fewbit_dct.hip's header; the two files differ only in how pass A orders
-// the rows it loads and in pass B's epilogue.
+// split N = N1 x N2 (split_rows, FB_FFT4_SPLITS), the kernels of both passes (pass_a_kernel, pass_a_zext_kernel, pass_b_kernel), the
+// workspace formula and the host side of a call (run: checks, LDS opt-in, dispatch).  The algorithm and the tiling are described in
+// fewbit_dct.hip's header; the two transforms differ only in how pass A orders the rows it loads (RowsMakhoul / RowsInOrder) and in pass
+// B's epilogue (CosineRows / FourierPlanes).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstdint>
 #include <type_traits>
 
@@ -431,24 +433,100 @@ __device__ __forceinline__ void sort_rows(ROWS rows, size_t proj, int *__restric
     __syncthreads();                                                   // (the tile takes this LDS over)
 }
 
-// ---- pass A of a zero-extended call ---------------------------------------------------------------------------------------------
-// The matrix has valid_rows <= N rows in memory and counts as N rows, the missing ones zero.  ORDER says which row of it the point n of
-// the transformed sequence is: the DFT's is row n, the DCT's Makhoul's reordering (fewbit_dct.hip, step 1).
+// ---- pass A -----------------------------------------------------------------------------------------------------------------
+// ORDER says which row of the matrix the point n of the transformed sequence is: the DFT's is row n, the DCT's Makhoul's reordering
+// (fewbit_dct.hip, step 1).  kReordered is what pass_a_kernel reads, row<N>(n) what pass_a_zext_kernel calls: the same map twice.
 struct RowsInOrder {
+    static constexpr bool kReordered = false;
     template <int N> static __device__ __forceinline__ size_t row(int n) { return static_cast<size_t>(n); }
 };
 struct RowsMakhoul {
+    static constexpr bool kReordered = true;
     template <int N> static __device__ __forceinline__ size_t row(int n) { return n < N / 2 ? 2 * static_cast<size_t>(n) : 2 * static_cast<size_t>(N - 1 - n) + 1; }
 };
-// dct_pass_a_kernel / dft_pass_a_kernel (fewbit_dct.hip, fewbit_dft.hip: the algorithm, the tile, the intermediate) with ONE difference: a
-// 16-byte piece whose row is >= valid_rows is zeros in registers and no memory request is made for it, so nothing at or beyond row
-// valid_rows of x is read and the pass moves valid_rows / N of the bytes.  Everything after the tile is filled is the same arithmetic on
-// the same values as the plain kernel's on a zero-filled copy: the same bits.  One template for both orders (the plain kernels are two
-// copies to keep the machine code they were measured as; these are new).
-// WHICH COPY LEADS.  Pass A now exists three times: dct_pass_a_kernel, dft_pass_a_kernel and this one.  The plain kernels are the
-// authoritative text: a change to pass A is made there first and then repeated here line by line (the bit-equality test of
-// tests/test_gpu_transform_zext.py fails when this copy is left behind).  Once a change of the plain kernels' machine code is acceptable,
-// both can be pass_a_zext_kernel<ORDER> with valid_rows = N and the three become one.
+// grid (N2, column tiles): workgroup (b, t) transforms the rows n = N2 n1 + b of column tile t.  inter: [half tile][k1][n2][16] complex fp32.
+// (One text for both transforms as a KERNEL template, not as an inlined function that two kernels call: a shared __forceinline__ body
+// gave 34 of the 152 bf16 kernels another machine code -- other instructions from N1 = 256 on -- while this template, with the row
+// spelled here under ORDER::kReordered and not taken through ORDER::row<N>, which reorders the DCT's 16-bit N1 = 16 kernels, compiles to the
+// instructions the two former kernels had: EXPERIMENTS 8.16.)
+template <typename ORDER, int DT, int N1, int N2, typename ROWS>
+__global__ __launch_bounds__(kThreadsA, (N1 > 128 ? 2 : 4)) void pass_a_kernel(const void *__restrict__ x, size_t features, size_t ld, f32x2 *__restrict__ inter, ROWS rows,
+                                                              size_t proj, int *__restrict__ offsets, Sample *__restrict__ sorted) {
+    constexpr int N = N1 * N2, kCoarse = coarse_entries(N), kThreads = kThreadsA, kSlots = kThreads / C;
+    static_assert(kRowsA == 1, "one n2 per workgroup");
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    f32x2 *tile = reinterpret_cast<f32x2 *>(lds_raw);                 // [N1][C]
+    f32x2 *tw = tile + N1 * C;                                        // W_N1^m, m < N1
+    f32x2 *fine = tw + N1, *coarse = fine + kFine;                    // W_N^m (m < 128), W_N^{128 m}
+    const int tid = threadIdx.x, c = tid % C, slot = tid / C;
+    const int b = blockIdx.x;
+    const size_t t = blockIdx.y, f0 = t * kFeatures;
+    // one workgroup of the launch sorts the sampled rows for pass B first (~2 us of its own time; the launch takes 16)
+    if (blockIdx.x == 0 && blockIdx.y == 0) sort_rows<N1, N, ROWS>(rows, proj, offsets, sorted, reinterpret_cast<int *>(lds_raw), tid);
+
+    // ---- loads first (all in flight), tables while they travel, then registers -> LDS
+    constexpr int PF = In<DT>::kPieceFeatures, PPS = In<DT>::kPiecesPerSegment, kTotal = N1 * PPS, kPieces = (kTotal + kThreads - 1) / kThreads;
+    // (one body per case, FULL tile or edge tile, each with its own registers from the loads to the LDS writes: were the two
+    // cases to meet in one set of registers in between, the copies at the join would wait for the loads right behind their issue)
+    auto fill_tile = [&](auto full) __attribute__((always_inline)) {
+        u32x4 raw[kPieces];
+#pragma unroll
+        for (int i = 0; i < kPieces; ++i) {
+            const int pid = tid + kThreads * i, n1 = pid / PPS, piece = pid % PPS;
+            if (kTotal % kThreads != 0 && pid >= kTotal) break;
+            const int n = N2 * n1 + b;                                  // index into the transformed sequence (the DCT's: the reordered v)
+            const size_t row = ORDER::kReordered ? (n < N / 2 ? 2 * static_cast<size_t>(n) : 2 * static_cast<size_t>(N - 1 - n) + 1) : static_cast<size_t>(n);
+            raw[i] = load_piece<DT, decltype(full)::value>(x, row, ld, f0, piece, features);
+        }
+        for (int m = tid; m < N1; m += kThreads) tw[m] = unit(m, N1);
+        for (int m = tid; m < kFine; m += kThreads) fine[m] = unit(m, N);
+        for (int m = tid; m < kCoarse; m += kThreads) coarse[m] = unit(m * kFine, N);
+#pragma unroll
+        for (int i = 0; i < kPieces; ++i) {
+            const int pid = tid + kThreads * i, n1 = pid / PPS, piece = pid % PPS;
+            if (kTotal % kThreads != 0 && pid >= kTotal) break;
+            float v[PF];
+            unpack_piece<DT>(raw[i], v);
+            f32x4 *dst = reinterpret_cast<f32x4 *>(tile + n1 * C + piece * (PF / 2));
+#pragma unroll
+            for (int e = 0; e < PF / 4; ++e) dst[e] = f32x4{v[4 * e], v[4 * e + 1], v[4 * e + 2], v[4 * e + 3]};
+        }
+    };
+    if (f0 + kFeatures <= features) fill_tile(std::true_type{});       // (workgroup-uniform)
+    else fill_tile(std::false_type{});
+    __syncthreads();
+
+    fft_tile<N1, kRowsA, kSlots>(tile, tw, c, slot);
+
+    // ---- twiddle + store: unit = two complex columns (16 B) of one position P; 16 consecutive lanes = the 256 contiguous bytes of one k1
+    constexpr int kUnitsTotal = N1 * (C / 2), kUnits = (kUnitsTotal + kThreads - 1) / kThreads;
+#pragma unroll
+    for (int i = 0; i < kUnits; ++i) {
+        const int uid = tid + kThreads * i, c2 = uid % (C / 2), p = uid / (C / 2);
+        if (kUnitsTotal % kThreads != 0 && uid >= kUnitsTotal) break;
+        const int k1 = pos_to_freq<N1>(p), e = b * k1;
+        const f32x2 w = table_unit(fine, coarse, e, kCoarse > 1);
+        const f32x4 z = *reinterpret_cast<const f32x4 *>(tile + p * C + 2 * c2);
+        const f32x2 a = cmul(f32x2{z[0], z[1]}, w), bb = cmul(f32x2{z[2], z[3]}, w);
+        // (the intermediate is kept per HALF tile of 16 complex columns -- what one pass-B workgroup reads: 128 contiguous bytes here)
+        f32x4 *dst = reinterpret_cast<f32x4 *>(inter + (((2 * t + c2 / (CB / 2)) * N1 + k1) * N2 + b) * CB + 2 * (c2 % (CB / 2)));
+        *dst = f32x4{a.x, a.y, bb.x, bb.y};
+    }
+}
+
+// ---- pass A of a zero-extended call ---------------------------------------------------------------------------------------------
+// The matrix has valid_rows <= N rows in memory and counts as N rows, the missing ones zero.
+// pass_a_kernel (the algorithm, the tile, the intermediate) with ONE difference: a 16-byte piece whose row is >= valid_rows is zeros in
+// registers and no memory request is made for it, so nothing at or beyond row valid_rows of x is read and the pass moves valid_rows / N
+// of the bytes.  Everything after the tile is filled is the same arithmetic on the same values as the plain kernel's on a zero-filled
+// copy: the same bits.
+// WHICH COPY LEADS.  Pass A exists twice: pass_a_kernel and this one.  The plain kernel is the authoritative text: a change to pass A is
+// made there first and then repeated here line by line (the bit-equality test of tests/test_gpu_transform_zext.py fails when this copy
+// is left behind).  Why the two are not one.  (1) Folded into pass_a_kernel through a span type as second kernel parameter, empty for
+// the plain kernels, this text changes the machine code of all 152 plain bf16 kernels (the instruction counts stay, the kernel-argument
+// offsets move) and of 90 of the 228 zero-extended and signed ones, and the project keeps measured kernels instruction for instruction
+// (EXPERIMENTS 8.16).  (2) Nor can the plain path become valid_rows = N of this kernel: it reaches the full tiles through a buffer
+// descriptor whose size is 32 bits (below), while the plain kernels, on 64-bit addresses, take matrices that span 4 GiB and more.
 // How a piece is left out.  A load under a lane-divergent `if (row < valid_rows)` makes hipcc wait for each load where the branches join
 // (the tile's loads then follow one another: seen in the assembly of this kernel written that way).  So the pieces of a full tile are
 // buffer loads through a descriptor of the valid_rows x ld elements of x: a piece of a missing row is given the offset kBeyondZext, which
@@ -570,6 +648,153 @@ __global__ __launch_bounds__(kThreadsA, (N1 > 128 ? 2 : 4)) void pass_a_zext_ker
     }
 }
 
+// ---- pass B -----------------------------------------------------------------------------------------------------------------
+// The epilogue EPI is what pass B does with Z[k] and Z[N - k] of a sampled k: kTables4N (it wants the tables of W_4N in LDS behind the
+// tile), factor (host: what the kernel is given as `scale`), prepare (what a thread computes once) and write (the values of one sampled
+// row that a lane holds, and their stores).
+// The cosine rows (fewbit_dct.hip, steps 1 and 2): out[j][:] in ODT.  LIBRARY is a tag and nothing else: the DCT's pass B is compiled
+// into both shared libraries, and the tag gives each its own kernel symbols.
+struct CoreLibrary;                         // libfewbit_hip.so
+struct CompanionLibrary;                    // libfewbit_hipx.so
+template <typename LIBRARY> struct CosineRows {
+    static constexpr bool kTables4N = true;                            // e^{-i pi k / 2N} = W_4N^k
+    static float factor(double scale, size_t) { return static_cast<float>(scale); }
+    float base;
+    template <int N> __device__ __forceinline__ void prepare(float scale, size_t, size_t) {
+        base = scale * __builtin_sqrtf(0.5f / static_cast<float>(N));                      // ortho: sqrt(1 / 2N) (k > 0), sqrt(1 / 4N) (k = 0)
+    }
+    template <int ODT, int E, int N>
+    __device__ __forceinline__ void write(const f32x2 (&zk)[E], const f32x2 (&zm)[E], int km, const f32x2 *fine, const f32x2 *coarse, void *out, size_t j,
+                                          size_t features, size_t fa) const {
+        const f32x2 w = table_unit(fine, coarse, km, coarse_entries(N) > 1);            // e^{-i pi k / 2N}
+        const float f = (km == 0 ? kR2 : 1.0f) * 2.0f * base;
+        float y[2 * E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            f32x2 m = zm[e];
+            m.y = -m.y;                                                 // conj Z[N - k]
+            const f32x2 va = (zk[e] + m) * 0.5f, d = (zk[e] - m) * 0.5f, vb = mul_mi(d);
+            y[2 * e] = (w.x * va.x - w.y * va.y) * f;                   // Re(w V)
+            y[2 * e + 1] = (w.x * vb.x - w.y * vb.y) * f;
+        }
+        store_values<ODT, E>(out, j * features + fa, y, fa, features);
+    }
+};
+// The Fourier planes (fewbit_dft.hip): out: [2][proj][features] in ODT (real plane, imaginary plane); no e^{-i pi k / 2N} twiddle, so no
+// W_4N tables, and no sqrt(2) at k = 0.
+struct FourierPlanes {
+    static constexpr bool kTables4N = false;
+    static float factor(double scale, size_t rows) { return static_cast<float>(scale / std::sqrt(static_cast<double>(rows))); }
+    float half;
+    size_t plane;
+    template <int N> __device__ __forceinline__ void prepare(float factor, size_t proj, size_t features) {
+        half = 0.5f * factor;
+        plane = proj * features;
+    }
+    template <int ODT, int E, int N>
+    __device__ __forceinline__ void write(const f32x2 (&zk)[E], const f32x2 (&zm)[E], int, const f32x2 *, const f32x2 *, void *out, size_t j, size_t features,
+                                          size_t fa) const {
+        // a = Z[k], b = Z[N - k]:  X_2c = (a + conj b) / 2,  X_2c+1 = (a - conj b) / 2i = ((a.y + b.y) + i (b.x - a.x)) / 2
+        float re[2 * E], im[2 * E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const f32x2 a = zk[e], b = zm[e];
+            re[2 * e] = (a.x + b.x) * half;
+            im[2 * e] = (a.y - b.y) * half;
+            re[2 * e + 1] = (a.y + b.y) * half;
+            im[2 * e + 1] = (b.x - a.x) * half;
+        }
+        const size_t at = j * features + fa;
+        store_values<ODT, E>(out, at, re, fa, features);
+        store_values<ODT, E>(out, plane + at, im, fa, features);
+    }
+};
+
+// grid (N1 / 2 + 1, half tiles of 16 complex columns): residues k1 = u and (N1 - u) % N1.  The LDS tile is [N2][2][16]: the two
+// residue rows sit side by side, so that a half-wave still touches 256 contiguous bytes per position and one butterfly serves
+// both rows -- to the transform it is one row of 32 columns.  scale: EPI::factor of the call.
+template <typename EPI, int ODT, int N1, int N2>
+__global__ __launch_bounds__(kThreadsB, (N2 > 128 ? 2 : 4)) void pass_b_kernel(const f32x2 *__restrict__ inter, const int *__restrict__ offsets, const Sample *__restrict__ sorted,
+                                                              size_t proj, size_t features, float scale, void *__restrict__ out) {
+    constexpr int N = N1 * N2, kCoarse = coarse_entries(N), kThreads = kThreadsB, kSlots = kThreads / C;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    f32x2 *tile = reinterpret_cast<f32x2 *>(lds_raw);                 // [N2][2][CB]
+    f32x2 *tw = tile + N2 * 2 * CB;                                   // W_N2^m
+    f32x2 *fine = tw + N2, *coarse = fine + kFine;                    // kTables4N: W_4N^m (m < 128), W_4N^{128 m}
+    const int tid = threadIdx.x;
+    const int u = blockIdx.x, k1a = u, k1b = (N1 - u) % N1;
+    const size_t t = blockIdx.y, f0 = t * (2 * CB);
+    // four lanes write one sampled row, four complex columns each: 64 rows at a time -- all of a typical workgroup's in one step (with 16
+    // lanes per row the four dependent steps of sample -> tile -> table -> store cost 1.5 us of a 18.8 us launch, profiles/r06_dct_serve_lanes.txt)
+    constexpr int kLanes = kServeLanes, E = CB / kLanes, kSGroups = kThreads / kLanes;       // lanes per sample, complex columns per lane
+    const int lane = tid % kLanes, sgroup = tid / kLanes;
+
+    // this workgroup's samples (pass A's workgroup (0, 0) sorted them): the first two of every group of lanes are requested FIRST (vmcnt
+    // counts in order: looking at them after the transform does not wait for anything), unconditionally (a clamped index: hipcc gives a
+    // load under a lane-divergent guard its own wait)
+    const int begin = offsets[u], count = offsets[u + 1] - begin;      // (scalar loads)
+    constexpr int kPre = 2;
+    Sample pre[kPre];
+#pragma unroll
+    for (int i = 0; i < kPre; ++i) {
+        const size_t e = static_cast<size_t>(begin) + sgroup + i * kSGroups;
+        pre[i] = sorted[e < proj ? e : proj - 1];
+    }
+    constexpr int kPerRow = N2 * (CB / 2), kTotal = 2 * kPerRow, kPieces = (kTotal + kThreads - 1) / kThreads;     // 16-byte pieces (two complex)
+    f32x4 v[kPieces];
+#pragma unroll
+    for (int i = 0; i < kPieces; ++i) {
+        const int pid = tid + kThreads * i, r = pid / kPerRow, rest = pid % kPerRow;
+        if (kTotal % kThreads != 0 && pid >= kTotal) break;
+        const f32x2 *src = inter + (t * N1 + (r == 0 ? k1a : k1b)) * static_cast<size_t>(N2) * CB;
+        v[i] = reinterpret_cast<const f32x4 *>(src)[rest];
+    }
+    for (int m = tid; m < N2; m += kThreads) tw[m] = unit(m, N2);
+    if constexpr (EPI::kTables4N) {
+        for (int m = tid; m < kFine; m += kThreads) fine[m] = unit(m, 4 * N);
+        for (int m = tid; m < kCoarse; m += kThreads) coarse[m] = unit(m * kFine, 4 * N);
+    }
+#pragma unroll
+    for (int i = 0; i < kPieces; ++i) {
+        const int pid = tid + kThreads * i, r = pid / kPerRow, rest = pid % kPerRow, n2 = rest / (CB / 2), c2 = rest % (CB / 2);
+        if (kTotal % kThreads != 0 && pid >= kTotal) break;
+        *reinterpret_cast<f32x4 *>(tile + (n2 * 2 + r) * CB + 2 * c2) = v[i];
+    }
+    __syncthreads();
+    fft_tile<N2, 1, kSlots>(tile, tw, tid % C, tid / C);               // (ends with a barrier)
+
+    // ---- the sampled rows of this workgroup's two residue classes: one per group of kServeLanes lanes at a time, lanes along the columns
+    EPI epilogue;
+    epilogue.template prepare<N>(scale, proj, features);
+    auto write_row = [&](int km, size_t j) __attribute__((always_inline)) {
+        const int k1 = km % N1, k2 = km / N1;
+        const int r = k1 == k1a ? 0 : 1;
+        const int k2m = k1 == 0 ? (N2 - k2) % N2 : N2 - 1 - k2;         // N - k = (N1 - k1) + N1 k2m
+        const f32x2 *pk = tile + (freq_to_pos<N2>(k2) * 2 + r) * CB + E * lane;
+        const f32x2 *pm = tile + (freq_to_pos<N2>(k2m) * 2 + (1 - r)) * CB + E * lane;
+        f32x2 zk[E], zm[E];
+        if constexpr (E >= 2) {
+#pragma unroll
+            for (int e = 0; e < E; e += 2) {
+                const f32x4 a4 = *reinterpret_cast<const f32x4 *>(pk + e), b4 = *reinterpret_cast<const f32x4 *>(pm + e);
+                zk[e] = f32x2{a4[0], a4[1]}; zk[e + 1] = f32x2{a4[2], a4[3]};
+                zm[e] = f32x2{b4[0], b4[1]}; zm[e + 1] = f32x2{b4[2], b4[3]};
+            }
+        } else {
+            zk[0] = pk[0]; zm[0] = pm[0];
+        }
+        epilogue.template write<ODT, E, N>(zk, zm, km, fine, coarse, out, j, features, f0 + 2 * E * lane);
+    };
+#pragma unroll
+    for (int i = 0; i < kPre; ++i)
+        if (sgroup + i * kSGroups < count) write_row(pre[i].k, static_cast<size_t>(pre[i].j));
+    // (more than 128 samples in these two classes: p beyond ~8000, or a skewed idx)
+    for (int e = sgroup + kPre * kSGroups; e < count; e += kSGroups) {
+        const Sample smp = sorted[static_cast<size_t>(begin) + e];
+        write_row(smp.k, static_cast<size_t>(smp.j));
+    }
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------------
 struct Split { int n1, n2; };
 // rows = N1 x N2.  2^8 .. 2^18: 16 <= N2 <= N1 <= 512, both powers of two (2^17 = 512 x 256 and 2^18 = 512 x 512: 128 KiB tiles, one
@@ -651,19 +876,27 @@ inline size_t inter_bytes(size_t rows, size_t features) { return tiles_of(featur
 inline size_t workspace_bytes_of(size_t rows, size_t features, size_t proj) { return inter_bytes(rows, features) + kOffsetsBytes + ((proj * sizeof(Sample) + 15) & ~static_cast<size_t>(15)); }
 
 template <int L> constexpr size_t lds_bytes_a(int n) { return (kRowsA * L * C + L + kFine + coarse_entries(n)) * sizeof(f32x2); }
-template <int L> constexpr size_t lds_bytes_b(int n) { return (2 * L * CB + L + kFine + coarse_entries(n)) * sizeof(f32x2); }
+template <typename EPI, int L> constexpr size_t lds_bytes_b(int n) { return (2 * L * CB + L + (EPI::kTables4N ? kFine + coarse_entries(n) : 0)) * sizeof(f32x2); }
 
 inline bool known_dtype(int dtype) { return dtype == FEWBIT_F32 || dtype == FEWBIT_F16 || dtype == FEWBIT_BF16; }
 inline RowsOfSeed rows_of_seed(uint64_t seed, const uint64_t *device) {
     return RowsOfSeed{sketch::key_of(seed), reinterpret_cast<const sketch::Key *>(device)};
 }
 
-// ---- the host side of both kernel pairs --------------------------------------------------------------------------------------
-// PAIR (fewbit_dct.hip: Dct, fewbit_dft.hip: Dft) holds what differs between them: its kernels (pass_a<DT, N1, N2, ROWS>() and
-// pass_b<ODT, N1, N2>()), pass B's LDS (lds_b<N1, N2>()), the factor pass B applies (factor(scale, rows)), the prefix of its messages
-// (kName), its workspace query (kWorkspace), its error reporter (fail: each library keeps its own last error), kSeededLast (below), and
-// what a zero-extended pair differs in: kZext (its pass A is a pass_a_zext_kernel and takes valid_rows) and PassB, the pair whose pass B
-// it runs (a plain pair: itself) -- whose opt_in_b<DT>() reserves the LDS of those kernels.
+// ---- the host side of the kernel pairs --------------------------------------------------------------------------------------
+// PAIR (fewbit_dct.hip: Dct, DctZext; fewbit_dft.hip: Dft, DftZext; fewbit_signed.hip: DctSigned, DftSigned) names what differs between
+// them: Order (the rows of pass A: RowsMakhoul / RowsInOrder), Epilogue (of pass B: CosineRows / FourierPlanes), kZext (its pass A is a
+// pass_a_zext_kernel and takes valid_rows), PassB (the pair whose pass B it runs -- a plain pair: itself -- and with it whose LDS opt-in
+// covers those kernels), kSeededLast (below), the prefix of its messages (kName), its workspace query (kWorkspace) and its error reporter
+// (fail: each library keeps its own last error); a pair with the signs of the seed also Unsigned, the zero-extended pair it extends.
+// The kernels, pass B's LDS and the factor pass B applies follow from those, here:
+template <typename PAIR, int DT, int N1, int N2, typename ROWS> constexpr auto pass_a_of() {
+    if constexpr (PAIR::kZext) return &pass_a_zext_kernel<typename PAIR::Order, DT, N1, N2, ROWS>;
+    else return &pass_a_kernel<typename PAIR::Order, DT, N1, N2, ROWS>;
+}
+template <typename PAIR, int ODT, int N1, int N2> constexpr auto pass_b_of() { return &pass_b_kernel<typename PAIR::Epilogue, ODT, N1, N2>; }
+template <typename PAIR, int N1, int N2> constexpr size_t lds_b_of() { return lds_bytes_b<typename PAIR::Epilogue, N2>(N1 * N2); }
+
 template <typename PAIR> int refuse_rows(const char *what, size_t rows) {
     return PAIR::fail(FEWBIT_ERR_UNSUPPORTED, "%s: rows = %zu is none of %s", what, rows, kRowFamilies);
 }
@@ -677,66 +910,70 @@ template <typename PAIR, typename K> int reserve_lds(K kern, size_t lds) {
     return FEWBIT_OK;
 }
 
-// The LDS opt-in of EVERY kernel of dtype DT whose tile exceeds 64 KiB (pass A reading DT, for both kinds of rows, and pass B writing
-// DT), once per device at the first call that uses DT -- not per instantiation at its own first launch: after one eager call of a
-// dtype, a hipGraph capture of any other row count of that dtype makes no attribute call.
-template <typename PAIR, int DT> int opt_in_dtype() {
-    static std::atomic<unsigned long long> done{0};
+// The LDS opt-ins below run once per device, at the first call that needs them -- not per instantiation at its own first launch: after
+// one eager call of a dtype, a hipGraph capture of any other row count of that dtype makes no attribute call.  `done` is the opt-in's
+// own set of devices; `reserve` is run until it has succeeded once on the current one.
+template <typename F> int once_per_device(std::atomic<unsigned long long> &done, F &&reserve) {
     int dev = 0;
     (void)hipGetDevice(&dev);
     const unsigned long long bit = 1ull << (dev & 63);
     if (done.load(std::memory_order_relaxed) & bit) return FEWBIT_OK;
-    int rc = FEWBIT_OK;
-    if constexpr (PAIR::kZext) rc = PAIR::PassB::template opt_in_b<DT>();      // (pass B is another pair's, or has an opt-in of its own)
-    // (the order in which a unit first names its kernels is their order in the device module, and the code generated for the last
-    // split depends on it: each pair names them in the order of its former host code -- the DCT's seeded pass A after all others)
-#define FB_FFT4_OPT_IN(A, B)                                                                                                  \
-    if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_a<DT, A, B, RowsInMemory>(), lds_bytes_a<A>(A * B));   \
-    if constexpr (!PAIR::kSeededLast) FB_FFT4_OPT_IN_SEEDED(A, B)                                                             \
-    if constexpr (!PAIR::kZext)                                                                                               \
-        if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_b<DT, A, B>(), PAIR::template lds_b<A, B>());
-#define FB_FFT4_OPT_IN_SEEDED(A, B) \
-    if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_a<DT, A, B, RowsOfSeed>(), lds_bytes_a<A>(A * B));
-    FB_FFT4_SPLITS(FB_FFT4_OPT_IN)
-    if constexpr (PAIR::kSeededLast) { FB_FFT4_SPLITS(FB_FFT4_OPT_IN_SEEDED) }
-#undef FB_FFT4_OPT_IN
-#undef FB_FFT4_OPT_IN_SEEDED
+    const int rc = reserve();
     if (rc == FEWBIT_OK) done.fetch_or(bit, std::memory_order_relaxed);
     return rc;
 }
+#define FB_FFT4_RESERVE_A(ROWS, A, B) if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(pass_a_of<PAIR, DT, A, B, ROWS>(), lds_bytes_a<A>(A * B));
+#define FB_FFT4_RESERVE_B(A, B) if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(pass_b_of<PAIR, DT, A, B>(), lds_b_of<PAIR, A, B>());
 
 // the LDS opt-in of every pass B of PAIR that writes DT alone: a pair whose pass A is zero-extended only (the DCT's in the companion library)
 template <typename PAIR, int DT> int opt_in_pass_b() {
     static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_relaxed) & bit) return FEWBIT_OK;
-    int rc = FEWBIT_OK;
-#define FB_FFT4_OPT_IN_B(A, B) \
-    if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_b<DT, A, B>(), PAIR::template lds_b<A, B>());
-    FB_FFT4_SPLITS(FB_FFT4_OPT_IN_B)
-#undef FB_FFT4_OPT_IN_B
-    if (rc == FEWBIT_OK) done.fetch_or(bit, std::memory_order_relaxed);
-    return rc;
+    return once_per_device(done, [] {
+        int rc = FEWBIT_OK;
+        FB_FFT4_SPLITS(FB_FFT4_RESERVE_B)
+        return rc;
+    });
 }
 
-// the LDS opt-in of a pair whose pass A takes the signs of the seed (fewbit_signed.hip): that of the zero-extended pair whose pass B it
-// runs (PAIR::opt_in_unsigned) and its own pass A reading DT -- once per device at the first signed call of DT, like opt_in_dtype
+// The LDS opt-in of EVERY kernel of dtype DT whose tile exceeds 64 KiB (pass A reading DT, for both kinds of rows, and pass B writing
+// DT).  Pass B of a zero-extended pair is another pair's, reserved by that pair's opt-in, or its own, by opt_in_pass_b.
+template <typename PAIR, int DT> int opt_in_dtype() {
+    static std::atomic<unsigned long long> done{0};
+    return once_per_device(done, [] {
+        int rc = FEWBIT_OK;
+        if constexpr (PAIR::kZext) {
+            if constexpr (std::is_same_v<typename PAIR::PassB, PAIR>) rc = opt_in_pass_b<PAIR, DT>();
+            else rc = opt_in_dtype<typename PAIR::PassB, DT>();
+        }
+        // (the order in which a unit first names its kernels is their order in the device module, and the code generated for the last
+        // split depends on it: each pair names them in the order of its former host code -- the DCT's seeded pass A after all others)
+#define FB_FFT4_OPT_IN(A, B)                                                  \
+    FB_FFT4_RESERVE_A(RowsInMemory, A, B)                                     \
+    if constexpr (!PAIR::kSeededLast) FB_FFT4_RESERVE_A(RowsOfSeed, A, B)     \
+    if constexpr (!PAIR::kZext) FB_FFT4_RESERVE_B(A, B)
+#define FB_FFT4_OPT_IN_SEEDED(A, B) FB_FFT4_RESERVE_A(RowsOfSeed, A, B)
+        FB_FFT4_SPLITS(FB_FFT4_OPT_IN)
+        if constexpr (PAIR::kSeededLast) { FB_FFT4_SPLITS(FB_FFT4_OPT_IN_SEEDED) }
+#undef FB_FFT4_OPT_IN
+#undef FB_FFT4_OPT_IN_SEEDED
+        return rc;
+    });
+}
+
+// the LDS opt-in of a pair whose pass A takes the signs of the seed (fewbit_signed.hip): that of the zero-extended pair it extends, whose
+// pass B it runs, and its own pass A reading DT -- at the first signed call of DT
 template <typename PAIR, int DT> int opt_in_signed() {
     static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_relaxed) & bit) return FEWBIT_OK;
-    int rc = PAIR::template opt_in_unsigned<DT>();
-#define FB_FFT4_OPT_IN_SIGNED(A, B) \
-    if (rc == FEWBIT_OK) rc = reserve_lds<PAIR>(PAIR::template pass_a<DT, A, B, SignedRowsOfSeed>(), lds_bytes_a<A>(A * B));
-    FB_FFT4_SPLITS(FB_FFT4_OPT_IN_SIGNED)
+    return once_per_device(done, [] {
+        int rc = opt_in_dtype<typename PAIR::Unsigned, DT>();
+#define FB_FFT4_OPT_IN_SIGNED(A, B) FB_FFT4_RESERVE_A(SignedRowsOfSeed, A, B)
+        FB_FFT4_SPLITS(FB_FFT4_OPT_IN_SIGNED)
 #undef FB_FFT4_OPT_IN_SIGNED
-    if (rc == FEWBIT_OK) done.fetch_or(bit, std::memory_order_relaxed);
-    return rc;
+        return rc;
+    });
 }
+#undef FB_FFT4_RESERVE_A
+#undef FB_FFT4_RESERVE_B
 
 // (valid_rows: the rows of m in memory, for a zero-extended pair; a plain pair's kernels do not take it)
 template <typename PAIR, int DT, typename ROWS>
@@ -746,11 +983,12 @@ int launch_a(Split sp, const void *m, size_t valid_rows, size_t features, size_t
     if (sp.n1 == A && sp.n2 == B) {                                                                                            \
         static_assert(lds_bytes_a<A>(A * B) >= 2 * (A / 2 + 2) * sizeof(int) && (A / 2 + 2) * sizeof(int) <= kOffsetsBytes,    \
                       "the sort's counters fit pass A's LDS and the offsets their slot");                                      \
-        constexpr auto kern = PAIR::template pass_a<DT, A, B, ROWS>();                                                         \
-        if constexpr (PAIR::kZext)                                                                                             \
-            hipLaunchKernelGGL(kern, dim3(B, tiles), dim3(kThreadsA), lds_bytes_a<A>(A * B), s, m, valid_rows, features, ld, inter, idx, proj, offsets, sorted); \
-        else                                                                                                                   \
-            hipLaunchKernelGGL(kern, dim3(B, tiles), dim3(kThreadsA), lds_bytes_a<A>(A * B), s, m, features, ld, inter, idx, proj, offsets, sorted); \
+        constexpr auto kern = pass_a_of<PAIR, DT, A, B, ROWS>();                                                               \
+        auto launch = [&](auto... held) {                                                                                      \
+            hipLaunchKernelGGL(kern, dim3(B, tiles), dim3(kThreadsA), lds_bytes_a<A>(A * B), s, m, held..., features, ld, inter, idx, proj, offsets, sorted); \
+        };                                                                                                                     \
+        if constexpr (PAIR::kZext) launch(valid_rows);                                                                         \
+        else launch();                                                                                                         \
         return FEWBIT_OK;                                                                                                      \
     }
     FB_FFT4_SPLITS(FB_FFT4_CASE_A)
@@ -763,8 +1001,8 @@ int launch_b(Split sp, const f32x2 *inter, const int *offsets, const Sample *sor
     const unsigned half_tiles = static_cast<unsigned>((features + 2 * CB - 1) / (2 * CB));
 #define FB_FFT4_CASE_B(A, B)                                                                                                   \
     if (sp.n1 == A && sp.n2 == B) {                                                                                            \
-        constexpr auto kern = PAIR::template pass_b<ODT, A, B>();                                                              \
-        hipLaunchKernelGGL(kern, dim3(A / 2 + 1, half_tiles), dim3(kThreadsB), (PAIR::template lds_b<A, B>()), s, inter, offsets, sorted, proj, features, factor, out); \
+        constexpr auto kern = pass_b_of<PAIR, ODT, A, B>();                                                                    \
+        hipLaunchKernelGGL(kern, dim3(A / 2 + 1, half_tiles), dim3(kThreadsB), (lds_b_of<PAIR, A, B>()), s, inter, offsets, sorted, proj, features, factor, out); \
         return FEWBIT_OK;                                                                                                      \
     }
     FB_FFT4_SPLITS(FB_FFT4_CASE_B)
@@ -835,7 +1073,7 @@ int run(int dtype, int out_dtype, const void *m, size_t rows, size_t valid_rows,
     Sample *sorted = reinterpret_cast<Sample *>(reinterpret_cast<uint8_t *>(offsets) + kOffsetsBytes);
     if (const int rc = with_dtype(dtype, [&](auto dt) { return launch_a<PAIR, decltype(dt)::value, ROWS>(sp, m, valid_rows, features, ld, idx, proj, inter, offsets, sorted, s); }))
         return rc;
-    const float factor = PAIR::factor(scale, rows);
+    const float factor = PAIR::Epilogue::factor(scale, rows);
     if (const int rc = with_dtype(out_dtype, [&](auto dt) { return launch_b<typename PAIR::PassB, decltype(dt)::value>(sp, inter, offsets, sorted, proj, features, factor, out, s); }))
         return rc;
     const hipError_t e = hipGetLastError();

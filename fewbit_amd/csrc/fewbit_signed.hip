@@ -12,7 +12,6 @@
 // each, both row orders; the C entry points with unit 0); without the define everything is one unit.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdint>
 #include <type_traits>
 
@@ -52,20 +51,20 @@ struct DctSigned {
     static constexpr const char *kName = "sampled_dct_signed", *kWorkspace = "fewbit_hipx_sampled_dft_workspace";
     static constexpr int (*fail)(int, const char *, ...) = dft::fail;
     static constexpr bool kSeededLast = false, kZext = true;
+    using Order = RowsMakhoul;
+    using Epilogue = CosineRows<CompanionLibrary>;
     using PassB = DctZext;
-    template <int DT> static int opt_in_unsigned() { return opt_in_dtype<DctZext, DT>(); }
-    template <int DT, int N1, int N2, typename ROWS> static constexpr auto pass_a() { return &pass_a_zext_kernel<RowsMakhoul, DT, N1, N2, ROWS>; }
-    static float factor(double scale, size_t) { return static_cast<float>(scale); }
+    using Unsigned = DctZext;
 };
 
 struct DftSigned {
     static constexpr const char *kName = "sampled_dft_signed", *kWorkspace = "fewbit_hipx_sampled_dft_workspace";
     static constexpr int (*fail)(int, const char *, ...) = dft::fail;
     static constexpr bool kSeededLast = false, kZext = true;
+    using Order = RowsInOrder;
+    using Epilogue = FourierPlanes;
     using PassB = Dft;
-    template <int DT> static int opt_in_unsigned() { return opt_in_dtype<DftZext, DT>(); }
-    template <int DT, int N1, int N2, typename ROWS> static constexpr auto pass_a() { return &pass_a_zext_kernel<RowsInOrder, DT, N1, N2, ROWS>; }
-    static float factor(double scale, size_t rows) { return static_cast<float>(scale / std::sqrt(static_cast<double>(rows))); }      // (Dft::factor)
+    using Unsigned = DftZext;
 };
 
 }  // namespace dft

@@ -89,7 +89,7 @@ int fewbit_hipx_sampled_dft_seeded(int dtype, const void *m, size_t rows, size_t
  * rows x valid_rows matrix that appends the zero rows, S = sqrt(rows / p) R C P has E[S^T S] = P^T C^T C P = P^T P = I, so (S G)^T (S X)
  * with the same R is an unbiased estimate of G^T X for matrices of valid_rows rows -- an estimator of the same kind as the layer's, but
  * NOT the reference's dct(X)[idx] at length valid_rows: another random variable with the same mean.
- * Pass A skips the missing rows (fewbit_amd/csrc/fewbit_fft4.h: pass_a_zext_kernel); pass B and the LDS note above are the plain pair's. */
+ * Pass A skips the missing rows (fewbit_amd/csrc/fewbit_fft4.h: pass_a_zext_kernel); pass B (pass_b_kernel) and the LDS note above are the plain pair's. */
 size_t fewbit_hipx_sampled_rows_ceil(size_t rows);
 int fewbit_hipx_sampled_dct_zext(int dtype, const void *m, size_t rows, size_t valid_rows, size_t features, size_t ld, const int64_t *idx, size_t proj,
                                  double scale, void *out, void *workspace, size_t workspace_bytes, void *stream);

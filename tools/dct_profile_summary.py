@@ -37,7 +37,7 @@ with open(find('trace', '*kernel_trace.csv'), newline='') as f:
             per[row['Kernel_Name']].append((int(row['Start_Timestamp']), int(row['End_Timestamp'])))
 es = 4 if run['dtype'] == 'f32' else 2
 inter = ((run['features'] + 63) // 64) * run['rows'] * 256
-alg = {'dct_pass_a_kernel': run['rows'] * run['features'] * es + inter, 'dct_pass_b_kernel': inter + run['proj'] * run['features'] * es}
+alg = {'pass_a_kernel': run['rows'] * run['features'] * es + inter, 'pass_b_kernel': inter + run['proj'] * run['features'] * es}
 total = 0.0
 print(f"{'kernel':<52} {'calls':>6} {'avg us':>9} {'min us':>9} {'max us':>9} {'bytes by design':>16} {'GB/s':>8} {'of 8 TB/s':>10}")
 for name, spans in sorted(per.items()):
@@ -69,5 +69,5 @@ if traffic:
     print('\n# HBM traffic per launch from the PMC passes (KiB counters; FETCH_SIZE x 2 on gfx950, as tools/summarize_profiles.py):')
     for k, d in sorted(traffic.items()):
         fetch, write = d.get('FETCH_SIZE', 0.0) * 2 * 1024, d.get('WRITE_SIZE', 0.0) * 1024
-        b = alg['dct_pass_a_kernel' if k == 'pass_a' else 'dct_pass_b_kernel']
+        b = alg['pass_a_kernel' if k == 'pass_a' else 'pass_b_kernel']
         print(f'  {k}: fetch {fetch / 1e6:.1f} MB + write {write / 1e6:.1f} MB = {(fetch + write) / 1e6:.1f} MB per launch = {(fetch + write) / b:.3f} x the bytes the design moves ({b / 1e6:.1f} MB)')

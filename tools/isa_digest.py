@@ -6,6 +6,10 @@ agree run the same instructions: how a source clean-up is shown to change no bit
 
     python3 tools/isa_digest.py [build dir] > digests.txt         # one line per kernel: <sha256[:16] in order> <sha256[:16] sorted> <instructions> <symbol>
     python3 tools/isa_digest.py --diff old.txt new.txt            # what differs (kernels added / removed / changed)
+    python3 tools/isa_digest.py --diff old.txt new.txt --rename 'regex=replacement' [--rename ...]
+                                                                  # the same after a source change that renames kernels: every symbol of BOTH files goes
+                                                                  # through re.sub(regex, replacement) of each --rename in turn (kernels are then "removed"
+                                                                  # and "added" only if the map misses them); two symbols of one file under one name: exit 2
     python3 tools/isa_digest.py --where old_build new_build       # WHERE each changed streaming kernel differs: only behind its tile loop, or in it
 
 --where is for a change that is meant to touch the element-wise tail of the streaming activation kernels (fewbit_kernels.hip) and nothing else.  The
@@ -112,22 +116,52 @@ def where(old: Path, new: Path) -> int:
     return 1 if count['LOOP CHANGED'] else 0
 
 
+def read_digests(path, renames):
+    """{symbol: [digest in order, digest sorted, instructions]} of a digest file, each symbol after every `regex=replacement` of `renames`
+    in turn (re.sub); two symbols of the file that end under one name are an error: one would hide the other from the comparison"""
+    out, source = {}, {}
+    for line in open(path):
+        if not line.strip() or line.startswith('#'):
+            continue
+        *fields, symbol = line.split(' ', 3)
+        symbol = name = symbol.strip()
+        for pattern, replacement in renames:
+            name = re.sub(pattern, replacement, name)
+        if name in out:
+            raise ValueError(f'{path}: {source[name]} and {symbol} are both named {name}')
+        out[name], source[name] = fields, symbol
+    return out
+
+
+def diff(old, new, renames=()) -> int:
+    try:
+        a, b = read_digests(old, renames), read_digests(new, renames)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    changed = [k for k in a if k in b and a[k][0] != b[k][0]]
+    reordered = [k for k in changed if a[k][1] == b[k][1]]
+    print(f'{len(a)} device functions before, {len(b)} after; removed {len(a.keys() - b.keys())}, added {len(b.keys() - a.keys())}, identical {len([k for k in a if k in b]) - len(changed)}, '
+          f'same instructions in another order {len(reordered)}, different instructions {len(changed) - len(reordered)}')
+    for k in sorted(a.keys() - b.keys()):
+        print('removed', k)
+    for k in sorted(b.keys() - a.keys()):
+        print('added  ', k)
+    for k in changed:
+        print('reordered' if k in reordered else 'CHANGED  ', a[k], '->', b[k], k)
+    return 1 if len(changed) > len(reordered) else 0
+
+
 def main():
     if len(sys.argv) > 3 and sys.argv[1] == '--where':
         return where(Path(sys.argv[2]), Path(sys.argv[3]))
     if len(sys.argv) > 1 and sys.argv[1] == '--diff':
-        a, b = ({l.split(' ', 3)[3].strip(): l.split(' ', 3)[:3] for l in open(f) if l.strip() and not l.startswith('#')} for f in sys.argv[2:4])
-        changed = [k for k in a if k in b and a[k][0] != b[k][0]]
-        reordered = [k for k in changed if a[k][1] == b[k][1]]
-        print(f'{len(a)} device functions before, {len(b)} after; removed {len(a.keys() - b.keys())}, added {len(b.keys() - a.keys())}, identical {len([k for k in a if k in b]) - len(changed)}, '
-              f'same instructions in another order {len(reordered)}, different instructions {len(changed) - len(reordered)}')
-        for k in sorted(a.keys() - b.keys()):
-            print('removed', k)
-        for k in sorted(b.keys() - a.keys()):
-            print('added  ', k)
-        for k in changed:
-            print('reordered' if k in reordered else 'CHANGED  ', a[k], '->', b[k], k)
-        return 1 if len(changed) > len(reordered) else 0
+        args, renames = sys.argv[2:], []
+        while '--rename' in args:
+            at = args.index('--rename')
+            renames.append(args[at + 1].split('=', 1))
+            del args[at:at + 2]
+        return diff(args[0], args[1], renames)
     build = Path(sys.argv[1]) if len(sys.argv) > 1 else ROOT / 'fewbit_amd' / 'csrc' / 'build' / 'gfx950'
     d = digests(build)
     print(f'# {len(d)} device functions in {build}')

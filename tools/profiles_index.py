@@ -51,6 +51,7 @@ ROWS = [
     ('signed_transform_kernel_stats.csv', 'rocprofv3 --kernel-trace --stats over tools/signed_transform_bench.py --trace: every kernel of the signed and unsigned calls', f'{E} 8.15'),
     ('roberta_signed_dct_*.json', 'tools/roberta_bench.py --table --matmul dct, use_sign_flips off and on: RoBERTa-base b128 x s128 step time and peak memory, bf16 and fp32', f'{E} 8.15'),
     ('convergence_demo_signed_*.txt', "tools/convergence_demo.py with the signed-DCT arm: bf16 at the usual step size and at SGD lr 1.0, where the unsigned DCT arm diverges", f'{D} 7.4'),
+    ('transform_one_text_isa_identity.txt', 'tools/isa_digest.py --diff --rename: machine code of all 2143 device functions before / after pass A and pass B of the plain pairs became one kernel template each (798 kernels renamed, none changed)', f'{E} 8.16'),
     ('signed_transform_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1915 device functions before / after the signed pass A was added (228 new)', f'{E} 8.15'),
     ('moments_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1890 device functions before / after fewbit_moments.hip was added (13 new)', f'{E} 8.9'),
     ('r06_dct_stagger.txt|r06_dct_fused_upper_bound.txt|r06_dct_inter16.txt', 'DCT experiments not kept: staggered starts, both passes in one launch (timing only), a bf16 intermediate', 'EXPERIMENTS.md'),

@@ -88,13 +88,13 @@ def merge(trace_dir: str, result: dict) -> dict:
     dt = {'fp32': 0, 'bf16': 2}
     for case in result['cases']:
         tiles, halves = (case['features'] + 63) // 64, (case['features'] + 31) // 32
-        order = 'RowsMakhoul' if case['kind'] == 'dct' else 'RowsInOrder'
+        order, epilogue = ('RowsMakhoul', 'CosineRows') if case['kind'] == 'dct' else ('RowsInOrder', 'FourierPlanes')
         kernels = {}
         for (name, y), spans in per.items():
             args = name[name.index('<') + 1:]
             if 'pass_a_zext_kernel' in name and order in name and y == tiles and args.split(',')[1].strip() == str(dt[case['dtype']]):
                 key = 'pass_a_signed_us' if 'SignedRowsOfSeed' in name else 'pass_a_unsigned_us'
-            elif f"{case['kind']}_pass_b_kernel" in name and y == halves and args.split(',')[0].strip() == str(dt[case['dtype']]):
+            elif 'pass_b_kernel' in name and epilogue in name and y == halves and args.split(',')[1].strip() == str(dt[case['dtype']]):
                 key = 'pass_b_us'                      # (one kernel for both arms: 2 x REPS dispatches)
             else:
                 continue
