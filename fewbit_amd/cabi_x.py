@@ -9,12 +9,13 @@ from typing import Optional, Tuple
 
 import torch
 
-from .cabi import DTYPES, FewbitHipError, _buffers, _matrix, _on, _planes_dtype, _row_numbers, _sampled_call, _seed_arguments, _span, _stream
+from .cabi import DTYPES, FewbitHipError, _buffers, _matrix, _on, _planes_dtype, _row_numbers, _same_device, _sampled_call, _seed_arguments, _span, _stream
 
 __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft', 'sampled_dft_seeded', 'sampled_dft_workspace_bytes', 'crs_columns',
            'crs_count', 'crs_workspace_bytes', 'crs_gather', 'crs_scatter', 'sampled_rows_ceil', 'sampled_dct_zext', 'sampled_dct_zext_seeded',
            'sampled_dft_zext', 'sampled_dft_zext_seeded', 'sampled_signs', 'sampled_dct_signed', 'sampled_dft_signed', 'moments_workspace_bytes', 'row_moments', 'sum_squares',
-           'DROPOUT_SWEEP', 'dropout_threshold', 'dropout_keep', 'dropout_apply']
+           'DROPOUT_SWEEP', 'dropout_threshold', 'dropout_keep', 'dropout_apply', 'QUANT_BITS', 'QUANT_GROUP', 'QUANT_SWEEP', 'quant_bytes', 'quant_pack',
+           'quant_unpack', 'quant_pack_host', 'quant_unpack_host']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -26,7 +27,8 @@ SYMBOLS = ('fewbit_hipx_abi_version', 'fewbit_hipx_last_error', 'fewbit_hipx_sam
            'fewbit_hipx_crs_scatter', 'fewbit_hipx_sampled_rows_ceil', 'fewbit_hipx_sampled_dct_zext', 'fewbit_hipx_sampled_dct_zext_seeded',
            'fewbit_hipx_sampled_dft_zext', 'fewbit_hipx_sampled_dft_zext_seeded', 'fewbit_hipx_moments_workspace', 'fewbit_hipx_row_moments',
            'fewbit_hipx_sum_squares', 'fewbit_hipx_dropout_threshold', 'fewbit_hipx_dropout_keep', 'fewbit_hipx_dropout', 'fewbit_hipx_sampled_signs',
-           'fewbit_hipx_sampled_dct_signed', 'fewbit_hipx_sampled_dft_signed')
+           'fewbit_hipx_sampled_dct_signed', 'fewbit_hipx_sampled_dft_signed', 'fewbit_hipx_quant_bytes', 'fewbit_hipx_quant_pack_host',
+           'fewbit_hipx_quant_unpack_host', 'fewbit_hipx_quant_pack', 'fewbit_hipx_quant_unpack')
 
 _lib = None
 
@@ -99,6 +101,17 @@ def lib() -> ctypes.CDLL:
         L.fewbit_hipx_sampled_dct_signed.argtypes = [i32, vp, sz, sz, sz, sz, u64, vp, sz, dbl, vp, vp, sz, vp]
         L.fewbit_hipx_sampled_dft_signed.restype = i32
         L.fewbit_hipx_sampled_dft_signed.argtypes = [i32, vp, sz, sz, sz, sz, u64, vp, sz, dbl, i32, vp, vp, sz, vp]
+        # the packed form of a seed: inside revision 2 as well, recognised by its symbols
+        L.fewbit_hipx_quant_bytes.restype = sz
+        L.fewbit_hipx_quant_bytes.argtypes = [sz, i32]
+        L.fewbit_hipx_quant_pack_host.restype = i32
+        L.fewbit_hipx_quant_pack_host.argtypes = [vp, sz, i32, u64, vp]
+        L.fewbit_hipx_quant_unpack_host.restype = i32
+        L.fewbit_hipx_quant_unpack_host.argtypes = [vp, sz, i32, vp]
+        L.fewbit_hipx_quant_pack.restype = i32
+        L.fewbit_hipx_quant_pack.argtypes = [i32, vp, sz, i32, u64, vp, vp, sz, vp]
+        L.fewbit_hipx_quant_unpack.restype = i32
+        L.fewbit_hipx_quant_unpack.argtypes = [vp, sz, i32, i32, vp, vp]
         _lib = L
     return _lib
 
@@ -402,4 +415,95 @@ def dropout_apply(src: torch.Tensor, seed, p: float, addend: Optional[torch.Tens
         out, _ = _buffers(src, others + (() if addend is None else (addend, )), out, src.shape, src.dtype, 'tensor of the shape and dtype of src', None, 0)
         _check(lib().fewbit_hipx_dropout(DTYPES[src.dtype], src.data_ptr(), None if addend is None else addend.data_ptr(), out.data_ptr(), src.numel(), first,
                                          value, word, threshold, _stream(stream, src.device)))
+    return out
+
+
+# ---- a tensor kept in 2, 4 or 8 bits per element (fewbit_amd/csrc/fewbit_quant.hip): the packed form of a seed, what QuantizedLinear keeps ------
+QUANT_BITS = (2, 4, 8)
+QUANT_GROUP = 64                                # elements that share one (lo, step) pair
+QUANT_SWEEP = 1 << 22                           # elements one sweep of the launch plan covers (2048 workgroups x 256 lanes x 8); beyond it lanes loop
+
+
+def quant_bytes(n: int, bits: int) -> int:
+    """Bytes of the packed form of ``n`` elements at ``bits`` bits: ``8 * ceil(n / 64) + bits * ceil(n / 8)``; 0 for ``bits`` other than 2, 4, 8
+    and for ``n`` outside 1 .. 2^36.  Evaluated on the host; no GPU needed."""
+    if n < 0:
+        return 0
+    return lib().fewbit_hipx_quant_bytes(n, bits)
+
+
+def _quant_size(n: int, bits: int, name: str) -> int:
+    if bits not in QUANT_BITS:
+        raise FewbitHipError(f'{name}: bits must be 2, 4 or 8 (got {bits})')
+    need = quant_bytes(n, bits)
+    if n != 0 and need == 0:
+        raise FewbitHipError(f'{name}: no packed form for {n} elements (1 .. 2^36 are supported)')
+    return need
+
+
+def quant_pack_host(values: torch.Tensor, seed: int, bits: int) -> torch.Tensor:
+    """The buffer ``quant_pack`` writes for ``seed``, evaluated on the host: ``values`` (any shape; taken as contiguous fp32, so pass the
+    values of a 16-bit tensor as ``.float()``) -> a host uint8 tensor of ``quant_bytes(values.numel(), bits)`` bytes.  The definition is
+    include/fewbit_hipx.h's ("the packed form of a seed"); no GPU needed."""
+    x = values.detach().to(device='cpu', dtype=torch.float32).contiguous()
+    out = torch.empty(_quant_size(x.numel(), bits, 'quant_pack_host'), dtype=torch.uint8)
+    _check(lib().fewbit_hipx_quant_pack_host(x.data_ptr(), x.numel(), bits, seed & 0xffffffffffffffff, out.data_ptr()))
+    return out
+
+
+def quant_unpack_host(packed: torch.Tensor, n: int, bits: int) -> torch.Tensor:
+    """The fp32 decode of a packed buffer on the host: a float32 tensor of ``n`` elements (``fma(code, step, lo)``; a poisoned group: NaN)"""
+    need = _quant_size(n, bits, 'quant_unpack_host')
+    if packed.device.type != 'cpu' or packed.dtype != torch.uint8 or not packed.is_contiguous() or packed.numel() < need:
+        raise FewbitHipError(f'packed must be a contiguous host uint8 tensor of at least {need} bytes')
+    out = torch.empty(n, dtype=torch.float32)
+    _check(lib().fewbit_hipx_quant_unpack_host(packed.data_ptr(), n, bits, out.data_ptr()))
+    return out
+
+
+def quant_pack(x: torch.Tensor, seed, bits: int, out: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+    """``x`` (a contiguous fp32 / fp16 / bf16 GPU tensor of any shape, taken by flat index) in ``bits`` bits per element with unbiased
+    stochastic rounding, in ONE launch: a uint8 tensor of ``quant_bytes(x.numel(), bits)`` bytes -- per group of 64 elements ``lo`` and
+    ``step = (hi - lo) / (2^bits - 1)`` as fp32, then the codes ``min(L, floor((x - lo) / step + U))``, ``U`` drawn from ``seed``.
+    ``seed``: an int, or a one-element int64 tensor on the device of ``x`` that is read when the kernel runs (``cabi.next_sketch_seed``: a
+    launch recorded into a hipGraph rounds afresh on every replay).  ``quant_pack_host`` gives the same bytes for the same seed.  ``out``: a
+    contiguous uint8 tensor of at least that many bytes (8-byte aligned); only the first ``quant_bytes`` bytes are written."""
+    if x.device.type != 'cuda':
+        raise FewbitHipError(f'x must live on the GPU (got {x.device})')
+    if x.dtype not in DTYPES:
+        raise FewbitHipError(f'unsupported dtype {x.dtype}')
+    if not x.is_contiguous():
+        raise FewbitHipError('x must be contiguous')
+    need = _quant_size(x.numel(), bits, 'quant_pack')
+    value, word, others = _seed_arguments(seed)
+    with _on(x.device):
+        if out is None:
+            out = torch.empty(need, dtype=torch.uint8, device=x.device)
+        elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
+            raise FewbitHipError('out must be a contiguous 1-D uint8 tensor')
+        _same_device(x, out, *others)
+        _check(lib().fewbit_hipx_quant_pack(DTYPES[x.dtype], x.data_ptr(), x.numel(), bits, value, word, out.data_ptr(), out.numel(),
+                                            _stream(stream, x.device)))
+    return out
+
+
+def quant_unpack(packed: torch.Tensor, n: int, bits: int, dtype: torch.dtype, out: Optional[torch.Tensor] = None,
+                 stream: Optional[int] = None) -> torch.Tensor:
+    """The decode of a ``quant_pack`` buffer in ONE launch: ``n`` elements of ``dtype`` (fp32 / fp16 / bf16, independent of the dtype that was
+    packed), each ``fma(code, step, lo)`` in fp32 rounded once to ``dtype``; a poisoned group decodes to NaN.  ``out``: a contiguous tensor of
+    ``n`` elements of ``dtype`` (any shape)."""
+    if packed.device.type != 'cuda':
+        raise FewbitHipError(f'packed must live on the GPU (got {packed.device})')
+    if dtype not in DTYPES:
+        raise FewbitHipError(f'unsupported dtype {dtype}')
+    need = _quant_size(n, bits, 'quant_unpack')
+    if packed.dtype != torch.uint8 or not packed.is_contiguous() or packed.numel() < need:
+        raise FewbitHipError(f'packed must be a contiguous uint8 tensor of at least {need} bytes')
+    with _on(packed.device):
+        if out is None:
+            out = torch.empty(n, dtype=dtype, device=packed.device)
+        elif out.numel() != n or out.dtype != dtype or not out.is_contiguous():
+            raise FewbitHipError(f'out must be a contiguous tensor of {n} elements of {dtype}')
+        _same_device(packed, out)
+        _check(lib().fewbit_hipx_quant_unpack(packed.data_ptr(), n, bits, DTYPES[dtype], out.data_ptr(), _stream(stream, packed.device)))
     return out

@@ -1,0 +1,428 @@
+// fewbit_quant.hip -- a tensor kept in 2, 4 or 8 bits per element with unbiased stochastic rounding, on gfx950; part of the companion library
+// libfewbit_hipx.so (include/fewbit_hipx.h, "the packed form of a seed"):
+//
+//     group g = elements 64 g .. 64 g + 63 of the flat tensor: lo = min, step = (max - min) / L, L = 2^bits - 1
+//     code(i) = min(L, floor((x[i] - lo) * inv + U(i))),  U(i) = 16 bits of Philox(seed, i) / 65536        decode: fma(code, step, lo)
+//
+// What QuantizedLinear (fewbit_amd/linear.py) keeps of its input for the weight gradient: every element, in a few bits, instead of a few rows
+// or columns in full.  The packed form is a pure function of (values, bits, seed) that fewbit_hipx_quant_pack_host evaluates alike.
+//
+// Pack: ONE launch, no LDS, no workspace, no atomics.  Lanes run along the blocks of eight elements (one Philox call and one code word of
+// `bits` bytes each); eight neighbouring lanes hold a group and reduce its minimum, maximum and poison flag with three DPP steps.  A
+// lane's block is one 16-byte load for the 16-bit types and two for fp32 when src is 16-byte aligned, element loads otherwise and in the block
+// that holds the tail -- the same arithmetic either way, so the same bytes.  Code words leave as one dword per lane pair (2 bits), per lane
+// (4 bits) or two (8 bits), the parameters as 8 bytes from the first lane of a group: ordinary vector stores.
+// Unpack: ONE launch; a lane reads its code word and its group's parameters and writes its block as 16-byte pieces.
+// Plan of both (a pure function of n): blocks = ceil(n / 8), workgroups of 256 lanes (32 groups), at most kMaxGroups of them; beyond that a
+// lane sweeps on by the grid's width.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+#include "fewbit_hipx.h"
+#include "fewbit_philox.h"
+
+#pragma clang fp contract(off)
+
+#define FEWBIT_HIDDEN __attribute__((visibility("hidden")))
+
+namespace fewbit_hip {
+namespace dft {
+FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));          // fewbit_dft.hip (g_last_error)
+}
+namespace quant {
+
+using dft::fail;
+using sketch::Key;
+
+constexpr uint32_t kRoundDomain = 7u;       // counter word 3 (0 and 2: the dense sketches, 3: the sampled rows, 4: the CRS columns, 5: the dropout, 6: the signs)
+constexpr int kThreads = 256, kBlock = 8;   // lanes per workgroup; elements per Philox call and per code word
+constexpr int kGroup = 64, kLanes = kGroup / kBlock;   // elements per group; lanes that hold one
+constexpr size_t kMaxGroups = 2048;         // one sweep of the grid: kMaxGroups * kThreads * kBlock = 2^22 elements
+constexpr size_t kMaxCount = size_t{1} << 36;
+constexpr uint32_t kNaN = 0x7fc00000u;      // what a poisoned group stores for lo and step, and decodes to
+
+static_assert(kThreads % kLanes == 0, "a group's lanes never straddle two sweeps of the grid");
+
+// ---- the definition, one element or one group at a time: host and device evaluate these very functions --------------------------------------
+// each is ONE correctly rounded fp32 operation (the device intrinsics keep the compiler from contracting a pair of them; the host is
+// compiled with contraction off)
+__host__ __device__ __forceinline__ float sub_rn(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fsub_rn(a, b);
+#else
+    return a - b;
+#endif
+}
+__host__ __device__ __forceinline__ float mul_rn(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fmul_rn(a, b);
+#else
+    return a * b;
+#endif
+}
+__host__ __device__ __forceinline__ float add_rn(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fadd_rn(a, b);
+#else
+    return a + b;
+#endif
+}
+__host__ __device__ __forceinline__ float div_rn(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fdiv_rn(a, b);
+#else
+    return a / b;
+#endif
+}
+__host__ __device__ __forceinline__ float fma_rn(float a, float b, float c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fmaf_rn(a, b, c);
+#else
+    return std::fmaf(a, b, c);
+#endif
+}
+
+__host__ __device__ __forceinline__ uint32_t bits_of_float(float v) { return __builtin_bit_cast(uint32_t, v); }
+__host__ __device__ __forceinline__ float float_of_bits(uint32_t b) { return __builtin_bit_cast(float, b); }
+
+// the order of the reals on the bits of a finite float, -0 below +0, as a signed integer (its own inverse)
+__host__ __device__ __forceinline__ int32_t order_key(uint32_t bits) {
+    return static_cast<int32_t>(bits ^ (static_cast<uint32_t>(static_cast<int32_t>(bits) >> 31) & 0x7fffffffu));
+}
+__host__ __device__ __forceinline__ bool non_finite(uint32_t bits) { return (bits & 0x7f800000u) == 0x7f800000u; }
+
+// the 16 bits of element e of a block (the dropout's choice: word e >> 1, low half for even e, high half for odd e) as U in [0, 1)
+__host__ __device__ __forceinline__ float uniform_of(const uint32_t (&w)[4], int e) {
+    return static_cast<float>((w[e >> 1] >> (16 * (e & 1))) & 0xffffu) * (1.0f / 65536.0f);             // (both exact)
+}
+__host__ __device__ __forceinline__ void block_words(uint64_t q, Key key, uint32_t (&w)[4]) {
+    sketch::philox4x32(static_cast<uint32_t>(q), static_cast<uint32_t>(q >> 32), 0u, kRoundDomain, key, w);
+}
+
+struct Params { float lo, step, inv; bool poisoned; };
+
+// from the keys of a group's minimum and maximum and whether it holds a NaN or an infinity
+__host__ __device__ __forceinline__ Params params_of(int32_t kmin, int32_t kmax, bool bad, float levels) {
+    Params p;
+    p.lo = float_of_bits(static_cast<uint32_t>(order_key(static_cast<uint32_t>(kmin))));
+    const float hi = float_of_bits(static_cast<uint32_t>(order_key(static_cast<uint32_t>(kmax))));
+    const float range = sub_rn(hi, p.lo);
+    p.poisoned = bad || non_finite(bits_of_float(range));
+    if (p.poisoned) {
+        p.lo = p.step = float_of_bits(kNaN);
+        p.inv = 0.0f;
+        return p;
+    }
+    p.step = div_rn(range, levels);
+    const float inv = range > 0.0f ? div_rn(levels, range) : 0.0f;
+    p.inv = non_finite(bits_of_float(inv)) ? 0.0f : inv;              // (a range below L / FLT_MAX: every code is 0, see the header)
+    return p;
+}
+__host__ __device__ __forceinline__ uint32_t code_of(float x, const Params &p, float u, uint32_t levels) {
+    if (p.poisoned) return 0u;
+    const float t = mul_rn(sub_rn(x, p.lo), p.inv);
+    const uint32_t c = static_cast<uint32_t>(floorf(add_rn(t, u)));    // (0 <= t + u < L + 2: the conversion is exact)
+    return c < levels ? c : levels;
+}
+__host__ __device__ __forceinline__ float decode(uint32_t code, float lo, float step) {
+    if (step != step) return float_of_bits(kNaN);
+    return fma_rn(static_cast<float>(code), step, lo);
+}
+
+inline bool known_dtype(int dtype) { return dtype == FEWBIT_F32 || dtype == FEWBIT_F16 || dtype == FEWBIT_BF16; }
+inline bool known_bits(int bits) { return bits == 2 || bits == 4 || bits == 8; }
+inline size_t size_of(int dtype) { return dtype == FEWBIT_F32 ? 4 : 2; }
+inline size_t bytes_of(size_t n, int bits) {
+    if (!known_bits(bits) || n == 0 || n > kMaxCount) return 0;
+    return 8 * ((n + kGroup - 1) / kGroup) + static_cast<size_t>(bits) * ((n + kBlock - 1) / kBlock);
+}
+
+template <int DT> struct Elem { using type = uint16_t; };
+template <> struct Elem<FEWBIT_F32> { using type = uint32_t; };
+
+template <int DT> __device__ __forceinline__ uint32_t widen(typename Elem<DT>::type raw) {              // the bits of the element as fp32 (exact)
+    if constexpr (DT == FEWBIT_F32) return raw;
+    else if constexpr (DT == FEWBIT_BF16) return static_cast<uint32_t>(raw) << 16;
+    else return bits_of_float(static_cast<float>(__builtin_bit_cast(_Float16, raw)));
+}
+// round to nearest even, as torch's conversions do (a NaN becomes the canonical quiet NaN of the format)
+template <int DT> __device__ __forceinline__ typename Elem<DT>::type narrow(float v) {
+    if constexpr (DT == FEWBIT_F32) return bits_of_float(v);
+    else if constexpr (DT == FEWBIT_BF16) {
+        const uint32_t bits = bits_of_float(v);
+        if (v != v) return static_cast<uint16_t>(0x7fc0u);
+        return static_cast<uint16_t>((bits + 0x7fffu + ((bits >> 16) & 1u)) >> 16);
+    } else {
+        // (left to itself the compiler folds the fma and the rounding to fp16 into one v_fma_mix*, which rounds the exact result once)
+        asm("" : "+v"(v));
+        return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v));
+    }
+}
+
+template <int DT> __device__ __forceinline__ void load8(const typename Elem<DT>::type *p, typename Elem<DT>::type (&v)[kBlock]) {
+    const uint4 *q = reinterpret_cast<const uint4 *>(p);
+    if constexpr (DT == FEWBIT_F32) {
+        const uint4 a = q[0], b = q[1];
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+        const uint4 a = q[0];
+        const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int e = 0; e < kBlock; ++e) v[e] = static_cast<uint16_t>(w[e >> 1] >> (16 * (e & 1)));
+    }
+}
+template <int DT> __device__ __forceinline__ void store8(typename Elem<DT>::type *p, const typename Elem<DT>::type (&v)[kBlock]) {
+    uint4 *q = reinterpret_cast<uint4 *>(p);
+    if constexpr (DT == FEWBIT_F32) {
+        q[0] = uint4{v[0], v[1], v[2], v[3]};
+        q[1] = uint4{v[4], v[5], v[6], v[7]};
+    } else {
+        q[0] = uint4{v[0] | static_cast<uint32_t>(v[1]) << 16, v[2] | static_cast<uint32_t>(v[3]) << 16, v[4] | static_cast<uint32_t>(v[5]) << 16,
+                     v[6] | static_cast<uint32_t>(v[7]) << 16};
+    }
+}
+
+// Data-parallel-primitive moves inside a row of 16 lanes (no LDS crossbar): quad_perm [1, 0, 3, 2], quad_perm [2, 3, 0, 1], row_half_mirror.
+// The eight lanes of a group are active together, so every source lane is.
+constexpr int kSwapPairs = 0xB1, kSwapHalves = 0x4E, kMirrorEight = 0x141;
+template <int CTRL> __device__ __forceinline__ int lane_move(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
+template <int CTRL> __device__ __forceinline__ void reduce_step(int32_t &kmin, int32_t &kmax, uint32_t &bad) {
+    const int32_t omin = lane_move<CTRL>(kmin), omax = lane_move<CTRL>(kmax);
+    bad |= static_cast<uint32_t>(lane_move<CTRL>(static_cast<int>(bad)));
+    kmin = omin < kmin ? omin : kmin;
+    kmax = omax > kmax ? omax : kmax;
+}
+
+// VEC: src is 16-byte aligned, so every whole block is.  out: 8-byte aligned; the parameters of group g at 8 g, the code word of block b at
+// 8 groups + BITS b.
+template <int DT, int BITS, bool VEC>
+__global__ __launch_bounds__(kThreads) void pack_kernel(const void *__restrict__ src_, size_t n, Key value, const Key *device, uint8_t *__restrict__ out) {
+    using T = typename Elem<DT>::type;
+    constexpr uint32_t kLevels = (1u << BITS) - 1u;
+    const T *src = static_cast<const T *>(src_);
+    Key key = value;
+    if (device != nullptr) key = *device;
+    const size_t blocks = (n + kBlock - 1) / kBlock, groups = (n + kGroup - 1) / kGroup, width = static_cast<size_t>(gridDim.x) * kThreads;
+    uint8_t *codes = out + 8 * groups;
+    // (the bound is a group's, not a block's: the eight lanes of a group leave the loop together, so every lane move below meets its partner)
+    for (size_t b = static_cast<size_t>(blockIdx.x) * kThreads + threadIdx.x; b < groups * kLanes; b += width) {
+        const size_t i0 = b * kBlock;
+        const int have = b >= blocks ? 0 : n - i0 < static_cast<size_t>(kBlock) ? static_cast<int>(n - i0) : kBlock;
+        T raw[kBlock];
+        if (VEC && have == kBlock) {
+            load8<DT>(src + i0, raw);
+        } else {
+            // (a missing element repeats the block's first, which moves neither the minimum, the maximum nor the flag, and its code is masked
+            // away below: the arithmetic has no branch per element; a lane without elements holds zeros and is made neutral below)
+#pragma unroll
+            for (int e = 0; e < kBlock; ++e) raw[e] = e < have ? src[i0 + e] : e == 0 ? T{0} : raw[0];
+        }
+        uint32_t x[kBlock];
+        int32_t kmin = INT32_MAX, kmax = INT32_MIN;
+        uint32_t bad = 0;
+#pragma unroll
+        for (int e = 0; e < kBlock; ++e) {
+            x[e] = widen<DT>(raw[e]);
+            const int32_t k = order_key(x[e]);
+            kmin = k < kmin ? k : kmin;
+            kmax = k > kmax ? k : kmax;
+            bad |= non_finite(x[e]) ? 1u : 0u;
+        }
+        if (have == 0) kmin = INT32_MAX, kmax = INT32_MIN, bad = 0;
+        // lane ^ 1, lane ^ 2, then the other quad of the eight (mirrored: every lane of a quad holds the quad's result by then)
+        reduce_step<kSwapPairs>(kmin, kmax, bad);
+        reduce_step<kSwapHalves>(kmin, kmax, bad);
+        reduce_step<kMirrorEight>(kmin, kmax, bad);
+        const Params p = params_of(kmin, kmax, bad != 0, static_cast<float>(kLevels));
+        uint32_t w[4];
+        block_words(b, key, w);
+        uint64_t word = 0;
+#pragma unroll
+        for (int e = 0; e < kBlock; ++e) word |= static_cast<uint64_t>(code_of(float_of_bits(x[e]), p, uniform_of(w, e), kLevels)) << (BITS * e);
+        if (have < kBlock) word &= (uint64_t{1} << (BITS * have)) - 1;                              // the missing elements of the last word are 0
+        if constexpr (BITS == 2) {
+            // two lanes' words as one dword from the even lane; the last block of an odd count has no partner inside the buffer
+            const uint32_t mine = static_cast<uint32_t>(word), other = static_cast<uint32_t>(lane_move<kSwapPairs>(static_cast<int>(mine)));
+            if ((b & 1) == 0 && b + 1 < blocks) *reinterpret_cast<uint32_t *>(codes + 2 * b) = mine | other << 16;
+            else if ((b & 1) == 0 && b < blocks) *reinterpret_cast<uint16_t *>(codes + 2 * b) = static_cast<uint16_t>(mine);
+        } else if constexpr (BITS == 4) {
+            if (b < blocks) *reinterpret_cast<uint32_t *>(codes + 4 * b) = static_cast<uint32_t>(word);
+        } else {
+            if (b < blocks) *reinterpret_cast<uint2 *>(codes + 8 * b) = uint2{static_cast<uint32_t>(word), static_cast<uint32_t>(word >> 32)};
+        }
+        if ((b & (kLanes - 1)) == 0) *reinterpret_cast<uint2 *>(out + 8 * (b / kLanes)) = uint2{bits_of_float(p.lo), bits_of_float(p.step)};
+    }
+}
+
+template <int DT, int BITS, bool VEC>
+__global__ __launch_bounds__(kThreads) void unpack_kernel(const uint8_t *__restrict__ packed, size_t n, void *__restrict__ out_) {
+    using T = typename Elem<DT>::type;
+    constexpr uint32_t kLevels = (1u << BITS) - 1u;
+    T *out = static_cast<T *>(out_);
+    const size_t blocks = (n + kBlock - 1) / kBlock, groups = (n + kGroup - 1) / kGroup, width = static_cast<size_t>(gridDim.x) * kThreads;
+    const uint8_t *codes = packed + 8 * groups;
+    for (size_t b = static_cast<size_t>(blockIdx.x) * kThreads + threadIdx.x; b < blocks; b += width) {
+        const uint2 par = *reinterpret_cast<const uint2 *>(packed + 8 * (b / kLanes));
+        uint64_t word;
+        if constexpr (BITS == 2) word = *reinterpret_cast<const uint16_t *>(codes + 2 * b);
+        else if constexpr (BITS == 4) word = *reinterpret_cast<const uint32_t *>(codes + 4 * b);
+        else {
+            const uint2 c = *reinterpret_cast<const uint2 *>(codes + 8 * b);
+            word = c.x | static_cast<uint64_t>(c.y) << 32;
+        }
+        const float lo = float_of_bits(par.x), step = float_of_bits(par.y);
+        T y[kBlock];
+#pragma unroll
+        for (int e = 0; e < kBlock; ++e) y[e] = narrow<DT>(decode(static_cast<uint32_t>(word >> (BITS * e)) & kLevels, lo, step));
+        const size_t i0 = b * kBlock;
+        if (VEC && i0 + kBlock <= n) {
+            store8<DT>(out + i0, y);
+        } else {
+            const int have = n - i0 < static_cast<size_t>(kBlock) ? static_cast<int>(n - i0) : kBlock;
+#pragma unroll
+            for (int e = 0; e < kBlock; ++e)
+                if (e < have) out[i0 + e] = y[e];
+        }
+    }
+}
+
+template <int DT, int BITS> void launch_pack(bool vec, unsigned groups, hipStream_t s, const void *src, size_t n, Key key, const Key *device, uint8_t *out) {
+    if (vec) hipLaunchKernelGGL((pack_kernel<DT, BITS, true>), dim3(groups), dim3(kThreads), 0, s, src, n, key, device, out);
+    else hipLaunchKernelGGL((pack_kernel<DT, BITS, false>), dim3(groups), dim3(kThreads), 0, s, src, n, key, device, out);
+}
+template <int DT> void launch_pack(int bits, bool vec, unsigned groups, hipStream_t s, const void *src, size_t n, Key key, const Key *device, uint8_t *out) {
+    if (bits == 2) launch_pack<DT, 2>(vec, groups, s, src, n, key, device, out);
+    else if (bits == 4) launch_pack<DT, 4>(vec, groups, s, src, n, key, device, out);
+    else launch_pack<DT, 8>(vec, groups, s, src, n, key, device, out);
+}
+
+template <int DT, int BITS> void launch_unpack(bool vec, unsigned groups, hipStream_t s, const uint8_t *packed, size_t n, void *out) {
+    if (vec) hipLaunchKernelGGL((unpack_kernel<DT, BITS, true>), dim3(groups), dim3(kThreads), 0, s, packed, n, out);
+    else hipLaunchKernelGGL((unpack_kernel<DT, BITS, false>), dim3(groups), dim3(kThreads), 0, s, packed, n, out);
+}
+template <int DT> void launch_unpack(int bits, bool vec, unsigned groups, hipStream_t s, const uint8_t *packed, size_t n, void *out) {
+    if (bits == 2) launch_unpack<DT, 2>(vec, groups, s, packed, n, out);
+    else if (bits == 4) launch_unpack<DT, 4>(vec, groups, s, packed, n, out);
+    else launch_unpack<DT, 8>(vec, groups, s, packed, n, out);
+}
+
+// workgroups for `lanes` lanes of work
+inline unsigned grid_of(size_t lanes) {
+    const size_t wanted = (lanes + kThreads - 1) / kThreads;
+    return static_cast<unsigned>(wanted < kMaxGroups ? wanted : kMaxGroups);
+}
+
+}  // namespace quant
+}  // namespace fewbit_hip
+
+using namespace fewbit_hip;
+using namespace fewbit_hip::quant;
+
+extern "C" {
+
+size_t fewbit_hipx_quant_bytes(size_t n, int bits) { return bytes_of(n, bits); }
+
+int fewbit_hipx_quant_pack_host(const float *x_host, size_t n, int bits, uint64_t seed, uint8_t *out_host) {
+    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack_host: bits = %d is not 2, 4 or 8", bits);
+    if (n == 0) return FEWBIT_OK;
+    if (n > kMaxCount) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack_host: n = %zu is beyond 2^36", n);
+    if (x_host == nullptr || out_host == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack_host: null pointer");
+    const uint32_t levels = (1u << bits) - 1u;
+    const size_t groups = (n + kGroup - 1) / kGroup;
+    const Key key = sketch::key_of(seed);
+    uint8_t *codes = out_host + 8 * groups;
+    for (size_t g = 0; g < groups; ++g) {
+        const size_t first = g * kGroup, count = n - first < static_cast<size_t>(kGroup) ? n - first : kGroup;
+        int32_t kmin = INT32_MAX, kmax = INT32_MIN;
+        bool bad = false;
+        for (size_t j = 0; j < count; ++j) {
+            const uint32_t bits32 = bits_of_float(x_host[first + j]);
+            const int32_t k = order_key(bits32);
+            kmin = k < kmin ? k : kmin;
+            kmax = k > kmax ? k : kmax;
+            bad = bad || non_finite(bits32);
+        }
+        const Params p = params_of(kmin, kmax, bad, static_cast<float>(levels));
+        const uint32_t par[2] = {bits_of_float(p.lo), bits_of_float(p.step)};
+        for (int h = 0; h < 2; ++h)
+            for (int c = 0; c < 4; ++c) out_host[8 * g + 4 * h + c] = static_cast<uint8_t>(par[h] >> (8 * c));
+        for (size_t j0 = 0; j0 < count; j0 += kBlock) {
+            const size_t b = (first + j0) / kBlock;
+            uint32_t w[4];
+            block_words(b, key, w);
+            uint64_t word = 0;
+            for (int e = 0; e < kBlock && j0 + e < count; ++e)
+                word |= static_cast<uint64_t>(code_of(x_host[first + j0 + e], p, uniform_of(w, e), levels)) << (bits * e);
+            for (int c = 0; c < bits; ++c) codes[static_cast<size_t>(bits) * b + c] = static_cast<uint8_t>(word >> (8 * c));
+        }
+    }
+    return FEWBIT_OK;
+}
+
+int fewbit_hipx_quant_unpack_host(const uint8_t *packed_host, size_t n, int bits, float *out_host) {
+    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack_host: bits = %d is not 2, 4 or 8", bits);
+    if (n == 0) return FEWBIT_OK;
+    if (n > kMaxCount) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack_host: n = %zu is beyond 2^36", n);
+    if (packed_host == nullptr || out_host == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack_host: null pointer");
+    const uint32_t levels = (1u << bits) - 1u;
+    const uint8_t *codes = packed_host + 8 * ((n + kGroup - 1) / kGroup);
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t par[2] = {0, 0};
+        for (int h = 0; h < 2; ++h)
+            for (int c = 0; c < 4; ++c) par[h] |= static_cast<uint32_t>(packed_host[8 * (i / kGroup) + 4 * h + c]) << (8 * c);
+        const size_t bit = static_cast<size_t>(bits) * (i % kBlock);
+        const uint32_t code = (codes[static_cast<size_t>(bits) * (i / kBlock) + bit / 8] >> (bit % 8)) & levels;
+        out_host[i] = decode(code, float_of_bits(par[0]), float_of_bits(par[1]));
+    }
+    return FEWBIT_OK;
+}
+
+int fewbit_hipx_quant_pack(int dtype, const void *src, size_t n, int bits, uint64_t seed, const uint64_t *seed_device, uint8_t *out, size_t out_bytes,
+                           void *stream) {
+    if (!known_dtype(dtype)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: unknown dtype %d", dtype);
+    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: bits = %d is not 2, 4 or 8", bits);
+    if ((reinterpret_cast<uintptr_t>(seed_device) & 7) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: the seed word in device memory must be 8-byte aligned");
+    if (n == 0) return FEWBIT_OK;
+    if (n > kMaxCount) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: n = %zu is beyond 2^36", n);
+    if (src == nullptr || out == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: null pointer");
+    if (reinterpret_cast<uintptr_t>(src) % size_of(dtype) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: src must be aligned to its element size");
+    if ((reinterpret_cast<uintptr_t>(out) & 7) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: out must be 8-byte aligned");
+    const size_t need = bytes_of(n, bits);
+    if (out_bytes < need) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: out has %zu bytes, %zu are needed", out_bytes, need);
+    const size_t groups = (n + kGroup - 1) / kGroup;
+    const unsigned grid = grid_of(groups * kLanes);
+    const bool vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+    const Key key = sketch::key_of(seed);
+    const Key *device = reinterpret_cast<const Key *>(seed_device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+    case FEWBIT_F32: launch_pack<FEWBIT_F32>(bits, vec, grid, s, src, n, key, device, out); break;
+    case FEWBIT_F16: launch_pack<FEWBIT_F16>(bits, vec, grid, s, src, n, key, device, out); break;
+    default: launch_pack<FEWBIT_BF16>(bits, vec, grid, s, src, n, key, device, out); break;
+    }
+    return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "quant_pack: the launch failed");
+}
+
+int fewbit_hipx_quant_unpack(const uint8_t *packed, size_t n, int bits, int out_dtype, void *out, void *stream) {
+    if (!known_dtype(out_dtype)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack: unknown dtype %d", out_dtype);
+    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack: bits = %d is not 2, 4 or 8", bits);
+    if (n == 0) return FEWBIT_OK;
+    if (n > kMaxCount) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack: n = %zu is beyond 2^36", n);
+    if (packed == nullptr || out == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack: null pointer");
+    if ((reinterpret_cast<uintptr_t>(packed) & 7) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack: packed must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out) % size_of(out_dtype) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack: out must be aligned to its element size");
+    const unsigned grid = grid_of((n + kBlock - 1) / kBlock);
+    const bool vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (out_dtype) {
+    case FEWBIT_F32: launch_unpack<FEWBIT_F32>(bits, vec, grid, s, packed, n, out); break;
+    case FEWBIT_F16: launch_unpack<FEWBIT_F16>(bits, vec, grid, s, packed, n, out); break;
+    default: launch_unpack<FEWBIT_BF16>(bits, vec, grid, s, packed, n, out); break;
+    }
+    return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "quant_unpack: the launch failed");
+}
+
+}  // extern "C"

@@ -252,6 +252,6 @@ del _name
 
 # Randomized linear layers and gradient-capture helpers live in the same namespace in the reference
 # (fewbit/functional/__init__.py:14-18).
-from .linear import linear_crs, linear_grp, linear_randomized  # noqa: E402,F401
+from .linear import linear_crs, linear_grp, linear_quantized, linear_randomized  # noqa: E402,F401
 from .variance import GradientStorage, catch_gradients  # noqa: E402,F401
 from .dropout import dropout, dropout_add  # noqa: E402,F401

@@ -77,6 +77,24 @@ of the call's seed (``cabi_x.crs_columns(seed, in_features, nopairs)`` on the ho
 one call that writes the whole weight gradient; the layer keeps its ``rows x m`` projection and one integer, reads nothing back and can be
 captured into a hipGraph (a captured layer keeps ``min(nopairs, in_features)`` columns, the unused ones zero).  ``use_native_sketch(False)``
 selects randint + bincount + nonzero, with its read-back.
+
+Every element in a few bits: ``linear_quantized`` / ``QuantizedLinear`` (this package's own; like ``Dropout`` they are not in
+``fewbit.modules.__all__``, which stays the reference's list) keep the WHOLE input, each element rounded to ``bits`` = 2, 4 or 8 bits --
+the other standard way to shrink what a linear layer saves, for users who cannot afford the variance of a projection that throws rows or
+columns away.  Per group of 64 consecutive elements (by flat index) the minimum ``lo`` and ``step = (max - lo) / (2^bits - 1)`` are kept as
+fp32 and every element as ``code = min(L, floor((x - lo) / step + U))`` with ``U`` uniform in [0, 1): ``E[lo + code * step] = x``, the error
+of an element is below ``step``, a constant group is exact.  Forward is ``F.linear``; ``grad_input`` and ``grad_bias`` are exact;
+``grad_weight = G^T X^`` with ``X^`` decoded into the gradient's dtype as a transient tensor -- one GEMM (a bf16 gradient at 8 bits: X^ decoded
+into fp32 and multiplied as two bf16 terms that meet in fp32, ``_decode_in_two_terms``: about twice the time of the other widths).  On fp32 / fp16 / bf16 GPU tensors
+packing and decoding are one launch each on the kernels of ``fewbit_amd/csrc/fewbit_quant.hip`` (``cabi_x.quant_pack`` / ``quant_unpack``;
+the definition, "the packed form of a seed", is include/fewbit_hipx.h's and ``cabi_x.quant_pack_host`` evaluates it on the host): ``U`` is a
+function of the call's 64-bit seed, the node keeps one uint8 buffer of ``cabi_x.quant_bytes(input.numel(), bits)`` bytes (0.3125 x a bf16
+input at 4 bits, 0.1875 x at 2, 0.5625 x at 8), the weight, the seed and the shape -- never the input -- reads nothing back and can be
+captured into a hipGraph after one eager call (the seed is then a device word: every replay rounds afresh).  A group that holds a NaN or an
+infinity decodes to NaN as a whole; other groups are untouched.  Host tensors, float64 and ``use_native_sketch(False)`` take a PyTorch
+formulation of the same scheme (the same groups, the same unbiased rounding, ``U`` from the call's generator, one code per byte; not bit
+for bit the kernel's).  Autocast, checkpointing, ``no_grad`` and a frozen weight behave as for the layers above.  Out of scope: fusing the
+decode into the GEMM, 3-bit codes, per-row groups.
 """
 import contextlib
 import os
@@ -88,7 +106,8 @@ import torch.nn.functional as F
 from .fft import dct
 
 __all__ = ('MATMUL_TYPES', 'projection_dim', 'linear_crs', 'linear_grp', 'linear_randomized', 'LinearCRS', 'LinearGRP',
-           'RandomizedLinear', 'use_native_sketch', 'use_row_extension', 'use_sign_flips', 'sampled_transform', 'sampled_transform_path')
+           'RandomizedLinear', 'use_native_sketch', 'use_row_extension', 'use_sign_flips', 'sampled_transform', 'sampled_transform_path',
+           'QUANT_BITS', 'linear_quantized', 'QuantizedLinear')
 
 MATMUL_TYPES = ('dct', 'dft', 'gaussian', 'rademacher')
 
@@ -670,6 +689,138 @@ def linear_crs(input: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
     return _LinearCRS.apply(input, weight, bias, int(nopairs))
 
 
+# ---- every element of the input in 2, 4 or 8 bits --------------------------------------------------------------------------------------
+
+QUANT_BITS = (2, 4, 8)
+_QUANT_GROUP = 64                                # elements (by flat index) that share one (lo, step) pair: cabi_x.QUANT_GROUP
+
+
+def _native_quant_applies(flat: torch.Tensor) -> bool:
+    """The gfx950 kernels (fewbit_amd/csrc/fewbit_quant.hip) take fp32 / fp16 / bf16 GPU tensors of up to 2^36 elements"""
+    return (_NATIVE_SKETCH and flat.device.type == 'cuda' and flat.dtype in (torch.float32, torch.float16, torch.bfloat16)
+            and flat.numel() <= 2**36)
+
+
+def _quantize_groups(flat: torch.Tensor, bits: int, generator: Optional[torch.Generator]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The PyTorch formulation of the packed form: -> (codes, one uint8 per element of the padded groups; lo; step, one per group), in fp32
+    (fp64 for a float64 input).  The tail of the last group is filled with the last element, which moves neither its minimum nor its maximum."""
+    levels = float(2**bits - 1)
+    work = flat.reshape(-1).to(torch.float64 if flat.dtype == torch.float64 else torch.float32)
+    pad = -work.numel() % _QUANT_GROUP
+    if pad:
+        work = torch.cat((work, work[-1:].expand(pad)))
+    work = work.view(-1, _QUANT_GROUP)
+    lo, hi = work.amin(dim=1, keepdim=True), work.amax(dim=1, keepdim=True)
+    span = hi - lo
+    poisoned = ~torch.isfinite(span)                                        # (a NaN reaches amin / amax, an infinity makes the span inf or NaN)
+    step = span / levels
+    inv = torch.where(span > 0, levels / span, torch.zeros_like(span))
+    inv = torch.where(torch.isfinite(inv), inv, torch.zeros_like(inv))
+    if generator is None:
+        u = torch.rand(work.shape, dtype=work.dtype, device=work.device)
+    else:
+        u = torch.rand(work.shape, dtype=work.dtype, device=generator.device, generator=generator).to(work.device)
+    codes = torch.floor((work - lo) * inv + u).clamp_(max=levels)
+    codes = torch.where(poisoned, torch.zeros_like(codes), codes).to(torch.uint8)
+    nan = torch.full_like(lo, float('nan'))
+    return codes.reshape(-1), torch.where(poisoned, nan, lo).reshape(-1), torch.where(poisoned, nan, step).reshape(-1)
+
+
+def _dequantize_groups(codes: torch.Tensor, lo: torch.Tensor, step: torch.Tensor, shape, dtype: torch.dtype) -> torch.Tensor:
+    values = torch.addcmul(lo[:, None], codes.view(-1, _QUANT_GROUP).to(lo.dtype), step[:, None])
+    return values.reshape(-1)[:shape[0] * shape[1]].view(shape).to(dtype)
+
+
+def _decode_in_two_terms(bits: int, dtype: torch.dtype) -> bool:
+    """Whether ``G^T X^`` needs X^ to better than ``dtype``: a bf16 gradient at 8 bits.  There the step, range / 255, is about one bf16 ulp of a
+    group's larger elements, and rounding ``lo + code * step`` to bf16 moves an element by up to half an ulp in a direction that does not depend
+    on the seed: over many seeds the mean weight gradient then sits several of its standard errors from ``G^T X`` (measured: 8.5, against 3.5
+    for the fp32 decode of the same buffers).  At 2 and 4 bits the step is 85 and 17 times larger, and fp16 has eight times bf16's resolution."""
+    return bits == 8 and dtype == torch.bfloat16
+
+
+def _two_term_product(g: torch.Tensor, decoded: torch.Tensor) -> torch.Tensor:
+    """``g^T decoded`` for a 16-bit ``g`` and an fp32 ``decoded`` on the 16-bit matrix pipe: ``decoded = head + tail`` with ``head`` its rounding to
+    the dtype of ``g`` (what ``quant_unpack`` into that dtype gives) and ``tail`` the rounding of the exact remainder.  Both products have to meet
+    in fp32 and be rounded once: summed after the first was rounded to 16 bits, that one swallows the second, a fraction of its ulp (measured:
+    the deviation stayed).  On the GPU the library GEMM gives fp32 results for 16-bit operands (``out_dtype``): two GEMMs, an fp32 sum, rounded
+    by the caller.  Elsewhere ONE GEMM of twice the depth, ``[g; g]^T [head; tail]``.  What is left of the rounding of ``decoded`` is 2^-9 of
+    the tail: 2^-18 of an element."""
+    rows = decoded.shape[0]
+    terms = torch.empty((2 * rows, decoded.shape[1]), dtype=g.dtype, device=decoded.device)
+    terms[:rows].copy_(decoded)                                             # head
+    torch.sub(decoded, terms[:rows], out=terms[rows:])                      # tail: the difference is exact in fp32, rounded on the store
+    if g.is_cuda:                                                           # two GEMMs with fp32 results: no copy of g, no doubled depth
+        with torch.autocast('cuda', enabled=False):
+            return torch.mm(g.T, terms[:rows], out_dtype=torch.float32) + torch.mm(g.T, terms[rows:], out_dtype=torch.float32)
+    return torch.cat((g, g)).T @ terms
+
+
+class _LinearQuantized(torch.autograd.Function):
+    """``F.linear`` that keeps its input in ``bits`` bits per element for the weight gradient (module docstring).  Kept for backward on the
+    kernels: ONE uint8 buffer (``cabi_x.quant_pack``), the weight, the seed (an int; a device word while the stream is being captured) and
+    the shape; in the PyTorch formulation the codes (one per byte) and the two parameters of every group."""
+
+    @staticmethod
+    def forward(ctx, input, weight, bias, bits: int, generator):
+        flat = input.detach().reshape(-1, input.shape[-1])
+        ctx.bits, ctx.flat_shape = bits, tuple(flat.shape)
+        ctx.has_bias = bias is not None
+        ctx.autocast = _autocast_seen(input.device.type)
+        ctx.native_seed = None
+        if _native_quant_applies(flat):
+            from . import cabi_x
+            ctx.native_seed = _sketch_seed(generator, flat.device)
+            # (a non-contiguous input is packed from a contiguous copy, which lives no longer than this call)
+            ctx.save_for_backward(cabi_x.quant_pack(flat if flat.is_contiguous() else flat.contiguous(), ctx.native_seed, bits), weight)
+        else:
+            ctx.save_for_backward(*_quantize_groups(flat, bits, generator), weight)
+        return F.linear(input, weight, bias)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        with _autocast_as(ctx.autocast):
+            return _LinearQuantized._backward(ctx, _dense_rows(grad_output))
+
+    @staticmethod
+    def _backward(ctx, grad_output):
+        saved = ctx.saved_tensors                       # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
+        weight = saved[-1]
+        grad_input = grad_weight = grad_bias = None
+        if ctx.needs_input_grad[0]:
+            grad_input = grad_output @ weight
+        flat = grad_output.reshape(-1, grad_output.shape[-1])
+        if ctx.needs_input_grad[1] and ctx.native_seed is not None:
+            from . import cabi_x
+            # X^ in the gradient's dtype (under autocast not the input's): a transient tensor, one GEMM
+            g2 = flat if flat.dtype in (torch.float32, torch.float16, torch.bfloat16) else flat.float()
+            rows, features = ctx.flat_shape
+            if _decode_in_two_terms(ctx.bits, g2.dtype):
+                grad_weight = _two_term_product(g2, cabi_x.quant_unpack(saved[0], rows * features, ctx.bits, torch.float32).view(rows, features)).to(weight.dtype)
+            else:
+                decoded = cabi_x.quant_unpack(saved[0], rows * features, ctx.bits, g2.dtype).view(rows, features)
+                grad_weight = (g2.T @ decoded).to(weight.dtype)
+        elif ctx.needs_input_grad[1] and _decode_in_two_terms(ctx.bits, flat.dtype):
+            grad_weight = _two_term_product(flat, _dequantize_groups(saved[0], saved[1], saved[2], ctx.flat_shape, torch.float32)).to(weight.dtype)
+        elif ctx.needs_input_grad[1]:
+            grad_weight = (flat.T @ _dequantize_groups(saved[0], saved[1], saved[2], ctx.flat_shape, flat.dtype)).to(weight.dtype)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            grad_bias = flat.sum(dim=0)
+        return grad_input, grad_weight, grad_bias, None, None
+
+
+def linear_quantized(input: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bits: int = 4,
+                     generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """``F.linear(input, weight, bias)`` that keeps its input in ``bits`` = 2, 4 or 8 bits per element, rounded without bias, for the weight
+    gradient: ``grad_input`` and ``grad_bias`` are exact, ``grad_weight = G^T X^`` (module docstring).  ``generator``: the source of the
+    rounding's randomness; without it the host default generator seeds every call."""
+    if bits not in QUANT_BITS:
+        raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+    if _plain_linear(input, weight):
+        return F.linear(input, weight, bias)
+    return _LinearQuantized.apply(input, weight, bias, int(bits), generator)
+
+
 # ---- modules ---------------------------------------------------------------------------------------------------------
 
 class LinearCRS(torch.nn.Linear):
@@ -748,3 +899,47 @@ class LinearGRP(torch.nn.Linear):
 
 
 RandomizedLinear = LinearGRP
+
+
+class QuantizedLinear(torch.nn.Linear):
+    r"""Drop-in :class:`torch.nn.Linear` that keeps its input in ``bits`` bits per element instead of the input itself and forms the weight
+    gradient from the decoded values; the output, the input gradient and the bias gradient are those of ``nn.Linear``.
+
+    Parameters (after those of ``nn.Linear``)
+    ----------
+    bits : {2, 4, 8}, default=4
+        Bits per kept element.  Groups of 64 elements share a minimum and a step (8 more bytes per group): a bf16 input is kept in 0.1875,
+        0.3125 or 0.5625 of its bytes.  The rounding is stochastic and unbiased; the error of an element is below its group's step.  With bf16
+        gradients, 8 bits cost about twice the backward time of 2 or 4 (the decode is then multiplied as two bf16 terms to stay unbiased).
+    generator : torch.Generator, optional
+        Source of the rounding's randomness; without it the host default generator seeds every call.  Inside ``torch.utils.checkpoint`` it
+        must be a default generator, as for :class:`LinearGRP`.
+
+    Examples:
+
+        >>> m = fewbit.QuantizedLinear(20, 30, bits=4)
+        >>> m(torch.randn(128, 20)).size()
+        torch.Size([128, 30])
+        >>> model = fewbit.map_module(model, lambda m, path: fewbit.QuantizedLinear.from_linear(m, bits=4) if type(m) is torch.nn.Linear else m)
+    """
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=None, bits: int = 4,
+                 generator: Optional[torch.Generator] = None) -> None:
+        if bits not in QUANT_BITS:
+            raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+        super().__init__(in_features, out_features, bias, device, dtype)
+        self.bits = bits
+        self.generator = generator
+
+    @classmethod
+    def from_linear(cls, module: torch.nn.Linear, bits: int = 4, generator: Optional[torch.Generator] = None) -> 'QuantizedLinear':
+        """A ``QuantizedLinear`` that SHARES the parameters of ``module`` (what ``map_module`` needs to swap the linears of a built model)"""
+        new = cls(module.in_features, module.out_features, module.bias is not None, device='meta', bits=bits, generator=generator)
+        new.weight, new.bias = module.weight, module.bias
+        return new.train(module.training)
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        return linear_quantized(input, self.weight, self.bias, self.bits, self.generator)
+
+    def extra_repr(self) -> str:
+        return f'{super().extra_repr()}, bits={self.bits}'

@@ -34,6 +34,8 @@ extern "C" {
  * So was the dropout whose mask is a function of a seed (fewbit_hipx_dropout_threshold, _dropout_keep, _dropout): inside revision 2,
  * recognised by the presence of the symbols.
  * So were the sampled transforms with the signs of a seed (fewbit_hipx_sampled_signs, _sampled_dct_signed, _sampled_dft_signed): inside
+ * revision 2, recognised by the presence of the symbols.
+ * So was the packed form of a seed (fewbit_hipx_quant_bytes, _quant_pack_host, _quant_unpack_host, _quant_pack, _quant_unpack): inside
  * revision 2, recognised by the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
@@ -250,6 +252,59 @@ int fewbit_hipx_dropout_threshold(double p);
 int fewbit_hipx_dropout_keep(uint64_t seed, uint32_t threshold, uint64_t first, size_t count, uint8_t *keep_host);
 int fewbit_hipx_dropout(int dtype, const void *src, const void *addend, void *out, size_t n, uint64_t first, uint64_t seed, const uint64_t *seed_device,
                         uint32_t threshold, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * A tensor kept in 2, 4 or 8 bits per element with unbiased stochastic rounding (what QuantizedLinear keeps of its input): the packed
+ * buffer is a pure function of (values, bits, seed), evaluated alike by the host function and the kernel.
+ *
+ * The packed form of a seed.  The input is a logical contiguous tensor of n elements (F32 / F16 / BF16), each widened exactly to fp32;
+ * bits = k in {2, 4, 8}, L = 2^k - 1; a 64-bit seed.  Elements are taken by flat index i; group g is the elements 64 g .. min(64 g + 64, n) - 1
+ * (groups may straddle the rows of a matrix).
+ *     u(i)    = the 16 bits the mask of a seed (above) takes for index i -- the same block q = i >> 3, word and half -- with counter word 3 = 7
+ *               (this domain's own: 0 and 2 to 6 are taken)
+ *     U(i)    = float(u(i)) / 65536                                         (exact)
+ *   per group:
+ *     lo, hi  = the minimum and the maximum of the group's elements (exact; -0 counts as below +0, so both are defined to the bit)
+ *     range   = hi - lo                                                     (one fp32 subtraction)
+ *     poisoned: an element is NaN or +-inf, or range is not finite.  Then lo = step = NaN (the canonical quiet NaN 0x7fc00000) and every
+ *               code is 0; every element of the group decodes to that NaN; other groups are untouched.
+ *     otherwise step = range / L and inv = range > 0 ? L / range : 0 (each ONE correctly rounded fp32 division); where L / range overflows
+ *               (range < L / FLT_MAX, about 7.5e-37 at 8 bits) inv = 0 as well: every element of such a group decodes to lo, within range.
+ *   per element:
+ *     t       = (x - lo) * inv                                              (two separate fp32 operations, never contracted)
+ *     code    = min(L, (uint)floor(t + U(i)))                               (one fp32 addition)
+ *     decode  = fma(float(code), step, lo), rounded once to the output dtype (a poisoned group: the canonical quiet NaN of that dtype)
+ * Hence |decode - x| <= step up to fp32 rounding, E[decode] = x up to the 2^-16 granularity of U, and a constant group decodes exactly.
+ *
+ * The buffer: fewbit_hipx_quant_bytes(n, k) = 8 ceil(n / 64) + k ceil(n / 8) bytes.  First the parameters, per group lo then step as fp32
+ * little-endian; then the codes, per 8 consecutive elements one little-endian word of k bytes with element j in bits [k j, k j + k).  The
+ * missing elements of the last word are 0.  The same arguments give the same bytes; the buffer does not depend on the source dtype beyond
+ * the values.
+ *
+ * fewbit_hipx_quant_bytes: the size above; 0 for bits other than 2, 4, 8 and for n outside 1 .. 2^36.
+ * fewbit_hipx_quant_pack_host / _unpack_host: the definition and the fp32 decode at HOST pointers; no device is touched.
+ * fewbit_hipx_quant_pack: ONE launch on `stream` (fewbit_amd/csrc/fewbit_quant.hip).
+ *   dtype, src   F32 / F16 / BF16; n elements, contiguous, aligned to the element.  With src 16-byte aligned a lane takes its 8 elements by
+ *                16-byte loads (one for the 16-bit types, two for fp32), otherwise and in the block that holds the tail element by element:
+ *                the same bytes either way.  No address at or beyond n elements is read.
+ *   seed, seed_device   as in fewbit_hipx_dropout: seed_device != NULL is an 8-byte aligned DEVICE word read when the kernel runs (`seed` is
+ *                ignored), so a launch recorded in a hipGraph rounds afresh on every replay
+ *   out, out_bytes   8-byte aligned, at least fewbit_hipx_quant_bytes(n, bits) bytes; nothing beyond that many bytes is written
+ * fewbit_hipx_quant_unpack: ONE launch on `stream`.
+ *   packed       the buffer of a pack call of the same n and bits, 8-byte aligned
+ *   out_dtype, out   F32 / F16 / BF16, independent of the dtype that was packed (under autocast a gradient's dtype differs from the input's);
+ *                n elements, aligned to the element; 16-byte stores where out is 16-byte aligned, element stores otherwise and in the tail
+ * No LDS, no workspace, no atomics, no read-back: the same arguments give the same bits.  The plan is a pure function of n: lanes take blocks
+ * of 8 elements, 8 neighbouring lanes hold a group (its minimum, maximum and poison flag are reduced across them by DPP lane moves, not through LDS), 256 lanes
+ * to a workgroup, at most 2048 workgroups (2^22 elements), beyond which each lane sweeps on by the width of the grid.
+ * Refused before anything is launched (FEWBIT_ERR_INVALID_ARGUMENT): an unknown dtype, bits other than 2, 4, 8, n beyond 2^36, a null or
+ * misaligned pointer, out_bytes below the size, a misaligned seed word.  n = 0: FEWBIT_OK, no launch. */
+size_t fewbit_hipx_quant_bytes(size_t n, int bits);
+int fewbit_hipx_quant_pack_host(const float *x_host, size_t n, int bits, uint64_t seed, uint8_t *out_host);
+int fewbit_hipx_quant_unpack_host(const uint8_t *packed_host, size_t n, int bits, float *out_host);
+int fewbit_hipx_quant_pack(int dtype, const void *src, size_t n, int bits, uint64_t seed, const uint64_t *seed_device, uint8_t *out, size_t out_bytes,
+                           void *stream);
+int fewbit_hipx_quant_unpack(const uint8_t *packed, size_t n, int bits, int out_dtype, void *out, void *stream);
 
 #ifdef __cplusplus
 }
