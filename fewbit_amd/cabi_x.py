@@ -1,6 +1,8 @@
 """ctypes binding of the companion library ``libfewbit_hipx.so`` (include/fewbit_hipx.h): the entry points added after the C-ABI
 of ``libfewbit_hip.so`` was frozen at version 5 (``cabi.SYMBOLS`` stays that list).  Same conventions as ``cabi``: device tensors,
-torch's current stream on the tensors' device, no fallback -- a missing library or an unsupported shape raises.
+torch's current stream on the tensors' device, no fallback -- a missing library or an unsupported shape raises.  What it binds: the sampled
+Fourier transform, the zero-extended and sign-flipped sampled transforms, the column sampling of LinearCRS, the moments of the variance
+estimator, the dropout of a seed, the packed form of a seed, and the layer norm that keeps the normalized rows of a seed.
 """
 import ctypes
 import os
@@ -15,7 +17,8 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'crs_count', 'crs_workspace_bytes', 'crs_gather', 'crs_scatter', 'sampled_rows_ceil', 'sampled_dct_zext', 'sampled_dct_zext_seeded',
            'sampled_dft_zext', 'sampled_dft_zext_seeded', 'sampled_signs', 'sampled_dct_signed', 'sampled_dft_signed', 'moments_workspace_bytes', 'row_moments', 'sum_squares',
            'DROPOUT_SWEEP', 'dropout_threshold', 'dropout_keep', 'dropout_apply', 'QUANT_BITS', 'QUANT_GROUP', 'QUANT_SWEEP', 'quant_bytes', 'quant_pack',
-           'quant_unpack', 'quant_pack_host', 'quant_unpack_host']
+           'quant_unpack', 'quant_pack_host', 'quant_unpack_host', 'NORM_MAX_WIDTH', 'norm_plan', 'norm_state_bytes', 'norm_workspace_bytes', 'norm_state_host',
+           'norm_state_unpack_host', 'layer_norm_forward', 'layer_norm_backward']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -28,7 +31,8 @@ SYMBOLS = ('fewbit_hipx_abi_version', 'fewbit_hipx_last_error', 'fewbit_hipx_sam
            'fewbit_hipx_sampled_dft_zext', 'fewbit_hipx_sampled_dft_zext_seeded', 'fewbit_hipx_moments_workspace', 'fewbit_hipx_row_moments',
            'fewbit_hipx_sum_squares', 'fewbit_hipx_dropout_threshold', 'fewbit_hipx_dropout_keep', 'fewbit_hipx_dropout', 'fewbit_hipx_sampled_signs',
            'fewbit_hipx_sampled_dct_signed', 'fewbit_hipx_sampled_dft_signed', 'fewbit_hipx_quant_bytes', 'fewbit_hipx_quant_pack_host',
-           'fewbit_hipx_quant_unpack_host', 'fewbit_hipx_quant_pack', 'fewbit_hipx_quant_unpack')
+           'fewbit_hipx_quant_unpack_host', 'fewbit_hipx_quant_pack', 'fewbit_hipx_quant_unpack', 'fewbit_hipx_norm_state_bytes', 'fewbit_hipx_norm_workspace',
+           'fewbit_hipx_norm_state_host', 'fewbit_hipx_norm_state_unpack_host', 'fewbit_hipx_layer_norm_forward', 'fewbit_hipx_layer_norm_backward')
 
 _lib = None
 
@@ -112,6 +116,19 @@ def lib() -> ctypes.CDLL:
         L.fewbit_hipx_quant_pack.argtypes = [i32, vp, sz, i32, u64, vp, vp, sz, vp]
         L.fewbit_hipx_quant_unpack.restype = i32
         L.fewbit_hipx_quant_unpack.argtypes = [vp, sz, i32, i32, vp, vp]
+        # the normalized rows of a seed (the layer norm): inside revision 2 as well, recognised by its symbols
+        L.fewbit_hipx_norm_state_bytes.restype = sz
+        L.fewbit_hipx_norm_state_bytes.argtypes = [sz, sz, i32]
+        L.fewbit_hipx_norm_workspace.restype = sz
+        L.fewbit_hipx_norm_workspace.argtypes = [sz, sz]
+        L.fewbit_hipx_norm_state_host.restype = i32
+        L.fewbit_hipx_norm_state_host.argtypes = [vp, sz, sz, i32, u64, vp]
+        L.fewbit_hipx_norm_state_unpack_host.restype = i32
+        L.fewbit_hipx_norm_state_unpack_host.argtypes = [vp, sz, sz, i32, vp]
+        L.fewbit_hipx_layer_norm_forward.restype = i32
+        L.fewbit_hipx_layer_norm_forward.argtypes = [i32, vp, sz, sz, vp, vp, dbl, i32, u64, vp, vp, vp, vp, sz, vp, vp]
+        L.fewbit_hipx_layer_norm_backward.restype = i32
+        L.fewbit_hipx_layer_norm_backward.argtypes = [i32, vp, vp, vp, vp, sz, sz, i32, vp, vp, vp, vp, sz, vp]
         _lib = L
     return _lib
 
@@ -507,3 +524,152 @@ def quant_unpack(packed: torch.Tensor, n: int, bits: int, dtype: torch.dtype, ou
         _same_device(packed, out)
         _check(lib().fewbit_hipx_quant_unpack(packed.data_ptr(), n, bits, DTYPES[dtype], out.data_ptr(), _stream(stream, packed.device)))
     return out
+
+
+# ---- the layer norm that keeps its normalized rows in 2, 4 or 8 bits (fewbit_amd/csrc/fewbit_norm.hip): what QuantizedLayerNorm keeps ---------------
+NORM_MAX_WIDTH = 8192                           # the widest row the kernels take
+
+
+def norm_plan(width: int) -> Tuple[int, int]:
+    """(lanes per row, blocks of 8 elements per lane) of the forward kernel at ``width``: the thresholds of ``plan_of`` in fewbit_norm.hip, restated
+    for the tests that stand on both sides of each.  256 / lanes rows share a forward workgroup, at most 16384 of which are launched; beyond
+    that a workgroup walks on by the width of the grid.  Backward has the same thresholds: its workgroups have 1024 lanes, one block per lane
+    (512 lanes per row beyond 2048 elements, 1024 beyond 4096), and there are at most 512 of them."""
+    for limit, plan in ((64, (8, 1)), (128, (16, 1)), (512, (64, 1)), (1024, (128, 1)), (2048, (256, 1)), (4096, (256, 2))):
+        if width <= limit:
+            return plan
+    return 256, 4
+
+
+def norm_state_bytes(rows: int, width: int, bits: int) -> int:
+    """Bytes of the state of a ``rows x width`` layer norm at ``bits`` bits: ``rows * (8 * ceil(width / 64) + C)`` with ``C = bits * ceil(width / 8)``
+    rounded up to a multiple of 4; 0 for ``bits`` other than 2, 4, 8, a width outside 1 .. 8192, no rows and ``rows * width`` beyond 2^36."""
+    if rows < 0 or width < 0:
+        return 0
+    return lib().fewbit_hipx_norm_state_bytes(rows, width, bits)
+
+
+def norm_workspace_bytes(rows: int, width: int) -> int:
+    """bytes of scratch ``layer_norm_backward`` needs for ``dgamma`` / ``dbeta`` (0: no kernel for this shape)"""
+    if rows < 0 or width < 0:
+        return 0
+    return lib().fewbit_hipx_norm_workspace(rows, width)
+
+
+def _norm_size(rows: int, width: int, bits: int, name: str) -> int:
+    if bits not in QUANT_BITS:
+        raise FewbitHipError(f'{name}: bits must be 2, 4 or 8 (got {bits})')
+    need = norm_state_bytes(rows, width, bits)
+    if rows != 0 and need == 0:
+        raise FewbitHipError(f'{name}: no state for {rows} rows of {width} elements (widths 1 .. {NORM_MAX_WIDTH}, rows * width <= 2^36)')
+    return need
+
+
+def norm_state_host(xhat: torch.Tensor, seed: int, bits: int) -> torch.Tensor:
+    """The state ``layer_norm_forward`` writes for ``seed``, evaluated on the host from given normalized rows ``xhat`` (2-D, taken as contiguous
+    fp32): a host uint8 tensor of ``norm_state_bytes`` bytes.  The definition is include/fewbit_hipx.h's ("the normalized rows of a seed"): the
+    packed form of a seed with groups and blocks per row; for a width that is a multiple of 64, ``quant_pack_host(xhat.flatten(), seed, bits)``."""
+    if xhat.dim() != 2:
+        raise FewbitHipError(f'xhat must be 2-D (got {xhat.dim()} dimensions)')
+    x = xhat.detach().to(device='cpu', dtype=torch.float32).contiguous()
+    rows, width = x.shape
+    if rows and not 1 <= width <= NORM_MAX_WIDTH:
+        _check(lib().fewbit_hipx_norm_state_host(None, rows, width, bits, 0, None))        # (the library words the refusal)
+    out = torch.empty(_norm_size(rows, width, bits, 'norm_state_host'), dtype=torch.uint8)
+    _check(lib().fewbit_hipx_norm_state_host(x.data_ptr(), rows, width, bits, seed & 0xffffffffffffffff, out.data_ptr()))
+    return out
+
+
+def norm_state_unpack_host(state: torch.Tensor, rows: int, width: int, bits: int) -> torch.Tensor:
+    """The fp32 decode of a state on the host: a float32 tensor ``rows x width`` (``fma(code, step, lo)``; a poisoned group: NaN)"""
+    need = _norm_size(rows, width, bits, 'norm_state_unpack_host')
+    if state.device.type != 'cpu' or state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < need:
+        raise FewbitHipError(f'state must be a contiguous host uint8 tensor of at least {need} bytes')
+    out = torch.empty((rows, width), dtype=torch.float32)
+    _check(lib().fewbit_hipx_norm_state_unpack_host(state.data_ptr(), rows, width, bits, out.data_ptr()))
+    return out
+
+
+def _norm_rows(t: torch.Tensor, what: str) -> Tuple[int, int]:
+    if t.device.type != 'cuda':
+        raise FewbitHipError(f'{what} must live on the GPU (got {t.device})')
+    if t.dtype not in DTYPES:
+        raise FewbitHipError(f'unsupported dtype {t.dtype}')
+    if t.dim() != 2 or not t.is_contiguous():
+        raise FewbitHipError(f'{what} must be a contiguous 2-D tensor')
+    return t.shape
+
+
+def _norm_vector(t: Optional[torch.Tensor], like: torch.Tensor, what: str) -> Optional[int]:
+    if t is None:
+        return None
+    if t.dtype != like.dtype or t.numel() != like.shape[1] or not t.is_contiguous():
+        raise FewbitHipError(f'{what} must be a contiguous tensor of {like.shape[1]} elements of {like.dtype}')
+    return t.data_ptr()
+
+
+def _norm_out(t: Optional[torch.Tensor], shape, dtype: torch.dtype, device, what: str) -> torch.Tensor:
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise FewbitHipError(f'{what} must be a contiguous {" x ".join(map(str, shape))} tensor of {dtype}')
+    return t
+
+
+def layer_norm_forward(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float, bits: int = 4, seed=0, keep: bool = True,
+                       want_xhat: bool = False, y: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
+                       xhat: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """The layer norm of the rows of ``x`` (contiguous, 2-D, fp32 / fp16 / bf16, on the GPU; ``gamma`` / ``beta``: its dtype, or None) in ONE
+    launch -> ``(y, rstd, state, xhat)``: ``y`` in the dtype of ``x``; ``rstd`` one fp32 per row; ``state`` the normalized rows in ``bits`` bits
+    rounded with ``seed`` (a uint8 tensor of ``norm_state_bytes`` bytes; ``norm_state_host`` gives the same bytes from ``xhat``); ``xhat`` the
+    fp32 normalized rows the kernel quantized, only with ``want_xhat`` (else None).  ``keep=False``: the plain forward, ``state`` is None and
+    nothing but ``y`` and ``rstd`` is written -- the same bytes as with a state.  ``seed``: an int, or a one-element int64 tensor on the device
+    of ``x`` that is read when the kernel runs (``cabi.next_sketch_seed``).  ``y``, ``rstd``, ``state``, ``xhat``: buffers to write into."""
+    rows, width = _norm_rows(x, 'x')
+    gp, bp = _norm_vector(gamma, x, 'gamma'), _norm_vector(beta, x, 'beta')
+    need = _norm_size(rows, width, bits, 'layer_norm_forward') if keep else 0
+    value, word, others = _seed_arguments(seed) if keep else (0, None, ())
+    with _on(x.device):
+        y = _norm_out(y, (rows, width), x.dtype, x.device, 'y')
+        rstd = _norm_out(rstd, (rows, ), torch.float32, x.device, 'rstd')
+        if keep and state is None:
+            state = torch.empty(need, dtype=torch.uint8, device=x.device)
+        elif keep and (state.dtype != torch.uint8 or state.dim() != 1 or not state.is_contiguous()):
+            raise FewbitHipError('state must be a contiguous 1-D uint8 tensor')
+        elif not keep:
+            state = None
+        if want_xhat or xhat is not None:
+            xhat = _norm_out(xhat, (rows, width), torch.float32, x.device, 'xhat')
+        _same_device(x, y, rstd, *others, *(t for t in (gamma, beta, state, xhat) if t is not None))
+        _check(lib().fewbit_hipx_layer_norm_forward(DTYPES[x.dtype], x.data_ptr(), rows, width, gp, bp, float(eps), bits, value, word, y.data_ptr(), rstd.data_ptr(),
+                                                    None if state is None else state.data_ptr(), 0 if state is None else state.numel(),
+                                                    None if xhat is None else xhat.data_ptr(), _stream(stream, x.device)))
+    return y, rstd, state, xhat
+
+
+def layer_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor], bits: int, want=(True, True, True),
+                        dx: Optional[torch.Tensor] = None, dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None,
+                        workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """The gradients of a layer norm from its state (``layer_norm_forward``) and ``gy`` (contiguous, 2-D, fp32 / fp16 / bf16; ``gamma``: its dtype,
+    or None) -> ``(dx, dgamma, dbeta)``: ``dx`` in the dtype of ``gy``, ``dgamma`` and ``dbeta`` as fp32 of ``width`` elements; where ``want`` is
+    False the output is None and nothing of it is computed or written.  Two launches (one when neither sum is wanted), fp32 arithmetic, a fixed
+    order of every sum: the same arguments give the same bits.  ``workspace``: a uint8 tensor of ``norm_workspace_bytes(rows, width)`` bytes."""
+    rows, width = _norm_rows(gy, 'gy')
+    gp = _norm_vector(gamma, gy, 'gamma')
+    need = _norm_size(rows, width, bits, 'layer_norm_backward')
+    if state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < need:
+        raise FewbitHipError(f'state must be a contiguous uint8 tensor of at least {need} bytes')
+    if rstd.dtype != torch.float32 or rstd.numel() != rows or not rstd.is_contiguous():
+        raise FewbitHipError(f'rstd must be a contiguous float32 tensor of {rows} elements')
+    want_dx, want_dgamma, want_dbeta = want
+    with _on(gy.device):
+        dx = _norm_out(dx, (rows, width), gy.dtype, gy.device, 'dx') if want_dx else None
+        dgamma = _norm_out(dgamma, (width, ), torch.float32, gy.device, 'dgamma') if want_dgamma else None
+        dbeta = _norm_out(dbeta, (width, ), torch.float32, gy.device, 'dbeta') if want_dbeta else None
+        if (want_dgamma or want_dbeta) and workspace is None:
+            workspace = torch.empty(norm_workspace_bytes(rows, width), dtype=torch.uint8, device=gy.device)
+        _same_device(gy, state, rstd, *(t for t in (gamma, dx, dgamma, dbeta, workspace) if t is not None))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _check(lib().fewbit_hipx_layer_norm_backward(DTYPES[gy.dtype], gy.data_ptr(), state.data_ptr(), rstd.data_ptr(), gp, rows, width, bits, ptr(dx), ptr(dgamma),
+                                                     ptr(dbeta), ptr(workspace), 0 if workspace is None else workspace.numel(), _stream(stream, gy.device)))
+    return dx, dgamma, dbeta

@@ -23,6 +23,7 @@
 
 #include "fewbit_hipx.h"
 #include "fewbit_philox.h"
+#include "fewbit_quantdef.h"
 
 #pragma clang fp contract(off)
 
@@ -35,165 +36,18 @@ FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(pri
 namespace quant {
 
 using dft::fail;
-using sketch::Key;
 
-constexpr uint32_t kRoundDomain = 7u;       // counter word 3 (0 and 2: the dense sketches, 3: the sampled rows, 4: the CRS columns, 5: the dropout, 6: the signs)
-constexpr int kThreads = 256, kBlock = 8;   // lanes per workgroup; elements per Philox call and per code word
-constexpr int kGroup = 64, kLanes = kGroup / kBlock;   // elements per group; lanes that hold one
+// (the definition itself -- lo, step, inv, code_of, decode, the poison rule, the rounding bits -- and the lane moves: fewbit_quantdef.h, the
+// text fewbit_norm.hip evaluates too)
+constexpr int kThreads = 256;               // lanes per workgroup
 constexpr size_t kMaxGroups = 2048;         // one sweep of the grid: kMaxGroups * kThreads * kBlock = 2^22 elements
 constexpr size_t kMaxCount = size_t{1} << 36;
-constexpr uint32_t kNaN = 0x7fc00000u;      // what a poisoned group stores for lo and step, and decodes to
 
 static_assert(kThreads % kLanes == 0, "a group's lanes never straddle two sweeps of the grid");
 
-// ---- the definition, one element or one group at a time: host and device evaluate these very functions --------------------------------------
-// each is ONE correctly rounded fp32 operation (the device intrinsics keep the compiler from contracting a pair of them; the host is
-// compiled with contraction off)
-__host__ __device__ __forceinline__ float sub_rn(float a, float b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fsub_rn(a, b);
-#else
-    return a - b;
-#endif
-}
-__host__ __device__ __forceinline__ float mul_rn(float a, float b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fmul_rn(a, b);
-#else
-    return a * b;
-#endif
-}
-__host__ __device__ __forceinline__ float add_rn(float a, float b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fadd_rn(a, b);
-#else
-    return a + b;
-#endif
-}
-__host__ __device__ __forceinline__ float div_rn(float a, float b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fdiv_rn(a, b);
-#else
-    return a / b;
-#endif
-}
-__host__ __device__ __forceinline__ float fma_rn(float a, float b, float c) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fmaf_rn(a, b, c);
-#else
-    return std::fmaf(a, b, c);
-#endif
-}
-
-__host__ __device__ __forceinline__ uint32_t bits_of_float(float v) { return __builtin_bit_cast(uint32_t, v); }
-__host__ __device__ __forceinline__ float float_of_bits(uint32_t b) { return __builtin_bit_cast(float, b); }
-
-// the order of the reals on the bits of a finite float, -0 below +0, as a signed integer (its own inverse)
-__host__ __device__ __forceinline__ int32_t order_key(uint32_t bits) {
-    return static_cast<int32_t>(bits ^ (static_cast<uint32_t>(static_cast<int32_t>(bits) >> 31) & 0x7fffffffu));
-}
-__host__ __device__ __forceinline__ bool non_finite(uint32_t bits) { return (bits & 0x7f800000u) == 0x7f800000u; }
-
-// the 16 bits of element e of a block (the dropout's choice: word e >> 1, low half for even e, high half for odd e) as U in [0, 1)
-__host__ __device__ __forceinline__ float uniform_of(const uint32_t (&w)[4], int e) {
-    return static_cast<float>((w[e >> 1] >> (16 * (e & 1))) & 0xffffu) * (1.0f / 65536.0f);             // (both exact)
-}
-__host__ __device__ __forceinline__ void block_words(uint64_t q, Key key, uint32_t (&w)[4]) {
-    sketch::philox4x32(static_cast<uint32_t>(q), static_cast<uint32_t>(q >> 32), 0u, kRoundDomain, key, w);
-}
-
-struct Params { float lo, step, inv; bool poisoned; };
-
-// from the keys of a group's minimum and maximum and whether it holds a NaN or an infinity
-__host__ __device__ __forceinline__ Params params_of(int32_t kmin, int32_t kmax, bool bad, float levels) {
-    Params p;
-    p.lo = float_of_bits(static_cast<uint32_t>(order_key(static_cast<uint32_t>(kmin))));
-    const float hi = float_of_bits(static_cast<uint32_t>(order_key(static_cast<uint32_t>(kmax))));
-    const float range = sub_rn(hi, p.lo);
-    p.poisoned = bad || non_finite(bits_of_float(range));
-    if (p.poisoned) {
-        p.lo = p.step = float_of_bits(kNaN);
-        p.inv = 0.0f;
-        return p;
-    }
-    p.step = div_rn(range, levels);
-    const float inv = range > 0.0f ? div_rn(levels, range) : 0.0f;
-    p.inv = non_finite(bits_of_float(inv)) ? 0.0f : inv;              // (a range below L / FLT_MAX: every code is 0, see the header)
-    return p;
-}
-__host__ __device__ __forceinline__ uint32_t code_of(float x, const Params &p, float u, uint32_t levels) {
-    if (p.poisoned) return 0u;
-    const float t = mul_rn(sub_rn(x, p.lo), p.inv);
-    const uint32_t c = static_cast<uint32_t>(floorf(add_rn(t, u)));    // (0 <= t + u < L + 2: the conversion is exact)
-    return c < levels ? c : levels;
-}
-__host__ __device__ __forceinline__ float decode(uint32_t code, float lo, float step) {
-    if (step != step) return float_of_bits(kNaN);
-    return fma_rn(static_cast<float>(code), step, lo);
-}
-
-inline bool known_dtype(int dtype) { return dtype == FEWBIT_F32 || dtype == FEWBIT_F16 || dtype == FEWBIT_BF16; }
-inline bool known_bits(int bits) { return bits == 2 || bits == 4 || bits == 8; }
-inline size_t size_of(int dtype) { return dtype == FEWBIT_F32 ? 4 : 2; }
 inline size_t bytes_of(size_t n, int bits) {
     if (!known_bits(bits) || n == 0 || n > kMaxCount) return 0;
     return 8 * ((n + kGroup - 1) / kGroup) + static_cast<size_t>(bits) * ((n + kBlock - 1) / kBlock);
-}
-
-template <int DT> struct Elem { using type = uint16_t; };
-template <> struct Elem<FEWBIT_F32> { using type = uint32_t; };
-
-template <int DT> __device__ __forceinline__ uint32_t widen(typename Elem<DT>::type raw) {              // the bits of the element as fp32 (exact)
-    if constexpr (DT == FEWBIT_F32) return raw;
-    else if constexpr (DT == FEWBIT_BF16) return static_cast<uint32_t>(raw) << 16;
-    else return bits_of_float(static_cast<float>(__builtin_bit_cast(_Float16, raw)));
-}
-// round to nearest even, as torch's conversions do (a NaN becomes the canonical quiet NaN of the format)
-template <int DT> __device__ __forceinline__ typename Elem<DT>::type narrow(float v) {
-    if constexpr (DT == FEWBIT_F32) return bits_of_float(v);
-    else if constexpr (DT == FEWBIT_BF16) {
-        const uint32_t bits = bits_of_float(v);
-        if (v != v) return static_cast<uint16_t>(0x7fc0u);
-        return static_cast<uint16_t>((bits + 0x7fffu + ((bits >> 16) & 1u)) >> 16);
-    } else {
-        // (left to itself the compiler folds the fma and the rounding to fp16 into one v_fma_mix*, which rounds the exact result once)
-        asm("" : "+v"(v));
-        return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v));
-    }
-}
-
-template <int DT> __device__ __forceinline__ void load8(const typename Elem<DT>::type *p, typename Elem<DT>::type (&v)[kBlock]) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(p);
-    if constexpr (DT == FEWBIT_F32) {
-        const uint4 a = q[0], b = q[1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else {
-        const uint4 a = q[0];
-        const uint32_t w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-        for (int e = 0; e < kBlock; ++e) v[e] = static_cast<uint16_t>(w[e >> 1] >> (16 * (e & 1)));
-    }
-}
-template <int DT> __device__ __forceinline__ void store8(typename Elem<DT>::type *p, const typename Elem<DT>::type (&v)[kBlock]) {
-    uint4 *q = reinterpret_cast<uint4 *>(p);
-    if constexpr (DT == FEWBIT_F32) {
-        q[0] = uint4{v[0], v[1], v[2], v[3]};
-        q[1] = uint4{v[4], v[5], v[6], v[7]};
-    } else {
-        q[0] = uint4{v[0] | static_cast<uint32_t>(v[1]) << 16, v[2] | static_cast<uint32_t>(v[3]) << 16, v[4] | static_cast<uint32_t>(v[5]) << 16,
-                     v[6] | static_cast<uint32_t>(v[7]) << 16};
-    }
-}
-
-// Data-parallel-primitive moves inside a row of 16 lanes (no LDS crossbar): quad_perm [1, 0, 3, 2], quad_perm [2, 3, 0, 1], row_half_mirror.
-// The eight lanes of a group are active together, so every source lane is.
-constexpr int kSwapPairs = 0xB1, kSwapHalves = 0x4E, kMirrorEight = 0x141;
-template <int CTRL> __device__ __forceinline__ int lane_move(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
-template <int CTRL> __device__ __forceinline__ void reduce_step(int32_t &kmin, int32_t &kmax, uint32_t &bad) {
-    const int32_t omin = lane_move<CTRL>(kmin), omax = lane_move<CTRL>(kmax);
-    bad |= static_cast<uint32_t>(lane_move<CTRL>(static_cast<int>(bad)));
-    kmin = omin < kmin ? omin : kmin;
-    kmax = omax > kmax ? omax : kmax;
 }
 
 // VEC: src is 16-byte aligned, so every whole block is.  out: 8-byte aligned; the parameters of group g at 8 g, the code word of block b at

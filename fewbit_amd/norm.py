@@ -1,0 +1,209 @@
+"""LayerNorm that keeps its normalized input in 2, 4 or 8 bits per element for backward.
+
+``torch.nn.LayerNorm`` saves its whole input plus a mean and an rstd per row, and in a transformer that input is the residual sum, which no
+other node saves.  Here the node keeps the NORMALIZED rows ``x^ = (x - mean) * rstd`` in the packed form of a seed (include/fewbit_hipx.h, "the
+normalized rows of a seed": per 64 elements of a row a minimum and a step, per element a code rounded stochastically and without bias) plus
+one fp32 ``rstd`` per row: at 4 bits 0.3125 of a bf16 input's bytes.  ``x^`` is close to N(0, 1) in every row, the distribution a min / step
+code per 64 elements suits best, and backward needs nothing else but gamma.
+
+* The forward value is the exact layer norm; only the gradients see the rounding.  ``dgamma = sum_r gy * x^q`` is unbiased (``E[x^q] = x^``);
+  ``dbeta`` is exact.  ``dx = rstd * (g^ - mean(g^) - x^q * mean(g^ * x^q))`` with ``g^ = gy * gamma`` is NOT exactly unbiased: ``x^q`` enters it
+  twice, so ``E[dx_q] - dx = -rstd * g^_i * Var(x^q_i) / width``, second order in the step and divided by the width (tests/test_norm_host.py
+  measures the sum of both against the noise of one call).
+* The kernels (fewbit_amd/csrc/fewbit_norm.hip: one launch forward, two backward) serve fp32 / fp16 / bf16 GPU tensors with a flattened
+  normalized width of 1 .. 8192 and gamma / beta of the input's dtype (or absent) while ``linear.use_native_sketch()`` is on.  Host tensors,
+  float64, wider rows and ``use_native_sketch(False)`` take a PyTorch formulation of the same definition: ``y`` is ``F.layer_norm``'s, the codes
+  come from ``linear._quantize_groups`` on the rows of ``x^`` padded to whole groups, backward is the formula above.
+* The seed comes from ``linear._sketch_seed``: an int drawn from the host generator, or a device word while the stream is being captured into
+  a hipGraph -- a captured layer draws fresh roundings on every replay and its recorded backward reads the state its forward wrote.  (One eager
+  call on the device precedes a capture, as for the randomized linears.)
+* With grad mode off, or when neither the input nor gamma nor beta requires grad, the call is the plain forward: no seed is drawn, no state
+  is written, no node is built; on the kernel path ``y`` has the bytes of the keeping call.
+* Under ``torch.autocast`` the output of the kernel path keeps the INPUT's dtype (the arithmetic inside is fp32 whatever the dtype, fp32
+  parameters are cast to the input's dtype first); torch's ``layer_norm`` would return fp32 there.  Backward runs under the autocast state
+  the forward saw (``linear._autocast_as``), so ``backward()`` may follow the block.
+* Inside ``torch.utils.checkpoint`` the generator must be a default one (``generator=None``, ``torch.default_generator``,
+  ``torch.cuda.default_generators[i]``): checkpoint saves and restores only those, and the recomputation must draw the forward's seed again.
+* A row with a NaN or an infinity gives NaN in that row of ``y`` and ``dx`` and in every column of ``dgamma``, as with torch.
+* Not differentiable twice (``once_differentiable``).
+"""
+import math
+from typing import Optional, Sequence, Union
+
+import torch
+import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
+
+from . import linear
+
+__all__ = ('layer_norm_quantized', 'QuantizedLayerNorm')
+
+_KERNEL_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+_MAX_WIDTH = 8192                                # cabi_x.NORM_MAX_WIDTH
+_GROUP = 64                                      # elements of a row that share one (lo, step) pair
+
+
+def _kernel_applies(flat: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor]) -> bool:
+    if not (linear.use_native_sketch() and flat.device.type == 'cuda' and flat.dtype in _KERNEL_DTYPES and 1 <= flat.shape[1] <= _MAX_WIDTH
+            and 0 < flat.numel() <= 2**36):
+        return False
+    # (under autocast fp32 parameters meet a 16-bit input: they are cast to it, a copy of `width` elements)
+    cast = torch.is_autocast_enabled('cuda')
+    return all(p is None or (p.device == flat.device and (p.dtype == flat.dtype or (cast and p.dtype in _KERNEL_DTYPES))) for p in (weight, bias))
+
+
+def _as(p: Optional[torch.Tensor], dtype: torch.dtype) -> Optional[torch.Tensor]:
+    return None if p is None else p.detach().reshape(-1).to(dtype).contiguous()
+
+
+def _normalized_rows(flat: torch.Tensor, eps: float):
+    """(x^, rstd) of the rows of ``flat`` in fp32 (fp64 for a float64 input), the two-pass variance of the definition"""
+    work = flat.to(torch.float64 if flat.dtype == torch.float64 else torch.float32)
+    centred = work - work.mean(dim=1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(centred.square().mean(dim=1, keepdim=True) + eps)
+    return centred * rstd, rstd.reshape(-1)
+
+
+def _padded_rows(xhat: torch.Tensor) -> torch.Tensor:
+    """the rows filled up to whole groups with their last element, which moves neither a group's minimum nor its maximum"""
+    pad = -xhat.shape[1] % _GROUP
+    return torch.cat((xhat, xhat[:, -1:].expand(-1, pad)), dim=1) if pad else xhat
+
+
+def _decoded_rows(codes: torch.Tensor, lo: torch.Tensor, step: torch.Tensor, rows: int, width: int) -> torch.Tensor:
+    values = torch.addcmul(lo[:, None], codes.view(-1, _GROUP).to(lo.dtype), step[:, None])
+    return values.view(rows, -1)[:, :width]
+
+
+def _backward_formula(gy: torch.Tensor, xq: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor]):
+    """(dx, dgamma, dbeta) of the definition in the dtype of ``xq``"""
+    gy = gy.to(xq.dtype)
+    gh = gy if gamma is None else gy * gamma.reshape(1, -1).to(xq.dtype)
+    dx = rstd[:, None] * (gh - gh.mean(dim=1, keepdim=True) - xq * (gh * xq).mean(dim=1, keepdim=True))
+    return dx, (gy * xq).sum(dim=0), gy.sum(dim=0)
+
+
+class _LayerNormQuantized(torch.autograd.Function):
+    """``F.layer_norm`` that keeps ``x^`` in ``bits`` bits per element (module docstring).  Kept for backward on the kernels: ONE uint8 buffer
+    (the state), ``rstd`` (fp32 per row) and gamma; in the PyTorch formulation the codes (one per byte), lo and step of every group, ``rstd``
+    and gamma."""
+
+    @staticmethod
+    def forward(ctx, input, weight, bias, normalized_shape, eps: float, bits: int, generator):
+        width = math.prod(normalized_shape)
+        flat = input.detach().reshape(-1, width)
+        ctx.bits, ctx.flat_shape, ctx.input_dtype = bits, tuple(flat.shape), input.dtype
+        ctx.has_weight, ctx.normalized_shape, ctx.bias_dtype = weight is not None, tuple(normalized_shape), None if bias is None else bias.dtype
+        ctx.autocast = linear._autocast_seen(input.device.type)
+        ctx.native_seed = None
+        if _kernel_applies(flat, weight, bias):
+            from . import cabi_x
+            ctx.native_seed = linear._sketch_seed(generator, flat.device)
+            y, rstd, state, _ = cabi_x.layer_norm_forward(flat if flat.is_contiguous() else flat.contiguous(), _as(weight, flat.dtype), _as(bias, flat.dtype),
+                                                           eps, bits, ctx.native_seed)
+            ctx.save_for_backward(state, rstd, *((weight, ) if ctx.has_weight else ()))
+            return y.view(input.shape)
+        xhat, rstd = _normalized_rows(flat, eps)
+        ctx.save_for_backward(*linear._quantize_groups(_padded_rows(xhat), bits, generator), rstd, *((weight, ) if ctx.has_weight else ()))
+        return F.layer_norm(input, normalized_shape, weight, bias, eps)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        with linear._autocast_as(ctx.autocast):
+            return _LayerNormQuantized._backward(ctx, linear._dense_rows(grad_output))
+
+    @staticmethod
+    def _backward(ctx, grad_output):
+        saved = ctx.saved_tensors                       # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
+        weight = saved[-1] if ctx.has_weight else None
+        rows, width = ctx.flat_shape
+        gy = grad_output.reshape(rows, width)
+        want = tuple(ctx.needs_input_grad[:3])
+        if ctx.native_seed is not None:
+            from . import cabi_x
+            gy = gy if gy.dtype in _KERNEL_DTYPES else gy.float()
+            dx, dgamma, dbeta = cabi_x.layer_norm_backward(gy, saved[0], saved[1], _as(weight, gy.dtype), ctx.bits, want)
+        else:
+            codes, lo, step, rstd = saved[:4]
+            dx, dgamma, dbeta = _backward_formula(gy, _decoded_rows(codes, lo, step, rows, width), rstd, weight)
+        grad_input = dx.to(ctx.input_dtype).view(grad_output.shape) if want[0] else None
+        grad_weight = dgamma.to(weight.dtype).view(weight.shape) if want[1] else None
+        grad_bias = dbeta.to(ctx.bias_dtype).view(ctx.normalized_shape) if want[2] else None
+        return grad_input, grad_weight, grad_bias, None, None, None, None
+
+
+def layer_norm_quantized(input: torch.Tensor, normalized_shape: Union[int, Sequence[int]], weight: Optional[torch.Tensor] = None,
+                         bias: Optional[torch.Tensor] = None, eps: float = 1e-5, bits: int = 4, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """``F.layer_norm(input, normalized_shape, weight, bias, eps)`` that keeps the normalized rows in ``bits`` = 2, 4 or 8 bits per element
+    (plus one fp32 ``rstd`` per row) instead of the input: the output is the exact layer norm, ``grad_bias`` is exact, ``grad_weight`` is
+    unbiased, ``grad_input`` carries a bias of second order in the rounding step (module docstring).  ``generator``: the source of the
+    rounding's randomness; without it the host default generator seeds every call.  Grad mode off, or nothing that requires grad: the plain
+    forward -- no seed is drawn and nothing is kept.  Under ``torch.autocast`` the kernel path returns the INPUT's dtype where torch returns
+    fp32.  Inside ``torch.utils.checkpoint`` ``generator`` must be a default one (``None`` included): checkpoint restores only those, and the
+    recomputation must draw the forward's seed again (module docstring)."""
+    if bits not in linear.QUANT_BITS:
+        raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+    normalized_shape = (normalized_shape, ) if isinstance(normalized_shape, int) else tuple(normalized_shape)
+    if tuple(input.shape[input.dim() - len(normalized_shape):]) != normalized_shape or not normalized_shape:
+        return F.layer_norm(input, normalized_shape, weight, bias, eps)                   # (torch words the refusal)
+    if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (input, weight, bias)):
+        flat = input.detach().reshape(-1, math.prod(normalized_shape))
+        if not _kernel_applies(flat, weight, bias):
+            return F.layer_norm(input, normalized_shape, weight, bias, eps)
+        from . import cabi_x
+        y, _, _, _ = cabi_x.layer_norm_forward(flat if flat.is_contiguous() else flat.contiguous(), _as(weight, flat.dtype), _as(bias, flat.dtype), eps,
+                                               keep=False)
+        return y.view(input.shape)
+    return _LayerNormQuantized.apply(input, weight, bias, normalized_shape, float(eps), int(bits), generator)
+
+
+class QuantizedLayerNorm(torch.nn.LayerNorm):
+    r"""Drop-in :class:`torch.nn.LayerNorm` that keeps its normalized input in ``bits`` bits per element, plus one fp32 per row, instead of the
+    input itself (:func:`layer_norm_quantized`); the output is that of ``nn.LayerNorm``.
+
+    Parameters (after those of ``nn.LayerNorm``)
+    ----------
+    bits : {2, 4, 8}, default=4
+        Bits per kept element.  Groups of 64 elements of a row share a minimum and a step (8 more bytes per group): a bf16 input is kept in
+        0.1875, 0.3125 or 0.5625 of its bytes.  The rounding is stochastic; the weight gradient is unbiased, the input gradient up to a term of
+        second order in the step.
+    generator : torch.Generator, optional
+        Source of the rounding's randomness; without it the host default generator seeds every call.  Inside ``torch.utils.checkpoint`` the
+        generator must be a default one (``None``, ``torch.default_generator``, ``torch.cuda.default_generators[i]``): checkpoint saves and
+        restores only those, so a generator of the caller's own draws a second seed in the recomputation and the gradients no longer belong to
+        the rounding of the forward.
+
+    Under ``torch.autocast`` the output keeps the input's dtype on the kernel path (``nn.LayerNorm`` returns fp32 there).  ``m.eval()`` keeps no
+    state and draws no seed: without gradients the call is the plain forward (the same output bytes as in training), and gradients asked for
+    in eval mode are ``F.layer_norm``'s exact ones.
+
+    Examples:
+
+        >>> m = fewbit.QuantizedLayerNorm(768, bits=4)
+        >>> model = fewbit.map_module(model, lambda m, path: fewbit.QuantizedLayerNorm.from_layer_norm(m, bits=4) if type(m) is torch.nn.LayerNorm else m)
+    """
+
+    def __init__(self, normalized_shape, eps: float = 1e-5, elementwise_affine: bool = True, bias: bool = True, device=None, dtype=None, bits: int = 4,
+                 generator: Optional[torch.Generator] = None) -> None:
+        if bits not in linear.QUANT_BITS:
+            raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+        super().__init__(normalized_shape, eps, elementwise_affine, bias, device, dtype)
+        self.bits = bits
+        self.generator = generator
+
+    @classmethod
+    def from_layer_norm(cls, module: torch.nn.LayerNorm, bits: int = 4, generator: Optional[torch.Generator] = None) -> 'QuantizedLayerNorm':
+        """A ``QuantizedLayerNorm`` that SHARES the parameters of ``module`` (what ``map_module`` needs to swap the norms of a built model)"""
+        new = cls(module.normalized_shape, module.eps, module.elementwise_affine, module.bias is not None, device='meta', bits=bits, generator=generator)
+        new.weight, new.bias = module.weight, module.bias
+        return new.train(module.training)
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        if not self.training and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, self.weight, self.bias)):
+            # eval mode is not where activation memory is short: gradients asked for there are torch's exact ones, nothing is rounded or drawn
+            return F.layer_norm(input, self.normalized_shape, self.weight, self.bias, self.eps)
+        return layer_norm_quantized(input, self.normalized_shape, self.weight, self.bias, self.eps, self.bits, self.generator)
+
+    def extra_repr(self) -> str:
+        return f'{super().extra_repr()}, bits={self.bits}'

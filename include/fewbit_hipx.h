@@ -36,7 +36,9 @@ extern "C" {
  * So were the sampled transforms with the signs of a seed (fewbit_hipx_sampled_signs, _sampled_dct_signed, _sampled_dft_signed): inside
  * revision 2, recognised by the presence of the symbols.
  * So was the packed form of a seed (fewbit_hipx_quant_bytes, _quant_pack_host, _quant_unpack_host, _quant_pack, _quant_unpack): inside
- * revision 2, recognised by the presence of the symbols. */
+ * revision 2, recognised by the presence of the symbols.
+ * So were the normalized rows of a seed (fewbit_hipx_norm_state_bytes, _norm_workspace, _norm_state_host, _norm_state_unpack_host,
+ * _layer_norm_forward, _layer_norm_backward): inside revision 2, recognised by the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -305,6 +307,74 @@ int fewbit_hipx_quant_unpack_host(const uint8_t *packed_host, size_t n, int bits
 int fewbit_hipx_quant_pack(int dtype, const void *src, size_t n, int bits, uint64_t seed, const uint64_t *seed_device, uint8_t *out, size_t out_bytes,
                            void *stream);
 int fewbit_hipx_quant_unpack(const uint8_t *packed, size_t n, int bits, int out_dtype, void *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * A layer norm that keeps its NORMALIZED input in 2, 4 or 8 bits per element for backward (what QuantizedLayerNorm keeps instead of its input):
+ * the state is a pure function of (x^, bits, seed), evaluated alike by the host function and the kernel.
+ *
+ * The normalized rows of a seed.  The input is a contiguous rows x width matrix (F32 / F16 / BF16), each element widened exactly to fp32.
+ *   Row statistics, per row r, every step ONE fp32 operation:
+ *     mean    = (the sum of the row) / width
+ *     var     = (the sum of (x - mean)^2) / width     two passes over the row the lanes already hold -- not E[x^2] - mean^2, which cancels
+ *               for a row such as 1000 + noise.  The order of the two sums is the kernel's (fewbit_amd/csrc/fewbit_norm.hip); what the state
+ *               is a function of is x^, which fewbit_hipx_layer_norm_forward hands out on request (xhat_out).
+ *     rstd    = 1 / sqrt(var + float32(eps))           (an addition, a square root, a division)
+ *     x^      = (x - mean) * rstd
+ *     y       = round_to_dtype(x^ * gamma + beta)      a product and a sum in fp32, rounded once.  gamma and beta are read in the dtype of x and
+ *               widened exactly; a NULL gamma counts as 1 and a NULL beta as 0.
+ *   Groups and blocks are PER ROW: B = ceil(width / 8) blocks and G = ceil(width / 64) groups to a row; the last block and the last group of a
+ *     row may be short.  Missing elements count for neither the minimum nor the maximum and their codes are 0 (the rule of the tail of a
+ *     tensor in the packed form of a seed).
+ *   Codes: lo, step, inv, code, decode and the poison rule are those of the packed form of a seed (above; one text, fewbit_quantdef.h).  The 16
+ *     rounding bits of element 8 b + e of row r are those the packed form takes for element e of block q = r * B + b (a 64-bit value), counter
+ *     word 3 = 7.
+ *   The state, fewbit_hipx_norm_state_bytes(rows, width, k) = rows * (8 G + C) bytes with C = k * B rounded up to a multiple of 4:
+ *     first the (lo, step) pairs, fp32 little-endian, ordered (r, g): 8 * rows * G bytes;
+ *     then the codes: row r starts at 8 * rows * G + r * C, block b of it is a little-endian word of k bytes at k * b with element j in bits
+ *     [k j, k j + k); the bytes of a row behind its last block (two of them, at 2 bits and an odd B) are 0.
+ *     For width % 64 == 0 the state is byte for byte fewbit_hipx_quant_pack_host of the flat x^ with the same seed and bits.
+ *   Backward, fp32 throughout, every step ONE operation:
+ *     x^q = decode(state), g^ = gy * gamma
+ *     dx  = round_to_dtype(rstd * ((g^ - mean_row(g^)) - x^q * mean_row(g^ * x^q)))              mean_row: (the sum of the row) / width
+ *     dgamma = sum_r gy * x^q,  dbeta = sum_r gy                                                   as fp32
+ *   NaN and infinity: a non-finite element (or a row whose fp32 sum overflows) makes its row's x^ and y NaN and poisons every group of the
+ *     row; that row of dx and the columns of dgamma it touches are then NaN, as with torch.  Other rows are untouched to the bit.
+ *   Since E[x^q] = x^, dgamma is unbiased.  dx is not exactly: x^q enters it twice, E[dx_q] - dx = -rstd * g^_i * Var(x^q_i) / width, second
+ *     order in the step.
+ *
+ * fewbit_hipx_norm_state_bytes: the size above; 0 for bits other than 2, 4, 8, width outside 1 .. 8192, rows = 0 and rows * width beyond 2^36.
+ * fewbit_hipx_norm_workspace: bytes of scratch of fewbit_hipx_layer_norm_backward (16-byte aligned; the per-workgroup partial sums of dgamma and
+ *   dbeta; contents are scratch); 0 for the same shapes.
+ * fewbit_hipx_norm_state_host / _unpack_host: the state of given fp32 x^ (rows x width, contiguous) and its fp32 decode (rows x width) at HOST
+ *   pointers; no device is touched.
+ * fewbit_hipx_layer_norm_forward: ONE launch on `stream`.
+ *   dtype, x, y, gamma, beta   F32 / F16 / BF16; aligned to the element; gamma and beta may be NULL.  A row is loaded once, by 16-byte accesses
+ *                where its base is 16-byte aligned and element by element otherwise and in its ragged tail: the same bytes either way
+ *   seed, seed_device   as in fewbit_hipx_quant_pack: seed_device != NULL is an 8-byte aligned DEVICE word read when the kernel runs
+ *   rstd         rows fp32; required with a state
+ *   state, state_bytes   8-byte aligned, at least fewbit_hipx_norm_state_bytes bytes; nothing beyond that many is written.  state == NULL: the
+ *                plain forward that keeps nothing (bits and the seed are ignored; rstd may be NULL too); y and rstd are the same bytes
+ *   xhat_out     NULL, or rows x width fp32 that receive the x^ the kernel quantized (the seam at which a test meets the host function)
+ * fewbit_hipx_layer_norm_backward: TWO launches on `stream`: dx and per-workgroup partial sums, then the partials added in a fixed order.
+ *   gy, dx, gamma   of `dtype`; dgamma, dbeta: width fp32.  dx, dgamma, dbeta may each be NULL: that output is skipped and nothing of it
+ *                written (both sums NULL: one launch, no workspace needed).  rstd is read for dx only.
+ * Widths 1 .. 8192, rows * width <= 2^36.  The plan is a pure function of (rows, width): a row takes 8, 16, 64, 128 or 256 lanes (widths up to
+ * 64, 128, 512, 1024, 2048), a lane one block of 8 elements; beyond 2048 elements a forward lane takes 2 blocks and beyond 4096 four, a backward
+ * row 512 and 1024 lanes.  Forward: 256 lanes to a workgroup, at most 16384 workgroups; backward: 1024 lanes, at most 512 workgroups; beyond
+ * that a workgroup walks on by the width of the grid.  Sums across lanes go by DPP lane moves inside 16 lanes, v_readlane inside a wave and LDS
+ * across the waves of a row, in a fixed order; there are no float atomics and no waiting between workgroups: the same arguments give the same
+ * bytes.
+ * Refused before anything is launched (FEWBIT_ERR_INVALID_ARGUMENT): an unknown dtype, bits other than 2, 4, 8, a width outside 1 .. 8192,
+ * rows * width beyond 2^36, eps negative or not finite, a null or misaligned pointer, a state or workspace that is too small, a misaligned
+ * seed word.  rows = 0: FEWBIT_OK, no launch. */
+size_t fewbit_hipx_norm_state_bytes(size_t rows, size_t width, int bits);
+size_t fewbit_hipx_norm_workspace(size_t rows, size_t width);
+int fewbit_hipx_norm_state_host(const float *xhat_host, size_t rows, size_t width, int bits, uint64_t seed, uint8_t *out_host);
+int fewbit_hipx_norm_state_unpack_host(const uint8_t *state_host, size_t rows, size_t width, int bits, float *out_host);
+int fewbit_hipx_layer_norm_forward(int dtype, const void *x, size_t rows, size_t width, const void *gamma, const void *beta, double eps, int bits, uint64_t seed,
+                                   const uint64_t *seed_device, void *y, float *rstd, uint8_t *state, size_t state_bytes, float *xhat_out, void *stream);
+int fewbit_hipx_layer_norm_backward(int dtype, const void *gy, const uint8_t *state, const float *rstd, const void *gamma, size_t rows, size_t width, int bits,
+                                    void *dx, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

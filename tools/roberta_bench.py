@@ -14,6 +14,10 @@ Two routes to the same kernels:
   --dropout fewbit          every `nn.Dropout` of the model is swapped for `fewbit.Dropout` (the mask of a seed: nothing saved for backward) in
                             the fewbit / op variants and in every non-vanilla row of --table; the line gains a `dropout` entry: the vanilla
                             model with ONLY the dropouts swapped, its peak memory and step time against the vanilla model.
+  --layer-norm fewbit       every `nn.LayerNorm` of the model is swapped for `fewbit.QuantizedLayerNorm` (--layer-norm-bits, default 4: the normalized
+                            input in a few bits instead of the input) in the fewbit / op variants and in every non-vanilla row of --table; the
+                            line gains a `layer_norm` entry: the vanilla model with ONLY the layer norms swapped, its peak memory and step time
+                            against the vanilla model.
   --sign-flips              `fewbit_amd.linear.use_sign_flips(True)`: with --table --matmul dct / dft the randomized layers negate a random half of
                             the rows in front of the transform (S = sqrt(N / p) R T D; the signs of the call's seed, evaluated in pass A)
 Prints one JSON line.
@@ -90,6 +94,20 @@ def swap_dropout(model):
     return n[0]
 
 
+def swap_layer_norm(model, bits):
+    """Every nn.LayerNorm -> fewbit.QuantizedLayerNorm sharing its parameters (the README's recipe)"""
+    n = [0]
+
+    def fn(mod, path):
+        if type(mod) is torch.nn.LayerNorm:
+            n[0] += 1
+            return fewbit.QuantizedLayerNorm.from_layer_norm(mod, bits=bits)
+        return mod
+
+    fewbit.map_module(model, fn)
+    return n[0]
+
+
 def swap_linear(model, ratio, sketch_dtype=None, matmul='gaussian'):
     """Every nn.Linear of the encoder -> fewbit.RandomizedLinear(proj_dim_ratio=ratio) sharing its parameters (the
     README's `convert_linear` recipe); the classification head stays exact."""
@@ -154,6 +172,9 @@ def main():
                     help='draw S with torch.randn / randint and multiply with torch.matmul (what round 3 measured) instead of the '
                          'gfx950 sketch kernels (fewbit_amd/csrc/fewbit_sketch.hip)')
     ap.add_argument('--dropout', default='torch', choices=('torch', 'fewbit'), help="'fewbit': swap every nn.Dropout for fewbit.Dropout (module docstring)")
+    ap.add_argument('--layer-norm', default='torch', choices=('torch', 'fewbit'),
+                    help="'fewbit': swap every nn.LayerNorm for fewbit.QuantizedLayerNorm (module docstring)")
+    ap.add_argument('--layer-norm-bits', type=int, default=4, choices=(2, 4, 8), help='bits per kept element of the swapped layer norms')
     ap.add_argument('--sign-flips', action='store_true', help="random row signs in front of the 'dct' / 'dft' sketches (fewbit_amd.linear.use_sign_flips)")
     args = ap.parse_args()
     dtype = {'fp32': torch.float32, 'bf16': torch.bfloat16}[args.dtype]
@@ -175,9 +196,11 @@ def main():
             ng = swap_gelu(model, args.bits) if gelu else 0
             nl = swap_linear(model, args.linear_ratio, torch.bfloat16 if args.sketch_bf16 else None, args.matmul) if linear else 0
             nd = swap_dropout(model) if args.dropout == 'fewbit' and (gelu or linear) else 0
+            nn_ = swap_layer_norm(model, args.layer_norm_bits) if args.layer_norm == 'fewbit' and (gelu or linear) else 0
             r = run(model, ids, labels, args.steps)
             rows.append({'gelu': f'{args.bits}-bit' if gelu else 'vanilla', 'linear': 'randomized' if linear else 'vanilla',
-                         'gelu_modules_swapped': ng, 'linear_modules_swapped': nl, 'dropout_modules_swapped': nd, 'ms_per_step': round(r['ms_per_step'], 2),
+                         'gelu_modules_swapped': ng, 'linear_modules_swapped': nl, 'dropout_modules_swapped': nd, 'layer_norm_modules_swapped': nn_,
+                         'ms_per_step': round(r['ms_per_step'], 2),
                          'peak_gib': round(r['peak_bytes'] / 2**30, 3), 'loss': r['loss']})
             del model
             torch.cuda.empty_cache()
@@ -196,6 +219,8 @@ def main():
     names = ('vanilla', 'fewbit') + (('op', ) if args.route in ('op', 'both') or args.only == 'op' else ())
     if args.dropout == 'fewbit' and not args.only:
         names += ('dropout', )
+    if args.layer_norm == 'fewbit' and not args.only:
+        names += ('layer_norm', )
     for name in names:
         if args.only and name != args.only:
             continue
@@ -206,9 +231,12 @@ def main():
             swapped = patch_gelu_with_raw_op(model, dtype, dev)
         else:
             swapped = swap_gelu(model, args.bits) if name == 'fewbit' else 0
-        dropouts = swap_dropout(model) if args.dropout == 'fewbit' and name != 'vanilla' else 0
+        dropouts = swap_dropout(model) if args.dropout == 'fewbit' and name not in ('vanilla', 'layer_norm') else 0
+        norms = swap_layer_norm(model, args.layer_norm_bits) if args.layer_norm == 'fewbit' and name not in ('vanilla', 'dropout') else 0
         res[name] = run(model, ids, labels, args.steps)
         res[name]['gelu_modules_swapped'], res[name]['dropout_modules_swapped'] = swapped, dropouts
+        if args.layer_norm == 'fewbit':
+            res[name]['layer_norm_modules_swapped'] = norms
         del model
         torch.cuda.empty_cache()
     if args.only:
@@ -239,6 +267,12 @@ def main():
                                   'peak_saving_bytes': res['vanilla']['peak_bytes'] - res['dropout']['peak_bytes'],
                                   'saved_tensor_saving_bytes': res['vanilla']['saved_for_backward_bytes'] - res['dropout']['saved_for_backward_bytes'],
                                   'step_time_ratio': res['dropout']['ms_per_step'] / res['vanilla']['ms_per_step']}
+    if 'layer_norm' in res:   # the layer norms alone
+        out['layer_norm'] = res['layer_norm']
+        out['layer_norm_summary'] = {'route': f'fewbit.QuantizedLayerNorm(bits={args.layer_norm_bits}) in place of every nn.LayerNorm, nothing else swapped',
+                                     'peak_saving_bytes': res['vanilla']['peak_bytes'] - res['layer_norm']['peak_bytes'],
+                                     'saved_tensor_saving_bytes': res['vanilla']['saved_for_backward_bytes'] - res['layer_norm']['saved_for_backward_bytes'],
+                                     'step_time_ratio': res['layer_norm']['ms_per_step'] / res['vanilla']['ms_per_step']}
     if 'fewbit' in res and 'op' in res:
         out['op_vs_module'] = {'step_time_ratio': res['op']['ms_per_step'] / res['fewbit']['ms_per_step'],
                                'saved_bytes_difference': res['op']['saved_for_backward_bytes'] - res['fewbit']['saved_for_backward_bytes'],
