@@ -2,7 +2,7 @@
 of ``libfewbit_hip.so`` was frozen at version 5 (``cabi.SYMBOLS`` stays that list).  Same conventions as ``cabi``: device tensors,
 torch's current stream on the tensors' device, no fallback -- a missing library or an unsupported shape raises.  What it binds: the sampled
 Fourier transform, the zero-extended and sign-flipped sampled transforms, the column sampling of LinearCRS, the moments of the variance
-estimator, the dropout of a seed, the packed form of a seed, and the layer norm that keeps the normalized rows of a seed.
+estimator, the dropout of a seed, the packed form of a seed, and the layer norm and the RMS norm that keep the normalized rows of a seed.
 """
 import ctypes
 import os
@@ -18,7 +18,7 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'sampled_dft_zext', 'sampled_dft_zext_seeded', 'sampled_signs', 'sampled_dct_signed', 'sampled_dft_signed', 'moments_workspace_bytes', 'row_moments', 'sum_squares',
            'DROPOUT_SWEEP', 'dropout_threshold', 'dropout_keep', 'dropout_apply', 'QUANT_BITS', 'QUANT_GROUP', 'QUANT_SWEEP', 'quant_bytes', 'quant_pack',
            'quant_unpack', 'quant_pack_host', 'quant_unpack_host', 'NORM_MAX_WIDTH', 'norm_plan', 'norm_state_bytes', 'norm_workspace_bytes', 'norm_state_host',
-           'norm_state_unpack_host', 'layer_norm_forward', 'layer_norm_backward']
+           'norm_state_unpack_host', 'layer_norm_forward', 'layer_norm_backward', 'rms_norm_forward', 'rms_norm_backward']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -32,7 +32,8 @@ SYMBOLS = ('fewbit_hipx_abi_version', 'fewbit_hipx_last_error', 'fewbit_hipx_sam
            'fewbit_hipx_sum_squares', 'fewbit_hipx_dropout_threshold', 'fewbit_hipx_dropout_keep', 'fewbit_hipx_dropout', 'fewbit_hipx_sampled_signs',
            'fewbit_hipx_sampled_dct_signed', 'fewbit_hipx_sampled_dft_signed', 'fewbit_hipx_quant_bytes', 'fewbit_hipx_quant_pack_host',
            'fewbit_hipx_quant_unpack_host', 'fewbit_hipx_quant_pack', 'fewbit_hipx_quant_unpack', 'fewbit_hipx_norm_state_bytes', 'fewbit_hipx_norm_workspace',
-           'fewbit_hipx_norm_state_host', 'fewbit_hipx_norm_state_unpack_host', 'fewbit_hipx_layer_norm_forward', 'fewbit_hipx_layer_norm_backward')
+           'fewbit_hipx_norm_state_host', 'fewbit_hipx_norm_state_unpack_host', 'fewbit_hipx_layer_norm_forward', 'fewbit_hipx_layer_norm_backward', 'fewbit_hipx_rms_norm_forward',
+           'fewbit_hipx_rms_norm_backward')
 
 _lib = None
 
@@ -129,6 +130,11 @@ def lib() -> ctypes.CDLL:
         L.fewbit_hipx_layer_norm_forward.argtypes = [i32, vp, sz, sz, vp, vp, dbl, i32, u64, vp, vp, vp, vp, sz, vp, vp]
         L.fewbit_hipx_layer_norm_backward.restype = i32
         L.fewbit_hipx_layer_norm_backward.argtypes = [i32, vp, vp, vp, vp, sz, sz, i32, vp, vp, vp, vp, sz, vp]
+        # the un-centred rows (the RMS norm): inside revision 2 as well, recognised by its symbols
+        L.fewbit_hipx_rms_norm_forward.restype = i32
+        L.fewbit_hipx_rms_norm_forward.argtypes = [i32, vp, sz, sz, vp, dbl, i32, u64, vp, vp, vp, vp, sz, vp, vp]
+        L.fewbit_hipx_rms_norm_backward.restype = i32
+        L.fewbit_hipx_rms_norm_backward.argtypes = [i32, vp, vp, vp, vp, sz, sz, i32, vp, vp, vp, sz, vp]
         _lib = L
     return _lib
 
@@ -526,7 +532,7 @@ def quant_unpack(packed: torch.Tensor, n: int, bits: int, dtype: torch.dtype, ou
     return out
 
 
-# ---- the layer norm that keeps its normalized rows in 2, 4 or 8 bits (fewbit_amd/csrc/fewbit_norm.hip): what QuantizedLayerNorm keeps ---------------
+# ---- the layer norm and the RMS norm that keep their normalized rows in 2, 4 or 8 bits (fewbit_amd/csrc/fewbit_norm.hip) ---------------------------
 NORM_MAX_WIDTH = 8192                           # the widest row the kernels take
 
 
@@ -550,7 +556,7 @@ def norm_state_bytes(rows: int, width: int, bits: int) -> int:
 
 
 def norm_workspace_bytes(rows: int, width: int) -> int:
-    """bytes of scratch ``layer_norm_backward`` needs for ``dgamma`` / ``dbeta`` (0: no kernel for this shape)"""
+    """bytes of scratch ``layer_norm_backward`` needs for ``dgamma`` / ``dbeta`` and ``rms_norm_backward`` for ``dgamma`` (0: no kernel for this shape)"""
     if rows < 0 or width < 0:
         return 0
     return lib().fewbit_hipx_norm_workspace(rows, width)
@@ -616,18 +622,12 @@ def _norm_out(t: Optional[torch.Tensor], shape, dtype: torch.dtype, device, what
     return t
 
 
-def layer_norm_forward(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float, bits: int = 4, seed=0, keep: bool = True,
-                       want_xhat: bool = False, y: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
-                       xhat: Optional[torch.Tensor] = None, stream: Optional[int] = None):
-    """The layer norm of the rows of ``x`` (contiguous, 2-D, fp32 / fp16 / bf16, on the GPU; ``gamma`` / ``beta``: its dtype, or None) in ONE
-    launch -> ``(y, rstd, state, xhat)``: ``y`` in the dtype of ``x``; ``rstd`` one fp32 per row; ``state`` the normalized rows in ``bits`` bits
-    rounded with ``seed`` (a uint8 tensor of ``norm_state_bytes`` bytes; ``norm_state_host`` gives the same bytes from ``xhat``); ``xhat`` the
-    fp32 normalized rows the kernel quantized, only with ``want_xhat`` (else None).  ``keep=False``: the plain forward, ``state`` is None and
-    nothing but ``y`` and ``rstd`` is written -- the same bytes as with a state.  ``seed``: an int, or a one-element int64 tensor on the device
-    of ``x`` that is read when the kernel runs (``cabi.next_sketch_seed``).  ``y``, ``rstd``, ``state``, ``xhat``: buffers to write into."""
+def _norm_forward(name: str, x, gamma, beta, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream):
+    """the forward call of either norm (``beta`` is False for the RMS norm, whose entry point has no such argument)"""
     rows, width = _norm_rows(x, 'x')
-    gp, bp = _norm_vector(gamma, x, 'gamma'), _norm_vector(beta, x, 'beta')
-    need = _norm_size(rows, width, bits, 'layer_norm_forward') if keep else 0
+    centred = beta is not False
+    gp, bp = _norm_vector(gamma, x, 'gamma'), _norm_vector(beta, x, 'beta') if centred else None
+    need = _norm_size(rows, width, bits, name) if keep else 0
     value, word, others = _seed_arguments(seed) if keep else (0, None, ())
     with _on(x.device):
         y = _norm_out(y, (rows, width), x.dtype, x.device, 'y')
@@ -640,11 +640,44 @@ def layer_norm_forward(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Opt
             state = None
         if want_xhat or xhat is not None:
             xhat = _norm_out(xhat, (rows, width), torch.float32, x.device, 'xhat')
-        _same_device(x, y, rstd, *others, *(t for t in (gamma, beta, state, xhat) if t is not None))
-        _check(lib().fewbit_hipx_layer_norm_forward(DTYPES[x.dtype], x.data_ptr(), rows, width, gp, bp, float(eps), bits, value, word, y.data_ptr(), rstd.data_ptr(),
-                                                    None if state is None else state.data_ptr(), 0 if state is None else state.numel(),
-                                                    None if xhat is None else xhat.data_ptr(), _stream(stream, x.device)))
+        _same_device(x, y, rstd, *others, *(t for t in (gamma, beta if centred else None, state, xhat) if t is not None))
+        _check(getattr(lib(), f'fewbit_hipx_{name}')(DTYPES[x.dtype], x.data_ptr(), rows, width, gp, *((bp, ) if centred else ()), float(eps), bits, value, word,
+                                                     y.data_ptr(), rstd.data_ptr(), None if state is None else state.data_ptr(),
+                                                     0 if state is None else state.numel(), None if xhat is None else xhat.data_ptr(), _stream(stream, x.device)))
     return y, rstd, state, xhat
+
+
+def _norm_backward(name: str, gy, state, rstd, gamma, bits, want, outs, workspace, stream):
+    """the backward call of either norm: ``want`` and ``outs`` are (dx, dgamma, dbeta) for the layer norm and (dx, dgamma) for the RMS norm"""
+    rows, width = _norm_rows(gy, 'gy')
+    gp = _norm_vector(gamma, gy, 'gamma')
+    need = _norm_size(rows, width, bits, name)
+    if state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < need:
+        raise FewbitHipError(f'state must be a contiguous uint8 tensor of at least {need} bytes')
+    if rstd.dtype != torch.float32 or rstd.numel() != rows or not rstd.is_contiguous():
+        raise FewbitHipError(f'rstd must be a contiguous float32 tensor of {rows} elements')
+    with _on(gy.device):
+        shapes = (((rows, width), gy.dtype, 'dx'), ((width, ), torch.float32, 'dgamma'), ((width, ), torch.float32, 'dbeta'))
+        outs = tuple(_norm_out(t, shape, dtype, gy.device, what) if wanted else None for t, wanted, (shape, dtype, what) in zip(outs, want, shapes))
+        if any(want[1:]) and workspace is None:
+            workspace = torch.empty(norm_workspace_bytes(rows, width), dtype=torch.uint8, device=gy.device)
+        _same_device(gy, state, rstd, *(t for t in (gamma, *outs, workspace) if t is not None))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _check(getattr(lib(), f'fewbit_hipx_{name}')(DTYPES[gy.dtype], gy.data_ptr(), state.data_ptr(), rstd.data_ptr(), gp, rows, width, bits, *map(ptr, outs),
+                                                     ptr(workspace), 0 if workspace is None else workspace.numel(), _stream(stream, gy.device)))
+    return outs
+
+
+def layer_norm_forward(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float, bits: int = 4, seed=0, keep: bool = True,
+                       want_xhat: bool = False, y: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
+                       xhat: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """The layer norm of the rows of ``x`` (contiguous, 2-D, fp32 / fp16 / bf16, on the GPU; ``gamma`` / ``beta``: its dtype, or None) in ONE
+    launch -> ``(y, rstd, state, xhat)``: ``y`` in the dtype of ``x``; ``rstd`` one fp32 per row; ``state`` the normalized rows in ``bits`` bits
+    rounded with ``seed`` (a uint8 tensor of ``norm_state_bytes`` bytes; ``norm_state_host`` gives the same bytes from ``xhat``); ``xhat`` the
+    fp32 normalized rows the kernel quantized, only with ``want_xhat`` (else None).  ``keep=False``: the plain forward, ``state`` is None and
+    nothing but ``y`` and ``rstd`` is written -- the same bytes as with a state.  ``seed``: an int, or a one-element int64 tensor on the device
+    of ``x`` that is read when the kernel runs (``cabi.next_sketch_seed``).  ``y``, ``rstd``, ``state``, ``xhat``: buffers to write into."""
+    return _norm_forward('layer_norm_forward', x, gamma, beta, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream)
 
 
 def layer_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor], bits: int, want=(True, True, True),
@@ -654,22 +687,25 @@ def layer_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tenso
     or None) -> ``(dx, dgamma, dbeta)``: ``dx`` in the dtype of ``gy``, ``dgamma`` and ``dbeta`` as fp32 of ``width`` elements; where ``want`` is
     False the output is None and nothing of it is computed or written.  Two launches (one when neither sum is wanted), fp32 arithmetic, a fixed
     order of every sum: the same arguments give the same bits.  ``workspace``: a uint8 tensor of ``norm_workspace_bytes(rows, width)`` bytes."""
-    rows, width = _norm_rows(gy, 'gy')
-    gp = _norm_vector(gamma, gy, 'gamma')
-    need = _norm_size(rows, width, bits, 'layer_norm_backward')
-    if state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < need:
-        raise FewbitHipError(f'state must be a contiguous uint8 tensor of at least {need} bytes')
-    if rstd.dtype != torch.float32 or rstd.numel() != rows or not rstd.is_contiguous():
-        raise FewbitHipError(f'rstd must be a contiguous float32 tensor of {rows} elements')
     want_dx, want_dgamma, want_dbeta = want
-    with _on(gy.device):
-        dx = _norm_out(dx, (rows, width), gy.dtype, gy.device, 'dx') if want_dx else None
-        dgamma = _norm_out(dgamma, (width, ), torch.float32, gy.device, 'dgamma') if want_dgamma else None
-        dbeta = _norm_out(dbeta, (width, ), torch.float32, gy.device, 'dbeta') if want_dbeta else None
-        if (want_dgamma or want_dbeta) and workspace is None:
-            workspace = torch.empty(norm_workspace_bytes(rows, width), dtype=torch.uint8, device=gy.device)
-        _same_device(gy, state, rstd, *(t for t in (gamma, dx, dgamma, dbeta, workspace) if t is not None))
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _check(lib().fewbit_hipx_layer_norm_backward(DTYPES[gy.dtype], gy.data_ptr(), state.data_ptr(), rstd.data_ptr(), gp, rows, width, bits, ptr(dx), ptr(dgamma),
-                                                     ptr(dbeta), ptr(workspace), 0 if workspace is None else workspace.numel(), _stream(stream, gy.device)))
-    return dx, dgamma, dbeta
+    return _norm_backward('layer_norm_backward', gy, state, rstd, gamma, bits, (want_dx, want_dgamma, want_dbeta), (dx, dgamma, dbeta), workspace, stream)
+
+
+def rms_norm_forward(x: torch.Tensor, gamma: Optional[torch.Tensor], eps: float, bits: int = 4, seed=0, keep: bool = True, want_xhat: bool = False,
+                     y: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
+                     xhat: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """The RMS norm of the rows of ``x`` in ONE launch -> ``(y, rstd, state, xhat)``, everything as in ``layer_norm_forward`` without ``beta``:
+    ``rstd = 1 / sqrt(mean(x^2) + eps)``, ``xhat = x * rstd``, ``y = xhat * gamma`` rounded once, ``state`` the state of these ``xhat``
+    (``norm_state_bytes`` bytes; ``norm_state_host`` gives the same bytes from ``xhat``).  ``eps`` is a number (``F.rms_norm``'s default
+    is ``torch.finfo(x.dtype).eps``)."""
+    return _norm_forward('rms_norm_forward', x, gamma, False, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream)
+
+
+def rms_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor], bits: int, want=(True, True),
+                      dx: Optional[torch.Tensor] = None, dgamma: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                      stream: Optional[int] = None):
+    """The gradients of an RMS norm from its state (``rms_norm_forward``) and ``gy`` -> ``(dx, dgamma)``, everything as in ``layer_norm_backward``
+    without the mean term and without ``dbeta``: ``dx = rstd * (g^ - x^q * mean(g^ * x^q))``, ``dgamma = sum_r gy * x^q``.  Two launches (one when
+    ``dgamma`` is not wanted, and then no workspace); ``workspace``: a uint8 tensor of ``norm_workspace_bytes(rows, width)`` bytes."""
+    want_dx, want_dgamma = want
+    return _norm_backward('rms_norm_backward', gy, state, rstd, gamma, bits, (want_dx, want_dgamma), (dx, dgamma), workspace, stream)

@@ -5,8 +5,13 @@
 //               state = per row and group of 64 (lo, step), then per row the codes of x^ -- the packed form of a seed, rows apart
 //     backward  x^q = decode(state), g^ = gy gamma, dx = rstd (g^ - mean(g^) - x^q mean(g^ x^q)), dgamma = sum_r gy x^q, dbeta = sum_r gy
 //
-// What QuantizedLayerNorm (fewbit_amd/norm.py) keeps: the state and one fp32 rstd per row instead of the input.  lo, step, inv, code_of, decode
-// and the poison rule are fewbit_quantdef.h's, the text fewbit_quant.hip evaluates.
+// and the RMS norm of the same state ("the un-centred rows"), the same kernels with the kind switched at compile time:
+//
+//     forward   rstd = 1 / sqrt(mean(x^2) + eps), x^ = x rstd, y = x^ gamma
+//     backward  dx = rstd (g^ - x^q mean(g^ x^q)), dgamma = sum_r gy x^q
+//
+// What QuantizedLayerNorm and QuantizedRMSNorm (fewbit_amd/norm.py) keep: the state and one fp32 rstd per row instead of the input.  lo, step, inv,
+// code_of, decode and the poison rule are fewbit_quantdef.h's, the text fewbit_quant.hip evaluates.
 //
 // The lanes of a row.  A lane holds K blocks of eight elements: block b = k LPR + l for lane l of the LPR lanes of its row, so eight neighbouring
 // lanes hold a group (their minimum, maximum and flag meet in three DPP steps) and a row is read once and stays in registers for the
@@ -145,8 +150,19 @@ template <int DT> __device__ __forceinline__ void store_block(typename Elem<DT>:
 }
 __device__ __forceinline__ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// BITS = 0: the plain forward that keeps nothing (state is not touched)
-template <int DT, int BITS, int LPR, int K>
+// The two norms of this unit are ONE text each for forward and backward, with the kind as a compile-time switch:
+//     CENTRED (the layer norm)   two row sums per tile (the row, then the squares of the centred row), beta, dbeta
+//     otherwise (the RMS norm)   ONE row sum per tile (the squares of the row as loaded); beta is neither loaded nor added, and backward has no
+//                                mean(g^) and no sum of gy
+// The slots of row_sum.  row_sum<LPR >= 128> writes slots[wave], meets ONE barrier, then reads its row's slots, so a call may reuse a slot array only
+// after another barrier that every wave of the workgroup has met.  With two row sums per tile on two arrays the barrier of the second separates a
+// tile's reads of the first array from the next tile's writes to it.  With one row sum per tile that barrier is missing (a fast wave would write
+// tile t + 1's value into a slot that a slow wave still reads for tile t), so the array alternates with the parity of the workgroup's own tile
+// count: the writes of iteration i + 2 follow the barrier of iteration i + 1, which every wave meets only after its reads of iteration i.
+constexpr bool kCentred = true, kUncentred = false;
+
+// BITS = 0: the plain forward that keeps nothing (state is not touched); an un-centred launch passes beta = NULL, which is never read
+template <int DT, int BITS, int LPR, int K, bool CENTRED>
 __global__ __launch_bounds__(kThreads) void forward_kernel(const void *__restrict__ x_, size_t rows, uint32_t width, const void *__restrict__ gamma_,
                                                            const void *__restrict__ beta_, float eps, Key value, const Key *device, void *__restrict__ y_,
                                                            float *__restrict__ rstd_out, uint8_t *__restrict__ state, float *__restrict__ xhat_out) {
@@ -162,7 +178,8 @@ __global__ __launch_bounds__(kThreads) void forward_kernel(const void *__restric
     const uint32_t blocks = (width + kBlock - 1) / kBlock, groups = (width + kGroup - 1) / kGroup;
     const size_t tiles = (rows + kRowsPerTile - 1) / kRowsPerTile, stride = BITS == 0 ? 0 : code_bytes(blocks, BITS);
     const float count = static_cast<float>(width);
-    const bool vec_gamma = gamma != nullptr && aligned16(gamma), vec_beta = beta != nullptr && aligned16(beta);
+    const bool vec_gamma = gamma != nullptr && aligned16(gamma), vec_beta = CENTRED && beta != nullptr && aligned16(beta);
+    [[maybe_unused]] uint32_t iteration = 0;    // of this workgroup's walk: the parity picks the slots of the one row sum of an un-centred tile
     for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const size_t r = tile * kRowsPerTile + sub;
         const bool live = r < rows;
@@ -178,20 +195,26 @@ __global__ __launch_bounds__(kThreads) void forward_kernel(const void *__restric
             have[k] = !live || b >= blocks ? 0 : width - i0 < static_cast<uint32_t>(kBlock) ? static_cast<int>(width - i0) : kBlock;
             load_block<DT>(xr + i0, vec_x, have[k], v[k]);
 #pragma unroll
-            for (int e = 0; e < kBlock; ++e) s = add_rn(s, v[k][e]);
+            for (int e = 0; e < kBlock; ++e) s = add_rn(s, CENTRED ? v[k][e] : mul_rn(v[k][e], v[k][e]));  // (a missing element: +0 either way)
         }
-        const float mean = div_rn(row_sum<LPR>(s, slots[0]), count);
-        float ss = 0.0f;
+        float second;                           // the mean of the squares: of the centred row, or of the row as it is
+        if constexpr (CENTRED) {
+            const float mean = div_rn(row_sum<LPR>(s, slots[0]), count);
+            float ss = 0.0f;
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
+            for (int k = 0; k < K; ++k) {
 #pragma unroll
-            for (int e = 0; e < kBlock; ++e) {
-                v[k][e] = e < have[k] ? sub_rn(v[k][e], mean) : 0.0f;
-                ss = add_rn(ss, mul_rn(v[k][e], v[k][e]));
+                for (int e = 0; e < kBlock; ++e) {
+                    v[k][e] = e < have[k] ? sub_rn(v[k][e], mean) : 0.0f;
+                    ss = add_rn(ss, mul_rn(v[k][e], v[k][e]));
+                }
             }
+            second = div_rn(row_sum<LPR>(ss, slots[1]), count);
+        } else {
+            second = div_rn(row_sum<LPR>(s, slots[iteration & 1]), count);
+            ++iteration;
         }
-        const float var = div_rn(row_sum<LPR>(ss, slots[1]), count);
-        const float rstd = div_rn(1.0f, sqrt_rn(add_rn(var, eps)));
+        const float rstd = div_rn(1.0f, sqrt_rn(add_rn(second, eps)));
         if (live && l == 0 && rstd_out != nullptr) rstd_out[r] = rstd;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -203,18 +226,20 @@ __global__ __launch_bounds__(kThreads) void forward_kernel(const void *__restric
 #pragma unroll
                 for (int e = 0; e < kBlock; ++e) g[e] = 1.0f;
             }
-            if (beta != nullptr) {
-                load_block<DT>(beta + i0, vec_beta, have[k], o);
-            } else {
+            if constexpr (CENTRED) {
+                if (beta != nullptr) {
+                    load_block<DT>(beta + i0, vec_beta, have[k], o);
+                } else {
 #pragma unroll
-                for (int e = 0; e < kBlock; ++e) o[e] = 0.0f;
+                    for (int e = 0; e < kBlock; ++e) o[e] = 0.0f;
+                }
             }
             int32_t kmin = INT32_MAX, kmax = INT32_MIN;
             uint32_t bad = 0;
 #pragma unroll
             for (int e = 0; e < kBlock; ++e) {
                 v[k][e] = mul_rn(v[k][e], rstd);                                                    // x^
-                o[e] = add_rn(mul_rn(v[k][e], g[e]), o[e]);
+                o[e] = CENTRED ? add_rn(mul_rn(v[k][e], g[e]), o[e]) : mul_rn(v[k][e], g[e]);
                 if (e < have[k]) {
                     const uint32_t bits = bits_of_float(v[k][e]);
                     const int32_t key_e = order_key(bits);
@@ -261,7 +286,9 @@ __global__ __launch_bounds__(kThreads) void forward_kernel(const void *__restric
 // partials: [workgroup][gy x^q, gy][LPR * 8 columns] fp32, or NULL when neither sum is wanted.  1024 lanes to a workgroup and ONE block per lane
 // (a row takes up to 1024 lanes): the column sums of a workgroup's rows stay in 16 registers per lane, and few workgroups -- few rows of
 // partials -- still fill the machine.
-template <int DT, int BITS, int LPR>
+// Un-centred: ONE row sum per tile (g^ x^q; its slots alternate as in the forward), only the gy x^q accumulators, and only that half of a
+// workgroup's partials is written (the layout stays [workgroup][2][columns], which the column sums read with the same stride).
+template <int DT, int BITS, int LPR, bool CENTRED>
 __global__ __launch_bounds__(kBackwardThreads) void backward_kernel(const void *__restrict__ gy_, const uint8_t *__restrict__ state,
                                                                     const float *__restrict__ rstd_in, const void *__restrict__ gamma_, size_t rows, uint32_t width,
                                                                     void *__restrict__ dx_, float *__restrict__ partials) {
@@ -288,6 +315,7 @@ __global__ __launch_bounds__(kBackwardThreads) void backward_kernel(const void *
     }
 #pragma unroll
     for (int e = 0; e < kBlock; ++e) acc_gamma[e] = acc_beta[e] = 0.0f;
+    [[maybe_unused]] uint32_t iteration = 0;
     for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const size_t r = tile * kRowsPerTile + sub;
         const bool live = r < rows;
@@ -309,39 +337,51 @@ __global__ __launch_bounds__(kBackwardThreads) void backward_kernel(const void *
             }
         }
         const float lo = float_of_bits(par.x), step = float_of_bits(par.y);
-        float s1 = 0.0f, s2 = 0.0f;
+        [[maybe_unused]] float s1 = 0.0f;
+        float s2 = 0.0f;
 #pragma unroll
         for (int e = 0; e < kBlock; ++e) {
             xq[e] = e < have ? decode(static_cast<uint32_t>(word >> (BITS * e)) & kLevels, lo, step) : 0.0f;
             if (partials != nullptr && e < have) {
                 acc_gamma[e] = add_rn(acc_gamma[e], mul_rn(gh[e], xq[e]));
-                acc_beta[e] = add_rn(acc_beta[e], gh[e]);
+                if constexpr (CENTRED) acc_beta[e] = add_rn(acc_beta[e], gh[e]);
             }
             gh[e] = mul_rn(gh[e], g[e]);                                                            // g^ (a missing element: +0)
-            s1 = add_rn(s1, gh[e]);
+            if constexpr (CENTRED) s1 = add_rn(s1, gh[e]);
             s2 = add_rn(s2, mul_rn(gh[e], xq[e]));
         }
-        const float m1 = div_rn(row_sum<LPR>(s1, slots[0]), count), m2 = div_rn(row_sum<LPR>(s2, slots[1]), count);
+        float m1 = 0.0f, m2;
+        if constexpr (CENTRED) {
+            m1 = div_rn(row_sum<LPR>(s1, slots[0]), count);
+            m2 = div_rn(row_sum<LPR>(s2, slots[1]), count);
+        } else {
+            m2 = div_rn(row_sum<LPR>(s2, slots[iteration & 1]), count);
+            ++iteration;
+        }
         if (dx != nullptr) {
             const float rstd = live ? rstd_in[r] : 0.0f;
             float o[kBlock];
 #pragma unroll
-            for (int e = 0; e < kBlock; ++e) o[e] = mul_rn(rstd, sub_rn(sub_rn(gh[e], m1), mul_rn(xq[e], m2)));
+            for (int e = 0; e < kBlock; ++e) o[e] = mul_rn(rstd, sub_rn(CENTRED ? sub_rn(gh[e], m1) : gh[e], mul_rn(xq[e], m2)));
             store_block<DT>(dr + i0, aligned16(dr), have, o);
         }
     }
     if (partials == nullptr) return;                                                                // (the same for every lane of the grid)
     float *mine = partials + static_cast<size_t>(blockIdx.x) * 2 * kPadded;
+    constexpr int kSums = CENTRED ? 2 : 1;
     if constexpr (kRowsPerTile == 1) {
-        float4 *pg = reinterpret_cast<float4 *>(mine + i0), *pb = reinterpret_cast<float4 *>(mine + kPadded + i0);
+        float4 *pg = reinterpret_cast<float4 *>(mine + i0);
+        [[maybe_unused]] float4 *pb = reinterpret_cast<float4 *>(mine + kPadded + i0);
         pg[0] = float4{acc_gamma[0], acc_gamma[1], acc_gamma[2], acc_gamma[3]};
         pg[1] = float4{acc_gamma[4], acc_gamma[5], acc_gamma[6], acc_gamma[7]};
-        pb[0] = float4{acc_beta[0], acc_beta[1], acc_beta[2], acc_beta[3]};
-        pb[1] = float4{acc_beta[4], acc_beta[5], acc_beta[6], acc_beta[7]};
+        if constexpr (CENTRED) {
+            pb[0] = float4{acc_beta[0], acc_beta[1], acc_beta[2], acc_beta[3]};
+            pb[1] = float4{acc_beta[4], acc_beta[5], acc_beta[6], acc_beta[7]};
+        }
     } else {
         // [row of the tile][column], first for gy x^q, then for gy: the rows of the tile are added in ascending order, a lane per column
 #pragma unroll
-        for (int which = 0; which < 2; ++which) {
+        for (int which = 0; which < kSums; ++which) {
             if (which == 1) __syncthreads();                                                        // (the first sum has been read)
 #pragma unroll
             for (int e = 0; e < kBlock; ++e) shared_sums[sub * kPadded + i0 + e] = which == 0 ? acc_gamma[e] : acc_beta[e];
@@ -394,61 +434,68 @@ struct BackwardArgs {
     const void *gy; const uint8_t *state; const float *rstd; const void *gamma; size_t rows; uint32_t width; void *dx; float *partials;
 };
 
-template <int DT, int BITS, int LPR, int K> void launch(unsigned grid, hipStream_t s, const ForwardArgs &a) {
-    hipLaunchKernelGGL((forward_kernel<DT, BITS, LPR, K>), dim3(grid), dim3(kThreads), 0, s, a.x, a.rows, a.width, a.gamma, a.beta, a.eps, a.key, a.device, a.y,
-                       a.rstd, a.state, a.xhat);
+template <int DT, int BITS, int LPR, int K, bool CENTRED> void launch(unsigned grid, hipStream_t s, const ForwardArgs &a) {
+    hipLaunchKernelGGL((forward_kernel<DT, BITS, LPR, K, CENTRED>), dim3(grid), dim3(kThreads), 0, s, a.x, a.rows, a.width, a.gamma, a.beta, a.eps, a.key, a.device,
+                       a.y, a.rstd, a.state, a.xhat);
 }
-template <int DT, int BITS> void launch_plan(Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
-    if (p.lpr == 8) launch<DT, BITS, 8, 1>(grid, s, a);
-    else if (p.lpr == 16) launch<DT, BITS, 16, 1>(grid, s, a);
-    else if (p.lpr == 64) launch<DT, BITS, 64, 1>(grid, s, a);
-    else if (p.lpr == 128) launch<DT, BITS, 128, 1>(grid, s, a);
-    else if (p.k == 1) launch<DT, BITS, 256, 1>(grid, s, a);
-    else if (p.k == 2) launch<DT, BITS, 256, 2>(grid, s, a);
-    else launch<DT, BITS, 256, 4>(grid, s, a);
+template <int DT, int BITS, bool CENTRED> void launch_plan(Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
+    if (p.lpr == 8) launch<DT, BITS, 8, 1, CENTRED>(grid, s, a);
+    else if (p.lpr == 16) launch<DT, BITS, 16, 1, CENTRED>(grid, s, a);
+    else if (p.lpr == 64) launch<DT, BITS, 64, 1, CENTRED>(grid, s, a);
+    else if (p.lpr == 128) launch<DT, BITS, 128, 1, CENTRED>(grid, s, a);
+    else if (p.k == 1) launch<DT, BITS, 256, 1, CENTRED>(grid, s, a);
+    else if (p.k == 2) launch<DT, BITS, 256, 2, CENTRED>(grid, s, a);
+    else launch<DT, BITS, 256, 4, CENTRED>(grid, s, a);
 }
-template <int DT, int BITS, int LPR> void launch_backward_lanes(unsigned grid, hipStream_t s, const BackwardArgs &a) {
+template <int DT, int BITS, int LPR, bool CENTRED> void launch_backward_lanes(unsigned grid, hipStream_t s, const BackwardArgs &a) {
     if constexpr (BITS != 0)
-        hipLaunchKernelGGL((backward_kernel<DT, BITS, LPR>), dim3(grid), dim3(kBackwardThreads), 0, s, a.gy, a.state, a.rstd, a.gamma, a.rows, a.width, a.dx, a.partials);
+        hipLaunchKernelGGL((backward_kernel<DT, BITS, LPR, CENTRED>), dim3(grid), dim3(kBackwardThreads), 0, s, a.gy, a.state, a.rstd, a.gamma, a.rows, a.width, a.dx,
+                           a.partials);
 }
-template <int DT, int BITS> void launch_plan(Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
-    if (p.lpr == 8) launch_backward_lanes<DT, BITS, 8>(grid, s, a);
-    else if (p.lpr == 16) launch_backward_lanes<DT, BITS, 16>(grid, s, a);
-    else if (p.lpr == 64) launch_backward_lanes<DT, BITS, 64>(grid, s, a);
-    else if (p.lpr == 128) launch_backward_lanes<DT, BITS, 128>(grid, s, a);
-    else if (p.lpr == 256) launch_backward_lanes<DT, BITS, 256>(grid, s, a);
-    else if (p.lpr == 512) launch_backward_lanes<DT, BITS, 512>(grid, s, a);
-    else launch_backward_lanes<DT, BITS, 1024>(grid, s, a);
+template <int DT, int BITS, bool CENTRED> void launch_plan(Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
+    if (p.lpr == 8) launch_backward_lanes<DT, BITS, 8, CENTRED>(grid, s, a);
+    else if (p.lpr == 16) launch_backward_lanes<DT, BITS, 16, CENTRED>(grid, s, a);
+    else if (p.lpr == 64) launch_backward_lanes<DT, BITS, 64, CENTRED>(grid, s, a);
+    else if (p.lpr == 128) launch_backward_lanes<DT, BITS, 128, CENTRED>(grid, s, a);
+    else if (p.lpr == 256) launch_backward_lanes<DT, BITS, 256, CENTRED>(grid, s, a);
+    else if (p.lpr == 512) launch_backward_lanes<DT, BITS, 512, CENTRED>(grid, s, a);
+    else launch_backward_lanes<DT, BITS, 1024, CENTRED>(grid, s, a);
 }
-template <int DT, class Args> void launch_bits(int bits, Plan p, unsigned grid, hipStream_t s, const Args &a) {
-    if (bits == 0) launch_plan<DT, 0>(p, grid, s, a);
-    else if (bits == 2) launch_plan<DT, 2>(p, grid, s, a);
-    else if (bits == 4) launch_plan<DT, 4>(p, grid, s, a);
-    else launch_plan<DT, 8>(p, grid, s, a);
+template <int DT, bool CENTRED, class Args> void launch_bits(int bits, Plan p, unsigned grid, hipStream_t s, const Args &a) {
+    if (bits == 0) launch_plan<DT, 0, CENTRED>(p, grid, s, a);
+    else if (bits == 2) launch_plan<DT, 2, CENTRED>(p, grid, s, a);
+    else if (bits == 4) launch_plan<DT, 4, CENTRED>(p, grid, s, a);
+    else launch_plan<DT, 8, CENTRED>(p, grid, s, a);
 }
-// one unit per dtype (-DFEWBIT_NORM_TU=0 / 1 / 2: fp32 with the C entry points, fp16, bf16), compiled in parallel and linked into one library
+// one unit per dtype and kind, compiled in parallel and linked into one library: -DFEWBIT_NORM_TU=0 / 1 / 2 the layer norm (fp32 with the C entry
+// points of both norms and the column sums, fp16, bf16), 3 / 4 / 5 the RMS norm in the same order of dtypes
 #ifndef FEWBIT_NORM_TU
 #define FEWBIT_NORM_TU 0
 #endif
-constexpr int kUnitDtype = FEWBIT_NORM_TU == 0 ? FEWBIT_F32 : FEWBIT_NORM_TU == 1 ? FEWBIT_F16 : FEWBIT_BF16;
-template <int DT> FEWBIT_HIDDEN void launch_forward(int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a);
-template <int DT> FEWBIT_HIDDEN void launch_backward(int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a);
-template <> void launch_forward<kUnitDtype>(int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) { launch_bits<kUnitDtype>(bits, p, grid, s, a); }
-template <> void launch_backward<kUnitDtype>(int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) { launch_bits<kUnitDtype>(bits, p, grid, s, a); }
+constexpr int kUnitDtype = FEWBIT_NORM_TU % 3 == 0 ? FEWBIT_F32 : FEWBIT_NORM_TU % 3 == 1 ? FEWBIT_F16 : FEWBIT_BF16;
+constexpr bool kUnitCentred = FEWBIT_NORM_TU < 3;
+template <int DT, bool CENTRED> FEWBIT_HIDDEN void launch_forward(int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a);
+template <int DT, bool CENTRED> FEWBIT_HIDDEN void launch_backward(int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a);
+template <> void launch_forward<kUnitDtype, kUnitCentred>(int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
+    launch_bits<kUnitDtype, kUnitCentred>(bits, p, grid, s, a);
+}
+template <> void launch_backward<kUnitDtype, kUnitCentred>(int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
+    launch_bits<kUnitDtype, kUnitCentred>(bits, p, grid, s, a);
+}
 
 #if FEWBIT_NORM_TU == 0
-void launch_dtype(int dtype, int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
+template <bool CENTRED> void launch_dtype(int dtype, int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
     switch (dtype) {
-    case FEWBIT_F32: launch_forward<FEWBIT_F32>(bits, p, grid, s, a); break;
-    case FEWBIT_F16: launch_forward<FEWBIT_F16>(bits, p, grid, s, a); break;
-    default: launch_forward<FEWBIT_BF16>(bits, p, grid, s, a); break;
+    case FEWBIT_F32: launch_forward<FEWBIT_F32, CENTRED>(bits, p, grid, s, a); break;
+    case FEWBIT_F16: launch_forward<FEWBIT_F16, CENTRED>(bits, p, grid, s, a); break;
+    default: launch_forward<FEWBIT_BF16, CENTRED>(bits, p, grid, s, a); break;
     }
 }
-void launch_dtype(int dtype, int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
+template <bool CENTRED> void launch_dtype(int dtype, int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
     switch (dtype) {
-    case FEWBIT_F32: launch_backward<FEWBIT_F32>(bits, p, grid, s, a); break;
-    case FEWBIT_F16: launch_backward<FEWBIT_F16>(bits, p, grid, s, a); break;
-    default: launch_backward<FEWBIT_BF16>(bits, p, grid, s, a); break;
+    case FEWBIT_F32: launch_backward<FEWBIT_F32, CENTRED>(bits, p, grid, s, a); break;
+    case FEWBIT_F16: launch_backward<FEWBIT_F16, CENTRED>(bits, p, grid, s, a); break;
+    default: launch_backward<FEWBIT_BF16, CENTRED>(bits, p, grid, s, a); break;
     }
 }
 
@@ -460,6 +507,75 @@ int check_shape(const char *name, int dtype, size_t rows, size_t width) {
     if (width == 0 || width > kMaxWidth) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: width = %zu is outside 1 .. %zu", name, width, kMaxWidth);
     if (rows == 0) return 1;
     if (rows > kMaxCount / width) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: rows * width = %zu * %zu is beyond 2^36", name, rows, width);
+    return FEWBIT_OK;
+}
+
+// the forward entry point of either norm: the refusals, the plan, ONE launch (the RMS norm: beta = NULL)
+template <bool CENTRED>
+int forward_call(const char *name, int dtype, const void *x, size_t rows, size_t width, const void *gamma, const void *beta, double eps, int bits, uint64_t seed,
+                 const uint64_t *seed_device, void *y, float *rstd, uint8_t *state, size_t state_bytes, float *xhat_out, void *stream) {
+    const int shape = check_shape(name, dtype, rows, width);
+    if (shape < 0) return shape;
+    if (state != nullptr && !known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: bits = %d is not 2, 4 or 8", name, bits);
+    if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: eps = %g is not a finite number >= 0", name, eps);
+    if (misaligned(seed_device, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the seed word in device memory must be 8-byte aligned", name);
+    if (shape == 1) return FEWBIT_OK;
+    if (x == nullptr || y == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (x or y)", name);
+    if (state != nullptr && rstd == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (rstd goes with the state)", name);
+    const size_t size = size_of(dtype);
+    if (misaligned(x, size) || misaligned(y, size) || misaligned(gamma, size) || misaligned(beta, size))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: %s must be aligned to their element size", name, CENTRED ? "x, y, gamma and beta" : "x, y and gamma");
+    if (misaligned(rstd, 4) || misaligned(xhat_out, 4)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: rstd and xhat_out must be 4-byte aligned", name);
+    if (misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: state must be 8-byte aligned", name);
+    if (state != nullptr) {
+        const size_t need = state_bytes_of(rows, width, bits);
+        if (state_bytes < need) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: state has %zu bytes, %zu are needed", name, state_bytes, need);
+    }
+    const Plan p = plan_of(width);
+    const size_t tiles = tiles_of(rows, p, kThreads);
+    const unsigned grid = static_cast<unsigned>(tiles < kMaxGridForward ? tiles : kMaxGridForward);
+    const ForwardArgs a{x, rows, static_cast<uint32_t>(width), gamma, beta, static_cast<float>(eps), sketch::key_of(seed), reinterpret_cast<const Key *>(seed_device),
+                        y, rstd, state, xhat_out};
+    launch_dtype<CENTRED>(dtype, state != nullptr ? bits : 0, p, grid, static_cast<hipStream_t>(stream), a);
+    return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
+}
+
+// the backward entry point of either norm: the refusals, the plan, the launch of dx and the partials, then the column sums (the RMS norm: dbeta =
+// NULL, and the column sums are launched for dgamma alone)
+template <bool CENTRED>
+int backward_call(const char *name, int dtype, const void *gy, const uint8_t *state, const float *rstd, const void *gamma, size_t rows, size_t width, int bits,
+                  void *dx, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream) {
+    const int shape = check_shape(name, dtype, rows, width);
+    if (shape < 0) return shape;
+    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: bits = %d is not 2, 4 or 8", name, bits);
+    if (shape == 1) return FEWBIT_OK;
+    if (gy == nullptr || state == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (gy or state)", name);
+    if (dx != nullptr && rstd == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (dx needs rstd)", name);
+    const size_t size = size_of(dtype);
+    if (misaligned(gy, size) || misaligned(dx, size) || misaligned(gamma, size))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: gy, dx and gamma must be aligned to their element size", name);
+    if (misaligned(rstd, 4) || misaligned(dgamma, 4) || misaligned(dbeta, 4))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", name, CENTRED ? "rstd, dgamma and dbeta" : "rstd and dgamma");
+    if (misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: state must be 8-byte aligned", name);
+    const bool sums = dgamma != nullptr || dbeta != nullptr;
+    if (dx == nullptr && !sums) return FEWBIT_OK;
+    const size_t need = workspace_of(rows, width);
+    if (sums && (workspace == nullptr || misaligned(workspace, 16))) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the workspace must be 16-byte aligned", name);
+    if (sums && workspace_bytes < need) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the workspace has %zu bytes, %zu are needed", name, workspace_bytes, need);
+    const Plan p = backward_plan_of(width);
+    const size_t tiles = tiles_of(rows, p, kBackwardThreads);
+    const unsigned grid = static_cast<unsigned>(tiles < kMaxGridBackward ? tiles : kMaxGridBackward);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const BackwardArgs a{gy, state, rstd, gamma, rows, static_cast<uint32_t>(width), dx, sums ? static_cast<float *>(workspace) : nullptr};
+    launch_dtype<CENTRED>(dtype, bits, p, grid, s, a);
+    if (hipGetLastError() != hipSuccess) return fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
+    if (sums) {
+        // a workgroup per 64 columns of each sum; the un-centred backward wrote only the first half of the partials, and only that is read
+        const unsigned chunks = (CENTRED ? 2 : 1) * static_cast<unsigned>((width + 63) / 64);
+        hipLaunchKernelGGL(column_sums_kernel, dim3(chunks), dim3(kBackwardThreads), 0, s, static_cast<const float *>(workspace), grid,
+                           static_cast<uint32_t>(padded_width(p)), static_cast<uint32_t>(width), dgamma, dbeta);
+        if (hipGetLastError() != hipSuccess) return fail(FEWBIT_ERR_LAUNCH, "%s: the launch of the column sums failed", name);
+    }
     return FEWBIT_OK;
 }
 
@@ -544,67 +660,23 @@ int fewbit_hipx_norm_state_unpack_host(const uint8_t *state_host, size_t rows, s
 
 int fewbit_hipx_layer_norm_forward(int dtype, const void *x, size_t rows, size_t width, const void *gamma, const void *beta, double eps, int bits, uint64_t seed,
                                    const uint64_t *seed_device, void *y, float *rstd, uint8_t *state, size_t state_bytes, float *xhat_out, void *stream) {
-    const char *name = "layer_norm_forward";
-    const int shape = check_shape(name, dtype, rows, width);
-    if (shape < 0) return shape;
-    if (state != nullptr && !known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: bits = %d is not 2, 4 or 8", name, bits);
-    if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: eps = %g is not a finite number >= 0", name, eps);
-    if (misaligned(seed_device, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the seed word in device memory must be 8-byte aligned", name);
-    if (shape == 1) return FEWBIT_OK;
-    if (x == nullptr || y == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (x or y)", name);
-    if (state != nullptr && rstd == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (rstd goes with the state)", name);
-    const size_t size = size_of(dtype);
-    if (misaligned(x, size) || misaligned(y, size) || misaligned(gamma, size) || misaligned(beta, size))
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: x, y, gamma and beta must be aligned to their element size", name);
-    if (misaligned(rstd, 4) || misaligned(xhat_out, 4)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: rstd and xhat_out must be 4-byte aligned", name);
-    if (misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: state must be 8-byte aligned", name);
-    if (state != nullptr) {
-        const size_t need = state_bytes_of(rows, width, bits);
-        if (state_bytes < need) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: state has %zu bytes, %zu are needed", name, state_bytes, need);
-    }
-    const Plan p = plan_of(width);
-    const size_t tiles = tiles_of(rows, p, kThreads);
-    const unsigned grid = static_cast<unsigned>(tiles < kMaxGridForward ? tiles : kMaxGridForward);
-    const ForwardArgs a{x, rows, static_cast<uint32_t>(width), gamma, beta, static_cast<float>(eps), sketch::key_of(seed), reinterpret_cast<const Key *>(seed_device),
-                        y, rstd, state, xhat_out};
-    launch_dtype(dtype, state != nullptr ? bits : 0, p, grid, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
+    return forward_call<kCentred>("layer_norm_forward", dtype, x, rows, width, gamma, beta, eps, bits, seed, seed_device, y, rstd, state, state_bytes, xhat_out, stream);
 }
 
 int fewbit_hipx_layer_norm_backward(int dtype, const void *gy, const uint8_t *state, const float *rstd, const void *gamma, size_t rows, size_t width, int bits,
                                     void *dx, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream) {
-    const char *name = "layer_norm_backward";
-    const int shape = check_shape(name, dtype, rows, width);
-    if (shape < 0) return shape;
-    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: bits = %d is not 2, 4 or 8", name, bits);
-    if (shape == 1) return FEWBIT_OK;
-    if (gy == nullptr || state == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (gy or state)", name);
-    if (dx != nullptr && rstd == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (dx needs rstd)", name);
-    const size_t size = size_of(dtype);
-    if (misaligned(gy, size) || misaligned(dx, size) || misaligned(gamma, size))
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: gy, dx and gamma must be aligned to their element size", name);
-    if (misaligned(rstd, 4) || misaligned(dgamma, 4) || misaligned(dbeta, 4))
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: rstd, dgamma and dbeta must be 4-byte aligned", name);
-    if (misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: state must be 8-byte aligned", name);
-    const bool sums = dgamma != nullptr || dbeta != nullptr;
-    if (dx == nullptr && !sums) return FEWBIT_OK;
-    const size_t need = workspace_of(rows, width);
-    if (sums && (workspace == nullptr || misaligned(workspace, 16))) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the workspace must be 16-byte aligned", name);
-    if (sums && workspace_bytes < need) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the workspace has %zu bytes, %zu are needed", name, workspace_bytes, need);
-    const Plan p = backward_plan_of(width);
-    const size_t tiles = tiles_of(rows, p, kBackwardThreads);
-    const unsigned grid = static_cast<unsigned>(tiles < kMaxGridBackward ? tiles : kMaxGridBackward);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const BackwardArgs a{gy, state, rstd, gamma, rows, static_cast<uint32_t>(width), dx, sums ? static_cast<float *>(workspace) : nullptr};
-    launch_dtype(dtype, bits, p, grid, s, a);
-    if (hipGetLastError() != hipSuccess) return fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
-    if (sums) {
-        const unsigned chunks = 2 * static_cast<unsigned>((width + 63) / 64);
-        hipLaunchKernelGGL(column_sums_kernel, dim3(chunks), dim3(kBackwardThreads), 0, s, static_cast<const float *>(workspace), grid,
-                           static_cast<uint32_t>(padded_width(p)), static_cast<uint32_t>(width), dgamma, dbeta);
-        if (hipGetLastError() != hipSuccess) return fail(FEWBIT_ERR_LAUNCH, "%s: the launch of the column sums failed", name);
-    }
-    return FEWBIT_OK;
+    return backward_call<kCentred>("layer_norm_backward", dtype, gy, state, rstd, gamma, rows, width, bits, dx, dgamma, dbeta, workspace, workspace_bytes, stream);
+}
+
+int fewbit_hipx_rms_norm_forward(int dtype, const void *x, size_t rows, size_t width, const void *gamma, double eps, int bits, uint64_t seed,
+                                 const uint64_t *seed_device, void *y, float *rstd, uint8_t *state, size_t state_bytes, float *xhat_out, void *stream) {
+    return forward_call<kUncentred>("rms_norm_forward", dtype, x, rows, width, gamma, nullptr, eps, bits, seed, seed_device, y, rstd, state, state_bytes, xhat_out,
+                                    stream);
+}
+
+int fewbit_hipx_rms_norm_backward(int dtype, const void *gy, const uint8_t *state, const float *rstd, const void *gamma, size_t rows, size_t width, int bits,
+                                  void *dx, float *dgamma, void *workspace, size_t workspace_bytes, void *stream) {
+    return backward_call<kUncentred>("rms_norm_backward", dtype, gy, state, rstd, gamma, rows, width, bits, dx, dgamma, nullptr, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

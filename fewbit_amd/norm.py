@@ -1,4 +1,4 @@
-"""LayerNorm that keeps its normalized input in 2, 4 or 8 bits per element for backward.
+"""LayerNorm and RMSNorm that keep their normalized input in 2, 4 or 8 bits per element for backward.
 
 ``torch.nn.LayerNorm`` saves its whole input plus a mean and an rstd per row, and in a transformer that input is the residual sum, which no
 other node saves.  Here the node keeps the NORMALIZED rows ``x^ = (x - mean) * rstd`` in the packed form of a seed (include/fewbit_hipx.h, "the
@@ -26,6 +26,14 @@ code per 64 elements suits best, and backward needs nothing else but gamma.
   ``torch.cuda.default_generators[i]``): checkpoint saves and restores only those, and the recomputation must draw the forward's seed again.
 * A row with a NaN or an infinity gives NaN in that row of ``y`` and ``dx`` and in every column of ``dgamma``, as with torch.
 * Not differentiable twice (``once_differentiable``).
+
+``QuantizedRMSNorm`` / ``rms_norm_quantized`` are the same node for ``torch.nn.RMSNorm`` (every model of the Llama / Mistral / Qwen / T5 family):
+``x^ = x * rstd`` with ``rstd = 1 / sqrt(mean(x^2) + eps)``, ``y = x^ * gamma``, the same state of ``x^``, and backward without the mean term and
+without beta: ``dx = rstd * (g^ - x^q * mean(g^ * x^q))``, ``dgamma = sum_r gy * x^q`` (include/fewbit_hipx.h, "The un-centred rows").  Every rule
+above holds for it; the bias of ``dx`` is the same ``-rstd * g^_i * Var(x^q_i) / width``.  Its non-finite values are those of the fp32 arithmetic
+and of torch's own formulation: a NaN element makes its row NaN; an INFINITE element makes ``mean(x^2)`` infinite, so ``rstd`` is 0 and ``x^`` is
+NaN at that element and +-0 elsewhere -- the group that holds it is poisoned, ``dx`` of the row is NaN and ``dgamma`` is NaN in that group's
+columns.  A finite row whose fp32 sum of squares overflows (bf16 values near 1e20) gives ``rstd`` = 0 and ``y`` = +-0.
 """
 import math
 from typing import Optional, Sequence, Union
@@ -36,7 +44,7 @@ from torch.autograd.function import once_differentiable
 
 from . import linear
 
-__all__ = ('layer_norm_quantized', 'QuantizedLayerNorm')
+__all__ = ('layer_norm_quantized', 'QuantizedLayerNorm', 'rms_norm_quantized', 'QuantizedRMSNorm')
 
 _KERNEL_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
 _MAX_WIDTH = 8192                                # cabi_x.NORM_MAX_WIDTH
@@ -204,6 +212,151 @@ class QuantizedLayerNorm(torch.nn.LayerNorm):
             # eval mode is not where activation memory is short: gradients asked for there are torch's exact ones, nothing is rounded or drawn
             return F.layer_norm(input, self.normalized_shape, self.weight, self.bias, self.eps)
         return layer_norm_quantized(input, self.normalized_shape, self.weight, self.bias, self.eps, self.bits, self.generator)
+
+    def extra_repr(self) -> str:
+        return f'{super().extra_repr()}, bits={self.bits}'
+
+
+# ---- the RMS norm: the un-centred statistic, backward without the mean term, no beta -----------------------------------------------------
+def _scaled_rows(flat: torch.Tensor, eps: float):
+    """(x^, rstd) of the rows of ``flat`` in fp32 (fp64 for a float64 input): ``x^ = x * rstd``, ``rstd = 1 / sqrt(mean(x^2) + eps)``"""
+    work = flat.to(torch.float64 if flat.dtype == torch.float64 else torch.float32)
+    rstd = 1.0 / torch.sqrt(work.square().mean(dim=1, keepdim=True) + eps)
+    return work * rstd, rstd.reshape(-1)
+
+
+def _rms_backward_formula(gy: torch.Tensor, xq: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor]):
+    """(dx, dgamma) of the definition in the dtype of ``xq``"""
+    gy = gy.to(xq.dtype)
+    gh = gy if gamma is None else gy * gamma.reshape(1, -1).to(xq.dtype)
+    dx = rstd[:, None] * (gh - xq * (gh * xq).mean(dim=1, keepdim=True))
+    return dx, (gy * xq).sum(dim=0)
+
+
+class _RMSNormQuantized(torch.autograd.Function):
+    """``F.rms_norm`` that keeps ``x^`` in ``bits`` bits per element (module docstring).  Kept for backward exactly what ``_LayerNormQuantized``
+    keeps: on the kernels the state, ``rstd`` and gamma; in the PyTorch formulation the codes, lo and step of every group, ``rstd`` and gamma."""
+
+    @staticmethod
+    def forward(ctx, input, weight, normalized_shape, eps: float, bits: int, generator):
+        width = math.prod(normalized_shape)
+        flat = input.detach().reshape(-1, width)
+        ctx.bits, ctx.flat_shape, ctx.input_dtype, ctx.has_weight = bits, tuple(flat.shape), input.dtype, weight is not None
+        ctx.autocast = linear._autocast_seen(input.device.type)
+        ctx.native_seed = None
+        if _kernel_applies(flat, weight, None):
+            from . import cabi_x
+            ctx.native_seed = linear._sketch_seed(generator, flat.device)
+            y, rstd, state, _ = cabi_x.rms_norm_forward(flat if flat.is_contiguous() else flat.contiguous(), _as(weight, flat.dtype), eps, bits, ctx.native_seed)
+            ctx.save_for_backward(state, rstd, *((weight, ) if ctx.has_weight else ()))
+            return y.view(input.shape)
+        xhat, rstd = _scaled_rows(flat, eps)
+        ctx.save_for_backward(*linear._quantize_groups(_padded_rows(xhat), bits, generator), rstd, *((weight, ) if ctx.has_weight else ()))
+        return F.rms_norm(input, normalized_shape, weight, eps)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        with linear._autocast_as(ctx.autocast):
+            return _RMSNormQuantized._backward(ctx, linear._dense_rows(grad_output))
+
+    @staticmethod
+    def _backward(ctx, grad_output):
+        saved = ctx.saved_tensors                       # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
+        weight = saved[-1] if ctx.has_weight else None
+        rows, width = ctx.flat_shape
+        gy = grad_output.reshape(rows, width)
+        want = tuple(ctx.needs_input_grad[:2])
+        if ctx.native_seed is not None:
+            from . import cabi_x
+            gy = gy if gy.dtype in _KERNEL_DTYPES else gy.float()
+            dx, dgamma = cabi_x.rms_norm_backward(gy, saved[0], saved[1], _as(weight, gy.dtype), ctx.bits, want)
+        else:
+            codes, lo, step, rstd = saved[:4]
+            dx, dgamma = _rms_backward_formula(gy, _decoded_rows(codes, lo, step, rows, width), rstd, weight)
+        grad_input = dx.to(ctx.input_dtype).view(grad_output.shape) if want[0] else None
+        grad_weight = dgamma.to(weight.dtype).view(weight.shape) if want[1] else None
+        return grad_input, grad_weight, None, None, None, None
+
+
+def rms_norm_quantized(input: torch.Tensor, normalized_shape: Union[int, Sequence[int]], weight: Optional[torch.Tensor] = None, eps: Optional[float] = None,
+                       bits: int = 4, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """``F.rms_norm(input, normalized_shape, weight, eps)`` that keeps the normalized rows ``x * rstd`` in ``bits`` = 2, 4 or 8 bits per element
+    (plus one fp32 ``rstd`` per row) instead of the input: the output is the exact RMS norm (``x^ * gamma`` in fp32, rounded ONCE), ``grad_weight``
+    is unbiased, ``grad_input`` carries the bias ``-rstd * g^_i * Var(x^q_i) / width``, second order in the rounding step (module docstring).
+    ``eps=None`` means ``torch.finfo(input.dtype).eps``, the default ``F.rms_norm`` documents (for a 16-bit host tensor torch 2.10's own
+    composite takes the epsilon of its fp32 arithmetic instead; pass ``eps`` to be independent of that).  ``generator``, grad mode off, ``torch.autocast`` and
+    ``torch.utils.checkpoint``: the rules of :func:`layer_norm_quantized`."""
+    if bits not in linear.QUANT_BITS:
+        raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+    normalized_shape = (normalized_shape, ) if isinstance(normalized_shape, int) else tuple(normalized_shape)
+    if tuple(input.shape[input.dim() - len(normalized_shape):]) != normalized_shape or not normalized_shape:
+        return F.rms_norm(input, normalized_shape, weight, eps)                           # (torch words the refusal)
+    eps = float(torch.finfo(input.dtype).eps if eps is None else eps)
+    if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (input, weight)):
+        flat = input.detach().reshape(-1, math.prod(normalized_shape))
+        if not _kernel_applies(flat, weight, None):
+            return F.rms_norm(input, normalized_shape, weight, eps)
+        from . import cabi_x
+        y, _, _, _ = cabi_x.rms_norm_forward(flat if flat.is_contiguous() else flat.contiguous(), _as(weight, flat.dtype), eps, keep=False)
+        return y.view(input.shape)
+    return _RMSNormQuantized.apply(input, weight, normalized_shape, eps, int(bits), generator)
+
+
+class QuantizedRMSNorm(torch.nn.RMSNorm):
+    r"""Drop-in :class:`torch.nn.RMSNorm` that keeps its normalized input in ``bits`` bits per element, plus one fp32 per row, instead of the
+    input itself (:func:`rms_norm_quantized`); the output is that of ``nn.RMSNorm``.
+
+    Parameters (after those of ``nn.RMSNorm``)
+    ----------
+    bits : {2, 4, 8}, default=4
+        Bits per kept element.  Groups of 64 elements of a row share a minimum and a step (8 more bytes per group): a bf16 input is kept in
+        0.1875, 0.3125 or 0.5625 of its bytes.  The rounding is stochastic; the weight gradient is unbiased, the input gradient up to
+        ``-rstd * g^_i * Var(x^q_i) / width``, a term of second order in the step.
+    generator : torch.Generator, optional
+        Source of the rounding's randomness, as for :class:`QuantizedLayerNorm` (inside ``torch.utils.checkpoint``: a default generator).
+
+    Under ``torch.autocast`` the output keeps the input's dtype on the kernel path.  ``m.eval()`` keeps no state and draws no seed: without
+    gradients the call is the plain forward, and gradients asked for in eval mode are ``F.rms_norm``'s exact ones.
+
+    Examples:
+
+        >>> m = fewbit.QuantizedRMSNorm(4096, eps=1e-6, bits=4)
+        >>> swap = lambda m, path: fewbit.QuantizedRMSNorm.from_rms_norm(m, bits=4) if type(m).__name__.endswith('RMSNorm') else m
+        >>> model = fewbit.map_module(model, swap)
+    """
+
+    def __init__(self, normalized_shape, eps: Optional[float] = None, elementwise_affine: bool = True, device=None, dtype=None, bits: int = 4,
+                 generator: Optional[torch.Generator] = None) -> None:
+        if bits not in linear.QUANT_BITS:
+            raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+        super().__init__(normalized_shape, eps, elementwise_affine, device, dtype)
+        self.bits = bits
+        self.generator = generator
+
+    @classmethod
+    def from_rms_norm(cls, module: torch.nn.Module, bits: int = 4, generator: Optional[torch.Generator] = None) -> 'QuantizedRMSNorm':
+        """A ``QuantizedRMSNorm`` that SHARES the weight of ``module``: a ``torch.nn.RMSNorm``, or any module with a 1-D ``weight`` and a float
+        ``variance_epsilon`` or ``eps`` (the ``LlamaRMSNorm`` / ``T5LayerNorm`` family of Hugging Face models), so that ``map_module`` can swap
+        the norms of a built model.  Those modules round ``x^`` to the input's dtype BEFORE they multiply by the weight; here ``x^ * weight`` is
+        formed in fp32 and rounded once, so a 16-bit output may differ from theirs in its last bit."""
+        if isinstance(module, torch.nn.RMSNorm):
+            shape, eps, affine = module.normalized_shape, module.eps, module.elementwise_affine
+        else:
+            weight = getattr(module, 'weight', None)
+            eps = getattr(module, 'variance_epsilon', getattr(module, 'eps', None))
+            if not isinstance(weight, torch.Tensor) or weight.dim() != 1 or not isinstance(eps, float):
+                raise TypeError(f'{type(module).__name__} is neither a torch.nn.RMSNorm nor a module with a 1-D weight and a float variance_epsilon or eps')
+            shape, affine = tuple(weight.shape), True
+        new = cls(shape, eps, affine, device='meta', bits=bits, generator=generator)
+        new.weight = module.weight
+        return new.train(module.training)
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        if not self.training and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, self.weight)):
+            # eval mode is not where activation memory is short: gradients asked for there are torch's exact ones, nothing is rounded or drawn
+            return F.rms_norm(input, self.normalized_shape, self.weight, self.eps)
+        return rms_norm_quantized(input, self.normalized_shape, self.weight, self.eps, self.bits, self.generator)
 
     def extra_repr(self) -> str:
         return f'{super().extra_repr()}, bits={self.bits}'

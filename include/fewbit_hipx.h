@@ -38,7 +38,9 @@ extern "C" {
  * So was the packed form of a seed (fewbit_hipx_quant_bytes, _quant_pack_host, _quant_unpack_host, _quant_pack, _quant_unpack): inside
  * revision 2, recognised by the presence of the symbols.
  * So were the normalized rows of a seed (fewbit_hipx_norm_state_bytes, _norm_workspace, _norm_state_host, _norm_state_unpack_host,
- * _layer_norm_forward, _layer_norm_backward): inside revision 2, recognised by the presence of the symbols. */
+ * _layer_norm_forward, _layer_norm_backward): inside revision 2, recognised by the presence of the symbols.
+ * So were the un-centred rows, the RMS norm of the same state (fewbit_hipx_rms_norm_forward, _rms_norm_backward): inside revision 2, recognised by
+ * the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -342,6 +344,26 @@ int fewbit_hipx_quant_unpack(const uint8_t *packed, size_t n, int bits, int out_
  *   Since E[x^q] = x^, dgamma is unbiased.  dx is not exactly: x^q enters it twice, E[dx_q] - dx = -rstd * g^_i * Var(x^q_i) / width, second
  *     order in the step.
  *
+ * The un-centred rows (the RMS norm: what QuantizedRMSNorm keeps).  The same input, every step again ONE fp32 operation, contraction off:
+ *     ms      = (the sum of x * x over the row) / width
+ *     rstd    = 1 / sqrt(ms + float32(eps))            (an addition, a square root, a division)
+ *     x^      = x * rstd
+ *     y       = round_to_dtype(x^ * gamma)             gamma in the dtype of x, widened exactly; NULL counts as 1; rounded once
+ *     state   = the state of the normalized rows of a seed for these x^: the same groups per row, rounding bits, layout and size
+ *               fewbit_hipx_norm_state_bytes(rows, width, bits); fewbit_hipx_norm_state_host / _unpack_host serve both norms (the state is a
+ *               function of x^ only)
+ *   Backward, fp32, one operation per step:
+ *     x^q = decode(state), g^ = gy * gamma
+ *     dx  = round_to_dtype(rstd * (g^ - x^q * mean_row(g^ * x^q)))
+ *     dgamma = sum_r gy * x^q                                                                      as fp32
+ *   The order of a row sum is the kernel's, that of the layer norm; the per-workgroup partials of dgamma are added in the same fixed order.
+ *   Since E[x^q] = x^, dgamma is unbiased; E[dx_q] - dx = -rstd * g^_i * Var(x^q_i) / width, second order in the step, as for the layer norm.
+ *   NaN and infinity are what the fp32 arithmetic gives, and what torch's own formulation gives.  A NaN element makes its row of x^, y and dx NaN,
+ *     poisons every group of the row and makes dgamma NaN in every column.  An INFINITE element makes ms infinite, so rstd is 0 and x^ is NaN at
+ *     that element and +-0 elsewhere: the group that holds the NaN is poisoned by the rule of the packed form, dx of that row is NaN (the row
+ *     mean is), dgamma is NaN in that group's columns.  Other rows are untouched to the bit.  A finite row whose fp32 sum of squares overflows
+ *     (bf16 values near 1e20) gives rstd = 0 and x^ = y = +-0.
+ *
  * fewbit_hipx_norm_state_bytes: the size above; 0 for bits other than 2, 4, 8, width outside 1 .. 8192, rows = 0 and rows * width beyond 2^36.
  * fewbit_hipx_norm_workspace: bytes of scratch of fewbit_hipx_layer_norm_backward (16-byte aligned; the per-workgroup partial sums of dgamma and
  *   dbeta; contents are scratch); 0 for the same shapes.
@@ -358,6 +380,10 @@ int fewbit_hipx_quant_unpack(const uint8_t *packed, size_t n, int bits, int out_
  * fewbit_hipx_layer_norm_backward: TWO launches on `stream`: dx and per-workgroup partial sums, then the partials added in a fixed order.
  *   gy, dx, gamma   of `dtype`; dgamma, dbeta: width fp32.  dx, dgamma, dbeta may each be NULL: that output is skipped and nothing of it
  *                written (both sums NULL: one launch, no workspace needed).  rstd is read for dx only.
+ * fewbit_hipx_rms_norm_forward / fewbit_hipx_rms_norm_backward: the un-centred rows by the same kernels with the kind switched at compile time, the
+ *   contracts, refusals and alignment rules of the layer-norm pair without beta and dbeta: ONE row sum per tile forward and backward, state == NULL
+ *   the plain forward with the same y and rstd bytes, dx or dgamma NULL skipped and untouched, dgamma NULL one launch and no workspace, otherwise the
+ *   column sums are launched for dgamma alone.  fewbit_hipx_norm_workspace is the size query for both backwards.
  * Widths 1 .. 8192, rows * width <= 2^36.  The plan is a pure function of (rows, width): a row takes 8, 16, 64, 128 or 256 lanes (widths up to
  * 64, 128, 512, 1024, 2048), a lane one block of 8 elements; beyond 2048 elements a forward lane takes 2 blocks and beyond 4096 four, a backward
  * row 512 and 1024 lanes.  Forward: 256 lanes to a workgroup, at most 16384 workgroups; backward: 1024 lanes, at most 512 workgroups; beyond
@@ -375,6 +401,10 @@ int fewbit_hipx_layer_norm_forward(int dtype, const void *x, size_t rows, size_t
                                    const uint64_t *seed_device, void *y, float *rstd, uint8_t *state, size_t state_bytes, float *xhat_out, void *stream);
 int fewbit_hipx_layer_norm_backward(int dtype, const void *gy, const uint8_t *state, const float *rstd, const void *gamma, size_t rows, size_t width, int bits,
                                     void *dx, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream);
+int fewbit_hipx_rms_norm_forward(int dtype, const void *x, size_t rows, size_t width, const void *gamma, double eps, int bits, uint64_t seed,
+                                 const uint64_t *seed_device, void *y, float *rstd, uint8_t *state, size_t state_bytes, float *xhat_out, void *stream);
+int fewbit_hipx_rms_norm_backward(int dtype, const void *gy, const uint8_t *state, const float *rstd, const void *gamma, size_t rows, size_t width,
+                                  int bits, void *dx, float *dgamma, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
