@@ -24,16 +24,57 @@ LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().wi
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
 REVISION = 2                                   # FEWBIT_HIPX_REVISION: additions inside ABI version 1 (2: the crs entry points)
 
-# every symbol include/fewbit_hipx.h declares
-SYMBOLS = ('fewbit_hipx_abi_version', 'fewbit_hipx_last_error', 'fewbit_hipx_sampled_dft_workspace', 'fewbit_hipx_sampled_dft',
-           'fewbit_hipx_sampled_dft_seeded', 'fewbit_hipx_revision', 'fewbit_hipx_crs_columns', 'fewbit_hipx_crs_workspace', 'fewbit_hipx_crs_gather',
-           'fewbit_hipx_crs_scatter', 'fewbit_hipx_sampled_rows_ceil', 'fewbit_hipx_sampled_dct_zext', 'fewbit_hipx_sampled_dct_zext_seeded',
-           'fewbit_hipx_sampled_dft_zext', 'fewbit_hipx_sampled_dft_zext_seeded', 'fewbit_hipx_moments_workspace', 'fewbit_hipx_row_moments',
-           'fewbit_hipx_sum_squares', 'fewbit_hipx_dropout_threshold', 'fewbit_hipx_dropout_keep', 'fewbit_hipx_dropout', 'fewbit_hipx_sampled_signs',
-           'fewbit_hipx_sampled_dct_signed', 'fewbit_hipx_sampled_dft_signed', 'fewbit_hipx_quant_bytes', 'fewbit_hipx_quant_pack_host',
-           'fewbit_hipx_quant_unpack_host', 'fewbit_hipx_quant_pack', 'fewbit_hipx_quant_unpack', 'fewbit_hipx_norm_state_bytes', 'fewbit_hipx_norm_workspace',
-           'fewbit_hipx_norm_state_host', 'fewbit_hipx_norm_state_unpack_host', 'fewbit_hipx_layer_norm_forward', 'fewbit_hipx_layer_norm_backward', 'fewbit_hipx_rms_norm_forward',
-           'fewbit_hipx_rms_norm_backward')
+_vp, _sz, _i32, _u32, _u64, _dbl = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double
+
+# every symbol include/fewbit_hipx.h declares: (restype, argtypes).  The ONE list: ``SYMBOLS`` is its keys, ``lib()`` refuses a library that lacks one
+# of them and types every one of them from here, so no entry point can be called with ctypes' default conversions.
+_SIGNATURES = {
+    'fewbit_hipx_abi_version': (_i32, []),
+    'fewbit_hipx_last_error': (ctypes.c_char_p, []),
+    'fewbit_hipx_sampled_dft_workspace': (_sz, [_i32, _sz, _sz, _sz]),
+    'fewbit_hipx_sampled_dft': (_i32, [_i32, _vp, _sz, _sz, _sz, _vp, _sz, _dbl, _i32, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_sampled_dft_seeded': (_i32, [_i32, _vp, _sz, _sz, _sz, _u64, _vp, _sz, _dbl, _i32, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_revision': (_i32, []),
+    'fewbit_hipx_crs_columns': (_i32, [_u64, _sz, _sz, _vp, _vp, ctypes.POINTER(_sz)]),
+    'fewbit_hipx_crs_workspace': (_sz, [_i32, _sz, _sz, _sz]),
+    'fewbit_hipx_crs_gather': (_i32, [_i32, _vp, _sz, _sz, _sz, _u64, _vp, _sz, _sz, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_crs_scatter': (_i32, [_i32, _vp, _sz, _sz, _u64, _vp, _sz, _sz, _vp, _vp, _sz, _vp]),
+    # the zero-extended sampled transforms: inside revision 2, recognised by their symbols (checked in lib() with every other name)
+    'fewbit_hipx_sampled_rows_ceil': (_sz, [_sz]),
+    'fewbit_hipx_sampled_dct_zext': (_i32, [_i32, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _dbl, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_sampled_dct_zext_seeded': (_i32, [_i32, _vp, _sz, _sz, _sz, _sz, _u64, _vp, _sz, _dbl, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_sampled_dft_zext': (_i32, [_i32, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _dbl, _i32, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_sampled_dft_zext_seeded': (_i32, [_i32, _vp, _sz, _sz, _sz, _sz, _u64, _vp, _sz, _dbl, _i32, _vp, _vp, _sz, _vp]),
+    # the moments of the variance estimator: inside revision 2 as well, recognised by their symbols
+    'fewbit_hipx_moments_workspace': (_sz, [_sz, _sz, _sz]),
+    'fewbit_hipx_row_moments': (_i32, [_i32, _vp, _sz, _sz, _i32, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_sum_squares': (_i32, [_i32, _vp, _sz, _vp, _vp, _sz, _vp]),
+    # the dropout of a seed: inside revision 2 as well, recognised by its symbols
+    'fewbit_hipx_dropout_threshold': (_i32, [_dbl]),
+    'fewbit_hipx_dropout_keep': (_i32, [_u64, _u32, _u64, _sz, _vp]),
+    'fewbit_hipx_dropout': (_i32, [_i32, _vp, _vp, _vp, _sz, _u64, _u64, _vp, _u32, _vp]),
+    # the sampled transforms with the signs of a seed: inside revision 2 as well, recognised by their symbols
+    'fewbit_hipx_sampled_signs': (_i32, [_u64, _u64, _sz, _vp]),
+    'fewbit_hipx_sampled_dct_signed': (_i32, [_i32, _vp, _sz, _sz, _sz, _sz, _u64, _vp, _sz, _dbl, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_sampled_dft_signed': (_i32, [_i32, _vp, _sz, _sz, _sz, _sz, _u64, _vp, _sz, _dbl, _i32, _vp, _vp, _sz, _vp]),
+    # the packed form of a seed: inside revision 2 as well, recognised by its symbols
+    'fewbit_hipx_quant_bytes': (_sz, [_sz, _i32]),
+    'fewbit_hipx_quant_pack_host': (_i32, [_vp, _sz, _i32, _u64, _vp]),
+    'fewbit_hipx_quant_unpack_host': (_i32, [_vp, _sz, _i32, _vp]),
+    'fewbit_hipx_quant_pack': (_i32, [_i32, _vp, _sz, _i32, _u64, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_quant_unpack': (_i32, [_vp, _sz, _i32, _i32, _vp, _vp]),
+    # the normalized rows of a seed (the layer norm): inside revision 2 as well, recognised by its symbols
+    'fewbit_hipx_norm_state_bytes': (_sz, [_sz, _sz, _i32]),
+    'fewbit_hipx_norm_workspace': (_sz, [_sz, _sz]),
+    'fewbit_hipx_norm_state_host': (_i32, [_vp, _sz, _sz, _i32, _u64, _vp]),
+    'fewbit_hipx_norm_state_unpack_host': (_i32, [_vp, _sz, _sz, _i32, _vp]),
+    'fewbit_hipx_layer_norm_forward': (_i32, [_i32, _vp, _sz, _sz, _vp, _vp, _dbl, _i32, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    'fewbit_hipx_layer_norm_backward': (_i32, [_i32, _vp, _vp, _vp, _vp, _sz, _sz, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # the un-centred rows (the RMS norm): inside revision 2 as well, recognised by its symbols
+    'fewbit_hipx_rms_norm_forward': (_i32, [_i32, _vp, _sz, _sz, _vp, _dbl, _i32, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    'fewbit_hipx_rms_norm_backward': (_i32, [_i32, _vp, _vp, _vp, _vp, _sz, _sz, _i32, _vp, _vp, _vp, _sz, _vp]),
+}
+SYMBOLS = tuple(_SIGNATURES)
 
 _lib = None
 
@@ -45,96 +86,17 @@ def lib() -> ctypes.CDLL:
             raise FewbitHipError(f'{LIB_PATH} is missing: build it with `make -C fewbit_amd/csrc` '
                                  '(or `python -c "import __graft_entry__ as g; g.build()"`)')
         L = ctypes.CDLL(str(LIB_PATH))
-        vp, sz, i32, dbl, u64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double, ctypes.c_uint64
         missing = [name for name in SYMBOLS if not hasattr(L, name)]
         if missing:
             raise FewbitHipError(f'{LIB_PATH} lacks {", ".join(missing)} (an older revision of the library): rebuild it (make -C fewbit_amd/csrc)')
-        L.fewbit_hipx_abi_version.restype = i32
-        L.fewbit_hipx_abi_version.argtypes = []
-        have = L.fewbit_hipx_abi_version()
+        have = L.fewbit_hipx_abi_version()                    # (`int f(void)`, as is the revision: what ctypes assumes of an untyped symbol)
         if have < ABI_VERSION:
             raise FewbitHipError(f'{LIB_PATH} has ABI version {have}, this binding needs {ABI_VERSION}: rebuild it (make -C fewbit_amd/csrc)')
-        L.fewbit_hipx_revision.restype = i32
-        L.fewbit_hipx_revision.argtypes = []
         if L.fewbit_hipx_revision() < REVISION:
             raise FewbitHipError(f'{LIB_PATH} has revision {L.fewbit_hipx_revision()}, this binding needs {REVISION}: rebuild it (make -C fewbit_amd/csrc)')
-        L.fewbit_hipx_last_error.restype = ctypes.c_char_p
-        L.fewbit_hipx_last_error.argtypes = []
-        L.fewbit_hipx_sampled_dft_workspace.restype = sz
-        L.fewbit_hipx_sampled_dft_workspace.argtypes = [i32, sz, sz, sz]
-        L.fewbit_hipx_sampled_dft.restype = i32
-        L.fewbit_hipx_sampled_dft.argtypes = [i32, vp, sz, sz, sz, vp, sz, dbl, i32, vp, vp, sz, vp]
-        L.fewbit_hipx_sampled_dft_seeded.restype = i32
-        L.fewbit_hipx_sampled_dft_seeded.argtypes = [i32, vp, sz, sz, sz, u64, vp, sz, dbl, i32, vp, vp, sz, vp]
-        L.fewbit_hipx_crs_columns.restype = i32
-        L.fewbit_hipx_crs_columns.argtypes = [u64, sz, sz, vp, vp, ctypes.POINTER(sz)]
-        L.fewbit_hipx_crs_workspace.restype = sz
-        L.fewbit_hipx_crs_workspace.argtypes = [i32, sz, sz, sz]
-        L.fewbit_hipx_crs_gather.restype = i32
-        L.fewbit_hipx_crs_gather.argtypes = [i32, vp, sz, sz, sz, u64, vp, sz, sz, vp, vp, sz, vp]
-        L.fewbit_hipx_crs_scatter.restype = i32
-        L.fewbit_hipx_crs_scatter.argtypes = [i32, vp, sz, sz, u64, vp, sz, sz, vp, vp, sz, vp]
-        # the zero-extended sampled transforms: inside revision 2, recognised by their symbols (checked above with every other name)
-        L.fewbit_hipx_sampled_rows_ceil.restype = sz
-        L.fewbit_hipx_sampled_rows_ceil.argtypes = [sz]
-        L.fewbit_hipx_sampled_dct_zext.restype = i32
-        L.fewbit_hipx_sampled_dct_zext.argtypes = [i32, vp, sz, sz, sz, sz, vp, sz, dbl, vp, vp, sz, vp]
-        L.fewbit_hipx_sampled_dct_zext_seeded.restype = i32
-        L.fewbit_hipx_sampled_dct_zext_seeded.argtypes = [i32, vp, sz, sz, sz, sz, u64, vp, sz, dbl, vp, vp, sz, vp]
-        L.fewbit_hipx_sampled_dft_zext.restype = i32
-        L.fewbit_hipx_sampled_dft_zext.argtypes = [i32, vp, sz, sz, sz, sz, vp, sz, dbl, i32, vp, vp, sz, vp]
-        L.fewbit_hipx_sampled_dft_zext_seeded.restype = i32
-        L.fewbit_hipx_sampled_dft_zext_seeded.argtypes = [i32, vp, sz, sz, sz, sz, u64, vp, sz, dbl, i32, vp, vp, sz, vp]
-        # the moments of the variance estimator: inside revision 2 as well, recognised by their symbols
-        L.fewbit_hipx_moments_workspace.restype = sz
-        L.fewbit_hipx_moments_workspace.argtypes = [sz, sz, sz]
-        L.fewbit_hipx_row_moments.restype = i32
-        L.fewbit_hipx_row_moments.argtypes = [i32, vp, sz, sz, i32, vp, sz, sz, sz, vp, vp, sz, vp]
-        L.fewbit_hipx_sum_squares.restype = i32
-        L.fewbit_hipx_sum_squares.argtypes = [i32, vp, sz, vp, vp, sz, vp]
-        # the dropout of a seed: inside revision 2 as well, recognised by its symbols
-        L.fewbit_hipx_dropout_threshold.restype = i32
-        L.fewbit_hipx_dropout_threshold.argtypes = [dbl]
-        L.fewbit_hipx_dropout_keep.restype = i32
-        L.fewbit_hipx_dropout_keep.argtypes = [u64, ctypes.c_uint32, u64, sz, vp]
-        L.fewbit_hipx_dropout.restype = i32
-        L.fewbit_hipx_dropout.argtypes = [i32, vp, vp, vp, sz, u64, u64, vp, ctypes.c_uint32, vp]
-        # the sampled transforms with the signs of a seed: inside revision 2 as well, recognised by their symbols
-        L.fewbit_hipx_sampled_signs.restype = i32
-        L.fewbit_hipx_sampled_signs.argtypes = [u64, u64, sz, vp]
-        L.fewbit_hipx_sampled_dct_signed.restype = i32
-        L.fewbit_hipx_sampled_dct_signed.argtypes = [i32, vp, sz, sz, sz, sz, u64, vp, sz, dbl, vp, vp, sz, vp]
-        L.fewbit_hipx_sampled_dft_signed.restype = i32
-        L.fewbit_hipx_sampled_dft_signed.argtypes = [i32, vp, sz, sz, sz, sz, u64, vp, sz, dbl, i32, vp, vp, sz, vp]
-        # the packed form of a seed: inside revision 2 as well, recognised by its symbols
-        L.fewbit_hipx_quant_bytes.restype = sz
-        L.fewbit_hipx_quant_bytes.argtypes = [sz, i32]
-        L.fewbit_hipx_quant_pack_host.restype = i32
-        L.fewbit_hipx_quant_pack_host.argtypes = [vp, sz, i32, u64, vp]
-        L.fewbit_hipx_quant_unpack_host.restype = i32
-        L.fewbit_hipx_quant_unpack_host.argtypes = [vp, sz, i32, vp]
-        L.fewbit_hipx_quant_pack.restype = i32
-        L.fewbit_hipx_quant_pack.argtypes = [i32, vp, sz, i32, u64, vp, vp, sz, vp]
-        L.fewbit_hipx_quant_unpack.restype = i32
-        L.fewbit_hipx_quant_unpack.argtypes = [vp, sz, i32, i32, vp, vp]
-        # the normalized rows of a seed (the layer norm): inside revision 2 as well, recognised by its symbols
-        L.fewbit_hipx_norm_state_bytes.restype = sz
-        L.fewbit_hipx_norm_state_bytes.argtypes = [sz, sz, i32]
-        L.fewbit_hipx_norm_workspace.restype = sz
-        L.fewbit_hipx_norm_workspace.argtypes = [sz, sz]
-        L.fewbit_hipx_norm_state_host.restype = i32
-        L.fewbit_hipx_norm_state_host.argtypes = [vp, sz, sz, i32, u64, vp]
-        L.fewbit_hipx_norm_state_unpack_host.restype = i32
-        L.fewbit_hipx_norm_state_unpack_host.argtypes = [vp, sz, sz, i32, vp]
-        L.fewbit_hipx_layer_norm_forward.restype = i32
-        L.fewbit_hipx_layer_norm_forward.argtypes = [i32, vp, sz, sz, vp, vp, dbl, i32, u64, vp, vp, vp, vp, sz, vp, vp]
-        L.fewbit_hipx_layer_norm_backward.restype = i32
-        L.fewbit_hipx_layer_norm_backward.argtypes = [i32, vp, vp, vp, vp, sz, sz, i32, vp, vp, vp, vp, sz, vp]
-        # the un-centred rows (the RMS norm): inside revision 2 as well, recognised by its symbols
-        L.fewbit_hipx_rms_norm_forward.restype = i32
-        L.fewbit_hipx_rms_norm_forward.argtypes = [i32, vp, sz, sz, vp, dbl, i32, u64, vp, vp, vp, vp, sz, vp, vp]
-        L.fewbit_hipx_rms_norm_backward.restype = i32
-        L.fewbit_hipx_rms_norm_backward.argtypes = [i32, vp, vp, vp, vp, sz, sz, i32, vp, vp, vp, sz, vp]
+        for name, (restype, argtypes) in _SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -622,11 +584,12 @@ def _norm_out(t: Optional[torch.Tensor], shape, dtype: torch.dtype, device, what
     return t
 
 
-def _norm_forward(name: str, x, gamma, beta, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream):
-    """the forward call of either norm (``beta`` is False for the RMS norm, whose entry point has no such argument)"""
+def _norm_forward(centred: bool, x, gamma, beta, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream):
+    """the forward call of either norm: ``centred`` is the layer norm, whose entry point alone takes ``beta`` (None for the RMS norm)"""
+    name = 'layer_norm_forward' if centred else 'rms_norm_forward'
     rows, width = _norm_rows(x, 'x')
-    centred = beta is not False
-    gp, bp = _norm_vector(gamma, x, 'gamma'), _norm_vector(beta, x, 'beta') if centred else None
+    gp = _norm_vector(gamma, x, 'gamma')
+    pointers = (gp, _norm_vector(beta, x, 'beta')) if centred else (gp, )
     need = _norm_size(rows, width, bits, name) if keep else 0
     value, word, others = _seed_arguments(seed) if keep else (0, None, ())
     with _on(x.device):
@@ -640,15 +603,16 @@ def _norm_forward(name: str, x, gamma, beta, eps, bits, seed, keep, want_xhat, y
             state = None
         if want_xhat or xhat is not None:
             xhat = _norm_out(xhat, (rows, width), torch.float32, x.device, 'xhat')
-        _same_device(x, y, rstd, *others, *(t for t in (gamma, beta if centred else None, state, xhat) if t is not None))
-        _check(getattr(lib(), f'fewbit_hipx_{name}')(DTYPES[x.dtype], x.data_ptr(), rows, width, gp, *((bp, ) if centred else ()), float(eps), bits, value, word,
+        _same_device(x, y, rstd, *others, *(t for t in (gamma, beta, state, xhat) if t is not None))
+        _check(getattr(lib(), f'fewbit_hipx_{name}')(DTYPES[x.dtype], x.data_ptr(), rows, width, *pointers, float(eps), bits, value, word,
                                                      y.data_ptr(), rstd.data_ptr(), None if state is None else state.data_ptr(),
                                                      0 if state is None else state.numel(), None if xhat is None else xhat.data_ptr(), _stream(stream, x.device)))
     return y, rstd, state, xhat
 
 
-def _norm_backward(name: str, gy, state, rstd, gamma, bits, want, outs, workspace, stream):
-    """the backward call of either norm: ``want`` and ``outs`` are (dx, dgamma, dbeta) for the layer norm and (dx, dgamma) for the RMS norm"""
+def _norm_backward(centred: bool, gy, state, rstd, gamma, bits, want, outs, workspace, stream):
+    """the backward call of either norm: ``want`` and ``outs`` are (dx, dgamma, dbeta) for the layer norm (``centred``) and (dx, dgamma) for the RMS norm"""
+    name = 'layer_norm_backward' if centred else 'rms_norm_backward'
     rows, width = _norm_rows(gy, 'gy')
     gp = _norm_vector(gamma, gy, 'gamma')
     need = _norm_size(rows, width, bits, name)
@@ -657,7 +621,7 @@ def _norm_backward(name: str, gy, state, rstd, gamma, bits, want, outs, workspac
     if rstd.dtype != torch.float32 or rstd.numel() != rows or not rstd.is_contiguous():
         raise FewbitHipError(f'rstd must be a contiguous float32 tensor of {rows} elements')
     with _on(gy.device):
-        shapes = (((rows, width), gy.dtype, 'dx'), ((width, ), torch.float32, 'dgamma'), ((width, ), torch.float32, 'dbeta'))
+        shapes = (((rows, width), gy.dtype, 'dx'), ((width, ), torch.float32, 'dgamma'), ((width, ), torch.float32, 'dbeta'))[:3 if centred else 2]
         outs = tuple(_norm_out(t, shape, dtype, gy.device, what) if wanted else None for t, wanted, (shape, dtype, what) in zip(outs, want, shapes))
         if any(want[1:]) and workspace is None:
             workspace = torch.empty(norm_workspace_bytes(rows, width), dtype=torch.uint8, device=gy.device)
@@ -677,7 +641,7 @@ def layer_norm_forward(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Opt
     fp32 normalized rows the kernel quantized, only with ``want_xhat`` (else None).  ``keep=False``: the plain forward, ``state`` is None and
     nothing but ``y`` and ``rstd`` is written -- the same bytes as with a state.  ``seed``: an int, or a one-element int64 tensor on the device
     of ``x`` that is read when the kernel runs (``cabi.next_sketch_seed``).  ``y``, ``rstd``, ``state``, ``xhat``: buffers to write into."""
-    return _norm_forward('layer_norm_forward', x, gamma, beta, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream)
+    return _norm_forward(True, x, gamma, beta, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream)
 
 
 def layer_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor], bits: int, want=(True, True, True),
@@ -688,7 +652,7 @@ def layer_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tenso
     False the output is None and nothing of it is computed or written.  Two launches (one when neither sum is wanted), fp32 arithmetic, a fixed
     order of every sum: the same arguments give the same bits.  ``workspace``: a uint8 tensor of ``norm_workspace_bytes(rows, width)`` bytes."""
     want_dx, want_dgamma, want_dbeta = want
-    return _norm_backward('layer_norm_backward', gy, state, rstd, gamma, bits, (want_dx, want_dgamma, want_dbeta), (dx, dgamma, dbeta), workspace, stream)
+    return _norm_backward(True, gy, state, rstd, gamma, bits, (want_dx, want_dgamma, want_dbeta), (dx, dgamma, dbeta), workspace, stream)
 
 
 def rms_norm_forward(x: torch.Tensor, gamma: Optional[torch.Tensor], eps: float, bits: int = 4, seed=0, keep: bool = True, want_xhat: bool = False,
@@ -698,7 +662,7 @@ def rms_norm_forward(x: torch.Tensor, gamma: Optional[torch.Tensor], eps: float,
     ``rstd = 1 / sqrt(mean(x^2) + eps)``, ``xhat = x * rstd``, ``y = xhat * gamma`` rounded once, ``state`` the state of these ``xhat``
     (``norm_state_bytes`` bytes; ``norm_state_host`` gives the same bytes from ``xhat``).  ``eps`` is a number (``F.rms_norm``'s default
     is ``torch.finfo(x.dtype).eps``)."""
-    return _norm_forward('rms_norm_forward', x, gamma, False, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream)
+    return _norm_forward(False, x, gamma, None, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream)
 
 
 def rms_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor], bits: int, want=(True, True),
@@ -708,4 +672,4 @@ def rms_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor,
     without the mean term and without ``dbeta``: ``dx = rstd * (g^ - x^q * mean(g^ * x^q))``, ``dgamma = sum_r gy * x^q``.  Two launches (one when
     ``dgamma`` is not wanted, and then no workspace); ``workspace``: a uint8 tensor of ``norm_workspace_bytes(rows, width)`` bytes."""
     want_dx, want_dgamma = want
-    return _norm_backward('rms_norm_backward', gy, state, rstd, gamma, bits, (want_dx, want_dgamma), (dx, dgamma), workspace, stream)
+    return _norm_backward(False, gy, state, rstd, gamma, bits, (want_dx, want_dgamma), (dx, dgamma), workspace, stream)

@@ -501,12 +501,24 @@ template <bool CENTRED> void launch_dtype(int dtype, int bits, Plan p, unsigned 
 
 inline bool misaligned(const void *p, size_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
 
-// the refusals both device entry points share; 1: nothing to do
-int check_shape(const char *name, int dtype, size_t rows, size_t width) {
-    if (!known_dtype(dtype)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: unknown dtype %d", name, dtype);
+// the refusals of a shape that every entry point shares, host and device; 1: nothing to do
+int check_extent(const char *name, size_t rows, size_t width) {
     if (width == 0 || width > kMaxWidth) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: width = %zu is outside 1 .. %zu", name, width, kMaxWidth);
     if (rows == 0) return 1;
     if (rows > kMaxCount / width) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: rows * width = %zu * %zu is beyond 2^36", name, rows, width);
+    return FEWBIT_OK;
+}
+// the device entry points: the dtype first
+int check_shape(const char *name, int dtype, size_t rows, size_t width) {
+    if (!known_dtype(dtype)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: unknown dtype %d", name, dtype);
+    return check_extent(name, rows, width);
+}
+// the host entry points: the bits first, the pointers last
+int check_host(const char *name, size_t rows, size_t width, int bits, const void *from, const void *to) {
+    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: bits = %d is not 2, 4 or 8", name, bits);
+    const int shape = check_extent(name, rows, width);
+    if (shape != FEWBIT_OK) return shape;
+    if (from == nullptr || to == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer", name);
     return FEWBIT_OK;
 }
 
@@ -595,65 +607,30 @@ size_t fewbit_hipx_norm_state_bytes(size_t rows, size_t width, int bits) { retur
 size_t fewbit_hipx_norm_workspace(size_t rows, size_t width) { return workspace_of(rows, width); }
 
 int fewbit_hipx_norm_state_host(const float *xhat_host, size_t rows, size_t width, int bits, uint64_t seed, uint8_t *out_host) {
-    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "norm_state_host: bits = %d is not 2, 4 or 8", bits);
-    if (width == 0 || width > kMaxWidth) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "norm_state_host: width = %zu is outside 1 .. %zu", width, kMaxWidth);
-    if (rows == 0) return FEWBIT_OK;
-    if (rows > kMaxCount / width) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "norm_state_host: rows * width = %zu * %zu is beyond 2^36", rows, width);
-    if (xhat_host == nullptr || out_host == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "norm_state_host: null pointer");
-    const uint32_t levels = (1u << bits) - 1u;
+    const int refused = check_host("norm_state_host", rows, width, bits, xhat_host, out_host);
+    if (refused != FEWBIT_OK) return refused < 0 ? refused : FEWBIT_OK;
     const size_t groups = groups_of(width), blocks = blocks_of(width), stride = code_bytes(blocks, bits);
     const Key key = sketch::key_of(seed);
+    // (group g of row r starts at block kLanes g of the row's `blocks`; the padding behind a row's code bytes is 0)
     for (size_t r = 0; r < rows; ++r) {
-        const float *row = xhat_host + r * width;
         uint8_t *codes = out_host + 8 * rows * groups + r * stride;
         std::memset(codes, 0, stride);
         for (size_t g = 0; g < groups; ++g) {
             const size_t first = g * kGroup, count = width - first < static_cast<size_t>(kGroup) ? width - first : kGroup;
-            int32_t kmin = INT32_MAX, kmax = INT32_MIN;
-            bool bad = false;
-            for (size_t j = 0; j < count; ++j) {
-                const uint32_t bits32 = bits_of_float(row[first + j]);
-                const int32_t k = order_key(bits32);
-                kmin = k < kmin ? k : kmin;
-                kmax = k > kmax ? k : kmax;
-                bad = bad || non_finite(bits32);
-            }
-            const Params p = params_of(kmin, kmax, bad, static_cast<float>(levels));
-            const uint32_t par[2] = {bits_of_float(p.lo), bits_of_float(p.step)};
-            for (int h = 0; h < 2; ++h)
-                for (int c = 0; c < 4; ++c) out_host[8 * (r * groups + g) + 4 * h + c] = static_cast<uint8_t>(par[h] >> (8 * c));
-            for (size_t j0 = 0; j0 < count; j0 += kBlock) {
-                const size_t b = (first + j0) / kBlock;
-                uint32_t w[4];
-                block_words(static_cast<uint64_t>(r) * blocks + b, key, w);
-                uint64_t word = 0;
-                for (int e = 0; e < kBlock && j0 + e < count; ++e)
-                    word |= static_cast<uint64_t>(code_of(row[first + j0 + e], p, uniform_of(w, e), levels)) << (bits * e);
-                for (int c = 0; c < bits; ++c) codes[static_cast<size_t>(bits) * b + c] = static_cast<uint8_t>(word >> (8 * c));
-            }
+            pack_group_host(xhat_host + r * width + first, count, static_cast<uint64_t>(r) * blocks + g * kLanes, key, bits, out_host + 8 * (r * groups + g),
+                            codes + static_cast<size_t>(bits) * kLanes * g);
         }
     }
     return FEWBIT_OK;
 }
 
 int fewbit_hipx_norm_state_unpack_host(const uint8_t *state_host, size_t rows, size_t width, int bits, float *out_host) {
-    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "norm_state_unpack_host: bits = %d is not 2, 4 or 8", bits);
-    if (width == 0 || width > kMaxWidth) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "norm_state_unpack_host: width = %zu is outside 1 .. %zu", width, kMaxWidth);
-    if (rows == 0) return FEWBIT_OK;
-    if (rows > kMaxCount / width) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "norm_state_unpack_host: rows * width = %zu * %zu is beyond 2^36", rows, width);
-    if (state_host == nullptr || out_host == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "norm_state_unpack_host: null pointer");
-    const uint32_t levels = (1u << bits) - 1u;
+    const int refused = check_host("norm_state_unpack_host", rows, width, bits, state_host, out_host);
+    if (refused != FEWBIT_OK) return refused < 0 ? refused : FEWBIT_OK;
     const size_t groups = groups_of(width), stride = code_bytes(blocks_of(width), bits);
     for (size_t r = 0; r < rows; ++r) {
-        const uint8_t *codes = state_host + 8 * rows * groups + r * stride;
-        for (size_t i = 0; i < width; ++i) {
-            uint32_t par[2] = {0, 0};
-            for (int h = 0; h < 2; ++h)
-                for (int c = 0; c < 4; ++c) par[h] |= static_cast<uint32_t>(state_host[8 * (r * groups + i / kGroup) + 4 * h + c]) << (8 * c);
-            const size_t bit = static_cast<size_t>(bits) * (i % kBlock);
-            const uint32_t code = (codes[static_cast<size_t>(bits) * (i / kBlock) + bit / 8] >> (bit % 8)) & levels;
-            out_host[r * width + i] = decode(code, float_of_bits(par[0]), float_of_bits(par[1]));
-        }
+        const uint8_t *params = state_host + 8 * r * groups, *codes = state_host + 8 * rows * groups + r * stride;
+        for (size_t i = 0; i < width; ++i) out_host[r * width + i] = decode_host(params, codes, i, bits);
     }
     return FEWBIT_OK;
 }

@@ -184,34 +184,13 @@ int fewbit_hipx_quant_pack_host(const float *x_host, size_t n, int bits, uint64_
     if (n == 0) return FEWBIT_OK;
     if (n > kMaxCount) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack_host: n = %zu is beyond 2^36", n);
     if (x_host == nullptr || out_host == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack_host: null pointer");
-    const uint32_t levels = (1u << bits) - 1u;
     const size_t groups = (n + kGroup - 1) / kGroup;
     const Key key = sketch::key_of(seed);
     uint8_t *codes = out_host + 8 * groups;
+    // (group g starts at block kLanes g of the flat tensor)
     for (size_t g = 0; g < groups; ++g) {
         const size_t first = g * kGroup, count = n - first < static_cast<size_t>(kGroup) ? n - first : kGroup;
-        int32_t kmin = INT32_MAX, kmax = INT32_MIN;
-        bool bad = false;
-        for (size_t j = 0; j < count; ++j) {
-            const uint32_t bits32 = bits_of_float(x_host[first + j]);
-            const int32_t k = order_key(bits32);
-            kmin = k < kmin ? k : kmin;
-            kmax = k > kmax ? k : kmax;
-            bad = bad || non_finite(bits32);
-        }
-        const Params p = params_of(kmin, kmax, bad, static_cast<float>(levels));
-        const uint32_t par[2] = {bits_of_float(p.lo), bits_of_float(p.step)};
-        for (int h = 0; h < 2; ++h)
-            for (int c = 0; c < 4; ++c) out_host[8 * g + 4 * h + c] = static_cast<uint8_t>(par[h] >> (8 * c));
-        for (size_t j0 = 0; j0 < count; j0 += kBlock) {
-            const size_t b = (first + j0) / kBlock;
-            uint32_t w[4];
-            block_words(b, key, w);
-            uint64_t word = 0;
-            for (int e = 0; e < kBlock && j0 + e < count; ++e)
-                word |= static_cast<uint64_t>(code_of(x_host[first + j0 + e], p, uniform_of(w, e), levels)) << (bits * e);
-            for (int c = 0; c < bits; ++c) codes[static_cast<size_t>(bits) * b + c] = static_cast<uint8_t>(word >> (8 * c));
-        }
+        pack_group_host(x_host + first, count, g * kLanes, key, bits, out_host + 8 * g, codes + static_cast<size_t>(bits) * kLanes * g);
     }
     return FEWBIT_OK;
 }
@@ -221,16 +200,8 @@ int fewbit_hipx_quant_unpack_host(const uint8_t *packed_host, size_t n, int bits
     if (n == 0) return FEWBIT_OK;
     if (n > kMaxCount) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack_host: n = %zu is beyond 2^36", n);
     if (packed_host == nullptr || out_host == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack_host: null pointer");
-    const uint32_t levels = (1u << bits) - 1u;
     const uint8_t *codes = packed_host + 8 * ((n + kGroup - 1) / kGroup);
-    for (size_t i = 0; i < n; ++i) {
-        uint32_t par[2] = {0, 0};
-        for (int h = 0; h < 2; ++h)
-            for (int c = 0; c < 4; ++c) par[h] |= static_cast<uint32_t>(packed_host[8 * (i / kGroup) + 4 * h + c]) << (8 * c);
-        const size_t bit = static_cast<size_t>(bits) * (i % kBlock);
-        const uint32_t code = (codes[static_cast<size_t>(bits) * (i / kBlock) + bit / 8] >> (bit % 8)) & levels;
-        out_host[i] = decode(code, float_of_bits(par[0]), float_of_bits(par[1]));
-    }
+    for (size_t i = 0; i < n; ++i) out_host[i] = decode_host(packed_host, codes, i, bits);
     return FEWBIT_OK;
 }
 

@@ -106,6 +106,42 @@ __host__ __device__ __forceinline__ float decode(uint32_t code, float lo, float 
     return fma_rn(static_cast<float>(code), step, lo);
 }
 
+// ---- the host evaluation, one group or one element at a time: what the four *_host entry points loop over -----------------------------------
+// the `count` (1 .. kGroup) values of a group whose first block is block `first_block` of the seed's stream -> its 8 parameter bytes (lo, step,
+// little-endian) and its bits * ceil(count / 8) code bytes (the missing elements of the last word are 0)
+inline void pack_group_host(const float *x, size_t count, uint64_t first_block, Key key, int bits, uint8_t *params, uint8_t *codes) {
+    const uint32_t levels = (1u << bits) - 1u;
+    int32_t kmin = INT32_MAX, kmax = INT32_MIN;
+    bool bad = false;
+    for (size_t j = 0; j < count; ++j) {
+        const uint32_t bits32 = bits_of_float(x[j]);
+        const int32_t k = order_key(bits32);
+        kmin = k < kmin ? k : kmin;
+        kmax = k > kmax ? k : kmax;
+        bad = bad || non_finite(bits32);
+    }
+    const Params p = params_of(kmin, kmax, bad, static_cast<float>(levels));
+    const uint32_t par[2] = {bits_of_float(p.lo), bits_of_float(p.step)};
+    for (int h = 0; h < 2; ++h)
+        for (int c = 0; c < 4; ++c) params[4 * h + c] = static_cast<uint8_t>(par[h] >> (8 * c));
+    for (size_t j0 = 0; j0 < count; j0 += kBlock) {
+        uint32_t w[4];
+        block_words(first_block + j0 / kBlock, key, w);
+        uint64_t word = 0;
+        for (int e = 0; e < kBlock && j0 + e < count; ++e) word |= static_cast<uint64_t>(code_of(x[j0 + e], p, uniform_of(w, e), levels)) << (bits * e);
+        for (int c = 0; c < bits; ++c) codes[static_cast<size_t>(bits) * (j0 / kBlock) + c] = static_cast<uint8_t>(word >> (8 * c));
+    }
+}
+// element i of a run of groups: `params` the parameter bytes of its first group, `codes` the code bytes of its first block
+inline float decode_host(const uint8_t *params, const uint8_t *codes, size_t i, int bits) {
+    uint32_t par[2] = {0, 0};
+    for (int h = 0; h < 2; ++h)
+        for (int c = 0; c < 4; ++c) par[h] |= static_cast<uint32_t>(params[8 * (i / kGroup) + 4 * h + c]) << (8 * c);
+    const size_t bit = static_cast<size_t>(bits) * (i % kBlock);
+    const uint32_t code = (codes[static_cast<size_t>(bits) * (i / kBlock) + bit / 8] >> (bit % 8)) & ((1u << bits) - 1u);
+    return decode(code, float_of_bits(par[0]), float_of_bits(par[1]));
+}
+
 inline bool known_dtype(int dtype) { return dtype == FEWBIT_F32 || dtype == FEWBIT_F16 || dtype == FEWBIT_BF16; }
 inline bool known_bits(int bits) { return bits == 2 || bits == 4 || bits == 8; }
 inline size_t size_of(int dtype) { return dtype == FEWBIT_F32 ? 4 : 2; }

@@ -691,8 +691,8 @@ def linear_crs(input: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
 
 # ---- every element of the input in 2, 4 or 8 bits --------------------------------------------------------------------------------------
 
-QUANT_BITS = (2, 4, 8)
-_QUANT_GROUP = 64                                # elements (by flat index) that share one (lo, step) pair: cabi_x.QUANT_GROUP
+# the code widths, and the elements (by flat index) that share one (lo, step) pair: the binding's constants (the import loads no library)
+from .cabi_x import QUANT_BITS, QUANT_GROUP as _QUANT_GROUP  # noqa: E402
 
 
 def _native_quant_applies(flat: torch.Tensor) -> bool:

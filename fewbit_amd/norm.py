@@ -42,103 +42,178 @@ import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import linear
+from . import cabi_x, linear
+from .cabi import DTYPES
 
 __all__ = ('layer_norm_quantized', 'QuantizedLayerNorm', 'rms_norm_quantized', 'QuantizedRMSNorm')
 
-_KERNEL_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
-_MAX_WIDTH = 8192                                # cabi_x.NORM_MAX_WIDTH
-_GROUP = 64                                      # elements of a row that share one (lo, step) pair
+# Everything below takes the kind as ``centred``: True for the layer norm, False for the RMS norm (the un-centred statistic, backward without the mean
+# term, no beta: ``bias`` is None throughout).
 
 
 def _kernel_applies(flat: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor]) -> bool:
-    if not (linear.use_native_sketch() and flat.device.type == 'cuda' and flat.dtype in _KERNEL_DTYPES and 1 <= flat.shape[1] <= _MAX_WIDTH
+    if not (linear.use_native_sketch() and flat.device.type == 'cuda' and flat.dtype in DTYPES and 1 <= flat.shape[1] <= cabi_x.NORM_MAX_WIDTH
             and 0 < flat.numel() <= 2**36):
         return False
     # (under autocast fp32 parameters meet a 16-bit input: they are cast to it, a copy of `width` elements)
     cast = torch.is_autocast_enabled('cuda')
-    return all(p is None or (p.device == flat.device and (p.dtype == flat.dtype or (cast and p.dtype in _KERNEL_DTYPES))) for p in (weight, bias))
+    return all(p is None or (p.device == flat.device and (p.dtype == flat.dtype or (cast and p.dtype in DTYPES))) for p in (weight, bias))
 
 
 def _as(p: Optional[torch.Tensor], dtype: torch.dtype) -> Optional[torch.Tensor]:
     return None if p is None else p.detach().reshape(-1).to(dtype).contiguous()
 
 
-def _normalized_rows(flat: torch.Tensor, eps: float):
-    """(x^, rstd) of the rows of ``flat`` in fp32 (fp64 for a float64 input), the two-pass variance of the definition"""
+def _torch_norm(centred: bool, input, normalized_shape, weight, bias, eps):
+    return F.layer_norm(input, normalized_shape, weight, bias, eps) if centred else F.rms_norm(input, normalized_shape, weight, eps)
+
+
+def _kernel_forward(centred: bool, flat, weight, bias, eps, bits: int = 4, seed=0, keep: bool = True):
+    """(y, rstd, state, None) of the entry point of the kind on the rows of ``flat``"""
+    flat = flat if flat.is_contiguous() else flat.contiguous()
+    if centred:
+        return cabi_x.layer_norm_forward(flat, _as(weight, flat.dtype), _as(bias, flat.dtype), eps, bits, seed, keep)
+    return cabi_x.rms_norm_forward(flat, _as(weight, flat.dtype), eps, bits, seed, keep)
+
+
+def _row_statistic(flat: torch.Tensor, eps: float, centred: bool):
+    """(x^, rstd) of the rows of ``flat`` in fp32 (fp64 for a float64 input): the two-pass variance of the definition, or, un-centred,
+    ``x^ = x * rstd`` with ``rstd = 1 / sqrt(mean(x^2) + eps)``"""
     work = flat.to(torch.float64 if flat.dtype == torch.float64 else torch.float32)
-    centred = work - work.mean(dim=1, keepdim=True)
-    rstd = 1.0 / torch.sqrt(centred.square().mean(dim=1, keepdim=True) + eps)
-    return centred * rstd, rstd.reshape(-1)
+    if centred:
+        work = work - work.mean(dim=1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(work.square().mean(dim=1, keepdim=True) + eps)
+    return work * rstd, rstd.reshape(-1)
 
 
 def _padded_rows(xhat: torch.Tensor) -> torch.Tensor:
     """the rows filled up to whole groups with their last element, which moves neither a group's minimum nor its maximum"""
-    pad = -xhat.shape[1] % _GROUP
+    pad = -xhat.shape[1] % cabi_x.QUANT_GROUP
     return torch.cat((xhat, xhat[:, -1:].expand(-1, pad)), dim=1) if pad else xhat
 
 
 def _decoded_rows(codes: torch.Tensor, lo: torch.Tensor, step: torch.Tensor, rows: int, width: int) -> torch.Tensor:
-    values = torch.addcmul(lo[:, None], codes.view(-1, _GROUP).to(lo.dtype), step[:, None])
+    values = torch.addcmul(lo[:, None], codes.view(-1, cabi_x.QUANT_GROUP).to(lo.dtype), step[:, None])
     return values.view(rows, -1)[:, :width]
 
 
-def _backward_formula(gy: torch.Tensor, xq: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor]):
-    """(dx, dgamma, dbeta) of the definition in the dtype of ``xq``"""
+def _backward_formula(gy: torch.Tensor, xq: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor], centred: bool):
+    """(dx, dgamma, dbeta) of the definition in the dtype of ``xq``; un-centred the mean term is absent and ``dbeta`` is None"""
     gy = gy.to(xq.dtype)
     gh = gy if gamma is None else gy * gamma.reshape(1, -1).to(xq.dtype)
-    dx = rstd[:, None] * (gh - gh.mean(dim=1, keepdim=True) - xq * (gh * xq).mean(dim=1, keepdim=True))
-    return dx, (gy * xq).sum(dim=0), gy.sum(dim=0)
+    deviation = gh - gh.mean(dim=1, keepdim=True) if centred else gh
+    dx = rstd[:, None] * (deviation - xq * (gh * xq).mean(dim=1, keepdim=True))
+    return dx, (gy * xq).sum(dim=0), gy.sum(dim=0) if centred else None
 
 
-class _LayerNormQuantized(torch.autograd.Function):
-    """``F.layer_norm`` that keeps ``x^`` in ``bits`` bits per element (module docstring).  Kept for backward on the kernels: ONE uint8 buffer
-    (the state), ``rstd`` (fp32 per row) and gamma; in the PyTorch formulation the codes (one per byte), lo and step of every group, ``rstd``
-    and gamma."""
+def _node_forward(ctx, centred: bool, input, weight, bias, normalized_shape, eps: float, bits: int, generator):
+    """Kept for backward on the kernels: ONE uint8 buffer (the state), ``rstd`` (fp32 per row) and gamma; in the PyTorch formulation the codes (one
+    per byte), lo and step of every group, ``rstd`` and gamma."""
+    width = math.prod(normalized_shape)
+    flat = input.detach().reshape(-1, width)
+    ctx.bits, ctx.flat_shape, ctx.input_dtype = bits, tuple(flat.shape), input.dtype
+    ctx.has_weight, ctx.normalized_shape, ctx.bias_dtype = weight is not None, tuple(normalized_shape), None if bias is None else bias.dtype
+    ctx.autocast = linear._autocast_seen(input.device.type)
+    ctx.native_seed = None
+    if _kernel_applies(flat, weight, bias):
+        ctx.native_seed = linear._sketch_seed(generator, flat.device)
+        y, rstd, state, _ = _kernel_forward(centred, flat, weight, bias, eps, bits, ctx.native_seed)
+        ctx.save_for_backward(state, rstd, *((weight, ) if ctx.has_weight else ()))
+        return y.view(input.shape)
+    xhat, rstd = _row_statistic(flat, eps, centred)
+    ctx.save_for_backward(*linear._quantize_groups(_padded_rows(xhat), bits, generator), rstd, *((weight, ) if ctx.has_weight else ()))
+    return _torch_norm(centred, input, normalized_shape, weight, bias, eps)
 
-    @staticmethod
-    def forward(ctx, input, weight, bias, normalized_shape, eps: float, bits: int, generator):
-        width = math.prod(normalized_shape)
-        flat = input.detach().reshape(-1, width)
-        ctx.bits, ctx.flat_shape, ctx.input_dtype = bits, tuple(flat.shape), input.dtype
-        ctx.has_weight, ctx.normalized_shape, ctx.bias_dtype = weight is not None, tuple(normalized_shape), None if bias is None else bias.dtype
-        ctx.autocast = linear._autocast_seen(input.device.type)
-        ctx.native_seed = None
-        if _kernel_applies(flat, weight, bias):
-            from . import cabi_x
-            ctx.native_seed = linear._sketch_seed(generator, flat.device)
-            y, rstd, state, _ = cabi_x.layer_norm_forward(flat if flat.is_contiguous() else flat.contiguous(), _as(weight, flat.dtype), _as(bias, flat.dtype),
-                                                           eps, bits, ctx.native_seed)
-            ctx.save_for_backward(state, rstd, *((weight, ) if ctx.has_weight else ()))
-            return y.view(input.shape)
-        xhat, rstd = _normalized_rows(flat, eps)
-        ctx.save_for_backward(*linear._quantize_groups(_padded_rows(xhat), bits, generator), rstd, *((weight, ) if ctx.has_weight else ()))
-        return F.layer_norm(input, normalized_shape, weight, bias, eps)
 
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_output):
-        with linear._autocast_as(ctx.autocast):
-            return _LayerNormQuantized._backward(ctx, linear._dense_rows(grad_output))
-
-    @staticmethod
-    def _backward(ctx, grad_output):
+def _node_backward(ctx, centred: bool, grad_output):
+    """(grad_input, grad_weight, grad_bias), under the autocast state the forward saw"""
+    with linear._autocast_as(ctx.autocast):
+        grad_output = linear._dense_rows(grad_output)
         saved = ctx.saved_tensors                       # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
         weight = saved[-1] if ctx.has_weight else None
         rows, width = ctx.flat_shape
         gy = grad_output.reshape(rows, width)
-        want = tuple(ctx.needs_input_grad[:3])
-        if ctx.native_seed is not None:
-            from . import cabi_x
-            gy = gy if gy.dtype in _KERNEL_DTYPES else gy.float()
-            dx, dgamma, dbeta = cabi_x.layer_norm_backward(gy, saved[0], saved[1], _as(weight, gy.dtype), ctx.bits, want)
-        else:
+        want = tuple(ctx.needs_input_grad[:3 if centred else 2])
+        if ctx.native_seed is None:
             codes, lo, step, rstd = saved[:4]
-            dx, dgamma, dbeta = _backward_formula(gy, _decoded_rows(codes, lo, step, rows, width), rstd, weight)
+            dx, dgamma, dbeta = _backward_formula(gy, _decoded_rows(codes, lo, step, rows, width), rstd, weight, centred)
+        else:
+            gy = gy if gy.dtype in DTYPES else gy.float()
+            call = cabi_x.layer_norm_backward if centred else cabi_x.rms_norm_backward
+            grads = call(gy, saved[0], saved[1], _as(weight, gy.dtype), ctx.bits, want)
+            dx, dgamma, dbeta = grads if centred else (*grads, None)
         grad_input = dx.to(ctx.input_dtype).view(grad_output.shape) if want[0] else None
         grad_weight = dgamma.to(weight.dtype).view(weight.shape) if want[1] else None
-        grad_bias = dbeta.to(ctx.bias_dtype).view(ctx.normalized_shape) if want[2] else None
-        return grad_input, grad_weight, grad_bias, None, None, None, None
+        grad_bias = dbeta.to(ctx.bias_dtype).view(ctx.normalized_shape) if centred and want[2] else None
+        return grad_input, grad_weight, grad_bias
+
+
+class _LayerNormQuantized(torch.autograd.Function):
+    """``F.layer_norm`` that keeps ``x^`` in ``bits`` bits per element (module docstring; what is kept: ``_node_forward``)"""
+
+    @staticmethod
+    def forward(ctx, input, weight, bias, normalized_shape, eps: float, bits: int, generator):
+        return _node_forward(ctx, True, input, weight, bias, normalized_shape, eps, bits, generator)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        return (*_node_backward(ctx, True, grad_output), None, None, None, None)
+
+
+class _RMSNormQuantized(torch.autograd.Function):
+    """``F.rms_norm`` that keeps ``x^`` in ``bits`` bits per element (module docstring).  Kept for backward exactly what ``_LayerNormQuantized``
+    keeps."""
+
+    @staticmethod
+    def forward(ctx, input, weight, normalized_shape, eps: float, bits: int, generator):
+        return _node_forward(ctx, False, input, weight, None, normalized_shape, eps, bits, generator)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        return (*_node_backward(ctx, False, grad_output)[:2], None, None, None, None)
+
+
+def _norm_quantized(centred: bool, input, normalized_shape, weight, bias, eps, bits, generator) -> torch.Tensor:
+    """the functional front of both kinds: the refusals, the plain forward when nothing is kept, the node otherwise"""
+    if bits not in cabi_x.QUANT_BITS:
+        raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+    normalized_shape = (normalized_shape, ) if isinstance(normalized_shape, int) else tuple(normalized_shape)
+    if tuple(input.shape[input.dim() - len(normalized_shape):]) != normalized_shape or not normalized_shape:
+        return _torch_norm(centred, input, normalized_shape, weight, bias, eps)              # (torch words the refusal)
+    if not centred:                                                                       # (the default F.rms_norm documents)
+        eps = float(torch.finfo(input.dtype).eps if eps is None else eps)
+    if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (input, weight, bias)):
+        flat = input.detach().reshape(-1, math.prod(normalized_shape))
+        if not _kernel_applies(flat, weight, bias):
+            return _torch_norm(centred, input, normalized_shape, weight, bias, eps)
+        return _kernel_forward(centred, flat, weight, bias, eps, keep=False)[0].view(input.shape)
+    if centred:
+        return _LayerNormQuantized.apply(input, weight, bias, normalized_shape, float(eps), int(bits), generator)
+    return _RMSNormQuantized.apply(input, weight, normalized_shape, eps, int(bits), generator)
+
+
+class _QuantizedNorm:
+    """What the two modules share, in front of ``nn.LayerNorm`` / ``nn.RMSNorm`` in their bases: the check of ``bits``, the eval-mode rule and the
+    repr.  ``_centred`` is the kind."""
+
+    def __init__(self, bits: int, generator: Optional[torch.Generator], *norm_arguments) -> None:
+        if bits not in cabi_x.QUANT_BITS:
+            raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+        super().__init__(*norm_arguments)
+        self.bits = bits
+        self.generator = generator
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        bias = self.bias if self._centred else None
+        if not self.training and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, self.weight, bias)):
+            # eval mode is not where activation memory is short: gradients asked for there are torch's exact ones, nothing is rounded or drawn
+            return _torch_norm(self._centred, input, self.normalized_shape, self.weight, bias, self.eps)
+        return _norm_quantized(self._centred, input, self.normalized_shape, self.weight, bias, self.eps, self.bits, self.generator)
+
+    def extra_repr(self) -> str:
+        return f'{super().extra_repr()}, bits={self.bits}'
 
 
 def layer_norm_quantized(input: torch.Tensor, normalized_shape: Union[int, Sequence[int]], weight: Optional[torch.Tensor] = None,
@@ -150,23 +225,10 @@ def layer_norm_quantized(input: torch.Tensor, normalized_shape: Union[int, Seque
     forward -- no seed is drawn and nothing is kept.  Under ``torch.autocast`` the kernel path returns the INPUT's dtype where torch returns
     fp32.  Inside ``torch.utils.checkpoint`` ``generator`` must be a default one (``None`` included): checkpoint restores only those, and the
     recomputation must draw the forward's seed again (module docstring)."""
-    if bits not in linear.QUANT_BITS:
-        raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
-    normalized_shape = (normalized_shape, ) if isinstance(normalized_shape, int) else tuple(normalized_shape)
-    if tuple(input.shape[input.dim() - len(normalized_shape):]) != normalized_shape or not normalized_shape:
-        return F.layer_norm(input, normalized_shape, weight, bias, eps)                   # (torch words the refusal)
-    if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (input, weight, bias)):
-        flat = input.detach().reshape(-1, math.prod(normalized_shape))
-        if not _kernel_applies(flat, weight, bias):
-            return F.layer_norm(input, normalized_shape, weight, bias, eps)
-        from . import cabi_x
-        y, _, _, _ = cabi_x.layer_norm_forward(flat if flat.is_contiguous() else flat.contiguous(), _as(weight, flat.dtype), _as(bias, flat.dtype), eps,
-                                               keep=False)
-        return y.view(input.shape)
-    return _LayerNormQuantized.apply(input, weight, bias, normalized_shape, float(eps), int(bits), generator)
+    return _norm_quantized(True, input, normalized_shape, weight, bias, eps, bits, generator)
 
 
-class QuantizedLayerNorm(torch.nn.LayerNorm):
+class QuantizedLayerNorm(_QuantizedNorm, torch.nn.LayerNorm):
     r"""Drop-in :class:`torch.nn.LayerNorm` that keeps its normalized input in ``bits`` bits per element, plus one fp32 per row, instead of the
     input itself (:func:`layer_norm_quantized`); the output is that of ``nn.LayerNorm``.
 
@@ -192,13 +254,11 @@ class QuantizedLayerNorm(torch.nn.LayerNorm):
         >>> model = fewbit.map_module(model, lambda m, path: fewbit.QuantizedLayerNorm.from_layer_norm(m, bits=4) if type(m) is torch.nn.LayerNorm else m)
     """
 
+    _centred = True
+
     def __init__(self, normalized_shape, eps: float = 1e-5, elementwise_affine: bool = True, bias: bool = True, device=None, dtype=None, bits: int = 4,
                  generator: Optional[torch.Generator] = None) -> None:
-        if bits not in linear.QUANT_BITS:
-            raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
-        super().__init__(normalized_shape, eps, elementwise_affine, bias, device, dtype)
-        self.bits = bits
-        self.generator = generator
+        super().__init__(bits, generator, normalized_shape, eps, elementwise_affine, bias, device, dtype)
 
     @classmethod
     def from_layer_norm(cls, module: torch.nn.LayerNorm, bits: int = 4, generator: Optional[torch.Generator] = None) -> 'QuantizedLayerNorm':
@@ -207,76 +267,6 @@ class QuantizedLayerNorm(torch.nn.LayerNorm):
         new.weight, new.bias = module.weight, module.bias
         return new.train(module.training)
 
-    def forward(self, input: torch.Tensor) -> torch.Tensor:
-        if not self.training and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, self.weight, self.bias)):
-            # eval mode is not where activation memory is short: gradients asked for there are torch's exact ones, nothing is rounded or drawn
-            return F.layer_norm(input, self.normalized_shape, self.weight, self.bias, self.eps)
-        return layer_norm_quantized(input, self.normalized_shape, self.weight, self.bias, self.eps, self.bits, self.generator)
-
-    def extra_repr(self) -> str:
-        return f'{super().extra_repr()}, bits={self.bits}'
-
-
-# ---- the RMS norm: the un-centred statistic, backward without the mean term, no beta -----------------------------------------------------
-def _scaled_rows(flat: torch.Tensor, eps: float):
-    """(x^, rstd) of the rows of ``flat`` in fp32 (fp64 for a float64 input): ``x^ = x * rstd``, ``rstd = 1 / sqrt(mean(x^2) + eps)``"""
-    work = flat.to(torch.float64 if flat.dtype == torch.float64 else torch.float32)
-    rstd = 1.0 / torch.sqrt(work.square().mean(dim=1, keepdim=True) + eps)
-    return work * rstd, rstd.reshape(-1)
-
-
-def _rms_backward_formula(gy: torch.Tensor, xq: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor]):
-    """(dx, dgamma) of the definition in the dtype of ``xq``"""
-    gy = gy.to(xq.dtype)
-    gh = gy if gamma is None else gy * gamma.reshape(1, -1).to(xq.dtype)
-    dx = rstd[:, None] * (gh - xq * (gh * xq).mean(dim=1, keepdim=True))
-    return dx, (gy * xq).sum(dim=0)
-
-
-class _RMSNormQuantized(torch.autograd.Function):
-    """``F.rms_norm`` that keeps ``x^`` in ``bits`` bits per element (module docstring).  Kept for backward exactly what ``_LayerNormQuantized``
-    keeps: on the kernels the state, ``rstd`` and gamma; in the PyTorch formulation the codes, lo and step of every group, ``rstd`` and gamma."""
-
-    @staticmethod
-    def forward(ctx, input, weight, normalized_shape, eps: float, bits: int, generator):
-        width = math.prod(normalized_shape)
-        flat = input.detach().reshape(-1, width)
-        ctx.bits, ctx.flat_shape, ctx.input_dtype, ctx.has_weight = bits, tuple(flat.shape), input.dtype, weight is not None
-        ctx.autocast = linear._autocast_seen(input.device.type)
-        ctx.native_seed = None
-        if _kernel_applies(flat, weight, None):
-            from . import cabi_x
-            ctx.native_seed = linear._sketch_seed(generator, flat.device)
-            y, rstd, state, _ = cabi_x.rms_norm_forward(flat if flat.is_contiguous() else flat.contiguous(), _as(weight, flat.dtype), eps, bits, ctx.native_seed)
-            ctx.save_for_backward(state, rstd, *((weight, ) if ctx.has_weight else ()))
-            return y.view(input.shape)
-        xhat, rstd = _scaled_rows(flat, eps)
-        ctx.save_for_backward(*linear._quantize_groups(_padded_rows(xhat), bits, generator), rstd, *((weight, ) if ctx.has_weight else ()))
-        return F.rms_norm(input, normalized_shape, weight, eps)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_output):
-        with linear._autocast_as(ctx.autocast):
-            return _RMSNormQuantized._backward(ctx, linear._dense_rows(grad_output))
-
-    @staticmethod
-    def _backward(ctx, grad_output):
-        saved = ctx.saved_tensors                       # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
-        weight = saved[-1] if ctx.has_weight else None
-        rows, width = ctx.flat_shape
-        gy = grad_output.reshape(rows, width)
-        want = tuple(ctx.needs_input_grad[:2])
-        if ctx.native_seed is not None:
-            from . import cabi_x
-            gy = gy if gy.dtype in _KERNEL_DTYPES else gy.float()
-            dx, dgamma = cabi_x.rms_norm_backward(gy, saved[0], saved[1], _as(weight, gy.dtype), ctx.bits, want)
-        else:
-            codes, lo, step, rstd = saved[:4]
-            dx, dgamma = _rms_backward_formula(gy, _decoded_rows(codes, lo, step, rows, width), rstd, weight)
-        grad_input = dx.to(ctx.input_dtype).view(grad_output.shape) if want[0] else None
-        grad_weight = dgamma.to(weight.dtype).view(weight.shape) if want[1] else None
-        return grad_input, grad_weight, None, None, None, None
 
 
 def rms_norm_quantized(input: torch.Tensor, normalized_shape: Union[int, Sequence[int]], weight: Optional[torch.Tensor] = None, eps: Optional[float] = None,
@@ -287,23 +277,10 @@ def rms_norm_quantized(input: torch.Tensor, normalized_shape: Union[int, Sequenc
     ``eps=None`` means ``torch.finfo(input.dtype).eps``, the default ``F.rms_norm`` documents (for a 16-bit host tensor torch 2.10's own
     composite takes the epsilon of its fp32 arithmetic instead; pass ``eps`` to be independent of that).  ``generator``, grad mode off, ``torch.autocast`` and
     ``torch.utils.checkpoint``: the rules of :func:`layer_norm_quantized`."""
-    if bits not in linear.QUANT_BITS:
-        raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
-    normalized_shape = (normalized_shape, ) if isinstance(normalized_shape, int) else tuple(normalized_shape)
-    if tuple(input.shape[input.dim() - len(normalized_shape):]) != normalized_shape or not normalized_shape:
-        return F.rms_norm(input, normalized_shape, weight, eps)                           # (torch words the refusal)
-    eps = float(torch.finfo(input.dtype).eps if eps is None else eps)
-    if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (input, weight)):
-        flat = input.detach().reshape(-1, math.prod(normalized_shape))
-        if not _kernel_applies(flat, weight, None):
-            return F.rms_norm(input, normalized_shape, weight, eps)
-        from . import cabi_x
-        y, _, _, _ = cabi_x.rms_norm_forward(flat if flat.is_contiguous() else flat.contiguous(), _as(weight, flat.dtype), eps, keep=False)
-        return y.view(input.shape)
-    return _RMSNormQuantized.apply(input, weight, normalized_shape, eps, int(bits), generator)
+    return _norm_quantized(False, input, normalized_shape, weight, None, eps, bits, generator)
 
 
-class QuantizedRMSNorm(torch.nn.RMSNorm):
+class QuantizedRMSNorm(_QuantizedNorm, torch.nn.RMSNorm):
     r"""Drop-in :class:`torch.nn.RMSNorm` that keeps its normalized input in ``bits`` bits per element, plus one fp32 per row, instead of the
     input itself (:func:`rms_norm_quantized`); the output is that of ``nn.RMSNorm``.
 
@@ -326,13 +303,11 @@ class QuantizedRMSNorm(torch.nn.RMSNorm):
         >>> model = fewbit.map_module(model, swap)
     """
 
+    _centred = False
+
     def __init__(self, normalized_shape, eps: Optional[float] = None, elementwise_affine: bool = True, device=None, dtype=None, bits: int = 4,
                  generator: Optional[torch.Generator] = None) -> None:
-        if bits not in linear.QUANT_BITS:
-            raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
-        super().__init__(normalized_shape, eps, elementwise_affine, device, dtype)
-        self.bits = bits
-        self.generator = generator
+        super().__init__(bits, generator, normalized_shape, eps, elementwise_affine, device, dtype)
 
     @classmethod
     def from_rms_norm(cls, module: torch.nn.Module, bits: int = 4, generator: Optional[torch.Generator] = None) -> 'QuantizedRMSNorm':
@@ -351,12 +326,3 @@ class QuantizedRMSNorm(torch.nn.RMSNorm):
         new = cls(shape, eps, affine, device='meta', bits=bits, generator=generator)
         new.weight = module.weight
         return new.train(module.training)
-
-    def forward(self, input: torch.Tensor) -> torch.Tensor:
-        if not self.training and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, self.weight)):
-            # eval mode is not where activation memory is short: gradients asked for there are torch's exact ones, nothing is rounded or drawn
-            return F.rms_norm(input, self.normalized_shape, self.weight, self.eps)
-        return rms_norm_quantized(input, self.normalized_shape, self.weight, self.eps, self.bits, self.generator)
-
-    def extra_repr(self) -> str:
-        return f'{super().extra_repr()}, bits={self.bits}'

@@ -13,7 +13,6 @@ and as a device word.
   ``(rows + 3) 2^-24 sum_r |terms|``, the bound of a fixed-order fp32 sum of `rows` rounded products; two runs byte-equal; NULL outputs skipped.
 The measured K and K' are printed (EXPERIMENTS.md 8.18 records them)."""
 import itertools
-import math
 
 import numpy as np
 import pytest
@@ -21,50 +20,16 @@ import torch
 import torch.nn.functional as F
 
 from fewbit_amd import cabi_x
+from norm_harness import DEV, EPS, FILL, SEED, UNIT, Guarded, allowance, options, seed_argument
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
 # 64 | 65, 128 | 129, 512 | 513, 1024 | 1025, 2048 | 2049, 4096 | 4097: one width on each side of every threshold of the plan (cabi_x.norm_plan)
 WIDTHS = (1, 7, 8, 9, 63, 64, 65, 128, 129, 200, 512, 513, 768, 770, 1024, 1025, 2048, 2049, 4096, 4097, 8192)
 ROWS = (1, 3, 37)
 DTYPES = (torch.float32, torch.float16, torch.bfloat16)
 BITS = (2, 4, 8)
-UNIT = {torch.float32: 2.0**-24, torch.float16: 2.0**-11, torch.bfloat16: 2.0**-8}
-EPS = 1e-5
 EPS32 = float(np.float32(EPS))
-SEED = 0x0123456789abcdef
-FILL = 0xA5
 ids = lambda d: str(d).split('.')[-1] if isinstance(d, torch.dtype) else None
-
-
-class Guarded:
-    """`numel` elements of `dtype` on the GPU, `off` elements behind a 256-byte aligned address, between 256 guard bytes on either side"""
-
-    def __init__(self, numel, dtype, off=0, like=None):
-        item = torch.empty(0, dtype=dtype).element_size()
-        self.lo = 256 + off * item
-        self.hi = self.lo + numel * item
-        self.raw = torch.full((self.hi + 256, ), FILL, dtype=torch.uint8, device=DEV)
-        assert self.raw.data_ptr() % 256 == 0
-        self.t = self.raw[self.lo:self.hi].view(dtype)
-        if like is not None:
-            self.t.copy_(like.reshape(-1))
-        self.before = self.raw.clone()
-
-    def intact(self):
-        return bool((self.raw[:self.lo] == FILL).all()) and bool((self.raw[self.hi:] == FILL).all())
-
-    def unchanged(self):
-        return torch.equal(self.raw, self.before)
-
-
-def options(i):
-    """offset from 16-byte alignment (elements), gamma / beta present, the seed as a device word: every combination within 8 cases"""
-    return i & 1, bool((i >> 1) & 1), bool((i >> 2) & 1)
-
-
-def seed_argument(device_word):
-    return torch.tensor([SEED], dtype=torch.int64, device=DEV) if device_word else SEED
 
 
 def inputs(rows, width, dtype, salt=0, kind='normal'):
@@ -91,10 +56,6 @@ def plain_fp32(x):
     centred = x - x.mean(dim=1, keepdim=True)
     rstd = 1.0 / torch.sqrt(centred.square().mean(dim=1, keepdim=True) + EPS32)
     return (centred * rstd).double().cpu(), rstd.double().cpu()
-
-
-def allowance(measured, width):
-    return max(2.0 * measured, math.log2(width) + 4.0)
 
 
 def run_forward(x, gamma, beta, bits, seed, off, keep=True, want_xhat=True):

@@ -18,7 +18,6 @@ a device word.
   sum alternate between tiles, which the sweeps of 2 and of 3 tiles per workgroup would show if they did not.
 The measured K and K' are printed (EXPERIMENTS.md 8.19 records them)."""
 import itertools
-import math
 
 import numpy as np
 import pytest
@@ -26,54 +25,20 @@ import torch
 import torch.nn.functional as F
 
 from fewbit_amd import cabi_x
+from norm_harness import DEV, EPS, FILL, SEED, UNIT, Guarded, allowance, options, seed_argument
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
 # 64 | 65, 128 | 129, 512 | 513, 1024 | 1025, 2048 | 2049, 4096 | 4097: one width on each side of every threshold of the plan (cabi_x.norm_plan)
 WIDTHS = (1, 7, 8, 9, 63, 64, 65, 128, 129, 200, 512, 513, 768, 770, 1024, 1025, 2048, 2049, 4096, 4097, 8192)
 ROWS = (1, 3, 37)
 DTYPES = (torch.float32, torch.float16, torch.bfloat16)
 BITS = (2, 4, 8)
-UNIT = {torch.float32: 2.0**-24, torch.float16: 2.0**-11, torch.bfloat16: 2.0**-8}
-EPS = 1e-5
 EPS32 = float(np.float32(EPS))
 TINY = 2.0**-149                                                      # the smallest fp32 denormal
 # half the spacing of the dtype's denormals: what ONE correct rounding to the dtype may err by where u |value| is smaller than that (a y or dx below
 # the smallest normal number: 2^-14 in fp16, which x^ = x rstd of an fp16 x near 1e-4 reaches)
 HALF_DENORMAL = {torch.float32: 2.0**-150, torch.float16: 2.0**-25, torch.bfloat16: 2.0**-134}
-SEED = 0x0123456789abcdef
-FILL = 0xA5
 ids = lambda d: str(d).split('.')[-1] if isinstance(d, torch.dtype) else None
-
-
-class Guarded:
-    """`numel` elements of `dtype` on the GPU, `off` elements behind a 256-byte aligned address, between 256 guard bytes on either side"""
-
-    def __init__(self, numel, dtype, off=0, like=None):
-        item = torch.empty(0, dtype=dtype).element_size()
-        self.lo = 256 + off * item
-        self.hi = self.lo + numel * item
-        self.raw = torch.full((self.hi + 256, ), FILL, dtype=torch.uint8, device=DEV)
-        assert self.raw.data_ptr() % 256 == 0
-        self.t = self.raw[self.lo:self.hi].view(dtype)
-        if like is not None:
-            self.t.copy_(like.reshape(-1))
-        self.before = self.raw.clone()
-
-    def intact(self):
-        return bool((self.raw[:self.lo] == FILL).all()) and bool((self.raw[self.hi:] == FILL).all())
-
-    def unchanged(self):
-        return torch.equal(self.raw, self.before)
-
-
-def options(i):
-    """offset from 16-byte alignment (elements), gamma present, the seed as a device word: every combination within 8 cases"""
-    return i & 1, bool((i >> 1) & 1), bool((i >> 2) & 1)
-
-
-def seed_argument(device_word):
-    return torch.tensor([SEED], dtype=torch.int64, device=DEV) if device_word else SEED
 
 
 def inputs(rows, width, dtype, salt=0, kind='normal'):
@@ -96,10 +61,6 @@ def plain_fp32(x):
     x = x.float()
     rstd = 1.0 / torch.sqrt(x.square().mean(dim=1, keepdim=True) + EPS32)
     return (x * rstd).double().cpu(), rstd.double().cpu()
-
-
-def allowance(measured, width):
-    return max(2.0 * measured, math.log2(width) + 4.0)
 
 
 def run_forward(x, gamma, bits, seed, off, keep=True, want_xhat=True):

@@ -8,64 +8,29 @@ import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
-from torch.utils.checkpoint import checkpoint
 
 import fewbit
-from fewbit_amd import cabi, cabi_x, linear
+import norm_harness as harness
+from fewbit_amd import cabi_x, linear
+from norm_harness import DEV, EPS, UNIT, native_sketch_on, saved_by, seeds  # noqa: F401 (the fixtures are used by name)
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
+KIND = harness.RMS_NORM
 SHAPES = ((256, 64), (200, 72), (8, 25, 72))
 DTYPES = (torch.bfloat16, torch.float32)
 BITS = (2, 4, 8)
-UNIT = {torch.float32: 2.0**-24, torch.float16: 2.0**-11, torch.bfloat16: 2.0**-8}
-EPS = 1e-5
 ids = lambda d: str(d).split('.')[-1] if isinstance(d, torch.dtype) else None
 
 
-@pytest.fixture(autouse=True)
-def native_sketch_on():
-    prev = linear.use_native_sketch(True)
-    yield
-    linear.use_native_sketch(prev)
-
-
-@pytest.fixture
-def seeds(monkeypatch):
-    """the seeds the layer draws, in order"""
-    drawn = []
-    real = linear._draw_seed
-
-    def draw(generator):
-        drawn.append(real(generator))
-        return drawn[-1]
-
-    monkeypatch.setattr(linear, '_draw_seed', draw)
-    return drawn
-
-
-def saved_by(call):
-    saved = []
-    with torch.autograd.graph.saved_tensors_hooks(lambda t: saved.append(t) or t, lambda t: t):
-        result = call()
-    return result, saved
-
-
 def problem(shape, dtype, salt=0):
-    g = torch.Generator().manual_seed(53 + salt)
-    width = shape[-1]
-    x = (3 + 2 * torch.randn(*shape, generator=g)).to(dtype).to(DEV).requires_grad_()
-    w = (1 + 0.5 * torch.randn(width, generator=g)).to(dtype).to(DEV).requires_grad_()
-    gy = torch.randn(*shape, generator=g).to(dtype).to(DEV)
+    x, (w, ), gy = harness.problem(KIND, shape, dtype, salt)
     return x, w, gy
 
 
 def entry_points(x, w, gy, bits, seed):
     """(y, dx, dgamma, state, rstd) of the entry points for `seed`"""
-    flat = x.detach().reshape(-1, x.shape[-1]).contiguous()
-    y, rstd, state, _ = cabi_x.rms_norm_forward(flat, w.detach(), EPS, bits, seed)
-    dx, dgamma = cabi_x.rms_norm_backward(gy.reshape(flat.shape).contiguous(), state, rstd, w.detach(), bits)
-    return y.view(x.shape), dx.view(x.shape), dgamma, state, rstd
+    y, grads, state, rstd = harness.entry_points(KIND, x, (w, ), gy, bits, seed)
+    return (y, *grads, state, rstd)
 
 
 @pytest.mark.parametrize('bits', BITS)
@@ -104,66 +69,22 @@ def test_the_layer_against_float64_and_the_recorded_seed(shape, dtype, bits, see
 
 @pytest.mark.parametrize('reentrant', (False, True))
 def test_checkpointing_gives_the_plain_runs_bits(reentrant):
-    x, w, gy = problem(SHAPES[1], torch.bfloat16, 2)
-    call = lambda t, weight: fewbit.functional.rms_norm_quantized(t, (t.shape[-1], ), weight, EPS, 4)
-    torch.manual_seed(12)
-    y0 = call(x, w)
-    plain = torch.autograd.grad(y0, (x, w), gy)
-    torch.manual_seed(12)
-    y = checkpoint(call, x, w, use_reentrant=reentrant)
-    x.grad = w.grad = None
-    y.backward(gy)
-    assert torch.equal(y, y0)
-    for got, want in zip((x.grad, w.grad), plain):
-        assert torch.equal(got, want)
-    x.grad = w.grad = None
+    harness.checkpointing_gives_the_plain_runs_bits(KIND, SHAPES[1], reentrant)
 
 
 def test_backward_may_follow_the_autocast_block(seeds):
-    x, w, gy = problem(SHAPES[1], torch.float32, 1)
-    x16 = x.detach().bfloat16().requires_grad_()
-    with torch.autocast('cuda', dtype=torch.bfloat16):
-        y = fewbit.functional.rms_norm_quantized(x16, (x.shape[-1], ), w, EPS, 4)
-    assert y.dtype == torch.bfloat16 and type(y.grad_fn).__name__ == '_RMSNormQuantizedBackward'
-    g16 = gy.bfloat16()
-    gx, gw = torch.autograd.grad(y, (x16, w), g16)                       # outside the block: the ordinary AMP pattern
-    assert gx.dtype == torch.bfloat16 and gw.dtype == torch.float32
-    ye, dxe, dge, _, _ = entry_points(x16, w.bfloat16(), g16, 4, seeds[0])
-    assert torch.equal(y, ye) and torch.equal(gx, dxe) and torch.equal(gw, dge)
+    harness.backward_may_follow_the_autocast_block(KIND, SHAPES[1], seeds)
 
 
 def test_no_grad_eval_and_frozen_parameters_build_no_node_and_keep_no_state(seeds):
     x, w, gy = problem(SHAPES[1], torch.bfloat16, 3)
-    layer = fewbit.QuantizedRMSNorm(x.shape[-1], eps=EPS, device=DEV, dtype=torch.bfloat16)
-    y_train, _ = saved_by(lambda: layer(x))
-    count = len(seeds)
-    assert count == 1
-    with torch.no_grad():
-        y, saved = saved_by(lambda: layer(x))
-    assert y.grad_fn is None and not saved and torch.equal(y, y_train)   # the plain forward: the same bytes
-    layer.eval()
-    y, saved = saved_by(lambda: layer(x))                                # eval: no state, no seed; gradients asked for there are torch's exact ones
-    assert 'Quantized' not in type(y.grad_fn).__name__ and not any(t.dtype == torch.uint8 for t in saved) and len(seeds) == count
-    with torch.no_grad():
-        assert torch.equal(layer(x), y_train)
-    layer.train()
-    layer.requires_grad_(False)
-    y, saved = saved_by(lambda: layer(x.detach()))
-    assert y.grad_fn is None and not saved and torch.equal(y, y_train) and len(seeds) == count
-    with torch.inference_mode():
-        assert torch.equal(layer(x), y_train) and len(seeds) == count
+    harness.no_grad_eval_and_frozen_parameters_build_no_node_and_keep_no_state(KIND, x, seeds)
     # eps=None on the kernels: torch.finfo(input.dtype).eps
     none = fewbit.QuantizedRMSNorm(x.shape[-1], device=DEV, dtype=torch.bfloat16)
     with torch.no_grad():
         flat = x.detach()
         assert torch.equal(none(x), cabi_x.rms_norm_forward(flat, none.weight.detach(), torch.finfo(torch.bfloat16).eps, keep=False)[0])
-    # a non-contiguous input is normalized from a contiguous copy
-    base = torch.randn(x.shape[1], x.shape[0], device=DEV, dtype=torch.bfloat16)
-    xt = base.t().requires_grad_()
-    y = fewbit.functional.rms_norm_quantized(xt, (x.shape[-1], ), w, EPS, 4)
-    ye, dxe, dge, _, _ = entry_points(xt, w, gy, 4, seeds[-1])
-    gx, gw = torch.autograd.grad(y, (xt, w), gy)
-    assert torch.equal(y, ye) and torch.equal(gx, dxe) and torch.equal(gw, dge.bfloat16())
+    harness.a_non_contiguous_input_is_normalized_from_a_contiguous_copy(KIND, x, (w, ), gy, seeds)
 
 
 def test_with_the_kernels_switched_off_the_host_formulation_runs_on_the_gpu_tensor():
@@ -192,36 +113,4 @@ def test_with_the_kernels_switched_off_the_host_formulation_runs_on_the_gpu_tens
 
 
 def test_a_captured_step_rounds_afresh_on_every_replay(monkeypatch):
-    bits = 4
-    x, w, gy = problem(SHAPES[0], torch.float32, 4)
-    rows, width = SHAPES[0]
-
-    def step():
-        y, saved = saved_by(lambda: fewbit.functional.rms_norm_quantized(x, (width, ), w, EPS, bits))
-        return (y, ) + torch.autograd.grad(y, (x, w), gy) + (saved[0], saved[1])
-
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        step()                                                        # the eager warm-up: the per-device replay counter exists from here on
-    torch.cuda.current_stream().wait_stream(side)
-    bases = []
-    monkeypatch.setattr(linear, '_draw_seed', lambda generator: bases.append(0x2468ace) or bases[-1])
-    counter = linear._replay_counter(torch.device(DEV))
-    torch.cuda.synchronize()
-    c0 = int(counter)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        y, gx, gw, state, rstd = step()
-    assert len(bases) == 1 and int(counter) == c0
-    seen = []
-    for replay in range(2):
-        g.replay()
-        torch.cuda.synchronize()
-        assert int(counter) == c0 + replay + 1
-        # each replay is consistent with its own state: the state of the seed the replay counter gave, and the gradients of that state
-        ye, dxe, dge, state_e, rstd_e = entry_points(x, w, gy, bits, cabi.mix_sketch_seed(bases[0], c0 + replay))
-        assert torch.equal(y, ye) and torch.equal(state, state_e) and torch.equal(rstd, rstd_e)
-        assert torch.equal(gx, dxe) and torch.equal(gw, dge)
-        seen.append(gw.clone())
-    assert not torch.equal(seen[0], seen[1])
+    harness.a_captured_step_rounds_afresh_on_every_replay(KIND, SHAPES[0], monkeypatch)

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 import fewbit_amd as fewbit
 from fewbit_amd import cabi, cabi_x, norm
+from norm_harness import LAYER_NORM as KIND, M32, input_gradient_averages_out, order_keys, philox, saved_by, weight_gradient_is_unbiased
 
 ROOT = Path(__file__).resolve().parents[1]
 NORM_SYMBOLS = ('fewbit_hipx_norm_state_bytes', 'fewbit_hipx_norm_workspace', 'fewbit_hipx_norm_state_host', 'fewbit_hipx_norm_state_unpack_host',
@@ -22,22 +23,10 @@ NORM_SYMBOLS = ('fewbit_hipx_norm_state_bytes', 'fewbit_hipx_norm_workspace', 'f
 BITS = (2, 4, 8)
 WIDTHS = (1, 3, 7, 8, 9, 63, 64, 65, 200, 770)
 SEED = 0x1234567887654321
-M32 = np.uint64(0xffffffff)
 NAN_BITS = 0x7fc00000
 
 
 # ---- the definition restated in numpy ----------------------------------------------------------------------------------------------------
-def philox(c0, c1, c2, c3, seed):
-    """Philox4x32-10 on arrays of counters (uint64 holding 32-bit words), key = the two halves of `seed`"""
-    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & M32 for c in np.broadcast_arrays(c0, c1, c2, c3))
-    k0, k1 = np.uint64(seed & 0xffffffff), np.uint64((seed >> 32) & 0xffffffff)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & M32
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
-    return c0, c1, c2, c3
-
-
 def row_uniforms(r, width, seed):
     """U of the elements of row r: element 8 b + e takes the 16 bits of element e of block q = r * B + b, counter (q low, q high, 0, 7)"""
     blocks = (width + 7) // 8
@@ -47,12 +36,6 @@ def row_uniforms(r, width, seed):
     word = words[i >> 3, (i & 7) >> 1]
     u = np.where(i & 1, word >> np.uint64(16), word & np.uint64(0xffff))
     return u.astype(np.float32) / np.float32(65536)
-
-
-def order_keys(x):
-    """the order of the reals on float32 bits, -0 below +0"""
-    b = x.view(np.int32).astype(np.int64)
-    return np.where(b < 0, -(b & 0x7fffffff) - 1, b)
 
 
 def restated(xhat, bits, seed):
@@ -245,28 +228,7 @@ def test_the_binding_refuses_host_tensors_and_unknown_widths():
 
 
 # ---- fewbit.QuantizedLayerNorm on the host --------------------------------------------------------------------------------------------------
-def saved_by(call):
-    """-> (result, the tensors autograd saved while `call` ran)"""
-    saved = []
-    with torch.autograd.graph.saved_tensors_hooks(lambda t: saved.append(t) or t, lambda t: t):
-        result = call()
-    return result, saved
-
-
-def formula64(gy, xq, rstd, gamma):
-    """(dx, dgamma, dbeta) of the definition in float64"""
-    gy, xq, rstd = gy.double(), xq.double(), rstd.double()
-    gh = gy * gamma.double() if gamma is not None else gy
-    dx = rstd[:, None] * (gh - gh.mean(dim=1, keepdim=True) - xq * (gh * xq).mean(dim=1, keepdim=True))
-    return dx, (gy * xq).sum(dim=0), gy.sum(dim=0)
-
-
-def exact_rows(x, eps):
-    """(x^, rstd) in float64"""
-    x = x.double()
-    centred = x - x.mean(dim=1, keepdim=True)
-    rstd = 1.0 / torch.sqrt(centred.square().mean(dim=1, keepdim=True) + eps)
-    return centred * rstd, rstd.reshape(-1)
+formula64, exact_rows = KIND.formula64, KIND.exact_rows          # (dx, dgamma, dbeta) and (x^, rstd) of the definition in float64
 
 
 @pytest.mark.parametrize('bits', BITS)
@@ -370,57 +332,14 @@ def test_the_generator_decides_the_rounding_and_checkpointing_reproduces_it():
     x.grad = w.grad = b.grad = None
 
 
-# ---- the statistics of the definition: 200 calls, fp32 host tensors, seeds from torch.manual_seed(0) -----------------------------------------
-CALLS = 200
-
-
-def gradients_over_calls(rows, width, bits, salt=0):
-    """-> (exact dx, exact dgamma, the dx and dgamma of CALLS calls, float64) for N(3, 2^2) inputs"""
-    g = torch.Generator().manual_seed(17 + salt)
-    x = (3 + 2 * torch.randn(rows, width, generator=g)).requires_grad_()
-    w = (1 + 0.5 * torch.randn(width, generator=g)).requires_grad_()
-    b = torch.randn(width, generator=g).requires_grad_()
-    gy = torch.randn(rows, width, generator=g)
-    xhat, rstd = exact_rows(x.detach(), 1e-5)
-    dx, dgamma, _ = formula64(gy, xhat, rstd, w.detach())
-    torch.manual_seed(0)
-    dxs, dgs = [], []
-    for _ in range(CALLS):
-        gx, gw, _ = torch.autograd.grad(fewbit.functional.layer_norm_quantized(x, (width, ), w, b, 1e-5, bits), (x, w, b), gy)
-        dxs.append(gx.double())
-        dgs.append(gw.double())
-    return dx, dgamma, torch.stack(dxs), torch.stack(dgs)
-
-
-def worst_standard_error(samples, exact):
-    mean, sd = samples.mean(dim=0), samples.std(dim=0)
-    assert bool((sd > 0).all())
-    return float(((mean - exact).abs() / (sd / math.sqrt(samples.shape[0]))).max())
-
-
-def ratio_of_the_mean(samples, exact):
-    """R = |mean(dx_q) - dx| / (rms one-call error / sqrt(calls)): 1 for unbiased independent calls, sqrt(calls) for one reused seed"""
-    one_call = math.sqrt(float((samples - exact).square().sum(dim=(1, 2)).mean()))
-    return float((samples.mean(dim=0) - exact).norm()) / (one_call / math.sqrt(samples.shape[0])), one_call / float(exact.norm())
-
-
+# ---- the statistics of the definition: 200 calls, fp32 host tensors, seeds from torch.manual_seed(0) (norm_harness) ------------------------------
 @pytest.mark.parametrize('bits', BITS)
 @pytest.mark.parametrize('shape', ((48, 200), (32, 64), (40, 8)), ids=lambda s: 'x'.join(map(str, s)))
 def test_the_weight_gradient_is_unbiased(shape, bits):
-    """Every entry of the mean dgamma of 200 calls within 5 standard errors of sum gy x^ (E[x^q] = x^, and dgamma is linear in x^q)"""
-    _, dgamma, _, dgs = gradients_over_calls(*shape, bits)
-    z = worst_standard_error(dgs, dgamma)
-    print(f'{shape} bits {bits}: worst entry of dgamma {z:.2f} standard errors')
-    assert z <= 5.0
+    weight_gradient_is_unbiased(KIND, shape, bits)
 
 
 @pytest.mark.parametrize('bits', BITS)
 @pytest.mark.parametrize('shape', ((48, 200), (24, 770)), ids=lambda s: 'x'.join(map(str, s)))
 def test_the_input_gradient_averages_out_up_to_its_second_order_bias(shape, bits):
-    """dx is NOT exactly unbiased: x^q enters it twice, E[dx_q] - dx = -rstd g^_i Var(x^q_i) / width, second order in the step.  R compares the
-    deviation of the mean of 200 calls with the noise that mean would have if the calls were unbiased and independent (R = 1); a layer that
-    reused one seed gives sqrt(200), about 14.  Bound: R <= 1.5, from width 64 on (at (40, 8) and 2 bits the bias itself gives 2.0)."""
-    dx, _, dxs, _ = gradients_over_calls(*shape, bits, 1)
-    R, relative = ratio_of_the_mean(dxs, dx)
-    print(f'{shape} bits {bits}: R = {R:.3f}, relative error of one call {relative:.5f}')
-    assert R <= 1.5
+    input_gradient_averages_out(KIND, shape, bits)

@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 import fewbit_amd as fewbit
 from fewbit_amd import cabi, cabi_x, linear
+from norm_harness import M32, order_keys, philox, saved_by
 
 ROOT = Path(__file__).resolve().parents[1]
 QUANT_SYMBOLS = ('fewbit_hipx_quant_bytes', 'fewbit_hipx_quant_pack_host', 'fewbit_hipx_quant_unpack_host', 'fewbit_hipx_quant_pack',
@@ -21,22 +22,10 @@ QUANT_SYMBOLS = ('fewbit_hipx_quant_bytes', 'fewbit_hipx_quant_pack_host', 'fewb
 BITS = (2, 4, 8)
 SIZES = (1, 7, 8, 9, 63, 64, 65, 205, 2573)
 SEED = 0x1234567887654321
-M32 = np.uint64(0xffffffff)
 NAN_BITS = 0x7fc00000
 
 
 # ---- the definition restated in numpy ----------------------------------------------------------------------------------------------------
-def philox(c0, c1, c2, c3, seed):
-    """Philox4x32-10 on arrays of counters (uint64 holding 32-bit words), key = the two halves of `seed`"""
-    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & M32 for c in np.broadcast_arrays(c0, c1, c2, c3))
-    k0, k1 = np.uint64(seed & 0xffffffff), np.uint64((seed >> 32) & 0xffffffff)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & M32
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
-    return c0, c1, c2, c3
-
-
 def uniforms(n, seed):
     """U(i) for i < n: block q = i >> 3, counter (q low, q high, 0, 7), word (i & 7) >> 1, low half for even i, high half for odd i"""
     q = np.arange((n + 7) // 8, dtype=np.uint64)
@@ -45,12 +34,6 @@ def uniforms(n, seed):
     word = words[i >> 3, (i & 7) >> 1]
     u = np.where(i & 1, word >> np.uint64(16), word & np.uint64(0xffff))
     return u.astype(np.float32) / np.float32(65536)
-
-
-def order_keys(x):
-    """the order of the reals on float32 bits, -0 below +0"""
-    b = x.view(np.int32).astype(np.int64)
-    return np.where(b < 0, -(b & 0x7fffffff) - 1, b)
 
 
 def restated(x, bits, seed):
@@ -271,14 +254,6 @@ def test_the_binding_refuses_host_tensors_and_unknown_widths():
 
 # ---- fewbit.QuantizedLinear on the host ----------------------------------------------------------------------------------------------------
 ROWS, IN, OUT = 96, 24, 16
-
-
-def saved_by(call):
-    """-> (result, the tensors autograd saved while `call` ran)"""
-    saved = []
-    with torch.autograd.graph.saved_tensors_hooks(lambda t: saved.append(t) or t, lambda t: t):
-        result = call()
-    return result, saved
 
 
 @pytest.mark.parametrize('bits', BITS)

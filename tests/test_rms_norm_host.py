@@ -13,6 +13,7 @@ import torch.nn.functional as F
 
 import fewbit_amd as fewbit
 from fewbit_amd import cabi, cabi_x, norm
+from norm_harness import RMS_NORM as KIND, input_gradient_averages_out, saved_by, weight_gradient_is_unbiased
 
 ROOT = Path(__file__).resolve().parents[1]
 RMS_SYMBOLS = ('fewbit_hipx_rms_norm_forward', 'fewbit_hipx_rms_norm_backward')
@@ -86,26 +87,7 @@ def test_the_binding_refuses_host_tensors():
 
 
 # ---- fewbit.QuantizedRMSNorm on the host ---------------------------------------------------------------------------------------------------
-def saved_by(call):
-    """-> (result, the tensors autograd saved while `call` ran)"""
-    saved = []
-    with torch.autograd.graph.saved_tensors_hooks(lambda t: saved.append(t) or t, lambda t: t):
-        result = call()
-    return result, saved
-
-
-def formula64(gy, xq, rstd, gamma):
-    """(dx, dgamma) of the definition in float64"""
-    gy, xq, rstd = gy.double(), xq.double(), rstd.double()
-    gh = gy * gamma.double() if gamma is not None else gy
-    return rstd[:, None] * (gh - xq * (gh * xq).mean(dim=1, keepdim=True)), (gy * xq).sum(dim=0)
-
-
-def exact_rows(x, eps):
-    """(x^, rstd) in float64"""
-    x = x.double()
-    rstd = 1.0 / torch.sqrt(x.square().mean(dim=1, keepdim=True) + eps)
-    return x * rstd, rstd.reshape(-1)
+formula64, exact_rows = KIND.formula64, KIND.exact_rows          # (dx, dgamma) and (x^, rstd) of the definition in float64
 
 
 @pytest.mark.parametrize('bits', BITS)
@@ -281,56 +263,14 @@ def test_the_generator_decides_the_rounding_and_checkpointing_reproduces_it():
     x.grad = w.grad = None
 
 
-# ---- the statistics of the definition: 200 calls, fp32 host tensors, seeds from torch.manual_seed(0) -----------------------------------------
-CALLS = 200
-
-
-def gradients_over_calls(rows, width, bits, salt=0):
-    """-> (exact dx, exact dgamma, the dx and dgamma of CALLS calls, float64) for N(3, 2^2) inputs"""
-    g = torch.Generator().manual_seed(17 + salt)
-    x = (3 + 2 * torch.randn(rows, width, generator=g)).requires_grad_()
-    w = (1 + 0.5 * torch.randn(width, generator=g)).requires_grad_()
-    gy = torch.randn(rows, width, generator=g)
-    xhat, rstd = exact_rows(x.detach(), 1e-5)
-    dx, dgamma = formula64(gy, xhat, rstd, w.detach())
-    torch.manual_seed(0)
-    dxs, dgs = [], []
-    for _ in range(CALLS):
-        gx, gw = torch.autograd.grad(fewbit.functional.rms_norm_quantized(x, (width, ), w, 1e-5, bits), (x, w), gy)
-        dxs.append(gx.double())
-        dgs.append(gw.double())
-    return dx, dgamma, torch.stack(dxs), torch.stack(dgs)
-
-
-def worst_standard_error(samples, exact):
-    mean, sd = samples.mean(dim=0), samples.std(dim=0)
-    assert bool((sd > 0).all())
-    return float(((mean - exact).abs() / (sd / math.sqrt(samples.shape[0]))).max())
-
-
-def ratio_of_the_mean(samples, exact):
-    """R = |mean(dx_q) - dx| / (rms one-call error / sqrt(calls)): 1 for unbiased independent calls, sqrt(calls) for one reused seed"""
-    one_call = math.sqrt(float((samples - exact).square().sum(dim=(1, 2)).mean()))
-    return float((samples.mean(dim=0) - exact).norm()) / (one_call / math.sqrt(samples.shape[0])), one_call / float(exact.norm())
-
-
+# ---- the statistics of the definition: 200 calls, fp32 host tensors, seeds from torch.manual_seed(0) (norm_harness) ------------------------------
 @pytest.mark.parametrize('bits', BITS)
 @pytest.mark.parametrize('shape', ((48, 200), (32, 64), (40, 8)), ids=lambda s: 'x'.join(map(str, s)))
 def test_the_weight_gradient_is_unbiased(shape, bits):
-    """Every entry of the mean dgamma of 200 calls within 5 standard errors of sum gy x^ (E[x^q] = x^, and dgamma is linear in x^q)"""
-    _, dgamma, _, dgs = gradients_over_calls(*shape, bits)
-    z = worst_standard_error(dgs, dgamma)
-    print(f'{shape} bits {bits}: worst entry of dgamma {z:.2f} standard errors')
-    assert z <= 5.0
+    weight_gradient_is_unbiased(KIND, shape, bits)
 
 
 @pytest.mark.parametrize('bits', BITS)
 @pytest.mark.parametrize('shape', ((48, 200), (24, 770)), ids=lambda s: 'x'.join(map(str, s)))
 def test_the_input_gradient_averages_out_up_to_its_second_order_bias(shape, bits):
-    """dx is NOT exactly unbiased: x^q enters it twice, E[dx_q] - dx = -rstd g^_i Var(x^q_i) / width, second order in the step.  R compares the
-    deviation of the mean of 200 calls with the noise that mean would have if the calls were unbiased and independent (R = 1); a layer that
-    reused one seed gives sqrt(200), about 14.  Bound: R <= 1.5, the layer norm's."""
-    dx, _, dxs, _ = gradients_over_calls(*shape, bits, 1)
-    R, relative = ratio_of_the_mean(dxs, dx)
-    print(f'{shape} bits {bits}: R = {R:.3f}, relative error of one call {relative:.5f}')
-    assert R <= 1.5
+    input_gradient_averages_out(KIND, shape, bits)
