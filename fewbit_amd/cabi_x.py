@@ -2,7 +2,8 @@
 of ``libfewbit_hip.so`` was frozen at version 5 (``cabi.SYMBOLS`` stays that list).  Same conventions as ``cabi``: device tensors,
 torch's current stream on the tensors' device, no fallback -- a missing library or an unsupported shape raises.  What it binds: the sampled
 Fourier transform, the zero-extended and sign-flipped sampled transforms, the column sampling of LinearCRS, the moments of the variance
-estimator, the dropout of a seed, the packed form of a seed, and the layer norm and the RMS norm that keep the normalized rows of a seed.
+estimator, the dropout of a seed, the packed form of a seed, the layer norm and the RMS norm that keep the normalized rows of a seed, and the
+same two norms with ``residual + dropout(x)`` fused in front.
 """
 import ctypes
 import os
@@ -18,7 +19,8 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'sampled_dft_zext', 'sampled_dft_zext_seeded', 'sampled_signs', 'sampled_dct_signed', 'sampled_dft_signed', 'moments_workspace_bytes', 'row_moments', 'sum_squares',
            'DROPOUT_SWEEP', 'dropout_threshold', 'dropout_keep', 'dropout_apply', 'QUANT_BITS', 'QUANT_GROUP', 'QUANT_SWEEP', 'quant_bytes', 'quant_pack',
            'quant_unpack', 'quant_pack_host', 'quant_unpack_host', 'NORM_MAX_WIDTH', 'norm_plan', 'norm_state_bytes', 'norm_workspace_bytes', 'norm_state_host',
-           'norm_state_unpack_host', 'layer_norm_forward', 'layer_norm_backward', 'rms_norm_forward', 'rms_norm_backward']
+           'norm_state_unpack_host', 'layer_norm_forward', 'layer_norm_backward', 'rms_norm_forward', 'rms_norm_backward', 'add_layer_norm_forward', 'add_layer_norm_backward',
+           'add_rms_norm_forward', 'add_rms_norm_backward']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -73,6 +75,11 @@ _SIGNATURES = {
     # the un-centred rows (the RMS norm): inside revision 2 as well, recognised by its symbols
     'fewbit_hipx_rms_norm_forward': (_i32, [_i32, _vp, _sz, _sz, _vp, _dbl, _i32, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'fewbit_hipx_rms_norm_backward': (_i32, [_i32, _vp, _vp, _vp, _vp, _sz, _sz, _i32, _vp, _vp, _vp, _sz, _vp]),
+    # the sum of a seed in front of the norm (residual + dropout(x), then either norm): inside revision 2 as well, recognised by its symbols
+    'fewbit_hipx_add_layer_norm_forward': (_i32, [_i32, _vp, _vp, _sz, _sz, _vp, _vp, _dbl, _i32, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    'fewbit_hipx_add_layer_norm_backward': (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i32, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_add_rms_norm_forward': (_i32, [_i32, _vp, _vp, _sz, _sz, _vp, _dbl, _i32, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    'fewbit_hipx_add_rms_norm_backward': (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i32, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -673,3 +680,107 @@ def rms_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor,
     ``dgamma`` is not wanted, and then no workspace); ``workspace``: a uint8 tensor of ``norm_workspace_bytes(rows, width)`` bytes."""
     want_dx, want_dgamma = want
     return _norm_backward(False, gy, state, rstd, gamma, bits, (want_dx, want_dgamma), (dx, dgamma), workspace, stream)
+
+
+# ---- residual + dropout(x) fused in front of either norm (include/fewbit_hipx.h, "The sum of a seed in front of the norm") ------------------------------
+def _like(t: Optional[torch.Tensor], x: torch.Tensor, what: str) -> Optional[torch.Tensor]:
+    if t is not None and (t.dtype != x.dtype or t.shape != x.shape or not t.is_contiguous()):
+        raise FewbitHipError(f'{what} must be a contiguous tensor of the shape and dtype of {"x" if what in ("residual", "h") else "gy"}')
+    return t
+
+
+def _add_norm_forward(centred: bool, x, residual, gamma, beta, eps, p, bits, seed, keep, want_h, want_xhat, y, h, rstd, state, xhat, stream):
+    name = 'add_layer_norm_forward' if centred else 'add_rms_norm_forward'
+    rows, width = _norm_rows(x, 'x')
+    _like(residual, x, 'residual')
+    gp = _norm_vector(gamma, x, 'gamma')
+    pointers = (gp, _norm_vector(beta, x, 'beta')) if centred else (gp, )
+    threshold = dropout_threshold(p)
+    need = _norm_size(rows, width, bits, name) if keep else 0
+    value, word, others = _seed_arguments(seed) if keep or threshold else (0, None, ())
+    with _on(x.device):
+        y = _norm_out(y, (rows, width), x.dtype, x.device, 'y')
+        rstd = _norm_out(rstd, (rows, ), torch.float32, x.device, 'rstd')
+        if want_h or h is not None:
+            h = _norm_out(h, (rows, width), x.dtype, x.device, 'h')
+        if keep and state is None:
+            state = torch.empty(need, dtype=torch.uint8, device=x.device)
+        elif keep and (state.dtype != torch.uint8 or state.dim() != 1 or not state.is_contiguous()):
+            raise FewbitHipError('state must be a contiguous 1-D uint8 tensor')
+        elif not keep:
+            state = None
+        if want_xhat or xhat is not None:
+            xhat = _norm_out(xhat, (rows, width), torch.float32, x.device, 'xhat')
+        _same_device(x, residual, y, rstd, *others, *(t for t in (gamma, beta, h, state, xhat) if t is not None))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _check(getattr(lib(), f'fewbit_hipx_{name}')(DTYPES[x.dtype], x.data_ptr(), residual.data_ptr(), rows, width, *pointers, float(eps), bits, value, word,
+                                                     threshold, y.data_ptr(), ptr(h), rstd.data_ptr(), ptr(state), 0 if state is None else state.numel(), ptr(xhat),
+                                                     _stream(stream, x.device)))
+    return y, h, rstd, state, xhat
+
+
+def _add_norm_backward(centred: bool, gy, state, rstd, gamma, bits, seed, p, gh, want, outs, workspace, stream):
+    """``want`` and ``outs``: (dres, dbranch, dgamma, dbeta) for the layer norm and (dres, dbranch, dgamma) for the RMS norm"""
+    name = 'add_layer_norm_backward' if centred else 'add_rms_norm_backward'
+    rows, width = _norm_rows(gy, 'gy')
+    _like(gh, gy, 'gh')
+    gp = _norm_vector(gamma, gy, 'gamma')
+    threshold = dropout_threshold(p)
+    if want is None:
+        want = (True, threshold > 0, True, True)[:4 if centred else 3]
+    need = _norm_size(rows, width, bits, name)
+    if state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < need:
+        raise FewbitHipError(f'state must be a contiguous uint8 tensor of at least {need} bytes')
+    if rstd.dtype != torch.float32 or rstd.numel() != rows or not rstd.is_contiguous():
+        raise FewbitHipError(f'rstd must be a contiguous float32 tensor of {rows} elements')
+    value, word, others = _seed_arguments(seed) if threshold else (0, None, ())
+    with _on(gy.device):
+        shapes = (((rows, width), gy.dtype, 'dres'), ((rows, width), gy.dtype, 'dbranch'), ((width, ), torch.float32, 'dgamma'),
+                  ((width, ), torch.float32, 'dbeta'))[:4 if centred else 3]
+        outs = tuple(_norm_out(t, shape, dtype, gy.device, what) if wanted else None for t, wanted, (shape, dtype, what) in zip(outs, want, shapes))
+        if any(want[2:]) and workspace is None:
+            workspace = torch.empty(norm_workspace_bytes(rows, width), dtype=torch.uint8, device=gy.device)
+        _same_device(gy, state, rstd, *others, *(t for t in (gh, gamma, *outs, workspace) if t is not None))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _check(getattr(lib(), f'fewbit_hipx_{name}')(DTYPES[gy.dtype], gy.data_ptr(), ptr(gh), state.data_ptr(), rstd.data_ptr(), gp, rows, width, bits, value, word,
+                                                     threshold, *map(ptr, outs), ptr(workspace), 0 if workspace is None else workspace.numel(),
+                                                     _stream(stream, gy.device)))
+    return outs
+
+
+def add_layer_norm_forward(x: torch.Tensor, residual: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float, p: float = 0.0,
+                           bits: int = 4, seed=0, keep: bool = True, want_h: bool = False, want_xhat: bool = False, y: Optional[torch.Tensor] = None,
+                           h: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
+                           xhat: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """``layer_norm_forward(dropout_apply(x, seed, p, addend=residual), gamma, beta, eps, bits, seed, keep)`` in ONE launch, bit for bit ->
+    ``(y, h, rstd, state, xhat)``: ``h`` is the rounded sum ``residual + dropout(x)`` the rows of which are normalized, written only with ``want_h``
+    (or a buffer ``h``), else None -- it is then never in memory.  ONE ``seed`` (an int, or a device word) gives the mask and the rounding.
+    ``p``: the drop probability (``dropout_threshold``; below 1).  With a mask (threshold > 0) the width must be a multiple of 8: anything else
+    is refused -- compose the two calls; without one every width 1 .. 8192 is served.  No output may overlap an input."""
+    return _add_norm_forward(True, x, residual, gamma, beta, eps, p, bits, seed, keep, want_h, want_xhat, y, h, rstd, state, xhat, stream)
+
+
+def add_layer_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor], bits: int, seed=0, p: float = 0.0,
+                            gh: Optional[torch.Tensor] = None, want=None, dres: Optional[torch.Tensor] = None, dbranch: Optional[torch.Tensor] = None,
+                            dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                            stream: Optional[int] = None):
+    """The gradients of ``add_layer_norm_forward`` from its state -> ``(dres, dbranch, dgamma, dbeta)``: ``dres``, the residual's, is the plain
+    backward's fp32 ``dx`` plus ``gh`` (the gradient arriving at ``h``, or None) rounded ONCE; ``dbranch``, the input's, is
+    ``dropout_apply(dres, seed, p)``; ``dgamma`` / ``dbeta`` are ``layer_norm_backward``'s.  ``want``: which of the four (default: all; ``dbranch``
+    only with a mask -- without one it is ``dres``, and asking for it is refused).  Two launches, one when neither sum is wanted."""
+    return _add_norm_backward(True, gy, state, rstd, gamma, bits, seed, p, gh, want, (dres, dbranch, dgamma, dbeta), workspace, stream)
+
+
+def add_rms_norm_forward(x: torch.Tensor, residual: torch.Tensor, gamma: Optional[torch.Tensor], eps: float, p: float = 0.0, bits: int = 4, seed=0,
+                         keep: bool = True, want_h: bool = False, want_xhat: bool = False, y: Optional[torch.Tensor] = None, h: Optional[torch.Tensor] = None,
+                         rstd: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None, xhat: Optional[torch.Tensor] = None,
+                         stream: Optional[int] = None):
+    """``add_layer_norm_forward`` for the RMS norm (no ``beta``): ``rms_norm_forward`` of ``residual + dropout(x)`` in ONE launch, bit for bit"""
+    return _add_norm_forward(False, x, residual, gamma, None, eps, p, bits, seed, keep, want_h, want_xhat, y, h, rstd, state, xhat, stream)
+
+
+def add_rms_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor], bits: int, seed=0, p: float = 0.0,
+                          gh: Optional[torch.Tensor] = None, want=None, dres: Optional[torch.Tensor] = None, dbranch: Optional[torch.Tensor] = None,
+                          dgamma: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """``add_layer_norm_backward`` for the RMS norm -> ``(dres, dbranch, dgamma)``"""
+    return _add_norm_backward(False, gy, state, rstd, gamma, bits, seed, p, gh, want, (dres, dbranch, dgamma), workspace, stream)

@@ -10,6 +10,12 @@
 //     forward   rstd = 1 / sqrt(mean(x^2) + eps), x^ = x rstd, y = x^ gamma
 //     backward  dx = rstd (g^ - x^q mean(g^ x^q)), dgamma = sum_r gy x^q
 //
+// and both with residual + dropout(x) formed in front ("the sum of a seed in front of the norm"; DropoutAddLayerNorm, DropoutAddRMSNorm), again the same
+// kernels with the fusion switched at compile time:
+//
+//     forward   h = keep ? narrow(x scale + residual) : residual as the blocks are loaded (the mask of the call's seed), then the norm of the rows of h
+//     backward  dres = narrow(dx32 + gh), dbranch = keep ? narrow(dres scale) : +0 in place of dx; the sums as before
+//
 // What QuantizedLayerNorm and QuantizedRMSNorm (fewbit_amd/norm.py) keep: the state and one fp32 rstd per row instead of the input.  lo, step, inv,
 // code_of, decode and the poison rule are fewbit_quantdef.h's, the text fewbit_quant.hip evaluates.
 //
@@ -150,6 +156,58 @@ template <int DT> __device__ __forceinline__ void store_block(typename Elem<DT>:
 }
 __device__ __forceinline__ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---- the fusion: residual + dropout(x) in front of the norm, its gradients behind the norm's backward ("the sum of a seed in front of the norm",
+// include/fewbit_hipx.h).  The mask is fewbit_dropout.hip's (counter word 3 = 5, one Philox call per block of eight FLAT elements), which a lane's
+// block of a row is only where width % 8 == 0: block b of row r is then flat block r * (width / 8) + b, the number the rounding bits take too.
+// The kernels gain it as a compile-time switch -- a trailing pack of arguments that is empty (the plain kernels) or one record.
+constexpr uint32_t kMaskDomain = 5u, kOne = 65536u;         // thresholds are in units of 2^-16
+struct NoFusion {};
+struct ForwardFusion { const void *residual; void *h_out; uint32_t threshold; float scale; };       // h_out: NULL, or where h is written
+// (the backward's `dx` is dres; gh: NULL, or the gradient that arrives at h; dbranch: NULL, or -- with threshold > 0 -- the input's gradient)
+struct BackwardFusion { const void *gh; void *dbranch; Key key; const Key *device; uint32_t threshold; float scale; };
+__device__ __forceinline__ NoFusion the_fusion() { return {}; }
+template <class F> __device__ __forceinline__ const F &the_fusion(const F &f) { return f; }
+
+// the 16 mask bits of the eight elements of flat block q; threshold 0 keeps everything and draws nothing
+__device__ __forceinline__ void mask_words(uint64_t q, Key key, uint32_t threshold, uint32_t (&w)[4]) {
+    w[0] = w[1] = w[2] = w[3] = ~0u;
+    if (threshold != 0) sketch::philox4x32(static_cast<uint32_t>(q), static_cast<uint32_t>(q >> 32), 0u, kMaskDomain, key, w);
+}
+__device__ __forceinline__ bool kept(const uint32_t (&w)[4], int e, uint32_t threshold) { return ((w[e >> 1] >> (16 * (e & 1))) & 0xffffu) >= threshold; }
+
+// eight elements as they lie in memory; the missing ones are 0
+template <int DT> __device__ __forceinline__ void load_raw(const typename Elem<DT>::type *p, bool vec, int have, typename Elem<DT>::type (&raw)[kBlock]) {
+    using T = typename Elem<DT>::type;
+    if (vec && have == kBlock) {
+        load8<DT>(p, raw);
+    } else {
+#pragma unroll
+        for (int e = 0; e < kBlock; ++e) raw[e] = e < have ? p[e] : T{0};
+    }
+}
+template <int DT> __device__ __forceinline__ void store_raw(typename Elem<DT>::type *p, bool vec, int have, const typename Elem<DT>::type (&raw)[kBlock]) {
+    if (vec && have == kBlock) {
+        store8<DT>(p, raw);
+    } else {
+#pragma unroll
+        for (int e = 0; e < kBlock; ++e)
+            if (e < have) p[e] = raw[e];
+    }
+}
+// h = keep ? narrow(widen(x) scale + widen(res)) : res -- `one<DT, true>` of fewbit_dropout.hip: the product and the sum are fp32 values of their
+// own (an fp16 operand's conversion, the arithmetic and the rounding must not meet in one v_fma_mix*, which is one step off at the ties)
+template <int DT> __device__ __forceinline__ typename Elem<DT>::type dropped_sum(typename Elem<DT>::type x, typename Elem<DT>::type res, bool keep, float scale) {
+    float v = mul_rn(float_of_bits(widen<DT>(x)), scale);
+    if constexpr (DT == FEWBIT_F16) asm("" : "+v"(v));
+    v = add_rn(v, float_of_bits(widen<DT>(res)));
+    return keep ? narrow<DT>(v) : res;
+}
+// dbranch = keep ? narrow(widen(dres) scale) : +0 -- `one<DT, false>` of fewbit_dropout.hip
+template <int DT> __device__ __forceinline__ typename Elem<DT>::type dropped_gradient(typename Elem<DT>::type dres, bool keep, float scale) {
+    const float v = mul_rn(float_of_bits(widen<DT>(dres)), scale);
+    return keep ? narrow<DT>(v) : typename Elem<DT>::type{0};
+}
+
 // The two norms of this unit are ONE text each for forward and backward, with the kind as a compile-time switch:
 //     CENTRED (the layer norm)   two row sums per tile (the row, then the squares of the centred row), beta, dbeta
 //     otherwise (the RMS norm)   ONE row sum per tile (the squares of the row as loaded); beta is neither loaded nor added, and backward has no
@@ -161,12 +219,17 @@ __device__ __forceinline__ bool aligned16(const void *p) { return (reinterpret_c
 // count: the writes of iteration i + 2 follow the barrier of iteration i + 1, which every wave meets only after its reads of iteration i.
 constexpr bool kCentred = true, kUncentred = false;
 
-// BITS = 0: the plain forward that keeps nothing (state is not touched); an un-centred launch passes beta = NULL, which is never read
-template <int DT, int BITS, int LPR, int K, bool CENTRED>
+// BITS = 0: the plain forward that keeps nothing (state is not touched); an un-centred launch passes beta = NULL, which is never read.
+// FUSION: nothing (the plain kernel, whose arguments and instructions are what they were before the switch existed), or ONE ForwardFusion: the row
+// that is normalized is then h = residual + dropout(x), formed as the blocks are loaded and written to h_out where asked.
+template <int DT, int BITS, int LPR, int K, bool CENTRED, class... FUSION>
 __global__ __launch_bounds__(kThreads) void forward_kernel(const void *__restrict__ x_, size_t rows, uint32_t width, const void *__restrict__ gamma_,
                                                            const void *__restrict__ beta_, float eps, Key value, const Key *device, void *__restrict__ y_,
-                                                           float *__restrict__ rstd_out, uint8_t *__restrict__ state, float *__restrict__ xhat_out) {
+                                                           float *__restrict__ rstd_out, uint8_t *__restrict__ state, float *__restrict__ xhat_out,
+                                                           FUSION... fusion) {
     using T = typename Elem<DT>::type;
+    constexpr bool FUSED = sizeof...(FUSION) != 0;
+    [[maybe_unused]] const auto &f = the_fusion(fusion...);
     constexpr int kRowsPerTile = kThreads / LPR;
     constexpr uint32_t kLevels = BITS == 0 ? 1u : (1u << BITS) - 1u;
     __shared__ float slots[2][4];
@@ -193,7 +256,23 @@ __global__ __launch_bounds__(kThreads) void forward_kernel(const void *__restric
         for (int k = 0; k < K; ++k) {
             const uint32_t b = static_cast<uint32_t>(k) * LPR + l, i0 = b * kBlock;
             have[k] = !live || b >= blocks ? 0 : width - i0 < static_cast<uint32_t>(kBlock) ? static_cast<int>(width - i0) : kBlock;
-            load_block<DT>(xr + i0, vec_x, have[k], v[k]);
+            if constexpr (FUSED) {
+                const T *rr = static_cast<const T *>(f.residual) + r * width;
+                T *hr = static_cast<T *>(f.h_out) + r * width;
+                T xs[kBlock], rs[kBlock], hs[kBlock];
+                load_raw<DT>(xr + i0, vec_x, have[k], xs);
+                load_raw<DT>(rr + i0, aligned16(rr), have[k], rs);
+                uint32_t w[4];
+                mask_words(static_cast<uint64_t>(r) * blocks + b, key, f.threshold, w);
+#pragma unroll
+                for (int e = 0; e < kBlock; ++e) {
+                    hs[e] = dropped_sum<DT>(xs[e], rs[e], kept(w, e, f.threshold), f.scale);
+                    v[k][e] = float_of_bits(widen<DT>(hs[e]));                                      // the norm runs on the ROUNDED sum
+                }
+                if (f.h_out != nullptr) store_raw<DT>(hr + i0, aligned16(hr), have[k], hs);
+            } else {
+                load_block<DT>(xr + i0, vec_x, have[k], v[k]);
+            }
 #pragma unroll
             for (int e = 0; e < kBlock; ++e) s = add_rn(s, CENTRED ? v[k][e] : mul_rn(v[k][e], v[k][e]));  // (a missing element: +0 either way)
         }
@@ -288,11 +367,15 @@ __global__ __launch_bounds__(kThreads) void forward_kernel(const void *__restric
 // partials -- still fill the machine.
 // Un-centred: ONE row sum per tile (g^ x^q; its slots alternate as in the forward), only the gy x^q accumulators, and only that half of a
 // workgroup's partials is written (the layout stays [workgroup][2][columns], which the column sums read with the same stride).
-template <int DT, int BITS, int LPR, bool CENTRED>
+// FUSION: nothing (the plain kernel), or ONE BackwardFusion: what is stored is then dres = narrow(dx32 + gh) (to dx_) and dbranch = the dropout's
+// backward of dres, each only where its pointer is given.
+template <int DT, int BITS, int LPR, bool CENTRED, class... FUSION>
 __global__ __launch_bounds__(kBackwardThreads) void backward_kernel(const void *__restrict__ gy_, const uint8_t *__restrict__ state,
                                                                     const float *__restrict__ rstd_in, const void *__restrict__ gamma_, size_t rows, uint32_t width,
-                                                                    void *__restrict__ dx_, float *__restrict__ partials) {
+                                                                    void *__restrict__ dx_, float *__restrict__ partials, FUSION... fusion) {
     using T = typename Elem<DT>::type;
+    constexpr bool FUSED = sizeof...(FUSION) != 0;
+    [[maybe_unused]] const auto &f = the_fusion(fusion...);
     constexpr int kRowsPerTile = kBackwardThreads / LPR;
     constexpr uint32_t kLevels = (1u << BITS) - 1u;
     constexpr int kPadded = LPR * kBlock;
@@ -316,6 +399,11 @@ __global__ __launch_bounds__(kBackwardThreads) void backward_kernel(const void *
 #pragma unroll
     for (int e = 0; e < kBlock; ++e) acc_gamma[e] = acc_beta[e] = 0.0f;
     [[maybe_unused]] uint32_t iteration = 0;
+    [[maybe_unused]] Key key{};
+    if constexpr (FUSED) {
+        key = f.key;
+        if (f.device != nullptr) key = *f.device;
+    }
     for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const size_t r = tile * kRowsPerTile + sub;
         const bool live = r < rows;
@@ -358,12 +446,36 @@ __global__ __launch_bounds__(kBackwardThreads) void backward_kernel(const void *
             m2 = div_rn(row_sum<LPR>(s2, slots[iteration & 1]), count);
             ++iteration;
         }
-        if (dx != nullptr) {
+        bool wanted = dx != nullptr;
+        if constexpr (FUSED) wanted = wanted || f.dbranch != nullptr;
+        if (wanted) {
             const float rstd = live ? rstd_in[r] : 0.0f;
             float o[kBlock];
 #pragma unroll
             for (int e = 0; e < kBlock; ++e) o[e] = mul_rn(rstd, sub_rn(CENTRED ? sub_rn(gh[e], m1) : gh[e], mul_rn(xq[e], m2)));
-            store_block<DT>(dr + i0, aligned16(dr), have, o);
+            if constexpr (FUSED) {
+                if (f.gh != nullptr) {
+                    const T *ar = static_cast<const T *>(f.gh) + r * width;
+                    float arriving[kBlock];
+                    load_block<DT>(ar + i0, aligned16(ar), have, arriving);
+#pragma unroll
+                    for (int e = 0; e < kBlock; ++e) o[e] = add_rn(o[e], arriving[e]);
+                }
+                T ds[kBlock];
+#pragma unroll
+                for (int e = 0; e < kBlock; ++e) ds[e] = narrow<DT>(o[e]);                          // dres
+                if (dx != nullptr) store_raw<DT>(dr + i0, aligned16(dr), have, ds);
+                if (f.dbranch != nullptr) {
+                    T *br = static_cast<T *>(f.dbranch) + r * width;
+                    uint32_t w[4];
+                    mask_words(static_cast<uint64_t>(r) * blocks + b, key, f.threshold, w);
+#pragma unroll
+                    for (int e = 0; e < kBlock; ++e) ds[e] = dropped_gradient<DT>(ds[e], kept(w, e, f.threshold), f.scale);
+                    store_raw<DT>(br + i0, aligned16(br), have, ds);
+                }
+            } else {
+                store_block<DT>(dr + i0, aligned16(dr), have, o);
+            }
         }
     }
     if (partials == nullptr) return;                                                                // (the same for every lane of the grid)
@@ -429,73 +541,85 @@ __global__ __launch_bounds__(kBackwardThreads) void column_sums_kernel(const flo
 
 struct ForwardArgs {
     const void *x; size_t rows; uint32_t width; const void *gamma, *beta; float eps; Key key; const Key *device; void *y; float *rstd; uint8_t *state; float *xhat;
+    ForwardFusion add;                          // read by the fused units only
 };
 struct BackwardArgs {
     const void *gy; const uint8_t *state; const float *rstd; const void *gamma; size_t rows; uint32_t width; void *dx; float *partials;
+    BackwardFusion add;                         // read by the fused units only; dx is dres there
 };
 
-template <int DT, int BITS, int LPR, int K, bool CENTRED> void launch(unsigned grid, hipStream_t s, const ForwardArgs &a) {
-    hipLaunchKernelGGL((forward_kernel<DT, BITS, LPR, K, CENTRED>), dim3(grid), dim3(kThreads), 0, s, a.x, a.rows, a.width, a.gamma, a.beta, a.eps, a.key, a.device,
-                       a.y, a.rstd, a.state, a.xhat);
-}
-template <int DT, int BITS, bool CENTRED> void launch_plan(Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
-    if (p.lpr == 8) launch<DT, BITS, 8, 1, CENTRED>(grid, s, a);
-    else if (p.lpr == 16) launch<DT, BITS, 16, 1, CENTRED>(grid, s, a);
-    else if (p.lpr == 64) launch<DT, BITS, 64, 1, CENTRED>(grid, s, a);
-    else if (p.lpr == 128) launch<DT, BITS, 128, 1, CENTRED>(grid, s, a);
-    else if (p.k == 1) launch<DT, BITS, 256, 1, CENTRED>(grid, s, a);
-    else if (p.k == 2) launch<DT, BITS, 256, 2, CENTRED>(grid, s, a);
-    else launch<DT, BITS, 256, 4, CENTRED>(grid, s, a);
-}
-template <int DT, int BITS, int LPR, bool CENTRED> void launch_backward_lanes(unsigned grid, hipStream_t s, const BackwardArgs &a) {
-    if constexpr (BITS != 0)
-        hipLaunchKernelGGL((backward_kernel<DT, BITS, LPR, CENTRED>), dim3(grid), dim3(kBackwardThreads), 0, s, a.gy, a.state, a.rstd, a.gamma, a.rows, a.width, a.dx,
-                           a.partials);
-}
-template <int DT, int BITS, bool CENTRED> void launch_plan(Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
-    if (p.lpr == 8) launch_backward_lanes<DT, BITS, 8, CENTRED>(grid, s, a);
-    else if (p.lpr == 16) launch_backward_lanes<DT, BITS, 16, CENTRED>(grid, s, a);
-    else if (p.lpr == 64) launch_backward_lanes<DT, BITS, 64, CENTRED>(grid, s, a);
-    else if (p.lpr == 128) launch_backward_lanes<DT, BITS, 128, CENTRED>(grid, s, a);
-    else if (p.lpr == 256) launch_backward_lanes<DT, BITS, 256, CENTRED>(grid, s, a);
-    else if (p.lpr == 512) launch_backward_lanes<DT, BITS, 512, CENTRED>(grid, s, a);
-    else launch_backward_lanes<DT, BITS, 1024, CENTRED>(grid, s, a);
-}
-template <int DT, bool CENTRED, class Args> void launch_bits(int bits, Plan p, unsigned grid, hipStream_t s, const Args &a) {
-    if (bits == 0) launch_plan<DT, 0, CENTRED>(p, grid, s, a);
-    else if (bits == 2) launch_plan<DT, 2, CENTRED>(p, grid, s, a);
-    else if (bits == 4) launch_plan<DT, 4, CENTRED>(p, grid, s, a);
-    else launch_plan<DT, 8, CENTRED>(p, grid, s, a);
-}
-// one unit per dtype and kind, compiled in parallel and linked into one library: -DFEWBIT_NORM_TU=0 / 1 / 2 the layer norm (fp32 with the C entry
-// points of both norms and the column sums, fp16, bf16), 3 / 4 / 5 the RMS norm in the same order of dtypes
+// one unit per dtype, kind and fusion, compiled in parallel and linked into one library: -DFEWBIT_NORM_TU=0 / 1 / 2 the layer norm (fp32 with the C
+// entry points of every norm and the column sums, fp16, bf16), 3 / 4 / 5 the RMS norm in the same order of dtypes, 6 .. 11 the same six with
+// residual + dropout(x) in front (the kernels with a fusion record and nothing else)
 #ifndef FEWBIT_NORM_TU
 #define FEWBIT_NORM_TU 0
 #endif
 constexpr int kUnitDtype = FEWBIT_NORM_TU % 3 == 0 ? FEWBIT_F32 : FEWBIT_NORM_TU % 3 == 1 ? FEWBIT_F16 : FEWBIT_BF16;
-constexpr bool kUnitCentred = FEWBIT_NORM_TU < 3;
-template <int DT, bool CENTRED> FEWBIT_HIDDEN void launch_forward(int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a);
-template <int DT, bool CENTRED> FEWBIT_HIDDEN void launch_backward(int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a);
-template <> void launch_forward<kUnitDtype, kUnitCentred>(int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
-    launch_bits<kUnitDtype, kUnitCentred>(bits, p, grid, s, a);
+constexpr bool kUnitCentred = FEWBIT_NORM_TU % 6 < 3, kUnitFused = FEWBIT_NORM_TU >= 6;
+
+// (FUSED is part of every launcher's name: the units are linked into one library, where two instantiations of one name would be ONE function)
+template <int DT, int BITS, int LPR, int K, bool CENTRED, bool FUSED> void launch(unsigned grid, hipStream_t s, const ForwardArgs &a) {
+    if constexpr (FUSED)
+        hipLaunchKernelGGL((forward_kernel<DT, BITS, LPR, K, CENTRED, ForwardFusion>), dim3(grid), dim3(kThreads), 0, s, a.x, a.rows, a.width, a.gamma, a.beta, a.eps,
+                           a.key, a.device, a.y, a.rstd, a.state, a.xhat, a.add);
+    else
+        hipLaunchKernelGGL((forward_kernel<DT, BITS, LPR, K, CENTRED>), dim3(grid), dim3(kThreads), 0, s, a.x, a.rows, a.width, a.gamma, a.beta, a.eps, a.key, a.device,
+                           a.y, a.rstd, a.state, a.xhat);
 }
-template <> void launch_backward<kUnitDtype, kUnitCentred>(int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
-    launch_bits<kUnitDtype, kUnitCentred>(bits, p, grid, s, a);
+template <int DT, int BITS, bool CENTRED, bool FUSED> void launch_plan(Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
+    if (p.lpr == 8) launch<DT, BITS, 8, 1, CENTRED, FUSED>(grid, s, a);
+    else if (p.lpr == 16) launch<DT, BITS, 16, 1, CENTRED, FUSED>(grid, s, a);
+    else if (p.lpr == 64) launch<DT, BITS, 64, 1, CENTRED, FUSED>(grid, s, a);
+    else if (p.lpr == 128) launch<DT, BITS, 128, 1, CENTRED, FUSED>(grid, s, a);
+    else if (p.k == 1) launch<DT, BITS, 256, 1, CENTRED, FUSED>(grid, s, a);
+    else if (p.k == 2) launch<DT, BITS, 256, 2, CENTRED, FUSED>(grid, s, a);
+    else launch<DT, BITS, 256, 4, CENTRED, FUSED>(grid, s, a);
+}
+template <int DT, int BITS, int LPR, bool CENTRED, bool FUSED> void launch_backward_lanes(unsigned grid, hipStream_t s, const BackwardArgs &a) {
+    if constexpr (BITS != 0 && FUSED)
+        hipLaunchKernelGGL((backward_kernel<DT, BITS, LPR, CENTRED, BackwardFusion>), dim3(grid), dim3(kBackwardThreads), 0, s, a.gy, a.state, a.rstd, a.gamma, a.rows,
+                           a.width, a.dx, a.partials, a.add);
+    else if constexpr (BITS != 0)
+        hipLaunchKernelGGL((backward_kernel<DT, BITS, LPR, CENTRED>), dim3(grid), dim3(kBackwardThreads), 0, s, a.gy, a.state, a.rstd, a.gamma, a.rows, a.width, a.dx,
+                           a.partials);
+}
+template <int DT, int BITS, bool CENTRED, bool FUSED> void launch_plan(Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
+    if (p.lpr == 8) launch_backward_lanes<DT, BITS, 8, CENTRED, FUSED>(grid, s, a);
+    else if (p.lpr == 16) launch_backward_lanes<DT, BITS, 16, CENTRED, FUSED>(grid, s, a);
+    else if (p.lpr == 64) launch_backward_lanes<DT, BITS, 64, CENTRED, FUSED>(grid, s, a);
+    else if (p.lpr == 128) launch_backward_lanes<DT, BITS, 128, CENTRED, FUSED>(grid, s, a);
+    else if (p.lpr == 256) launch_backward_lanes<DT, BITS, 256, CENTRED, FUSED>(grid, s, a);
+    else if (p.lpr == 512) launch_backward_lanes<DT, BITS, 512, CENTRED, FUSED>(grid, s, a);
+    else launch_backward_lanes<DT, BITS, 1024, CENTRED, FUSED>(grid, s, a);
+}
+template <int DT, bool CENTRED, bool FUSED, class Args> void launch_bits(int bits, Plan p, unsigned grid, hipStream_t s, const Args &a) {
+    if (bits == 0) launch_plan<DT, 0, CENTRED, FUSED>(p, grid, s, a);
+    else if (bits == 2) launch_plan<DT, 2, CENTRED, FUSED>(p, grid, s, a);
+    else if (bits == 4) launch_plan<DT, 4, CENTRED, FUSED>(p, grid, s, a);
+    else launch_plan<DT, 8, CENTRED, FUSED>(p, grid, s, a);
+}
+template <int DT, bool CENTRED, bool FUSED> FEWBIT_HIDDEN void launch_forward(int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a);
+template <int DT, bool CENTRED, bool FUSED> FEWBIT_HIDDEN void launch_backward(int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a);
+template <> void launch_forward<kUnitDtype, kUnitCentred, kUnitFused>(int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
+    launch_bits<kUnitDtype, kUnitCentred, kUnitFused>(bits, p, grid, s, a);
+}
+template <> void launch_backward<kUnitDtype, kUnitCentred, kUnitFused>(int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
+    launch_bits<kUnitDtype, kUnitCentred, kUnitFused>(bits, p, grid, s, a);
 }
 
 #if FEWBIT_NORM_TU == 0
-template <bool CENTRED> void launch_dtype(int dtype, int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
+template <bool CENTRED, bool FUSED> void launch_dtype(int dtype, int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
     switch (dtype) {
-    case FEWBIT_F32: launch_forward<FEWBIT_F32, CENTRED>(bits, p, grid, s, a); break;
-    case FEWBIT_F16: launch_forward<FEWBIT_F16, CENTRED>(bits, p, grid, s, a); break;
-    default: launch_forward<FEWBIT_BF16, CENTRED>(bits, p, grid, s, a); break;
+    case FEWBIT_F32: launch_forward<FEWBIT_F32, CENTRED, FUSED>(bits, p, grid, s, a); break;
+    case FEWBIT_F16: launch_forward<FEWBIT_F16, CENTRED, FUSED>(bits, p, grid, s, a); break;
+    default: launch_forward<FEWBIT_BF16, CENTRED, FUSED>(bits, p, grid, s, a); break;
     }
 }
-template <bool CENTRED> void launch_dtype(int dtype, int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
+template <bool CENTRED, bool FUSED> void launch_dtype(int dtype, int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
     switch (dtype) {
-    case FEWBIT_F32: launch_backward<FEWBIT_F32, CENTRED>(bits, p, grid, s, a); break;
-    case FEWBIT_F16: launch_backward<FEWBIT_F16, CENTRED>(bits, p, grid, s, a); break;
-    default: launch_backward<FEWBIT_BF16, CENTRED>(bits, p, grid, s, a); break;
+    case FEWBIT_F32: launch_backward<FEWBIT_F32, CENTRED, FUSED>(bits, p, grid, s, a); break;
+    case FEWBIT_F16: launch_backward<FEWBIT_F16, CENTRED, FUSED>(bits, p, grid, s, a); break;
+    default: launch_backward<FEWBIT_BF16, CENTRED, FUSED>(bits, p, grid, s, a); break;
     }
 }
 
@@ -522,21 +646,40 @@ int check_host(const char *name, size_t rows, size_t width, int bits, const void
     return FEWBIT_OK;
 }
 
-// the forward entry point of either norm: the refusals, the plan, ONE launch (the RMS norm: beta = NULL)
+// what the fused entry points refuse on top, forward and backward: a threshold that drops everything or more, and a mask on rows whose blocks of
+// eight are not the flat tensor's
+int check_threshold(const char *name, uint32_t threshold, size_t width) {
+    if (threshold >= kOne) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: threshold = %u is outside 0 .. 65535", name, threshold);
+    if (threshold != 0 && width % kBlock != 0)
+        return fail(FEWBIT_ERR_UNSUPPORTED, "%s: a mask (threshold = %u) needs a width that is a multiple of 8, not %zu", name, threshold, width);
+    return FEWBIT_OK;
+}
+inline float scale_of(uint32_t threshold) { return static_cast<float>(65536.0 / static_cast<double>(kOne - threshold)); }     // (fewbit_dropout.hip's)
+
+// the forward entry point of either norm: the refusals, the plan, ONE launch (the RMS norm: beta = NULL); `add`: the fused call's residual, h_out and
+// threshold (its scale is filled in here), NULL for the plain one
 template <bool CENTRED>
 int forward_call(const char *name, int dtype, const void *x, size_t rows, size_t width, const void *gamma, const void *beta, double eps, int bits, uint64_t seed,
-                 const uint64_t *seed_device, void *y, float *rstd, uint8_t *state, size_t state_bytes, float *xhat_out, void *stream) {
+                 const uint64_t *seed_device, void *y, float *rstd, uint8_t *state, size_t state_bytes, float *xhat_out, void *stream,
+                 const ForwardFusion *add = nullptr) {
     const int shape = check_shape(name, dtype, rows, width);
     if (shape < 0) return shape;
+    if (add != nullptr) {
+        const int refused = check_threshold(name, add->threshold, width);
+        if (refused != FEWBIT_OK) return refused;
+    }
     if (state != nullptr && !known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: bits = %d is not 2, 4 or 8", name, bits);
     if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: eps = %g is not a finite number >= 0", name, eps);
     if (misaligned(seed_device, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the seed word in device memory must be 8-byte aligned", name);
     if (shape == 1) return FEWBIT_OK;
     if (x == nullptr || y == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (x or y)", name);
+    if (add != nullptr && add->residual == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (residual)", name);
     if (state != nullptr && rstd == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (rstd goes with the state)", name);
     const size_t size = size_of(dtype);
     if (misaligned(x, size) || misaligned(y, size) || misaligned(gamma, size) || misaligned(beta, size))
         return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: %s must be aligned to their element size", name, CENTRED ? "x, y, gamma and beta" : "x, y and gamma");
+    if (add != nullptr && (misaligned(add->residual, size) || misaligned(add->h_out, size)))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: residual and h_out must be aligned to their element size", name);
     if (misaligned(rstd, 4) || misaligned(xhat_out, 4)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: rstd and xhat_out must be 4-byte aligned", name);
     if (misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: state must be 8-byte aligned", name);
     if (state != nullptr) {
@@ -546,31 +689,48 @@ int forward_call(const char *name, int dtype, const void *x, size_t rows, size_t
     const Plan p = plan_of(width);
     const size_t tiles = tiles_of(rows, p, kThreads);
     const unsigned grid = static_cast<unsigned>(tiles < kMaxGridForward ? tiles : kMaxGridForward);
-    const ForwardArgs a{x, rows, static_cast<uint32_t>(width), gamma, beta, static_cast<float>(eps), sketch::key_of(seed), reinterpret_cast<const Key *>(seed_device),
-                        y, rstd, state, xhat_out};
-    launch_dtype<CENTRED>(dtype, state != nullptr ? bits : 0, p, grid, static_cast<hipStream_t>(stream), a);
+    ForwardArgs a{x, rows, static_cast<uint32_t>(width), gamma, beta, static_cast<float>(eps), sketch::key_of(seed), reinterpret_cast<const Key *>(seed_device),
+                  y, rstd, state, xhat_out, {}};
+    if (add != nullptr) {
+        a.add = ForwardFusion{add->residual, add->h_out, add->threshold, scale_of(add->threshold)};
+        launch_dtype<CENTRED, true>(dtype, state != nullptr ? bits : 0, p, grid, static_cast<hipStream_t>(stream), a);
+    } else {
+        launch_dtype<CENTRED, false>(dtype, state != nullptr ? bits : 0, p, grid, static_cast<hipStream_t>(stream), a);
+    }
     return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
 }
 
 // the backward entry point of either norm: the refusals, the plan, the launch of dx and the partials, then the column sums (the RMS norm: dbeta =
 // NULL, and the column sums are launched for dgamma alone)
+// `add`: the fused call's gh, dbranch, seed and threshold (dx is its dres; its scale is filled in here), NULL for the plain one
 template <bool CENTRED>
 int backward_call(const char *name, int dtype, const void *gy, const uint8_t *state, const float *rstd, const void *gamma, size_t rows, size_t width, int bits,
-                  void *dx, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream) {
+                  void *dx, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream, const BackwardFusion *add = nullptr) {
     const int shape = check_shape(name, dtype, rows, width);
     if (shape < 0) return shape;
+    if (add != nullptr) {
+        const int refused = check_threshold(name, add->threshold, width);
+        if (refused != FEWBIT_OK) return refused;
+        if (add->dbranch != nullptr && add->threshold == 0)
+            return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: with threshold = 0 dbranch is dres: pass dbranch = NULL", name);
+        if (misaligned(add->device, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the seed word in device memory must be 8-byte aligned", name);
+    }
+    void *const dbranch = add != nullptr ? add->dbranch : nullptr;
     if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: bits = %d is not 2, 4 or 8", name, bits);
     if (shape == 1) return FEWBIT_OK;
     if (gy == nullptr || state == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (gy or state)", name);
-    if (dx != nullptr && rstd == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (dx needs rstd)", name);
+    if ((dx != nullptr || dbranch != nullptr) && rstd == nullptr)
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (%s rstd)", name, add != nullptr ? "dres and dbranch need" : "dx needs");
     const size_t size = size_of(dtype);
     if (misaligned(gy, size) || misaligned(dx, size) || misaligned(gamma, size))
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: gy, dx and gamma must be aligned to their element size", name);
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: gy, %s and gamma must be aligned to their element size", name, add != nullptr ? "dres" : "dx");
+    if (add != nullptr && (misaligned(add->gh, size) || misaligned(dbranch, size)))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: gh and dbranch must be aligned to their element size", name);
     if (misaligned(rstd, 4) || misaligned(dgamma, 4) || misaligned(dbeta, 4))
         return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", name, CENTRED ? "rstd, dgamma and dbeta" : "rstd and dgamma");
     if (misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: state must be 8-byte aligned", name);
     const bool sums = dgamma != nullptr || dbeta != nullptr;
-    if (dx == nullptr && !sums) return FEWBIT_OK;
+    if (dx == nullptr && dbranch == nullptr && !sums) return FEWBIT_OK;
     const size_t need = workspace_of(rows, width);
     if (sums && (workspace == nullptr || misaligned(workspace, 16))) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the workspace must be 16-byte aligned", name);
     if (sums && workspace_bytes < need) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the workspace has %zu bytes, %zu are needed", name, workspace_bytes, need);
@@ -578,8 +738,14 @@ int backward_call(const char *name, int dtype, const void *gy, const uint8_t *st
     const size_t tiles = tiles_of(rows, p, kBackwardThreads);
     const unsigned grid = static_cast<unsigned>(tiles < kMaxGridBackward ? tiles : kMaxGridBackward);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const BackwardArgs a{gy, state, rstd, gamma, rows, static_cast<uint32_t>(width), dx, sums ? static_cast<float *>(workspace) : nullptr};
-    launch_dtype<CENTRED>(dtype, bits, p, grid, s, a);
+    BackwardArgs a{gy, state, rstd, gamma, rows, static_cast<uint32_t>(width), dx, sums ? static_cast<float *>(workspace) : nullptr, {}};
+    if (add != nullptr) {
+        a.add = *add;
+        a.add.scale = scale_of(add->threshold);
+        launch_dtype<CENTRED, true>(dtype, bits, p, grid, s, a);
+    } else {
+        launch_dtype<CENTRED, false>(dtype, bits, p, grid, s, a);
+    }
     if (hipGetLastError() != hipSuccess) return fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
     if (sums) {
         // a workgroup per 64 columns of each sum; the un-centred backward wrote only the first half of the partials, and only that is read
@@ -654,6 +820,40 @@ int fewbit_hipx_rms_norm_forward(int dtype, const void *x, size_t rows, size_t w
 int fewbit_hipx_rms_norm_backward(int dtype, const void *gy, const uint8_t *state, const float *rstd, const void *gamma, size_t rows, size_t width, int bits,
                                   void *dx, float *dgamma, void *workspace, size_t workspace_bytes, void *stream) {
     return backward_call<kUncentred>("rms_norm_backward", dtype, gy, state, rstd, gamma, rows, width, bits, dx, dgamma, nullptr, workspace, workspace_bytes, stream);
+}
+
+// residual + dropout(x) in front of either norm: the plain entry points' arguments plus the residual, the threshold and where h goes; backward gives
+// the gradient of the residual (dres, with the gradient arriving at h added) and of the input (dbranch) in place of dx
+int fewbit_hipx_add_layer_norm_forward(int dtype, const void *x, const void *residual, size_t rows, size_t width, const void *gamma, const void *beta, double eps,
+                                       int bits, uint64_t seed, const uint64_t *seed_device, uint32_t threshold, void *y, void *h_out, float *rstd, uint8_t *state,
+                                       size_t state_bytes, float *xhat_out, void *stream) {
+    const ForwardFusion add{residual, h_out, threshold, 0.0f};
+    return forward_call<kCentred>("add_layer_norm_forward", dtype, x, rows, width, gamma, beta, eps, bits, seed, seed_device, y, rstd, state, state_bytes, xhat_out,
+                                  stream, &add);
+}
+
+int fewbit_hipx_add_layer_norm_backward(int dtype, const void *gy, const void *gh, const uint8_t *state, const float *rstd, const void *gamma, size_t rows,
+                                        size_t width, int bits, uint64_t seed, const uint64_t *seed_device, uint32_t threshold, void *dres, void *dbranch,
+                                        float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream) {
+    const BackwardFusion add{gh, dbranch, sketch::key_of(seed), reinterpret_cast<const Key *>(seed_device), threshold, 0.0f};
+    return backward_call<kCentred>("add_layer_norm_backward", dtype, gy, state, rstd, gamma, rows, width, bits, dres, dgamma, dbeta, workspace, workspace_bytes, stream,
+                                   &add);
+}
+
+int fewbit_hipx_add_rms_norm_forward(int dtype, const void *x, const void *residual, size_t rows, size_t width, const void *gamma, double eps, int bits,
+                                     uint64_t seed, const uint64_t *seed_device, uint32_t threshold, void *y, void *h_out, float *rstd, uint8_t *state,
+                                     size_t state_bytes, float *xhat_out, void *stream) {
+    const ForwardFusion add{residual, h_out, threshold, 0.0f};
+    return forward_call<kUncentred>("add_rms_norm_forward", dtype, x, rows, width, gamma, nullptr, eps, bits, seed, seed_device, y, rstd, state, state_bytes, xhat_out,
+                                    stream, &add);
+}
+
+int fewbit_hipx_add_rms_norm_backward(int dtype, const void *gy, const void *gh, const uint8_t *state, const float *rstd, const void *gamma, size_t rows, size_t width,
+                                      int bits, uint64_t seed, const uint64_t *seed_device, uint32_t threshold, void *dres, void *dbranch, float *dgamma,
+                                      void *workspace, size_t workspace_bytes, void *stream) {
+    const BackwardFusion add{gh, dbranch, sketch::key_of(seed), reinterpret_cast<const Key *>(seed_device), threshold, 0.0f};
+    return backward_call<kUncentred>("add_rms_norm_backward", dtype, gy, state, rstd, gamma, rows, width, bits, dres, dgamma, nullptr, workspace, workspace_bytes,
+                                     stream, &add);
 }
 
 }  // extern "C"

@@ -34,6 +34,16 @@ above holds for it; the bias of ``dx`` is the same ``-rstd * g^_i * Var(x^q_i) /
 and of torch's own formulation: a NaN element makes its row NaN; an INFINITE element makes ``mean(x^2)`` infinite, so ``rstd`` is 0 and ``x^`` is
 NaN at that element and +-0 elsewhere -- the group that holds it is poisoned, ``dx`` of the row is NaN and ``dgamma`` is NaN in that group's
 columns.  A finite row whose fp32 sum of squares overflows (bf16 values near 1e20) gives ``rstd`` = 0 and ``y`` = +-0.
+
+``DropoutAddLayerNorm`` / ``DropoutAddRMSNorm`` (``dropout_add_layer_norm_quantized`` / ``dropout_add_rms_norm_quantized``) are a sublayer's whole
+ending, ``y = norm(residual + dropout(input))``, as ONE node: one seed per call (the mask and the rounding are two Philox domains of it), one
+launch forward and two backward where ``dropout_add`` followed by the quantized norm takes two and three.  Kept: the state, ``rstd``, gamma and,
+on ``ctx``, the seed and ``p`` -- no mask, and not the sum ``h``, which post-norm (``prenorm=False``) is never in memory.  With ``prenorm=True``
+the call returns ``(y, h)`` and the gradient arriving at ``h`` is added inside the backward kernel.  The values are the composition's, bit for bit
+(include/fewbit_hipx.h, "The sum of a seed in front of the norm").  The kernel path is that of the plain norms plus a residual of the input's
+shape, dtype and device plus, with a mask, a width that is a multiple of 8; everything else IS the composition of ``dropout_add`` and the
+quantized norm (two seeds).  Grad mode off or nothing that requires grad: the plain fused forward, which still drops while ``training and p > 0``.
+Every rule above -- autocast, checkpoint, capture, non-finite values, ``once_differentiable`` -- holds for it.
 """
 import math
 from typing import Optional, Sequence, Union
@@ -44,8 +54,10 @@ from torch.autograd.function import once_differentiable
 
 from . import cabi_x, linear
 from .cabi import DTYPES
+from .dropout import _check_p, dropout_add
 
-__all__ = ('layer_norm_quantized', 'QuantizedLayerNorm', 'rms_norm_quantized', 'QuantizedRMSNorm')
+__all__ = ('layer_norm_quantized', 'QuantizedLayerNorm', 'rms_norm_quantized', 'QuantizedRMSNorm', 'dropout_add_layer_norm_quantized', 'DropoutAddLayerNorm',
+           'dropout_add_rms_norm_quantized', 'DropoutAddRMSNorm')
 
 # Everything below takes the kind as ``centred``: True for the layer norm, False for the RMS norm (the un-centred statistic, backward without the mean
 # term, no beta: ``bias`` is None throughout).
@@ -326,3 +338,170 @@ class QuantizedRMSNorm(_QuantizedNorm, torch.nn.RMSNorm):
         new = cls(shape, eps, affine, device='meta', bits=bits, generator=generator)
         new.weight = module.weight
         return new.train(module.training)
+
+
+# ---- residual + dropout(input) fused in front of either norm (module docstring, last paragraph) ------------------------------------------------
+def _add_kernel_forward(centred: bool, flat, residual, weight, bias, eps, p: float, bits: int = 4, seed=0, keep: bool = True, want_h: bool = False):
+    """(y, h, rstd, state, None) of the fused entry point of the kind"""
+    gamma = _as(weight, flat.dtype)
+    if centred:
+        return cabi_x.add_layer_norm_forward(flat, residual, gamma, _as(bias, flat.dtype), eps, p, bits, seed, keep, want_h)
+    return cabi_x.add_rms_norm_forward(flat, residual, gamma, eps, p, bits, seed, keep, want_h)
+
+
+class _DropoutAddNormQuantized(torch.autograd.Function):
+    """``norm(residual + dropout(input))`` on the fused kernels, both kinds (``centred``).  Kept: the state, ``rstd`` and gamma; on ``ctx`` the ONE
+    seed of the call and ``p``.  With ``prenorm`` the outputs are ``(y, h)`` and backward takes the gradient arriving at ``h``."""
+
+    @staticmethod
+    def forward(ctx, input, residual, weight, bias, centred: bool, normalized_shape, eps: float, bits: int, p: float, prenorm: bool, generator):
+        width = math.prod(normalized_shape)
+        flat = input.detach().reshape(-1, width).contiguous()
+        ctx.centred, ctx.bits, ctx.p, ctx.prenorm, ctx.input_dtype = centred, bits, p, prenorm, input.dtype
+        ctx.has_weight, ctx.normalized_shape, ctx.bias_dtype = weight is not None, tuple(normalized_shape), None if bias is None else bias.dtype
+        ctx.autocast = linear._autocast_seen(input.device.type)
+        ctx.set_materialize_grads(False)
+        ctx.seed = linear._sketch_seed(generator, flat.device)
+        y, h, rstd, state, _ = _add_kernel_forward(centred, flat, residual.detach().reshape(-1, width).contiguous(), weight, bias, eps, p, bits, ctx.seed,
+                                                   want_h=prenorm)
+        ctx.save_for_backward(state, rstd, *((weight, ) if ctx.has_weight else ()))
+        return (y.view(input.shape), h.view(input.shape)) if prenorm else y.view(input.shape)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output, grad_h=None):
+        with linear._autocast_as(ctx.autocast):
+            saved = ctx.saved_tensors
+            state, rstd = saved[:2]
+            weight = saved[-1] if ctx.has_weight else None
+            rows, width = rstd.numel(), math.prod(ctx.normalized_shape)
+            shape = (grad_output if grad_output is not None else grad_h).shape
+            if grad_output is None:                     # (only h reached the loss: the norm's own terms are those of a zero gradient)
+                grad_output = torch.zeros_like(grad_h)
+            gy = linear._dense_rows(grad_output).reshape(rows, width)
+            gy = gy if gy.dtype in DTYPES else gy.float()
+            gh = None if grad_h is None else linear._dense_rows(grad_h.to(gy.dtype)).reshape(rows, width)
+            want_input, want_residual, want_weight, want_bias = ctx.needs_input_grad[:4]
+            mask = cabi_x.dropout_threshold(ctx.p) > 0
+            # without a mask the two gradients are the same values: ONE tensor is written and returned for both
+            want = (want_residual or (want_input and not mask), want_input and mask, want_weight) + ((want_bias, ) if ctx.centred else ())
+            call = cabi_x.add_layer_norm_backward if ctx.centred else cabi_x.add_rms_norm_backward
+            dres, dbranch, dgamma, *rest = call(gy, state, rstd, _as(weight, gy.dtype), ctx.bits, ctx.seed, ctx.p, gh, want)
+            shaped = lambda t: t.to(ctx.input_dtype).view(shape)
+            grad_residual = shaped(dres) if want_residual else None
+            grad_input = (shaped(dbranch) if mask else shaped(dres)) if want_input else None
+            grad_weight = dgamma.to(weight.dtype).view(weight.shape) if want_weight else None
+            grad_bias = rest[0].to(ctx.bias_dtype).view(ctx.normalized_shape) if ctx.centred and want_bias else None
+            return grad_input, grad_residual, grad_weight, grad_bias, None, None, None, None, None, None, None
+
+
+def _dropout_add_norm_quantized(centred: bool, input, residual, normalized_shape, weight, bias, eps, p, training, bits, prenorm, generator):
+    """the functional front of both fused kinds: the refusals, the composition off the kernel path, the plain fused forward when nothing is kept, the
+    node otherwise"""
+    if bits not in cabi_x.QUANT_BITS:
+        raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+    _check_p(p)
+    if tuple(residual.shape) != tuple(input.shape):
+        raise ValueError(f'residual should have the shape of input, {tuple(input.shape)}, but got {tuple(residual.shape)}.')
+    normalized_shape = (normalized_shape, ) if isinstance(normalized_shape, int) else tuple(normalized_shape)
+    p = float(p) if training else 0.0
+    fits = bool(normalized_shape) and tuple(input.shape[input.dim() - len(normalized_shape):]) == normalized_shape
+    flat = input.detach().reshape(-1, math.prod(normalized_shape)) if fits else None
+    if (not fits or not _kernel_applies(flat, weight, bias) or residual.dtype != input.dtype or residual.device != input.device
+            or (cabi_x.dropout_threshold(p) > 0 and flat.shape[1] % 8 != 0)):
+        h = dropout_add(input, residual, p, training, generator)
+        y = _norm_quantized(centred, h, normalized_shape, weight, bias, eps, bits, generator)
+        return (y, h) if prenorm else y
+    if not centred:
+        eps = float(torch.finfo(input.dtype).eps if eps is None else eps)
+    if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (input, residual, weight, bias)):
+        seed = linear._sketch_seed(generator, flat.device) if cabi_x.dropout_threshold(p) > 0 else 0
+        y, h, *_ = _add_kernel_forward(centred, flat.contiguous(), residual.detach().reshape(flat.shape).contiguous(), weight, bias, eps, p, seed=seed, keep=False,
+                                       want_h=prenorm)
+        return (y.view(input.shape), h.view(input.shape)) if prenorm else y.view(input.shape)
+    return _DropoutAddNormQuantized.apply(input, residual, weight, bias, centred, normalized_shape, float(eps), int(bits), p, bool(prenorm), generator)
+
+
+def dropout_add_layer_norm_quantized(input: torch.Tensor, residual: torch.Tensor, normalized_shape: Union[int, Sequence[int]],
+                                     weight: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, eps: float = 1e-5, p: float = 0.0,
+                                     training: bool = True, bits: int = 4, prenorm: bool = False, generator: Optional[torch.Generator] = None):
+    """``layer_norm_quantized(dropout_add(input, residual, p, training), normalized_shape, weight, bias, eps, bits)`` as ONE node with ONE seed: one
+    launch forward, two backward; what is kept is the quantized norm's (the state, ``rstd``, gamma) plus the seed -- no mask and not the sum.
+    Returns ``y``, or ``(y, h)`` with ``prenorm=True``, where ``h = residual + dropout(input)`` is the residual stream that goes on; the gradient
+    arriving at ``h`` is added inside the backward kernel.  The values are those of the composition bit for bit, and off the kernel path (host
+    tensors, a residual of another dtype, a mask at a width that is no multiple of 8, ...) the call IS that composition.  ``generator``, grad
+    mode off, ``torch.autocast``, ``torch.utils.checkpoint`` and capture: the rules of :func:`layer_norm_quantized` (module docstring)."""
+    return _dropout_add_norm_quantized(True, input, residual, normalized_shape, weight, bias, eps, p, training, bits, prenorm, generator)
+
+
+def dropout_add_rms_norm_quantized(input: torch.Tensor, residual: torch.Tensor, normalized_shape: Union[int, Sequence[int]],
+                                   weight: Optional[torch.Tensor] = None, eps: Optional[float] = None, p: float = 0.0, training: bool = True, bits: int = 4,
+                                   prenorm: bool = False, generator: Optional[torch.Generator] = None):
+    """:func:`dropout_add_layer_norm_quantized` for the RMS norm: ``rms_norm_quantized(dropout_add(input, residual, p, training), ...)`` as one node
+    with one seed (pre-norm models: ``prenorm=True`` returns ``(y, h)``)."""
+    return _dropout_add_norm_quantized(False, input, residual, normalized_shape, weight, None, eps, p, training, bits, prenorm, generator)
+
+
+class _DropoutAddNorm:
+    """What the two fused modules put in front of their quantized norm: ``p``, ``prenorm`` and a ``forward`` of two tensors."""
+
+    def _configure(self, p: float, prenorm: bool):
+        _check_p(p)
+        self.p, self.prenorm = float(p), bool(prenorm)
+        return self
+
+    def forward(self, input: torch.Tensor, residual: torch.Tensor):
+        bias = self.bias if self._centred else None
+        if not self.training and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, residual, self.weight, bias)):
+            # the eval rule of the quantized norms: the dropout is off and the gradients are torch's exact ones on residual + input
+            h = residual + input
+            y = _torch_norm(self._centred, h, self.normalized_shape, self.weight, bias, self.eps)
+            return (y, h) if self.prenorm else y
+        return _dropout_add_norm_quantized(self._centred, input, residual, self.normalized_shape, self.weight, bias, self.eps, self.p, self.training, self.bits,
+                                           self.prenorm, self.generator)
+
+    def extra_repr(self) -> str:
+        return f'{super().extra_repr()}, p={self.p}, prenorm={self.prenorm}'
+
+
+class DropoutAddLayerNorm(_DropoutAddNorm, QuantizedLayerNorm):
+    r"""``LayerNorm(residual + dropout(input))``, a post-norm sublayer's ending (``prenorm=True``: ``(y, h)`` with the sum that goes on), as one node
+    on one launch forward and two backward (:func:`dropout_add_layer_norm_quantized`).  A :class:`QuantizedLayerNorm` whose ``forward`` takes
+    ``(input, residual)``; parameters after the norm's: ``p`` (drop probability, default 0), ``prenorm``, ``bits``, ``generator``.  ``m.eval()``
+    switches the dropout off; gradients asked for in eval mode are torch's exact ones on ``residual + input``.
+
+        >>> m = fewbit.DropoutAddLayerNorm(768, eps=1e-12, p=0.1)
+        >>> hidden = m(dense(hidden), residual)                       # LayerNorm(dropout(dense(x)) + residual)
+    """
+
+    def __init__(self, normalized_shape, eps: float = 1e-5, elementwise_affine: bool = True, bias: bool = True, device=None, dtype=None, p: float = 0.0,
+                 prenorm: bool = False, bits: int = 4, generator: Optional[torch.Generator] = None) -> None:
+        super().__init__(normalized_shape, eps, elementwise_affine, bias, device, dtype, bits, generator)
+        self._configure(p, prenorm)
+
+    @classmethod
+    def from_layer_norm(cls, module: torch.nn.LayerNorm, p: float = 0.0, prenorm: bool = False, bits: int = 4,
+                        generator: Optional[torch.Generator] = None) -> 'DropoutAddLayerNorm':
+        """A ``DropoutAddLayerNorm`` that SHARES the parameters of ``module``"""
+        return super().from_layer_norm(module, bits, generator)._configure(p, prenorm)
+
+
+class DropoutAddRMSNorm(_DropoutAddNorm, QuantizedRMSNorm):
+    r"""``RMSNorm(residual + dropout(input))`` as one node (:func:`dropout_add_rms_norm_quantized`); with ``prenorm=True``, the pre-norm block of the
+    Llama / Mistral / Qwen / T5 family, ``forward`` returns ``(y, h)`` and ``h`` goes on as the residual stream.  A :class:`QuantizedRMSNorm` whose
+    ``forward`` takes ``(input, residual)``; parameters after the norm's: ``p`` (default 0), ``prenorm``, ``bits``, ``generator``.
+
+        >>> m = fewbit.DropoutAddRMSNorm(4096, eps=1e-6, prenorm=True)
+        >>> normed, stream = m(attention_output, stream)
+    """
+
+    def __init__(self, normalized_shape, eps: Optional[float] = None, elementwise_affine: bool = True, device=None, dtype=None, p: float = 0.0,
+                 prenorm: bool = False, bits: int = 4, generator: Optional[torch.Generator] = None) -> None:
+        super().__init__(normalized_shape, eps, elementwise_affine, device, dtype, bits, generator)
+        self._configure(p, prenorm)
+
+    @classmethod
+    def from_rms_norm(cls, module: torch.nn.Module, p: float = 0.0, prenorm: bool = False, bits: int = 4,
+                      generator: Optional[torch.Generator] = None) -> 'DropoutAddRMSNorm':
+        """A ``DropoutAddRMSNorm`` that SHARES the weight of ``module`` (what :meth:`QuantizedRMSNorm.from_rms_norm` accepts)"""
+        return super().from_rms_norm(module, bits, generator)._configure(p, prenorm)

@@ -40,7 +40,9 @@ extern "C" {
  * So were the normalized rows of a seed (fewbit_hipx_norm_state_bytes, _norm_workspace, _norm_state_host, _norm_state_unpack_host,
  * _layer_norm_forward, _layer_norm_backward): inside revision 2, recognised by the presence of the symbols.
  * So were the un-centred rows, the RMS norm of the same state (fewbit_hipx_rms_norm_forward, _rms_norm_backward): inside revision 2, recognised by
- * the presence of the symbols. */
+ * the presence of the symbols.
+ * So was the sum of a seed in front of the norm (fewbit_hipx_add_layer_norm_forward, _add_layer_norm_backward, _add_rms_norm_forward,
+ * _add_rms_norm_backward): inside revision 2, recognised by the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -405,6 +407,41 @@ int fewbit_hipx_rms_norm_forward(int dtype, const void *x, size_t rows, size_t w
                                  const uint64_t *seed_device, void *y, float *rstd, uint8_t *state, size_t state_bytes, float *xhat_out, void *stream);
 int fewbit_hipx_rms_norm_backward(int dtype, const void *gy, const uint8_t *state, const float *rstd, const void *gamma, size_t rows, size_t width,
                                   int bits, void *dx, float *dgamma, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The sum of a seed in front of the norm: a sublayer's ending, y = norm(residual + dropout(x)), as ONE launch forward and TWO backward (what
+ * DropoutAddLayerNorm and DropoutAddRMSNorm run).  ONE seed feeds the mask (counter word 3 = 5) and the rounding bits (counter word 3 = 7).
+ * Everything is the existing arithmetic in the existing order, so every output is bit for bit what fewbit_hipx_dropout followed by the plain
+ * entry point of the norm gives:
+ *     T = threshold (0 .. 65535, in units of 2^-16: fewbit_hipx_dropout_threshold), scale = float32(65536 / (65536 - T))
+ *     keep(i) = the mask of the seed at flat index i = r * width + c
+ *   forward, per element, fp32:
+ *     h       = keep ? round_to_dtype(float(x) * scale + float(residual)) : residual (its bits)        T = 0: every element is kept, nothing is drawn
+ *     the norm of the rows of h AS ROUNDED: y, rstd, state and xhat_out are those of the plain forward on h with the same seed
+ *     h_out   NULL, or rows x width of `dtype` that receive h (post-norm: nobody else reads the sum, so it never exists in memory)
+ *   backward, per element, fp32:
+ *     dx32    = what the plain backward rounds to dx
+ *     dres    = round_to_dtype(dx32 + float(gh))          gh: NULL, or the gradient arriving at h (pre-norm: h goes on as the residual stream)
+ *     dbranch = keep ? round_to_dtype(float(dres) * scale) : +0                                        fewbit_hipx_dropout of dres, no addend
+ *     dres is the gradient of the residual, dbranch that of x.  With T = 0 they are the same values: dbranch must be NULL then.
+ *     dgamma, dbeta: those of the plain backward (the same partial sums, the same second launch).
+ *   dres, dbranch, dgamma and dbeta may each be NULL: that output is skipped and nothing of it is written.
+ * The mask is drawn on blocks of eight FLAT elements and a lane holds eight elements of a ROW: with T > 0 the width must be a multiple of 8
+ * (anything else: FEWBIT_ERR_UNSUPPORTED; compose the two calls).  With T = 0 every width 1 .. 8192 is served.
+ * No output may overlap an input or another output.  The plan, the alignment rules and the refusals are those of the plain pair; refused on top:
+ * threshold >= 65536, a NULL residual, residual / h_out / gh / dres / dbranch not aligned to their element, dbranch with T = 0. */
+int fewbit_hipx_add_layer_norm_forward(int dtype, const void *x, const void *residual, size_t rows, size_t width, const void *gamma, const void *beta, double eps,
+                                       int bits, uint64_t seed, const uint64_t *seed_device, uint32_t threshold, void *y, void *h_out, float *rstd, uint8_t *state,
+                                       size_t state_bytes, float *xhat_out, void *stream);
+int fewbit_hipx_add_layer_norm_backward(int dtype, const void *gy, const void *gh, const uint8_t *state, const float *rstd, const void *gamma, size_t rows,
+                                        size_t width, int bits, uint64_t seed, const uint64_t *seed_device, uint32_t threshold, void *dres, void *dbranch,
+                                        float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream);
+int fewbit_hipx_add_rms_norm_forward(int dtype, const void *x, const void *residual, size_t rows, size_t width, const void *gamma, double eps, int bits,
+                                     uint64_t seed, const uint64_t *seed_device, uint32_t threshold, void *y, void *h_out, float *rstd, uint8_t *state,
+                                     size_t state_bytes, float *xhat_out, void *stream);
+int fewbit_hipx_add_rms_norm_backward(int dtype, const void *gy, const void *gh, const uint8_t *state, const float *rstd, const void *gamma, size_t rows, size_t width,
+                                      int bits, uint64_t seed, const uint64_t *seed_device, uint32_t threshold, void *dres, void *dbranch, float *dgamma,
+                                      void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

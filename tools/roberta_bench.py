@@ -18,6 +18,11 @@ Two routes to the same kernels:
                             input in a few bits instead of the input) in the fewbit / op variants and in every non-vanilla row of --table; the
                             line gains a `layer_norm` entry: the vanilla model with ONLY the layer norms swapped, its peak memory and step time
                             against the vanilla model.
+  --layer-norm fused        as `fewbit`, and the two sublayer endings of every encoder layer, `RobertaSelfOutput` and `RobertaOutput`
+                            (`LayerNorm(dropout(dense(x)) + input)`), call `fewbit.DropoutAddLayerNorm` instead: dropout, residual add and norm as one
+                            node on one launch forward and two backward (the dropout of these endings is then the seeded one whatever --dropout
+                            says).  The embeddings' norm has no residual and stays the `fewbit.QuantizedLayerNorm` of `--layer-norm fewbit`.  The
+                            line gains the same `layer_norm` entry.
   --sign-flips              `fewbit_amd.linear.use_sign_flips(True)`: with --table --matmul dct / dft the randomized layers negate a random half of
                             the rows in front of the transform (S = sqrt(N / p) R T D; the signs of the call's seed, evaluated in pass A)
 Prints one JSON line.
@@ -108,6 +113,23 @@ def swap_layer_norm(model, bits):
     return n[0]
 
 
+def fuse_sublayer_endings(model, bits):
+    """`RobertaSelfOutput.forward` and `RobertaOutput.forward` -> `DropoutAddLayerNorm(dense(x), input)`, sharing the parameters of their LayerNorm"""
+    import types
+    from transformers.models.roberta.modeling_roberta import RobertaOutput, RobertaSelfOutput
+
+    def forward(self, hidden_states, input_tensor):
+        return self.LayerNorm(self.dense(hidden_states), input_tensor)
+
+    n = 0
+    for mod in model.modules():
+        if isinstance(mod, (RobertaSelfOutput, RobertaOutput)):
+            mod.LayerNorm = fewbit.DropoutAddLayerNorm.from_layer_norm(mod.LayerNorm, p=mod.dropout.p, bits=bits)
+            mod.forward = types.MethodType(forward, mod)
+            n += 1
+    return n
+
+
 def swap_linear(model, ratio, sketch_dtype=None, matmul='gaussian'):
     """Every nn.Linear of the encoder -> fewbit.RandomizedLinear(proj_dim_ratio=ratio) sharing its parameters (the
     README's `convert_linear` recipe); the classification head stays exact."""
@@ -172,8 +194,9 @@ def main():
                     help='draw S with torch.randn / randint and multiply with torch.matmul (what round 3 measured) instead of the '
                          'gfx950 sketch kernels (fewbit_amd/csrc/fewbit_sketch.hip)')
     ap.add_argument('--dropout', default='torch', choices=('torch', 'fewbit'), help="'fewbit': swap every nn.Dropout for fewbit.Dropout (module docstring)")
-    ap.add_argument('--layer-norm', default='torch', choices=('torch', 'fewbit'),
-                    help="'fewbit': swap every nn.LayerNorm for fewbit.QuantizedLayerNorm (module docstring)")
+    ap.add_argument('--layer-norm', default='torch', choices=('torch', 'fewbit', 'fused'),
+                    help="'fewbit': swap every nn.LayerNorm for fewbit.QuantizedLayerNorm; 'fused': also run the sublayer endings on "
+                         "fewbit.DropoutAddLayerNorm (module docstring)")
     ap.add_argument('--layer-norm-bits', type=int, default=4, choices=(2, 4, 8), help='bits per kept element of the swapped layer norms')
     ap.add_argument('--sign-flips', action='store_true', help="random row signs in front of the 'dct' / 'dft' sketches (fewbit_amd.linear.use_sign_flips)")
     args = ap.parse_args()
@@ -187,6 +210,13 @@ def main():
     if args.torch_sketch:
         fewbit_amd.linear.use_native_sketch(False)
     fewbit_amd.linear.use_sign_flips(args.sign_flips)
+    quantized_norms = args.layer_norm in ('fewbit', 'fused')
+
+    def swap_norms(model):
+        """-> the number of norms swapped, the fused sublayer endings among them"""
+        fused = fuse_sublayer_endings(model, args.layer_norm_bits) if args.layer_norm == 'fused' else 0
+        return fused + swap_layer_norm(model, args.layer_norm_bits)
+
     if args.table:
         rows = []
         for i, (gelu, linear) in enumerate(((False, False), (True, False), (False, True), (True, True))):
@@ -196,7 +226,7 @@ def main():
             ng = swap_gelu(model, args.bits) if gelu else 0
             nl = swap_linear(model, args.linear_ratio, torch.bfloat16 if args.sketch_bf16 else None, args.matmul) if linear else 0
             nd = swap_dropout(model) if args.dropout == 'fewbit' and (gelu or linear) else 0
-            nn_ = swap_layer_norm(model, args.layer_norm_bits) if args.layer_norm == 'fewbit' and (gelu or linear) else 0
+            nn_ = swap_norms(model) if quantized_norms and (gelu or linear) else 0
             r = run(model, ids, labels, args.steps)
             rows.append({'gelu': f'{args.bits}-bit' if gelu else 'vanilla', 'linear': 'randomized' if linear else 'vanilla',
                          'gelu_modules_swapped': ng, 'linear_modules_swapped': nl, 'dropout_modules_swapped': nd, 'layer_norm_modules_swapped': nn_,
@@ -219,7 +249,7 @@ def main():
     names = ('vanilla', 'fewbit') + (('op', ) if args.route in ('op', 'both') or args.only == 'op' else ())
     if args.dropout == 'fewbit' and not args.only:
         names += ('dropout', )
-    if args.layer_norm == 'fewbit' and not args.only:
+    if quantized_norms and not args.only:
         names += ('layer_norm', )
     for name in names:
         if args.only and name != args.only:
@@ -232,10 +262,10 @@ def main():
         else:
             swapped = swap_gelu(model, args.bits) if name == 'fewbit' else 0
         dropouts = swap_dropout(model) if args.dropout == 'fewbit' and name not in ('vanilla', 'layer_norm') else 0
-        norms = swap_layer_norm(model, args.layer_norm_bits) if args.layer_norm == 'fewbit' and name not in ('vanilla', 'dropout') else 0
+        norms = swap_norms(model) if quantized_norms and name not in ('vanilla', 'dropout') else 0
         res[name] = run(model, ids, labels, args.steps)
         res[name]['gelu_modules_swapped'], res[name]['dropout_modules_swapped'] = swapped, dropouts
-        if args.layer_norm == 'fewbit':
+        if quantized_norms:
             res[name]['layer_norm_modules_swapped'] = norms
         del model
         torch.cuda.empty_cache()
@@ -269,7 +299,11 @@ def main():
                                   'step_time_ratio': res['dropout']['ms_per_step'] / res['vanilla']['ms_per_step']}
     if 'layer_norm' in res:   # the layer norms alone
         out['layer_norm'] = res['layer_norm']
-        out['layer_norm_summary'] = {'route': f'fewbit.QuantizedLayerNorm(bits={args.layer_norm_bits}) in place of every nn.LayerNorm, nothing else swapped',
+        route = f'fewbit.QuantizedLayerNorm(bits={args.layer_norm_bits}) in place of every nn.LayerNorm, nothing else swapped'
+        if args.layer_norm == 'fused':
+            route = (f'fewbit.DropoutAddLayerNorm(bits={args.layer_norm_bits}) as the ending of RobertaSelfOutput and RobertaOutput, '
+                     'fewbit.QuantizedLayerNorm for the embeddings, nothing else swapped')
+        out['layer_norm_summary'] = {'route': route,
                                      'peak_saving_bytes': res['vanilla']['peak_bytes'] - res['layer_norm']['peak_bytes'],
                                      'saved_tensor_saving_bytes': res['vanilla']['saved_for_backward_bytes'] - res['layer_norm']['saved_for_backward_bytes'],
                                      'step_time_ratio': res['layer_norm']['ms_per_step'] / res['vanilla']['ms_per_step']}
