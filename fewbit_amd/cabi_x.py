@@ -3,7 +3,7 @@ of ``libfewbit_hip.so`` was frozen at version 5 (``cabi.SYMBOLS`` stays that lis
 torch's current stream on the tensors' device, no fallback -- a missing library or an unsupported shape raises.  What it binds: the sampled
 Fourier transform, the zero-extended and sign-flipped sampled transforms, the column sampling of LinearCRS, the moments of the variance
 estimator, the dropout of a seed, the packed form of a seed, the layer norm and the RMS norm that keep the normalized rows of a seed, and the
-same two norms with ``residual + dropout(x)`` fused in front.
+same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed.
 """
 import ctypes
 import os
@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from .cabi import DTYPES, FewbitHipError, _buffers, _matrix, _on, _planes_dtype, _row_numbers, _same_device, _sampled_call, _seed_arguments, _span, _stream
+from .cabi import CONTINUOUS, DTYPES, FewbitHipError, _buffers, _matrix, _on, _planes_dtype, _row_numbers, _same_device, _sampled_call, _seed_arguments, _span, _stream
 
 __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft', 'sampled_dft_seeded', 'sampled_dft_workspace_bytes', 'crs_columns',
            'crs_count', 'crs_workspace_bytes', 'crs_gather', 'crs_scatter', 'sampled_rows_ceil', 'sampled_dct_zext', 'sampled_dct_zext_seeded',
@@ -20,7 +20,7 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'DROPOUT_SWEEP', 'dropout_threshold', 'dropout_keep', 'dropout_apply', 'QUANT_BITS', 'QUANT_GROUP', 'QUANT_SWEEP', 'quant_bytes', 'quant_pack',
            'quant_unpack', 'quant_pack_host', 'quant_unpack_host', 'NORM_MAX_WIDTH', 'norm_plan', 'norm_state_bytes', 'norm_workspace_bytes', 'norm_state_host',
            'norm_state_unpack_host', 'layer_norm_forward', 'layer_norm_backward', 'rms_norm_forward', 'rms_norm_backward', 'add_layer_norm_forward', 'add_layer_norm_backward',
-           'add_rms_norm_forward', 'add_rms_norm_backward']
+           'add_rms_norm_forward', 'add_rms_norm_backward', 'GLU_ACTIVATIONS', 'glu_state_bytes', 'glu_state_host', 'glu_forward', 'glu_backward']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -80,6 +80,11 @@ _SIGNATURES = {
     'fewbit_hipx_add_layer_norm_backward': (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i32, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'fewbit_hipx_add_rms_norm_forward': (_i32, [_i32, _vp, _vp, _sz, _sz, _vp, _dbl, _i32, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'fewbit_hipx_add_rms_norm_backward': (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i32, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # the gate and the up of a seed (the product of a gated MLP): inside revision 2 as well, recognised by its symbols
+    'fewbit_hipx_glu_state_bytes': (_sz, [_sz, _i32]),
+    'fewbit_hipx_glu_state_host': (_i32, [_vp, _vp, _sz, _i32, _u64, _vp]),
+    'fewbit_hipx_glu_forward': (_i32, [_i32, _i32, _vp, _sz, _vp, _sz, _sz, _sz, _i32, _u64, _vp, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_glu_backward': (_i32, [_i32, _i32, _vp, _vp, _sz, _sz, _i32, _vp, _sz, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -784,3 +789,120 @@ def add_rms_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Ten
                           dgamma: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None):
     """``add_layer_norm_backward`` for the RMS norm -> ``(dres, dbranch, dgamma)``"""
     return _add_norm_backward(False, gy, state, rstd, gamma, bits, seed, p, gh, want, (dres, dbranch, dgamma), workspace, stream)
+
+
+# ---- the product of a gated MLP that keeps its gate and its up in 2, 4 or 8 bits (fewbit_amd/csrc/fewbit_glu.hip) -------------------------------------
+GLU_ACTIVATIONS = ('silu', 'gelu')              # gelu: the erf form
+
+
+def glu_state_bytes(n: int, bits: int) -> int:
+    """Bytes of the state of ``n`` elements of gate and of up at ``bits`` bits: two parts of ``quant_bytes(n, bits)`` rounded up to a multiple of 8
+    each; 0 for ``bits`` other than 2, 4, 8 and for ``n`` outside 1 .. 2^36.  Evaluated on the host; no GPU needed."""
+    if n < 0:
+        return 0
+    return lib().fewbit_hipx_glu_state_bytes(n, bits)
+
+
+def _glu_size(n: int, bits: int, name: str) -> int:
+    if bits not in QUANT_BITS:
+        raise FewbitHipError(f'{name}: bits must be 2, 4 or 8 (got {bits})')
+    need = glu_state_bytes(n, bits)
+    if n != 0 and need == 0:
+        raise FewbitHipError(f'{name}: no state for {n} elements (1 .. 2^36 are supported)')
+    return need
+
+
+def _glu_activation(activation: str) -> int:
+    if activation not in GLU_ACTIVATIONS:
+        raise FewbitHipError(f"activation must be 'silu' or 'gelu' (got {activation!r})")
+    return CONTINUOUS.index(activation)             # enum fewbit_function
+
+
+def glu_state_host(gate: torch.Tensor, up: torch.Tensor, seed: int, bits: int) -> torch.Tensor:
+    """The state ``glu_forward`` writes for ``seed``, evaluated on the host: ``gate`` and ``up`` (one shape; taken as contiguous fp32, so pass the
+    values of a 16-bit tensor as ``.float()``) -> a host uint8 tensor of ``glu_state_bytes`` bytes.  The definition is include/fewbit_hipx.h's
+    ("the gate and the up of a seed"): the first half is ``quant_pack_host(gate, seed, bits)`` filled up with zero bytes, the second half the
+    same of ``up`` with the next rounding domain; ``quant_unpack_host`` decodes either half.  No GPU needed."""
+    if gate.shape != up.shape:
+        raise FewbitHipError(f'gate and up must have one shape (got {tuple(gate.shape)} and {tuple(up.shape)})')
+    g = gate.detach().to(device='cpu', dtype=torch.float32).contiguous()
+    u = up.detach().to(device='cpu', dtype=torch.float32).contiguous()
+    out = torch.empty(_glu_size(g.numel(), bits, 'glu_state_host'), dtype=torch.uint8)
+    _check(lib().fewbit_hipx_glu_state_host(g.data_ptr(), u.data_ptr(), g.numel(), bits, seed & 0xffffffffffffffff, out.data_ptr()))
+    return out
+
+
+def _glu_rows(t: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    """(rows, width, row stride) of a 2-D GPU tensor with unit stride along its width and rows at least a width apart"""
+    if t.device.type != 'cuda':
+        raise FewbitHipError(f'{what} must live on the GPU (got {t.device})')
+    if t.dtype not in DTYPES:
+        raise FewbitHipError(f'unsupported dtype {t.dtype}')
+    if t.dim() != 2:
+        raise FewbitHipError(f'{what} must be 2-D (got {t.dim()} dimensions)')
+    rows, width = t.shape
+    ld = t.stride(0) if rows > 1 else width
+    if (width > 1 and t.stride(1) != 1) or ld < width:
+        raise FewbitHipError(f'{what} must have unit stride along its width and rows at least a width apart (strides {tuple(t.stride())})')
+    return rows, width, ld
+
+
+def glu_forward(gate: torch.Tensor, up: torch.Tensor, activation: str = 'silu', bits: int = 4, seed=0, keep: bool = True, y: Optional[torch.Tensor] = None,
+                state: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """``act(gate) * up`` in ONE launch -> ``(y, state)``.  ``gate`` and ``up``: 2-D fp32 / fp16 / bf16 GPU tensors of one shape and dtype with
+    unit stride along the width and any row stride (the halves of ``x.chunk(2, -1)`` as they are); ``y``: contiguous, their dtype, ``act`` in
+    fp32 and ONE product rounded once; ``state``: both inputs in ``bits`` bits rounded with ``seed`` (a uint8 tensor of ``glu_state_bytes`` bytes;
+    ``glu_state_host`` gives the same bytes).  ``keep=False``: the plain forward, ``state`` is None and ``y`` has the same bytes.  ``seed``: an int,
+    or a one-element int64 tensor on the device of ``gate`` that is read when the kernel runs (``cabi.next_sketch_seed``).  ``y``, ``state``:
+    buffers to write into."""
+    rows, width, ld_gate = _glu_rows(gate, 'gate')
+    if up.shape != gate.shape or up.dtype != gate.dtype:
+        raise FewbitHipError('up must have the shape and dtype of gate')
+    ld_up = _glu_rows(up, 'up')[2]
+    act = _glu_activation(activation)
+    need = _glu_size(rows * width, bits, 'glu_forward') if keep else 0
+    value, word, others = _seed_arguments(seed) if keep else (0, None, ())
+    with _on(gate.device):
+        y = _norm_out(y, (rows, width), gate.dtype, gate.device, 'y')
+        if keep and state is None:
+            state = torch.empty(need, dtype=torch.uint8, device=gate.device)
+        elif keep and (state.dtype != torch.uint8 or state.dim() != 1 or not state.is_contiguous()):
+            raise FewbitHipError('state must be a contiguous 1-D uint8 tensor')
+        elif not keep:
+            state = None
+        _same_device(gate, up, y, *others, *(() if state is None else (state, )))
+        _check(lib().fewbit_hipx_glu_forward(DTYPES[gate.dtype], act, gate.data_ptr(), ld_gate, up.data_ptr(), ld_up, rows, width, bits, value, word, y.data_ptr(),
+                                             None if state is None else state.data_ptr(), 0 if state is None else state.numel(), _stream(stream, gate.device)))
+    return y, state
+
+
+def glu_backward(gy: torch.Tensor, state: torch.Tensor, activation: str, bits: int, want=(True, True), d_gate: Optional[torch.Tensor] = None,
+                 d_up: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """The gradients of ``act(gate) * up`` from its state (``glu_forward``) and ``gy`` (contiguous, 2-D, fp32 / fp16 / bf16) in ONE launch ->
+    ``(d_gate, d_up)`` in the dtype of ``gy``: ``d_up = gy * act(g^)``, ``d_gate = (gy * u^) * act'(g^)`` on the decodes, fp32, rounded once.  Where
+    ``want`` is False the output is None and nothing of it is computed or written.  ``d_gate``, ``d_up``: buffers to write into, 2-D of the
+    shape of ``gy`` with unit stride along the width and any row stride -- the halves of ONE ``rows x 2 width`` tensor, for a packed
+    ``[gate | up]`` input; the gap of a row stride is not written."""
+    if gy.dim() != 2 or not gy.is_contiguous():
+        raise FewbitHipError('gy must be a contiguous 2-D tensor')
+    rows, width, _ = _glu_rows(gy, 'gy')
+    act = _glu_activation(activation)
+    need = _glu_size(rows * width, bits, 'glu_backward')
+    if state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < need:
+        raise FewbitHipError(f'state must be a contiguous uint8 tensor of at least {need} bytes')
+    with _on(gy.device):
+        outs, lds = [], []
+        for t, wanted, what in ((d_gate, want[0], 'd_gate'), (d_up, want[1], 'd_up')):
+            if not wanted:
+                t = None
+            elif t is None:
+                t = torch.empty((rows, width), dtype=gy.dtype, device=gy.device)
+            elif t.dtype != gy.dtype or tuple(t.shape) != (rows, width):
+                raise FewbitHipError(f'{what} must be a {rows} x {width} tensor of {gy.dtype}')
+            outs.append(t)
+            lds.append(0 if t is None else _glu_rows(t, what)[2])
+        _same_device(gy, state, *(t for t in outs if t is not None))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _check(lib().fewbit_hipx_glu_backward(DTYPES[gy.dtype], act, gy.data_ptr(), state.data_ptr(), rows, width, bits, ptr(outs[0]), lds[0], ptr(outs[1]), lds[1],
+                                              _stream(stream, gy.device)))
+    return tuple(outs)

@@ -72,8 +72,10 @@ __host__ __device__ __forceinline__ bool non_finite(uint32_t bits) { return (bit
 __host__ __device__ __forceinline__ float uniform_of(const uint32_t (&w)[4], int e) {
     return static_cast<float>((w[e >> 1] >> (16 * (e & 1))) & 0xffffu) * (1.0f / 65536.0f);             // (both exact)
 }
-__host__ __device__ __forceinline__ void block_words(uint64_t q, Key key, uint32_t (&w)[4]) {
-    sketch::philox4x32(static_cast<uint32_t>(q), static_cast<uint32_t>(q >> 32), 0u, kRoundDomain, key, w);
+// (DOMAIN: counter word 3, a compile-time constant as it always was; kUpDomain is the second tensor of a call that packs two, fewbit_glu.hip)
+constexpr uint32_t kUpDomain = 8u;
+template <uint32_t DOMAIN = kRoundDomain> __host__ __device__ __forceinline__ void block_words(uint64_t q, Key key, uint32_t (&w)[4]) {
+    sketch::philox4x32(static_cast<uint32_t>(q), static_cast<uint32_t>(q >> 32), 0u, DOMAIN, key, w);
 }
 
 struct Params { float lo, step, inv; bool poisoned; };
@@ -109,6 +111,7 @@ __host__ __device__ __forceinline__ float decode(uint32_t code, float lo, float 
 // ---- the host evaluation, one group or one element at a time: what the four *_host entry points loop over -----------------------------------
 // the `count` (1 .. kGroup) values of a group whose first block is block `first_block` of the seed's stream -> its 8 parameter bytes (lo, step,
 // little-endian) and its bits * ceil(count / 8) code bytes (the missing elements of the last word are 0)
+template <uint32_t DOMAIN = kRoundDomain>
 inline void pack_group_host(const float *x, size_t count, uint64_t first_block, Key key, int bits, uint8_t *params, uint8_t *codes) {
     const uint32_t levels = (1u << bits) - 1u;
     int32_t kmin = INT32_MAX, kmax = INT32_MIN;
@@ -126,7 +129,7 @@ inline void pack_group_host(const float *x, size_t count, uint64_t first_block, 
         for (int c = 0; c < 4; ++c) params[4 * h + c] = static_cast<uint8_t>(par[h] >> (8 * c));
     for (size_t j0 = 0; j0 < count; j0 += kBlock) {
         uint32_t w[4];
-        block_words(first_block + j0 / kBlock, key, w);
+        block_words<DOMAIN>(first_block + j0 / kBlock, key, w);
         uint64_t word = 0;
         for (int e = 0; e < kBlock && j0 + e < count; ++e) word |= static_cast<uint64_t>(code_of(x[j0 + e], p, uniform_of(w, e), levels)) << (bits * e);
         for (int c = 0; c < bits; ++c) codes[static_cast<size_t>(bits) * (j0 / kBlock) + c] = static_cast<uint8_t>(word >> (8 * c));

@@ -42,7 +42,9 @@ extern "C" {
  * So were the un-centred rows, the RMS norm of the same state (fewbit_hipx_rms_norm_forward, _rms_norm_backward): inside revision 2, recognised by
  * the presence of the symbols.
  * So was the sum of a seed in front of the norm (fewbit_hipx_add_layer_norm_forward, _add_layer_norm_backward, _add_rms_norm_forward,
- * _add_rms_norm_backward): inside revision 2, recognised by the presence of the symbols. */
+ * _add_rms_norm_backward): inside revision 2, recognised by the presence of the symbols.
+ * So were the gate and the up of a seed, the product of a gated MLP (fewbit_hipx_glu_state_bytes, _glu_state_host, _glu_forward, _glu_backward):
+ * inside revision 2, recognised by the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -442,6 +444,71 @@ int fewbit_hipx_add_rms_norm_forward(int dtype, const void *x, const void *resid
 int fewbit_hipx_add_rms_norm_backward(int dtype, const void *gy, const void *gh, const uint8_t *state, const float *rstd, const void *gamma, size_t rows, size_t width,
                                       int bits, uint64_t seed, const uint64_t *seed_device, uint32_t threshold, void *dres, void *dbranch, float *dgamma,
                                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The product of a gated MLP, y = act(gate) * up (down(act(gate(x)) * up(x)) of the Llama / Mistral / Qwen / Gemma / T5-v1.1 blocks), that keeps
+ * BOTH inputs in 2, 4 or 8 bits per element for backward instead of gate, act(gate) and up (what QuantizedGLU keeps): ONE launch forward, ONE
+ * backward.  The state is a pure function of (gate, up, bits, seed), evaluated alike by the host function and the kernel.
+ *
+ * The gate and the up of a seed.  gate and up are logical rows x width matrices of one dtype (F32 / F16 / BF16) with unit stride along the width
+ * and row strides ld_gate, ld_up >= width in elements (gate and up may be the two halves of one rows x 2 width matrix: ld = 2 width).  Elements are
+ * taken by logical flat index i = r * width + c, n = rows * width; each is widened exactly to fp32.
+ *   Forward, per element:
+ *     y[i]    = round_to_dtype(act(g) * u)       act evaluated in fp32, then ONE fp32 product, rounded once; y is contiguous (rows x width).
+ *               (torch's F.silu(gate) * up rounds act(gate) to the dtype first: a 16-bit y may differ from it in its last bit.)
+ *     act     = FEWBIT_SILU: g * sigmoid(g), or FEWBIT_GELU: g * Phi(g), the erf form.  The functors of the activation kernels
+ *               (fewbit_amd/csrc/fewbit_device.h): the precise class for fp32 I/O, the fast class for 16-bit I/O.  The tanh form of gelu is not done.
+ *               One exception: gelu with 16-bit I/O.  Both classes hold gelu to an error relative to |g|, which below g = -2 is not relative to
+ *               gelu(g) (the fast class keeps Phi(-|g|) to 4.5e-8 absolute, the precise class cancels in 1 + erf), and here the value is multiplied
+ *               by u and rounded to half an ulp of the PRODUCT.  There g < -1/2 is evaluated as g * 0.5 * erfc(-g / sqrt 2) with the rounding error
+ *               of the argument fed back (fewbit_glu.hip, gelu_relative): a few fp32 ulps of gelu(g) on the whole line.
+ *   The state, fewbit_hipx_glu_state_bytes(n, k) = 2 P bytes with P = fewbit_hipx_quant_bytes(n, k) rounded up to a multiple of 8:
+ *     bytes [0, P): the gate part, byte for byte fewbit_hipx_quant_pack_host(gate as a contiguous tensor, n, k, seed) -- flat groups of 64 (they
+ *               may straddle rows), counter word 3 = 7 -- then zero bytes up to P;
+ *     bytes [P, 2 P): the up part, the same definition of up with counter word 3 = 8 (the next free domain: the two roundings of one seed are
+ *               independent), then zero bytes.
+ *     fewbit_hipx_quant_unpack_host decodes either part (pass state or state + P).
+ *   Backward, fp32, every step ONE operation, never contracted.  With g^ = decode(gate part), u^ = decode(up part):
+ *     d_up    = round_to_dtype(gy * act(g^))
+ *     d_gate  = round_to_dtype((gy * u^) * act'(g^))
+ *     silu:   s = sigmoid(g^), act' = s * (1 + g^ * (1 - s))
+ *     gelu:   act' = Phi(g^) + g^ * phi(g^),  Phi = 0.5 * (1 + erf(g^ / sqrt 2)),  phi = exp(-g^ g^ / 2) / sqrt(2 pi)
+ *     act and sigmoid are the functors of the forward; gy is contiguous; d_gate and d_up have row strides ld_dgate, ld_dup >= width.
+ *   E[g^] = g and E[u^] = u, and the two are independent, but act is not linear: E[act(g^)] - act(g) = act''(g) Var(g^) / 2 + ..., so BOTH gradients
+ *     carry a bias of second order in the step (d_up through act, d_gate through act'), as dx of the norms does.  Exactly:
+ *     E[d_up] = gy * ((1 - f) act(v0) + f act(v1)) and E[d_gate] = gy * u * ((1 - f) act'(v0) + f act'(v1)), v0 and v1 = v0 + step the two neighbouring
+ *     levels of g and f = (g - v0) / step (up to the 2^-16 granularity of U).
+ *   NaN and infinity: y is always the exact forward, whatever the groups hold.  A group of EITHER input that holds a NaN or an infinity is poisoned
+ *     by the rule of the packed form and decodes to NaN; BOTH gradients are then NaN on the 64 elements of that group, whichever input it was.
+ *     Other groups are untouched to the bit.
+ *
+ * fewbit_hipx_glu_state_bytes: the size above; 0 for bits other than 2, 4, 8 and for n outside 1 .. 2^36.
+ * fewbit_hipx_glu_state_host: the state of given fp32 values (n each, contiguous) at HOST pointers; no device is touched.
+ * fewbit_hipx_glu_forward: ONE launch on `stream` (fewbit_amd/csrc/fewbit_glu.hip).
+ *   gate, up, y  of `dtype`, aligned to the element.  A lane takes a block of 8 flat elements of both inputs by 16-byte accesses where
+ *                width % 8 == 0, every row stride times the element size is a multiple of 16 and gate, up and y are 16-byte aligned; element by
+ *                element with (r, c) from the flat index otherwise: the same bytes either way.  No address between `width` and a row stride is
+ *                touched, none beyond the last row.  y may not overlap gate or up.
+ *   seed, seed_device   as in fewbit_hipx_quant_pack: seed_device != NULL is an 8-byte aligned DEVICE word read when the kernel runs (`seed` is
+ *                ignored), so a launch recorded in a hipGraph rounds afresh on every replay
+ *   state, state_bytes   8-byte aligned, at least fewbit_hipx_glu_state_bytes(n, bits) bytes; nothing beyond that many is written.  state == NULL:
+ *                the plain forward that keeps nothing (bits and the seed are ignored); y is the same bytes
+ * fewbit_hipx_glu_backward: ONE launch on `stream`.
+ *   gy           rows x width of `dtype`, contiguous; state: the buffer of a forward of the same rows, width and bits
+ *   d_gate, d_up of `dtype`; either may be NULL: that output is skipped and nothing of it is written (both NULL: no launch).  The 16-byte path
+ *                needs width % 8 == 0 and gy and every output present 16-byte aligned with such a row stride.  The gap of a row stride is not written.
+ * No LDS, no workspace, no atomics, no read-back: the same arguments give the same bits.  The plan is that of the packed form of a seed: lanes take
+ * blocks of 8 elements (of both inputs: two Philox calls, two code words), 8 neighbouring lanes hold a group of each and reduce both minima, maxima
+ * and poison flags by DPP lane moves, 256 lanes to a workgroup, at most 2048 workgroups, beyond which each lane sweeps on by the width of the grid.
+ * Refused before anything is launched (FEWBIT_ERR_INVALID_ARGUMENT): an unknown dtype, an activation other than FEWBIT_SILU and FEWBIT_GELU, bits
+ * other than 2, 4, 8 (with a state), width = 0, rows * width beyond 2^36, a row stride below the width, a null or misaligned pointer, state_bytes
+ * below the size, a misaligned seed word.  rows = 0: FEWBIT_OK, no launch. */
+size_t fewbit_hipx_glu_state_bytes(size_t n, int bits);
+int fewbit_hipx_glu_state_host(const float *gate_host, const float *up_host, size_t n, int bits, uint64_t seed, uint8_t *out_host);
+int fewbit_hipx_glu_forward(int dtype, int act, const void *gate, size_t ld_gate, const void *up, size_t ld_up, size_t rows, size_t width, int bits, uint64_t seed,
+                            const uint64_t *seed_device, void *y, uint8_t *state, size_t state_bytes, void *stream);
+int fewbit_hipx_glu_backward(int dtype, int act, const void *gy, const uint8_t *state, size_t rows, size_t width, int bits, void *d_gate, size_t ld_dgate, void *d_up,
+                             size_t ld_dup, void *stream);
 
 #ifdef __cplusplus
 }
