@@ -84,7 +84,7 @@ from .linear import LinearCRS, LinearGRP, QuantizedLinear, RandomizedLinear  # n
 from .dropout import Dropout, dropout, dropout_add  # noqa: E402,F401  (fewbit_amd.dropout is the function from here on; the module: sys.modules['fewbit_amd.dropout'])
 from .norm import (DropoutAddLayerNorm, DropoutAddRMSNorm, QuantizedLayerNorm, QuantizedRMSNorm, dropout_add_layer_norm_quantized,  # noqa: E402,F401
                    dropout_add_rms_norm_quantized, layer_norm_quantized, rms_norm_quantized)
-from .glu import QuantizedGatedMLP, QuantizedGLU, glu_quantized  # noqa: E402,F401
+from .glu import QuantizedGatedMLP, QuantizedGLU, gated_mlp_quantized, glu_quantized  # noqa: E402,F401
 from .util import map_module, memory_usage_hooks  # noqa: E402,F401
 
 __version__ = '0.2.0'

@@ -3,7 +3,7 @@ of ``libfewbit_hip.so`` was frozen at version 5 (``cabi.SYMBOLS`` stays that lis
 torch's current stream on the tensors' device, no fallback -- a missing library or an unsupported shape raises.  What it binds: the sampled
 Fourier transform, the zero-extended and sign-flipped sampled transforms, the column sampling of LinearCRS, the moments of the variance
 estimator, the dropout of a seed, the packed form of a seed, the layer norm and the RMS norm that keep the normalized rows of a seed, and the
-same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed.
+same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed, with the backward that also rebuilds that product from the state.
 """
 import ctypes
 import os
@@ -20,7 +20,8 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'DROPOUT_SWEEP', 'dropout_threshold', 'dropout_keep', 'dropout_apply', 'QUANT_BITS', 'QUANT_GROUP', 'QUANT_SWEEP', 'quant_bytes', 'quant_pack',
            'quant_unpack', 'quant_pack_host', 'quant_unpack_host', 'NORM_MAX_WIDTH', 'norm_plan', 'norm_state_bytes', 'norm_workspace_bytes', 'norm_state_host',
            'norm_state_unpack_host', 'layer_norm_forward', 'layer_norm_backward', 'rms_norm_forward', 'rms_norm_backward', 'add_layer_norm_forward', 'add_layer_norm_backward',
-           'add_rms_norm_forward', 'add_rms_norm_backward', 'GLU_ACTIVATIONS', 'glu_state_bytes', 'glu_state_host', 'glu_forward', 'glu_backward']
+           'add_rms_norm_forward', 'add_rms_norm_backward', 'GLU_ACTIVATIONS', 'glu_state_bytes', 'glu_state_host', 'glu_forward', 'glu_backward',
+           'glu_backward_product']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -85,6 +86,8 @@ _SIGNATURES = {
     'fewbit_hipx_glu_state_host': (_i32, [_vp, _vp, _sz, _i32, _u64, _vp]),
     'fewbit_hipx_glu_forward': (_i32, [_i32, _i32, _vp, _sz, _vp, _sz, _sz, _sz, _i32, _u64, _vp, _vp, _vp, _sz, _vp]),
     'fewbit_hipx_glu_backward': (_i32, [_i32, _i32, _vp, _vp, _sz, _sz, _i32, _vp, _sz, _vp, _sz, _vp]),
+    # the same backward that also rebuilds the product from the decodes (the gated MLP as one node): inside revision 2 as well, recognised by its symbol
+    'fewbit_hipx_glu_backward_product': (_i32, [_i32, _i32, _vp, _vp, _sz, _sz, _i32, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -905,4 +908,54 @@ def glu_backward(gy: torch.Tensor, state: torch.Tensor, activation: str, bits: i
         ptr = lambda t: None if t is None else t.data_ptr()
         _check(lib().fewbit_hipx_glu_backward(DTYPES[gy.dtype], act, gy.data_ptr(), state.data_ptr(), rows, width, bits, ptr(outs[0]), lds[0], ptr(outs[1]), lds[1],
                                               _stream(stream, gy.device)))
+    return tuple(outs)
+
+
+def glu_backward_product(gy: Optional[torch.Tensor], state: torch.Tensor, activation: str, bits: int, want=(True, True, True), d_gate: Optional[torch.Tensor] = None,
+                         d_up: Optional[torch.Tensor] = None, product: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """``glu_backward`` that also rebuilds the product from the state, in the same ONE launch -> ``(d_gate, d_up, product)`` in the dtype of ``gy``:
+    ``d_gate`` and ``d_up`` with the bytes of ``glu_backward``, ``product = act(g^) * u^``, the forward's own expression on the decodes (``act`` in
+    fp32, one product, rounded once) -- what a ``down_proj`` behind the product needs for its weight gradient, so that nothing of ``y`` is kept.
+    Where ``want`` is False the output is None and nothing of it is computed or written; nothing wanted: no launch.  ``gy`` may be None when
+    neither gradient is wanted: the shape and the dtype are then those of ``product``, which must be given.  ``d_gate``, ``d_up``, ``product``:
+    buffers to write into, 2-D of the shape of ``gy`` with unit stride along the width and any row stride; the gap of a row stride is not
+    written.  A poisoned group is NaN on its 64 elements of all three outputs."""
+    want = tuple(bool(w) for w in want)
+    if len(want) != 3:
+        raise FewbitHipError('want must name three outputs (d_gate, d_up, product)')
+    # (what needs no look at a tensor is refused first)
+    act = _glu_activation(activation)
+    if bits not in QUANT_BITS:
+        raise FewbitHipError(f'glu_backward_product: bits must be 2, 4 or 8 (got {bits})')
+    if gy is None:
+        if want[0] or want[1]:
+            raise FewbitHipError('gy may be None only when neither d_gate nor d_up is wanted')
+        if not want[2]:
+            return None, None, None
+        if product is None:
+            raise FewbitHipError('without gy the product buffer must be given: it carries the shape and the dtype')
+        like = product
+    else:
+        if gy.dim() != 2 or not gy.is_contiguous():
+            raise FewbitHipError('gy must be a contiguous 2-D tensor')
+        like = gy
+    rows, width, _ = _glu_rows(like, 'product' if gy is None else 'gy')
+    need = _glu_size(rows * width, bits, 'glu_backward_product')
+    if state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < need:
+        raise FewbitHipError(f'state must be a contiguous uint8 tensor of at least {need} bytes')
+    with _on(like.device):
+        outs, lds = [], []
+        for t, wanted, what in ((d_gate, want[0], 'd_gate'), (d_up, want[1], 'd_up'), (product, want[2], 'product')):
+            if not wanted:
+                t = None
+            elif t is None:
+                t = torch.empty((rows, width), dtype=like.dtype, device=like.device)
+            elif t.dtype != like.dtype or tuple(t.shape) != (rows, width):
+                raise FewbitHipError(f'{what} must be a {rows} x {width} tensor of {like.dtype}')
+            outs.append(t)
+            lds.append(0 if t is None else _glu_rows(t, what)[2])
+        _same_device(like, state, *(t for t in outs if t is not None))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _check(lib().fewbit_hipx_glu_backward_product(DTYPES[like.dtype], act, ptr(gy), state.data_ptr(), rows, width, bits, ptr(outs[0]), lds[0], ptr(outs[1]), lds[1],
+                                                      ptr(outs[2]), lds[2], _stream(stream, like.device)))
     return tuple(outs)

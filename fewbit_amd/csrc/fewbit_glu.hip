@@ -14,13 +14,15 @@
 // width is a multiple of 8 (a block never straddles two rows then) and every base and row stride is 16-byte aligned, element accesses with (r, c)
 // from the flat index otherwise: the same arithmetic either way, so the same bytes.  The gap between `width` and a row stride is never touched.
 // Backward: ONE launch; a lane reads its two code words, the parameters of its two groups and its block of gy and writes its blocks of d_gate and
-// d_up (either may be absent).
+// d_up (either may be absent).  The same launch with PRODUCT set (fewbit_hipx_glu_backward_product) also writes act(g^) * u^, the product rebuilt from
+// the decodes: what the gated MLP as one node (fewbit_amd/glu.py, gated_mlp_quantized) feeds to the weight gradient of down_proj instead of a kept y.
 // One unit per dtype (-DFEWBIT_GLU_TU=0 / 1 / 2: fp32 with the C entry points, fp16, bf16), compiled in parallel and linked into one library.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 #include "fewbit_device.h"
 #include "fewbit_hipx.h"
@@ -62,6 +64,10 @@ struct BackwardArgs {
     size_t part, width, n;
     void *d_gate, *d_up;
     size_t ld_dgate, ld_dup;
+};
+struct ProductArgs : BackwardArgs {         // the PRODUCT kernels: a third output; gy may then be nullptr where d_gate and d_up both are
+    void *product;
+    size_t ld_product;
 };
 
 // ---- where flat index i lies in a matrix of `width` columns whose rows are `ld` elements apart ---------------------------------------------------
@@ -259,8 +265,12 @@ __global__ __launch_bounds__(kThreads) void glu_forward_kernel(ForwardArgs a) {
     }
 }
 
-template <int DT, int ACT, int BITS, bool VEC>
-__global__ __launch_bounds__(kThreads) void glu_backward_kernel(BackwardArgs a) {
+// PRODUCT: a third output, product[i] = narrow(act(g^) * u^), the forward's own expression on the decodes; gy may then be absent (with both gradients).
+// PRODUCT = false is the backward as it was, instruction for instruction (tools/isa_digest.py): the flag is a parameter of the ONE kernel text, not a
+// device function both kernels call, and the product's stride is folded in behind the declaration of `gradients_strided` -- either of the other
+// two spellings compiles the plain kernels to a few instructions more.
+template <int DT, int ACT, int BITS, bool VEC, bool PRODUCT>
+__global__ __launch_bounds__(kThreads) void glu_backward_kernel(std::conditional_t<PRODUCT, ProductArgs, BackwardArgs> a) {
     using T = typename Elem<DT>::type;
     constexpr bool kFast = DT != FEWBIT_F32;
     constexpr uint32_t kLevels = (1u << BITS) - 1u;
@@ -268,33 +278,49 @@ __global__ __launch_bounds__(kThreads) void glu_backward_kernel(BackwardArgs a) 
     const size_t n = a.n, blocks = (n + kBlock - 1) / kBlock, groups = (n + kGroup - 1) / kGroup, span = static_cast<size_t>(gridDim.x) * kThreads;
     const uint8_t *second = a.state + a.part;
     const bool want_gate = a.d_gate != nullptr, want_up = a.d_up != nullptr;
-    const bool small = (n >> 32) == 0, strided = (want_gate && a.ld_dgate != a.width) || (want_up && a.ld_dup != a.width);
+    const bool small = (n >> 32) == 0, gradients_strided = (want_gate && a.ld_dgate != a.width) || (want_up && a.ld_dup != a.width);
+    bool strided = gradients_strided;
+    if constexpr (PRODUCT) strided = strided || (a.product != nullptr && a.ld_product != a.width);
     for (size_t b = static_cast<size_t>(blockIdx.x) * kThreads + threadIdx.x; b < blocks; b += span) {
         const size_t i0 = b * kBlock;
         const int have = n - i0 < static_cast<size_t>(kBlock) ? static_cast<int>(n - i0) : kBlock;
         const uint2 par_g = *reinterpret_cast<const uint2 *>(a.state + 8 * (b / kLanes)), par_u = *reinterpret_cast<const uint2 *>(second + 8 * (b / kLanes));
         const uint64_t word_g = load_word<BITS>(a.state + 8 * groups, b), word_u = load_word<BITS>(second + 8 * groups, b);
         const float lo_g = float_of_bits(par_g.x), step_g = float_of_bits(par_g.y), lo_u = float_of_bits(par_u.x), step_u = float_of_bits(par_u.y);
-        // a poisoned group of EITHER input: both gradients are NaN on its 64 elements
+        // a poisoned group of EITHER input: every output is NaN on its 64 elements
         const bool poisoned = step_g != step_g || step_u != step_u;
-        T rgy[kBlock], rdg[kBlock], rdu[kBlock];
-        load_rows<DT, VEC>(gy, 0, ~size_t{0}, Where{0, i0}, have, rgy);
+        T rgy[kBlock], rdg[kBlock], rdu[kBlock], rpr[kBlock];
+        if (PRODUCT && gy == nullptr) {
+#pragma unroll
+            for (int e = 0; e < kBlock; ++e) rgy[e] = T{0};                                        // (no gradient is wanted: the product alone)
+        } else {
+            load_rows<DT, VEC>(gy, 0, ~size_t{0}, Where{0, i0}, have, rgy);
+        }
 #pragma unroll
         for (int e = 0; e < kBlock; ++e) {
             const float g = decode(static_cast<uint32_t>(word_g >> (BITS * e)) & kLevels, lo_g, step_g);
             const float u = decode(static_cast<uint32_t>(word_u >> (BITS * e)) & kLevels, lo_u, step_u);
             const float upstream = float_of_bits(widen<DT>(rgy[e]));
-            const float du = mul_rn(upstream, act_of<ACT, kFast>(g));
-            rdu[e] = narrow<DT>(poisoned ? float_of_bits(kNaN) : du);
+            // (the plain kernels evaluate d_up whether or not it is stored, as they always have; the PRODUCT kernels only where it is wanted)
+            if (!PRODUCT || want_up) {
+                const float du = mul_rn(upstream, act_of<ACT, kFast>(g));
+                rdu[e] = narrow<DT>(poisoned ? float_of_bits(kNaN) : du);
+            }
             if (want_gate) {
                 const float dg = mul_rn(mul_rn(upstream, u), slope_of<ACT, kFast>(g));
                 rdg[e] = narrow<DT>(poisoned ? float_of_bits(kNaN) : dg);
+            }
+            if constexpr (PRODUCT) {
+                if (a.product != nullptr) rpr[e] = narrow<DT>(poisoned ? float_of_bits(kNaN) : mul_rn(act_of<ACT, kFast>(g), u));
             }
         }
         const Where at = strided ? where_of(i0, a.width, small) : Where{0, i0};
         const size_t wrap = strided ? a.width : ~size_t{0};
         if (want_gate) store_rows<DT, VEC>(static_cast<T *>(a.d_gate), a.ld_dgate, wrap, at, have, rdg);
         if (want_up) store_rows<DT, VEC>(static_cast<T *>(a.d_up), a.ld_dup, wrap, at, have, rdu);
+        if constexpr (PRODUCT) {
+            if (a.product != nullptr) store_rows<DT, VEC>(static_cast<T *>(a.product), a.ld_product, wrap, at, have, rpr);
+        }
     }
 }
 
@@ -315,8 +341,14 @@ template <int DT, int ACT, int BITS> void launch(bool vec, unsigned grid, hipStr
 }
 template <int DT, int ACT, int BITS> void launch(bool vec, unsigned grid, hipStream_t s, const BackwardArgs &a) {
     if constexpr (BITS != 0) {
-        if (vec) hipLaunchKernelGGL((glu_backward_kernel<DT, ACT, BITS, true>), dim3(grid), dim3(kThreads), 0, s, a);
-        else hipLaunchKernelGGL((glu_backward_kernel<DT, ACT, BITS, false>), dim3(grid), dim3(kThreads), 0, s, a);
+        if (vec) hipLaunchKernelGGL((glu_backward_kernel<DT, ACT, BITS, true, false>), dim3(grid), dim3(kThreads), 0, s, a);
+        else hipLaunchKernelGGL((glu_backward_kernel<DT, ACT, BITS, false, false>), dim3(grid), dim3(kThreads), 0, s, a);
+    }
+}
+template <int DT, int ACT, int BITS> void launch(bool vec, unsigned grid, hipStream_t s, const ProductArgs &a) {
+    if constexpr (BITS != 0) {
+        if (vec) hipLaunchKernelGGL((glu_backward_kernel<DT, ACT, BITS, true, true>), dim3(grid), dim3(kThreads), 0, s, a);
+        else hipLaunchKernelGGL((glu_backward_kernel<DT, ACT, BITS, false, true>), dim3(grid), dim3(kThreads), 0, s, a);
     }
 }
 template <int DT, int ACT, class Args> void launch_bits(int bits, bool vec, unsigned grid, hipStream_t s, const Args &a) {
@@ -332,10 +364,15 @@ template <int DT, class Args> void launch_act(int act, int bits, bool vec, unsig
 // (bits = 0: the plain forward)
 template <int DT> FEWBIT_HIDDEN void launch_forward(int act, int bits, bool vec, unsigned grid, hipStream_t s, const ForwardArgs &a);
 template <int DT> FEWBIT_HIDDEN void launch_backward(int act, int bits, bool vec, unsigned grid, hipStream_t s, const BackwardArgs &a);
+template <int DT> FEWBIT_HIDDEN void launch_product(int act, int bits, bool vec, unsigned grid, hipStream_t s, const ProductArgs &a);
 template <> void launch_forward<kUnitDtype>(int act, int bits, bool vec, unsigned grid, hipStream_t s, const ForwardArgs &a) {
     launch_act<kUnitDtype>(act, bits, vec, grid, s, a);
 }
 template <> void launch_backward<kUnitDtype>(int act, int bits, bool vec, unsigned grid, hipStream_t s, const BackwardArgs &a) {
+    launch_act<kUnitDtype>(act, bits, vec, grid, s, a);
+}
+
+template <> void launch_product<kUnitDtype>(int act, int bits, bool vec, unsigned grid, hipStream_t s, const ProductArgs &a) {
     launch_act<kUnitDtype>(act, bits, vec, grid, s, a);
 }
 
@@ -451,6 +488,38 @@ int fewbit_hipx_glu_backward(int dtype, int act, const void *gy, const uint8_t *
     default: glu::launch_backward<FEWBIT_BF16>(act, bits, vec, grid, s, a); break;
     }
     return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "glu_backward: the launch failed");
+}
+
+int fewbit_hipx_glu_backward_product(int dtype, int act, const void *gy, const uint8_t *state, size_t rows, size_t width, int bits, void *d_gate, size_t ld_dgate,
+                                     void *d_up, size_t ld_dup, void *product, size_t ld_product, void *stream) {
+    using glu::fail;
+    using glu::misaligned;
+    size_t n = 0;
+    if (!quant::known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward_product: bits = %d is not 2, 4 or 8", bits);
+    const int shape = glu::shape_of("glu_backward_product", dtype, act, rows, width, n);
+    if (shape != 0) return shape < 0 ? shape : FEWBIT_OK;
+    if ((d_gate != nullptr && ld_dgate < width) || (d_up != nullptr && ld_dup < width) || (product != nullptr && ld_product < width))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward_product: a row stride (%zu, %zu, %zu) is below the width %zu", ld_dgate, ld_dup, ld_product, width);
+    if (state == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward_product: null pointer");
+    if (gy == nullptr && (d_gate != nullptr || d_up != nullptr))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward_product: gy is a null pointer and a gradient is wanted (gy may be absent only with d_gate and d_up)");
+    const size_t item = quant::size_of(dtype);
+    if (misaligned(gy, item) || misaligned(d_gate, item) || misaligned(d_up, item) || misaligned(product, item))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward_product: gy, d_gate, d_up and product must be aligned to their element size");
+    if (misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward_product: state must be 8-byte aligned");
+    if (d_gate == nullptr && d_up == nullptr && product == nullptr) return FEWBIT_OK;
+    if (rows == 1) ld_dgate = ld_dup = ld_product = width;
+    const auto wide = [&](const void *p, size_t ld) { return p == nullptr || ((ld * item) % 16 == 0 && !misaligned(p, 16)); };
+    const bool vec = width % 8 == 0 && !misaligned(gy, 16) && wide(d_gate, ld_dgate) && wide(d_up, ld_dup) && wide(product, ld_product);
+    const glu::ProductArgs a{{gy, state, glu::part_bytes(n, bits), width, n, d_gate, d_up, ld_dgate, ld_dup}, product, ld_product};
+    const unsigned grid = glu::grid_of((n + quant::kBlock - 1) / quant::kBlock);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+    case FEWBIT_F32: glu::launch_product<FEWBIT_F32>(act, bits, vec, grid, s, a); break;
+    case FEWBIT_F16: glu::launch_product<FEWBIT_F16>(act, bits, vec, grid, s, a); break;
+    default: glu::launch_product<FEWBIT_BF16>(act, bits, vec, grid, s, a); break;
+    }
+    return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "glu_backward_product: the launch failed");
 }
 
 }  // extern "C"

@@ -255,5 +255,5 @@ del _name
 from .linear import linear_crs, linear_grp, linear_quantized, linear_randomized  # noqa: E402,F401
 from .variance import GradientStorage, catch_gradients  # noqa: E402,F401
 from .dropout import dropout, dropout_add  # noqa: E402,F401
-from .glu import glu_quantized  # noqa: E402,F401
+from .glu import gated_mlp_quantized, glu_quantized  # noqa: E402,F401
 from .norm import dropout_add_layer_norm_quantized, dropout_add_rms_norm_quantized, layer_norm_quantized, rms_norm_quantized  # noqa: E402,F401

@@ -38,7 +38,7 @@ from torch.autograd.function import once_differentiable
 from . import cabi_x, linear
 from .cabi import DTYPES
 
-__all__ = ('glu_quantized', 'QuantizedGLU', 'QuantizedGatedMLP')
+__all__ = ('glu_quantized', 'gated_mlp_quantized', 'QuantizedGLU', 'QuantizedGatedMLP')
 
 ACTIVATIONS = cabi_x.GLU_ACTIVATIONS
 
@@ -165,6 +165,180 @@ def glu_quantized(gate: torch.Tensor, up: Optional[torch.Tensor] = None, activat
     return _GLUQuantized.apply(gate, up, activation, int(bits), generator)
 
 
+class _GatedMLPQuantized(torch.autograd.Function):
+    """``down(act(gate(x)) * up(x))`` as ONE node (:func:`gated_mlp_quantized`).  Kept for backward on the kernels: the packed form of ``x`` (one
+    uint8 buffer, ``cabi_x.quant_pack``; only while ``gate_weight`` or ``up_weight`` requires grad), the state of gate and up (one uint8 buffer,
+    ``cabi_x.glu_forward``; only while something other than ``down_bias`` requires grad) and the three weights; in the PyTorch formulation the
+    codes (one per byte), lo and step of every group of each.  On ``ctx``: the two seeds (ints; device words while the stream is being captured;
+    None where nothing is rounded).
+    Nothing of the shape of ``x``, ``gate``, ``up`` or ``y`` in a float dtype."""
+
+    @staticmethod
+    def forward(ctx, x, gate_weight, up_weight, down_weight, gate_bias, up_bias, down_bias, activation: str, bits: int, generator):
+        needs = ctx.needs_input_grad
+        ctx.activation, ctx.bits, ctx.input_shape, ctx.input_dtype = activation, bits, tuple(x.shape), x.dtype
+        ctx.autocast = linear._autocast_seen(x.device.type)
+        ctx.keeps_x = needs[1] or needs[2]
+        ctx.keeps_gate_up = any(needs[:6])
+        ctx.seeds = None
+        flat = x.detach().reshape(-1, x.shape[-1])
+        gate, up = F.linear(x, gate_weight, gate_bias), F.linear(x, up_weight, up_bias)
+        lead, width = gate.shape[:-1], gate.shape[-1]
+        gate, up = gate.reshape(-1, width), up.reshape(-1, width)
+        ctx.flat_shape, ctx.width = tuple(flat.shape), width
+        kept = []
+        if _kernel_applies(gate, up) and flat.dtype in DTYPES:
+            if ctx.keeps_gate_up:
+                # two seeds wherever anything is rounded (also where x^ is not kept: the stream of the generator does not depend on what is frozen),
+                # seed_x first.  ONE would not do: the packed form and the gate part of the state both round in counter domain 7, so x^ and g^
+                # would meet the same uniforms at the same flat indices and E[d_gate^T x^] would no longer factor
+                ctx.seeds = (linear._sketch_seed(generator, flat.device), linear._sketch_seed(generator, flat.device))
+                if ctx.keeps_x:
+                    kept.append(cabi_x.quant_pack(flat if flat.is_contiguous() else flat.contiguous(), ctx.seeds[0], bits))
+                y, state = cabi_x.glu_forward(gate, up, activation, bits, ctx.seeds[1])
+                kept.append(state)
+            else:
+                # only down_bias is trained: its gradient is a column sum of the incoming one.  Nothing is rounded, no seed is drawn
+                y = cabi_x.glu_forward(gate, up, activation, keep=False)[0]
+        else:
+            if ctx.keeps_x:
+                kept.extend(linear._quantize_groups(flat, bits, generator))
+            if ctx.keeps_gate_up:
+                kept.extend(linear._quantize_groups(gate, bits, generator) + linear._quantize_groups(up, bits, generator))
+            y = _torch_product(gate, up, activation)
+        ctx.save_for_backward(*kept, gate_weight, up_weight, down_weight)
+        return F.linear(y.view(*lead, width), down_weight, down_bias)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        with linear._autocast_as(ctx.autocast):
+            return _GatedMLPQuantized._backward(ctx, linear._dense_rows(grad_output))
+
+    @staticmethod
+    def _backward(ctx, grad_output):
+        saved = ctx.saved_tensors                           # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
+        gate_weight, up_weight, down_weight = saved[-3:]
+        needs = ctx.needs_input_grad
+        rows, width = ctx.flat_shape[0], ctx.width
+        native = ctx.seeds is not None
+        G = grad_output.reshape(-1, grad_output.shape[-1])
+        if native and G.dtype not in DTYPES:
+            G = G.float()
+        want_gate, want_up, want_product = needs[0] or needs[1] or needs[4], needs[0] or needs[2] or needs[5], needs[3]
+        d_y = G @ down_weight if want_gate or want_up else None
+        d_gate = d_up = product = None
+        if native and (want_gate or want_up or want_product):
+            if d_y is not None and d_y.dtype not in DTYPES:
+                d_y = d_y.float()
+            dtype = G.dtype if d_y is None else d_y.dtype
+            if want_gate and want_up:
+                # [d_gate | d_up] in ONE buffer: the launch writes its two halves where they lie (row stride 2 width)
+                both = torch.empty((rows, 2 * width), dtype=dtype, device=G.device)
+                d_gate, d_up = both[:, :width], both[:, width:]
+            elif want_gate or want_up:
+                d_gate = torch.empty((rows, width), dtype=dtype, device=G.device) if want_gate else None
+                d_up = torch.empty((rows, width), dtype=dtype, device=G.device) if want_up else None
+            # (y^ in the gradient's dtype, 8-bit bf16 included: the tensor it stands for, y in bf16, is itself rounded to that grid)
+            product = torch.empty((rows, width), dtype=dtype, device=G.device) if want_product else None
+            cabi_x.glu_backward_product(d_y, saved[-4], ctx.activation, ctx.bits, (want_gate, want_up, want_product), d_gate, d_up, product)
+        elif want_gate or want_up or want_product:
+            g, u = _decoded(*saved[-9:-6], (rows, width)), _decoded(*saved[-6:-3], (rows, width))
+            work = g.dtype
+            poisoned = torch.isnan(g) | torch.isnan(u)
+            nan = torch.full((), float('nan'), dtype=work, device=g.device)
+            act = F.silu(g) if ctx.activation == 'silu' else F.gelu(g)
+            if want_gate or want_up:
+                gy = d_y.to(work)
+                d_up = torch.where(poisoned, nan, gy * act).to(d_y.dtype) if want_up else None
+                d_gate = torch.where(poisoned, nan, gy * u * _slope(g, ctx.activation)).to(d_y.dtype) if want_gate else None
+            product = torch.where(poisoned, nan, act * u).to(G.dtype) if want_product else None
+        grads = [None] * 10
+        if needs[3]:
+            grads[3] = (G.T @ product).to(down_weight.dtype)
+        if needs[6]:
+            grads[6] = G.sum(dim=0)
+        if needs[1] or needs[2]:
+            # x^ decoded ONCE for both products, in the gradient's dtype (a bf16 gradient at 8 bits: in fp32, two terms, as in QuantizedLinear)
+            like = d_gate if needs[1] else d_up
+            two_terms = linear._decode_in_two_terms(ctx.bits, like.dtype)
+            dtype = torch.float32 if two_terms else like.dtype
+            if native:
+                decoded = cabi_x.quant_unpack(saved[0], ctx.flat_shape[0] * ctx.flat_shape[1], ctx.bits, dtype).view(ctx.flat_shape)
+            else:
+                decoded = linear._dequantize_groups(*saved[:3], ctx.flat_shape, dtype)
+            if two_terms:
+                terms = linear._split_in_two_terms(decoded, like.dtype)     # (split once as well)
+                times_x = lambda d: linear._product_of_two_terms(d, terms)
+            else:
+                times_x = lambda d: d.T @ decoded
+            if needs[1]:
+                grads[1] = times_x(d_gate).to(gate_weight.dtype)
+            if needs[2]:
+                grads[2] = times_x(d_up).to(up_weight.dtype)
+        if needs[4]:
+            grads[4] = d_gate.sum(dim=0)
+        if needs[5]:
+            grads[5] = d_up.sum(dim=0)
+        if needs[0]:
+            # (two products into one sum: the weights are never concatenated)
+            dx = torch.addmm(d_gate @ gate_weight, d_up, up_weight)
+            grads[0] = dx.view(ctx.input_shape).to(ctx.input_dtype)
+        return tuple(grads)
+
+
+def _plain_gated_mlp(x, gate_weight, up_weight, down_weight, gate_bias, up_bias, down_bias, activation: str) -> torch.Tensor:
+    """the forward that keeps nothing (no gradient can follow): on the kernel path the product with the bytes of the keeping call"""
+    gate, up = F.linear(x, gate_weight, gate_bias), F.linear(x, up_weight, up_bias)
+    if _kernel_applies(gate, up) and x.dtype in DTYPES:
+        width = gate.shape[-1]
+        y = cabi_x.glu_forward(gate.reshape(-1, width), up.reshape(-1, width), activation, keep=False)[0].view(gate.shape)
+    else:
+        y = _torch_product(gate, up, activation)
+    return F.linear(y, down_weight, down_bias)
+
+
+def gated_mlp_quantized(x: torch.Tensor, gate_weight: torch.Tensor, up_weight: torch.Tensor, down_weight: torch.Tensor,
+                        gate_bias: Optional[torch.Tensor] = None, up_bias: Optional[torch.Tensor] = None, down_bias: Optional[torch.Tensor] = None,
+                        activation: str = 'silu', bits: int = 4, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """``F.linear(act(F.linear(x, gate_weight, gate_bias)) * F.linear(x, up_weight, up_bias), down_weight, down_bias)``, the gated MLP of the Llama
+    family, as ONE node that keeps ``x`` in the packed form of a seed (``bits`` = 2, 4 or 8 bits per element, as :func:`linear_quantized` keeps
+    it), ``gate`` and ``up`` in the state of :func:`glu_quantized`, and NOTHING of the product ``y``: three plain ``nn.Linear`` layers around
+    ``glu_quantized`` keep ``x`` and ``y`` in full, and ``y`` is the widest tensor of the block.  Per token of H = 4096, I = 11008 in bf16 at 4
+    bits: 2560 + 13760 bytes instead of 8192 + 13760 + 22016.
+
+    * The forward is the three GEMMs of torch and the product kernel: the output has the bytes of the unfused composition.
+    * Backward: ``d_y = G @ down_weight``; ONE launch (``cabi_x.glu_backward_product``) writes ``d_gate``, ``d_up`` and rebuilds
+      ``y^ = act(g^) * u^``, the forward's own expression on the decodes; ``d down_weight = G^T y^``, ``d gate_weight = d_gate^T x^``,
+      ``d up_weight = d_up^T x^`` with ``x^`` decoded once, ``dx = d_gate @ gate_weight + d_up @ up_weight``; the bias gradients are column sums.
+    * ``d_gate`` and ``d_up`` carry the bias of second order in the step that :func:`glu_quantized` states, and so does ``d down_weight``: the
+      two roundings are independent, so ``E[y^] = E[act(g^)] * u``, and ``act`` is not linear (tests/test_gated_mlp_host.py checks the mean of many
+      seeds against the exact expectation).  ``E[x^] = x``, rounded with a seed of its own, independent of ``g^`` and ``u^``.
+    * ``y^`` is written in the gradient's dtype, a bf16 gradient at 8 bits included: unlike ``X^`` of ``QuantizedLinear``, the exact tensor it
+      stands for (``y`` in bf16) is itself rounded to that grid, and torch's own ``d down_weight`` carries that rounding.  ``x^`` of a bf16
+      gradient at 8 bits is decoded in two terms, as in ``QuantizedLinear``.
+    * Seeds: TWO per call from ``linear._sketch_seed``, the one of ``x`` first: a call moves the host generator by two draws, or by none where only
+      ``down_bias`` requires grad and nothing is rounded (one seed would round ``x^`` and ``g^`` with the same uniforms at equal flat indices:
+      both round in counter domain 7).  While the stream is being captured into a hipGraph they are two device words (one eager call on the
+      device precedes a capture).
+    * Only what a requested gradient can need is kept: the packed ``x`` only while ``gate_weight`` or ``up_weight`` requires grad.  Grad mode
+      off, or nothing that requires grad: the plain forward -- no seed is drawn, nothing is kept, the same bytes.
+    * The kernels serve fp32 / fp16 / bf16 GPU tensors while ``linear.use_native_sketch()`` is on; host tensors, float64 and
+      ``use_native_sketch(False)`` take the PyTorch formulation of the same definition (``linear._quantize_groups``).
+    * Backward runs under the autocast state the forward saw; not differentiable twice; inside ``torch.utils.checkpoint`` ``generator`` must be
+      a default one (``None`` included)."""
+    if bits not in cabi_x.QUANT_BITS:
+        raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation should be 'silu' or 'gelu', but got {activation!r}.")
+    tensors = (x, gate_weight, up_weight, down_weight, gate_bias, up_bias, down_bias)
+    if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in tensors) or x.numel() == 0:
+        if x.numel() == 0:
+            return F.linear(_torch_product(F.linear(x, gate_weight, gate_bias), F.linear(x, up_weight, up_bias), activation), down_weight, down_bias)
+        return _plain_gated_mlp(*(None if t is None else t.detach() for t in tensors), activation)
+    return _GatedMLPQuantized.apply(*tensors, activation, int(bits), generator)
+
+
 class QuantizedGLU(torch.nn.Module):
     r"""``act(gate) * up`` of a gated MLP that keeps both inputs in ``bits`` bits per element for backward (:func:`glu_quantized`).
 
@@ -218,25 +392,37 @@ class QuantizedGatedMLP(torch.nn.Module):
     inputs in ``bits`` bits per element (:class:`QuantizedGLU`).  The projections are plain ``nn.Linear`` layers named as in those models.
 
     Parameters: ``in_features``, ``hidden_features`` (the intermediate width), ``bias`` (default False), ``activation`` (``'silu'`` or ``'gelu'``),
-    ``bits``, ``generator``, ``device``, ``dtype``.
+    ``bits``, ``generator``, ``device``, ``dtype``, and ``fused`` (default False): the whole MLP as ONE node (:func:`gated_mlp_quantized`) that
+    keeps ``x`` in ``bits`` bits as well and nothing of the product, where the default keeps ``x`` and the product in full for the three ``nn.Linear``
+    layers.  In ``eval()`` mode gradients that are asked for are torch's exact ones either way.
 
         >>> swap = lambda m, path: fewbit.QuantizedGatedMLP.from_mlp(m, bits=4) if type(m).__name__.endswith('MLP') else m
         >>> model = fewbit.map_module(model, swap)
     """
 
     def __init__(self, in_features: int, hidden_features: int, bias: bool = False, activation: str = 'silu', bits: int = 4,
-                 generator: Optional[torch.Generator] = None, device=None, dtype=None) -> None:
+                 generator: Optional[torch.Generator] = None, device=None, dtype=None, fused: bool = False) -> None:
         super().__init__()
+        self.fused = bool(fused)
         self.gate_proj = torch.nn.Linear(in_features, hidden_features, bias, device, dtype)
         self.up_proj = torch.nn.Linear(in_features, hidden_features, bias, device, dtype)
         self.down_proj = torch.nn.Linear(hidden_features, in_features, bias, device, dtype)
         self.glu = QuantizedGLU(activation, bits, generator)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self.down_proj(self.glu(self.gate_proj(x), self.up_proj(x)))
+        if not self.fused:
+            return self.down_proj(self.glu(self.gate_proj(x), self.up_proj(x)))
+        gate, up, down, glu = self.gate_proj, self.up_proj, self.down_proj, self.glu
+        if not self.training and torch.is_grad_enabled() and any(t.requires_grad for t in (x, *self.parameters())):
+            # eval mode is not where activation memory is short: gradients asked for there are torch's exact ones, nothing is rounded or drawn
+            return down(_torch_product(gate(x), up(x), glu.activation))
+        return gated_mlp_quantized(x, gate.weight, up.weight, down.weight, gate.bias, up.bias, down.bias, glu.activation, glu.bits, glu.generator)
+
+    def extra_repr(self) -> str:
+        return f'fused={self.fused}'
 
     @classmethod
-    def from_mlp(cls, module: torch.nn.Module, bits: int = 4, generator: Optional[torch.Generator] = None) -> 'QuantizedGatedMLP':
+    def from_mlp(cls, module: torch.nn.Module, bits: int = 4, generator: Optional[torch.Generator] = None, fused: bool = False) -> 'QuantizedGatedMLP':
         """A ``QuantizedGatedMLP`` that SHARES the three projections of ``module``: any module with ``gate_proj``, ``up_proj``, ``down_proj`` and an
         ``act_fn`` that is ``nn.SiLU``, ``nn.GELU()`` of the erf form, ``F.silu`` or ``F.gelu`` (``LlamaMLP`` and its kin), so that ``map_module``
         can swap the MLPs of a built model.  Any other ``act_fn``: ``ValueError``."""
@@ -244,6 +430,6 @@ class QuantizedGatedMLP(torch.nn.Module):
         if missing:
             raise TypeError(f'{type(module).__name__} has no {", ".join(missing)}: not a gated MLP of the gate_proj / up_proj / down_proj kind')
         activation = _activation_of(module.act_fn)
-        new = cls(1, 1, activation=activation, bits=bits, generator=generator, device='meta')
+        new = cls(1, 1, activation=activation, bits=bits, generator=generator, device='meta', fused=fused)
         new.gate_proj, new.up_proj, new.down_proj = module.gate_proj, module.up_proj, module.down_proj
         return new.train(module.training)

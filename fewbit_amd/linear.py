@@ -746,10 +746,20 @@ def _two_term_product(g: torch.Tensor, decoded: torch.Tensor) -> torch.Tensor:
     the deviation stayed).  On the GPU the library GEMM gives fp32 results for 16-bit operands (``out_dtype``): two GEMMs, an fp32 sum, rounded
     by the caller.  Elsewhere ONE GEMM of twice the depth, ``[g; g]^T [head; tail]``.  What is left of the rounding of ``decoded`` is 2^-9 of
     the tail: 2^-18 of an element."""
+    return _product_of_two_terms(g, _split_in_two_terms(decoded, g.dtype))
+
+
+def _split_in_two_terms(decoded: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """``[head; tail]`` of an fp32 ``decoded`` in ``dtype`` (``_two_term_product``): split ONCE where several gradients multiply one decode"""
     rows = decoded.shape[0]
-    terms = torch.empty((2 * rows, decoded.shape[1]), dtype=g.dtype, device=decoded.device)
+    terms = torch.empty((2 * rows, decoded.shape[1]), dtype=dtype, device=decoded.device)
     terms[:rows].copy_(decoded)                                             # head
     torch.sub(decoded, terms[:rows], out=terms[rows:])                      # tail: the difference is exact in fp32, rounded on the store
+    return terms
+
+
+def _product_of_two_terms(g: torch.Tensor, terms: torch.Tensor) -> torch.Tensor:
+    rows = terms.shape[0] // 2
     if g.is_cuda:                                                           # two GEMMs with fp32 results: no copy of g, no doubled depth
         with torch.autocast('cuda', enabled=False):
             return torch.mm(g.T, terms[:rows], out_dtype=torch.float32) + torch.mm(g.T, terms[rows:], out_dtype=torch.float32)

@@ -44,7 +44,9 @@ extern "C" {
  * So was the sum of a seed in front of the norm (fewbit_hipx_add_layer_norm_forward, _add_layer_norm_backward, _add_rms_norm_forward,
  * _add_rms_norm_backward): inside revision 2, recognised by the presence of the symbols.
  * So were the gate and the up of a seed, the product of a gated MLP (fewbit_hipx_glu_state_bytes, _glu_state_host, _glu_forward, _glu_backward):
- * inside revision 2, recognised by the presence of the symbols. */
+ * inside revision 2, recognised by the presence of the symbols.
+ * So was the backward of that product that also rebuilds the product from the state (fewbit_hipx_glu_backward_product, what the gated MLP as one
+ * node needs): inside revision 2, recognised by the presence of the symbol. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -497,6 +499,16 @@ int fewbit_hipx_add_rms_norm_backward(int dtype, const void *gy, const void *gh,
  *   gy           rows x width of `dtype`, contiguous; state: the buffer of a forward of the same rows, width and bits
  *   d_gate, d_up of `dtype`; either may be NULL: that output is skipped and nothing of it is written (both NULL: no launch).  The 16-byte path
  *                needs width % 8 == 0 and gy and every output present 16-byte aligned with such a row stride.  The gap of a row stride is not written.
+ * fewbit_hipx_glu_backward_product: fewbit_hipx_glu_backward with a third output, in the same ONE launch and by the same plan (what the gated MLP
+ *                as one node runs: down_proj's weight gradient needs the product y, and nothing of y is kept).
+ *   product      rows x width of `dtype`, row stride ld_product >= width:  product[i] = round_to_dtype(act(g^) * u^), the forward's own expression
+ *                (the same act, ONE fp32 product, rounded once) evaluated on the decodes.  E[product] = E[act(g^)] * u: the two roundings are
+ *                independent, and act is not linear -- a bias of second order in the step, as d_up carries.
+ *   d_gate, d_up exactly the arithmetic, and the bytes, of fewbit_hipx_glu_backward.
+ *   Any of the three outputs may be NULL: that output is skipped and nothing of it is written (all three NULL: no launch).  gy may be NULL only
+ *                where d_gate and d_up both are (only the product is wanted).  A poisoned group is NaN on its 64 elements of all three outputs.
+ *   The rules of alignment and stride, the choice between the 16-byte and the element path and the refusals are those of fewbit_hipx_glu_backward
+ *                with `product` as one more output; a NULL gy with a gradient wanted is refused.  The gap of a row stride is never written.
  * No LDS, no workspace, no atomics, no read-back: the same arguments give the same bits.  The plan is that of the packed form of a seed: lanes take
  * blocks of 8 elements (of both inputs: two Philox calls, two code words), 8 neighbouring lanes hold a group of each and reduce both minima, maxima
  * and poison flags by DPP lane moves, 256 lanes to a workgroup, at most 2048 workgroups, beyond which each lane sweeps on by the width of the grid.
@@ -509,6 +521,8 @@ int fewbit_hipx_glu_forward(int dtype, int act, const void *gate, size_t ld_gate
                             const uint64_t *seed_device, void *y, uint8_t *state, size_t state_bytes, void *stream);
 int fewbit_hipx_glu_backward(int dtype, int act, const void *gy, const uint8_t *state, size_t rows, size_t width, int bits, void *d_gate, size_t ld_dgate, void *d_up,
                              size_t ld_dup, void *stream);
+int fewbit_hipx_glu_backward_product(int dtype, int act, const void *gy, const uint8_t *state, size_t rows, size_t width, int bits, void *d_gate, size_t ld_dgate,
+                                     void *d_up, size_t ld_dup, void *product, size_t ld_product, void *stream);
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,7 @@ ROWS = [
     ('rms_norm_bench.json', 'tools/rms_norm_bench.py: fewbit.QuantizedRMSNorm at 2 / 4 / 8 bits forward + backward beside nn.RMSNorm at 16384 x 768 / 3072 / 4096, bf16 and fp32; bytes kept; gradient errors; the forward and backward entry points alone against their byte floors and against the layer-norm entry points', f'{E} 8.19'),
     ('add_norm_bench.json|add_norm_bench_run?.json', 'tools/add_norm_bench.py: fewbit.DropoutAddLayerNorm / DropoutAddRMSNorm at 2 / 4 / 8 bits forward + backward beside dropout_add + the quantized norm and beside torch at 16384 x 768 / 3072 (layer norm, p = 0.1) and 16384 x 4096 (RMS norm, prenorm), bf16 and fp32; bytes kept; the fused entry points alone against their byte floors (add_norm_bench.json and run2 .. run5: the five invocations whose minima are quoted)', f'{E} 8.21'),
     ('glu_bench.json', 'tools/glu_bench.py: fewbit.functional.glu_quantized at 2 / 4 / 8 bits forward + backward beside F.silu(gate) * up at 16384 x 3072 / 11008, bf16 and fp32; bytes kept; gradient errors; the forward and backward entry points alone against their byte floors', f'{E} 8.22'),
+    ('gated_mlp_bench.json', 'tools/gated_mlp_bench.py: fewbit.QuantizedGatedMLP(fused=True) at 2 / 4 / 8 bits forward + backward beside fused=False and the torch MLP at 16384 x 4096 -> 11008 / 768 -> 3072, bf16 and fp32, five alternating invocations; bytes saved for backward; the glu_backward_product entry point alone against its byte floor', f'{E} 8.23'),
     ('roberta_add_norm_bf16.json', 'tools/roberta_bench.py --dtype bf16 --dropout fewbit --layer-norm fused and --layer-norm fewbit, one run each: RoBERTa-base b128 x s128 with the sublayer endings on DropoutAddLayerNorm against dropout + QuantizedLayerNorm', f'{E} 8.21'),
     ('roberta_layer_norm_bf16.json', 'tools/roberta_bench.py --dtype bf16 --layer-norm fewbit: RoBERTa-base b128 x s128 with every nn.LayerNorm swapped for QuantizedLayerNorm(bits=4), alone and with the GELU swap', f'{E} 8.18'),
     ('dropout_kernel_times.txt', 'rocprofv3 --kernel-trace over tools/dropout_bench.py: per-dispatch durations of the dropout kernel and of torch\'s forward / backward dropout kernels, per shape', f'{E} 8.11'),
