@@ -1,7 +1,7 @@
 // fewbit_glu.hip -- the product of a gated MLP, y = act(gate) * up, that keeps BOTH inputs in 2, 4 or 8 bits per element for backward, on gfx950;
 // part of the companion library libfewbit_hipx.so (include/fewbit_hipx.h, "the gate and the up of a seed"):
 //
-//     y[i]   = round_to_dtype(act(g) * u)                                   act: silu or gelu (erf), the functors of fewbit_device.h (16-bit gelu: gelu_relative)
+//     y[i]   = round_to_dtype(act(g) * u)                                   act: silu or gelu (erf), the functors of fewbit_device.h (16-bit I/O: gelu_relative, sigmoid_relative)
 //     state  = [the packed form of the seed of gate | zero bytes up to a multiple of 8 | the same of up with counter word 3 = 8 | zero bytes]
 //     d_up   = round(gy * act(g^)),  d_gate = round((gy * u^) * act'(g^))   g^, u^: the decodes
 //
@@ -141,16 +141,45 @@ __device__ __forceinline__ float gelu_relative(float g) {
     return g < -0.5f ? mul_rn(g, mul_rn(0.5f, tail)) : head;
 }
 
-// act in fp32.  silu: the precise class for fp32 I/O, the fast class for 16-bit I/O, as in the activation kernels.  gelu: the precise class for
-// fp32 I/O (ATen's formula, and the check of fp32 is against ATen); gelu_relative for 16-bit I/O
+// sigmoid to a few fp32 ulps RELATIVE to its value on the whole line, as a scaled pair: sigmoid(g) = m * scale, 1 - sigmoid(g) = rest.  The fast
+// class's sigmoid_fast is rcp(1 + exp2(g * -log2e)): the one rounding of the argument costs |g| 2^-24 of exp(-g), which below g = -16 is more of
+// sigmoid(g) than the 2^-20 a product is allowed, and from g = -87.4 down the reciprocal is an fp32 subnormal that v_rcp_f32 gives as 0, while
+// silu(g) stays a normal bf16 number down to g = -97 and a subnormal one down to g = -105 (every bf16 gate, tests/test_gpu_glu_values.py).  So:
+//   the argument   t log2e as uh + ul, t = -g clamped to [-128, 256] (beyond: sigmoid is 1, or below every fp32 number; no inf - inf in ul),
+//                  the rounding error of the product and what fp32(log2 e) leaves of log2 e fed back: exp(-g) = exp2(uh) (1 + ul ln 2)
+//   g >= -64     : m = rcp(1 + e) (1 - ul ln 2 (1 - m)), scale = 1, rest = 1 - m
+//   g <  -64     : 1 + e is e in fp32 (e > 2^92): m = rcp(exp2(uh - 64)) (1 - ul ln 2), a normal number down to g = -131, scale = 2^-64, rest = 1.
+//                  The caller multiplies by the scale LAST, so that the one product that enters the subnormals is rounded once.
+struct Sigmoid { float m, scale, rest; };
+__device__ __forceinline__ Sigmoid sigmoid_relative(float g) {
+    constexpr float kHi = 1.44269502162933349609375f, kLo = 1.92596299112661746e-08f;                 // fp32(log2 e) and what it leaves of log2 e
+    const bool far = g < -64.0f;
+    const float t = __builtin_fminf(__builtin_fmaxf(-g, -128.0f), 256.0f);
+    const float uh = mul_rn(t, kHi);
+    const float ul = add_rn(fma_rn(t, kHi, -uh), mul_rn(t, kLo));
+    const float e = __builtin_amdgcn_exp2f(far ? sub_rn(uh, 64.0f) : uh);
+    const float m0 = __builtin_amdgcn_rcpf(far ? e : add_rn(1.0f, e));
+    const float rest0 = sub_rn(1.0f, m0);
+    const float m = fma_rn(-m0, mul_rn(mul_rn(ul, kLn2), far ? 1.0f : rest0), m0);
+    return Sigmoid{m, far ? 0x1p-64f : 1.0f, far ? 1.0f : sub_rn(1.0f, m)};
+}
+
+// act in fp32.  silu: the precise class for fp32 I/O; g * sigmoid_relative(g) for 16-bit I/O.  gelu: the precise class for fp32 I/O (ATen's
+// formula, and the check of fp32 is against ATen); gelu_relative for 16-bit I/O
 template <int ACT, bool FAST> __device__ __forceinline__ float act_of(float g) {
     if constexpr (ACT == FEWBIT_GELU && FAST) return gelu_relative(g);
-    else return Act<ACT, FAST>::eval(g, 0.0f, 0.0f);
+    else if constexpr (ACT == FEWBIT_SILU && FAST) {
+        const Sigmoid s = sigmoid_relative(g);
+        return mul_rn(mul_rn(g, s.m), s.scale);
+    } else return Act<ACT, FAST>::eval(g, 0.0f, 0.0f);
 }
 
 // act' in fp32, one operation per step:  silu: s (1 + g (1 - s)), s = sigmoid(g);  gelu: Phi(g) + g phi(g)
 template <int ACT, bool FAST> __device__ __forceinline__ float slope_of(float g) {
-    if constexpr (ACT == FEWBIT_SILU) {
+    if constexpr (ACT == FEWBIT_SILU && FAST) {
+        const Sigmoid s = sigmoid_relative(g);
+        return mul_rn(mul_rn(s.m, add_rn(1.0f, mul_rn(g, s.rest))), s.scale);
+    } else if constexpr (ACT == FEWBIT_SILU) {
         const float s = Act<FEWBIT_SIGMOID, FAST>::eval(g, 0.0f, 0.0f);
         return mul_rn(s, add_rn(1.0f, mul_rn(g, sub_rn(1.0f, s))));
     } else {

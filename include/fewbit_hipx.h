@@ -464,6 +464,10 @@ int fewbit_hipx_add_rms_norm_backward(int dtype, const void *gy, const void *gh,
  *               gelu(g) (the fast class keeps Phi(-|g|) to 4.5e-8 absolute, the precise class cancels in 1 + erf), and here the value is multiplied
  *               by u and rounded to half an ulp of the PRODUCT.  There g < -1/2 is evaluated as g * 0.5 * erfc(-g / sqrt 2) with the rounding error
  *               of the argument fed back (fewbit_glu.hip, gelu_relative): a few fp32 ulps of gelu(g) on the whole line.
+ *               And silu with 16-bit I/O, for the same reason: the fast class's sigmoid rounds its argument once (|g| 2^-24 of the value) and is 0
+ *               below g = -87.4, where silu(g) is still a bf16 number down to g = -105.  g * sigmoid(g) is evaluated with the rounding error of
+ *               g log2 e fed back and, below g = -64, with the exponent scaled by 2^64 and the scale multiplied in last (sigmoid_relative): a few
+ *               fp32 ulps of silu(g), or half an fp32 subnormal, on the whole line.  act' of silu takes the same sigmoid.
  *   The state, fewbit_hipx_glu_state_bytes(n, k) = 2 P bytes with P = fewbit_hipx_quant_bytes(n, k) rounded up to a multiple of 8:
  *     bytes [0, P): the gate part, byte for byte fewbit_hipx_quant_pack_host(gate as a contiguous tensor, n, k, seed) -- flat groups of 64 (they
  *               may straddle rows), counter word 3 = 7 -- then zero bytes up to P;
