@@ -346,7 +346,9 @@ int fewbit_hipx_quant_unpack(const uint8_t *packed, size_t n, int bits, int out_
  *     dx  = round_to_dtype(rstd * ((g^ - mean_row(g^)) - x^q * mean_row(g^ * x^q)))              mean_row: (the sum of the row) / width
  *     dgamma = sum_r gy * x^q,  dbeta = sum_r gy                                                   as fp32
  *   NaN and infinity: a non-finite element (or a row whose fp32 sum overflows) makes its row's x^ and y NaN and poisons every group of the
- *     row; that row of dx and the columns of dgamma it touches are then NaN, as with torch.  Other rows are untouched to the bit.
+ *     row; that row of dx and the columns of dgamma it touches are then NaN, as with torch.  Other rows are untouched to the bit.  A finite
+ *     row whose sum stays finite while the fp32 sum of its centred squares overflows (alternating +-2^66 at an even width: the sum is exactly
+ *     0) gives var = inf, rstd = 0, x^ = +-0 and y = beta; no group is poisoned, and that row of dx is +-0.
  *   Since E[x^q] = x^, dgamma is unbiased.  dx is not exactly: x^q enters it twice, E[dx_q] - dx = -rstd * g^_i * Var(x^q_i) / width, second
  *     order in the step.
  *

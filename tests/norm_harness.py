@@ -2,8 +2,9 @@
 ``philox`` and ``order_keys`` also serve tests/test_quant_host.py): guarded GPU buffers and the options of a sweep, the hooks that show what a
 call saved and which seeds it drew, the numpy pieces of the definition, the two statistics over many calls, and -- as functions of a ``Kind``, the
 record of what differs between the layer norm and the RMS norm -- the bodies that are one text for both: the layer inside checkpointing,
-autocast, no_grad / eval and a captured graph, and the gradients of 200 calls on host tensors.  Wherever the two kinds assert different things
-(bounds, non-finite patterns, the walks of a workgroup) the tests stay in their own files."""
+autocast, no_grad / eval and a captured graph, and the gradients of 200 calls on host tensors; the row counts at which a workgroup of the entry
+points walks on to a later tile (``walk``), the tables of such cases and the two bodies that run them through a module's own ``run_*`` and
+``check_*``.  Wherever the two kinds assert different things (bounds, non-finite patterns) the tests stay in their own files."""
 import math
 from typing import Callable, NamedTuple
 
@@ -90,6 +91,152 @@ def seed_argument(device_word):
 
 def allowance(measured, width):
     return max(2.0 * measured, math.log2(width) + 4.0)
+
+
+# ---- where a workgroup begins to walk ------------------------------------------------------------------------------------------------------------
+DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+BITS = (2, 4, 8)
+CAP = {'forward': 16384, 'backward': 512}       # kMaxGridForward, kMaxGridBackward of fewbit_norm.hip: the most workgroups a launch has
+LANES = {'forward': 256, 'backward': 1024}      # kThreads, kBackwardThreads: the lanes of a workgroup
+
+
+def lanes_per_row(width, direction):
+    """``cabi_x.norm_plan``'s lanes forward; backward a lane holds ONE block, so beyond 2048 elements a row takes 512 or 1024 lanes (its docstring)"""
+    lanes, blocks = cabi_x.norm_plan(width)
+    return lanes if direction == 'forward' else lanes * blocks
+
+
+def walk(width, direction, tiles, extra=None):
+    """The rows at which a workgroup of `direction` ('forward' / 'backward') at `width` takes its tile number `tiles`:
+    ``(tiles - 1) * cap * rows_per_tile + extra`` with rows_per_tile = 256 / lanes forward and 1024 / lanes backward (lanes: ``norm_plan``'s, and the
+    backward rule of its docstring) and cap = 16384 workgroups forward, 512 backward -- the constants of fewbit_norm.hip that ``norm_plan`` quotes.
+    `extra` rows go into the last sweep: 1 makes workgroup 0 alone walk on, with one live row in its tile; None is a full sweep, every workgroup
+    walks.  Backward the walk is asserted from the library: the workspace is that of a grid at its cap, and there are more tiles than that."""
+    lanes = lanes_per_row(width, direction)
+    per_tile, cap = LANES[direction] // lanes, CAP[direction]
+    extra = cap * per_tile if extra is None else extra
+    assert tiles >= 2 and 1 <= extra <= cap * per_tile
+    rows = (tiles - 1) * cap * per_tile + extra
+    if direction == 'backward':
+        assert cabi_x.norm_workspace_bytes(rows, width) == 512 * 2 * lanes * 8 * 4, f'{rows} x {width}: the backward grid is not 512 workgroups of {lanes} lanes per row'
+        assert -(-rows // per_tile) > 512, f'{rows} x {width}: no workgroup takes a second tile'
+    return rows
+
+
+class Walk(NamedTuple):
+    lanes: int                    # per row
+    blocks: int                   # of 8 elements per lane
+    width: int
+    tiles: int                    # the tile of its walk that workgroup 0 reaches
+    extra: object                 # rows in the last sweep; None: a full one
+    dtype: torch.dtype
+    bits: int
+    off: int                      # elements off 16-byte alignment
+    affine: bool
+
+    def rows(self, direction):
+        rows = walk(self.width, direction, self.tiles, self.extra)
+        assert (self.lanes, self.blocks) == (lanes_per_row(self.width, direction), 1 if direction == 'backward' else cabi_x.norm_plan(self.width)[1])
+        return rows
+
+    def __str__(self):
+        return f'{self.lanes}x{self.blocks}-w{self.width}-{self.tiles}_tiles{"" if self.extra is None else "+%d" % self.extra}-{str(self.dtype)[6:]}-{self.bits}b'
+
+
+# backward: (lanes per row, widths, (tile reached, rows of the last sweep)); every width with every row count.  Width 4097 runs one element off
+# 16-byte alignment (its rows are off it by themselves from the second on)
+BACKWARD_WALKS = ((16, (72, 128), ((2, 1), (3, 1))), (64, (136, 192), ((2, 1), (3, 1))), (256, (1032, 2048), ((2, 1), (3, 1), (3, None))),
+                  (512, (2056, 4096), ((2, 1), (3, 1), (3, None))), (1024, (4104, 8192, 4097), ((2, 1), (3, 1), (3, None))))
+# forward: ((lanes per row, blocks per lane), widths, (tile reached, rows of the last sweep)); 136 and 1032 keep a short last group inside a walk
+FORWARD_WALKS = (((16, 1), (128, ), ((2, 1), )), ((64, 1), (192, 136), ((2, 1), )), ((256, 1), (1088, 1032), ((2, 1), (3, 1))),
+                 ((256, 2), (2112, ), ((2, 1), )), ((256, 4), (4160, ), ((2, 1), )))
+
+
+def walks(direction, shift=0, fused=False):
+    """The cases of a table.  dtype and bits rotate over the cases of a plan (`shift`: where the rotation starts, so that the two kinds differ) such
+    that the plain cases of ONE kind hold every (plan, dtype) and every (plan, bits) pair: a plan with fewer than three cases repeats them with the
+    next dtype and bits.  The forward plan of four blocks per lane runs in the 16-bit dtypes, which halves its input.  `fused`: ONE width per
+    plan -- `shift` picks which -- with every row count once, and forward only the plans of 256 lanes per row (1, 2 and 4 blocks per lane)."""
+    for plan, widths, sweeps in FORWARD_WALKS if direction == 'forward' else BACKWARD_WALKS:
+        lanes, blocks = plan if direction == 'forward' else (plan, 1)
+        if fused and direction == 'forward' and lanes < 256:
+            continue
+        base = [(w, t, e) for w in ((widths[shift % len(widths)], ) if fused else widths) for t, e in sweeps]
+        dtypes = DTYPES[1:] if blocks == 4 else DTYPES
+        for i in range(len(base) if fused else max(3, len(base))):
+            width, tiles, extra = base[i % len(base)]
+            j = i + shift
+            yield Walk(lanes, blocks, width, tiles, extra, dtypes[j % len(dtypes)], BITS[(j + i // 3) % 3], 1 if width % 4 else i & 1, i % 4 != 3)
+
+
+def first_difference(a, b, row_bytes=None):
+    """where two tensors of the same bytes first differ, for the message of a failed byte comparison ('' when equal): flat byte offsets, and the
+    rows they lie in when a row has `row_bytes` bytes"""
+    a, b = a.contiguous().view(-1).view(torch.uint8), b.contiguous().view(-1).view(torch.uint8)
+    if a.numel() != b.numel():
+        return f'{a.numel()} against {b.numel()} bytes'
+    at = torch.nonzero(a != b).flatten()
+    if at.numel() == 0:
+        return ''
+    rows = '' if row_bytes is None else f', rows {sorted(set((at[:64] // row_bytes).tolist()))[:8]}'
+    return f'{at.numel()} bytes differ, the first at {at[:8].tolist()}{rows}'
+
+
+def state_rows(state, rows, width):
+    """the bytes of a state row by row: (the (lo, step) pairs, the codes)"""
+    pairs = 8 * rows * -(-width // 64)
+    return state[:pairs].view(rows, -1), state[pairs:].view(rows, -1)
+
+
+def backward_walks_on(case, backward_problem, run_backward, check_backward_values):
+    """A backward workgroup on a later tile of its walk, from the host state of a module's `backward_problem` through its `run_backward` (guards
+    intact, inputs unchanged) and `check_backward_values` (the float64 formula, the unchanged bounds); two runs byte-equal -> (K', the torch ops')"""
+    rows, width = case.rows('backward'), case.width
+    state, xq, rstd, gy, gamma = backward_problem(rows, width, case.dtype, case.bits, case.affine)
+    outs = run_backward(state, rstd, gy, gamma, case.bits, case.off)
+    k = check_backward_values(xq, rstd, gy, gamma, outs[0].t.view(rows, width), *(o.t for o in outs[1:]), f'{rows} x {width} ({case})')
+    again = run_backward(state, rstd, gy, gamma, case.bits, case.off)
+    for name, a, b in zip(('dx', 'dgamma', 'dbeta'), outs, again):
+        assert torch.equal(a.raw, b.raw), f'{rows} x {width} ({case}): two runs differ in {name}: {first_difference(a.t, b.t, width * a.t.element_size() if name == "dx" else None)}'
+    print(f"{rows} x {width} ({case}): K'(dx) = {k[0]:.2f}; plain fp32 torch ops: {k[1]:.2f}")
+    return k
+
+
+def tiled(small, rows):
+    """`rows` rows on the GPU: row r is row r % len(small) of `small`, and the index that says so"""
+    index = torch.arange(rows, device=DEV) % small.shape[0]
+    return small.to(DEV)[index], index
+
+
+def forward_walks_on(case, inputs, run_forward, check_forward_values):
+    """A forward workgroup on a later tile of its walk.  The input is the 37 distinct rows of a module's `inputs` repeated.  The 37 rows alone, a call
+    of their own, are held to float64 by the module's `check_forward_values`; the plan is a function of the width alone and a row's arithmetic does not
+    depend on its tile, so row r of the long call has the BYTES of row r % 37 of the short one in y, rstd and x^.  The state depends on r through
+    the Philox counter: for a width that is a multiple of 64 it is ``quant_pack`` of the flat x^ (the header; tests/test_gpu_quant.py pins that to the
+    host evaluation), for a ragged width ``norm_state_host`` in full.  Two runs byte-equal; ``keep=False`` gives the same y and rstd bytes."""
+    rows, width = case.rows('forward'), case.width
+    label = f'{rows} x {width} ({case})'
+    small, *parameters = inputs(37, width, case.dtype)
+    parameters = parameters if case.affine else [None] * len(parameters)
+    y0, rstd0, _, xhat0 = run_forward(small, *parameters, case.bits, SEED, case.off)
+    k = check_forward_values(small, *parameters, y0.t.view(37, width), rstd0.t, xhat0.t.view(37, width), f'37 x {width} ({case})')
+    x, index = tiled(small, rows)
+    y, rstd, state, xhat = run_forward(x, *parameters, case.bits, SEED, case.off)
+    for name, long, short in (('y', y, y0), ('rstd', rstd, rstd0), ('xhat', xhat, xhat0)):
+        a, b = long.t.view(rows, -1), short.t.view(37, -1)[index]
+        assert torch.equal(a.view(torch.uint8), b.view(torch.uint8)), f'{label}: {name} of row r is not that of row r % 37: {first_difference(a, b, a.shape[1] * a.element_size())}'
+    if width % 64 == 0:
+        want = cabi_x.quant_pack(xhat.t.clone(), SEED, case.bits)
+    else:
+        want = cabi_x.norm_state_host(xhat.t.view(rows, width).cpu(), SEED, case.bits).to(DEV)
+    assert torch.equal(state.t, want), f'{label}: the state: {first_difference(state.t, want)}'
+    plain = run_forward(x, *parameters, case.bits, SEED, case.off, keep=False, want_xhat=False)
+    assert torch.equal(plain[0].raw, y.raw) and torch.equal(plain[1].raw, rstd.raw), f'{label}: keep=False: y {first_difference(plain[0].t, y.t)} rstd {first_difference(plain[1].t, rstd.t)}'
+    again = run_forward(x, *parameters, case.bits, SEED, case.off)
+    for name, a, b in zip(('y', 'rstd', 'state', 'xhat'), (y, rstd, state, xhat), again):
+        assert torch.equal(a.raw, b.raw), f'{label}: two runs differ in {name}: {first_difference(a.t, b.t)}'
+    print(f'37 x {width} ({case}): K(x^) = {k[0]:.2f}, K(rstd) = {k[1]:.2f}; plain fp32 torch ops: {k[2]:.2f}, {k[3]:.2f}')
+    return k
 
 
 # ---- what a call saved, which seeds it drew -----------------------------------------------------------------------------------------------------

@@ -9,14 +9,16 @@ has, because the definition is the existing arithmetic in the existing order:
   width only, so that is the same arithmetic); ``dbranch`` is ``dropout_apply(dres, seed, p)``; the sums are the plain backward's bytes;
 * guard bytes intact, inputs unchanged, two runs byte-equal, NULL outputs skipped and without the sums the workspace untouched.
 
-Widths: with a mask every plan threshold and the next multiple of 8; without one also the ragged widths around them."""
+Widths: with a mask every plan threshold and the next multiple of 8; without one also the ragged widths around them.  A workgroup that walks several
+tiles: widths 8 and 520, and -- with ``norm_harness.walk`` and the tables of tests/test_gpu_norm.py -- backward every lanes-per-row from 16 to 1024,
+forward 256 lanes per row with 1, 2 and 4 blocks per lane, each with a mask."""
 import itertools
 
 import pytest
 import torch
 
 from fewbit_amd import cabi_x
-from norm_harness import DEV, EPS, FILL, SEED, Guarded, options, seed_argument
+from norm_harness import DEV, EPS, FILL, SEED, Guarded, first_difference, options, seed_argument, tiled, walks
 
 pytestmark = pytest.mark.gpu
 MASKED_WIDTHS = (8, 64, 72, 128, 136, 512, 520, 768, 1024, 1032, 2048, 2056, 4096, 4104, 8192)
@@ -186,6 +188,46 @@ def test_backward_width_520_a_workgroup_walks_on(rows):
     want = composed_backward(kind, gy, gh, state, rstd, parameters[0], bits, SEED, p)
     for name, a, b in zip(('dres', 'dbranch', 'dgamma', 'dbeta'), got, want):
         assert same(a, b), f'{name} differs'
+
+
+def mismatch(got, want, names, row_bytes):
+    """'' when every output has the bytes it should have, else the first output that does not and where"""
+    for name, a, b in zip(names, got, want):
+        if not ((a is None and b is None) or same(a, b)):
+            return f'{name}: {first_difference(a, b, row_bytes(a))}'
+    return ''
+
+
+def tiled_inputs(case, rows, centred):
+    """`inputs` of 37 rows repeated on the GPU (the masks and the rounding bits still differ from row to row: they come from the flat index)"""
+    x, res, parameters, gy, gh = inputs(37, case.width, case.dtype, centred, case.affine)
+    return (*(tiled(t, rows)[0] for t in (x, res)), parameters, *(tiled(t, rows)[0] for t in (gy, gh)))
+
+
+@pytest.mark.parametrize('kind, case', [(kind, case) for shift, kind in enumerate(KINDS) for case in walks('forward', shift, fused=True)], ids=str)
+def test_forward_a_workgroup_walks_on_at_256_lanes_per_row_and_1_2_4_blocks_per_lane(kind, case):
+    """one row past one or two sweeps of the 16384 workgroups with a mask, where a lane holds 1, 2 or 4 blocks: the composition, bit for bit"""
+    rows, p = case.rows('forward'), (0.1, 0.5)[case.bits == 4]
+    x, res, parameters, _, _ = tiled_inputs(case, rows, KINDS[kind][4])
+    got = run_forward(kind, x, res, parameters, case.bits, SEED, p, case.off)
+    want = composed_forward(kind, x, res, parameters, case.bits, SEED, p)
+    wrong = mismatch(got, want, ('y', 'h', 'rstd', 'state', 'xhat'), lambda t: t[0].numel() * t.element_size() if t.dim() == 2 else None)
+    assert not wrong, f'{kind} {rows} x {case.width} ({case}) p {p}: {wrong}'
+
+
+@pytest.mark.parametrize('kind, case', [(kind, case) for shift, kind in enumerate(KINDS) for case in walks('backward', shift, fused=True)], ids=str)
+def test_backward_a_workgroup_walks_on_at_every_lanes_per_row(kind, case):
+    """16 to 1024 lanes per row (norm_harness.walk asserts the 512 workgroups from the workspace query), one row past one and two sweeps and three
+    full sweeps, with gh, a mask and every output: the composition, bit for bit"""
+    rows, p = case.rows('backward'), (0.1, 0.5)[case.bits == 4]
+    centred = KINDS[kind][4]
+    x, res, parameters, gy, gh = tiled_inputs(case, rows, centred)
+    _, _, rstd, state, _ = composed_forward(kind, x, res, parameters, case.bits, SEED, p)
+    names = ('dres', 'dbranch', 'dgamma', 'dbeta')[:4 if centred else 3]
+    got = run_backward(kind, gy, gh, state, rstd, parameters[0], case.bits, SEED, p, case.off, (True, ) * len(names))
+    want = composed_backward(kind, gy, gh, state, rstd, parameters[0], case.bits, SEED, p)
+    wrong = mismatch(got, want, names, lambda t: t[0].numel() * t.element_size() if t.dim() == 2 else None)
+    assert not wrong, f'{kind} {rows} x {case.width} ({case}) p {p}: {wrong}'
 
 
 # ---- non-finite inputs -------------------------------------------------------------------------------------------------------------------------

@@ -11,7 +11,12 @@ and as a device word.
 * Backward from a given (host) state: dx against the float64 formula on ``norm_state_unpack_host`` within
   ``u |dx| + K' 2^-24 rstd (|g^| + mean|g^| + |x^q| mean|g^ x^q|)``, K' measured the same way; dgamma and dbeta within
   ``(rows + 3) 2^-24 sum_r |terms|``, the bound of a fixed-order fp32 sum of `rows` rounded products; two runs byte-equal; NULL outputs skipped.
-The measured K and K' are printed (EXPERIMENTS.md 8.18 records them)."""
+* A workgroup that walks several tiles, at every lanes-per-row of the plan above 8 (``norm_harness.walk`` says where a walk begins and, backward,
+  asserts it from the workspace query): backward a second and a third tile and three full sweeps by the bounds above; forward one row past one
+  or two sweeps, the long call's rows byte for byte those of a call of its 37 distinct rows, which is held to float64, and the state that of the
+  x^ handed out.
+* A finite row whose centred squares overflow: rstd = 0, x^ = +-0, y = beta.
+The measured K and K' are printed (EXPERIMENTS.md 8.18 and 8.25 record them)."""
 import itertools
 
 import numpy as np
@@ -20,7 +25,7 @@ import torch
 import torch.nn.functional as F
 
 from fewbit_amd import cabi_x
-from norm_harness import DEV, EPS, FILL, SEED, UNIT, Guarded, allowance, options, seed_argument
+from norm_harness import DEV, EPS, FILL, SEED, UNIT, Guarded, allowance, backward_walks_on, forward_walks_on, options, seed_argument, state_rows, walks
 
 pytestmark = pytest.mark.gpu
 # 64 | 65, 128 | 129, 512 | 513, 1024 | 1025, 2048 | 2049, 4096 | 4097: one width on each side of every threshold of the plan (cabi_x.norm_plan)
@@ -209,6 +214,48 @@ def test_width_8_one_row_past_a_full_sweep_of_the_grid(dtype):
     host_state, xq, rstd_given, gy, gamma = backward_problem(rows, width, dtype, bits, True)
     dx, dgamma, dbeta = run_backward(host_state, rstd_given, gy, gamma, bits, 1)
     check_backward_values(xq, rstd_given, gy, gamma, dx.t.view(rows, width), dgamma.t, dbeta.t, 'the long sweep')
+
+
+@pytest.mark.parametrize('case', walks('backward'), ids=str)
+def test_backward_a_workgroup_walks_on_at_every_lanes_per_row(case):
+    """16 to 1024 lanes per row, 512 workgroups (asserted from the workspace query): one row past one and past two sweeps -- workgroup 0 alone walks on,
+    with one live row in a tile of dead lanes; its third tile writes the slots of the first again -- and three full sweeps.  The column accumulators
+    are carried across the tiles into the direct store (1 row per tile), the LDS column loop (2 or 4 rows per tile: more than one trip) or the plain
+    one, and 512 partials per column enter the column sums"""
+    backward_walks_on(case, backward_problem, run_backward, check_backward_values)
+
+
+@pytest.mark.parametrize('case', walks('forward'), ids=str)
+def test_forward_a_workgroup_walks_on_at_every_lanes_per_row(case):
+    """16 to 256 lanes per row and 1, 2 or 4 blocks per lane, one row past one or two sweeps of the 16384 workgroups (norm_harness.forward_walks_on)"""
+    forward_walks_on(case, inputs, run_forward, check_forward_values)
+
+
+@pytest.mark.parametrize('dtype', (torch.float32, torch.bfloat16), ids=ids)
+def test_a_finite_row_whose_centred_squares_overflow_gives_rstd_0_and_y_beta(dtype):
+    """A row of alternating +-2^66 at an even width: its sum is exactly 0, so the mean is 0 and only the squares of the centred row overflow.
+    var = inf, rstd = 0, x^ = +-0 (nothing is NaN, no group is poisoned), y = beta; backward from that state: dx of the row is 0, dgamma is
+    finite and the bytes of the same call without the row's gy.  Every other row has the bytes of a run where the row holds ordinary values"""
+    rows, width, bits, at = 5, 200, 4, 2
+    clean, gamma, beta = inputs(rows, width, dtype, 5)
+    x = clean.clone()
+    x[at] = (2.0**66 * (1 - 2 * (torch.arange(width) % 2))).to(dtype)
+    gy = torch.randn(rows, width, generator=torch.Generator().manual_seed(11)).to(dtype)
+    others = [r for r in range(rows) if r != at]
+    y, rstd, state, xhat = run_forward(x, gamma, beta, bits, SEED, 0)
+    y0, rstd0, state0, xhat0 = run_forward(clean, gamma, beta, bits, SEED, 0)
+    assert float(rstd.t[at]) == 0.0 and not bool(xhat.t.view(rows, width)[at].any()) and torch.equal(y.t.view(rows, width)[at].cpu(), beta)
+    xq = cabi_x.norm_state_unpack_host(state.t.cpu(), rows, width, bits)
+    assert not bool(torch.isnan(xq).any()) and not bool(xq[at].any())
+    assert all(torch.equal(a[others], b[others]) for a, b in zip(state_rows(state.t, rows, width), state_rows(state0.t, rows, width)))
+    for a, b in ((y, y0), (xhat, xhat0), (rstd, rstd0)):
+        assert torch.equal(a.t.view(rows, -1)[others].view(torch.uint8), b.t.view(rows, -1)[others].view(torch.uint8))
+    dx, dgamma, dbeta = run_backward(state.t, rstd.t, gy, gamma, bits, 0)
+    dx0 = run_backward(state0.t, rstd0.t, gy, gamma, bits, 0)[0]
+    assert not bool(dx.t.view(rows, width)[at].any()) and torch.equal(dx.t.view(rows, width)[others], dx0.t.view(rows, width)[others])
+    without = gy.clone()
+    without[at] = 0
+    assert bool(torch.isfinite(dgamma.t).all()) and torch.equal(run_backward(state.t, rstd.t, without, gamma, bits, 0)[1].raw, dgamma.raw)
 
 
 @pytest.mark.parametrize('bits', BITS)

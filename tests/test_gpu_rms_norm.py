@@ -15,8 +15,11 @@ a device word.
   ``u |dx| + K' 2^-24 rstd (|g^| + |x^q| mean|g^ x^q|)``, K' measured the same way; dgamma within ``(rows + 3) 2^-24 sum_r |gy x^q|``, the bound
   of a fixed-order fp32 sum of `rows` rounded products; two runs byte-equal; NULL outputs skipped, and without dgamma the workspace untouched.
 * A workgroup that walks several tiles with ONE row sum per tile through LDS (rows of 520 elements, 128 lanes per row): the slots of the row
-  sum alternate between tiles, which the sweeps of 2 and of 3 tiles per workgroup would show if they did not.
-The measured K and K' are printed (EXPERIMENTS.md 8.19 records them)."""
+  sum alternate between tiles, which the sweeps of 2 and of 3 tiles per workgroup would show if they did not.  The same at every other
+  lanes-per-row of the plan above 8 -- the row sum of 4, 8 and 16 waves, 2 and 4 blocks per lane forward -- by the method of tests/test_gpu_norm.py
+  (``norm_harness.walk``, ``backward_walks_on``, ``forward_walks_on``).
+* A finite row whose sum of squares overflows: rstd = 0, x^ = y = +-0, no group poisoned.
+The measured K and K' are printed (EXPERIMENTS.md 8.19 and 8.25 record them)."""
 import itertools
 
 import numpy as np
@@ -25,7 +28,7 @@ import torch
 import torch.nn.functional as F
 
 from fewbit_amd import cabi_x
-from norm_harness import DEV, EPS, FILL, SEED, UNIT, Guarded, allowance, options, seed_argument
+from norm_harness import DEV, EPS, FILL, SEED, UNIT, Guarded, allowance, backward_walks_on, forward_walks_on, options, seed_argument, state_rows, walks
 
 pytestmark = pytest.mark.gpu
 # 64 | 65, 128 | 129, 512 | 513, 1024 | 1025, 2048 | 2049, 4096 | 4097: one width on each side of every threshold of the plan (cabi_x.norm_plan)
@@ -236,6 +239,51 @@ def test_forward_width_520_a_workgroup_walks_on_with_one_row_sum_through_lds(row
     again = run_forward(x, gamma, bits, SEED, 0)
     assert all(torch.equal(a.raw, b.raw) for a, b in zip(again, (y, rstd, state, xhat)))
     print(f'{rows} x {width}: K(x^) = {k[0]:.2f}, K(rstd) = {k[1]:.2f}; plain fp32 torch ops: {k[2]:.2f}, {k[3]:.2f}')
+
+
+@pytest.mark.parametrize('case', walks('backward', 1), ids=str)
+def test_backward_a_workgroup_walks_on_at_every_lanes_per_row(case):
+    """16 to 1024 lanes per row, 512 workgroups (asserted from the workspace query): one row past one and past two sweeps -- workgroup 0 alone walks on,
+    with one live row in a tile of dead lanes; on its third tile the ONE row sum of 4, 8 or 16 waves writes the slots of the first again -- and three
+    full sweeps.  The column accumulators are carried across the tiles into the direct store (1 row per tile), the LDS column loop (2 or 4 rows
+    per tile: more than one trip) or the plain one, and 512 partials per column enter the column sums"""
+    backward_walks_on(case, backward_problem, run_backward, check_backward_values)
+
+
+@pytest.mark.parametrize('case', walks('forward', 1), ids=str)
+def test_forward_a_workgroup_walks_on_at_every_lanes_per_row(case):
+    """16 to 256 lanes per row and 1, 2 or 4 blocks per lane, one row past one or two sweeps of the 16384 workgroups (norm_harness.forward_walks_on)"""
+    forward_walks_on(case, inputs, run_forward, check_forward_values)
+
+
+@pytest.mark.parametrize('dtype', (torch.float32, torch.bfloat16), ids=ids)
+def test_a_finite_row_whose_sum_of_squares_overflows_gives_rstd_0_and_zeros(dtype):
+    """The header: "a finite row whose fp32 sum of squares overflows gives rstd = 0 and x^ = y = +-0".  One row of values of either sign and of
+    size 2^66 .. 2^67 among ordinary rows: rstd = 0, x^ and y are zeros, no group is poisoned (the host decode is 0, not NaN); backward from that
+    state: dx of the row is 0, dgamma is finite and the bytes of the same call without the row's gy.  Every other row has the bytes of a run where
+    the row holds ordinary values"""
+    rows, width, bits, at = 5, 200, 4, 2
+    clean, gamma = inputs(rows, width, dtype, 5)
+    g = torch.Generator().manual_seed(9)
+    x = clean.clone()
+    x[at] = (2.0**66 * (1 + torch.rand(width, generator=g)) * (1 - 2 * torch.randint(0, 2, (width, ), generator=g))).to(dtype)
+    gy = torch.randn(rows, width, generator=g).to(dtype)
+    others = [r for r in range(rows) if r != at]
+    assert bool(torch.isfinite(x).all()) and bool(torch.isinf(x[at].float().square().sum()))
+    y, rstd, state, xhat = run_forward(x, gamma, bits, SEED, 0)
+    y0, rstd0, state0, xhat0 = run_forward(clean, gamma, bits, SEED, 0)
+    assert float(rstd.t[at]) == 0.0 and not bool(xhat.t.view(rows, width)[at].any()) and not bool(y.t.view(rows, width)[at].any())
+    xq = cabi_x.norm_state_unpack_host(state.t.cpu(), rows, width, bits)
+    assert not bool(torch.isnan(xq).any()) and not bool(xq[at].any())
+    assert all(torch.equal(a[others], b[others]) for a, b in zip(state_rows(state.t, rows, width), state_rows(state0.t, rows, width)))
+    for a, b in ((y, y0), (xhat, xhat0), (rstd, rstd0)):
+        assert torch.equal(a.t.view(rows, -1)[others].view(torch.uint8), b.t.view(rows, -1)[others].view(torch.uint8))
+    dx, dgamma = run_backward(state.t, rstd.t, gy, gamma, bits, 0)
+    dx0 = run_backward(state0.t, rstd0.t, gy, gamma, bits, 0)[0]
+    assert not bool(dx.t.view(rows, width)[at].any()) and torch.equal(dx.t.view(rows, width)[others], dx0.t.view(rows, width)[others])
+    without = gy.clone()
+    without[at] = 0
+    assert bool(torch.isfinite(dgamma.t).all()) and torch.equal(run_backward(state.t, rstd.t, without, gamma, bits, 0)[1].raw, dgamma.raw)
 
 
 @pytest.mark.parametrize('bits', BITS)

@@ -15,7 +15,8 @@ import torch.nn.functional as F
 
 import fewbit_amd as fewbit
 from fewbit_amd import cabi, cabi_x, norm
-from norm_harness import LAYER_NORM as KIND, M32, input_gradient_averages_out, order_keys, philox, saved_by, weight_gradient_is_unbiased
+import norm_harness
+from norm_harness import LAYER_NORM as KIND, M32, input_gradient_averages_out, order_keys, philox, saved_by, walk, walks, weight_gradient_is_unbiased
 
 ROOT = Path(__file__).resolve().parents[1]
 NORM_SYMBOLS = ('fewbit_hipx_norm_state_bytes', 'fewbit_hipx_norm_workspace', 'fewbit_hipx_norm_state_host', 'fewbit_hipx_norm_state_unpack_host',
@@ -124,6 +125,31 @@ def test_state_bytes_is_the_formula():
     assert cabi_x.norm_workspace_bytes(0, 8) == 0 and cabi_x.norm_workspace_bytes(4, 8193) == 0
     assert [cabi_x.norm_plan(w) for w in (64, 65, 128, 129, 512, 513, 1024, 1025, 2048, 2049, 4096, 4097, 8192)] == [
         (8, 1), (16, 1), (16, 1), (64, 1), (64, 1), (128, 1), (128, 1), (256, 1), (256, 1), (256, 2), (256, 2), (256, 4), (256, 4)]
+
+
+def test_the_walks_of_the_gpu_tests_begin_where_the_tables_say_and_rotate_over_every_dtype_and_code_width():
+    """norm_harness.walk / walks, which tests/test_gpu_norm.py, test_gpu_rms_norm.py and test_gpu_add_norm.py stand on: the row counts are the ones
+    written out here; a backward walk is refused by the helper where the library's workspace query says the grid is not at its cap; and the
+    plain cases of either kind hold every (plan, dtype) and (plan, bits) pair, every width and every sweep"""
+    assert [walk(w, 'backward', t, e) for w, t, e in ((72, 2, 1), (128, 3, 1), (136, 2, 1), (192, 3, 1), (1032, 2, 1), (2048, 3, 1), (2048, 3, None), (2056, 2, 1),
+                                                      (4096, 3, 1), (4096, 3, None), (4104, 2, 1), (4097, 3, 1), (8192, 3, None))] == [
+        32769, 65537, 8193, 16385, 2049, 4097, 3 * 2048, 1025, 2049, 3 * 1024, 513, 1025, 3 * 512]
+    assert [walk(w, 'forward', t, 1) for w, t in ((128, 2), (192, 2), (136, 2), (1088, 2), (1032, 3), (2112, 2), (4160, 2))] == [
+        16 * 16384 + 1, 4 * 16384 + 1, 4 * 16384 + 1, 16384 + 1, 2 * 16384 + 1, 16384 + 1, 16384 + 1]
+    for width, tiles, extra in ((2048, 1, 1), (2048, 2, 0), (2048, 2, 2049)):
+        with pytest.raises(AssertionError):
+            walk(width, 'backward', tiles, extra)
+    for direction, plans, widths in (('backward', 5, 11), ('forward', 5, 7)):
+        for shift in (0, 1):
+            cases = list(walks(direction, shift))
+            assert all(c.rows(direction) > 0 for c in cases)
+            assert len({(c.lanes, c.blocks) for c in cases}) == plans and len({c.width for c in cases}) == widths
+            dtypes, bits = {(c.lanes, c.blocks, c.dtype) for c in cases}, {(c.lanes, c.blocks, c.bits) for c in cases}
+            assert len(bits) == 3 * plans and len(dtypes) == 3 * plans - (direction == 'forward')      # (four blocks per lane: the two 16-bit dtypes)
+            assert all(c.dtype != torch.float32 for c in cases if c.blocks == 4) and all(c.off == 1 for c in cases if c.width == 4097)
+    assert len(list(walks('backward'))) == 29 and len(list(walks('forward'))) == 16
+    assert {(c.width, c.tiles, c.extra) for c in walks('backward')} == {(w, t, e) for _, ws, sweeps in norm_harness.BACKWARD_WALKS for w in ws for t, e in sweeps}
+    assert {(c.width, c.tiles, c.extra) for c in walks('forward')} == {(w, t, e) for _, ws, sweeps in norm_harness.FORWARD_WALKS for w in ws for t, e in sweeps}
 
 
 @pytest.mark.parametrize('width', WIDTHS)
