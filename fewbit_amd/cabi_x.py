@@ -432,13 +432,39 @@ def quant_bytes(n: int, bits: int) -> int:
     return lib().fewbit_hipx_quant_bytes(n, bits)
 
 
-def _quant_size(n: int, bits: int, name: str) -> int:
+_QUANT = (quant_bytes, 'no packed form for {} elements (1 .. 2^36 are supported)')
+
+
+def _size(family, name: str, bits: int, *extents: int) -> int:
+    """Bytes of what ``name`` keeps at ``extents``: ``family`` is (the library's size query, the refusal of a size of zero in the family's own words)"""
+    query, refusal = family
     if bits not in QUANT_BITS:
         raise FewbitHipError(f'{name}: bits must be 2, 4 or 8 (got {bits})')
-    need = quant_bytes(n, bits)
-    if n != 0 and need == 0:
-        raise FewbitHipError(f'{name}: no packed form for {n} elements (1 .. 2^36 are supported)')
+    need = query(*extents, bits)
+    if extents[0] != 0 and need == 0:
+        raise FewbitHipError(f'{name}: {refusal.format(*extents)}')
     return need
+
+
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return None if t is None else t.data_ptr()
+
+
+def _state_to_write(state: Optional[torch.Tensor], keep: bool, need: int, device, what: str = 'state') -> Optional[torch.Tensor]:
+    """the state buffer of a forward: a new one of ``need`` bytes, or the given one checked (the library checks its size), or None with ``keep=False``"""
+    if not keep:
+        return None
+    if state is None:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    if state.dtype != torch.uint8 or state.dim() != 1 or not state.is_contiguous():
+        raise FewbitHipError(f'{what} must be a contiguous 1-D uint8 tensor')
+    return state
+
+
+def _state_to_read(state: torch.Tensor, need: int, what: str = 'state', host: bool = False) -> None:
+    """the state given to a backward or, with ``host``, to a host decode"""
+    if (host and state.device.type != 'cpu') or state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < need:
+        raise FewbitHipError(f'{what} must be a contiguous {"host " if host else ""}uint8 tensor of at least {need} bytes')
 
 
 def quant_pack_host(values: torch.Tensor, seed: int, bits: int) -> torch.Tensor:
@@ -446,16 +472,14 @@ def quant_pack_host(values: torch.Tensor, seed: int, bits: int) -> torch.Tensor:
     values of a 16-bit tensor as ``.float()``) -> a host uint8 tensor of ``quant_bytes(values.numel(), bits)`` bytes.  The definition is
     include/fewbit_hipx.h's ("the packed form of a seed"); no GPU needed."""
     x = values.detach().to(device='cpu', dtype=torch.float32).contiguous()
-    out = torch.empty(_quant_size(x.numel(), bits, 'quant_pack_host'), dtype=torch.uint8)
+    out = torch.empty(_size(_QUANT, 'quant_pack_host', bits, x.numel()), dtype=torch.uint8)
     _check(lib().fewbit_hipx_quant_pack_host(x.data_ptr(), x.numel(), bits, seed & 0xffffffffffffffff, out.data_ptr()))
     return out
 
 
 def quant_unpack_host(packed: torch.Tensor, n: int, bits: int) -> torch.Tensor:
     """The fp32 decode of a packed buffer on the host: a float32 tensor of ``n`` elements (``fma(code, step, lo)``; a poisoned group: NaN)"""
-    need = _quant_size(n, bits, 'quant_unpack_host')
-    if packed.device.type != 'cpu' or packed.dtype != torch.uint8 or not packed.is_contiguous() or packed.numel() < need:
-        raise FewbitHipError(f'packed must be a contiguous host uint8 tensor of at least {need} bytes')
+    _state_to_read(packed, _size(_QUANT, 'quant_unpack_host', bits, n), 'packed', host=True)
     out = torch.empty(n, dtype=torch.float32)
     _check(lib().fewbit_hipx_quant_unpack_host(packed.data_ptr(), n, bits, out.data_ptr()))
     return out
@@ -474,13 +498,10 @@ def quant_pack(x: torch.Tensor, seed, bits: int, out: Optional[torch.Tensor] = N
         raise FewbitHipError(f'unsupported dtype {x.dtype}')
     if not x.is_contiguous():
         raise FewbitHipError('x must be contiguous')
-    need = _quant_size(x.numel(), bits, 'quant_pack')
+    need = _size(_QUANT, 'quant_pack', bits, x.numel())
     value, word, others = _seed_arguments(seed)
     with _on(x.device):
-        if out is None:
-            out = torch.empty(need, dtype=torch.uint8, device=x.device)
-        elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
-            raise FewbitHipError('out must be a contiguous 1-D uint8 tensor')
+        out = _state_to_write(out, True, need, x.device, 'out')
         _same_device(x, out, *others)
         _check(lib().fewbit_hipx_quant_pack(DTYPES[x.dtype], x.data_ptr(), x.numel(), bits, value, word, out.data_ptr(), out.numel(),
                                             _stream(stream, x.device)))
@@ -496,9 +517,7 @@ def quant_unpack(packed: torch.Tensor, n: int, bits: int, dtype: torch.dtype, ou
         raise FewbitHipError(f'packed must live on the GPU (got {packed.device})')
     if dtype not in DTYPES:
         raise FewbitHipError(f'unsupported dtype {dtype}')
-    need = _quant_size(n, bits, 'quant_unpack')
-    if packed.dtype != torch.uint8 or not packed.is_contiguous() or packed.numel() < need:
-        raise FewbitHipError(f'packed must be a contiguous uint8 tensor of at least {need} bytes')
+    _state_to_read(packed, _size(_QUANT, 'quant_unpack', bits, n), 'packed')
     with _on(packed.device):
         if out is None:
             out = torch.empty(n, dtype=dtype, device=packed.device)
@@ -539,13 +558,7 @@ def norm_workspace_bytes(rows: int, width: int) -> int:
     return lib().fewbit_hipx_norm_workspace(rows, width)
 
 
-def _norm_size(rows: int, width: int, bits: int, name: str) -> int:
-    if bits not in QUANT_BITS:
-        raise FewbitHipError(f'{name}: bits must be 2, 4 or 8 (got {bits})')
-    need = norm_state_bytes(rows, width, bits)
-    if rows != 0 and need == 0:
-        raise FewbitHipError(f'{name}: no state for {rows} rows of {width} elements (widths 1 .. {NORM_MAX_WIDTH}, rows * width <= 2^36)')
-    return need
+_NORM = (norm_state_bytes, f'no state for {{}} rows of {{}} elements (widths 1 .. {NORM_MAX_WIDTH}, rows * width <= 2^36)')
 
 
 def norm_state_host(xhat: torch.Tensor, seed: int, bits: int) -> torch.Tensor:
@@ -558,16 +571,14 @@ def norm_state_host(xhat: torch.Tensor, seed: int, bits: int) -> torch.Tensor:
     rows, width = x.shape
     if rows and not 1 <= width <= NORM_MAX_WIDTH:
         _check(lib().fewbit_hipx_norm_state_host(None, rows, width, bits, 0, None))        # (the library words the refusal)
-    out = torch.empty(_norm_size(rows, width, bits, 'norm_state_host'), dtype=torch.uint8)
+    out = torch.empty(_size(_NORM, 'norm_state_host', bits, rows, width), dtype=torch.uint8)
     _check(lib().fewbit_hipx_norm_state_host(x.data_ptr(), rows, width, bits, seed & 0xffffffffffffffff, out.data_ptr()))
     return out
 
 
 def norm_state_unpack_host(state: torch.Tensor, rows: int, width: int, bits: int) -> torch.Tensor:
     """The fp32 decode of a state on the host: a float32 tensor ``rows x width`` (``fma(code, step, lo)``; a poisoned group: NaN)"""
-    need = _norm_size(rows, width, bits, 'norm_state_unpack_host')
-    if state.device.type != 'cpu' or state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < need:
-        raise FewbitHipError(f'state must be a contiguous host uint8 tensor of at least {need} bytes')
+    _state_to_read(state, _size(_NORM, 'norm_state_unpack_host', bits, rows, width), host=True)
     out = torch.empty((rows, width), dtype=torch.float32)
     _check(lib().fewbit_hipx_norm_state_unpack_host(state.data_ptr(), rows, width, bits, out.data_ptr()))
     return out
@@ -599,51 +610,73 @@ def _norm_out(t: Optional[torch.Tensor], shape, dtype: torch.dtype, device, what
     return t
 
 
-def _norm_forward(centred: bool, x, gamma, beta, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream):
-    """the forward call of either norm: ``centred`` is the layer norm, whose entry point alone takes ``beta`` (None for the RMS norm)"""
-    name = 'layer_norm_forward' if centred else 'rms_norm_forward'
+def _like(t: Optional[torch.Tensor], x: torch.Tensor, what: str) -> Optional[torch.Tensor]:
+    if t is not None and (t.dtype != x.dtype or t.shape != x.shape or not t.is_contiguous()):
+        raise FewbitHipError(f'{what} must be a contiguous tensor of the shape and dtype of {"x" if what in ("residual", "h") else "gy"}')
+    return t
+
+
+def _norm_forward(centred: bool, x, gamma, beta, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream, add=None):
+    """The forward call of either norm -> ``(y, h, rstd, state, xhat)``: ``centred`` is the layer norm, whose entry point alone takes ``beta`` (None for
+    the RMS norm).  ``add``: None, or ``(residual, p, want_h, h)`` for the entry point with ``residual + dropout(x)`` fused in front, which alone
+    evaluates a threshold, needs the seed for its mask too, and writes ``h``."""
+    residual, p, want_h, h = add or (None, None, False, None)
     rows, width = _norm_rows(x, 'x')
+    if add is not None:
+        _like(residual, x, 'residual')
     gp = _norm_vector(gamma, x, 'gamma')
     pointers = (gp, _norm_vector(beta, x, 'beta')) if centred else (gp, )
-    need = _norm_size(rows, width, bits, name) if keep else 0
-    value, word, others = _seed_arguments(seed) if keep else (0, None, ())
+    threshold = 0 if add is None else dropout_threshold(p)
+    name = ('layer_norm_forward' if centred else 'rms_norm_forward') if add is None else ('add_layer_norm_forward' if centred else 'add_rms_norm_forward')
+    need = _size(_NORM, name, bits, rows, width) if keep else 0
+    value, word, others = _seed_arguments(seed) if keep or threshold else (0, None, ())
     with _on(x.device):
         y = _norm_out(y, (rows, width), x.dtype, x.device, 'y')
         rstd = _norm_out(rstd, (rows, ), torch.float32, x.device, 'rstd')
-        if keep and state is None:
-            state = torch.empty(need, dtype=torch.uint8, device=x.device)
-        elif keep and (state.dtype != torch.uint8 or state.dim() != 1 or not state.is_contiguous()):
-            raise FewbitHipError('state must be a contiguous 1-D uint8 tensor')
-        elif not keep:
-            state = None
+        if want_h or h is not None:
+            h = _norm_out(h, (rows, width), x.dtype, x.device, 'h')
+        state = _state_to_write(state, keep, need, x.device)
         if want_xhat or xhat is not None:
             xhat = _norm_out(xhat, (rows, width), torch.float32, x.device, 'xhat')
-        _same_device(x, y, rstd, *others, *(t for t in (gamma, beta, state, xhat) if t is not None))
-        _check(getattr(lib(), f'fewbit_hipx_{name}')(DTYPES[x.dtype], x.data_ptr(), rows, width, *pointers, float(eps), bits, value, word,
-                                                     y.data_ptr(), rstd.data_ptr(), None if state is None else state.data_ptr(),
-                                                     0 if state is None else state.numel(), None if xhat is None else xhat.data_ptr(), _stream(stream, x.device)))
-    return y, rstd, state, xhat
+        # (what the fused entry point takes besides: the residual behind x, the threshold and h around y)
+        read = (x.data_ptr(), ) if add is None else (x.data_ptr(), residual.data_ptr())
+        written = (y.data_ptr(), ) if add is None else (threshold, y.data_ptr(), _ptr(h))
+        _same_device(x, *(() if add is None else (residual, )), y, rstd, *others, *(t for t in (gamma, beta, h, state, xhat) if t is not None))
+        _check(getattr(lib(), 'fewbit_hipx_' + name)(DTYPES[x.dtype], *read, rows, width, *pointers, float(eps), bits, value, word, *written, rstd.data_ptr(),
+                                                     None if state is None else state.data_ptr(), 0 if state is None else state.numel(),
+                                                     None if xhat is None else xhat.data_ptr(), _stream(stream, x.device)))
+    return y, h, rstd, state, xhat
 
 
-def _norm_backward(centred: bool, gy, state, rstd, gamma, bits, want, outs, workspace, stream):
-    """the backward call of either norm: ``want`` and ``outs`` are (dx, dgamma, dbeta) for the layer norm (``centred``) and (dx, dgamma) for the RMS norm"""
-    name = 'layer_norm_backward' if centred else 'rms_norm_backward'
+def _norm_backward(centred: bool, gy, state, rstd, gamma, bits, want, outs, workspace, stream, add=None):
+    """The backward call of either norm: ``want`` and ``outs`` are (dx, dgamma, dbeta) for the layer norm (``centred``) and (dx, dgamma) for the RMS norm.
+    ``add``: None, or ``(gh, seed, p)`` for the backward of the fused entry point, where (dres, dbranch) stand in the place of dx and ``want`` may be
+    None: everything, ``dbranch`` only with a mask."""
+    gh, seed, p = add or (None, 0, None)
     rows, width = _norm_rows(gy, 'gy')
+    if gh is not None:
+        _like(gh, gy, 'gh')
     gp = _norm_vector(gamma, gy, 'gamma')
-    need = _norm_size(rows, width, bits, name)
-    if state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < need:
-        raise FewbitHipError(f'state must be a contiguous uint8 tensor of at least {need} bytes')
+    threshold = 0 if add is None else dropout_threshold(p)
+    if want is None:
+        want = (True, threshold > 0, True, True)[:4 if centred else 3]
+    name = ('layer_norm_backward' if centred else 'rms_norm_backward') if add is None else ('add_layer_norm_backward' if centred else 'add_rms_norm_backward')
+    _state_to_read(state, _size(_NORM, name, bits, rows, width))
     if rstd.dtype != torch.float32 or rstd.numel() != rows or not rstd.is_contiguous():
         raise FewbitHipError(f'rstd must be a contiguous float32 tensor of {rows} elements')
+    value, word, others = _seed_arguments(seed) if threshold else (0, None, ())
     with _on(gy.device):
-        shapes = (((rows, width), gy.dtype, 'dx'), ((width, ), torch.float32, 'dgamma'), ((width, ), torch.float32, 'dbeta'))[:3 if centred else 2]
+        matrix, sums = ((rows, width), gy.dtype), (((width, ), torch.float32, 'dgamma'), ((width, ), torch.float32, 'dbeta'))
+        shapes = ((*matrix, 'dx'), *sums) if add is None else ((*matrix, 'dres'), (*matrix, 'dbranch'), *sums)
         outs = tuple(_norm_out(t, shape, dtype, gy.device, what) if wanted else None for t, wanted, (shape, dtype, what) in zip(outs, want, shapes))
-        if any(want[1:]) and workspace is None:
+        if any(want[1 if add is None else 2:]) and workspace is None:
             workspace = torch.empty(norm_workspace_bytes(rows, width), dtype=torch.uint8, device=gy.device)
-        _same_device(gy, state, rstd, *(t for t in (gamma, *outs, workspace) if t is not None))
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _check(getattr(lib(), f'fewbit_hipx_{name}')(DTYPES[gy.dtype], gy.data_ptr(), state.data_ptr(), rstd.data_ptr(), gp, rows, width, bits, *map(ptr, outs),
-                                                     ptr(workspace), 0 if workspace is None else workspace.numel(), _stream(stream, gy.device)))
+        _same_device(gy, state, rstd, *others, *(t for t in (gh, gamma, *outs, workspace) if t is not None))
+        # (what the fused entry point takes besides: gh behind gy, the seed and the threshold behind bits)
+        read = (gy.data_ptr(), ) if add is None else (gy.data_ptr(), _ptr(gh))
+        mask = () if add is None else (value, word, threshold)
+        _check(getattr(lib(), 'fewbit_hipx_' + name)(DTYPES[gy.dtype], *read, state.data_ptr(), rstd.data_ptr(), gp, rows, width, bits, *mask, *map(_ptr, outs),
+                                                     _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream(stream, gy.device)))
     return outs
 
 
@@ -656,7 +689,8 @@ def layer_norm_forward(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Opt
     fp32 normalized rows the kernel quantized, only with ``want_xhat`` (else None).  ``keep=False``: the plain forward, ``state`` is None and
     nothing but ``y`` and ``rstd`` is written -- the same bytes as with a state.  ``seed``: an int, or a one-element int64 tensor on the device
     of ``x`` that is read when the kernel runs (``cabi.next_sketch_seed``).  ``y``, ``rstd``, ``state``, ``xhat``: buffers to write into."""
-    return _norm_forward(True, x, gamma, beta, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream)
+    y, _, rstd, state, xhat = _norm_forward(True, x, gamma, beta, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream)
+    return y, rstd, state, xhat
 
 
 def layer_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor], bits: int, want=(True, True, True),
@@ -677,7 +711,8 @@ def rms_norm_forward(x: torch.Tensor, gamma: Optional[torch.Tensor], eps: float,
     ``rstd = 1 / sqrt(mean(x^2) + eps)``, ``xhat = x * rstd``, ``y = xhat * gamma`` rounded once, ``state`` the state of these ``xhat``
     (``norm_state_bytes`` bytes; ``norm_state_host`` gives the same bytes from ``xhat``).  ``eps`` is a number (``F.rms_norm``'s default
     is ``torch.finfo(x.dtype).eps``)."""
-    return _norm_forward(False, x, gamma, None, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream)
+    y, _, rstd, state, xhat = _norm_forward(False, x, gamma, None, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream)
+    return y, rstd, state, xhat
 
 
 def rms_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor], bits: int, want=(True, True),
@@ -691,71 +726,6 @@ def rms_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor,
 
 
 # ---- residual + dropout(x) fused in front of either norm (include/fewbit_hipx.h, "The sum of a seed in front of the norm") ------------------------------
-def _like(t: Optional[torch.Tensor], x: torch.Tensor, what: str) -> Optional[torch.Tensor]:
-    if t is not None and (t.dtype != x.dtype or t.shape != x.shape or not t.is_contiguous()):
-        raise FewbitHipError(f'{what} must be a contiguous tensor of the shape and dtype of {"x" if what in ("residual", "h") else "gy"}')
-    return t
-
-
-def _add_norm_forward(centred: bool, x, residual, gamma, beta, eps, p, bits, seed, keep, want_h, want_xhat, y, h, rstd, state, xhat, stream):
-    name = 'add_layer_norm_forward' if centred else 'add_rms_norm_forward'
-    rows, width = _norm_rows(x, 'x')
-    _like(residual, x, 'residual')
-    gp = _norm_vector(gamma, x, 'gamma')
-    pointers = (gp, _norm_vector(beta, x, 'beta')) if centred else (gp, )
-    threshold = dropout_threshold(p)
-    need = _norm_size(rows, width, bits, name) if keep else 0
-    value, word, others = _seed_arguments(seed) if keep or threshold else (0, None, ())
-    with _on(x.device):
-        y = _norm_out(y, (rows, width), x.dtype, x.device, 'y')
-        rstd = _norm_out(rstd, (rows, ), torch.float32, x.device, 'rstd')
-        if want_h or h is not None:
-            h = _norm_out(h, (rows, width), x.dtype, x.device, 'h')
-        if keep and state is None:
-            state = torch.empty(need, dtype=torch.uint8, device=x.device)
-        elif keep and (state.dtype != torch.uint8 or state.dim() != 1 or not state.is_contiguous()):
-            raise FewbitHipError('state must be a contiguous 1-D uint8 tensor')
-        elif not keep:
-            state = None
-        if want_xhat or xhat is not None:
-            xhat = _norm_out(xhat, (rows, width), torch.float32, x.device, 'xhat')
-        _same_device(x, residual, y, rstd, *others, *(t for t in (gamma, beta, h, state, xhat) if t is not None))
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _check(getattr(lib(), f'fewbit_hipx_{name}')(DTYPES[x.dtype], x.data_ptr(), residual.data_ptr(), rows, width, *pointers, float(eps), bits, value, word,
-                                                     threshold, y.data_ptr(), ptr(h), rstd.data_ptr(), ptr(state), 0 if state is None else state.numel(), ptr(xhat),
-                                                     _stream(stream, x.device)))
-    return y, h, rstd, state, xhat
-
-
-def _add_norm_backward(centred: bool, gy, state, rstd, gamma, bits, seed, p, gh, want, outs, workspace, stream):
-    """``want`` and ``outs``: (dres, dbranch, dgamma, dbeta) for the layer norm and (dres, dbranch, dgamma) for the RMS norm"""
-    name = 'add_layer_norm_backward' if centred else 'add_rms_norm_backward'
-    rows, width = _norm_rows(gy, 'gy')
-    _like(gh, gy, 'gh')
-    gp = _norm_vector(gamma, gy, 'gamma')
-    threshold = dropout_threshold(p)
-    if want is None:
-        want = (True, threshold > 0, True, True)[:4 if centred else 3]
-    need = _norm_size(rows, width, bits, name)
-    if state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < need:
-        raise FewbitHipError(f'state must be a contiguous uint8 tensor of at least {need} bytes')
-    if rstd.dtype != torch.float32 or rstd.numel() != rows or not rstd.is_contiguous():
-        raise FewbitHipError(f'rstd must be a contiguous float32 tensor of {rows} elements')
-    value, word, others = _seed_arguments(seed) if threshold else (0, None, ())
-    with _on(gy.device):
-        shapes = (((rows, width), gy.dtype, 'dres'), ((rows, width), gy.dtype, 'dbranch'), ((width, ), torch.float32, 'dgamma'),
-                  ((width, ), torch.float32, 'dbeta'))[:4 if centred else 3]
-        outs = tuple(_norm_out(t, shape, dtype, gy.device, what) if wanted else None for t, wanted, (shape, dtype, what) in zip(outs, want, shapes))
-        if any(want[2:]) and workspace is None:
-            workspace = torch.empty(norm_workspace_bytes(rows, width), dtype=torch.uint8, device=gy.device)
-        _same_device(gy, state, rstd, *others, *(t for t in (gh, gamma, *outs, workspace) if t is not None))
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _check(getattr(lib(), f'fewbit_hipx_{name}')(DTYPES[gy.dtype], gy.data_ptr(), ptr(gh), state.data_ptr(), rstd.data_ptr(), gp, rows, width, bits, value, word,
-                                                     threshold, *map(ptr, outs), ptr(workspace), 0 if workspace is None else workspace.numel(),
-                                                     _stream(stream, gy.device)))
-    return outs
-
-
 def add_layer_norm_forward(x: torch.Tensor, residual: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float, p: float = 0.0,
                            bits: int = 4, seed=0, keep: bool = True, want_h: bool = False, want_xhat: bool = False, y: Optional[torch.Tensor] = None,
                            h: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
@@ -765,7 +735,7 @@ def add_layer_norm_forward(x: torch.Tensor, residual: torch.Tensor, gamma: Optio
     (or a buffer ``h``), else None -- it is then never in memory.  ONE ``seed`` (an int, or a device word) gives the mask and the rounding.
     ``p``: the drop probability (``dropout_threshold``; below 1).  With a mask (threshold > 0) the width must be a multiple of 8: anything else
     is refused -- compose the two calls; without one every width 1 .. 8192 is served.  No output may overlap an input."""
-    return _add_norm_forward(True, x, residual, gamma, beta, eps, p, bits, seed, keep, want_h, want_xhat, y, h, rstd, state, xhat, stream)
+    return _norm_forward(True, x, gamma, beta, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream, (residual, p, want_h, h))
 
 
 def add_layer_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor], bits: int, seed=0, p: float = 0.0,
@@ -776,7 +746,7 @@ def add_layer_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.T
     backward's fp32 ``dx`` plus ``gh`` (the gradient arriving at ``h``, or None) rounded ONCE; ``dbranch``, the input's, is
     ``dropout_apply(dres, seed, p)``; ``dgamma`` / ``dbeta`` are ``layer_norm_backward``'s.  ``want``: which of the four (default: all; ``dbranch``
     only with a mask -- without one it is ``dres``, and asking for it is refused).  Two launches, one when neither sum is wanted."""
-    return _add_norm_backward(True, gy, state, rstd, gamma, bits, seed, p, gh, want, (dres, dbranch, dgamma, dbeta), workspace, stream)
+    return _norm_backward(True, gy, state, rstd, gamma, bits, want, (dres, dbranch, dgamma, dbeta), workspace, stream, (gh, seed, p))
 
 
 def add_rms_norm_forward(x: torch.Tensor, residual: torch.Tensor, gamma: Optional[torch.Tensor], eps: float, p: float = 0.0, bits: int = 4, seed=0,
@@ -784,14 +754,14 @@ def add_rms_norm_forward(x: torch.Tensor, residual: torch.Tensor, gamma: Optiona
                          rstd: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None, xhat: Optional[torch.Tensor] = None,
                          stream: Optional[int] = None):
     """``add_layer_norm_forward`` for the RMS norm (no ``beta``): ``rms_norm_forward`` of ``residual + dropout(x)`` in ONE launch, bit for bit"""
-    return _add_norm_forward(False, x, residual, gamma, None, eps, p, bits, seed, keep, want_h, want_xhat, y, h, rstd, state, xhat, stream)
+    return _norm_forward(False, x, gamma, None, eps, bits, seed, keep, want_xhat, y, rstd, state, xhat, stream, (residual, p, want_h, h))
 
 
 def add_rms_norm_backward(gy: torch.Tensor, state: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor], bits: int, seed=0, p: float = 0.0,
                           gh: Optional[torch.Tensor] = None, want=None, dres: Optional[torch.Tensor] = None, dbranch: Optional[torch.Tensor] = None,
                           dgamma: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None):
     """``add_layer_norm_backward`` for the RMS norm -> ``(dres, dbranch, dgamma)``"""
-    return _add_norm_backward(False, gy, state, rstd, gamma, bits, seed, p, gh, want, (dres, dbranch, dgamma), workspace, stream)
+    return _norm_backward(False, gy, state, rstd, gamma, bits, want, (dres, dbranch, dgamma), workspace, stream, (gh, seed, p))
 
 
 # ---- the product of a gated MLP that keeps its gate and its up in 2, 4 or 8 bits (fewbit_amd/csrc/fewbit_glu.hip) -------------------------------------
@@ -806,13 +776,7 @@ def glu_state_bytes(n: int, bits: int) -> int:
     return lib().fewbit_hipx_glu_state_bytes(n, bits)
 
 
-def _glu_size(n: int, bits: int, name: str) -> int:
-    if bits not in QUANT_BITS:
-        raise FewbitHipError(f'{name}: bits must be 2, 4 or 8 (got {bits})')
-    need = glu_state_bytes(n, bits)
-    if n != 0 and need == 0:
-        raise FewbitHipError(f'{name}: no state for {n} elements (1 .. 2^36 are supported)')
-    return need
+_GLU = (glu_state_bytes, 'no state for {} elements (1 .. 2^36 are supported)')
 
 
 def _glu_activation(activation: str) -> int:
@@ -830,7 +794,7 @@ def glu_state_host(gate: torch.Tensor, up: torch.Tensor, seed: int, bits: int) -
         raise FewbitHipError(f'gate and up must have one shape (got {tuple(gate.shape)} and {tuple(up.shape)})')
     g = gate.detach().to(device='cpu', dtype=torch.float32).contiguous()
     u = up.detach().to(device='cpu', dtype=torch.float32).contiguous()
-    out = torch.empty(_glu_size(g.numel(), bits, 'glu_state_host'), dtype=torch.uint8)
+    out = torch.empty(_size(_GLU, 'glu_state_host', bits, g.numel()), dtype=torch.uint8)
     _check(lib().fewbit_hipx_glu_state_host(g.data_ptr(), u.data_ptr(), g.numel(), bits, seed & 0xffffffffffffffff, out.data_ptr()))
     return out
 
@@ -863,20 +827,42 @@ def glu_forward(gate: torch.Tensor, up: torch.Tensor, activation: str = 'silu', 
         raise FewbitHipError('up must have the shape and dtype of gate')
     ld_up = _glu_rows(up, 'up')[2]
     act = _glu_activation(activation)
-    need = _glu_size(rows * width, bits, 'glu_forward') if keep else 0
+    need = _size(_GLU, 'glu_forward', bits, rows * width) if keep else 0
     value, word, others = _seed_arguments(seed) if keep else (0, None, ())
     with _on(gate.device):
         y = _norm_out(y, (rows, width), gate.dtype, gate.device, 'y')
-        if keep and state is None:
-            state = torch.empty(need, dtype=torch.uint8, device=gate.device)
-        elif keep and (state.dtype != torch.uint8 or state.dim() != 1 or not state.is_contiguous()):
-            raise FewbitHipError('state must be a contiguous 1-D uint8 tensor')
-        elif not keep:
-            state = None
+        state = _state_to_write(state, keep, need, gate.device)
         _same_device(gate, up, y, *others, *(() if state is None else (state, )))
         _check(lib().fewbit_hipx_glu_forward(DTYPES[gate.dtype], act, gate.data_ptr(), ld_gate, up.data_ptr(), ld_up, rows, width, bits, value, word, y.data_ptr(),
-                                             None if state is None else state.data_ptr(), 0 if state is None else state.numel(), _stream(stream, gate.device)))
+                                             _ptr(state), 0 if state is None else state.numel(), _stream(stream, gate.device)))
     return y, state
+
+
+def _glu_backward(name: str, gy: Optional[torch.Tensor], like: torch.Tensor, state, activation: str, bits: int, outputs, stream, act: Optional[int] = None):
+    """What the two backward entry points share, behind what each refuses first: ``like`` carries the shape and the dtype (``gy``, or the product buffer
+    where there is no ``gy``); ``outputs``: (buffer or None, wanted, name) of every output the entry point ``name`` writes, in its order; ``act``: the
+    activation where the caller has evaluated it already"""
+    if gy is not None and (gy.dim() != 2 or not gy.is_contiguous()):
+        raise FewbitHipError('gy must be a contiguous 2-D tensor')
+    rows, width, _ = _glu_rows(like, 'product' if gy is None else 'gy')
+    if act is None:
+        act = _glu_activation(activation)
+    _state_to_read(state, _size(_GLU, name, bits, rows * width))
+    with _on(like.device):
+        outs, written = [], []                                  # (written: pointer and row stride of every output, as the entry point takes them)
+        for t, wanted, what in outputs:
+            if not wanted:
+                t = None
+            elif t is None:
+                t = torch.empty((rows, width), dtype=like.dtype, device=like.device)
+            elif t.dtype != like.dtype or tuple(t.shape) != (rows, width):
+                raise FewbitHipError(f'{what} must be a {rows} x {width} tensor of {like.dtype}')
+            outs.append(t)
+            written += (None, 0) if t is None else (t.data_ptr(), _glu_rows(t, what)[2])
+        _same_device(like, state, *(t for t in outs if t is not None))
+        _check(getattr(lib(), f'fewbit_hipx_{name}')(DTYPES[like.dtype], act, _ptr(gy), state.data_ptr(), rows, width, bits,
+                                                     *written, _stream(stream, like.device)))
+    return tuple(outs)
 
 
 def glu_backward(gy: torch.Tensor, state: torch.Tensor, activation: str, bits: int, want=(True, True), d_gate: Optional[torch.Tensor] = None,
@@ -886,29 +872,7 @@ def glu_backward(gy: torch.Tensor, state: torch.Tensor, activation: str, bits: i
     ``want`` is False the output is None and nothing of it is computed or written.  ``d_gate``, ``d_up``: buffers to write into, 2-D of the
     shape of ``gy`` with unit stride along the width and any row stride -- the halves of ONE ``rows x 2 width`` tensor, for a packed
     ``[gate | up]`` input; the gap of a row stride is not written."""
-    if gy.dim() != 2 or not gy.is_contiguous():
-        raise FewbitHipError('gy must be a contiguous 2-D tensor')
-    rows, width, _ = _glu_rows(gy, 'gy')
-    act = _glu_activation(activation)
-    need = _glu_size(rows * width, bits, 'glu_backward')
-    if state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < need:
-        raise FewbitHipError(f'state must be a contiguous uint8 tensor of at least {need} bytes')
-    with _on(gy.device):
-        outs, lds = [], []
-        for t, wanted, what in ((d_gate, want[0], 'd_gate'), (d_up, want[1], 'd_up')):
-            if not wanted:
-                t = None
-            elif t is None:
-                t = torch.empty((rows, width), dtype=gy.dtype, device=gy.device)
-            elif t.dtype != gy.dtype or tuple(t.shape) != (rows, width):
-                raise FewbitHipError(f'{what} must be a {rows} x {width} tensor of {gy.dtype}')
-            outs.append(t)
-            lds.append(0 if t is None else _glu_rows(t, what)[2])
-        _same_device(gy, state, *(t for t in outs if t is not None))
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _check(lib().fewbit_hipx_glu_backward(DTYPES[gy.dtype], act, gy.data_ptr(), state.data_ptr(), rows, width, bits, ptr(outs[0]), lds[0], ptr(outs[1]), lds[1],
-                                              _stream(stream, gy.device)))
-    return tuple(outs)
+    return _glu_backward('glu_backward', gy, gy, state, activation, bits, ((d_gate, want[0], 'd_gate'), (d_up, want[1], 'd_up')), stream)
 
 
 def glu_backward_product(gy: Optional[torch.Tensor], state: torch.Tensor, activation: str, bits: int, want=(True, True, True), d_gate: Optional[torch.Tensor] = None,
@@ -934,28 +898,5 @@ def glu_backward_product(gy: Optional[torch.Tensor], state: torch.Tensor, activa
             return None, None, None
         if product is None:
             raise FewbitHipError('without gy the product buffer must be given: it carries the shape and the dtype')
-        like = product
-    else:
-        if gy.dim() != 2 or not gy.is_contiguous():
-            raise FewbitHipError('gy must be a contiguous 2-D tensor')
-        like = gy
-    rows, width, _ = _glu_rows(like, 'product' if gy is None else 'gy')
-    need = _glu_size(rows * width, bits, 'glu_backward_product')
-    if state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < need:
-        raise FewbitHipError(f'state must be a contiguous uint8 tensor of at least {need} bytes')
-    with _on(like.device):
-        outs, lds = [], []
-        for t, wanted, what in ((d_gate, want[0], 'd_gate'), (d_up, want[1], 'd_up'), (product, want[2], 'product')):
-            if not wanted:
-                t = None
-            elif t is None:
-                t = torch.empty((rows, width), dtype=like.dtype, device=like.device)
-            elif t.dtype != like.dtype or tuple(t.shape) != (rows, width):
-                raise FewbitHipError(f'{what} must be a {rows} x {width} tensor of {like.dtype}')
-            outs.append(t)
-            lds.append(0 if t is None else _glu_rows(t, what)[2])
-        _same_device(like, state, *(t for t in outs if t is not None))
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _check(lib().fewbit_hipx_glu_backward_product(DTYPES[like.dtype], act, ptr(gy), state.data_ptr(), rows, width, bits, ptr(outs[0]), lds[0], ptr(outs[1]), lds[1],
-                                                      ptr(outs[2]), lds[2], _stream(stream, like.device)))
-    return tuple(outs)
+    outputs = ((d_gate, want[0], 'd_gate'), (d_up, want[1], 'd_up'), (product, want[2], 'product'))
+    return _glu_backward('glu_backward_product', gy, product if gy is None else gy, state, activation, bits, outputs, stream, act)

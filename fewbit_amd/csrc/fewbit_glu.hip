@@ -436,6 +436,42 @@ using fewbit_hip::sketch::Key;
 namespace glu = fewbit_hip::quant::glu;
 namespace quant = fewbit_hip::quant;
 
+// What the two backward entry points share.  `with_product`: fewbit_hipx_glu_backward_product, which alone has a third output, may lack gy where neither
+// gradient is wanted, and launches the PRODUCT kernels (the plain entry point keeps its own: they are faster); each words its refusals as it did.
+static int backward_call(const char *name, bool with_product, int dtype, int act, const void *gy, const uint8_t *state, size_t rows, size_t width, int bits,
+                         void *d_gate, size_t ld_dgate, void *d_up, size_t ld_dup, void *product, size_t ld_product, void *stream) {
+    using glu::fail;
+    using glu::misaligned;
+    size_t n = 0;
+    if (!quant::known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: bits = %d is not 2, 4 or 8", name, bits);
+    const int shape = glu::shape_of(name, dtype, act, rows, width, n);
+    if (shape != 0) return shape < 0 ? shape : FEWBIT_OK;
+    if ((d_gate != nullptr && ld_dgate < width) || (d_up != nullptr && ld_dup < width) || (product != nullptr && ld_product < width))
+        return with_product ? fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: a row stride (%zu, %zu, %zu) is below the width %zu", name, ld_dgate, ld_dup, ld_product, width)
+                            : fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: a row stride (%zu, %zu) is below the width %zu", name, ld_dgate, ld_dup, width);
+    if (state == nullptr || (gy == nullptr && !with_product)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer", name);
+    if (gy == nullptr && (d_gate != nullptr || d_up != nullptr))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: gy is a null pointer and a gradient is wanted (gy may be absent only with d_gate and d_up)", name);
+    const size_t item = quant::size_of(dtype);
+    if (misaligned(gy, item) || misaligned(d_gate, item) || misaligned(d_up, item) || misaligned(product, item))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: gy, d_gate%s must be aligned to their element size", name, with_product ? ", d_up and product" : " and d_up");
+    if (misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: state must be 8-byte aligned", name);
+    if (d_gate == nullptr && d_up == nullptr && product == nullptr) return FEWBIT_OK;
+    if (rows == 1) ld_dgate = ld_dup = ld_product = width;
+    const auto wide = [&](const void *p, size_t ld) { return p == nullptr || ((ld * item) % 16 == 0 && !misaligned(p, 16)); };
+    const bool vec = width % 8 == 0 && !misaligned(gy, 16) && wide(d_gate, ld_dgate) && wide(d_up, ld_dup) && wide(product, ld_product);
+    const glu::ProductArgs a{{gy, state, glu::part_bytes(n, bits), width, n, d_gate, d_up, ld_dgate, ld_dup}, product, ld_product};
+    const unsigned grid = glu::grid_of((n + quant::kBlock - 1) / quant::kBlock);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const glu::BackwardArgs &plain = a;
+    switch (dtype) {
+    case FEWBIT_F32: with_product ? glu::launch_product<FEWBIT_F32>(act, bits, vec, grid, s, a) : glu::launch_backward<FEWBIT_F32>(act, bits, vec, grid, s, plain); break;
+    case FEWBIT_F16: with_product ? glu::launch_product<FEWBIT_F16>(act, bits, vec, grid, s, a) : glu::launch_backward<FEWBIT_F16>(act, bits, vec, grid, s, plain); break;
+    default: with_product ? glu::launch_product<FEWBIT_BF16>(act, bits, vec, grid, s, a) : glu::launch_backward<FEWBIT_BF16>(act, bits, vec, grid, s, plain); break;
+    }
+    return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
+}
+
 extern "C" {
 
 size_t fewbit_hipx_glu_state_bytes(size_t n, int bits) { return 2 * glu::part_bytes(n, bits); }
@@ -491,64 +527,12 @@ int fewbit_hipx_glu_forward(int dtype, int act, const void *gate, size_t ld_gate
 
 int fewbit_hipx_glu_backward(int dtype, int act, const void *gy, const uint8_t *state, size_t rows, size_t width, int bits, void *d_gate, size_t ld_dgate, void *d_up,
                              size_t ld_dup, void *stream) {
-    using glu::fail;
-    using glu::misaligned;
-    size_t n = 0;
-    if (!quant::known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward: bits = %d is not 2, 4 or 8", bits);
-    const int shape = glu::shape_of("glu_backward", dtype, act, rows, width, n);
-    if (shape != 0) return shape < 0 ? shape : FEWBIT_OK;
-    if ((d_gate != nullptr && ld_dgate < width) || (d_up != nullptr && ld_dup < width))
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward: a row stride (%zu, %zu) is below the width %zu", ld_dgate, ld_dup, width);
-    if (gy == nullptr || state == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward: null pointer");
-    const size_t item = quant::size_of(dtype);
-    if (misaligned(gy, item) || misaligned(d_gate, item) || misaligned(d_up, item))
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward: gy, d_gate and d_up must be aligned to their element size");
-    if (misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward: state must be 8-byte aligned");
-    if (d_gate == nullptr && d_up == nullptr) return FEWBIT_OK;
-    if (rows == 1) ld_dgate = ld_dup = width;
-    const bool vec = width % 8 == 0 && !misaligned(gy, 16) && (d_gate == nullptr || ((ld_dgate * item) % 16 == 0 && !misaligned(d_gate, 16))) &&
-                     (d_up == nullptr || ((ld_dup * item) % 16 == 0 && !misaligned(d_up, 16)));
-    const glu::BackwardArgs a{gy, state, glu::part_bytes(n, bits), width, n, d_gate, d_up, ld_dgate, ld_dup};
-    const unsigned grid = glu::grid_of((n + quant::kBlock - 1) / quant::kBlock);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case FEWBIT_F32: glu::launch_backward<FEWBIT_F32>(act, bits, vec, grid, s, a); break;
-    case FEWBIT_F16: glu::launch_backward<FEWBIT_F16>(act, bits, vec, grid, s, a); break;
-    default: glu::launch_backward<FEWBIT_BF16>(act, bits, vec, grid, s, a); break;
-    }
-    return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "glu_backward: the launch failed");
+    return backward_call("glu_backward", false, dtype, act, gy, state, rows, width, bits, d_gate, ld_dgate, d_up, ld_dup, nullptr, 0, stream);
 }
 
 int fewbit_hipx_glu_backward_product(int dtype, int act, const void *gy, const uint8_t *state, size_t rows, size_t width, int bits, void *d_gate, size_t ld_dgate,
                                      void *d_up, size_t ld_dup, void *product, size_t ld_product, void *stream) {
-    using glu::fail;
-    using glu::misaligned;
-    size_t n = 0;
-    if (!quant::known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward_product: bits = %d is not 2, 4 or 8", bits);
-    const int shape = glu::shape_of("glu_backward_product", dtype, act, rows, width, n);
-    if (shape != 0) return shape < 0 ? shape : FEWBIT_OK;
-    if ((d_gate != nullptr && ld_dgate < width) || (d_up != nullptr && ld_dup < width) || (product != nullptr && ld_product < width))
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward_product: a row stride (%zu, %zu, %zu) is below the width %zu", ld_dgate, ld_dup, ld_product, width);
-    if (state == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward_product: null pointer");
-    if (gy == nullptr && (d_gate != nullptr || d_up != nullptr))
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward_product: gy is a null pointer and a gradient is wanted (gy may be absent only with d_gate and d_up)");
-    const size_t item = quant::size_of(dtype);
-    if (misaligned(gy, item) || misaligned(d_gate, item) || misaligned(d_up, item) || misaligned(product, item))
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward_product: gy, d_gate, d_up and product must be aligned to their element size");
-    if (misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_backward_product: state must be 8-byte aligned");
-    if (d_gate == nullptr && d_up == nullptr && product == nullptr) return FEWBIT_OK;
-    if (rows == 1) ld_dgate = ld_dup = ld_product = width;
-    const auto wide = [&](const void *p, size_t ld) { return p == nullptr || ((ld * item) % 16 == 0 && !misaligned(p, 16)); };
-    const bool vec = width % 8 == 0 && !misaligned(gy, 16) && wide(d_gate, ld_dgate) && wide(d_up, ld_dup) && wide(product, ld_product);
-    const glu::ProductArgs a{{gy, state, glu::part_bytes(n, bits), width, n, d_gate, d_up, ld_dgate, ld_dup}, product, ld_product};
-    const unsigned grid = glu::grid_of((n + quant::kBlock - 1) / quant::kBlock);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case FEWBIT_F32: glu::launch_product<FEWBIT_F32>(act, bits, vec, grid, s, a); break;
-    case FEWBIT_F16: glu::launch_product<FEWBIT_F16>(act, bits, vec, grid, s, a); break;
-    default: glu::launch_product<FEWBIT_BF16>(act, bits, vec, grid, s, a); break;
-    }
-    return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "glu_backward_product: the launch failed");
+    return backward_call("glu_backward_product", true, dtype, act, gy, state, rows, width, bits, d_gate, ld_dgate, d_up, ld_dup, product, ld_product, stream);
 }
 
 }  // extern "C"

@@ -16,7 +16,7 @@ bytes of the two bf16 inputs, a tenth of what torch keeps.  The few-bit activati
   the halves of ``x.chunk(2, -1)``, are taken as they are; other layouts are gathered first -- or ONE tensor ``[gate | up]`` along the last
   dimension (``up=None``), whose one gradient tensor the one backward launch then writes in place, without a copy.  Host tensors, float64 and
   ``use_native_sketch(False)`` take a PyTorch formulation of the same definition: ``y`` is torch's ``act(gate) * up``, the codes come from
-  ``linear._quantize_groups``, backward is the formula above.
+  ``kept.quantize_groups``, backward is the formula above.
 * ``activation``: ``'silu'`` or ``'gelu'`` (the erf form; the tanh form is not done).
 * The seed comes from ``linear._sketch_seed``: an int drawn from the host generator, or a device word while the stream is being captured into a
   hipGraph (one eager call on the device precedes a capture, as for the randomized linears).
@@ -35,7 +35,7 @@ import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import cabi_x, linear
+from . import cabi_x, kept, linear
 from .cabi import DTYPES
 
 __all__ = ('glu_quantized', 'gated_mlp_quantized', 'QuantizedGLU', 'QuantizedGatedMLP')
@@ -70,8 +70,7 @@ def _rows(t: torch.Tensor) -> torch.Tensor:
 
 
 def _kernel_applies(gate: torch.Tensor, up: torch.Tensor) -> bool:
-    return (linear.use_native_sketch() and gate.device.type == 'cuda' and gate.dtype in DTYPES and up.dtype == gate.dtype and up.device == gate.device
-            and 0 < gate.numel() <= 2**36)
+    return linear._kernels_take(gate) and up.dtype == gate.dtype and up.device == gate.device
 
 
 def _slope(g: torch.Tensor, activation: str) -> torch.Tensor:
@@ -82,9 +81,26 @@ def _slope(g: torch.Tensor, activation: str) -> torch.Tensor:
     return 0.5 * (1 + torch.erf(g * math.sqrt(0.5))) + g * torch.exp(-0.5 * g * g) * (1 / math.sqrt(2 * math.pi))
 
 
-def _decoded(codes: torch.Tensor, lo: torch.Tensor, step: torch.Tensor, shape) -> torch.Tensor:
-    values = torch.addcmul(lo[:, None], codes.view(-1, cabi_x.QUANT_GROUP).to(lo.dtype), step[:, None])
-    return values.reshape(-1)[:math.prod(shape)].view(shape)
+def _check(activation: str, bits: int) -> None:
+    kept.check_bits(bits)
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation should be 'silu' or 'gelu', but got {activation!r}.")
+
+
+def _formula_backward(gy: Optional[torch.Tensor], gate_kept, up_kept, shape, activation: str, want):
+    """The PyTorch formulation of backward from the codes, lo and step of gate and of up -> ``(d_gate, d_up, product)`` in the dtype of the decodes,
+    None where ``want`` is False: the definition's formulas on the decodes, NaN on the elements of a poisoned group"""
+    count = math.prod(shape)
+    g, u = kept.decode(*gate_kept, 1, count).view(shape), kept.decode(*up_kept, 1, count).view(shape)
+    poisoned = torch.isnan(g) | torch.isnan(u)
+    nan = torch.full((), float('nan'), dtype=g.dtype, device=g.device)
+    if gy is not None:
+        gy = gy.to(g.dtype)
+    act = (F.silu(g) if activation == 'silu' else F.gelu(g)) if want[1] or want[2] else None
+    d_gate = torch.where(poisoned, nan, gy * u * _slope(g, activation)) if want[0] else None
+    d_up = torch.where(poisoned, nan, gy * act) if want[1] else None
+    product = torch.where(poisoned, nan, act * u) if want[2] else None
+    return d_gate, d_up, product
 
 
 class _GLUQuantized(torch.autograd.Function):
@@ -105,7 +121,7 @@ class _GLUQuantized(torch.autograd.Function):
             y, state = cabi_x.glu_forward(_rows(g), _rows(u), activation, bits, ctx.native_seed)
             ctx.save_for_backward(state)
             return y.view(ctx.shape)
-        ctx.save_for_backward(*linear._quantize_groups(g, bits, generator), *linear._quantize_groups(u, bits, generator))
+        ctx.save_for_backward(*kept.quantize_groups(g, bits, generator), *kept.quantize_groups(u, bits, generator))
         return _torch_product(g, u, activation)
 
     @staticmethod
@@ -117,13 +133,7 @@ class _GLUQuantized(torch.autograd.Function):
             width = ctx.shape[-1]
             want = (True, True) if ctx.packed else tuple(ctx.needs_input_grad[:2])
             if ctx.native_seed is None:
-                work = saved[1].dtype
-                g, u = _decoded(*saved[:3], ctx.shape), _decoded(*saved[3:], ctx.shape)
-                poisoned = torch.isnan(g) | torch.isnan(u)
-                gy = grad_output.to(work)
-                nan = torch.full((), float('nan'), dtype=work, device=gy.device)
-                d_up = torch.where(poisoned, nan, gy * (F.silu(g) if ctx.activation == 'silu' else F.gelu(g))) if want[1] else None
-                d_gate = torch.where(poisoned, nan, gy * u * _slope(g, ctx.activation)) if want[0] else None
+                d_gate, d_up, _ = _formula_backward(grad_output, saved[:3], saved[3:], ctx.shape, ctx.activation, (*want, False))
                 if ctx.packed:
                     return torch.cat((d_gate, d_up), dim=-1).to(ctx.input_dtype), None, None, None, None
                 return (None if d_gate is None else d_gate.to(ctx.input_dtype), None if d_up is None else d_up.to(ctx.up_dtype), None, None, None)
@@ -149,15 +159,12 @@ def glu_quantized(gate: torch.Tensor, up: Optional[torch.Tensor] = None, activat
     ``generator``: the source of the rounding's randomness; without it the host default generator seeds every call.  Grad mode off, or nothing
     that requires grad: the plain forward -- no seed is drawn and nothing is kept.  Inside ``torch.utils.checkpoint`` ``generator`` must be a
     default one (``None`` included)."""
-    if bits not in cabi_x.QUANT_BITS:
-        raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
-    if activation not in ACTIVATIONS:
-        raise ValueError(f"activation should be 'silu' or 'gelu', but got {activation!r}.")
+    _check(activation, bits)
     if up is not None and up.shape != gate.shape:
         raise ValueError(f'up should have the shape of gate, {tuple(gate.shape)}, but got {tuple(up.shape)}.')
     if up is None:
         _halves(gate)                                                                          # (the refusal of an odd width)
-    if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (gate, up)):
+    if not kept.trains(gate, up):
         g, u = _halves(gate.detach()) if up is None else (gate.detach(), up.detach())
         if not _kernel_applies(g, u):
             return _torch_product(g, u, activation)
@@ -170,7 +177,7 @@ class _GatedMLPQuantized(torch.autograd.Function):
     uint8 buffer, ``cabi_x.quant_pack``; only while ``gate_weight`` or ``up_weight`` requires grad), the state of gate and up (one uint8 buffer,
     ``cabi_x.glu_forward``; only while something other than ``down_bias`` requires grad) and the three weights; in the PyTorch formulation the
     codes (one per byte), lo and step of every group of each.  On ``ctx``: the two seeds (ints; device words while the stream is being captured;
-    None where nothing is rounded).
+    None where nothing is rounded) and ``layout``, how many of the saved tensors are those of ``x`` and those of gate and up (the three weights follow).
     Nothing of the shape of ``x``, ``gate``, ``up`` or ``y`` in a float dtype."""
 
     @staticmethod
@@ -178,35 +185,27 @@ class _GatedMLPQuantized(torch.autograd.Function):
         needs = ctx.needs_input_grad
         ctx.activation, ctx.bits, ctx.input_shape, ctx.input_dtype = activation, bits, tuple(x.shape), x.dtype
         ctx.autocast = linear._autocast_seen(x.device.type)
-        ctx.keeps_x = needs[1] or needs[2]
-        ctx.keeps_gate_up = any(needs[:6])
-        ctx.seeds = None
+        keeps_x, keeps_gate_up = needs[1] or needs[2], any(needs[:6])
         flat = x.detach().reshape(-1, x.shape[-1])
         gate, up = F.linear(x, gate_weight, gate_bias), F.linear(x, up_weight, up_bias)
         lead, width = gate.shape[:-1], gate.shape[-1]
         gate, up = gate.reshape(-1, width), up.reshape(-1, width)
         ctx.flat_shape, ctx.width = tuple(flat.shape), width
-        kept = []
-        if _kernel_applies(gate, up) and flat.dtype in DTYPES:
-            if ctx.keeps_gate_up:
-                # two seeds wherever anything is rounded (also where x^ is not kept: the stream of the generator does not depend on what is frozen),
-                # seed_x first.  ONE would not do: the packed form and the gate part of the state both round in counter domain 7, so x^ and g^
-                # would meet the same uniforms at the same flat indices and E[d_gate^T x^] would no longer factor
-                ctx.seeds = (linear._sketch_seed(generator, flat.device), linear._sketch_seed(generator, flat.device))
-                if ctx.keeps_x:
-                    kept.append(cabi_x.quant_pack(flat if flat.is_contiguous() else flat.contiguous(), ctx.seeds[0], bits))
-                y, state = cabi_x.glu_forward(gate, up, activation, bits, ctx.seeds[1])
-                kept.append(state)
-            else:
-                # only down_bias is trained: its gradient is a column sum of the incoming one.  Nothing is rounded, no seed is drawn
-                y = cabi_x.glu_forward(gate, up, activation, keep=False)[0]
+        native = _kernel_applies(gate, up) and flat.dtype in DTYPES
+        # two seeds wherever the kernels round anything (also where x^ is not kept: the stream of the generator does not depend on what is frozen), seed_x
+        # first, both before anything is packed.  ONE would not do: the packed form and the gate part of the state both round in counter domain 7, so x^
+        # and g^ would meet the same uniforms at the same flat indices and E[d_gate^T x^] would no longer factor.  Only down_bias is trained: its
+        # gradient is a column sum of the incoming one, nothing is rounded, no seed is drawn
+        ctx.seeds = (linear._sketch_seed(generator, flat.device), linear._sketch_seed(generator, flat.device)) if native and keeps_gate_up else None
+        x_kept = kept.keep(flat, bits, ctx.seeds[0] if native else None, generator) if keeps_x else ()
+        if native:
+            y, state = cabi_x.glu_forward(gate, up, activation, bits, ctx.seeds[1] if keeps_gate_up else 0, keeps_gate_up)
+            gate_up_kept = (state, ) if keeps_gate_up else ()
         else:
-            if ctx.keeps_x:
-                kept.extend(linear._quantize_groups(flat, bits, generator))
-            if ctx.keeps_gate_up:
-                kept.extend(linear._quantize_groups(gate, bits, generator) + linear._quantize_groups(up, bits, generator))
+            gate_up_kept = kept.quantize_groups(gate, bits, generator) + kept.quantize_groups(up, bits, generator) if keeps_gate_up else ()
             y = _torch_product(gate, up, activation)
-        ctx.save_for_backward(*kept, gate_weight, up_weight, down_weight)
+        ctx.layout = (len(x_kept), len(gate_up_kept))           # how many of the saved tensors are x^, and gate and up; the three weights follow
+        ctx.save_for_backward(*x_kept, *gate_up_kept, gate_weight, up_weight, down_weight)
         return F.linear(y.view(*lead, width), down_weight, down_bias)
 
     @staticmethod
@@ -218,41 +217,35 @@ class _GatedMLPQuantized(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, grad_output):
         saved = ctx.saved_tensors                           # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
-        gate_weight, up_weight, down_weight = saved[-3:]
+        of_x, of_gate_up = ctx.layout
+        x_kept, gate_up_kept, (gate_weight, up_weight, down_weight) = saved[:of_x], saved[of_x:of_x + of_gate_up], saved[of_x + of_gate_up:]
         needs = ctx.needs_input_grad
         rows, width = ctx.flat_shape[0], ctx.width
         native = ctx.seeds is not None
         G = grad_output.reshape(-1, grad_output.shape[-1])
         if native and G.dtype not in DTYPES:
             G = G.float()
-        want_gate, want_up, want_product = needs[0] or needs[1] or needs[4], needs[0] or needs[2] or needs[5], needs[3]
-        d_y = G @ down_weight if want_gate or want_up else None
+        want = (needs[0] or needs[1] or needs[4], needs[0] or needs[2] or needs[5], needs[3])       # d_gate, d_up, the product
+        d_y = G @ down_weight if want[0] or want[1] else None
         d_gate = d_up = product = None
-        if native and (want_gate or want_up or want_product):
+        if native and any(want):
             if d_y is not None and d_y.dtype not in DTYPES:
                 d_y = d_y.float()
             dtype = G.dtype if d_y is None else d_y.dtype
-            if want_gate and want_up:
+            if want[0] and want[1]:
                 # [d_gate | d_up] in ONE buffer: the launch writes its two halves where they lie (row stride 2 width)
                 both = torch.empty((rows, 2 * width), dtype=dtype, device=G.device)
                 d_gate, d_up = both[:, :width], both[:, width:]
-            elif want_gate or want_up:
-                d_gate = torch.empty((rows, width), dtype=dtype, device=G.device) if want_gate else None
-                d_up = torch.empty((rows, width), dtype=dtype, device=G.device) if want_up else None
+            elif want[0] or want[1]:
+                d_gate = torch.empty((rows, width), dtype=dtype, device=G.device) if want[0] else None
+                d_up = torch.empty((rows, width), dtype=dtype, device=G.device) if want[1] else None
             # (y^ in the gradient's dtype, 8-bit bf16 included: the tensor it stands for, y in bf16, is itself rounded to that grid)
-            product = torch.empty((rows, width), dtype=dtype, device=G.device) if want_product else None
-            cabi_x.glu_backward_product(d_y, saved[-4], ctx.activation, ctx.bits, (want_gate, want_up, want_product), d_gate, d_up, product)
-        elif want_gate or want_up or want_product:
-            g, u = _decoded(*saved[-9:-6], (rows, width)), _decoded(*saved[-6:-3], (rows, width))
-            work = g.dtype
-            poisoned = torch.isnan(g) | torch.isnan(u)
-            nan = torch.full((), float('nan'), dtype=work, device=g.device)
-            act = F.silu(g) if ctx.activation == 'silu' else F.gelu(g)
-            if want_gate or want_up:
-                gy = d_y.to(work)
-                d_up = torch.where(poisoned, nan, gy * act).to(d_y.dtype) if want_up else None
-                d_gate = torch.where(poisoned, nan, gy * u * _slope(g, ctx.activation)).to(d_y.dtype) if want_gate else None
-            product = torch.where(poisoned, nan, act * u).to(G.dtype) if want_product else None
+            product = torch.empty((rows, width), dtype=dtype, device=G.device) if want[2] else None
+            cabi_x.glu_backward_product(d_y, gate_up_kept[0], ctx.activation, ctx.bits, want, d_gate, d_up, product)
+        elif any(want):
+            d_gate, d_up, product = _formula_backward(d_y, gate_up_kept[:3], gate_up_kept[3:], (rows, width), ctx.activation, want)
+            d_gate, d_up = (None if d is None else d.to(d_y.dtype) for d in (d_gate, d_up))
+            product = None if product is None else product.to(G.dtype)
         grads = [None] * 10
         if needs[3]:
             grads[3] = (G.T @ product).to(down_weight.dtype)
@@ -260,22 +253,11 @@ class _GatedMLPQuantized(torch.autograd.Function):
             grads[6] = G.sum(dim=0)
         if needs[1] or needs[2]:
             # x^ decoded ONCE for both products, in the gradient's dtype (a bf16 gradient at 8 bits: in fp32, two terms, as in QuantizedLinear)
-            like = d_gate if needs[1] else d_up
-            two_terms = linear._decode_in_two_terms(ctx.bits, like.dtype)
-            dtype = torch.float32 if two_terms else like.dtype
-            if native:
-                decoded = cabi_x.quant_unpack(saved[0], ctx.flat_shape[0] * ctx.flat_shape[1], ctx.bits, dtype).view(ctx.flat_shape)
-            else:
-                decoded = linear._dequantize_groups(*saved[:3], ctx.flat_shape, dtype)
-            if two_terms:
-                terms = linear._split_in_two_terms(decoded, like.dtype)     # (split once as well)
-                times_x = lambda d: linear._product_of_two_terms(d, terms)
-            else:
-                times_x = lambda d: d.T @ decoded
+            by_gate, by_up = kept.products((d_gate if needs[1] else None, d_up if needs[2] else None), x_kept, ctx.flat_shape, ctx.bits)
             if needs[1]:
-                grads[1] = times_x(d_gate).to(gate_weight.dtype)
+                grads[1] = by_gate.to(gate_weight.dtype)
             if needs[2]:
-                grads[2] = times_x(d_up).to(up_weight.dtype)
+                grads[2] = by_up.to(up_weight.dtype)
         if needs[4]:
             grads[4] = d_gate.sum(dim=0)
         if needs[5]:
@@ -324,15 +306,12 @@ def gated_mlp_quantized(x: torch.Tensor, gate_weight: torch.Tensor, up_weight: t
     * Only what a requested gradient can need is kept: the packed ``x`` only while ``gate_weight`` or ``up_weight`` requires grad.  Grad mode
       off, or nothing that requires grad: the plain forward -- no seed is drawn, nothing is kept, the same bytes.
     * The kernels serve fp32 / fp16 / bf16 GPU tensors while ``linear.use_native_sketch()`` is on; host tensors, float64 and
-      ``use_native_sketch(False)`` take the PyTorch formulation of the same definition (``linear._quantize_groups``).
+      ``use_native_sketch(False)`` take the PyTorch formulation of the same definition (``kept.quantize_groups``).
     * Backward runs under the autocast state the forward saw; not differentiable twice; inside ``torch.utils.checkpoint`` ``generator`` must be
       a default one (``None`` included)."""
-    if bits not in cabi_x.QUANT_BITS:
-        raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
-    if activation not in ACTIVATIONS:
-        raise ValueError(f"activation should be 'silu' or 'gelu', but got {activation!r}.")
+    _check(activation, bits)
     tensors = (x, gate_weight, up_weight, down_weight, gate_bias, up_bias, down_bias)
-    if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in tensors) or x.numel() == 0:
+    if not kept.trains(*tensors) or x.numel() == 0:
         if x.numel() == 0:
             return F.linear(_torch_product(F.linear(x, gate_weight, gate_bias), F.linear(x, up_weight, up_bias), activation), down_weight, down_bias)
         return _plain_gated_mlp(*(None if t is None else t.detach() for t in tensors), activation)
@@ -361,16 +340,12 @@ class QuantizedGLU(torch.nn.Module):
     """
 
     def __init__(self, activation: str = 'silu', bits: int = 4, generator: Optional[torch.Generator] = None) -> None:
-        if bits not in cabi_x.QUANT_BITS:
-            raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
-        if activation not in ACTIVATIONS:
-            raise ValueError(f"activation should be 'silu' or 'gelu', but got {activation!r}.")
+        _check(activation, bits)
         super().__init__()
         self.activation, self.bits, self.generator = activation, bits, generator
 
     def forward(self, gate: torch.Tensor, up: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if not self.training and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (gate, up)):
-            # eval mode is not where activation memory is short: gradients asked for there are torch's exact ones, nothing is rounded or drawn
+        if kept.exact_in_eval(self, gate, up):
             return _torch_product(*(_halves(gate) if up is None else (gate, up)), self.activation)
         return glu_quantized(gate, up, self.activation, self.bits, self.generator)
 
@@ -413,8 +388,7 @@ class QuantizedGatedMLP(torch.nn.Module):
         if not self.fused:
             return self.down_proj(self.glu(self.gate_proj(x), self.up_proj(x)))
         gate, up, down, glu = self.gate_proj, self.up_proj, self.down_proj, self.glu
-        if not self.training and torch.is_grad_enabled() and any(t.requires_grad for t in (x, *self.parameters())):
-            # eval mode is not where activation memory is short: gradients asked for there are torch's exact ones, nothing is rounded or drawn
+        if kept.exact_in_eval(self, x, *self.parameters()):
             return down(_torch_product(gate(x), up(x), glu.activation))
         return gated_mlp_quantized(x, gate.weight, up.weight, down.weight, gate.bias, up.bias, down.bias, glu.activation, glu.bits, glu.generator)
 

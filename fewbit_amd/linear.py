@@ -85,7 +85,7 @@ columns away.  Per group of 64 consecutive elements (by flat index) the minimum 
 fp32 and every element as ``code = min(L, floor((x - lo) / step + U))`` with ``U`` uniform in [0, 1): ``E[lo + code * step] = x``, the error
 of an element is below ``step``, a constant group is exact.  Forward is ``F.linear``; ``grad_input`` and ``grad_bias`` are exact;
 ``grad_weight = G^T X^`` with ``X^`` decoded into the gradient's dtype as a transient tensor -- one GEMM (a bf16 gradient at 8 bits: X^ decoded
-into fp32 and multiplied as two bf16 terms that meet in fp32, ``_decode_in_two_terms``: about twice the time of the other widths).  On fp32 / fp16 / bf16 GPU tensors
+into fp32 and multiplied as two bf16 terms that meet in fp32, ``kept.decode_in_two_terms``: about twice the time of the other widths).  On fp32 / fp16 / bf16 GPU tensors
 packing and decoding are one launch each on the kernels of ``fewbit_amd/csrc/fewbit_quant.hip`` (``cabi_x.quant_pack`` / ``quant_unpack``;
 the definition, "the packed form of a seed", is include/fewbit_hipx.h's and ``cabi_x.quant_pack_host`` evaluates it on the host): ``U`` is a
 function of the call's 64-bit seed, the node keeps one uint8 buffer of ``cabi_x.quant_bytes(input.numel(), bits)`` bytes (0.3125 x a bf16
@@ -98,7 +98,7 @@ decode into the GEMM, 3-bit codes, per-row groups.
 """
 import contextlib
 import os
-from typing import Optional, Tuple
+from typing import Optional
 
 import torch
 import torch.nn.functional as F
@@ -691,79 +691,21 @@ def linear_crs(input: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
 
 # ---- every element of the input in 2, 4 or 8 bits --------------------------------------------------------------------------------------
 
-# the code widths, and the elements (by flat index) that share one (lo, step) pair: the binding's constants (the import loads no library)
-from .cabi_x import QUANT_BITS, QUANT_GROUP as _QUANT_GROUP  # noqa: E402
+# the code widths: the binding's constant (the import loads no library).  What the node keeps, and how it is decoded and multiplied: ``kept``
+from . import kept  # noqa: E402
+from .cabi import DTYPES as _DTYPES  # noqa: E402
+from .cabi_x import QUANT_BITS  # noqa: E402
+from .kept import decode_in_two_terms as _decode_in_two_terms, two_term_product as _two_term_product  # noqa: E402,F401  (their names here: tests use them)
+
+
+def _kernels_take(t: torch.Tensor) -> bool:
+    """Whether ``t`` is a tensor the quantizing kernels take: fp32 / fp16 / bf16, on the GPU, 1 .. 2^36 elements, while ``use_native_sketch()`` is on"""
+    return _NATIVE_SKETCH and t.device.type == 'cuda' and t.dtype in _DTYPES and 0 < t.numel() <= 2**36
 
 
 def _native_quant_applies(flat: torch.Tensor) -> bool:
     """The gfx950 kernels (fewbit_amd/csrc/fewbit_quant.hip) take fp32 / fp16 / bf16 GPU tensors of up to 2^36 elements"""
-    return (_NATIVE_SKETCH and flat.device.type == 'cuda' and flat.dtype in (torch.float32, torch.float16, torch.bfloat16)
-            and flat.numel() <= 2**36)
-
-
-def _quantize_groups(flat: torch.Tensor, bits: int, generator: Optional[torch.Generator]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """The PyTorch formulation of the packed form: -> (codes, one uint8 per element of the padded groups; lo; step, one per group), in fp32
-    (fp64 for a float64 input).  The tail of the last group is filled with the last element, which moves neither its minimum nor its maximum."""
-    levels = float(2**bits - 1)
-    work = flat.reshape(-1).to(torch.float64 if flat.dtype == torch.float64 else torch.float32)
-    pad = -work.numel() % _QUANT_GROUP
-    if pad:
-        work = torch.cat((work, work[-1:].expand(pad)))
-    work = work.view(-1, _QUANT_GROUP)
-    lo, hi = work.amin(dim=1, keepdim=True), work.amax(dim=1, keepdim=True)
-    span = hi - lo
-    poisoned = ~torch.isfinite(span)                                        # (a NaN reaches amin / amax, an infinity makes the span inf or NaN)
-    step = span / levels
-    inv = torch.where(span > 0, levels / span, torch.zeros_like(span))
-    inv = torch.where(torch.isfinite(inv), inv, torch.zeros_like(inv))
-    if generator is None:
-        u = torch.rand(work.shape, dtype=work.dtype, device=work.device)
-    else:
-        u = torch.rand(work.shape, dtype=work.dtype, device=generator.device, generator=generator).to(work.device)
-    codes = torch.floor((work - lo) * inv + u).clamp_(max=levels)
-    codes = torch.where(poisoned, torch.zeros_like(codes), codes).to(torch.uint8)
-    nan = torch.full_like(lo, float('nan'))
-    return codes.reshape(-1), torch.where(poisoned, nan, lo).reshape(-1), torch.where(poisoned, nan, step).reshape(-1)
-
-
-def _dequantize_groups(codes: torch.Tensor, lo: torch.Tensor, step: torch.Tensor, shape, dtype: torch.dtype) -> torch.Tensor:
-    values = torch.addcmul(lo[:, None], codes.view(-1, _QUANT_GROUP).to(lo.dtype), step[:, None])
-    return values.reshape(-1)[:shape[0] * shape[1]].view(shape).to(dtype)
-
-
-def _decode_in_two_terms(bits: int, dtype: torch.dtype) -> bool:
-    """Whether ``G^T X^`` needs X^ to better than ``dtype``: a bf16 gradient at 8 bits.  There the step, range / 255, is about one bf16 ulp of a
-    group's larger elements, and rounding ``lo + code * step`` to bf16 moves an element by up to half an ulp in a direction that does not depend
-    on the seed: over many seeds the mean weight gradient then sits several of its standard errors from ``G^T X`` (measured: 8.5, against 3.5
-    for the fp32 decode of the same buffers).  At 2 and 4 bits the step is 85 and 17 times larger, and fp16 has eight times bf16's resolution."""
-    return bits == 8 and dtype == torch.bfloat16
-
-
-def _two_term_product(g: torch.Tensor, decoded: torch.Tensor) -> torch.Tensor:
-    """``g^T decoded`` for a 16-bit ``g`` and an fp32 ``decoded`` on the 16-bit matrix pipe: ``decoded = head + tail`` with ``head`` its rounding to
-    the dtype of ``g`` (what ``quant_unpack`` into that dtype gives) and ``tail`` the rounding of the exact remainder.  Both products have to meet
-    in fp32 and be rounded once: summed after the first was rounded to 16 bits, that one swallows the second, a fraction of its ulp (measured:
-    the deviation stayed).  On the GPU the library GEMM gives fp32 results for 16-bit operands (``out_dtype``): two GEMMs, an fp32 sum, rounded
-    by the caller.  Elsewhere ONE GEMM of twice the depth, ``[g; g]^T [head; tail]``.  What is left of the rounding of ``decoded`` is 2^-9 of
-    the tail: 2^-18 of an element."""
-    return _product_of_two_terms(g, _split_in_two_terms(decoded, g.dtype))
-
-
-def _split_in_two_terms(decoded: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    """``[head; tail]`` of an fp32 ``decoded`` in ``dtype`` (``_two_term_product``): split ONCE where several gradients multiply one decode"""
-    rows = decoded.shape[0]
-    terms = torch.empty((2 * rows, decoded.shape[1]), dtype=dtype, device=decoded.device)
-    terms[:rows].copy_(decoded)                                             # head
-    torch.sub(decoded, terms[:rows], out=terms[rows:])                      # tail: the difference is exact in fp32, rounded on the store
-    return terms
-
-
-def _product_of_two_terms(g: torch.Tensor, terms: torch.Tensor) -> torch.Tensor:
-    rows = terms.shape[0] // 2
-    if g.is_cuda:                                                           # two GEMMs with fp32 results: no copy of g, no doubled depth
-        with torch.autocast('cuda', enabled=False):
-            return torch.mm(g.T, terms[:rows], out_dtype=torch.float32) + torch.mm(g.T, terms[rows:], out_dtype=torch.float32)
-    return torch.cat((g, g)).T @ terms
+    return _kernels_take(flat)
 
 
 class _LinearQuantized(torch.autograd.Function):
@@ -777,14 +719,8 @@ class _LinearQuantized(torch.autograd.Function):
         ctx.bits, ctx.flat_shape = bits, tuple(flat.shape)
         ctx.has_bias = bias is not None
         ctx.autocast = _autocast_seen(input.device.type)
-        ctx.native_seed = None
-        if _native_quant_applies(flat):
-            from . import cabi_x
-            ctx.native_seed = _sketch_seed(generator, flat.device)
-            # (a non-contiguous input is packed from a contiguous copy, which lives no longer than this call)
-            ctx.save_for_backward(cabi_x.quant_pack(flat if flat.is_contiguous() else flat.contiguous(), ctx.native_seed, bits), weight)
-        else:
-            ctx.save_for_backward(*_quantize_groups(flat, bits, generator), weight)
+        ctx.native_seed = _sketch_seed(generator, flat.device) if _native_quant_applies(flat) else None
+        ctx.save_for_backward(*kept.keep(flat, bits, ctx.native_seed, generator), weight)
         return F.linear(input, weight, bias)
 
     @staticmethod
@@ -794,26 +730,15 @@ class _LinearQuantized(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, grad_output):
-        saved = ctx.saved_tensors                       # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
-        weight = saved[-1]
+        *x_kept, weight = ctx.saved_tensors             # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
         grad_input = grad_weight = grad_bias = None
         if ctx.needs_input_grad[0]:
             grad_input = grad_output @ weight
         flat = grad_output.reshape(-1, grad_output.shape[-1])
-        if ctx.needs_input_grad[1] and ctx.native_seed is not None:
-            from . import cabi_x
-            # X^ in the gradient's dtype (under autocast not the input's): a transient tensor, one GEMM
-            g2 = flat if flat.dtype in (torch.float32, torch.float16, torch.bfloat16) else flat.float()
-            rows, features = ctx.flat_shape
-            if _decode_in_two_terms(ctx.bits, g2.dtype):
-                grad_weight = _two_term_product(g2, cabi_x.quant_unpack(saved[0], rows * features, ctx.bits, torch.float32).view(rows, features)).to(weight.dtype)
-            else:
-                decoded = cabi_x.quant_unpack(saved[0], rows * features, ctx.bits, g2.dtype).view(rows, features)
-                grad_weight = (g2.T @ decoded).to(weight.dtype)
-        elif ctx.needs_input_grad[1] and _decode_in_two_terms(ctx.bits, flat.dtype):
-            grad_weight = _two_term_product(flat, _dequantize_groups(saved[0], saved[1], saved[2], ctx.flat_shape, torch.float32)).to(weight.dtype)
-        elif ctx.needs_input_grad[1]:
-            grad_weight = (flat.T @ _dequantize_groups(saved[0], saved[1], saved[2], ctx.flat_shape, flat.dtype)).to(weight.dtype)
+        if ctx.needs_input_grad[1]:
+            # X^ in the gradient's dtype (under autocast not the input's): a transient tensor, one GEMM (the kernels decode into fp32 / fp16 / bf16)
+            g2 = flat if ctx.native_seed is None or flat.dtype in _DTYPES else flat.float()
+            grad_weight = kept.products((g2, ), x_kept, ctx.flat_shape, ctx.bits)[0].to(weight.dtype)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             grad_bias = flat.sum(dim=0)
         return grad_input, grad_weight, grad_bias, None, None
@@ -824,8 +749,7 @@ def linear_quantized(input: torch.Tensor, weight: torch.Tensor, bias: Optional[t
     """``F.linear(input, weight, bias)`` that keeps its input in ``bits`` = 2, 4 or 8 bits per element, rounded without bias, for the weight
     gradient: ``grad_input`` and ``grad_bias`` are exact, ``grad_weight = G^T X^`` (module docstring).  ``generator``: the source of the
     rounding's randomness; without it the host default generator seeds every call."""
-    if bits not in QUANT_BITS:
-        raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+    kept.check_bits(bits)
     if _plain_linear(input, weight):
         return F.linear(input, weight, bias)
     return _LinearQuantized.apply(input, weight, bias, int(bits), generator)
@@ -935,8 +859,7 @@ class QuantizedLinear(torch.nn.Linear):
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=None, bits: int = 4,
                  generator: Optional[torch.Generator] = None) -> None:
-        if bits not in QUANT_BITS:
-            raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+        kept.check_bits(bits)
         super().__init__(in_features, out_features, bias, device, dtype)
         self.bits = bits
         self.generator = generator

@@ -13,7 +13,7 @@ code per 64 elements suits best, and backward needs nothing else but gamma.
 * The kernels (fewbit_amd/csrc/fewbit_norm.hip: one launch forward, two backward) serve fp32 / fp16 / bf16 GPU tensors with a flattened
   normalized width of 1 .. 8192 and gamma / beta of the input's dtype (or absent) while ``linear.use_native_sketch()`` is on.  Host tensors,
   float64, wider rows and ``use_native_sketch(False)`` take a PyTorch formulation of the same definition: ``y`` is ``F.layer_norm``'s, the codes
-  come from ``linear._quantize_groups`` on the rows of ``x^`` padded to whole groups, backward is the formula above.
+  come from ``kept.quantize_groups`` on the rows of ``x^`` padded to whole groups, backward is the formula above.
 * The seed comes from ``linear._sketch_seed``: an int drawn from the host generator, or a device word while the stream is being captured into
   a hipGraph -- a captured layer draws fresh roundings on every replay and its recorded backward reads the state its forward wrote.  (One eager
   call on the device precedes a capture, as for the randomized linears.)
@@ -52,7 +52,7 @@ import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import cabi_x, linear
+from . import cabi_x, kept, linear
 from .cabi import DTYPES
 from .dropout import _check_p, dropout_add
 
@@ -64,8 +64,7 @@ __all__ = ('layer_norm_quantized', 'QuantizedLayerNorm', 'rms_norm_quantized', '
 
 
 def _kernel_applies(flat: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor]) -> bool:
-    if not (linear.use_native_sketch() and flat.device.type == 'cuda' and flat.dtype in DTYPES and 1 <= flat.shape[1] <= cabi_x.NORM_MAX_WIDTH
-            and 0 < flat.numel() <= 2**36):
+    if not (linear._kernels_take(flat) and 1 <= flat.shape[1] <= cabi_x.NORM_MAX_WIDTH):
         return False
     # (under autocast fp32 parameters meet a 16-bit input: they are cast to it, a copy of `width` elements)
     cast = torch.is_autocast_enabled('cuda')
@@ -80,12 +79,16 @@ def _torch_norm(centred: bool, input, normalized_shape, weight, bias, eps):
     return F.layer_norm(input, normalized_shape, weight, bias, eps) if centred else F.rms_norm(input, normalized_shape, weight, eps)
 
 
-def _kernel_forward(centred: bool, flat, weight, bias, eps, bits: int = 4, seed=0, keep: bool = True):
-    """(y, rstd, state, None) of the entry point of the kind on the rows of ``flat``"""
+def _kernel_forward(centred: bool, flat, weight, bias, eps, bits: int = 4, seed=0, keep: bool = True, residual=None, p: float = 0.0, want_h: bool = False):
+    """(y, h, rstd, state) of the entry point of the kind on the rows of ``flat``; with a ``residual`` (2-D as well) the fused entry point, which normalizes
+    ``h = residual + dropout(flat)`` and returns it with ``want_h`` (else, and without a residual, ``h`` is None)"""
     flat = flat if flat.is_contiguous() else flat.contiguous()
-    if centred:
-        return cabi_x.layer_norm_forward(flat, _as(weight, flat.dtype), _as(bias, flat.dtype), eps, bits, seed, keep)
-    return cabi_x.rms_norm_forward(flat, _as(weight, flat.dtype), eps, bits, seed, keep)
+    parameters = (_as(weight, flat.dtype), _as(bias, flat.dtype)) if centred else (_as(weight, flat.dtype), )
+    if residual is None:
+        y, rstd, state, _ = (cabi_x.layer_norm_forward if centred else cabi_x.rms_norm_forward)(flat, *parameters, eps, bits, seed, keep)
+        return y, None, rstd, state
+    call = cabi_x.add_layer_norm_forward if centred else cabi_x.add_rms_norm_forward
+    return call(flat, residual if residual.is_contiguous() else residual.contiguous(), *parameters, eps, p, bits, seed, keep, want_h)[:4]
 
 
 def _row_statistic(flat: torch.Tensor, eps: float, centred: bool):
@@ -104,11 +107,6 @@ def _padded_rows(xhat: torch.Tensor) -> torch.Tensor:
     return torch.cat((xhat, xhat[:, -1:].expand(-1, pad)), dim=1) if pad else xhat
 
 
-def _decoded_rows(codes: torch.Tensor, lo: torch.Tensor, step: torch.Tensor, rows: int, width: int) -> torch.Tensor:
-    values = torch.addcmul(lo[:, None], codes.view(-1, cabi_x.QUANT_GROUP).to(lo.dtype), step[:, None])
-    return values.view(rows, -1)[:, :width]
-
-
 def _backward_formula(gy: torch.Tensor, xq: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor], centred: bool):
     """(dx, dgamma, dbeta) of the definition in the dtype of ``xq``; un-centred the mean term is absent and ``dbeta`` is None"""
     gy = gy.to(xq.dtype)
@@ -118,46 +116,71 @@ def _backward_formula(gy: torch.Tensor, xq: torch.Tensor, rstd: torch.Tensor, ga
     return dx, (gy * xq).sum(dim=0), gy.sum(dim=0) if centred else None
 
 
-def _node_forward(ctx, centred: bool, input, weight, bias, normalized_shape, eps: float, bits: int, generator):
+def _node_forward(ctx, centred: bool, input, weight, bias, normalized_shape, eps: float, bits: int, generator, add=None):
     """Kept for backward on the kernels: ONE uint8 buffer (the state), ``rstd`` (fp32 per row) and gamma; in the PyTorch formulation the codes (one
-    per byte), lo and step of every group, ``rstd`` and gamma."""
+    per byte), lo and step of every group, ``rstd`` and gamma.  ``add``: None, or ``(residual, p, prenorm)``: the node is then
+    ``norm(residual + dropout(input))`` on the fused kernels, which have no PyTorch formulation here -- the CALLER has made sure that they apply
+    (``_dropout_add_norm_quantized``).  The same tensors are kept, the ONE seed of the call and ``p`` are on ``ctx``, and with ``prenorm`` the result is
+    the pair ``(y, h)``."""
+    residual, p, prenorm = add or (None, 0.0, False)
     width = math.prod(normalized_shape)
     flat = input.detach().reshape(-1, width)
-    ctx.bits, ctx.flat_shape, ctx.input_dtype = bits, tuple(flat.shape), input.dtype
+    ctx.bits, ctx.flat_shape, ctx.input_dtype, ctx.p = bits, tuple(flat.shape), input.dtype, p
     ctx.has_weight, ctx.normalized_shape, ctx.bias_dtype = weight is not None, tuple(normalized_shape), None if bias is None else bias.dtype
     ctx.autocast = linear._autocast_seen(input.device.type)
     ctx.native_seed = None
-    if _kernel_applies(flat, weight, bias):
+    if add is not None or _kernel_applies(flat, weight, bias):
         ctx.native_seed = linear._sketch_seed(generator, flat.device)
-        y, rstd, state, _ = _kernel_forward(centred, flat, weight, bias, eps, bits, ctx.native_seed)
+        y, h, rstd, state = _kernel_forward(centred, flat, weight, bias, eps, bits, ctx.native_seed, True,
+                                            None if add is None else residual.detach().reshape(-1, width), p, prenorm)
         ctx.save_for_backward(state, rstd, *((weight, ) if ctx.has_weight else ()))
-        return y.view(input.shape)
+        return (y.view(input.shape), h.view(input.shape)) if prenorm else y.view(input.shape)
     xhat, rstd = _row_statistic(flat, eps, centred)
-    ctx.save_for_backward(*linear._quantize_groups(_padded_rows(xhat), bits, generator), rstd, *((weight, ) if ctx.has_weight else ()))
+    ctx.save_for_backward(*kept.quantize_groups(_padded_rows(xhat), bits, generator), rstd, *((weight, ) if ctx.has_weight else ()))
     return _torch_norm(centred, input, normalized_shape, weight, bias, eps)
 
 
-def _node_backward(ctx, centred: bool, grad_output):
-    """(grad_input, grad_weight, grad_bias), under the autocast state the forward saw"""
+def _node_backward(ctx, centred: bool, grad_output, fused: bool = False, grad_h=None):
+    """(grad_input, grad_weight, grad_bias, grad_residual) as ``ctx.needs_input_grad`` wants them, under the autocast state the forward saw.  The inputs
+    of the plain nodes are (input, weight[, bias]); ``fused``: (input, residual, weight, bias), ``grad_h`` is the gradient arriving at ``h``, and either
+    gradient may be None."""
     with linear._autocast_as(ctx.autocast):
-        grad_output = linear._dense_rows(grad_output)
         saved = ctx.saved_tensors                       # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
         weight = saved[-1] if ctx.has_weight else None
         rows, width = ctx.flat_shape
-        gy = grad_output.reshape(rows, width)
-        want = tuple(ctx.needs_input_grad[:3 if centred else 2])
+        needs = ctx.needs_input_grad
+        if fused:
+            want_input, want_residual, want_weight, want_bias = needs[:4]
+            shape = (grad_output if grad_output is not None else grad_h).shape
+            if grad_output is None:                     # (only h reached the loss: the norm's own terms are those of a zero gradient)
+                grad_output = torch.zeros_like(grad_h)
+        else:
+            want_input, want_weight, want_bias, want_residual, shape = needs[0], needs[1], centred and needs[2], False, grad_output.shape
+        gy = linear._dense_rows(grad_output).reshape(rows, width)
+        sums = (want_weight, want_bias) if centred else (want_weight, )
+        dres = None
         if ctx.native_seed is None:
             codes, lo, step, rstd = saved[:4]
-            dx, dgamma, dbeta = _backward_formula(gy, _decoded_rows(codes, lo, step, rows, width), rstd, weight, centred)
+            dx, dgamma, dbeta = _backward_formula(gy, kept.decode(codes, lo, step, rows, width), rstd, weight, centred)
+        elif fused:
+            gy = gy if gy.dtype in DTYPES else gy.float()
+            gh = None if grad_h is None else linear._dense_rows(grad_h.to(gy.dtype)).reshape(rows, width)
+            mask = cabi_x.dropout_threshold(ctx.p) > 0
+            # without a mask the two gradients are the same values: ONE tensor is written and returned for both
+            call = cabi_x.add_layer_norm_backward if centred else cabi_x.add_rms_norm_backward
+            dres, dbranch, dgamma, *dbeta = call(gy, saved[0], saved[1], _as(weight, gy.dtype), ctx.bits, ctx.native_seed, ctx.p, gh,
+                                                 (want_residual or (want_input and not mask), want_input and mask, *sums))
+            dx, dbeta = dbranch if mask else dres, dbeta[0] if centred else None
         else:
             gy = gy if gy.dtype in DTYPES else gy.float()
             call = cabi_x.layer_norm_backward if centred else cabi_x.rms_norm_backward
-            grads = call(gy, saved[0], saved[1], _as(weight, gy.dtype), ctx.bits, want)
-            dx, dgamma, dbeta = grads if centred else (*grads, None)
-        grad_input = dx.to(ctx.input_dtype).view(grad_output.shape) if want[0] else None
-        grad_weight = dgamma.to(weight.dtype).view(weight.shape) if want[1] else None
-        grad_bias = dbeta.to(ctx.bias_dtype).view(ctx.normalized_shape) if centred and want[2] else None
-        return grad_input, grad_weight, grad_bias
+            dx, dgamma, *dbeta = call(gy, saved[0], saved[1], _as(weight, gy.dtype), ctx.bits, (want_input, *sums))
+            dbeta = dbeta[0] if centred else None
+        grad_input = dx.to(ctx.input_dtype).view(shape) if want_input else None
+        grad_residual = dres.to(ctx.input_dtype).view(shape) if want_residual else None
+        grad_weight = dgamma.to(weight.dtype).view(weight.shape) if want_weight else None
+        grad_bias = dbeta.to(ctx.bias_dtype).view(ctx.normalized_shape) if want_bias else None
+        return grad_input, grad_weight, grad_bias, grad_residual
 
 
 class _LayerNormQuantized(torch.autograd.Function):
@@ -170,7 +193,7 @@ class _LayerNormQuantized(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        return (*_node_backward(ctx, True, grad_output), None, None, None, None)
+        return (*_node_backward(ctx, True, grad_output)[:3], None, None, None, None)
 
 
 class _RMSNormQuantized(torch.autograd.Function):
@@ -190,12 +213,13 @@ class _RMSNormQuantized(torch.autograd.Function):
 def _norm_quantized(centred: bool, input, normalized_shape, weight, bias, eps, bits, generator) -> torch.Tensor:
     """the functional front of both kinds: the refusals, the plain forward when nothing is kept, the node otherwise"""
     if bits not in cabi_x.QUANT_BITS:
-        raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+        kept.check_bits(bits)                                                             # (words the refusal)
     normalized_shape = (normalized_shape, ) if isinstance(normalized_shape, int) else tuple(normalized_shape)
     if tuple(input.shape[input.dim() - len(normalized_shape):]) != normalized_shape or not normalized_shape:
         return _torch_norm(centred, input, normalized_shape, weight, bias, eps)              # (torch words the refusal)
     if not centred:                                                                       # (the default F.rms_norm documents)
         eps = float(torch.finfo(input.dtype).eps if eps is None else eps)
+    # (inline, not kept.trains: a norm's step at width 768 is bound by the Python around its launches)
     if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (input, weight, bias)):
         flat = input.detach().reshape(-1, math.prod(normalized_shape))
         if not _kernel_applies(flat, weight, bias):
@@ -211,16 +235,14 @@ class _QuantizedNorm:
     repr.  ``_centred`` is the kind."""
 
     def __init__(self, bits: int, generator: Optional[torch.Generator], *norm_arguments) -> None:
-        if bits not in cabi_x.QUANT_BITS:
-            raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+        kept.check_bits(bits)
         super().__init__(*norm_arguments)
         self.bits = bits
         self.generator = generator
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
         bias = self.bias if self._centred else None
-        if not self.training and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, self.weight, bias)):
-            # eval mode is not where activation memory is short: gradients asked for there are torch's exact ones, nothing is rounded or drawn
+        if not self.training and kept.trains(input, self.weight, bias):           # (the eval-mode rule, kept.exact_in_eval, at no cost while training)
             return _torch_norm(self._centred, input, self.normalized_shape, self.weight, bias, self.eps)
         return _norm_quantized(self._centred, input, self.normalized_shape, self.weight, bias, self.eps, self.bits, self.generator)
 
@@ -341,65 +363,28 @@ class QuantizedRMSNorm(_QuantizedNorm, torch.nn.RMSNorm):
 
 
 # ---- residual + dropout(input) fused in front of either norm (module docstring, last paragraph) ------------------------------------------------
-def _add_kernel_forward(centred: bool, flat, residual, weight, bias, eps, p: float, bits: int = 4, seed=0, keep: bool = True, want_h: bool = False):
-    """(y, h, rstd, state, None) of the fused entry point of the kind"""
-    gamma = _as(weight, flat.dtype)
-    if centred:
-        return cabi_x.add_layer_norm_forward(flat, residual, gamma, _as(bias, flat.dtype), eps, p, bits, seed, keep, want_h)
-    return cabi_x.add_rms_norm_forward(flat, residual, gamma, eps, p, bits, seed, keep, want_h)
-
-
 class _DropoutAddNormQuantized(torch.autograd.Function):
-    """``norm(residual + dropout(input))`` on the fused kernels, both kinds (``centred``).  Kept: the state, ``rstd`` and gamma; on ``ctx`` the ONE
-    seed of the call and ``p``.  With ``prenorm`` the outputs are ``(y, h)`` and backward takes the gradient arriving at ``h``."""
+    """``norm(residual + dropout(input))`` on the fused kernels, both kinds (``centred``): the plain node with a residual (``_node_forward``).  With
+    ``prenorm`` the outputs are ``(y, h)`` and backward takes the gradient arriving at ``h``."""
 
     @staticmethod
     def forward(ctx, input, residual, weight, bias, centred: bool, normalized_shape, eps: float, bits: int, p: float, prenorm: bool, generator):
-        width = math.prod(normalized_shape)
-        flat = input.detach().reshape(-1, width).contiguous()
-        ctx.centred, ctx.bits, ctx.p, ctx.prenorm, ctx.input_dtype = centred, bits, p, prenorm, input.dtype
-        ctx.has_weight, ctx.normalized_shape, ctx.bias_dtype = weight is not None, tuple(normalized_shape), None if bias is None else bias.dtype
-        ctx.autocast = linear._autocast_seen(input.device.type)
+        ctx.centred = centred
         ctx.set_materialize_grads(False)
-        ctx.seed = linear._sketch_seed(generator, flat.device)
-        y, h, rstd, state, _ = _add_kernel_forward(centred, flat, residual.detach().reshape(-1, width).contiguous(), weight, bias, eps, p, bits, ctx.seed,
-                                                   want_h=prenorm)
-        ctx.save_for_backward(state, rstd, *((weight, ) if ctx.has_weight else ()))
-        return (y.view(input.shape), h.view(input.shape)) if prenorm else y.view(input.shape)
+        return _node_forward(ctx, centred, input, weight, bias, normalized_shape, eps, bits, generator, (residual, p, prenorm))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output, grad_h=None):
-        with linear._autocast_as(ctx.autocast):
-            saved = ctx.saved_tensors
-            state, rstd = saved[:2]
-            weight = saved[-1] if ctx.has_weight else None
-            rows, width = rstd.numel(), math.prod(ctx.normalized_shape)
-            shape = (grad_output if grad_output is not None else grad_h).shape
-            if grad_output is None:                     # (only h reached the loss: the norm's own terms are those of a zero gradient)
-                grad_output = torch.zeros_like(grad_h)
-            gy = linear._dense_rows(grad_output).reshape(rows, width)
-            gy = gy if gy.dtype in DTYPES else gy.float()
-            gh = None if grad_h is None else linear._dense_rows(grad_h.to(gy.dtype)).reshape(rows, width)
-            want_input, want_residual, want_weight, want_bias = ctx.needs_input_grad[:4]
-            mask = cabi_x.dropout_threshold(ctx.p) > 0
-            # without a mask the two gradients are the same values: ONE tensor is written and returned for both
-            want = (want_residual or (want_input and not mask), want_input and mask, want_weight) + ((want_bias, ) if ctx.centred else ())
-            call = cabi_x.add_layer_norm_backward if ctx.centred else cabi_x.add_rms_norm_backward
-            dres, dbranch, dgamma, *rest = call(gy, state, rstd, _as(weight, gy.dtype), ctx.bits, ctx.seed, ctx.p, gh, want)
-            shaped = lambda t: t.to(ctx.input_dtype).view(shape)
-            grad_residual = shaped(dres) if want_residual else None
-            grad_input = (shaped(dbranch) if mask else shaped(dres)) if want_input else None
-            grad_weight = dgamma.to(weight.dtype).view(weight.shape) if want_weight else None
-            grad_bias = rest[0].to(ctx.bias_dtype).view(ctx.normalized_shape) if ctx.centred and want_bias else None
-            return grad_input, grad_residual, grad_weight, grad_bias, None, None, None, None, None, None, None
+        grad_input, grad_weight, grad_bias, grad_residual = _node_backward(ctx, ctx.centred, grad_output, True, grad_h)
+        return grad_input, grad_residual, grad_weight, grad_bias, None, None, None, None, None, None, None
 
 
 def _dropout_add_norm_quantized(centred: bool, input, residual, normalized_shape, weight, bias, eps, p, training, bits, prenorm, generator):
     """the functional front of both fused kinds: the refusals, the composition off the kernel path, the plain fused forward when nothing is kept, the
     node otherwise"""
     if bits not in cabi_x.QUANT_BITS:
-        raise ValueError(f'bits should be 2, 4 or 8, but got {bits}.')
+        kept.check_bits(bits)
     _check_p(p)
     if tuple(residual.shape) != tuple(input.shape):
         raise ValueError(f'residual should have the shape of input, {tuple(input.shape)}, but got {tuple(residual.shape)}.')
@@ -416,8 +401,7 @@ def _dropout_add_norm_quantized(centred: bool, input, residual, normalized_shape
         eps = float(torch.finfo(input.dtype).eps if eps is None else eps)
     if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (input, residual, weight, bias)):
         seed = linear._sketch_seed(generator, flat.device) if cabi_x.dropout_threshold(p) > 0 else 0
-        y, h, *_ = _add_kernel_forward(centred, flat.contiguous(), residual.detach().reshape(flat.shape).contiguous(), weight, bias, eps, p, seed=seed, keep=False,
-                                       want_h=prenorm)
+        y, h, *_ = _kernel_forward(centred, flat, weight, bias, eps, seed=seed, keep=False, residual=residual.detach().reshape(flat.shape), p=p, want_h=prenorm)
         return (y.view(input.shape), h.view(input.shape)) if prenorm else y.view(input.shape)
     return _DropoutAddNormQuantized.apply(input, residual, weight, bias, centred, normalized_shape, float(eps), int(bits), p, bool(prenorm), generator)
 
@@ -452,8 +436,7 @@ class _DropoutAddNorm:
 
     def forward(self, input: torch.Tensor, residual: torch.Tensor):
         bias = self.bias if self._centred else None
-        if not self.training and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, residual, self.weight, bias)):
-            # the eval rule of the quantized norms: the dropout is off and the gradients are torch's exact ones on residual + input
+        if not self.training and kept.trains(input, residual, self.weight, bias):     # (eval: the dropout is off, torch's exact gradients on residual + input)
             h = residual + input
             y = _torch_norm(self._centred, h, self.normalized_shape, self.weight, bias, self.eps)
             return (y, h) if self.prenorm else y
