@@ -30,16 +30,12 @@
 
 #include "fewbit_hipx.h"
 #include "fewbit_philox.h"
-
-#define FEWBIT_HIDDEN __attribute__((visibility("hidden")))
+#include "fewbit_unit.h"
 
 namespace fewbit_hip {
-namespace dft {
-FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));          // fewbit_dft.hip (g_last_error)
-}
 namespace crs {
 
-using dft::fail;
+using unit::fail, unit::known_dtype, unit::misaligned, unit::check_dtype, unit::check_seed_word;
 using sketch::Key;
 
 constexpr uint32_t kColsDomain = 4u;        // counter word 3 (0 and 2: the dense sketches, 3: the sampled rows)
@@ -55,7 +51,6 @@ __host__ __device__ __forceinline__ float scale_of(int32_t count, uint32_t in_fe
     return static_cast<float>(static_cast<double>(count) * static_cast<double>(in_features) / static_cast<double>(nopairs));
 }
 
-inline bool known_dtype(int dtype) { return dtype == FEWBIT_F32 || dtype == FEWBIT_F16 || dtype == FEWBIT_BF16; }
 inline bool in_range(size_t in_features, size_t nopairs) { return in_features >= 1 && in_features <= kMaxCols && nopairs >= 1 && nopairs <= kMaxPairs; }
 inline size_t round16(size_t b) { return (b + 15) / 16 * 16; }
 inline size_t cap_max(size_t in_features, size_t nopairs) { return nopairs < in_features ? nopairs : in_features; }
@@ -142,6 +137,7 @@ __global__ __launch_bounds__(kPrepThreads) void crs_prep_kernel(Key value, const
 }
 
 // ---- spread: out[r][j] = idx[j] >= 0 ? src[r][idx[j]] (* scale[j]) : 0 ------------------------------------------------------------------
+// (not fewbit_quantdef.h's Elem: E, the elements of a 16-byte piece; fewbit_moments.hip has the same)
 template <int DT> struct Elem { using type = uint16_t; static constexpr int E = 8; };
 template <> struct Elem<FEWBIT_F32> { using type = uint32_t; static constexpr int E = 4; };
 
@@ -274,16 +270,16 @@ int spread(int dtype, const void *src, size_t rows, size_t ld, const int *idx, c
 // what both entry points check before anything is launched; -> FEWBIT_OK, or the status of the refusal
 inline int check(const char *name, int dtype, size_t rows, size_t in_features, size_t nopairs, size_t cap, const uint64_t *seed_device, const void *workspace,
                  size_t workspace_bytes) {
-    if (!known_dtype(dtype)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: unknown dtype %d", name, dtype);
+    if (const int rc = check_dtype(name, dtype)) return rc;
     if (!in_range(in_features, nopairs))
         return fail(FEWBIT_ERR_UNSUPPORTED, "%s: in_features = %zu, nopairs = %zu has no kernel (1 .. %zu columns, 1 .. %zu pairs)", name, in_features, nopairs,
                     kMaxCols, kMaxPairs);
     if (rows == 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: no rows", name);
     if (cap == 0 || cap > cap_max(in_features, nopairs))
         return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: cap = %zu is not in 1 .. min(nopairs, in_features) = %zu", name, cap, cap_max(in_features, nopairs));
-    if ((reinterpret_cast<uintptr_t>(seed_device) & 7) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the seed word in device memory must be 8-byte aligned", name);
+    if (const int rc = check_seed_word(name, seed_device)) return rc;
     const size_t need = carve(nullptr, in_features, nopairs).bytes;
-    if (workspace == nullptr || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
+    if (workspace == nullptr || workspace_bytes < need || misaligned(workspace, 16))
         return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the workspace must be 16-byte aligned and hold fewbit_hipx_crs_workspace = %zu bytes (got %zu)", name, need,
                     workspace_bytes);
     return FEWBIT_OK;

@@ -29,15 +29,12 @@
 #include "fewbit_fft4.h"
 #include "fewbit_hipx.h"
 
-#define FEWBIT_HIDDEN __attribute__((visibility("hidden")))
-
 namespace fewbit_hip {
 namespace dft {
 
 using namespace dct;
 
-FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
+// (fail, which every unit of the companion library reports through, is declared by fewbit_unit.h and defined below)
 // (both passes: fewbit_fft4.h -- pass_a_kernel / pass_a_zext_kernel on the rows in their order, pass_b_kernel with the epilogue FourierPlanes)
 
 // ---- host side (fewbit_fft4.h: the checks, the dispatch and the LDS opt-in of both pairs) ------------------------------------------

@@ -15,6 +15,7 @@
 
 #include "fewbit_hip.h"
 #include "fewbit_philox.h"
+#include "fewbit_unit.h"
 
 namespace fewbit_hip {
 namespace dct {
@@ -878,7 +879,7 @@ inline size_t workspace_bytes_of(size_t rows, size_t features, size_t proj) { re
 template <int L> constexpr size_t lds_bytes_a(int n) { return (kRowsA * L * C + L + kFine + coarse_entries(n)) * sizeof(f32x2); }
 template <typename EPI, int L> constexpr size_t lds_bytes_b(int n) { return (2 * L * CB + L + (EPI::kTables4N ? kFine + coarse_entries(n) : 0)) * sizeof(f32x2); }
 
-inline bool known_dtype(int dtype) { return dtype == FEWBIT_F32 || dtype == FEWBIT_F16 || dtype == FEWBIT_BF16; }
+using unit::known_dtype;
 inline RowsOfSeed rows_of_seed(uint64_t seed, const uint64_t *device) {
     return RowsOfSeed{sketch::key_of(seed), reinterpret_cast<const sketch::Key *>(device)};
 }

@@ -31,23 +31,12 @@
 
 #pragma clang fp contract(off)
 
-#define FEWBIT_HIDDEN __attribute__((visibility("hidden")))
-
 namespace fewbit_hip {
-namespace dft {
-FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));          // fewbit_dft.hip (g_last_error)
-}
 namespace quant {
 namespace glu {
 
-using dft::fail;
-
-// the plan of fewbit_quant.hip
-constexpr int kThreads = 256;               // lanes per workgroup
-constexpr size_t kMaxGroups = 2048;         // one sweep of the grid: kMaxGroups * kThreads * kBlock = 2^22 elements
-constexpr size_t kMaxCount = size_t{1} << 36;
-
-static_assert(kThreads % kLanes == 0, "a group's lanes never straddle two sweeps of the grid");
+using namespace unit;                       // (named again for the entry points below, which speak of glu::)
+using namespace unit::sweep;                // the plan of fewbit_quant.hip: kThreads, kMaxGroups, grid_of (fewbit_unit.h)
 
 struct ForwardArgs {
     const void *gate, *up;
@@ -353,44 +342,22 @@ __global__ __launch_bounds__(kThreads) void glu_backward_kernel(std::conditional
     }
 }
 
-// workgroups for `lanes` lanes of work
-inline unsigned grid_of(size_t lanes) {
-    const size_t wanted = (lanes + kThreads - 1) / kThreads;
-    return static_cast<unsigned>(wanted < kMaxGroups ? wanted : kMaxGroups);
-}
-
 #ifndef FEWBIT_GLU_TU
 #define FEWBIT_GLU_TU 0
 #endif
 constexpr int kUnitDtype = FEWBIT_GLU_TU == 0 ? FEWBIT_F32 : FEWBIT_GLU_TU == 1 ? FEWBIT_F16 : FEWBIT_BF16;
 
-template <int DT, int ACT, int BITS> void launch(bool vec, unsigned grid, hipStream_t s, const ForwardArgs &a) {
-    if (vec) hipLaunchKernelGGL((glu_forward_kernel<DT, ACT, BITS, true>), dim3(grid), dim3(kThreads), 0, s, a);
-    else hipLaunchKernelGGL((glu_forward_kernel<DT, ACT, BITS, false>), dim3(grid), dim3(kThreads), 0, s, a);
-}
-template <int DT, int ACT, int BITS> void launch(bool vec, unsigned grid, hipStream_t s, const BackwardArgs &a) {
-    if constexpr (BITS != 0) {
-        if (vec) hipLaunchKernelGGL((glu_backward_kernel<DT, ACT, BITS, true, false>), dim3(grid), dim3(kThreads), 0, s, a);
-        else hipLaunchKernelGGL((glu_backward_kernel<DT, ACT, BITS, false, false>), dim3(grid), dim3(kThreads), 0, s, a);
-    }
-}
-template <int DT, int ACT, int BITS> void launch(bool vec, unsigned grid, hipStream_t s, const ProductArgs &a) {
-    if constexpr (BITS != 0) {
-        if (vec) hipLaunchKernelGGL((glu_backward_kernel<DT, ACT, BITS, true, true>), dim3(grid), dim3(kThreads), 0, s, a);
-        else hipLaunchKernelGGL((glu_backward_kernel<DT, ACT, BITS, false, true>), dim3(grid), dim3(kThreads), 0, s, a);
-    }
-}
-template <int DT, int ACT, class Args> void launch_bits(int bits, bool vec, unsigned grid, hipStream_t s, const Args &a) {
-    if (bits == 0) launch<DT, ACT, 0>(vec, grid, s, a);
-    else if (bits == 2) launch<DT, ACT, 2>(vec, grid, s, a);
-    else if (bits == 4) launch<DT, ACT, 4>(vec, grid, s, a);
-    else launch<DT, ACT, 8>(vec, grid, s, a);
-}
+// the kernel of a call, by its record of arguments: the forward (bits = 0: the plain one), the backward or the PRODUCT backward (bits = 0: no kernel)
+// (vec before not: the order in which a unit first names its kernels is their order in the device module, fewbit_quant.hip)
 template <int DT, class Args> void launch_act(int act, int bits, bool vec, unsigned grid, hipStream_t s, const Args &a) {
-    if (act == FEWBIT_SILU) launch_bits<DT, FEWBIT_SILU>(bits, vec, grid, s, a);
-    else launch_bits<DT, FEWBIT_GELU>(bits, vec, grid, s, a);
+    pick<FEWBIT_SILU, FEWBIT_GELU>(act, [&](auto ac) { pick<0, 2, 4, 8>(bits, [&](auto b) { pick<1, 0>(vec, [&](auto v) {
+        constexpr int ACT = decltype(ac)::value, BITS = decltype(b)::value;
+        constexpr bool VEC = decltype(v)::value != 0;
+        if constexpr (std::is_same_v<Args, ForwardArgs>) hipLaunchKernelGGL((glu_forward_kernel<DT, ACT, BITS, VEC>), dim3(grid), dim3(kThreads), 0, s, a);
+        else if constexpr (BITS != 0)
+            hipLaunchKernelGGL((glu_backward_kernel<DT, ACT, BITS, VEC, std::is_same_v<Args, ProductArgs>>), dim3(grid), dim3(kThreads), 0, s, a);
+    }); }); });
 }
-// (bits = 0: the plain forward)
 template <int DT> FEWBIT_HIDDEN void launch_forward(int act, int bits, bool vec, unsigned grid, hipStream_t s, const ForwardArgs &a);
 template <int DT> FEWBIT_HIDDEN void launch_backward(int act, int bits, bool vec, unsigned grid, hipStream_t s, const BackwardArgs &a);
 template <int DT> FEWBIT_HIDDEN void launch_product(int act, int bits, bool vec, unsigned grid, hipStream_t s, const ProductArgs &a);
@@ -406,18 +373,12 @@ template <> void launch_product<kUnitDtype>(int act, int bits, bool vec, unsigne
 }
 
 #if FEWBIT_GLU_TU == 0
-inline bool misaligned(const void *p, size_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
-
 // bytes of one part: the packed form, filled up to a multiple of 8 (0: no state for these arguments)
-inline size_t part_bytes(size_t n, int bits) {
-    if (!known_bits(bits) || n == 0 || n > kMaxCount) return 0;
-    const size_t used = 8 * ((n + kGroup - 1) / kGroup) + static_cast<size_t>(bits) * ((n + kBlock - 1) / kBlock);
-    return (used + 7) & ~size_t{7};
-}
+inline size_t part_bytes(size_t n, int bits) { return known_bits(bits) && n != 0 && n <= kMaxCount ? (packed_bytes(n, bits) + 7) & ~size_t{7} : 0; }
 
 // what both launches refuse alike: -> 0 to go on with n set, 1 for rows = 0 (FEWBIT_OK, no launch), a negative status otherwise
 int shape_of(const char *name, int dtype, int act, size_t rows, size_t width, size_t &n) {
-    if (!known_dtype(dtype)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: unknown dtype %d", name, dtype);
+    if (const int rc = check_dtype(name, dtype)) return rc;
     if (act != FEWBIT_SILU && act != FEWBIT_GELU) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: activation %d is neither FEWBIT_SILU nor FEWBIT_GELU", name, act);
     if (rows == 0) return 1;
     if (width == 0 || rows > kMaxCount || width > kMaxCount || rows * width > kMaxCount)
@@ -443,19 +404,19 @@ static int backward_call(const char *name, bool with_product, int dtype, int act
     using glu::fail;
     using glu::misaligned;
     size_t n = 0;
-    if (!quant::known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: bits = %d is not 2, 4 or 8", name, bits);
+    if (const int rc = quant::check_bits(name, bits)) return rc;
     const int shape = glu::shape_of(name, dtype, act, rows, width, n);
     if (shape != 0) return shape < 0 ? shape : FEWBIT_OK;
     if ((d_gate != nullptr && ld_dgate < width) || (d_up != nullptr && ld_dup < width) || (product != nullptr && ld_product < width))
         return with_product ? fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: a row stride (%zu, %zu, %zu) is below the width %zu", name, ld_dgate, ld_dup, ld_product, width)
                             : fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: a row stride (%zu, %zu) is below the width %zu", name, ld_dgate, ld_dup, width);
-    if (state == nullptr || (gy == nullptr && !with_product)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer", name);
+    if (state == nullptr || (gy == nullptr && !with_product)) return glu::refuse_null(name);
     if (gy == nullptr && (d_gate != nullptr || d_up != nullptr))
         return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: gy is a null pointer and a gradient is wanted (gy may be absent only with d_gate and d_up)", name);
     const size_t item = quant::size_of(dtype);
     if (misaligned(gy, item) || misaligned(d_gate, item) || misaligned(d_up, item) || misaligned(product, item))
         return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: gy, d_gate%s must be aligned to their element size", name, with_product ? ", d_up and product" : " and d_up");
-    if (misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: state must be 8-byte aligned", name);
+    if (const int rc = glu::check_aligned8(name, "state", state)) return rc;
     if (d_gate == nullptr && d_up == nullptr && product == nullptr) return FEWBIT_OK;
     if (rows == 1) ld_dgate = ld_dup = ld_product = width;
     const auto wide = [&](const void *p, size_t ld) { return p == nullptr || ((ld * item) % 16 == 0 && !misaligned(p, 16)); };
@@ -463,12 +424,10 @@ static int backward_call(const char *name, bool with_product, int dtype, int act
     const glu::ProductArgs a{{gy, state, glu::part_bytes(n, bits), width, n, d_gate, d_up, ld_dgate, ld_dup}, product, ld_product};
     const unsigned grid = glu::grid_of((n + quant::kBlock - 1) / quant::kBlock);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const glu::BackwardArgs &plain = a;
-    switch (dtype) {
-    case FEWBIT_F32: with_product ? glu::launch_product<FEWBIT_F32>(act, bits, vec, grid, s, a) : glu::launch_backward<FEWBIT_F32>(act, bits, vec, grid, s, plain); break;
-    case FEWBIT_F16: with_product ? glu::launch_product<FEWBIT_F16>(act, bits, vec, grid, s, a) : glu::launch_backward<FEWBIT_F16>(act, bits, vec, grid, s, plain); break;
-    default: with_product ? glu::launch_product<FEWBIT_BF16>(act, bits, vec, grid, s, a) : glu::launch_backward<FEWBIT_BF16>(act, bits, vec, grid, s, plain); break;
-    }
+    glu::pick_dtype(dtype, [&](auto dt) {
+        if (with_product) glu::launch_product<decltype(dt)::value>(act, bits, vec, grid, s, a);
+        else glu::launch_backward<decltype(dt)::value>(act, bits, vec, grid, s, a);
+    });
     return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
 }
 
@@ -477,11 +436,10 @@ extern "C" {
 size_t fewbit_hipx_glu_state_bytes(size_t n, int bits) { return 2 * glu::part_bytes(n, bits); }
 
 int fewbit_hipx_glu_state_host(const float *gate_host, const float *up_host, size_t n, int bits, uint64_t seed, uint8_t *out_host) {
-    using glu::fail;
-    if (!quant::known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_state_host: bits = %d is not 2, 4 or 8", bits);
+    if (const int rc = quant::check_bits("glu_state_host", bits)) return rc;
     if (n == 0) return FEWBIT_OK;
-    if (n > glu::kMaxCount) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_state_host: n = %zu is beyond 2^36", n);
-    if (gate_host == nullptr || up_host == nullptr || out_host == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_state_host: null pointer");
+    if (const int rc = glu::check_count("glu_state_host", n)) return rc;
+    if (gate_host == nullptr || up_host == nullptr || out_host == nullptr) return glu::refuse_null("glu_state_host");
     const size_t groups = (n + quant::kGroup - 1) / quant::kGroup, part = glu::part_bytes(n, bits), stride = static_cast<size_t>(bits) * quant::kLanes;
     const Key key = fewbit_hip::sketch::key_of(seed);
     std::memset(out_host, 0, 2 * part);
@@ -499,17 +457,19 @@ int fewbit_hipx_glu_forward(int dtype, int act, const void *gate, size_t ld_gate
     using glu::fail;
     using glu::misaligned;
     size_t n = 0;
-    if (state != nullptr && !quant::known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_forward: bits = %d is not 2, 4 or 8", bits);
-    if (state != nullptr && misaligned(seed_device, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_forward: the seed word in device memory must be 8-byte aligned");
+    if (state != nullptr) {
+        if (const int rc = quant::check_bits("glu_forward", bits)) return rc;
+        if (const int rc = glu::check_seed_word("glu_forward", seed_device)) return rc;
+    }
     const int shape = glu::shape_of("glu_forward", dtype, act, rows, width, n);
     if (shape != 0) return shape < 0 ? shape : FEWBIT_OK;
     if (ld_gate < width || ld_up < width) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_forward: a row stride (%zu, %zu) is below the width %zu", ld_gate, ld_up, width);
-    if (gate == nullptr || up == nullptr || y == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_forward: null pointer");
+    if (gate == nullptr || up == nullptr || y == nullptr) return glu::refuse_null("glu_forward");
     const size_t item = quant::size_of(dtype);
     if (misaligned(gate, item) || misaligned(up, item) || misaligned(y, item)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_forward: gate, up and y must be aligned to their element size");
     const size_t part = state != nullptr ? glu::part_bytes(n, bits) : 0;
-    if (state != nullptr && misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_forward: state must be 8-byte aligned");
-    if (state != nullptr && state_bytes < 2 * part) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "glu_forward: state has %zu bytes, %zu are needed", state_bytes, 2 * part);
+    if (const int rc = glu::check_aligned8("glu_forward", "state", state)) return rc;                   // (no state: a null pointer is aligned, and 0 bytes are needed)
+    if (const int rc = glu::check_bytes("glu_forward", "state", state_bytes, 2 * part)) return rc;
     // (one row: the stride is never used, and the row is the flat tensor)
     if (rows == 1) ld_gate = ld_up = width;
     const bool vec = width % 8 == 0 && (ld_gate * item) % 16 == 0 && (ld_up * item) % 16 == 0 && !misaligned(gate, 16) && !misaligned(up, 16) && !misaligned(y, 16);
@@ -517,11 +477,7 @@ int fewbit_hipx_glu_forward(int dtype, int act, const void *gate, size_t ld_gate
     const unsigned grid = glu::grid_of((n + quant::kGroup - 1) / quant::kGroup * quant::kLanes);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int kept = state != nullptr ? bits : 0;
-    switch (dtype) {
-    case FEWBIT_F32: glu::launch_forward<FEWBIT_F32>(act, kept, vec, grid, s, a); break;
-    case FEWBIT_F16: glu::launch_forward<FEWBIT_F16>(act, kept, vec, grid, s, a); break;
-    default: glu::launch_forward<FEWBIT_BF16>(act, kept, vec, grid, s, a); break;
-    }
+    glu::pick_dtype(dtype, [&](auto dt) { glu::launch_forward<decltype(dt)::value>(act, kept, vec, grid, s, a); });
     return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "glu_forward: the launch failed");
 }
 

@@ -34,16 +34,12 @@
 #include <cstdint>
 
 #include "fewbit_hipx.h"
-
-#define FEWBIT_HIDDEN __attribute__((visibility("hidden")))
+#include "fewbit_unit.h"
 
 namespace fewbit_hip {
-namespace dft {
-FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));          // fewbit_dft.hip (g_last_error)
-}
 namespace moments {
 
-using dft::fail;
+using unit::fail, unit::known_dtype, unit::misaligned, unit::size_of;
 
 // (tuning builds: -DFEWBIT_MOMENTS_MAX_GROUPS / _MIN_ROWS / _UNROLL; the contract, the header and the tests speak of the defaults)
 #ifndef FEWBIT_MOMENTS_MAX_GROUPS
@@ -72,9 +68,7 @@ inline Plan plan(size_t rows, size_t at_least) {
     return Plan{per, (rows + per - 1) / per};
 }
 
-inline bool known_dtype(int dtype) { return dtype == FEWBIT_F32 || dtype == FEWBIT_F16 || dtype == FEWBIT_BF16; }
-inline size_t size_of(int dtype) { return dtype == FEWBIT_F32 ? 4 : 2; }
-
+// (not fewbit_quantdef.h's Elem: E, the elements of a 16-byte piece, and a widening to double; fewbit_crs.hip has the same with one to float)
 template <int DT> struct Elem { using type = uint16_t; static constexpr int E = 8; };
 template <> struct Elem<FEWBIT_F32> { using type = uint32_t; static constexpr int E = 4; };
 
@@ -209,7 +203,7 @@ template <int DX> int launch_rows(int dtype_g, const void *x, size_t n, size_t l
 }
 
 inline int check_workspace(const char *name, const void *workspace, size_t workspace_bytes) {
-    if (workspace == nullptr || workspace_bytes < kWorkspaceBytes || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
+    if (workspace == nullptr || workspace_bytes < kWorkspaceBytes || misaligned(workspace, 16))
         return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the workspace must be 16-byte aligned and hold fewbit_hipx_moments_workspace = %zu bytes (got %zu)", name,
                     kWorkspaceBytes, workspace_bytes);
     return FEWBIT_OK;
@@ -240,7 +234,7 @@ int fewbit_hipx_row_moments(int dtype_x, const void *x, size_t n, size_t ldx, in
     if (ldx > kMaxRows) return fail(FEWBIT_ERR_UNSUPPORTED, "row_moments: ldx = %zu is beyond %zu", ldx, kMaxRows);
     if (ldg > kMaxRows) return fail(FEWBIT_ERR_UNSUPPORTED, "row_moments: ldg = %zu is beyond %zu", ldg, kMaxRows);
     if (x == nullptr || g == nullptr || out3 == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "row_moments: null pointer");
-    if (reinterpret_cast<uintptr_t>(x) % size_of(dtype_x) != 0 || reinterpret_cast<uintptr_t>(g) % size_of(dtype_g) != 0 || (reinterpret_cast<uintptr_t>(out3) & 7) != 0)
+    if (misaligned(x, size_of(dtype_x)) || misaligned(g, size_of(dtype_g)) || misaligned(out3, 8))
         return fail(FEWBIT_ERR_INVALID_ARGUMENT, "row_moments: x and g must be aligned to their element size, out3 to 8 bytes");
     if (const int rc = check_workspace("row_moments", workspace, workspace_bytes)) return rc;
     const Plan p = plan(rows, kMinRows);
@@ -261,7 +255,7 @@ int fewbit_hipx_sum_squares(int dtype, const void *t, size_t count, double *out1
     if (!known_dtype(dtype)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sum_squares: unknown dtype %d", dtype);
     if (count == 0 || count > kMaxRows) return fail(FEWBIT_ERR_UNSUPPORTED, "sum_squares: count = %zu has no kernel (1 .. %zu elements)", count, kMaxRows);
     if (t == nullptr || out1 == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sum_squares: null pointer");
-    if (reinterpret_cast<uintptr_t>(t) % size_of(dtype) != 0 || (reinterpret_cast<uintptr_t>(out1) & 7) != 0)
+    if (misaligned(t, size_of(dtype)) || misaligned(out1, 8))
         return fail(FEWBIT_ERR_INVALID_ARGUMENT, "sum_squares: t must be aligned to its element size, out1 to 8 bytes");
     if (const int rc = check_workspace("sum_squares", workspace, workspace_bytes)) return rc;
     const size_t pieces = (count + kPiece - 1) / kPiece;

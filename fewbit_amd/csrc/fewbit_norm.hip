@@ -50,19 +50,13 @@
 
 #pragma clang fp contract(off)
 
-#define FEWBIT_HIDDEN __attribute__((visibility("hidden")))
-
 namespace fewbit_hip {
-namespace dft {
-FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));          // fewbit_dft.hip (g_last_error)
-}
 namespace norm {
 
-using namespace quant;
-using dft::fail;
+using namespace quant;                      // (and with it fewbit_unit.h: fail, the predicates, the mask of a seed, the refusals, pick)
 
 constexpr int kThreads = 256, kBackwardThreads = 1024;       // lanes per workgroup, forward and backward
-constexpr size_t kMaxWidth = 8192, kMaxCount = size_t{1} << 36;
+constexpr size_t kMaxWidth = 8192;
 constexpr size_t kMaxGridForward = 16384, kMaxGridBackward = 512;
 constexpr int kMirrorSixteen = 0x140;       // row_mirror: by then both halves of the 16 lanes hold their own result
 
@@ -160,7 +154,7 @@ __device__ __forceinline__ bool aligned16(const void *p) { return (reinterpret_c
 // include/fewbit_hipx.h).  The mask is fewbit_dropout.hip's (counter word 3 = 5, one Philox call per block of eight FLAT elements), which a lane's
 // block of a row is only where width % 8 == 0: block b of row r is then flat block r * (width / 8) + b, the number the rounding bits take too.
 // The kernels gain it as a compile-time switch -- a trailing pack of arguments that is empty (the plain kernels) or one record.
-constexpr uint32_t kMaskDomain = 5u, kOne = 65536u;         // thresholds are in units of 2^-16
+// (kMaskDomain, kOne, mask_bits and scale_of: fewbit_unit.h, the text fewbit_dropout.hip evaluates)
 struct NoFusion {};
 struct ForwardFusion { const void *residual; void *h_out; uint32_t threshold; float scale; };       // h_out: NULL, or where h is written
 // (the backward's `dx` is dres; gh: NULL, or the gradient that arrives at h; dbranch: NULL, or -- with threshold > 0 -- the input's gradient)
@@ -171,9 +165,9 @@ template <class F> __device__ __forceinline__ const F &the_fusion(const F &f) { 
 // the 16 mask bits of the eight elements of flat block q; threshold 0 keeps everything and draws nothing
 __device__ __forceinline__ void mask_words(uint64_t q, Key key, uint32_t threshold, uint32_t (&w)[4]) {
     w[0] = w[1] = w[2] = w[3] = ~0u;
-    if (threshold != 0) sketch::philox4x32(static_cast<uint32_t>(q), static_cast<uint32_t>(q >> 32), 0u, kMaskDomain, key, w);
+    if (threshold != 0) block_words<kMaskDomain>(q, key, w);
 }
-__device__ __forceinline__ bool kept(const uint32_t (&w)[4], int e, uint32_t threshold) { return ((w[e >> 1] >> (16 * (e & 1))) & 0xffffu) >= threshold; }
+__device__ __forceinline__ bool kept(const uint32_t (&w)[4], int e, uint32_t threshold) { return mask_bits(w, e) >= threshold; }
 
 // eight elements as they lie in memory; the missing ones are 0
 template <int DT> __device__ __forceinline__ void load_raw(const typename Elem<DT>::type *p, bool vec, int have, typename Elem<DT>::type (&raw)[kBlock]) {
@@ -195,7 +189,9 @@ template <int DT> __device__ __forceinline__ void store_raw(typename Elem<DT>::t
     }
 }
 // h = keep ? narrow(widen(x) scale + widen(res)) : res -- `one<DT, true>` of fewbit_dropout.hip: the product and the sum are fp32 values of their
-// own (an fp16 operand's conversion, the arithmetic and the rounding must not meet in one v_fma_mix*, which is one step off at the ties)
+// own (an fp16 operand's conversion, the arithmetic and the rounding must not meet in one v_fma_mix*, which is one step off at the ties).  The two
+// texts stay apart: narrow<FEWBIT_F16> has the barrier that `one` places itself, and units 4 and 7 written through `one` change 98 of 98 kernels
+// (a plain forward: 483 -> 519 instructions, EXPERIMENTS.md 8.27)
 template <int DT> __device__ __forceinline__ typename Elem<DT>::type dropped_sum(typename Elem<DT>::type x, typename Elem<DT>::type res, bool keep, float scale) {
     float v = mul_rn(float_of_bits(widen<DT>(x)), scale);
     if constexpr (DT == FEWBIT_F16) asm("" : "+v"(v));
@@ -566,15 +562,6 @@ template <int DT, int BITS, int LPR, int K, bool CENTRED, bool FUSED> void launc
         hipLaunchKernelGGL((forward_kernel<DT, BITS, LPR, K, CENTRED>), dim3(grid), dim3(kThreads), 0, s, a.x, a.rows, a.width, a.gamma, a.beta, a.eps, a.key, a.device,
                            a.y, a.rstd, a.state, a.xhat);
 }
-template <int DT, int BITS, bool CENTRED, bool FUSED> void launch_plan(Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
-    if (p.lpr == 8) launch<DT, BITS, 8, 1, CENTRED, FUSED>(grid, s, a);
-    else if (p.lpr == 16) launch<DT, BITS, 16, 1, CENTRED, FUSED>(grid, s, a);
-    else if (p.lpr == 64) launch<DT, BITS, 64, 1, CENTRED, FUSED>(grid, s, a);
-    else if (p.lpr == 128) launch<DT, BITS, 128, 1, CENTRED, FUSED>(grid, s, a);
-    else if (p.k == 1) launch<DT, BITS, 256, 1, CENTRED, FUSED>(grid, s, a);
-    else if (p.k == 2) launch<DT, BITS, 256, 2, CENTRED, FUSED>(grid, s, a);
-    else launch<DT, BITS, 256, 4, CENTRED, FUSED>(grid, s, a);
-}
 template <int DT, int BITS, int LPR, bool CENTRED, bool FUSED> void launch_backward_lanes(unsigned grid, hipStream_t s, const BackwardArgs &a) {
     if constexpr (BITS != 0 && FUSED)
         hipLaunchKernelGGL((backward_kernel<DT, BITS, LPR, CENTRED, BackwardFusion>), dim3(grid), dim3(kBackwardThreads), 0, s, a.gy, a.state, a.rstd, a.gamma, a.rows,
@@ -583,20 +570,17 @@ template <int DT, int BITS, int LPR, bool CENTRED, bool FUSED> void launch_backw
         hipLaunchKernelGGL((backward_kernel<DT, BITS, LPR, CENTRED>), dim3(grid), dim3(kBackwardThreads), 0, s, a.gy, a.state, a.rstd, a.gamma, a.rows, a.width, a.dx,
                            a.partials);
 }
-template <int DT, int BITS, bool CENTRED, bool FUSED> void launch_plan(Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
-    if (p.lpr == 8) launch_backward_lanes<DT, BITS, 8, CENTRED, FUSED>(grid, s, a);
-    else if (p.lpr == 16) launch_backward_lanes<DT, BITS, 16, CENTRED, FUSED>(grid, s, a);
-    else if (p.lpr == 64) launch_backward_lanes<DT, BITS, 64, CENTRED, FUSED>(grid, s, a);
-    else if (p.lpr == 128) launch_backward_lanes<DT, BITS, 128, CENTRED, FUSED>(grid, s, a);
-    else if (p.lpr == 256) launch_backward_lanes<DT, BITS, 256, CENTRED, FUSED>(grid, s, a);
-    else if (p.lpr == 512) launch_backward_lanes<DT, BITS, 512, CENTRED, FUSED>(grid, s, a);
-    else launch_backward_lanes<DT, BITS, 1024, CENTRED, FUSED>(grid, s, a);
+// the kernel of a plan (plan_of, backward_plan_of: a lane has more than one block only where a row takes a forward workgroup's 256 lanes)
+template <int DT, bool CENTRED, bool FUSED> void launch_bits(int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
+    pick<0, 2, 4, 8>(bits, [&](auto b) { pick<8, 16, 64, 128, 256>(p.lpr, [&](auto lpr) { pick<1, 2, 4>(p.k, [&](auto k) {
+        constexpr int LPR = decltype(lpr)::value, K = decltype(k)::value;
+        if constexpr (LPR == 256 || K == 1) launch<DT, decltype(b)::value, LPR, K, CENTRED, FUSED>(grid, s, a);
+    }); }); });
 }
-template <int DT, bool CENTRED, bool FUSED, class Args> void launch_bits(int bits, Plan p, unsigned grid, hipStream_t s, const Args &a) {
-    if (bits == 0) launch_plan<DT, 0, CENTRED, FUSED>(p, grid, s, a);
-    else if (bits == 2) launch_plan<DT, 2, CENTRED, FUSED>(p, grid, s, a);
-    else if (bits == 4) launch_plan<DT, 4, CENTRED, FUSED>(p, grid, s, a);
-    else launch_plan<DT, 8, CENTRED, FUSED>(p, grid, s, a);
+template <int DT, bool CENTRED, bool FUSED> void launch_bits(int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
+    pick<0, 2, 4, 8>(bits, [&](auto b) { pick<8, 16, 64, 128, 256, 512, 1024>(p.lpr, [&](auto lpr) {
+        launch_backward_lanes<DT, decltype(b)::value, decltype(lpr)::value, CENTRED, FUSED>(grid, s, a);
+    }); });
 }
 template <int DT, bool CENTRED, bool FUSED> FEWBIT_HIDDEN void launch_forward(int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a);
 template <int DT, bool CENTRED, bool FUSED> FEWBIT_HIDDEN void launch_backward(int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a);
@@ -609,21 +593,11 @@ template <> void launch_backward<kUnitDtype, kUnitCentred, kUnitFused>(int bits,
 
 #if FEWBIT_NORM_TU == 0
 template <bool CENTRED, bool FUSED> void launch_dtype(int dtype, int bits, Plan p, unsigned grid, hipStream_t s, const ForwardArgs &a) {
-    switch (dtype) {
-    case FEWBIT_F32: launch_forward<FEWBIT_F32, CENTRED, FUSED>(bits, p, grid, s, a); break;
-    case FEWBIT_F16: launch_forward<FEWBIT_F16, CENTRED, FUSED>(bits, p, grid, s, a); break;
-    default: launch_forward<FEWBIT_BF16, CENTRED, FUSED>(bits, p, grid, s, a); break;
-    }
+    pick_dtype(dtype, [&](auto dt) { launch_forward<decltype(dt)::value, CENTRED, FUSED>(bits, p, grid, s, a); });
 }
 template <bool CENTRED, bool FUSED> void launch_dtype(int dtype, int bits, Plan p, unsigned grid, hipStream_t s, const BackwardArgs &a) {
-    switch (dtype) {
-    case FEWBIT_F32: launch_backward<FEWBIT_F32, CENTRED, FUSED>(bits, p, grid, s, a); break;
-    case FEWBIT_F16: launch_backward<FEWBIT_F16, CENTRED, FUSED>(bits, p, grid, s, a); break;
-    default: launch_backward<FEWBIT_BF16, CENTRED, FUSED>(bits, p, grid, s, a); break;
-    }
+    pick_dtype(dtype, [&](auto dt) { launch_backward<decltype(dt)::value, CENTRED, FUSED>(bits, p, grid, s, a); });
 }
-
-inline bool misaligned(const void *p, size_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
 
 // the refusals of a shape that every entry point shares, host and device; 1: nothing to do
 int check_extent(const char *name, size_t rows, size_t width) {
@@ -634,16 +608,15 @@ int check_extent(const char *name, size_t rows, size_t width) {
 }
 // the device entry points: the dtype first
 int check_shape(const char *name, int dtype, size_t rows, size_t width) {
-    if (!known_dtype(dtype)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: unknown dtype %d", name, dtype);
+    if (const int rc = check_dtype(name, dtype)) return rc;
     return check_extent(name, rows, width);
 }
 // the host entry points: the bits first, the pointers last
 int check_host(const char *name, size_t rows, size_t width, int bits, const void *from, const void *to) {
-    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: bits = %d is not 2, 4 or 8", name, bits);
+    if (const int rc = check_bits(name, bits)) return rc;
     const int shape = check_extent(name, rows, width);
     if (shape != FEWBIT_OK) return shape;
-    if (from == nullptr || to == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer", name);
-    return FEWBIT_OK;
+    return from == nullptr || to == nullptr ? refuse_null(name) : FEWBIT_OK;
 }
 
 // what the fused entry points refuse on top, forward and backward: a threshold that drops everything or more, and a mask on rows whose blocks of
@@ -654,7 +627,6 @@ int check_threshold(const char *name, uint32_t threshold, size_t width) {
         return fail(FEWBIT_ERR_UNSUPPORTED, "%s: a mask (threshold = %u) needs a width that is a multiple of 8, not %zu", name, threshold, width);
     return FEWBIT_OK;
 }
-inline float scale_of(uint32_t threshold) { return static_cast<float>(65536.0 / static_cast<double>(kOne - threshold)); }     // (fewbit_dropout.hip's)
 
 // the forward entry point of either norm: the refusals, the plan, ONE launch (the RMS norm: beta = NULL); `add`: the fused call's residual, h_out and
 // threshold (its scale is filled in here), NULL for the plain one
@@ -668,9 +640,10 @@ int forward_call(const char *name, int dtype, const void *x, size_t rows, size_t
         const int refused = check_threshold(name, add->threshold, width);
         if (refused != FEWBIT_OK) return refused;
     }
-    if (state != nullptr && !known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: bits = %d is not 2, 4 or 8", name, bits);
+    if (state != nullptr)
+        if (const int rc = check_bits(name, bits)) return rc;
     if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: eps = %g is not a finite number >= 0", name, eps);
-    if (misaligned(seed_device, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the seed word in device memory must be 8-byte aligned", name);
+    if (const int rc = check_seed_word(name, seed_device)) return rc;
     if (shape == 1) return FEWBIT_OK;
     if (x == nullptr || y == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (x or y)", name);
     if (add != nullptr && add->residual == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (residual)", name);
@@ -681,11 +654,9 @@ int forward_call(const char *name, int dtype, const void *x, size_t rows, size_t
     if (add != nullptr && (misaligned(add->residual, size) || misaligned(add->h_out, size)))
         return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: residual and h_out must be aligned to their element size", name);
     if (misaligned(rstd, 4) || misaligned(xhat_out, 4)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: rstd and xhat_out must be 4-byte aligned", name);
-    if (misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: state must be 8-byte aligned", name);
-    if (state != nullptr) {
-        const size_t need = state_bytes_of(rows, width, bits);
-        if (state_bytes < need) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: state has %zu bytes, %zu are needed", name, state_bytes, need);
-    }
+    if (const int rc = check_aligned8(name, "state", state)) return rc;
+    if (state != nullptr)
+        if (const int rc = check_bytes(name, "state", state_bytes, state_bytes_of(rows, width, bits))) return rc;
     const Plan p = plan_of(width);
     const size_t tiles = tiles_of(rows, p, kThreads);
     const unsigned grid = static_cast<unsigned>(tiles < kMaxGridForward ? tiles : kMaxGridForward);
@@ -713,10 +684,10 @@ int backward_call(const char *name, int dtype, const void *gy, const uint8_t *st
         if (refused != FEWBIT_OK) return refused;
         if (add->dbranch != nullptr && add->threshold == 0)
             return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: with threshold = 0 dbranch is dres: pass dbranch = NULL", name);
-        if (misaligned(add->device, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the seed word in device memory must be 8-byte aligned", name);
+        if (const int rc = check_seed_word(name, add->device)) return rc;
     }
     void *const dbranch = add != nullptr ? add->dbranch : nullptr;
-    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: bits = %d is not 2, 4 or 8", name, bits);
+    if (const int rc = check_bits(name, bits)) return rc;
     if (shape == 1) return FEWBIT_OK;
     if (gy == nullptr || state == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (gy or state)", name);
     if ((dx != nullptr || dbranch != nullptr) && rstd == nullptr)
@@ -728,12 +699,12 @@ int backward_call(const char *name, int dtype, const void *gy, const uint8_t *st
         return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: gh and dbranch must be aligned to their element size", name);
     if (misaligned(rstd, 4) || misaligned(dgamma, 4) || misaligned(dbeta, 4))
         return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", name, CENTRED ? "rstd, dgamma and dbeta" : "rstd and dgamma");
-    if (misaligned(state, 8)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: state must be 8-byte aligned", name);
+    if (const int rc = check_aligned8(name, "state", state)) return rc;
     const bool sums = dgamma != nullptr || dbeta != nullptr;
     if (dx == nullptr && dbranch == nullptr && !sums) return FEWBIT_OK;
-    const size_t need = workspace_of(rows, width);
     if (sums && (workspace == nullptr || misaligned(workspace, 16))) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the workspace must be 16-byte aligned", name);
-    if (sums && workspace_bytes < need) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: the workspace has %zu bytes, %zu are needed", name, workspace_bytes, need);
+    if (sums)
+        if (const int rc = check_bytes(name, "the workspace", workspace_bytes, workspace_of(rows, width))) return rc;
     const Plan p = backward_plan_of(width);
     const size_t tiles = tiles_of(rows, p, kBackwardThreads);
     const unsigned grid = static_cast<unsigned>(tiles < kMaxGridBackward ? tiles : kMaxGridBackward);

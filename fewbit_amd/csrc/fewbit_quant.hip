@@ -13,8 +13,9 @@
 // that holds the tail -- the same arithmetic either way, so the same bytes.  Code words leave as one dword per lane pair (2 bits), per lane
 // (4 bits) or two (8 bits), the parameters as 8 bytes from the first lane of a group: ordinary vector stores.
 // Unpack: ONE launch; a lane reads its code word and its group's parameters and writes its block as 16-byte pieces.
-// Plan of both (a pure function of n): blocks = ceil(n / 8), workgroups of 256 lanes (32 groups), at most kMaxGroups of them; beyond that a
-// lane sweeps on by the grid's width.
+// Plan of both (a pure function of n; fewbit_unit.h, `sweep`): blocks = ceil(n / 8), workgroups of 256 lanes (32 groups), at most kMaxGroups of
+// them; beyond that a lane sweeps on by the grid's width.  The refusals the entry points share with the other units and the dispatcher that names
+// the kernel of a call (pick) are fewbit_unit.h's too.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,28 +28,14 @@
 
 #pragma clang fp contract(off)
 
-#define FEWBIT_HIDDEN __attribute__((visibility("hidden")))
-
 namespace fewbit_hip {
-namespace dft {
-FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));          // fewbit_dft.hip (g_last_error)
-}
 namespace quant {
 
-using dft::fail;
-
 // (the definition itself -- lo, step, inv, code_of, decode, the poison rule, the rounding bits -- and the lane moves: fewbit_quantdef.h, the
-// text fewbit_norm.hip evaluates too)
-constexpr int kThreads = 256;               // lanes per workgroup
-constexpr size_t kMaxGroups = 2048;         // one sweep of the grid: kMaxGroups * kThreads * kBlock = 2^22 elements
-constexpr size_t kMaxCount = size_t{1} << 36;
+// text fewbit_norm.hip evaluates too; the plan -- kThreads, kMaxGroups, grid_of -- and the refusals: fewbit_unit.h)
+using namespace unit::sweep;
 
-static_assert(kThreads % kLanes == 0, "a group's lanes never straddle two sweeps of the grid");
-
-inline size_t bytes_of(size_t n, int bits) {
-    if (!known_bits(bits) || n == 0 || n > kMaxCount) return 0;
-    return 8 * ((n + kGroup - 1) / kGroup) + static_cast<size_t>(bits) * ((n + kBlock - 1) / kBlock);
-}
+inline size_t bytes_of(size_t n, int bits) { return known_bits(bits) && n != 0 && n <= kMaxCount ? packed_bytes(n, bits) : 0; }
 
 // VEC: src is 16-byte aligned, so every whole block is.  out: 8-byte aligned; the parameters of group g at 8 g, the code word of block b at
 // 8 groups + BITS b.
@@ -143,30 +130,18 @@ __global__ __launch_bounds__(kThreads) void unpack_kernel(const uint8_t *__restr
     }
 }
 
-template <int DT, int BITS> void launch_pack(bool vec, unsigned groups, hipStream_t s, const void *src, size_t n, Key key, const Key *device, uint8_t *out) {
-    if (vec) hipLaunchKernelGGL((pack_kernel<DT, BITS, true>), dim3(groups), dim3(kThreads), 0, s, src, n, key, device, out);
-    else hipLaunchKernelGGL((pack_kernel<DT, BITS, false>), dim3(groups), dim3(kThreads), 0, s, src, n, key, device, out);
-}
-template <int DT> void launch_pack(int bits, bool vec, unsigned groups, hipStream_t s, const void *src, size_t n, Key key, const Key *device, uint8_t *out) {
-    if (bits == 2) launch_pack<DT, 2>(vec, groups, s, src, n, key, device, out);
-    else if (bits == 4) launch_pack<DT, 4>(vec, groups, s, src, n, key, device, out);
-    else launch_pack<DT, 8>(vec, groups, s, src, n, key, device, out);
+// f(dtype, bits, vec as compile-time constants) for the kernel of a call (vec before not: the order in which a unit first names its kernels is their
+// order in the device module, and the code of the first and the last of them depends on it, EXPERIMENTS.md 8.27)
+template <class F> void pick_kernel(int dtype, int bits, bool vec, F &&f) {
+    pick_dtype(dtype, [&](auto dt) { pick<2, 4, 8>(bits, [&](auto b) { pick<1, 0>(vec, [&](auto v) { f(dt, b, v); }); }); });
 }
 
-template <int DT, int BITS> void launch_unpack(bool vec, unsigned groups, hipStream_t s, const uint8_t *packed, size_t n, void *out) {
-    if (vec) hipLaunchKernelGGL((unpack_kernel<DT, BITS, true>), dim3(groups), dim3(kThreads), 0, s, packed, n, out);
-    else hipLaunchKernelGGL((unpack_kernel<DT, BITS, false>), dim3(groups), dim3(kThreads), 0, s, packed, n, out);
-}
-template <int DT> void launch_unpack(int bits, bool vec, unsigned groups, hipStream_t s, const uint8_t *packed, size_t n, void *out) {
-    if (bits == 2) launch_unpack<DT, 2>(vec, groups, s, packed, n, out);
-    else if (bits == 4) launch_unpack<DT, 4>(vec, groups, s, packed, n, out);
-    else launch_unpack<DT, 8>(vec, groups, s, packed, n, out);
-}
-
-// workgroups for `lanes` lanes of work
-inline unsigned grid_of(size_t lanes) {
-    const size_t wanted = (lanes + kThreads - 1) / kThreads;
-    return static_cast<unsigned>(wanted < kMaxGroups ? wanted : kMaxGroups);
+// what the two host entry points refuse alike, the pointers last; 1: n = 0, nothing to do
+inline int check_host(const char *name, int bits, size_t n, const void *from, const void *to) {
+    if (const int rc = check_bits(name, bits)) return rc;
+    if (n == 0) return 1;
+    if (const int rc = check_count(name, n)) return rc;
+    return from == nullptr || to == nullptr ? refuse_null(name) : FEWBIT_OK;
 }
 
 }  // namespace quant
@@ -180,10 +155,7 @@ extern "C" {
 size_t fewbit_hipx_quant_bytes(size_t n, int bits) { return bytes_of(n, bits); }
 
 int fewbit_hipx_quant_pack_host(const float *x_host, size_t n, int bits, uint64_t seed, uint8_t *out_host) {
-    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack_host: bits = %d is not 2, 4 or 8", bits);
-    if (n == 0) return FEWBIT_OK;
-    if (n > kMaxCount) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack_host: n = %zu is beyond 2^36", n);
-    if (x_host == nullptr || out_host == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack_host: null pointer");
+    if (const int rc = check_host("quant_pack_host", bits, n, x_host, out_host)) return rc < 0 ? rc : FEWBIT_OK;
     const size_t groups = (n + kGroup - 1) / kGroup;
     const Key key = sketch::key_of(seed);
     uint8_t *codes = out_host + 8 * groups;
@@ -196,10 +168,7 @@ int fewbit_hipx_quant_pack_host(const float *x_host, size_t n, int bits, uint64_
 }
 
 int fewbit_hipx_quant_unpack_host(const uint8_t *packed_host, size_t n, int bits, float *out_host) {
-    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack_host: bits = %d is not 2, 4 or 8", bits);
-    if (n == 0) return FEWBIT_OK;
-    if (n > kMaxCount) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack_host: n = %zu is beyond 2^36", n);
-    if (packed_host == nullptr || out_host == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack_host: null pointer");
+    if (const int rc = check_host("quant_unpack_host", bits, n, packed_host, out_host)) return rc < 0 ? rc : FEWBIT_OK;
     const uint8_t *codes = packed_host + 8 * ((n + kGroup - 1) / kGroup);
     for (size_t i = 0; i < n; ++i) out_host[i] = decode_host(packed_host, codes, i, bits);
     return FEWBIT_OK;
@@ -207,46 +176,35 @@ int fewbit_hipx_quant_unpack_host(const uint8_t *packed_host, size_t n, int bits
 
 int fewbit_hipx_quant_pack(int dtype, const void *src, size_t n, int bits, uint64_t seed, const uint64_t *seed_device, uint8_t *out, size_t out_bytes,
                            void *stream) {
-    if (!known_dtype(dtype)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: unknown dtype %d", dtype);
-    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: bits = %d is not 2, 4 or 8", bits);
-    if ((reinterpret_cast<uintptr_t>(seed_device) & 7) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: the seed word in device memory must be 8-byte aligned");
+    const char *name = "quant_pack";
+    if (const int rc = check_dtype(name, dtype)) return rc;
+    if (const int rc = check_bits(name, bits)) return rc;
+    if (const int rc = check_seed_word(name, seed_device)) return rc;
     if (n == 0) return FEWBIT_OK;
-    if (n > kMaxCount) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: n = %zu is beyond 2^36", n);
-    if (src == nullptr || out == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: null pointer");
-    if (reinterpret_cast<uintptr_t>(src) % size_of(dtype) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: src must be aligned to its element size");
-    if ((reinterpret_cast<uintptr_t>(out) & 7) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: out must be 8-byte aligned");
-    const size_t need = bytes_of(n, bits);
-    if (out_bytes < need) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: out has %zu bytes, %zu are needed", out_bytes, need);
-    const size_t groups = (n + kGroup - 1) / kGroup;
-    const unsigned grid = grid_of(groups * kLanes);
-    const bool vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+    if (const int rc = check_count(name, n)) return rc;
+    if (src == nullptr || out == nullptr) return refuse_null(name);
+    if (misaligned(src, size_of(dtype))) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_pack: src must be aligned to its element size");
+    if (const int rc = check_aligned8(name, "out", out)) return rc;
+    if (const int rc = check_bytes(name, "out", out_bytes, bytes_of(n, bits))) return rc;
+    const unsigned grid = grid_of((n + kGroup - 1) / kGroup * kLanes);
     const Key key = sketch::key_of(seed);
     const Key *device = reinterpret_cast<const Key *>(seed_device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case FEWBIT_F32: launch_pack<FEWBIT_F32>(bits, vec, grid, s, src, n, key, device, out); break;
-    case FEWBIT_F16: launch_pack<FEWBIT_F16>(bits, vec, grid, s, src, n, key, device, out); break;
-    default: launch_pack<FEWBIT_BF16>(bits, vec, grid, s, src, n, key, device, out); break;
-    }
+    pick_kernel(dtype, bits, !misaligned(src, 16), [&](auto dt, auto b, auto v) {
+        hipLaunchKernelGGL((pack_kernel<dt(), b(), v() != 0>), dim3(grid), dim3(kThreads), 0, static_cast<hipStream_t>(stream), src, n, key, device, out);
+    });
     return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "quant_pack: the launch failed");
 }
 
 int fewbit_hipx_quant_unpack(const uint8_t *packed, size_t n, int bits, int out_dtype, void *out, void *stream) {
-    if (!known_dtype(out_dtype)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack: unknown dtype %d", out_dtype);
-    if (!known_bits(bits)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack: bits = %d is not 2, 4 or 8", bits);
-    if (n == 0) return FEWBIT_OK;
-    if (n > kMaxCount) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack: n = %zu is beyond 2^36", n);
-    if (packed == nullptr || out == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack: null pointer");
-    if ((reinterpret_cast<uintptr_t>(packed) & 7) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack: packed must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out) % size_of(out_dtype) != 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack: out must be aligned to its element size");
+    const char *name = "quant_unpack";
+    if (const int rc = check_dtype(name, out_dtype)) return rc;
+    if (const int rc = check_host(name, bits, n, packed, out)) return rc < 0 ? rc : FEWBIT_OK;
+    if (const int rc = check_aligned8(name, "packed", packed)) return rc;
+    if (misaligned(out, size_of(out_dtype))) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "quant_unpack: out must be aligned to its element size");
     const unsigned grid = grid_of((n + kBlock - 1) / kBlock);
-    const bool vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (out_dtype) {
-    case FEWBIT_F32: launch_unpack<FEWBIT_F32>(bits, vec, grid, s, packed, n, out); break;
-    case FEWBIT_F16: launch_unpack<FEWBIT_F16>(bits, vec, grid, s, packed, n, out); break;
-    default: launch_unpack<FEWBIT_BF16>(bits, vec, grid, s, packed, n, out); break;
-    }
+    pick_kernel(out_dtype, bits, !misaligned(out, 16), [&](auto dt, auto b, auto v) {
+        hipLaunchKernelGGL((unpack_kernel<dt(), b(), v() != 0>), dim3(grid), dim3(kThreads), 0, static_cast<hipStream_t>(stream), packed, n, out);
+    });
     return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "quant_unpack: the launch failed");
 }
 

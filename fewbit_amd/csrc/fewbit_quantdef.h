@@ -1,6 +1,6 @@
 // fewbit_quantdef.h -- the definition of "the packed form of a seed" (include/fewbit_hipx.h), one element or one group at a time: the ONE text
 // that fewbit_quant.hip (a tensor taken by flat index) and fewbit_norm.hip (the normalized rows of a layer norm) evaluate, on the host and
-// on the device alike.  Also the element access and the lane moves both units share.
+// on the device alike.  Also the element access and the lane moves both units share (fewbit_dropout.hip: the element access; fewbit_glu.hip: all of it).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,15 +9,16 @@
 
 #include "fewbit_hipx.h"
 #include "fewbit_philox.h"
+#include "fewbit_unit.h"
 
 namespace fewbit_hip {
 namespace quant {
 
+using namespace unit;                       // (the predicates, the refusals, pick)
+using unit::kBlock, unit::kGroup, unit::kLanes;        // (declared here: fewbit_device.h has a kBlock of its own in fewbit_hip)
 using sketch::Key;
 
 constexpr uint32_t kRoundDomain = 7u;       // counter word 3 (0 and 2: the dense sketches, 3: the sampled rows, 4: the CRS columns, 5: the dropout, 6: the signs)
-constexpr int kBlock = 8;                   // elements per Philox call and per code word
-constexpr int kGroup = 64, kLanes = kGroup / kBlock;   // elements per group; lanes that hold one
 constexpr uint32_t kNaN = 0x7fc00000u;      // what a poisoned group stores for lo and step, and decodes to
 
 // ---- the definition, one element or one group at a time: host and device evaluate these very functions --------------------------------------
@@ -68,9 +69,9 @@ __host__ __device__ __forceinline__ int32_t order_key(uint32_t bits) {
 }
 __host__ __device__ __forceinline__ bool non_finite(uint32_t bits) { return (bits & 0x7f800000u) == 0x7f800000u; }
 
-// the 16 bits of element e of a block (the dropout's choice: word e >> 1, low half for even e, high half for odd e) as U in [0, 1)
+// the 16 bits of element e of a block (the dropout's choice: mask_bits, fewbit_unit.h) as U in [0, 1)
 __host__ __device__ __forceinline__ float uniform_of(const uint32_t (&w)[4], int e) {
-    return static_cast<float>((w[e >> 1] >> (16 * (e & 1))) & 0xffffu) * (1.0f / 65536.0f);             // (both exact)
+    return static_cast<float>(mask_bits(w, e)) * (1.0f / 65536.0f);                                     // (both exact)
 }
 // (DOMAIN: counter word 3, a compile-time constant as it always was; kUpDomain is the second tensor of a call that packs two, fewbit_glu.hip)
 constexpr uint32_t kUpDomain = 8u;
@@ -145,14 +146,18 @@ inline float decode_host(const uint8_t *params, const uint8_t *codes, size_t i, 
     return decode(code, float_of_bits(par[0]), float_of_bits(par[1]));
 }
 
-inline bool known_dtype(int dtype) { return dtype == FEWBIT_F32 || dtype == FEWBIT_F16 || dtype == FEWBIT_BF16; }
 inline bool known_bits(int bits) { return bits == 2 || bits == 4 || bits == 8; }
-inline size_t size_of(int dtype) { return dtype == FEWBIT_F32 ? 4 : 2; }
+// (the refusal of the others, beside those of fewbit_unit.h)
+inline int check_bits(const char *name, int bits) {
+    return known_bits(bits) ? FEWBIT_OK : fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: bits = %d is not 2, 4 or 8", name, bits);
+}
 
 // ---- element access ----------------------------------------------------------------------------------------------------------------------
 template <int DT> struct Elem { using type = uint16_t; };
 template <> struct Elem<FEWBIT_F32> { using type = uint32_t; };
 
+// (widen / narrow are not fewbit_dropout.hip's to_float / from_float: narrow<FEWBIT_F16> carries the barrier that `one` places itself there, and either
+// unit written with the other's pair changes its fp16 kernels, EXPERIMENTS.md 8.27)
 template <int DT> __device__ __forceinline__ uint32_t widen(typename Elem<DT>::type raw) {              // the bits of the element as fp32 (exact)
     if constexpr (DT == FEWBIT_F32) return raw;
     else if constexpr (DT == FEWBIT_BF16) return static_cast<uint32_t>(raw) << 16;

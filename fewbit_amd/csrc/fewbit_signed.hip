@@ -18,8 +18,6 @@
 #include "fewbit_fft4.h"
 #include "fewbit_hipx.h"
 
-#define FEWBIT_HIDDEN __attribute__((visibility("hidden")))
-
 #ifndef FEWBIT_SIGNED_TU
 #define FEWBIT_SIGNED_TU -1
 #endif
@@ -31,8 +29,7 @@ struct DctZext;                             // (fewbit_dct.hip, units 3 .. 5: it
 namespace dft {
 using namespace dct;
 struct Dft;                                 // (fewbit_dft.hip)
-struct DftZext;
-FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+struct DftZext;                             // (fail: fewbit_unit.h)
 }
 
 #define FB_SIGNED_LINKED(DT)                                                                                                   \

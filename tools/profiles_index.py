@@ -60,6 +60,9 @@ ROWS = [
     ('roberta_signed_dct_*.json', 'tools/roberta_bench.py --table --matmul dct, use_sign_flips off and on: RoBERTa-base b128 x s128 step time and peak memory, bf16 and fp32', f'{E} 8.15'),
     ('convergence_demo_signed_*.txt', "tools/convergence_demo.py with the signed-DCT arm: bf16 at the usual step size and at SGD lr 1.0, where the unsigned DCT arm diverges", f'{D} 7.4'),
     ('transform_one_text_isa_identity.txt', 'tools/isa_digest.py --diff --rename: machine code of all 2143 device functions before / after pass A and pass B of the plain pairs became one kernel template each (798 kernels renamed, none changed)', f'{E} 8.16'),
+    ('unit_fold_isa_identity.txt', "tools/isa_digest.py --diff: machine code of all 2888 device functions before / after the companion units' host code and element access moved into fewbit_unit.h (none changed)", f'{E} 8.27'),
+    ('refusal_digest.txt', 'tools/refusal_digest.py: status and message of every refusal of the quant, glu, norm, fused-norm and dropout entry points, single faults and pairs (tests/test_refusals_host.py compares)', f'{E} 8.27'),
+    ('unit_fold_speed*.txt', 'the launch-bound entry-point arms of quant_linear_bench, dropout_bench, glu_bench and layer_norm_bench from the parent and from the tree with fewbit_unit.h, alternating five times', f'{E} 8.27'),
     ('signed_transform_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1915 device functions before / after the signed pass A was added (228 new)', f'{E} 8.15'),
     ('moments_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1890 device functions before / after fewbit_moments.hip was added (13 new)', f'{E} 8.9'),
     ('r06_dct_stagger.txt|r06_dct_fused_upper_bound.txt|r06_dct_inter16.txt', 'DCT experiments not kept: staggered starts, both passes in one launch (timing only), a bf16 intermediate', 'EXPERIMENTS.md'),
