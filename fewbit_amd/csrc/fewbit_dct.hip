@@ -54,6 +54,7 @@
 #include <cstdio>
 #include <type_traits>
 
+#include "fewbit_core.h"       // (fail: shared with the core unit of fewbit_kernels.hip)
 #include "fewbit_fft4.h"
 #include "fewbit_hip.h"
 #include "fewbit_philox.h"
@@ -68,13 +69,7 @@
 #include "fewbit_hipx.h"
 #endif
 
-#define FEWBIT_HIDDEN __attribute__((visibility("hidden")))
-
 namespace fewbit_hip {
-
-// shared with the core unit of fewbit_kernels.hip
-FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
 namespace dct {
 
 // (tiles, small transforms, row loads, tables, the rows of a seed and their sort, both passes -- pass_a_kernel / pass_a_zext_kernel in

@@ -20,6 +20,8 @@
 //   quantize_*_wide_kernel        tables of 5..8 bits and tables that do not fill their bit width
 // No kernel needs aligned pointers: gfx950 global accesses take any address (see fewbit_device.h).
 //   pack/unpack_codes_kernel      codec seam used by the tests
+// Host side (second half of the file): do_* (an entry point's checks, in its own order; ends_at_buffers of fewbit_core.h) -> with_dtype / pick_fn
+// (unit::pick of fewbit_unit.h) -> launch_* (open_call, pick_u, name_plan, close_call) -> launch_stream (kTiled / kLut, launch_shape of fewbit_core.h).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -29,8 +31,10 @@
 #include <cstring>
 #include <mutex>
 #include <type_traits>
+#include <utility>
 
 #include "fewbit_codepack.h"
+#include "fewbit_core.h"
 #include "fewbit_device.h"
 
 namespace fewbit_hip {
@@ -169,6 +173,19 @@ __device__ __forceinline__ void pipeline2(const Span &s, Init &&init, Load &&loa
     }
 }
 
+// group g of a tile as lane ln requests it (no use of the data): fp32 in its split layout where that is compiled in (see SplitF32)
+template <int DT> __device__ __forceinline__ typename GroupIO<DT>::Raw load_tile_group(const void *base, size_t g, int ln) {
+    typename GroupIO<DT>::Raw out;
+    if constexpr ((DT == FEWBIT_F32) && (FEWBIT_F32_SPLIT != 0)) {
+        const SplitF32::Raw r = SplitF32::load_raw(base, g, ln);
+        out.a = r.a;
+        out.b = r.b;
+    } else {
+        out = GroupIO<DT>::load_raw(base, g);
+    }
+    return out;
+}
+
 // occupancy each forward instantiation is compiled for: 8 waves/SIMD (<= 64 VGPRs) where the table and
 // the two prefetch buffers fit without spilling, 6 (<= 80) for 4-bit tables (15 border VGPRs), fp32
 // groups (8 VGPRs per buffer) and mish (ocml log1p+exp+tanh).  The launcher sizes the grid from the occupancy the runtime reports.
@@ -208,13 +225,7 @@ __global__ __launch_bounds__(kBlock, (forward_waves_per_simd<FN, DT, K, U>())) v
         [&](size_t t, int ln, Buf &buf) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if constexpr (kSplit) {
-                    const SplitF32::Raw r = SplitF32::load_raw(x, (t * U + u) * kWave + ln, ln);
-                    buf.r[u].a = r.a;
-                    buf.r[u].b = r.b;
-                } else {
-                    buf.r[u] = GroupIO<DT>::load_raw(x, (t * U + u) * kWave + ln);
-                }
+                buf.r[u] = load_tile_group<DT>(x, (t * U + u) * kWave + ln, ln);
             }
         },
         [&](size_t t, const Buf &buf) {
@@ -314,6 +325,7 @@ __global__ __launch_bounds__(BLOCK, (lut_waves_per_simd<BLOCK>())) void quantize
         float b[NBMAX];
 #pragma unroll
         for (int j = 0; j < NBMAX; ++j) b[j] = bits_f32(__builtin_amdgcn_readlane(f32_bits(mine), j));
+        // (both passes are written again in quantize_forward_lut_wide_kernel: one text for both changes this kernel's code, 8.28)
         // pass 1: chunks of 64 patterns, one per thread (1024-thread blocks); a chunk that starts on a NaN pattern is all
         // NaN -> nborders
 #pragma unroll
@@ -422,7 +434,7 @@ __device__ __forceinline__ void wide_forward_tail(const Span &s, const void *x, 
                 Elem<DT>::store(y, e0 + i, Act<FN, kFast>::eval(Elem<DT>::load(x, e0 + i), p0, p1));
             }
         }
-        uint8_t *p = state + static_cast<size_t>(nbits) * g;
+        uint8_t *p = state + static_cast<size_t>(nbits) * g;      // (the same loop: pack_codes_kernel; one text for both changes code, 8.28)
         for (int j = 0; j < nbits; ++j) p[j] = static_cast<uint8_t>(w >> (8 * j));
     }
 }
@@ -502,6 +514,7 @@ __global__ __launch_bounds__(kLutBlock, (lut_waves_per_simd<kLutBlock>())) void 
             sr[threadIdx.x] = static_cast<uint16_t>(mine_raw);
         }
         __syncthreads();
+        // (both passes as in quantize_forward_lut_kernel, see there: one text for both changes that kernel's code, 8.28)
         for (uint32_t c = threadIdx.x; c < 1024u; c += kLutBlock) {
             const uint32_t r0 = c * 64u;
             const uint32_t c_first = ((r0 & 0x7fffu) > kInf) ? static_cast<uint32_t>(nborders)
@@ -594,7 +607,7 @@ __global__ __launch_bounds__(kBlock, kWavesPerSimd) void quantize_backward_wide_
     if (!s.tail_owner) return;
     for (size_t g = s.tail_g0 + s.lane; g < s.ngroups; g += kWave) {
         const size_t e0 = g << 3;
-        const uint8_t *p = state + static_cast<size_t>(nbits) * g;
+        const uint8_t *p = state + static_cast<size_t>(nbits) * g;      // (the same loop: unpack_codes_kernel; one text for both changes code, 8.28)
         uint64_t w = 0;
         for (int j = 0; j < nbits; ++j) w |= static_cast<uint64_t>(p[j]) << (8 * j);
         for (int i = 0; i < 8; ++i)
@@ -632,13 +645,7 @@ __global__ __launch_bounds__(kBlock, (stream_waves_per_simd<DT, U>())) void quan
         [&](size_t t, int ln, Buf &buf) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if constexpr (kSplit) {
-                    const SplitF32::Raw r = SplitF32::load_raw(gy, (t * U + u) * kWave + ln, ln);
-                    buf.r[u].a = r.a;
-                    buf.r[u].b = r.b;
-                } else {
-                    buf.r[u] = GroupIO<DT>::load_raw(gy, (t * U + u) * kWave + ln);
-                }
+                buf.r[u] = load_tile_group<DT>(gy, (t * U + u) * kWave + ln, ln);
                 buf.w[u] = load_state_quad_raw<K>(state, (t * U + u) * kWave + ln, ln);
             }
         },
@@ -694,13 +701,7 @@ __global__ __launch_bounds__(kBlock, (stream_waves_per_simd<DT, U>())) void step
         [&](size_t t, int ln, Buf &buf) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if constexpr (kSplit) {
-                    const SplitF32::Raw r = SplitF32::load_raw(x, (t * U + u) * kWave + ln, ln);
-                    buf.r[u].a = r.a;
-                    buf.r[u].b = r.b;
-                } else {
-                    buf.r[u] = GroupIO<DT>::load_raw(x, (t * U + u) * kWave + ln);
-                }
+                buf.r[u] = load_tile_group<DT>(x, (t * U + u) * kWave + ln, ln);
             }
         },
         [&](size_t t, const Buf &buf) {
@@ -753,13 +754,7 @@ __global__ __launch_bounds__(kBlock, (stream_waves_per_simd<DT, U>())) void step
         [&](size_t t, int ln, Buf &buf) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if constexpr (kSplit) {
-                    const SplitF32::Raw r = SplitF32::load_raw(gy, (t * U + u) * kWave + ln, ln);
-                    buf.r[u].a = r.a;
-                    buf.r[u].b = r.b;
-                } else {
-                    buf.r[u] = GroupIO<DT>::load_raw(gy, (t * U + u) * kWave + ln);
-                }
+                buf.r[u] = load_tile_group<DT>(gy, (t * U + u) * kWave + ln, ln);
                 buf.w[u] = load_state_quad_raw<1>(state, (t * U + u) * kWave + ln, ln);
             }
         },
@@ -802,7 +797,7 @@ __global__ __launch_bounds__(kBlock) void pack_codes_kernel(const int32_t *__res
     uint64_t w = 0;
     for (int i = 0; i < 8; ++i)
         if (e0 + i < n) w |= (static_cast<uint64_t>(static_cast<uint32_t>(codes[e0 + i])) & mask) << (nbits * i);
-    uint8_t *p = state + static_cast<size_t>(nbits) * g;
+    uint8_t *p = state + static_cast<size_t>(nbits) * g;      // (the same loop: wide_forward_tail; one text for both changes code, 8.28)
     for (int j = 0; j < nbits; ++j) p[j] = static_cast<uint8_t>(w >> (8 * j));
 }
 
@@ -811,7 +806,7 @@ __global__ __launch_bounds__(kBlock) void unpack_codes_kernel(const uint8_t *__r
     const size_t g = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
     const size_t e0 = g << 3;
     if (e0 >= n) return;
-    const uint8_t *p = state + static_cast<size_t>(nbits) * g;
+    const uint8_t *p = state + static_cast<size_t>(nbits) * g;      // (the same loop: the tail of quantize_backward_wide_kernel; see there)
     uint64_t w = 0;
     for (int j = 0; j < nbits; ++j) w |= static_cast<uint64_t>(p[j]) << (8 * j);
     const uint64_t mask = (1ull << nbits) - 1ull;
@@ -826,14 +821,13 @@ __global__ __launch_bounds__(kBlock) void unpack_codes_kernel(const uint8_t *__r
 // Split build (Makefile): the forward functors -- nine tenths of the compile time -- are compiled in parallel as units
 // -DFEWBIT_TU=1..FEWBIT_TU_COUNT (three functors each, only dispatch_forward_dtype<FN> instantiated), everything else is unit
 // -DFEWBIT_TU=0; without FEWBIT_TU one unit holds everything (`make variant`).  What the units share has external (hidden)
-// linkage and is defined in the core unit; all the rest below is per unit.
+// linkage and is defined in the core unit (fewbit_core.h declares what the sketch and dct units use of it); all the rest below is per unit.
 #if defined(FEWBIT_TU) && FEWBIT_TU != 0
 #define FEWBIT_CORE_TU 0
 #else
 #define FEWBIT_CORE_TU 1
 #endif
 #define FEWBIT_TU_COUNT 5
-#define FEWBIT_HIDDEN __attribute__((visibility("hidden")))
 
 // Run-time tuning.  Every key is -1 ("built-in policy") unless its environment variable is set when the library makes
 // its first launch, or fewbit_hip_tune() sets it later (measurement scripts sweep shapes inside one process that way).
@@ -860,11 +854,20 @@ struct Plan {
     int threads, chunk, u, k, blocks_per_cu;
 };
 
-extern FEWBIT_HIDDEN thread_local char g_last_error[256];
+// The frame of one call, from its entry point to its launch: the plan to fill (or none), whether it is dry (describe: the same dispatch without the
+// launch), the element count, the stream, and the device -- the calling thread's current one, resolved ONCE per call by open_call (the torch glue and
+// the ctypes binding both make the tensors' device current first).
+struct Device { int index = 0, cus = 256; };
+struct Call {
+    Plan *plan;
+    bool dry;
+    size_t n;
+    hipStream_t s;
+    Device dev;
+};
+
 extern FEWBIT_HIDDEN std::atomic<long long> g_tune[T_COUNT];
-FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 FEWBIT_HIDDEN void tune_init();
-FEWBIT_HIDDEN int sketch_tune(const char *key, long long value, bool *known);      // fewbit_sketch.hip
 
 #if FEWBIT_CORE_TU
 thread_local char g_last_error[256] = "";
@@ -891,84 +894,53 @@ void tune_init() {
 
 namespace {
 
-int check_launch(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FEWBIT_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-    return FEWBIT_OK;
-}
-
-
-// FEWBIT_HIP_VALIDATE=1 (debug aid, off by default: two runtime queries per pointer): every pointer handed to the
-// C-ABI must be device memory and [p, p + bytes) must lie inside its allocation -- a host pointer or a state buffer
-// sized with the wrong bit width then fails with FEWBIT_ERR_INVALID_ARGUMENT instead of a fault on the GPU.
-bool validate_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("FEWBIT_HIP_VALIDATE");
-        return e && atoi(e) != 0;
-    }();
-    return on;
-}
-
-int validate_range(const char *what, const void *p, size_t bytes) {
-    if (!validate_enabled() || bytes == 0) return FEWBIT_OK;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s (%p) is not a pointer known to the HIP runtime", what, p);
-    }
-    if (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s (%p) is not device memory", what, p);
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s (%p): no allocation found", what, p);
-    }
-    const size_t off = static_cast<size_t>(static_cast<const char *>(p) - static_cast<const char *>(base));
-    if (off + bytes > size)
-        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s needs %zu bytes but only %zu remain in its allocation", what, bytes, size - off);
-    return FEWBIT_OK;
-}
-
-size_t dtype_size(int dtype) { return dtype == FEWBIT_F32 ? 4 : 2; }
-
-#define FB_VALIDATE(WHAT, P, BYTES)                                  \
-    do {                                                             \
-        const int rc_ = validate_range((WHAT), (P), (BYTES));        \
-        if (rc_ != FEWBIT_OK) return rc_;                            \
-    } while (0)
-
 long long tune(TuneKey k) {
     tune_init();
     return g_tune[k].load(std::memory_order_relaxed);
 }
 
-// ------------------------------------------------------------------------------------------------
-// The device a call launches on = the calling thread's current device, resolved ONCE per call (the torch glue and the
-// ctypes binding both make the tensors' device current first).  Geometry is cached per device index.
-constexpr int kMaxDevices = 64;
-struct Device { int index = 0, cus = 256; };
+int refuse_dtype(int dtype) { return fail(FEWBIT_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype); }
 
-int get_device(Device &d) {
-    static std::atomic<int> cus[kMaxDevices];
+// rc of f(integral_constant<dtype>) (every entry point has refused an unknown dtype before it gets here)
+template <class F> int with_dtype(int dtype, F &&f) {
+    int rc = FEWBIT_OK;
+    return unit::pick_dtype(dtype, [&](auto dt) { rc = f(dt); }) ? rc : refuse_dtype(dtype);
+}
+
+// f(integral_constant<id>) for the functor id in 0 .. N-1 that `fn` names, in the order of the ids, which is the order of the case ladders this
+// replaces (the order of a pick's list sets the order in which the unit emits its kernels: EXPERIMENTS.md 8.27); false (and no call) for none
+template <int... ID, class F> bool pick_of(std::integer_sequence<int, ID...>, int fn, F &&f) { return unit::pick<ID...>(fn, f); }
+template <int N, class F> bool pick_fn(int fn, F &&f) { return pick_of(std::make_integer_sequence<int, N>{}, fn, f); }
+
+// ------------------------------------------------------------------------------------------------
+// The three steps every launch_* shares.  open_call: the device (geometry is cached per device index, fewbit_core.h) and the plan's bit width;
+// name_plan: which instantiation it is; close_call: what the launch left behind.
+int open_call(Call &c, int k) {
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) {
         (void)hipGetLastError();
         return fail(FEWBIT_ERR_LAUNCH, "hipGetDevice failed: no current HIP device");
     }
     if (dev < 0 || dev >= kMaxDevices) return fail(FEWBIT_ERR_UNSUPPORTED, "device index %d outside [0, %d)", dev, kMaxDevices);
-    int v = cus[dev].load(std::memory_order_relaxed);
-    if (v == 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) {
-            (void)hipGetLastError();
-            v = 256;
-        }
-        cus[dev].store(v, std::memory_order_relaxed);     // (two threads racing on a first use store the same value)
-    }
-    d.index = dev;
-    d.cus = v;
+    c.dev = Device{dev, cached_cus(dev)};
+    if (c.plan) c.plan->k = k;
     return FEWBIT_OK;
 }
+
+__attribute__((format(printf, 2, 3))) void name_plan(const Call &c, const char *fmt, ...) {
+    if (!c.plan) return;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(c.plan->kernel, sizeof c.plan->kernel, fmt, ap);
+    va_end(ap);
+}
+
+int check_launch(const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(FEWBIT_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
+    return FEWBIT_OK;
+}
+int close_call(const Call &c, const char *what) { return c.dry ? FEWBIT_OK : check_launch(what); }
 
 // resident blocks per CU of a kernel instantiation: the runtime's occupancy answer, cached per kernel and device
 template <auto Kern> int occupancy_blocks_per_cu(const Device &d, int threads) {
@@ -991,79 +963,39 @@ const char *const kStepNames[FEWBIT_STEPWISE_COUNT] = {"hardshrink", "hardsigmoi
                                                        "softshrink", "threshold"};
 const char *dtype_name(int dt) { return dt == FEWBIT_F32 ? "f32" : dt == FEWBIT_F16 ? "f16" : "bf16"; }
 
-// Launch shape of a streaming kernel (see Span): RESIDENT (chunk = 0: one wave per tile until the chip is full, then the
-// resident waves loop round-robin) or CHUNKED (chunk = T tiles per wave, block-contiguous, as many blocks as that takes).
-struct Shape { unsigned blocks; int chunk; };
+// The two classes of streaming kernel, by what their launch differs in (the shape itself: launch_shape, fewbit_core.h).
+struct StreamClass {
+    int block, max_per_cu;         // threads per block; ceiling on the resident blocks per CU the grid is sized for
+    TuneKey cap;                   // the key that lowers that ceiling ...
+    bool cap_in_waves;             // ... counted in waves per CU (else in blocks per CU)
+    TuneKey chunk;                 // the key of the shape: launch_shape's `setting`
+    int auto_chunk;                // the built-in policy: tiles per wave of the chunked shape ...
+    size_t auto_ratio;             // ... which is used from this many tiles per resident wave up
+};
+// search / backward / 1-bit kernels, 256-thread blocks (cheap per-block setup): one tile per wave from 4 tiles per resident wave up
+constexpr StreamClass kTiled = {kBlock, 8, T_WAVES_PER_CU, true, T_CHUNK, 1, 4};
+// pattern-table forward, 1024-thread blocks of which at most two are resident per CU (64 KiB table in LDS each): three tiles per wave (an odd count:
+// chunks of a power-of-two size start every block on the same memory channels, T = 4 measured 5-15 % slower than T = 3) from 12 tiles per
+// resident wave up
+constexpr StreamClass kLut = {kLutBlock, 2, T_LUT_BLOCKS_PER_CU, false, T_LUT_CHUNK, 3, 12};
 
-// Built-in policy (measured on MI355X, scratch/headvar.py with SIZES=..., EXPERIMENTS.md section 6): the resident shape wins
-// while a wave has only a few tiles (4096x4096 bf16: 11.2 vs 11.6 us), the chunked shape wins once the tensor is many
-// times the resident generation, where statically assigned waves drift apart and the launch waits for the slowest
-// (2^28 bf16 elements: backward 235 -> 197 us, pattern-table forward 224 -> 197 us; RoBERTa-size fp32, 5*10^7 elements:
-// forward+backward 169 -> 151 us).  `min_ratio` = tiles per resident wave from which the chunked shape is used.
-// `setting`: -1 = that policy, 0 = always resident, T = chunk of T wherever the tensor has more tiles than resident waves.
-Shape launch_shape(size_t ntiles, int waves_per_block, size_t resident_blocks, long long setting, int auto_chunk, size_t min_ratio) {
-    const size_t wpb = static_cast<size_t>(waves_per_block);
-    size_t blocks = (ntiles + wpb - 1) / wpb;                      // one tile per wave
-    int chunk = 0;
-    if (blocks > resident_blocks) {
-        long long t = setting;
-        if (t < 0) t = ntiles >= min_ratio * resident_blocks * wpb ? auto_chunk : 0;
-        const size_t chunked = t > 0 ? (ntiles + wpb * t - 1) / (wpb * t) : 0;
-        if (t > 0 && chunked > resident_blocks) {
-            blocks = chunked;
-            chunk = static_cast<int>(t);
-        } else {
-            blocks = resident_blocks;
-        }
+// launch (or, dry, only describe) a streaming kernel instantiation, each wave looping over its tiles; the kernels' last parameter is the chunk
+template <auto Kern, typename... Args> void launch_stream(const Call &c, const StreamClass &cls, int U, Args... args) {
+    int per_cu = occupancy_blocks_per_cu<Kern>(c.dev, cls.block);
+    if (per_cu > cls.max_per_cu) per_cu = cls.max_per_cu;
+    const long long cap = tune(cls.cap), per_block = cls.cap_in_waves ? cls.block / kWave : 1;
+    if (cap >= per_block && cap / per_block < per_cu) per_cu = static_cast<int>(cap / per_block);
+    const size_t ntiles = (c.n / 8) / (static_cast<size_t>(U) * kWave);
+    const Shape sh = launch_shape(ntiles, cls.block / kWave, static_cast<size_t>(c.dev.cus) * per_cu, tune(cls.chunk), cls.auto_chunk,
+                                  cls.auto_ratio);
+    if (c.plan) {
+        c.plan->blocks = sh.blocks;
+        c.plan->threads = cls.block;
+        c.plan->chunk = sh.chunk;
+        c.plan->u = U;
+        c.plan->blocks_per_cu = per_cu;
     }
-    if (blocks < 1) blocks = 1;
-    return Shape{static_cast<unsigned>(blocks), chunk};
-}
-
-// search / backward / 1-bit kernels (cheap per-block setup): one tile per wave from 4 tiles per resident wave up;
-// pattern-table forward (64 KiB table per block): three tiles per wave (an odd count: chunks of a power-of-two size start
-// every block on the same memory channels, T = 4 measured 5-15 % slower than T = 3) from 12 tiles per resident wave up
-constexpr int kAutoChunk = 1, kAutoLutChunk = 3;
-constexpr size_t kAutoChunkRatio = 4, kAutoLutChunkRatio = 12;
-
-// launch (or, dry, only describe) a 256-thread streaming kernel instantiation; the kernels' last parameter is the chunk
-template <auto Kern, typename... Args>
-void launch_tiled(Plan *plan, bool dry, const Device &dev, size_t n, int U, hipStream_t s, Args... args) {
-    int per_cu = occupancy_blocks_per_cu<Kern>(dev, kBlock);
-    if (per_cu > 8) per_cu = 8;
-    const long long cap = tune(T_WAVES_PER_CU);
-    if (cap >= kWavesPerBlock && cap / kWavesPerBlock < per_cu) per_cu = static_cast<int>(cap / kWavesPerBlock);
-    const size_t ntiles = (n / 8) / (static_cast<size_t>(U) * kWave);
-    const Shape sh = launch_shape(ntiles, kWavesPerBlock, static_cast<size_t>(dev.cus) * per_cu, tune(T_CHUNK), kAutoChunk,
-                                  kAutoChunkRatio);
-    if (plan) {
-        plan->blocks = sh.blocks;
-        plan->threads = kBlock;
-        plan->chunk = sh.chunk;
-        plan->u = U;
-        plan->blocks_per_cu = per_cu;
-    }
-    if (!dry) hipLaunchKernelGGL(Kern, dim3(sh.blocks), dim3(kBlock), 0, s, args..., sh.chunk);
-}
-
-// pattern-table forward: BLOCK-thread blocks, at most two resident per CU (LDS), each wave loops over its tiles
-template <auto Kern, int BLOCK, typename... Args>
-void launch_lut(Plan *plan, bool dry, const Device &dev, size_t n, int U, hipStream_t s, Args... args) {
-    int per_cu = occupancy_blocks_per_cu<Kern>(dev, BLOCK);
-    if (per_cu > 2) per_cu = 2;
-    const long long cap = tune(T_LUT_BLOCKS_PER_CU);
-    if (cap >= 1 && cap < per_cu) per_cu = static_cast<int>(cap);
-    const size_t ntiles = (n / 8) / (static_cast<size_t>(U) * kWave);
-    const Shape sh = launch_shape(ntiles, BLOCK / kWave, static_cast<size_t>(dev.cus) * per_cu, tune(T_LUT_CHUNK),
-                                  kAutoLutChunk, kAutoLutChunkRatio);
-    if (plan) {
-        plan->blocks = sh.blocks;
-        plan->threads = BLOCK;
-        plan->chunk = sh.chunk;
-        plan->u = U;
-        plan->blocks_per_cu = per_cu;
-    }
-    if (!dry) hipLaunchKernelGGL(Kern, dim3(sh.blocks), dim3(BLOCK), 0, s, args..., sh.chunk);
+    if (!c.dry) hipLaunchKernelGGL(Kern, dim3(sh.blocks), dim3(cls.block), 0, c.s, args..., sh.chunk);
 }
 
 // Smallest tensor that takes the pattern-table forward: building the table costs the same whatever the table, the register
@@ -1078,24 +1010,11 @@ size_t lut_min_elements(int k) {
 
 // Groups per lane per pipeline stage, the values the policy uses: backward, 1-bit and fp32 forward 1 and 2; 16-bit forward 1
 // (U = 4 never won a size class: profiles/r03_backward_shape_sweep.txt).
-template <int... Us> struct UList {};
-typedef UList<1> FwdUs16;
-typedef UList<1, 2> FwdUs32;
-typedef UList<1, 2> StreamUs16;
-typedef UList<1, 2> StreamUs32;
-
-// call f(integral_constant<U>) for the U of the list that `want` names (the list's first entry if it names none)
-template <int U0, int... Us, typename F> void with_u(UList<U0, Us...>, long long want, F &&f) {
-    bool done = false;
-    auto one = [&](auto tag) {
-        if (!done && want == decltype(tag)::value) {
-            done = true;
-            f(tag);
-        }
-    };
-    one(std::integral_constant<int, U0>{});
-    (one(std::integral_constant<int, Us>{}), ...);
-    if (!done) f(std::integral_constant<int, U0>{});
+// f(integral_constant<U>) for the U of the list that `want` names (the list's first entry if it names none).  Only pick calls f: a second call of
+// f here for the first entry put the kernels of U = 2 in front of those of U = 1 in the unit, and that changed the code of two of them (8.28)
+template <int U0, int... Us, typename F> void pick_u(long long want, F &&f) {
+    const bool named = ((want == U0) || ... || (want == Us));
+    unit::pick<U0, Us...>(named ? static_cast<int>(want) : U0, f);
 }
 
 // Built-in U policy (MI355X, round 3: profiles/r03_shape_sweep_*.txt, profiles/r03_backward_size_crossover.txt).
@@ -1130,98 +1049,68 @@ long long tuned(TuneKey key, long long policy) {
 unsigned group_grid(size_t n) { return static_cast<unsigned>(((n + 7) / 8 + kBlock - 1) / kBlock); }
 
 template <int FN, int DT>
-int launch_forward(Plan *plan, bool dry, const void *x, void *y, uint8_t *state, size_t n, const void *borders, int nborders,
-                   int k, float p0, float p1, hipStream_t s) {
-    Device dev;
-    if (const int rc = get_device(dev)) return rc;
-    const bool pow2 = nborders == (1 << k) - 1;
-    if (plan) plan->k = k;
+int launch_forward(Call c, const void *x, void *y, uint8_t *state, const void *borders, int nborders, int k, float p0, float p1) {
+    if (const int rc = open_call(c, k)) return rc;
+    const size_t n = c.n;
     auto name = [&](const char *kern, int U, int block) {
-        if (plan) snprintf(plan->kernel, sizeof plan->kernel, "%s<%s, %s, %d bits, U=%d, block=%d>", kern, kFnNames[FN], dtype_name(DT), k, U, block);
+        name_plan(c, "%s<%s, %s, %d bits, U=%d, block=%d>", kern, kFnNames[FN], dtype_name(DT), k, U, block);
     };
     // (a folded key |x - shift| is an fp32 value, not one of the 65 536 input patterns: search kernels only)
     if constexpr (DT != FEWBIT_F32 && FN != FEWBIT_IDENTITY_FOLD) {
         // 16-bit dtypes, any table (power of two or not): pattern-table kernel once the tensor is big enough to pay for
         // building the table in every block
         if (n >= lut_min_elements(k)) {
-            if (k > 4) {
-                launch_lut<quantize_forward_lut_wide_kernel<FN, DT>, kLutBlock>(plan, dry, dev, n, 1, s, x, y, state, n, borders, nborders, k, p0, p1);
-                name("quantize_forward_lut_wide_kernel", 1, kLutBlock);
-                return dry ? FEWBIT_OK : check_launch("quantize_forward(lut)");
-            }
             constexpr int U = 1, B = kLutBlock;      // one group per lane per stage, 1024-thread blocks (the only shape that ever won)
-            switch (k) {
-            case 1: launch_lut<quantize_forward_lut_kernel<FN, DT, 1, U, B>, B>(plan, dry, dev, n, U, s, x, y, state, n, borders, nborders, p0, p1); break;
-            case 2: launch_lut<quantize_forward_lut_kernel<FN, DT, 2, U, B>, B>(plan, dry, dev, n, U, s, x, y, state, n, borders, nborders, p0, p1); break;
-            case 3: launch_lut<quantize_forward_lut_kernel<FN, DT, 3, U, B>, B>(plan, dry, dev, n, U, s, x, y, state, n, borders, nborders, p0, p1); break;
-            default: launch_lut<quantize_forward_lut_kernel<FN, DT, 4, U, B>, B>(plan, dry, dev, n, U, s, x, y, state, n, borders, nborders, p0, p1); break;
+            if (k > 4) {
+                launch_stream<quantize_forward_lut_wide_kernel<FN, DT>>(c, kLut, 1, x, y, state, n, borders, nborders, k, p0, p1);
+                name("quantize_forward_lut_wide_kernel", 1, kLutBlock);
+            } else {
+                unit::pick<1, 2, 3, 4>(k, [&](auto bits) {         // (the order of the ladder this replaces)
+                    launch_stream<quantize_forward_lut_kernel<FN, DT, decltype(bits)::value, U, B>>(c, kLut, U, x, y, state, n, borders, nborders, p0, p1);
+                });
+                name("quantize_forward_lut_kernel", U, B);
             }
-            name("quantize_forward_lut_kernel", U, B);
-            return dry ? FEWBIT_OK : check_launch("quantize_forward(lut)");
+            return close_call(c, "quantize_forward(lut)");
         }
     }
-    if (pow2 && k <= 4) {          // full 1..4-bit tables: borders in registers
-        typedef typename std::conditional<DT == FEWBIT_F32, FwdUs32, FwdUs16>::type Us;
-        with_u(Us{}, tuned(T_U_FWD, policy_u_fwd<DT>(n)), [&](auto tag) {
+    if (nborders == (1 << k) - 1 && k <= 4) {          // full 1..4-bit tables: borders in registers
+        auto search = [&](auto tag) {
             constexpr int U = decltype(tag)::value;
-            switch (k) {
-            case 1: launch_tiled<quantize_forward_kernel<FN, DT, 1, U>>(plan, dry, dev, n, U, s, x, y, state, n, borders, p0, p1); break;
-            case 2: launch_tiled<quantize_forward_kernel<FN, DT, 2, U>>(plan, dry, dev, n, U, s, x, y, state, n, borders, p0, p1); break;
-            case 3: launch_tiled<quantize_forward_kernel<FN, DT, 3, U>>(plan, dry, dev, n, U, s, x, y, state, n, borders, p0, p1); break;
-            default: launch_tiled<quantize_forward_kernel<FN, DT, 4, U>>(plan, dry, dev, n, U, s, x, y, state, n, borders, p0, p1); break;
-            }
+            unit::pick<1, 2, 3, 4>(k, [&](auto bits) {             // (the order of the ladder this replaces)
+                launch_stream<quantize_forward_kernel<FN, DT, decltype(bits)::value, U>>(c, kTiled, U, x, y, state, n, borders, p0, p1);
+            });
             name("quantize_forward_kernel", U, kBlock);
-        });
+        };
+        const long long want = tuned(T_U_FWD, policy_u_fwd<DT>(n));
+        if constexpr (DT == FEWBIT_F32) pick_u<1, 2>(want, search);
+        else pick_u<1>(want, search);
     } else {                       // 5..8-bit tables and tables that do not fill their bit width: borders in LDS
-        launch_tiled<quantize_forward_wide_kernel<FN, DT>>(plan, dry, dev, n, 1, s, x, y, state, n, borders, nborders, k, p0, p1);
+        launch_stream<quantize_forward_wide_kernel<FN, DT>>(c, kTiled, 1, x, y, state, n, borders, nborders, k, p0, p1);
         name("quantize_forward_wide_kernel", 1, kBlock);
     }
-    return dry ? FEWBIT_OK : check_launch("quantize_forward");
+    return close_call(c, "quantize_forward");
 }
 
 }  // namespace
 
 // one functor, every dtype: the unit of the split build (external, hidden linkage; see FEWBIT_TU above)
 template <int FN>
-FEWBIT_HIDDEN int dispatch_forward_dtype(Plan *plan, bool dry, int dtype, const void *x, void *y, uint8_t *state, size_t n,
-                                         const void *borders, int nborders, int k, float p0, float p1, hipStream_t s) {
-    switch (dtype) {
-    case FEWBIT_F32: return launch_forward<FN, FEWBIT_F32>(plan, dry, x, y, state, n, borders, nborders, k, p0, p1, s);
-    case FEWBIT_F16: return launch_forward<FN, FEWBIT_F16>(plan, dry, x, y, state, n, borders, nborders, k, p0, p1, s);
-    case FEWBIT_BF16: return launch_forward<FN, FEWBIT_BF16>(plan, dry, x, y, state, n, borders, nborders, k, p0, p1, s);
-    default: return fail(FEWBIT_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
-    }
+FEWBIT_HIDDEN int dispatch_forward_dtype(Call c, int dtype, const void *x, void *y, uint8_t *state, const void *borders, int nborders, int k,
+                                         float p0, float p1) {
+    return with_dtype(dtype, [&](auto dt) { return launch_forward<FN, decltype(dt)::value>(c, x, y, state, borders, nborders, k, p0, p1); });
 }
 
 #ifdef FEWBIT_TU
-// functor id F is compiled by unit 1 + F / 3; every other unit only declares it
-#define FB_DISPATCH_ARGS (Plan *, bool, int, const void *, void *, uint8_t *, size_t, const void *, int, int, float, float, hipStream_t)
+// functor id F is compiled by unit 1 + F / 3: every unit declares all fifteen, and units 1 .. 5 then define their three (an explicit instantiation
+// declaration may be followed by the definition in the same unit)
+#define FB_CONTINUOUS_IDS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14)
+#define FB_DISPATCH_ARGS (Call, int, const void *, void *, uint8_t *, const void *, int, int, float, float)
 #define FB_DECLARE(F) extern template int dispatch_forward_dtype<F> FB_DISPATCH_ARGS;
-#define FB_DEFINE(F) template int dispatch_forward_dtype<F> FB_DISPATCH_ARGS;
-#if FEWBIT_TU == 1
-FB_DEFINE(0) FB_DEFINE(1) FB_DEFINE(2)
-#else
-FB_DECLARE(0) FB_DECLARE(1) FB_DECLARE(2)
-#endif
-#if FEWBIT_TU == 2
-FB_DEFINE(3) FB_DEFINE(4) FB_DEFINE(5)
-#else
-FB_DECLARE(3) FB_DECLARE(4) FB_DECLARE(5)
-#endif
-#if FEWBIT_TU == 3
-FB_DEFINE(6) FB_DEFINE(7) FB_DEFINE(8)
-#else
-FB_DECLARE(6) FB_DECLARE(7) FB_DECLARE(8)
-#endif
-#if FEWBIT_TU == 4
-FB_DEFINE(9) FB_DEFINE(10) FB_DEFINE(11)
-#else
-FB_DECLARE(9) FB_DECLARE(10) FB_DECLARE(11)
-#endif
-#if FEWBIT_TU == 5
-FB_DEFINE(12) FB_DEFINE(13) FB_DEFINE(14)
-#else
-FB_DECLARE(12) FB_DECLARE(13) FB_DECLARE(14)
+FB_CONTINUOUS_IDS(FB_DECLARE)
+#if FEWBIT_TU != 0
+template int dispatch_forward_dtype<3 * (FEWBIT_TU - 1) + 0> FB_DISPATCH_ARGS;
+template int dispatch_forward_dtype<3 * (FEWBIT_TU - 1) + 1> FB_DISPATCH_ARGS;
+template int dispatch_forward_dtype<3 * (FEWBIT_TU - 1) + 2> FB_DISPATCH_ARGS;
 #endif
 static_assert(FEWBIT_CONTINUOUS_COUNT == 3 * FEWBIT_TU_COUNT, "every continuous functor needs a unit");
 #endif
@@ -1229,172 +1118,124 @@ static_assert(FEWBIT_CONTINUOUS_COUNT == 3 * FEWBIT_TU_COUNT, "every continuous 
 #if FEWBIT_CORE_TU
 namespace {
 
-template <int DT>
-int launch_backward(Plan *plan, bool dry, const void *gy, const uint8_t *state, void *gx, size_t n, const void *levels, int nlevels,
-                    int k, hipStream_t s) {
-    Device dev;
-    if (const int rc = get_device(dev)) return rc;
-    if (plan) plan->k = k;
+template <int DT> int launch_backward(Call c, const void *gy, const uint8_t *state, void *gx, const void *levels, int nlevels, int k) {
+    if (const int rc = open_call(c, k)) return rc;
     if (k > 4) {
-        launch_tiled<quantize_backward_wide_kernel<DT>>(plan, dry, dev, n, 1, s, gy, state, gx, n, levels, nlevels, k);
-        if (plan) snprintf(plan->kernel, sizeof plan->kernel, "quantize_backward_wide_kernel<%s, %d bits>", dtype_name(DT), k);
-        return dry ? FEWBIT_OK : check_launch("quantize_backward");
+        launch_stream<quantize_backward_wide_kernel<DT>>(c, kTiled, 1, gy, state, gx, c.n, levels, nlevels, k);
+        name_plan(c, "quantize_backward_wide_kernel<%s, %d bits>", dtype_name(DT), k);
+        return close_call(c, "quantize_backward");
     }
-    typedef typename std::conditional<DT == FEWBIT_F32, StreamUs32, StreamUs16>::type Us;
-    with_u(Us{}, tuned(T_U_BWD, policy_u_bwd<DT>(n)), [&](auto tag) {
+    pick_u<1, 2>(tuned(T_U_BWD, policy_u_bwd<DT>(c.n)), [&](auto tag) {
         constexpr int U = decltype(tag)::value;
-        switch (k) {
-        case 1: launch_tiled<quantize_backward_kernel<DT, 1, U>>(plan, dry, dev, n, U, s, gy, state, gx, n, levels, nlevels); break;
-        case 2: launch_tiled<quantize_backward_kernel<DT, 2, U>>(plan, dry, dev, n, U, s, gy, state, gx, n, levels, nlevels); break;
-        case 3: launch_tiled<quantize_backward_kernel<DT, 3, U>>(plan, dry, dev, n, U, s, gy, state, gx, n, levels, nlevels); break;
-        default: launch_tiled<quantize_backward_kernel<DT, 4, U>>(plan, dry, dev, n, U, s, gy, state, gx, n, levels, nlevels); break;
-        }
-        if (plan) snprintf(plan->kernel, sizeof plan->kernel, "quantize_backward_kernel<%s, %d bits, U=%d>", dtype_name(DT), k, U);
+        unit::pick<1, 2, 3, 4>(k, [&](auto bits) {                 // (the order of the ladder this replaces)
+            launch_stream<quantize_backward_kernel<DT, decltype(bits)::value, U>>(c, kTiled, U, gy, state, gx, c.n, levels, nlevels);
+        });
+        name_plan(c, "quantize_backward_kernel<%s, %d bits, U=%d>", dtype_name(DT), k, U);
     });
-    return dry ? FEWBIT_OK : check_launch("quantize_backward");
+    return close_call(c, "quantize_backward");
 }
 
-template <int FN, int DT>
-int launch_step1_forward(Plan *plan, bool dry, const void *x, void *y, uint8_t *state, size_t n, float p0, float p1, hipStream_t s) {
-    Device dev;
-    if (const int rc = get_device(dev)) return rc;
-    if (plan) plan->k = 1;
-    typedef typename std::conditional<DT == FEWBIT_F32, StreamUs32, StreamUs16>::type Us;
-    with_u(Us{}, tuned(T_U_STEP1, policy_u_step1_fwd<DT>(n)), [&](auto tag) {
+template <int FN, int DT> int launch_step1_forward(Call c, const void *x, void *y, uint8_t *state, float p0, float p1) {
+    if (const int rc = open_call(c, 1)) return rc;
+    pick_u<1, 2>(tuned(T_U_STEP1, policy_u_step1_fwd<DT>(c.n)), [&](auto tag) {
         constexpr int U = decltype(tag)::value;
-        launch_tiled<stepwise1_forward_kernel<FN, DT, U>>(plan, dry, dev, n, U, s, x, y, state, n, p0, p1);
-        if (plan) snprintf(plan->kernel, sizeof plan->kernel, "stepwise1_forward_kernel<%s, %s, U=%d>", kStepNames[FN], dtype_name(DT), U);
+        launch_stream<stepwise1_forward_kernel<FN, DT, U>>(c, kTiled, U, x, y, state, c.n, p0, p1);
+        name_plan(c, "stepwise1_forward_kernel<%s, %s, U=%d>", kStepNames[FN], dtype_name(DT), U);
     });
-    return dry ? FEWBIT_OK : check_launch("stepwise1_forward");
+    return close_call(c, "stepwise1_forward");
 }
 
-template <int FN>
-int dispatch_step1_dtype(Plan *plan, bool dry, int dtype, const void *x, void *y, uint8_t *state, size_t n, float p0, float p1,
-                         hipStream_t s) {
-    switch (dtype) {
-    case FEWBIT_F32: return launch_step1_forward<FN, FEWBIT_F32>(plan, dry, x, y, state, n, p0, p1, s);
-    case FEWBIT_F16: return launch_step1_forward<FN, FEWBIT_F16>(plan, dry, x, y, state, n, p0, p1, s);
-    case FEWBIT_BF16: return launch_step1_forward<FN, FEWBIT_BF16>(plan, dry, x, y, state, n, p0, p1, s);
-    default: return fail(FEWBIT_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
-    }
-}
-
-template <int DT>
-int launch_step1_backward(Plan *plan, bool dry, const void *gy, const uint8_t *state, void *gx, size_t n, float m0, float m1,
-                          hipStream_t s) {
-    Device dev;
-    if (const int rc = get_device(dev)) return rc;
-    if (plan) plan->k = 1;
-    typedef typename std::conditional<DT == FEWBIT_F32, StreamUs32, StreamUs16>::type Us;
-    with_u(Us{}, tuned(T_U_STEP1, policy_u_step1_bwd<DT>(n)), [&](auto tag) {
+template <int DT> int launch_step1_backward(Call c, const void *gy, const uint8_t *state, void *gx, float m0, float m1) {
+    if (const int rc = open_call(c, 1)) return rc;
+    pick_u<1, 2>(tuned(T_U_STEP1, policy_u_step1_bwd<DT>(c.n)), [&](auto tag) {
         constexpr int U = decltype(tag)::value;
-        launch_tiled<stepwise1_backward_kernel<DT, U>>(plan, dry, dev, n, U, s, gy, state, gx, n, m0, m1);
-        if (plan) snprintf(plan->kernel, sizeof plan->kernel, "stepwise1_backward_kernel<%s, U=%d>", dtype_name(DT), U);
+        launch_stream<stepwise1_backward_kernel<DT, U>>(c, kTiled, U, gy, state, gx, c.n, m0, m1);
+        name_plan(c, "stepwise1_backward_kernel<%s, U=%d>", dtype_name(DT), U);
     });
-    return dry ? FEWBIT_OK : check_launch("stepwise1_backward");
+    return close_call(c, "stepwise1_backward");
 }
-
-#define FB_CONTINUOUS_CASES                                                                                  \
-    FB_CASE(FEWBIT_CELU) FB_CASE(FEWBIT_ELU) FB_CASE(FEWBIT_GELU) FB_CASE(FEWBIT_HARDSWISH)                 \
-    FB_CASE(FEWBIT_LOGSIGMOID) FB_CASE(FEWBIT_MISH) FB_CASE(FEWBIT_SELU) FB_CASE(FEWBIT_SIGMOID)            \
-    FB_CASE(FEWBIT_SILU) FB_CASE(FEWBIT_SOFTPLUS) FB_CASE(FEWBIT_SOFTSIGN) FB_CASE(FEWBIT_TANH)             \
-    FB_CASE(FEWBIT_TANHSHRINK) FB_CASE(FEWBIT_IDENTITY) FB_CASE(FEWBIT_IDENTITY_FOLD)
-#define FB_STEPWISE_CASES                                                                                    \
-    FB_CASE(FEWBIT_HARDSHRINK) FB_CASE(FEWBIT_HARDSIGMOID) FB_CASE(FEWBIT_HARDTANH) FB_CASE(FEWBIT_LEAKY_RELU) \
-    FB_CASE(FEWBIT_RELU) FB_CASE(FEWBIT_RELU6) FB_CASE(FEWBIT_SOFTSHRINK) FB_CASE(FEWBIT_THRESHOLD)
 
 // ---- the four entry points with a `dry` flag (describe = the same dispatch without the launch) ----
+// Each tests its arguments in an order of its own, and that order is behaviour: the table size, then the dtype, then (not dry) the buffers
+// (ends_at_buffers, fewbit_core.h); fn LAST in the two forwards (the default of what was a case ladder) but FIRST in do_stepwise1_backward.
 int do_quantize_forward(Plan *plan, bool dry, int fn, int dtype, const void *x, void *y, uint8_t *state, size_t n,
                         const void *borders, int nborders, double p0, double p1, void *stream) {
     if (nborders < 1 || nborders > 255) return fail(FEWBIT_ERR_UNSUPPORTED, "nborders=%d outside [1,255]", nborders);
-    if (dtype != FEWBIT_F32 && dtype != FEWBIT_F16 && dtype != FEWBIT_BF16) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
+    if (!unit::known_dtype(dtype)) return refuse_dtype(dtype);
     const int k = fewbit_hip_bitwidth(nborders + 1);
-    if (!dry) {
-        if (n == 0) return FEWBIT_OK;
-        if (!x || !y || !state || !borders) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "null pointer argument");
-        FB_VALIDATE("x", x, n * dtype_size(dtype));
-        FB_VALIDATE("y", y, n * dtype_size(dtype));
-        FB_VALIDATE("state", state, fewbit_hip_state_nbytes(n, k));
-        FB_VALIDATE("borders", borders, static_cast<size_t>(nborders) * dtype_size(dtype));
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t size = unit::size_of(dtype);
+    int rc;
+    if (!dry && ends_at_buffers(&rc, n, {{"x", x, n * size}, {"y", y, n * size}, {"state", state, fewbit_hip_state_nbytes(n, k)},
+                                         {"borders", borders, static_cast<size_t>(nborders) * size}}))
+        return rc;
+    const Call c{plan, dry, n, static_cast<hipStream_t>(stream), {}};
     const float a = static_cast<float>(p0), b = static_cast<float>(p1);
-#define FB_CASE(F) case F: return dispatch_forward_dtype<F>(plan, dry, dtype, x, y, state, n, borders, nborders, k, a, b, s);
-    switch (fn) {
-        FB_CONTINUOUS_CASES
-    default: return fail(FEWBIT_ERR_INVALID_ARGUMENT, "unknown continuous fn %d", fn);
-    }
-#undef FB_CASE
+    const bool known = pick_fn<FEWBIT_CONTINUOUS_COUNT>(fn, [&](auto f) {
+        rc = dispatch_forward_dtype<decltype(f)::value>(c, dtype, x, y, state, borders, nborders, k, a, b);
+    });
+    return known ? rc : fail(FEWBIT_ERR_INVALID_ARGUMENT, "unknown continuous fn %d", fn);
 }
 
 int do_quantize_backward(Plan *plan, bool dry, int dtype, const void *gy, const uint8_t *state, void *gx, size_t n,
                          const void *levels, int nlevels, void *stream) {
     if (nlevels < 2 || nlevels > 256) return fail(FEWBIT_ERR_UNSUPPORTED, "nlevels=%d outside [2,256]", nlevels);
-    if (dtype != FEWBIT_F32 && dtype != FEWBIT_F16 && dtype != FEWBIT_BF16) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
+    if (!unit::known_dtype(dtype)) return refuse_dtype(dtype);
     const int k = fewbit_hip_bitwidth(nlevels);
-    if (!dry) {
-        if (n == 0) return FEWBIT_OK;
-        if (!gy || !gx || !state || !levels) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "null pointer argument");
-        FB_VALIDATE("gy", gy, n * dtype_size(dtype));
-        FB_VALIDATE("gx", gx, n * dtype_size(dtype));
-        FB_VALIDATE("state", state, fewbit_hip_state_nbytes(n, k));
-        FB_VALIDATE("levels", levels, static_cast<size_t>(nlevels) * dtype_size(dtype));
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case FEWBIT_F32: return launch_backward<FEWBIT_F32>(plan, dry, gy, state, gx, n, levels, nlevels, k, s);
-    case FEWBIT_F16: return launch_backward<FEWBIT_F16>(plan, dry, gy, state, gx, n, levels, nlevels, k, s);
-    default: return launch_backward<FEWBIT_BF16>(plan, dry, gy, state, gx, n, levels, nlevels, k, s);
-    }
+    const size_t size = unit::size_of(dtype);
+    int rc;
+    if (!dry && ends_at_buffers(&rc, n, {{"gy", gy, n * size}, {"gx", gx, n * size}, {"state", state, fewbit_hip_state_nbytes(n, k)},
+                                         {"levels", levels, static_cast<size_t>(nlevels) * size}}))
+        return rc;
+    const Call c{plan, dry, n, static_cast<hipStream_t>(stream), {}};
+    return with_dtype(dtype, [&](auto dt) { return launch_backward<decltype(dt)::value>(c, gy, state, gx, levels, nlevels, k); });
 }
 
 int do_stepwise1_forward(Plan *plan, bool dry, int fn, int dtype, const void *x, void *y, uint8_t *state, size_t n, double p0,
                          double p1, void *stream) {
-    if (dtype != FEWBIT_F32 && dtype != FEWBIT_F16 && dtype != FEWBIT_BF16) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
-    if (!dry) {
-        if (n == 0) return FEWBIT_OK;
-        if (!x || !y || !state) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "null pointer argument");
-        FB_VALIDATE("x", x, n * dtype_size(dtype));
-        FB_VALIDATE("y", y, n * dtype_size(dtype));
-        FB_VALIDATE("state", state, fewbit_hip_state_nbytes(n, 1));
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!unit::known_dtype(dtype)) return refuse_dtype(dtype);
+    const size_t size = unit::size_of(dtype);
+    int rc;
+    if (!dry && ends_at_buffers(&rc, n, {{"x", x, n * size}, {"y", y, n * size}, {"state", state, fewbit_hip_state_nbytes(n, 1)}})) return rc;
+    const Call c{plan, dry, n, static_cast<hipStream_t>(stream), {}};
     const float a = static_cast<float>(p0), b = static_cast<float>(p1);
-#define FB_CASE(F) case F: return dispatch_step1_dtype<F>(plan, dry, dtype, x, y, state, n, a, b, s);
-    switch (fn) {
-        FB_STEPWISE_CASES
-    default: return fail(FEWBIT_ERR_INVALID_ARGUMENT, "unknown stepwise fn %d", fn);
-    }
-#undef FB_CASE
+    const bool known = pick_fn<FEWBIT_STEPWISE_COUNT>(fn, [&](auto f) {
+        rc = with_dtype(dtype, [&](auto dt) { return launch_step1_forward<decltype(f)::value, decltype(dt)::value>(c, x, y, state, a, b); });
+    });
+    return known ? rc : fail(FEWBIT_ERR_INVALID_ARGUMENT, "unknown stepwise fn %d", fn);
 }
 
 int do_stepwise1_backward(Plan *plan, bool dry, int fn, int dtype, const void *gy, const uint8_t *state, void *gx, size_t n,
                           double p0, void *stream) {
     if (fn < 0 || fn >= FEWBIT_STEPWISE_COUNT) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "unknown stepwise fn %d", fn);
-    if (dtype != FEWBIT_F32 && dtype != FEWBIT_F16 && dtype != FEWBIT_BF16) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
-    if (!dry) {
-        if (n == 0) return FEWBIT_OK;
-        if (!gy || !gx || !state) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "null pointer argument");
-        FB_VALIDATE("gy", gy, n * dtype_size(dtype));
-        FB_VALIDATE("gx", gx, n * dtype_size(dtype));
-        FB_VALIDATE("state", state, fewbit_hip_state_nbytes(n, 1));
-    }
+    if (!unit::known_dtype(dtype)) return refuse_dtype(dtype);
+    const size_t size = unit::size_of(dtype);
+    int rc;
+    if (!dry && ends_at_buffers(&rc, n, {{"gy", gy, n * size}, {"gx", gx, n * size}, {"state", state, fewbit_hip_state_nbytes(n, 1)}})) return rc;
     float m0 = 0.0f, m1 = 1.0f;
     if (fn == FEWBIT_HARDSIGMOID) m1 = 1.0f / 6.0f;
     if (fn == FEWBIT_LEAKY_RELU) { m0 = 1.0f; m1 = static_cast<float>(p0); }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case FEWBIT_F32: return launch_step1_backward<FEWBIT_F32>(plan, dry, gy, state, gx, n, m0, m1, s);
-    case FEWBIT_F16: return launch_step1_backward<FEWBIT_F16>(plan, dry, gy, state, gx, n, m0, m1, s);
-    default: return launch_step1_backward<FEWBIT_BF16>(plan, dry, gy, state, gx, n, m0, m1, s);
-    }
+    const Call c{plan, dry, n, static_cast<hipStream_t>(stream), {}};
+    return with_dtype(dtype, [&](auto dt) { return launch_step1_backward<decltype(dt)::value>(c, gy, state, gx, m0, m1); });
 }
 
-int write_plan(const Plan &p, char *buf, size_t len) {
+// what fewbit_hip_describe_* returns: the plan of the dry call `run`, as JSON
+template <class Run> int describe(char *buf, size_t len, Run &&run) {
+    Plan p{};
+    if (const int rc = run(&p)) return rc;
     if (!buf || len == 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "describe: no output buffer");
     snprintf(buf, len, "{\"kernel\": \"%s\", \"blocks\": %u, \"threads\": %d, \"blocks_per_cu\": %d, \"chunk\": %d, \"u\": %d, \"bits\": %d}",
              p.kernel, p.blocks, p.threads, p.blocks_per_cu, p.chunk, p.u, p.k);
     return FEWBIT_OK;
+}
+
+// both codec entry points: `first` and `second` are the kernel's pointers in its order, codes and state the same two by name
+template <auto Kern, class First, class Second>
+int run_codec(const char *what, First first, Second second, const int32_t *codes, const uint8_t *state, size_t n, int nbits, void *stream) {
+    if (nbits < 1 || nbits > 8) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "nbits=%d outside [1,8]", nbits);
+    int rc;
+    if (ends_at_buffers(&rc, n, {{"codes", codes, n * sizeof(int32_t)}, {"state", state, fewbit_hip_state_nbytes(n, nbits)}})) return rc;
+    hipLaunchKernelGGL(Kern, dim3(group_grid(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), first, second, n, nbits);
+    return check_launch(what);
 }
 
 }  // namespace
@@ -1442,27 +1283,21 @@ int fewbit_hip_stepwise1_backward(int fn, int dtype, const void *gy, const uint8
 }
 
 int fewbit_hip_describe_quantize_forward(int fn, int dtype, size_t n, int nborders, char *buf, size_t len) {
-    Plan p{};
-    const int rc = do_quantize_forward(&p, true, fn, dtype, nullptr, nullptr, nullptr, n, nullptr, nborders, 0.0, 0.0, nullptr);
-    return rc ? rc : write_plan(p, buf, len);
+    return describe(buf, len, [&](Plan *p) {
+        return do_quantize_forward(p, true, fn, dtype, nullptr, nullptr, nullptr, n, nullptr, nborders, 0.0, 0.0, nullptr);
+    });
 }
 
 int fewbit_hip_describe_quantize_backward(int dtype, size_t n, int nlevels, char *buf, size_t len) {
-    Plan p{};
-    const int rc = do_quantize_backward(&p, true, dtype, nullptr, nullptr, nullptr, n, nullptr, nlevels, nullptr);
-    return rc ? rc : write_plan(p, buf, len);
+    return describe(buf, len, [&](Plan *p) { return do_quantize_backward(p, true, dtype, nullptr, nullptr, nullptr, n, nullptr, nlevels, nullptr); });
 }
 
 int fewbit_hip_describe_stepwise1_forward(int fn, int dtype, size_t n, char *buf, size_t len) {
-    Plan p{};
-    const int rc = do_stepwise1_forward(&p, true, fn, dtype, nullptr, nullptr, nullptr, n, 0.0, 0.0, nullptr);
-    return rc ? rc : write_plan(p, buf, len);
+    return describe(buf, len, [&](Plan *p) { return do_stepwise1_forward(p, true, fn, dtype, nullptr, nullptr, nullptr, n, 0.0, 0.0, nullptr); });
 }
 
 int fewbit_hip_describe_stepwise1_backward(int fn, int dtype, size_t n, char *buf, size_t len) {
-    Plan p{};
-    const int rc = do_stepwise1_backward(&p, true, fn, dtype, nullptr, nullptr, nullptr, n, 0.0, nullptr);
-    return rc ? rc : write_plan(p, buf, len);
+    return describe(buf, len, [&](Plan *p) { return do_stepwise1_backward(p, true, fn, dtype, nullptr, nullptr, nullptr, n, 0.0, nullptr); });
 }
 
 int fewbit_hip_tune(const char *key, long long value) {
@@ -1481,25 +1316,11 @@ int fewbit_hip_tune(const char *key, long long value) {
 }
 
 int fewbit_hip_pack_codes(const int32_t *codes, uint8_t *state, size_t n, int nbits, void *stream) {
-    if (nbits < 1 || nbits > 8) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "nbits=%d outside [1,8]", nbits);
-    if (n == 0) return FEWBIT_OK;
-    if (!codes || !state) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "null pointer argument");
-    FB_VALIDATE("codes", codes, n * sizeof(int32_t));
-    FB_VALIDATE("state", state, fewbit_hip_state_nbytes(n, nbits));
-    hipLaunchKernelGGL(pack_codes_kernel, dim3(group_grid(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), codes,
-                       state, n, nbits);
-    return check_launch("pack_codes");
+    return run_codec<pack_codes_kernel>("pack_codes", codes, state, codes, state, n, nbits, stream);
 }
 
 int fewbit_hip_unpack_codes(const uint8_t *state, int32_t *codes, size_t n, int nbits, void *stream) {
-    if (nbits < 1 || nbits > 8) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "nbits=%d outside [1,8]", nbits);
-    if (n == 0) return FEWBIT_OK;
-    if (!codes || !state) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "null pointer argument");
-    FB_VALIDATE("codes", codes, n * sizeof(int32_t));
-    FB_VALIDATE("state", state, fewbit_hip_state_nbytes(n, nbits));
-    hipLaunchKernelGGL(unpack_codes_kernel, dim3(group_grid(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
-                       state, codes, n, nbits);
-    return check_launch("unpack_codes");
+    return run_codec<unpack_codes_kernel>("unpack_codes", state, codes, codes, state, n, nbits, stream);
 }
 
 }  // extern "C"

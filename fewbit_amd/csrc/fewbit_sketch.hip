@@ -59,17 +59,11 @@
 #include <cstring>
 #include <type_traits>
 
+#include "fewbit_core.h"       // (fail, the CU count of a device: shared with the core unit of fewbit_kernels.hip)
 #include "fewbit_hip.h"
 #include "fewbit_philox.h"
 
-#define FEWBIT_HIDDEN __attribute__((visibility("hidden")))
-
 namespace fewbit_hip {
-
-// shared with the core unit of fewbit_kernels.hip
-extern FEWBIT_HIDDEN thread_local char g_last_error[256];
-FEWBIT_HIDDEN int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
 namespace sketch {
 
 constexpr int BN = 256;                     // features per tile
@@ -886,15 +880,9 @@ Tuning tuning_now() {
 }
 
 int device_cus() {
-    static std::atomic<int> cached[64];
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return 256; }
-    int v = cached[dev].load(std::memory_order_relaxed);
-    if (v == 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) { (void)hipGetLastError(); v = 256; }
-        cached[dev].store(v, std::memory_order_relaxed);
-    }
-    return v;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) { (void)hipGetLastError(); return 256; }
+    return cached_cus(dev);
 }
 
 constexpr size_t kWorkspaceAlign = 256;

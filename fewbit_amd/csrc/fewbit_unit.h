@@ -1,5 +1,7 @@
 // fewbit_unit.h -- what a unit of the companion library libfewbit_hipx.so shares with the others: the error reporter, the dtype and pointer
 // predicates, the mask of a seed, the plan of a flat sweep, the refusals every entry point words alike and the dispatcher of compile-time choices.
+// The units of libfewbit_hip.so take the predicates (known_dtype, size_of) and the dispatcher (pick, pick_dtype) from here too, through fewbit_core.h,
+// but none of the refusals: those report through dft::fail, and that library has a reporter and wordings of its own.
 // Host code and constants only, beyond the one-line mask_bits: the kernels' bodies stay in their units (routing a kernel through a shared
 // __device__ function changes its code, EXPERIMENTS.md 8.16 and 8.27).  Included by fewbit_quantdef.h and fewbit_fft4.h and by the units that
 // include neither.

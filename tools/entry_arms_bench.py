@@ -4,7 +4,9 @@ forward_plain) and layer_norm_bench.py (the same three) at the smallest size of 
 whose time is one launch into preallocated buffers, so the ones a change of the C host code in front of a launch can move.  Built and timed as the
 tools do (tools/sketch_bench.py::timed, every arm once before any is timed, two alternations, the smaller median quoted).  `--root` names the tree
 whose package and library are measured, so one file measures a checkout of another commit beside this one; `--rows` (default: the tools' 16384)
-makes the kernels short enough for the launch itself to be the whole arm.
+makes the kernels short enough for the launch itself to be the whole arm.  `--families core` / `companion` times only the four activation entry points
+of libfewbit_hip.so (quantize_forward with gelu and 15 borders, quantize_backward, stepwise1_forward and stepwise1_backward with relu, through
+fewbit_amd.cabi's pre-resolved launches, at rows x 768 and at n = 4096, where the arm is bound by the launch) or only the arms of the companion library.
 
     python tools/entry_arms_bench.py [--root TREE] [--rows N]        ->  one JSON line: {"root", "rows", "us": {arm: microseconds}}
 """
@@ -17,22 +19,42 @@ ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
 ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument('--rows', type=int, default=16384)
 ap.add_argument('--reps', type=int, default=200, help='back-to-back calls per timed round')
+ap.add_argument('--families', choices=('all', 'core', 'companion'), default='all')
 args = ap.parse_args()
 ROOT = os.path.abspath(args.root)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import torch  # noqa: E402
-from fewbit_amd import cabi_x  # noqa: E402
+from fewbit_amd import cabi, cabi_x  # noqa: E402
 from sketch_bench import timed  # noqa: E402
 
 DEV, SEED, P, EPS, BITS = 'cuda', 2026, 0.1, 1e-5, (2, 4, 8)
 ROWS = args.rows
 
 
+def core_arms_of(dtype):
+    """the four activation entry points of libfewbit_hip.so, each one launch into preallocated buffers"""
+    tag = str(dtype).replace('torch.', '')
+    borders = torch.linspace(-3, 3, 15, device=DEV).to(dtype)
+    levels = torch.linspace(0, 1, 16, device=DEV).to(dtype)
+    arms = {}
+    for n in (ROWS * 768, 4096):
+        x, gy = torch.randn(n, device=DEV).to(dtype), torch.randn(n, device=DEV).to(dtype)
+        y, gx = torch.empty_like(x), torch.empty_like(x)
+        state, bit = (torch.empty(cabi.state_nbytes(n, k), dtype=torch.uint8, device=DEV) for k in (4, 1))
+        arms[f'core {tag} quantize_forward n={n}'] = cabi.bind_forward('gelu', x, borders, y, state)
+        arms[f'core {tag} quantize_backward n={n}'] = cabi.bind_backward(gy, state, levels, gx)
+        arms[f'core {tag} stepwise1_forward n={n}'] = cabi.bind_stepwise1_forward('relu', x, y, bit)
+        arms[f'core {tag} stepwise1_backward n={n}'] = cabi.bind_stepwise1_backward('relu', gy, bit, gx)
+    return arms
+
+
 def arms_of(dtype):
     tag = str(dtype).replace('torch.', '')
     new = lambda width: torch.randn(ROWS, width, device=DEV).to(dtype)
-    arms = {}
+    arms = core_arms_of(dtype) if args.families != 'companion' else {}
+    if args.families == 'core':
+        return arms
     # quant_linear_bench: 16384 x 768
     x, n = new(768), ROWS * 768
     out, packed = torch.empty_like(x), {bits: cabi_x.quant_pack(x, SEED, bits) for bits in BITS}

@@ -62,7 +62,11 @@ ROWS = [
     ('transform_one_text_isa_identity.txt', 'tools/isa_digest.py --diff --rename: machine code of all 2143 device functions before / after pass A and pass B of the plain pairs became one kernel template each (798 kernels renamed, none changed)', f'{E} 8.16'),
     ('unit_fold_isa_identity.txt', "tools/isa_digest.py --diff: machine code of all 2888 device functions before / after the companion units' host code and element access moved into fewbit_unit.h (none changed)", f'{E} 8.27'),
     ('refusal_digest.txt', 'tools/refusal_digest.py: status and message of every refusal of the quant, glu, norm, fused-norm and dropout entry points, single faults and pairs (tests/test_refusals_host.py compares)', f'{E} 8.27'),
-    ('unit_fold_speed*.txt', 'the launch-bound entry-point arms of quant_linear_bench, dropout_bench, glu_bench and layer_norm_bench from the parent and from the tree with fewbit_unit.h, alternating five times', f'{E} 8.27'),
+    ('core_fold_isa_identity.txt', "tools/isa_digest.py --diff: machine code of all 2888 device functions before / after the activation unit's dispatch, checks and launch code were said once (none changed)", f'{E} 8.28'),
+    ('core_refusal_digest.txt', 'tools/core_refusal_digest.py: status and message of every refusal of the activation launches, describes, tune and codec entry points, single faults and pairs, plain and with FEWBIT_HIP_VALIDATE=1; recorded from the library before the fold (tests/test_core_refusals_host.py compares)', f'{E} 8.28'),
+    ('core_fold_plan_digest.txt', 'tools/plan_digest.py --digest: lines and sha256 per entry point and tune setting of the 1 449 569 plans of the sweep on a 256-CU MI355X, the same from the parent and from the tree', f'{E} 8.28'),
+    ('core_fold_speed.txt', 'the four activation entry points at 16384 x 768 and at n = 4096, bf16 and fp32, from the parent and from the tree with the folded host code, alternating five times', f'{E} 8.28'),
+    ('unit_fold_speed*.txt','the launch-bound entry-point arms of quant_linear_bench, dropout_bench, glu_bench and layer_norm_bench from the parent and from the tree with fewbit_unit.h, alternating five times', f'{E} 8.27'),
     ('signed_transform_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1915 device functions before / after the signed pass A was added (228 new)', f'{E} 8.15'),
     ('moments_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1890 device functions before / after fewbit_moments.hip was added (13 new)', f'{E} 8.9'),
     ('r06_dct_stagger.txt|r06_dct_fused_upper_bound.txt|r06_dct_inter16.txt', 'DCT experiments not kept: staggered starts, both passes in one launch (timing only), a bf16 intermediate', 'EXPERIMENTS.md'),
