@@ -78,13 +78,14 @@ else:
 
 from . import functional  # noqa: E402,F401
 from . import modules  # noqa: E402,F401
-from . import approx, cli, compat, fft, glu, linear, norm, variance  # noqa: E402,F401
+from . import approx, cli, compat, fft, glu, linear, norm, variance, xent  # noqa: E402,F401
 from .modules import *  # noqa: E402,F401,F403
 from .linear import LinearCRS, LinearGRP, QuantizedLinear, RandomizedLinear  # noqa: E402,F401
 from .dropout import Dropout, dropout, dropout_add  # noqa: E402,F401  (fewbit_amd.dropout is the function from here on; the module: sys.modules['fewbit_amd.dropout'])
 from .norm import (DropoutAddLayerNorm, DropoutAddRMSNorm, QuantizedLayerNorm, QuantizedRMSNorm, dropout_add_layer_norm_quantized,  # noqa: E402,F401
                    dropout_add_rms_norm_quantized, layer_norm_quantized, rms_norm_quantized)
 from .glu import QuantizedGatedMLP, QuantizedGLU, gated_mlp_quantized, glu_quantized  # noqa: E402,F401
+from .xent import CrossEntropyLoss, cross_entropy  # noqa: E402,F401
 from .util import map_module, memory_usage_hooks  # noqa: E402,F401
 
 __version__ = '0.2.0'

@@ -3,7 +3,7 @@ of ``libfewbit_hip.so`` was frozen at version 5 (``cabi.SYMBOLS`` stays that lis
 torch's current stream on the tensors' device, no fallback -- a missing library or an unsupported shape raises.  What it binds: the sampled
 Fourier transform, the zero-extended and sign-flipped sampled transforms, the column sampling of LinearCRS, the moments of the variance
 estimator, the dropout of a seed, the packed form of a seed, the layer norm and the RMS norm that keep the normalized rows of a seed, and the
-same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed, with the backward that also rebuilds that product from the state.
+same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed, with the backward that also rebuilds that product from the state, and the cross entropy of a row that keeps the logits as given and one float per row.
 """
 import ctypes
 import os
@@ -21,13 +21,13 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'quant_unpack', 'quant_pack_host', 'quant_unpack_host', 'NORM_MAX_WIDTH', 'norm_plan', 'norm_state_bytes', 'norm_workspace_bytes', 'norm_state_host',
            'norm_state_unpack_host', 'layer_norm_forward', 'layer_norm_backward', 'rms_norm_forward', 'rms_norm_backward', 'add_layer_norm_forward', 'add_layer_norm_backward',
            'add_rms_norm_forward', 'add_rms_norm_backward', 'GLU_ACTIVATIONS', 'glu_state_bytes', 'glu_state_host', 'glu_forward', 'glu_backward',
-           'glu_backward_product']
+           'glu_backward_product', 'CROSS_ENTROPY_MAX_GROUPS', 'cross_entropy_host', 'cross_entropy_forward', 'cross_entropy_backward']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
 REVISION = 2                                   # FEWBIT_HIPX_REVISION: additions inside ABI version 1 (2: the crs entry points)
 
-_vp, _sz, _i32, _u32, _u64, _dbl = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double
+_vp, _sz, _i32, _u32, _u64, _dbl, _i64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double, ctypes.c_int64
 
 # every symbol include/fewbit_hipx.h declares: (restype, argtypes).  The ONE list: ``SYMBOLS`` is its keys, ``lib()`` refuses a library that lacks one
 # of them and types every one of them from here, so no entry point can be called with ctypes' default conversions.
@@ -88,6 +88,10 @@ _SIGNATURES = {
     'fewbit_hipx_glu_backward': (_i32, [_i32, _i32, _vp, _vp, _sz, _sz, _i32, _vp, _sz, _vp, _sz, _vp]),
     # the same backward that also rebuilds the product from the decodes (the gated MLP as one node): inside revision 2 as well, recognised by its symbol
     'fewbit_hipx_glu_backward_product': (_i32, [_i32, _i32, _vp, _vp, _sz, _sz, _i32, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    # the loss of a row (the cross entropy that keeps the logits as given and one float per row): inside revision 2 as well, recognised by its symbols
+    'fewbit_hipx_cross_entropy_host': (_i32, [_vp, _vp, _sz, _sz, _i64, _vp, _vp, _vp, _vp]),
+    'fewbit_hipx_cross_entropy_forward': (_i32, [_i32, _vp, _sz, _sz, _sz, _vp, _i64, _vp, _vp, _vp]),
+    'fewbit_hipx_cross_entropy_backward': (_i32, [_i32, _vp, _sz, _sz, _sz, _vp, _i64, _vp, _vp, _sz, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -900,3 +904,94 @@ def glu_backward_product(gy: Optional[torch.Tensor], state: torch.Tensor, activa
             raise FewbitHipError('without gy the product buffer must be given: it carries the shape and the dtype')
     outputs = ((d_gate, want[0], 'd_gate'), (d_up, want[1], 'd_up'), (product, want[2], 'product'))
     return _glu_backward('glu_backward_product', gy, product if gy is None else gy, state, activation, bits, outputs, stream, act)
+
+
+# ---- the cross entropy of a row that keeps the logits as given and one float per row (fewbit_amd/csrc/fewbit_xent.hip) -----------------------------------
+CROSS_ENTROPY_MAX_GROUPS = 2048                 # workgroups of either launch (kMaxGroups in fewbit_xent.hip), one row each at a time; beyond it they walk on
+
+
+def cross_entropy_host(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -100, grow: Optional[torch.Tensor] = None, want_grad: bool = True):
+    """The definition (include/fewbit_hipx.h, "The loss of a row") evaluated on the host in float64 -> ``(lse, loss, dlogits)``: ``logits`` 2-D (taken
+    as contiguous fp32, so pass the values of a 16-bit tensor as ``.float()``), ``target`` int64 of ``rows`` elements, ``grow`` one number per row (or
+    None: 1).  ``lse`` and ``loss``: float64 of ``rows`` elements; ``dlogits``: float64 ``rows x width``, or None without ``want_grad``.  No GPU needed."""
+    if logits.dim() != 2:
+        raise FewbitHipError(f'logits must be 2-D (got {logits.dim()} dimensions)')
+    x = logits.detach().to(device='cpu', dtype=torch.float32).contiguous()
+    rows, width = x.shape
+    t = target.detach().to(device='cpu', dtype=torch.int64).contiguous()
+    if t.numel() != rows:
+        raise FewbitHipError(f'target must have {rows} elements (got {t.numel()})')
+    g = None if grow is None else grow.detach().to(device='cpu', dtype=torch.float64).expand(rows).contiguous()
+    lse, loss = torch.empty(rows, dtype=torch.float64), torch.empty(rows, dtype=torch.float64)
+    dlogits = torch.empty((rows, width), dtype=torch.float64) if want_grad else None
+    _check(lib().fewbit_hipx_cross_entropy_host(x.data_ptr(), t.data_ptr(), rows, width, ignore_index, _ptr(g), lse.data_ptr(), loss.data_ptr(), _ptr(dlogits)))
+    return lse, loss, dlogits
+
+
+def _logits_rows(t: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    """(rows, width, row stride) of a 2-D GPU tensor of logits: unit stride along the width, rows at least a width apart"""
+    if t.device.type != 'cuda':
+        raise FewbitHipError(f'{what} must live on the GPU (got {t.device})')
+    if t.dtype not in DTYPES:
+        raise FewbitHipError(f'unsupported dtype {t.dtype}')
+    if t.dim() != 2:
+        raise FewbitHipError(f'{what} must be 2-D (got {t.dim()} dimensions)')
+    rows, width = t.shape
+    ld = t.stride(0) if rows > 1 else width
+    if (width > 1 and t.stride(1) != 1) or ld < width:
+        raise FewbitHipError(f'{what} must have unit stride along its width and rows at least a width apart (strides {tuple(t.stride())})')
+    return rows, width, ld
+
+
+def _row_vector(t: Optional[torch.Tensor], dtype: torch.dtype, rows: int, device, what: str) -> torch.Tensor:
+    if t is None:
+        return torch.empty(rows, dtype=dtype, device=device)
+    if t.dtype != dtype or t.numel() != rows or not t.is_contiguous():
+        raise FewbitHipError(f'{what} must be a contiguous {dtype} tensor of {rows} elements')
+    return t
+
+
+def cross_entropy_forward(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -100, lse: Optional[torch.Tensor] = None,
+                          loss: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """``(lse, loss)`` of the rows of ``logits`` in ONE launch: ``lse = logsumexp(logits.float(), 1)`` and ``loss = F.cross_entropy(logits.float(),
+    target, reduction='none', ignore_index=ignore_index)`` as float32 tensors of ``rows`` elements, each row read once.  ``logits``: a 2-D fp32 / fp16 /
+    bf16 GPU tensor with unit stride along the classes and any row stride and alignment (a row-sliced view as it is); ``target``: int64 of ``rows``
+    elements on its device.  An ignored row has loss +0; a target outside ``[0, width)`` gives NaN (no device assertion); a row with a NaN or a
+    ``+inf``, or of ``-inf`` only, gives NaN.  ``lse``, ``loss``: buffers to write into.  Enqueued on torch's current stream; nothing is read back."""
+    rows, width, ld = _logits_rows(logits, 'logits')
+    if target.dtype != torch.int64 or target.numel() != rows or not target.is_contiguous():
+        raise FewbitHipError(f'target must be a contiguous int64 tensor of {rows} elements')
+    with _on(logits.device):
+        lse = _row_vector(lse, torch.float32, rows, logits.device, 'lse')
+        loss = _row_vector(loss, torch.float32, rows, logits.device, 'loss')
+        _same_device(logits, target, lse, loss)
+        _check(lib().fewbit_hipx_cross_entropy_forward(DTYPES[logits.dtype], logits.data_ptr(), rows, width, ld, target.data_ptr(), ignore_index, lse.data_ptr(),
+                                                       loss.data_ptr(), _stream(stream, logits.device)))
+    return lse, loss
+
+
+def cross_entropy_backward(logits: torch.Tensor, target: torch.Tensor, lse: torch.Tensor, grow: torch.Tensor, ignore_index: int = -100,
+                           out: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+    """``grow * (softmax(logits.float(), 1) - one_hot(target))`` rounded once to the dtype of ``logits``, in ONE launch that reads every element once
+    and writes it once.  ``lse``: what ``cross_entropy_forward`` gave for these logits; ``grow``: a float32 GPU tensor of ONE element (the same
+    gradient for every row: a sum, or a mean with ``1 / count`` multiplied in) or of ``rows`` elements -- a device tensor either way, nothing is read
+    back.  ``out``: a 2-D tensor of the shape and dtype of ``logits`` with unit stride along the classes and any row stride; ``out is logits`` (or the
+    same memory and strides) is the backward in place: the gradient replaces the logits, bit for bit.  An ignored row is +0, a row whose target is out
+    of range is NaN."""
+    rows, width, ld = _logits_rows(logits, 'logits')
+    if target.dtype != torch.int64 or target.numel() != rows or not target.is_contiguous():
+        raise FewbitHipError(f'target must be a contiguous int64 tensor of {rows} elements')
+    _row_vector(lse, torch.float32, rows, logits.device, 'lse')
+    if grow.dtype != torch.float32 or grow.numel() not in (1, rows) or not grow.is_contiguous():
+        raise FewbitHipError(f'grow must be a contiguous float32 tensor of 1 or {rows} elements')
+    with _on(logits.device):
+        if out is None:
+            out = torch.empty((rows, width), dtype=logits.dtype, device=logits.device)
+        elif out.dtype != logits.dtype or tuple(out.shape) != (rows, width):
+            raise FewbitHipError(f'out must be a {rows} x {width} tensor of {logits.dtype}')
+        ld_out = _logits_rows(out, 'out')[2]
+        _same_device(logits, target, lse, grow, out)
+        _check(lib().fewbit_hipx_cross_entropy_backward(DTYPES[logits.dtype], logits.data_ptr(), rows, width, ld, target.data_ptr(), ignore_index, lse.data_ptr(),
+                                                        grow.data_ptr(), 0 if grow.numel() == 1 else 1,
+                                                        out.data_ptr(), ld_out, _stream(stream, logits.device)))
+    return out

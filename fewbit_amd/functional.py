@@ -257,3 +257,4 @@ from .variance import GradientStorage, catch_gradients  # noqa: E402,F401
 from .dropout import dropout, dropout_add  # noqa: E402,F401
 from .glu import gated_mlp_quantized, glu_quantized  # noqa: E402,F401
 from .norm import dropout_add_layer_norm_quantized, dropout_add_rms_norm_quantized, layer_norm_quantized, rms_norm_quantized  # noqa: E402,F401
+from .xent import cross_entropy  # noqa: E402,F401

@@ -46,7 +46,9 @@ extern "C" {
  * So were the gate and the up of a seed, the product of a gated MLP (fewbit_hipx_glu_state_bytes, _glu_state_host, _glu_forward, _glu_backward):
  * inside revision 2, recognised by the presence of the symbols.
  * So was the backward of that product that also rebuilds the product from the state (fewbit_hipx_glu_backward_product, what the gated MLP as one
- * node needs): inside revision 2, recognised by the presence of the symbol. */
+ * node needs): inside revision 2, recognised by the presence of the symbol.
+ * So was the loss of a row, the cross entropy that keeps the logits as given and one float per row (fewbit_hipx_cross_entropy_host,
+ * _cross_entropy_forward, _cross_entropy_backward): inside revision 2, recognised by the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -529,6 +531,60 @@ int fewbit_hipx_glu_backward(int dtype, int act, const void *gy, const uint8_t *
                              size_t ld_dup, void *stream);
 int fewbit_hipx_glu_backward_product(int dtype, int act, const void *gy, const uint8_t *state, size_t rows, size_t width, int bits, void *d_gate, size_t ld_dgate,
                                      void *d_up, size_t ld_dup, void *product, size_t ld_product, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The loss of a row: the cross entropy of a row of logits against a class index, F.cross_entropy(x, t, reduction='none') with its gradient,
+ * that keeps for backward the logits AS GIVEN and ONE fp32 number per row (what fewbit.CrossEntropyLoss keeps) instead of the log-softmax of every
+ * element -- in fp32 where the logits are cast first, as the Hugging Face losses and torch.autocast do.  ONE launch forward, ONE backward.
+ *
+ * logits is a rows x width matrix of `dtype` (F32 / F16 / BF16) with unit stride along the width and a row stride of ld >= width elements;
+ * target holds rows int64 class indices.  Per row, with x the row widened exactly and t its target:
+ *     lse       = log sum_j exp(x_j)          evaluated as M + log sum_j exp(x_j - M), M = max_j x_j
+ *     loss      = lse - x_t
+ *     dlogits_j = grow * (exp(x_j - lse) - [j = t])       rounded ONCE to `dtype`
+ *   The host function evaluates this in float64 and is the definition; the kernels evaluate the same in fp32 (fewbit_amd/csrc/fewbit_xent.hip:
+ *   exp(a) as v_exp_f32 of a * log2(e), a running maximum and sum per lane rescaled once per block of eight elements, the lanes merged by a
+ *   fixed xor butterfly and the four waves in wave order; no floating-point atomics, the same arguments give the same bits).  For |x| <= 16
+ *   and V = width, against the host function:
+ *     |lse - lse64|   <= E = (V + 128) 2^-24 + 4 2^-24 |lse64|
+ *     |loss - loss64| <= E + 4 2^-24 (|lse64| + |x_t|)
+ *     |d - d64|       <= |grow| (p64 (E + 160 2^-24) + 2^-23) + r |d64|,  p64 = exp(x_j - lse64),  r = 0 (F32), 2^-11 and 2^-25 absolute
+ *                        (F16), 2^-8 (BF16)
+ *   Special rows:
+ *     t == ignore_index          loss = +0 and every dlogits_j = +0; lse is still written; backward reads nothing of the row
+ *     t outside [0, width)       (and not ignore_index) loss = NaN and every dlogits_j = NaN; nothing of the row is read through t, no
+ *                                device assertion fires
+ *     x_j = -inf                 has probability 0 and dlogits_j = +0 (also for grow < 0)
+ *     a NaN or a +inf in the row, or -inf everywhere: loss = NaN and every dlogits_j = NaN (torch's results); lse is NaN, or -inf for a row of
+ *                                -inf.  Other rows are untouched.
+ *
+ * fewbit_hipx_cross_entropy_host: HOST pointers, no device is touched.  logits_host rows x width fp32, contiguous (pass the values of a 16-bit
+ *   tensor widened); grow_host one double per row, or NULL: 1; lse_host, loss_host rows doubles; dlogits_host rows x width doubles, or NULL:
+ *   no gradient.  Refuses what the launches refuse of rows, width and null pointers.
+ * fewbit_hipx_cross_entropy_forward: ONE launch on `stream`; every row is read once, by one workgroup of 256 lanes; rows are taken by the
+ *   width of the grid, at most 2048 workgroups.  lse, loss: rows floats each.
+ * fewbit_hipx_cross_entropy_backward: ONE launch on `stream`, the same plan; every element is read once and written once.
+ *   lse          what the forward wrote for these logits
+ *   grow         the gradient arriving at the row's loss, a DEVICE pointer either way, so nothing is read back and both launches can be
+ *                recorded into a hipGraph: grow_stride = 1: one float per row; grow_stride = 0: ONE float for every row (the gradient of a sum,
+ *                or of a mean with 1 / count multiplied in)
+ *   dlogits      rows x width of `dtype`, row stride ld_out >= width.  dlogits == logits with ld_out == ld is the backward IN PLACE: the
+ *                gradient replaces the logits, bit for bit what the out-of-place call writes.  Any other overlap of the two is refused.
+ *                The gap of a row stride is neither read nor written.
+ * No alignment is asked of logits, dlogits, ld or ld_out beyond that of the element: a row is walked as [head | aligned 16-byte pieces | tail]
+ * wherever it starts (a 50265-wide bf16 row starts on a 2-byte boundary); nothing outside [row, row + width) is touched.  Backward stores by
+ * 16-byte pieces where the output row starts at the same offset from a 16-byte boundary as the input row, and element by element otherwise:
+ * the same bytes either way.
+ * Refused before anything is launched: an unknown dtype, a null pointer, grow_stride > 1, an overlap (FEWBIT_ERR_INVALID_ARGUMENT); rows outside
+ * 1 .. 2^31, width outside 1 .. 2^24, ld or ld_out below the width or beyond 2^31 (FEWBIT_ERR_UNSUPPORTED).
+ * Not done: a row split over several workgroups (few rows of a huge width), a wave per row for narrow rows, class weights, label smoothing
+ * and probability targets, the loss fused into the GEMM of the LM head. */
+int fewbit_hipx_cross_entropy_host(const float *logits_host, const int64_t *target_host, size_t rows, size_t width, int64_t ignore_index,
+                                   const double *grow_host, double *lse_host, double *loss_host, double *dlogits_host);
+int fewbit_hipx_cross_entropy_forward(int dtype, const void *logits, size_t rows, size_t width, size_t ld, const int64_t *target, int64_t ignore_index,
+                                      float *lse, float *loss, void *stream);
+int fewbit_hipx_cross_entropy_backward(int dtype, const void *logits, size_t rows, size_t width, size_t ld, const int64_t *target, int64_t ignore_index,
+                                       const float *lse, const float *grow, size_t grow_stride, void *dlogits, size_t ld_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -66,6 +66,8 @@ ROWS = [
     ('core_refusal_digest.txt', 'tools/core_refusal_digest.py: status and message of every refusal of the activation launches, describes, tune and codec entry points, single faults and pairs, plain and with FEWBIT_HIP_VALIDATE=1; recorded from the library before the fold (tests/test_core_refusals_host.py compares)', f'{E} 8.28'),
     ('core_fold_plan_digest.txt', 'tools/plan_digest.py --digest: lines and sha256 per entry point and tune setting of the 1 449 569 plans of the sweep on a 256-CU MI355X, the same from the parent and from the tree', f'{E} 8.28'),
     ('core_fold_speed.txt', 'the four activation entry points at 16384 x 768 and at n = 4096, bf16 and fp32, from the parent and from the tree with the folded host code, alternating five times', f'{E} 8.28'),
+    ('cross_entropy_bench.json', 'tools/cross_entropy_bench.py: fewbit.functional.cross_entropy forward + backward, plain and with inplace_backward, beside F.cross_entropy on the logits as given, on their fp32 copy and under autocast at 16384 x 32000 / 50265 / 128256, bf16 and fp32; bytes saved for backward; peak allocation; the forward and backward entry points alone against their byte floors', f'{E} 8.29'),
+    ('cross_entropy_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2888 device functions before / after fewbit_xent.hip was added (6 new)', f'{E} 8.29'),
     ('unit_fold_speed*.txt','the launch-bound entry-point arms of quant_linear_bench, dropout_bench, glu_bench and layer_norm_bench from the parent and from the tree with fewbit_unit.h, alternating five times', f'{E} 8.27'),
     ('signed_transform_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1915 device functions before / after the signed pass A was added (228 new)', f'{E} 8.15'),
     ('moments_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1890 device functions before / after fewbit_moments.hip was added (13 new)', f'{E} 8.9'),
