@@ -21,7 +21,8 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'quant_unpack', 'quant_pack_host', 'quant_unpack_host', 'NORM_MAX_WIDTH', 'norm_plan', 'norm_state_bytes', 'norm_workspace_bytes', 'norm_state_host',
            'norm_state_unpack_host', 'layer_norm_forward', 'layer_norm_backward', 'rms_norm_forward', 'rms_norm_backward', 'add_layer_norm_forward', 'add_layer_norm_backward',
            'add_rms_norm_forward', 'add_rms_norm_backward', 'GLU_ACTIVATIONS', 'glu_state_bytes', 'glu_state_host', 'glu_forward', 'glu_backward',
-           'glu_backward_product', 'CROSS_ENTROPY_MAX_GROUPS', 'cross_entropy_host', 'cross_entropy_forward', 'cross_entropy_backward']
+           'glu_backward_product', 'CROSS_ENTROPY_MAX_GROUPS', 'cross_entropy_host', 'cross_entropy_forward', 'cross_entropy_backward',
+           'CROSS_ENTROPY_STEP_STAGED_BYTES', 'cross_entropy_step']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -92,6 +93,7 @@ _SIGNATURES = {
     'fewbit_hipx_cross_entropy_host': (_i32, [_vp, _vp, _sz, _sz, _i64, _vp, _vp, _vp, _vp]),
     'fewbit_hipx_cross_entropy_forward': (_i32, [_i32, _vp, _sz, _sz, _sz, _vp, _i64, _vp, _vp, _vp]),
     'fewbit_hipx_cross_entropy_backward': (_i32, [_i32, _vp, _sz, _sz, _sz, _vp, _i64, _vp, _vp, _sz, _vp, _sz, _vp]),
+    'fewbit_hipx_cross_entropy_step': (_i32, [_i32, _vp, _sz, _sz, _sz, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -908,6 +910,9 @@ def glu_backward_product(gy: Optional[torch.Tensor], state: torch.Tensor, activa
 
 # ---- the cross entropy of a row that keeps the logits as given and one float per row (fewbit_amd/csrc/fewbit_xent.hip) -----------------------------------
 CROSS_ENTROPY_MAX_GROUPS = 2048                 # workgroups of either launch (kMaxGroups in fewbit_xent.hip), one row each at a time; beyond it they walk on
+# the bytes of a row that the step kernel keeps in LDS between its two passes, per tier (kStagedBytes in fewbit_xent.hip): a workgroup of 256 / 512 /
+# 1024 lanes on a quarter, a half or all of a CU's LDS; a longer row takes the forward and the backward in place, two launches
+CROSS_ENTROPY_STEP_STAGED_BYTES = (40832, 81792, 163712)
 
 
 def cross_entropy_host(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -100, grow: Optional[torch.Tensor] = None, want_grad: bool = True):
@@ -995,3 +1000,25 @@ def cross_entropy_backward(logits: torch.Tensor, target: torch.Tensor, lse: torc
                                                         grow.data_ptr(), 0 if grow.numel() == 1 else 1,
                                                         out.data_ptr(), ld_out, _stream(stream, logits.device)))
     return out
+
+
+def cross_entropy_step(logits: torch.Tensor, target: torch.Tensor, grow: torch.Tensor, ignore_index: int = -100, lse: Optional[torch.Tensor] = None,
+                       loss: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """``cross_entropy_forward`` and ``cross_entropy_backward(out=logits)`` as ONE launch -> ``(lse, loss)``, and ``logits`` IS OVERWRITTEN by its own
+    gradient ``grow * (softmax(logits.float(), 1) - one_hot(target))``, rounded once to its dtype: what a chunked LM head runs between its GEMMs.  A row of
+    at most ``CROSS_ENTROPY_STEP_STAGED_BYTES[-1]`` bytes is read from global memory once (it waits in LDS between the reduction and the gradient); a
+    longer one takes the pair's two launches inside the entry point.  ``grow``: a float32 GPU tensor of ONE element or of ``rows`` elements, known before the loss is (1
+    for a sum, ``1 / count`` for a mean).  ``lse``, ``loss``: buffers to write into.  The other arguments, the special rows and the bounds are those of
+    the pair.  Enqueued on torch's current stream; nothing is read back."""
+    rows, width, ld = _logits_rows(logits, 'logits')
+    if target.dtype != torch.int64 or target.numel() != rows or not target.is_contiguous():
+        raise FewbitHipError(f'target must be a contiguous int64 tensor of {rows} elements')
+    if grow.dtype != torch.float32 or grow.numel() not in (1, rows) or not grow.is_contiguous():
+        raise FewbitHipError(f'grow must be a contiguous float32 tensor of 1 or {rows} elements')
+    with _on(logits.device):
+        lse = _row_vector(lse, torch.float32, rows, logits.device, 'lse')
+        loss = _row_vector(loss, torch.float32, rows, logits.device, 'loss')
+        _same_device(logits, target, grow, lse, loss)
+        _check(lib().fewbit_hipx_cross_entropy_step(DTYPES[logits.dtype], logits.data_ptr(), rows, width, ld, target.data_ptr(), ignore_index, grow.data_ptr(),
+                                                    0 if grow.numel() == 1 else 1, lse.data_ptr(), loss.data_ptr(), _stream(stream, logits.device)))
+    return lse, loss

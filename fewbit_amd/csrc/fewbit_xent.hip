@@ -35,6 +35,12 @@
 #include "fewbit_hipx.h"
 #include "fewbit_unit.h"
 
+// Two translation units (-DFEWBIT_XENT_TU=0: forward_kernel, backward_kernel and their entry points, the host function; 1: step_kernel and its entry
+// point), so that the step's instantiations leave the code of the pair as it was: in one unit backward_kernel<BF16> came out an instruction longer.
+#ifndef FEWBIT_XENT_TU
+#error "fewbit_xent.hip is built as two units: -DFEWBIT_XENT_TU=0 and -DFEWBIT_XENT_TU=1"
+#endif
+
 namespace fewbit_hip {
 namespace xent {
 
@@ -123,6 +129,13 @@ template <int N> __device__ __forceinline__ void fold(const float (&v)[N], float
 // s of a run whose maximum is m, at the maximum `to` >= m of several runs
 __device__ __forceinline__ float rescaled(float m, float s, float to) { return m > -INFINITY ? s * exp_of(m - to) : s; }
 
+// d = g * (exp(x - lse) - [e == hot]) + 0: the last term turns a -0 (g < 0 times a probability of 0) into +0
+template <int DT> __device__ __forceinline__ typename Elem<DT>::type gradient(float x, float l, float g, bool hot) {
+    const float prob = exp_of(x - l);
+    return narrow<DT>(g * (hot ? prob - 1.0f : prob) + 0.0f);
+}
+
+#if FEWBIT_XENT_TU == 0
 template <int DT>
 __global__ __launch_bounds__(kThreads) void forward_kernel(const void *__restrict__ logits_, size_t rows, size_t width, size_t ld, const int64_t *__restrict__ target,
                                                             int64_t ignore_index, float *__restrict__ lse, float *__restrict__ loss) {
@@ -202,12 +215,6 @@ __global__ __launch_bounds__(kThreads) void forward_kernel(const void *__restric
 }
 
 // ---- backward ---------------------------------------------------------------------------------------------------------------------------------
-// d = g * (exp(x - lse) - [e == hot]) + 0: the last term turns a -0 (g < 0 times a probability of 0) into +0
-template <int DT> __device__ __forceinline__ typename Elem<DT>::type gradient(float x, float l, float g, bool hot) {
-    const float prob = exp_of(x - l);
-    return narrow<DT>(g * (hot ? prob - 1.0f : prob) + 0.0f);
-}
-
 template <int DT>
 __global__ __launch_bounds__(kThreads) void backward_kernel(const void *logits_, size_t rows, size_t width, size_t ld, const int64_t *__restrict__ target,
                                                              int64_t ignore_index, const float *__restrict__ lse, const float *__restrict__ grow, size_t grow_stride,
@@ -257,6 +264,144 @@ __global__ __launch_bounds__(kThreads) void backward_kernel(const void *logits_,
     }
 }
 
+#else  // FEWBIT_XENT_TU == 1
+// ---- the step: loss and gradient of a row in one launch, the row read from HBM once -------------------------------------------------------------
+// What the chunked LM head needs between its GEMMs (fewbit_amd/xent.py, linear_cross_entropy): forward_kernel's (lse, loss) and backward_kernel's
+// gradient IN PLACE, without the second read of the row.  Pass 1 folds the row into the lane's (m, s) as forward_kernel does and keeps every raw
+// 16-byte piece in LDS (the head and the tail element of a lane stay in two registers); after the merge every lane has lse and pass 2 forms the
+// gradient from the kept pieces and stores it over the row.  Lane l keeps piece c at uint4 slot c of the LDS array: a wave's ds_write_b128 /
+// ds_read_b128 cover 1024 consecutive bytes, which is the conflict-free pattern, and a lane reads back only what it wrote itself, so the merge's
+// barrier is the only one between the passes.  x_t is read by lane 0 before anything of the row is written.
+//
+// Tiers.  A CU has kLdsBytes of LDS; a workgroup takes kLdsBytes / 4, / 2 or / 1 of it (kStepWaveBytes of each for the waves' (M, s)), so four, two
+// or one workgroups share a CU, and is 256, 512 or 1024 lanes wide: sixteen waves stream on a CU in every tier.  A row takes the smallest tier
+// that holds width * sizeof(element) bytes.  A row beyond the largest takes forward_kernel and backward_kernel in place, two launches: a variant of
+// this kernel that read such a row a second time from global memory (256 workgroups of 1024 lanes) was slower than the pair at two widths of three
+// (EXPERIMENTS.md 8.30) and is not kept.
+// Lane l of T lanes owns the pieces l, l + T, ..; the butterfly and the waves in wave order are forward_kernel's.
+constexpr size_t kLdsBytes = 163840, kStepWaveBytes = 128;
+constexpr size_t kStagedBytes[3] = {kLdsBytes / 4 - kStepWaveBytes, kLdsBytes / 2 - kStepWaveBytes, kLdsBytes - kStepWaveBytes};   // 40832, 81792, 163712
+constexpr int kStepThreads[3] = {256, 512, 1024};
+constexpr int kTiers = 3;
+
+template <int DT, int TIER>
+__global__ __launch_bounds__(kStepThreads[TIER]) void step_kernel(void *logits_, size_t rows, size_t width, size_t ld, const int64_t *__restrict__ target,
+                                                                   int64_t ignore_index, const float *__restrict__ grow, size_t grow_stride,
+                                                                   float *__restrict__ lse, float *__restrict__ loss) {
+    using T = typename Elem<DT>::type;
+    constexpr int E = Elem<DT>::E, THREADS = kStepThreads[TIER], WAVES = THREADS / 64;
+    constexpr size_t SLOTS = kStagedBytes[TIER] / 16;
+    static_assert(WAVES * 2 * sizeof(float) <= kStepWaveBytes, "the waves' (M, s) fit what the tiers leave free");
+    __shared__ uint4 kept[SLOTS];
+    __shared__ float of_wave[WAVES][2];
+    const int lane = threadIdx.x % 64, wave = threadIdx.x / 64;
+    for (size_t r = blockIdx.x; r < rows; r += gridDim.x) {
+        T *p = static_cast<T *>(logits_) + r * ld;
+        const int64_t t = target[r];
+        const bool ignored = t == ignore_index, valid = t >= 0 && static_cast<uint64_t>(t) < width;
+        const float xt = threadIdx.x == 0 && valid ? widen<DT>(p[t]) : 0.0f;         // (before the row is written over)
+        const Span<T> sp = span_of(p, width);
+        const bool has_head = threadIdx.x < sp.head, has_tail = sp.tail + threadIdx.x < width;
+        T head_raw = 0, tail_raw = 0;
+        float m = -INFINITY, s = 0.0f;
+        if (has_head) {
+            head_raw = p[threadIdx.x];
+            const float v[1] = {widen<DT>(head_raw)};
+            fold<1>(v, m, s);
+        }
+        uint4 *q = reinterpret_cast<uint4 *>(p + sp.head);
+        size_t c = threadIdx.x;
+        for (; c + THREADS < sp.pieces; c += 2 * THREADS) {                          // two pieces in flight
+            const uint4 a = q[c], b = q[c + THREADS];
+            kept[c] = a;
+            kept[c + THREADS] = b;
+            if constexpr (E == 4) {
+                float v[8], u[4];
+                unpack<DT>(a, u);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = u[e];
+                unpack<DT>(b, u);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[4 + e] = u[e];
+                fold<8>(v, m, s);
+            } else {
+                float v[8];
+                unpack<DT>(a, v);
+                fold<8>(v, m, s);
+                unpack<DT>(b, v);
+                fold<8>(v, m, s);
+            }
+        }
+        if (c < sp.pieces) {
+            const uint4 a = q[c];
+            kept[c] = a;
+            float v[E];
+            unpack<DT>(a, v);
+            fold<E>(v, m, s);
+        }
+        if (has_tail) {
+            tail_raw = p[sp.tail + threadIdx.x];
+            const float v[1] = {widen<DT>(tail_raw)};
+            fold<1>(v, m, s);
+        }
+        // the lanes, then the waves in wave order (forward_kernel's merge); every lane merges the waves, so every lane has lse
+        float top = m;
+#pragma unroll
+        for (int d = 32; d >= 1; d /= 2) top = fmaxf(top, __shfl_xor(top, d, 64));
+        float sum = rescaled(m, s, top);
+#pragma unroll
+        for (int d = 32; d >= 1; d /= 2) sum += __shfl_xor(sum, d, 64);
+        if (lane == 0) {
+            of_wave[wave][0] = top;
+            of_wave[wave][1] = sum;
+        }
+        __syncthreads();
+        float all = of_wave[0][0];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) all = fmaxf(all, of_wave[w][0]);
+        float total = rescaled(of_wave[0][0], of_wave[0][1], all);
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) total += rescaled(of_wave[w][0], of_wave[w][1], all);
+        const float l = all + logf(total);                                           // (all -inf: -inf + log 0 = -inf)
+        __syncthreads();                                                             // (of_wave is written again for the next row)
+        if (threadIdx.x == 0) {
+            lse[r] = l;
+            loss[r] = ignored ? 0.0f : valid ? l - xt : __builtin_bit_cast(float, kNaN);
+        }
+        // pass 2: the gradient over the row, by the lanes that read it
+        if (ignored || !valid) {
+            const T fill = narrow<DT>(__builtin_bit_cast(float, ignored ? 0u : kNaN));   // +0 for an ignored row, NaN for a target out of range
+            T o[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) o[e] = fill;
+            const uint4 w = pack<DT>(o);
+            if (has_head) p[threadIdx.x] = fill;
+            for (c = threadIdx.x; c < sp.pieces; c += THREADS) q[c] = w;
+            if (has_tail) p[sp.tail + threadIdx.x] = fill;
+            continue;
+        }
+        const float g = grow[r * grow_stride];
+        const uint32_t hot = static_cast<uint32_t>(t);
+        if (has_head) p[threadIdx.x] = gradient<DT>(widen<DT>(head_raw), l, g, threadIdx.x == hot);
+#pragma unroll 2
+        for (c = threadIdx.x; c < sp.pieces; c += THREADS) {
+            float v[E];
+            unpack<DT>(kept[c], v);
+            const uint32_t at = hot - static_cast<uint32_t>(sp.head + c * E);        // (the hot element's place in this piece, if below E)
+            T o[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) o[e] = gradient<DT>(v[e], l, g, at == static_cast<uint32_t>(e));
+            q[c] = pack<DT>(o);
+        }
+        if (has_tail) p[sp.tail + threadIdx.x] = gradient<DT>(widen<DT>(tail_raw), l, g, static_cast<uint32_t>(sp.tail + threadIdx.x) == hot);
+    }
+}
+
+// the smallest tier that holds a row of `bytes`, or kTiers
+inline int tier_of(size_t bytes) { return bytes <= kStagedBytes[0] ? 0 : bytes <= kStagedBytes[1] ? 1 : bytes <= kStagedBytes[2] ? 2 : kTiers; }
+
+#endif  // FEWBIT_XENT_TU
+
 inline unsigned grid_of(size_t rows) { return static_cast<unsigned>(rows < kMaxGroups ? rows : kMaxGroups); }
 
 // what both launches refuse alike, in this order
@@ -281,6 +426,7 @@ using namespace fewbit_hip::xent;
 
 extern "C" {
 
+#if FEWBIT_XENT_TU == 0
 int fewbit_hipx_cross_entropy_host(const float *logits_host, const int64_t *target_host, size_t rows, size_t width, int64_t ignore_index, const double *grow_host,
                                    double *lse_host, double *loss_host, double *dlogits_host) {
     const char *name = "cross_entropy_host";
@@ -346,5 +492,30 @@ int fewbit_hipx_cross_entropy_backward(int dtype, const void *logits, size_t row
     });
     return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
 }
+
+#else  // FEWBIT_XENT_TU == 1
+int fewbit_hipx_cross_entropy_step(int dtype, void *logits, size_t rows, size_t width, size_t ld, const int64_t *target, int64_t ignore_index, const float *grow,
+                                   size_t grow_stride, float *lse, float *loss, void *stream) {
+    const char *name = "cross_entropy_step";
+    if (const int rc = check_rows(name, dtype, rows, width, ld)) return rc;
+    if (grow_stride > 1) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: grow_stride = %zu is neither 0 (one scalar) nor 1 (one per row)", name, grow_stride);
+    if (logits == nullptr || target == nullptr || grow == nullptr || lse == nullptr || loss == nullptr) return refuse_null(name);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int tier = tier_of(width * size_of(dtype));
+    if (tier == kTiers) {
+        if (const int rc = fewbit_hipx_cross_entropy_forward(dtype, logits, rows, width, ld, target, ignore_index, lse, loss, stream)) return rc;
+        return fewbit_hipx_cross_entropy_backward(dtype, logits, rows, width, ld, target, ignore_index, lse, grow, grow_stride, logits, ld, stream);
+    }
+    const dim3 grid(grid_of(rows)), block(kStepThreads[tier]);
+    pick_dtype(dtype, [&](auto dt) {
+        unit::pick<0, 1, 2>(tier, [&](auto tr) {
+            hipLaunchKernelGGL((step_kernel<decltype(dt)::value, decltype(tr)::value>), grid, block, 0, s, logits, rows, width, ld, target, ignore_index, grow,
+                               grow_stride, lse, loss);
+        });
+    });
+    return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
+}
+
+#endif  // FEWBIT_XENT_TU
 
 }  // extern "C"

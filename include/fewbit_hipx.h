@@ -48,7 +48,9 @@ extern "C" {
  * So was the backward of that product that also rebuilds the product from the state (fewbit_hipx_glu_backward_product, what the gated MLP as one
  * node needs): inside revision 2, recognised by the presence of the symbol.
  * So was the loss of a row, the cross entropy that keeps the logits as given and one float per row (fewbit_hipx_cross_entropy_host,
- * _cross_entropy_forward, _cross_entropy_backward): inside revision 2, recognised by the presence of the symbols. */
+ * _cross_entropy_forward, _cross_entropy_backward): inside revision 2, recognised by the presence of the symbols.
+ * So was the step of a chunked LM head, the loss and the gradient of a row in one launch (fewbit_hipx_cross_entropy_step): inside revision 2,
+ * recognised by the presence of the symbol. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -578,13 +580,27 @@ int fewbit_hipx_glu_backward_product(int dtype, int act, const void *gy, const u
  * Refused before anything is launched: an unknown dtype, a null pointer, grow_stride > 1, an overlap (FEWBIT_ERR_INVALID_ARGUMENT); rows outside
  * 1 .. 2^31, width outside 1 .. 2^24, ld or ld_out below the width or beyond 2^31 (FEWBIT_ERR_UNSUPPORTED).
  * Not done: a row split over several workgroups (few rows of a huge width), a wave per row for narrow rows, class weights, label smoothing
- * and probability targets, the loss fused into the GEMM of the LM head. */
+ * and probability targets, the loss fused into the GEMM of the LM head.
+ *
+ * fewbit_hipx_cross_entropy_step: forward and backward IN PLACE as ONE launch on `stream`, what a chunked LM head runs between its GEMMs
+ *   (fewbit.functional.linear_cross_entropy): lse and loss are what _cross_entropy_forward defines (lse for every row, ignored rows included), and
+ *   logits is overwritten by grow * (exp(x - lse) - [j = t]) + 0 rounded once to `dtype`, what _cross_entropy_backward with dlogits == logits
+ *   defines; the bounds and the special rows above hold as they stand.  grow, grow_stride: as for the backward (device memory; 0: one scalar,
+ *   1: one per row) -- known BEFORE the loss is, which is what 'sum' (1) and 'mean' (1 / count) allow.
+ *   A row of at most 163712 bytes (40928 fp32 or 81856 16-bit classes) is read from global memory ONCE: its 16-byte pieces wait in LDS between
+ *   the reduction and the gradient.  A workgroup takes a quarter, a half or all of a CU's 160 KB of LDS by the row's bytes (at most 40832 /
+ *   81792 / 163712) and is 256 / 512 / 1024 lanes wide, so sixteen waves stream on a CU either way.  A longer row (128256 bf16 classes) takes
+ *   the forward and the backward in place, TWO launches and the same bits as calling them: re-reading such a row inside one launch was slower.
+ *   Lane l of T owns the pieces l, l + T, ..; the merge is the forward's; no floating-point atomics, the same arguments give the same bits.
+ *   Refused like the forward, then grow_stride > 1, then null pointers. */
 int fewbit_hipx_cross_entropy_host(const float *logits_host, const int64_t *target_host, size_t rows, size_t width, int64_t ignore_index,
                                    const double *grow_host, double *lse_host, double *loss_host, double *dlogits_host);
 int fewbit_hipx_cross_entropy_forward(int dtype, const void *logits, size_t rows, size_t width, size_t ld, const int64_t *target, int64_t ignore_index,
                                       float *lse, float *loss, void *stream);
 int fewbit_hipx_cross_entropy_backward(int dtype, const void *logits, size_t rows, size_t width, size_t ld, const int64_t *target, int64_t ignore_index,
                                        const float *lse, const float *grow, size_t grow_stride, void *dlogits, size_t ld_out, void *stream);
+int fewbit_hipx_cross_entropy_step(int dtype, void *logits, size_t rows, size_t width, size_t ld, const int64_t *target, int64_t ignore_index,
+                                   const float *grow, size_t grow_stride, float *lse, float *loss, void *stream);
 
 #ifdef __cplusplus
 }
