@@ -3,7 +3,7 @@ of ``libfewbit_hip.so`` was frozen at version 5 (``cabi.SYMBOLS`` stays that lis
 torch's current stream on the tensors' device, no fallback -- a missing library or an unsupported shape raises.  What it binds: the sampled
 Fourier transform, the zero-extended and sign-flipped sampled transforms, the column sampling of LinearCRS, the moments of the variance
 estimator, the dropout of a seed, the packed form of a seed, the layer norm and the RMS norm that keep the normalized rows of a seed, and the
-same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed, with the backward that also rebuilds that product from the state, and the cross entropy of a row that keeps the logits as given and one float per row.
+same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed, with the backward that also rebuilds that product from the state, and the cross entropy of a row that keeps the logits as given and one float per row, and the weight gradient of a layer straight from the packed form of its input.
 """
 import ctypes
 import os
@@ -22,7 +22,8 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'norm_state_unpack_host', 'layer_norm_forward', 'layer_norm_backward', 'rms_norm_forward', 'rms_norm_backward', 'add_layer_norm_forward', 'add_layer_norm_backward',
            'add_rms_norm_forward', 'add_rms_norm_backward', 'GLU_ACTIVATIONS', 'glu_state_bytes', 'glu_state_host', 'glu_forward', 'glu_backward',
            'glu_backward_product', 'CROSS_ENTROPY_MAX_GROUPS', 'cross_entropy_host', 'cross_entropy_forward', 'cross_entropy_backward',
-           'CROSS_ENTROPY_STEP_STAGED_BYTES', 'cross_entropy_step']
+           'CROSS_ENTROPY_STEP_STAGED_BYTES', 'cross_entropy_step', 'QUANT_WGRAD_TILE', 'quant_wgrad_serves', 'quant_wgrad_slices', 'quant_wgrad_workspace',
+           'quant_wgrad']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -94,6 +95,9 @@ _SIGNATURES = {
     'fewbit_hipx_cross_entropy_forward': (_i32, [_i32, _vp, _sz, _sz, _sz, _vp, _i64, _vp, _vp, _vp]),
     'fewbit_hipx_cross_entropy_backward': (_i32, [_i32, _vp, _sz, _sz, _sz, _vp, _i64, _vp, _vp, _sz, _vp, _sz, _vp]),
     'fewbit_hipx_cross_entropy_step': (_i32, [_i32, _vp, _sz, _sz, _sz, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
+    # the weight gradient from the packed form (the decode fused into the product): inside revision 2 as well, recognised by its symbols
+    'fewbit_hipx_quant_wgrad_workspace': (_sz, [_i32, _sz, _sz, _sz, _i32]),
+    'fewbit_hipx_quant_wgrad': (_i32, [_i32, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _i32, _i32, _vp, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -1022,3 +1026,74 @@ def cross_entropy_step(logits: torch.Tensor, target: torch.Tensor, grow: torch.T
         _check(lib().fewbit_hipx_cross_entropy_step(DTYPES[logits.dtype], logits.data_ptr(), rows, width, ld, target.data_ptr(), ignore_index, grow.data_ptr(),
                                                     0 if grow.numel() == 1 else 1, lse.data_ptr(), loss.data_ptr(), _stream(stream, logits.device)))
     return lse, loss
+
+
+# ---- the weight gradient from the packed form (fewbit_amd/csrc/fewbit_qgemm.hip): G^T X^ with the decode fused into the MFMA kernel ------------------
+QUANT_WGRAD_TILE = (256, 128, 64)               # (BM out_features, BN in_features, BK rows) of a workgroup's tile and of a stage of its K loop
+QUANT_WGRAD_TARGET = 256                        # workgroups the plan tries to reach by slicing the rows (kTargetGroups in fewbit_qgemm.hip)
+QUANT_WGRAD_MAX_WIDTH = 1 << 23
+
+
+def quant_wgrad_serves(dtype: torch.dtype, rows: int, in_features: int, out_features: int, bits: int) -> bool:
+    """Whether ``quant_wgrad`` has a kernel for a ``rows x out_features`` gradient of ``dtype`` against ``rows x in_features`` kept elements at
+    ``bits`` bits: bf16 / fp16, bits 2 / 4 / 8, ``in_features`` a multiple of 64 (a group is then 64 features of one row), ``out_features`` of 8.
+    The host predicate the layers ask (``serves`` in fewbit_qgemm.hip); no GPU needed."""
+    return (dtype in (torch.float16, torch.bfloat16) and bits in QUANT_BITS and rows >= 1 and 1 <= in_features <= QUANT_WGRAD_MAX_WIDTH
+            and in_features % QUANT_GROUP == 0 and 1 <= out_features <= QUANT_WGRAD_MAX_WIDTH and out_features % 8 == 0
+            and rows * in_features <= 2**36 and out_features * in_features <= 2**36)
+
+
+def quant_wgrad_slices(rows: int, in_features: int, out_features: int) -> int:
+    """K slices of the plan at served extents (``make_plan`` in fewbit_qgemm.hip, the same arithmetic): as many as bring the workgroups to at most
+    ``QUANT_WGRAD_TARGET``, never more than keep the workspace within ``rows * in_features * 2`` bytes, none of them empty"""
+    bm, bn, bk = QUANT_WGRAD_TILE
+    tiles = -(-in_features // bn) * -(-out_features // bm)
+    stages = -(-rows // bk)
+    want = min(QUANT_WGRAD_TARGET // tiles, rows // (2 * out_features), stages, 65535)
+    if want < 2:
+        return 1
+    per_slice = -(-stages // want)
+    return -(-stages // per_slice)
+
+
+def quant_wgrad_workspace(dtype: torch.dtype, rows: int, in_features: int, out_features: int, bits: int) -> int:
+    """Bytes of scratch ``quant_wgrad`` needs (the library's own answer): the fp32 partial sums of the K slices, 0 with one slice and for a call
+    the kernel does not serve.  Never more than ``rows * in_features`` elements of ``dtype``."""
+    if dtype not in DTYPES or min(rows, in_features, out_features) < 0:
+        return 0
+    return lib().fewbit_hipx_quant_wgrad_workspace(DTYPES[dtype], rows, in_features, out_features, bits)
+
+
+def quant_wgrad(grad: torch.Tensor, packed: torch.Tensor, in_features: int, bits: int, out_dtype: Optional[torch.dtype] = None,
+                out: Optional[torch.Tensor] = None, stream: Optional[int] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``grad^T X^`` straight from the codes: ``grad`` a ``rows x out_features`` bf16 / fp16 GPU tensor (unit stride along its width, row stride a
+    multiple of 8, 16-byte aligned), ``packed`` the ``quant_pack`` buffer of a ``rows x in_features`` tensor at ``bits`` bits -> ``out_features x
+    in_features`` in ``out_dtype`` (float32, or the dtype of ``grad`` rounded once from the fp32 sums; default: the dtype of ``grad``).  X^ is what
+    ``quant_unpack`` into the dtype of ``grad`` gives -- at bf16 / 8 bits the two bf16 terms of the fp32 decode (``kept.decode_in_two_terms``) -- but
+    exists in LDS only.  The same arguments give the same bits; nothing is read back, the call can be captured.  A call ``quant_wgrad_serves``
+    denies raises.  ``out``, ``workspace`` (uint8, at least ``quant_wgrad_workspace`` bytes): buffers to use."""
+    if grad.device.type != 'cuda' or packed.device.type != 'cuda':
+        raise FewbitHipError(f'grad and packed must live on the GPU (got {grad.device}, {packed.device})')
+    if grad.dtype not in DTYPES:
+        raise FewbitHipError(f'unsupported dtype {grad.dtype}')
+    rows, out_features, ld = _logits_rows(grad, 'grad')
+    out_dtype = grad.dtype if out_dtype is None else out_dtype
+    if out_dtype not in DTYPES:
+        raise FewbitHipError(f'unsupported dtype {out_dtype}')
+    if packed.dtype != torch.uint8 or not packed.is_contiguous():
+        raise FewbitHipError('packed must be a contiguous uint8 tensor')
+    with _on(grad.device):
+        if out is None:
+            out = torch.empty((out_features, in_features), dtype=out_dtype, device=grad.device)
+        elif out.dtype != out_dtype or tuple(out.shape) != (out_features, in_features) or not out.is_contiguous():
+            raise FewbitHipError(f'out must be a contiguous {out_features} x {in_features} tensor of {out_dtype}')
+        need = quant_wgrad_workspace(grad.dtype, rows, in_features, out_features, bits)
+        if workspace is None and need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=grad.device)
+        elif workspace is not None and (workspace.dtype != torch.uint8 or not workspace.is_contiguous()):
+            raise FewbitHipError('workspace must be a contiguous uint8 tensor')
+        _same_device(grad, packed, out, *(() if workspace is None else (workspace, )))
+        _check(lib().fewbit_hipx_quant_wgrad(DTYPES[grad.dtype], grad.data_ptr(), ld, packed.data_ptr(), packed.numel(), rows, in_features, out_features, bits,
+                                             DTYPES[out_dtype], out.data_ptr(), _ptr(workspace), 0 if workspace is None else workspace.numel(),
+                                             _stream(stream, grad.device)))
+    return out

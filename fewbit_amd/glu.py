@@ -253,7 +253,9 @@ class _GatedMLPQuantized(torch.autograd.Function):
             grads[6] = G.sum(dim=0)
         if needs[1] or needs[2]:
             # x^ decoded ONCE for both products, in the gradient's dtype (a bf16 gradient at 8 bits: in fp32, two terms, as in QuantizedLinear)
-            by_gate, by_up = kept.products((d_gate if needs[1] else None, d_up if needs[2] else None), x_kept, ctx.flat_shape, ctx.bits)
+            # (linear.use_fused_weight_gradient(): both straight from the codes on the MFMA kernel, the column halves of [d_gate | d_up] where they lie)
+            by_gate, by_up = kept.products((d_gate if needs[1] else None, d_up if needs[2] else None), x_kept, ctx.flat_shape, ctx.bits,
+                                           linear.use_fused_weight_gradient())
             if needs[1]:
                 grads[1] = by_gate.to(gate_weight.dtype)
             if needs[2]:

@@ -114,10 +114,23 @@ def _product_of_two_terms(g: torch.Tensor, terms: torch.Tensor) -> torch.Tensor:
     return torch.cat((g, g)).T @ terms
 
 
-def products(gradients: Sequence[Optional[torch.Tensor]], saved: Sequence[torch.Tensor], shape, bits: int) -> list:
+def _kernel_multiplies(g: torch.Tensor, saved: Sequence[torch.Tensor], shape, bits: int) -> bool:
+    """Whether ``cabi_x.quant_wgrad`` takes ``g`` and what ``saved`` keeps: a kernel buffer, extents and a dtype the kernel serves, and a gradient it
+    can address (unit stride along its width, rows a multiple of 8 elements apart, 16-byte aligned: a column half of one buffer included)"""
+    return (len(saved) == 1 and g.is_cuda and g.dim() == 2 and g.shape[0] == shape[0]
+            and cabi_x.quant_wgrad_serves(g.dtype, shape[0], shape[1], g.shape[1], bits)
+            and g.stride(1) == 1 and (g.shape[0] == 1 or (g.stride(0) >= g.shape[1] and g.stride(0) % 8 == 0)) and g.data_ptr() % 16 == 0)
+
+
+def products(gradients: Sequence[Optional[torch.Tensor]], saved: Sequence[torch.Tensor], shape, bits: int, fused: bool = False) -> list:
     """``g^T X^`` for every ``g`` of ``gradients`` (2-D, one dtype; None stays None) with the X^ that ``saved`` keeps (``keep``): X^ is decoded ONCE,
     in the gradients' dtype -- under autocast not the input's -- and multiplied in one GEMM each; a bf16 gradient at 8 bits meets an fp32 decode
-    split ONCE into two bf16 terms (``decode_in_two_terms``: about twice the time of the other widths).  The caller rounds to the weight's dtype."""
+    split ONCE into two bf16 terms (``decode_in_two_terms``: about twice the time of the other widths).  The caller rounds to the weight's dtype.
+    ``fused`` (``linear.use_fused_weight_gradient``): where ``saved`` is a kernel buffer and ``cabi_x.quant_wgrad`` serves the call, ONE call of it
+    per gradient instead -- the same operand values, in two terms where the route above takes two, multiplied straight from the codes: nothing is
+    decoded into memory, the result is the fp32 sums.  Any other call takes the route above and gives its bits."""
+    if fused and all(g is None or _kernel_multiplies(g, saved, shape, bits) for g in gradients):
+        return [None if g is None else cabi_x.quant_wgrad(g, saved[0], shape[1], bits, torch.float32) for g in gradients]
     dtype = next(g.dtype for g in gradients if g is not None)
     if decode_in_two_terms(bits, dtype):
         terms = _split_in_two_terms(kept_as(saved, shape, bits, torch.float32), dtype)

@@ -93,8 +93,11 @@ input at 4 bits, 0.1875 x at 2, 0.5625 x at 8), the weight, the seed and the sha
 captured into a hipGraph after one eager call (the seed is then a device word: every replay rounds afresh).  A group that holds a NaN or an
 infinity decodes to NaN as a whole; other groups are untouched.  Host tensors, float64 and ``use_native_sketch(False)`` take a PyTorch
 formulation of the same scheme (the same groups, the same unbiased rounding, ``U`` from the call's generator, one code per byte; not bit
-for bit the kernel's).  Autocast, checkpointing, ``no_grad`` and a frozen weight behave as for the layers above.  Out of scope: fusing the
-decode into the GEMM, 3-bit codes, per-row groups.
+for bit the kernel's).  Autocast, checkpointing, ``no_grad`` and a frozen weight behave as for the layers above.  With
+``use_fused_weight_gradient(True)`` (or ``FEWBIT_FUSED_WGRAD=1``; off by default) ``G^T X^`` is ONE MFMA kernel that decodes the codes on their
+way into the matrix pipe (``cabi_x.quant_wgrad``, ``fewbit_amd/csrc/fewbit_qgemm.hip``): X^ is never written to memory, the two bf16 terms of
+8 bits meet in the same accumulators, and backward allocates nothing of the input's size; served are bf16 / fp16 gradients with ``in_features`` a
+multiple of 64 and ``out_features`` of 8, every other call takes the route above.  Out of scope: 3-bit codes, per-row groups.
 """
 import contextlib
 import os
@@ -106,7 +109,8 @@ import torch.nn.functional as F
 from .fft import dct
 
 __all__ = ('MATMUL_TYPES', 'projection_dim', 'linear_crs', 'linear_grp', 'linear_randomized', 'LinearCRS', 'LinearGRP',
-           'RandomizedLinear', 'use_native_sketch', 'use_row_extension', 'use_sign_flips', 'sampled_transform', 'sampled_transform_path',
+           'RandomizedLinear', 'use_native_sketch', 'use_row_extension', 'use_sign_flips', 'use_fused_weight_gradient', 'sampled_transform',
+           'sampled_transform_path',
            'QUANT_BITS', 'linear_quantized', 'QuantizedLinear')
 
 MATMUL_TYPES = ('dct', 'dft', 'gaussian', 'rademacher')
@@ -195,6 +199,25 @@ def use_sign_flips(on: Optional[bool] = None) -> bool:
     prev = _SIGN_FLIPS
     if on is not None:
         _SIGN_FLIPS = bool(on)
+    return prev
+
+
+_FUSED_WGRAD = os.environ.get('FEWBIT_FUSED_WGRAD', '0') in ('1', 'yes', 'true')
+
+
+def use_fused_weight_gradient(on: Optional[bool] = None) -> bool:
+    """Query / set whether the quantized layers (``linear_quantized`` / ``QuantizedLinear``, the gated MLP as one node) form ``G^T X^`` with
+    ``cabi_x.quant_wgrad``: ONE gfx950 MFMA kernel that decodes the packed codes on their way into the matrix pipe, so that X^ is never written to
+    memory (fewbit_amd/csrc/fewbit_qgemm.hip).  Off by default (environment: ``FEWBIT_FUSED_WGRAD=1`` turns it on): off, backward decodes X^ into a
+    transient tensor and calls the library GEMM, bit for bit as before.  On, it applies where the kept input is a kernel buffer, the gradient is
+    bf16 or fp16, ``in_features`` is a multiple of 64 and ``out_features`` of 8 (``cabi_x.quant_wgrad_serves``); every other call takes the route
+    above and gives its bits.  The operand values are the same on both routes (the two bf16 terms at bf16 / 8 bits included); the fp32 sums are
+    added in another order, so the results agree to rounding, not to the bit.  A backward follows the switch as it stands when it runs.  Returns
+    the previous setting."""
+    global _FUSED_WGRAD
+    prev = _FUSED_WGRAD
+    if on is not None:
+        _FUSED_WGRAD = bool(on)
     return prev
 
 
@@ -738,7 +761,8 @@ class _LinearQuantized(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             # X^ in the gradient's dtype (under autocast not the input's): a transient tensor, one GEMM (the kernels decode into fp32 / fp16 / bf16)
             g2 = flat if ctx.native_seed is None or flat.dtype in _DTYPES else flat.float()
-            grad_weight = kept.products((g2, ), x_kept, ctx.flat_shape, ctx.bits)[0].to(weight.dtype)
+            # (use_fused_weight_gradient(): straight from the codes on the MFMA kernel where it serves the call, nothing decoded into memory)
+            grad_weight = kept.products((g2, ), x_kept, ctx.flat_shape, ctx.bits, _FUSED_WGRAD)[0].to(weight.dtype)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             grad_bias = flat.sum(dim=0)
         return grad_input, grad_weight, grad_bias, None, None

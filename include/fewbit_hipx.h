@@ -50,7 +50,9 @@ extern "C" {
  * So was the loss of a row, the cross entropy that keeps the logits as given and one float per row (fewbit_hipx_cross_entropy_host,
  * _cross_entropy_forward, _cross_entropy_backward): inside revision 2, recognised by the presence of the symbols.
  * So was the step of a chunked LM head, the loss and the gradient of a row in one launch (fewbit_hipx_cross_entropy_step): inside revision 2,
- * recognised by the presence of the symbol. */
+ * recognised by the presence of the symbol.
+ * So was the weight gradient from the packed form (fewbit_hipx_quant_wgrad_workspace, _quant_wgrad): inside revision 2, recognised by the
+ * presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -601,6 +603,36 @@ int fewbit_hipx_cross_entropy_backward(int dtype, const void *logits, size_t row
                                        const float *lse, const float *grow, size_t grow_stride, void *dlogits, size_t ld_out, void *stream);
 int fewbit_hipx_cross_entropy_step(int dtype, void *logits, size_t rows, size_t width, size_t ld, const int64_t *target, int64_t ignore_index,
                                    const float *grow, size_t grow_stride, float *lse, float *loss, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The weight gradient from the packed form: dW = G^T X^ of a layer that keeps its input X as a quant_pack buffer, with the decode fused into the
+ * product (fewbit_amd/csrc/fewbit_qgemm.hip): X^ is never written to memory.
+ *     out[o][f] = sum over r < rows of G[r][o] * op(X^[r][f])           o < out_features, f < in_features
+ *   G       rows x out_features, row-major with leading dimension ld_grad, BF16 or F16 (`dtype`)
+ *   X^      the decode ("The packed form of a seed", above) of a buffer of rows * in_features elements at `bits` bits; with in_features a multiple of
+ *           64 a group is 64 features of one row: group r * in_features / 64 + f / 64
+ *   op(x)   x rounded once to `dtype` (what fewbit_hipx_quant_unpack into that dtype gives); for BF16 at 8 bits the two terms head = bf16(x) and
+ *           tail = bf16(x - head), both multiplied onto the same fp32 sums.  A poisoned group is NaN, and so are its 64 columns of out.
+ *   out     out_features x in_features, contiguous, F32 or `dtype` (`out_dtype`): the fp32 sums, rounded once for a 16-bit out_dtype
+ * Products of 16-bit operands are exact in fp32 and the sums are fp32 (v_mfma_f32_32x32x16_bf16 / _f16): entry by entry the result is within
+ * 2 (rows + slices + 2) 2^-24 sum |G| |op| of the exact sum of the same operands.
+ * Served: dtype BF16 or F16; bits 2, 4 or 8; rows >= 1; in_features a multiple of 64 and out_features a multiple of 8, each at most 2^23;
+ * rows * in_features and out_features * in_features at most 2^36.  Everything else of known dtype is FEWBIT_ERR_UNSUPPORTED (fp32 gradients
+ * on purpose: the 16-bit matrix pipe would round them), and fewbit_hipx_quant_wgrad_workspace returns 0 for it.
+ * The plan is a pure function of the extents: workgroups of 512 lanes own tiles of 256 out_features x 128 in_features and walk the rows in
+ * stages of 64; where the tiles alone are fewer than 256 the rows are cut into slices (multiples of 64 rows) whose fp32 partial sums go to the
+ * workspace and are added by a second launch in slice order: no atomics, the same arguments give the same bits.  The slice count is capped so
+ * that the workspace -- slices * out_features * in_features * 4 bytes, 0 with one slice -- never exceeds rows * in_features * sizeof(dtype),
+ * the decoded tensor this entry point does away with.
+ *   grad, ld_grad     16-byte aligned, ld_grad a multiple of 8 and at least out_features.  No row at or beyond `rows` is read.
+ *   packed, packed_bytes   8-byte aligned, at least fewbit_hipx_quant_bytes(rows * in_features, bits) bytes; nothing beyond that many is read
+ *   out               16-byte aligned; workspace: 16-byte aligned, at least the queried size (may be NULL when that is 0)
+ * Refused before anything is launched: an unknown dtype or out_dtype, an out_dtype that is neither F32 nor dtype, rows = 0, a bad ld_grad, null or
+ * misaligned pointers, packed_bytes or workspace_bytes too small (FEWBIT_ERR_INVALID_ARGUMENT).  One or two launches on `stream`, nothing is
+ * read back, no host synchronisation: the call can be captured into a hipGraph. */
+size_t fewbit_hipx_quant_wgrad_workspace(int dtype, size_t rows, size_t in_features, size_t out_features, int bits);
+int fewbit_hipx_quant_wgrad(int dtype, const void *grad, size_t ld_grad, const uint8_t *packed, size_t packed_bytes, size_t rows, size_t in_features,
+                            size_t out_features, int bits, int out_dtype, void *out, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

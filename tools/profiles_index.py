@@ -70,6 +70,8 @@ ROWS = [
     ('cross_entropy_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2888 device functions before / after fewbit_xent.hip was added (6 new)', f'{E} 8.29'),
     ('linear_cross_entropy_bench.json', 'tools/linear_cross_entropy_bench.py: fewbit.functional.linear_cross_entropy forward + backward beside fewbit.functional.cross_entropy(F.linear(x, W), t), plain and with inplace_backward, and F.cross_entropy(F.linear(x, W).float(), t) at 16384 tokens, 4096 -> 32000 / 128256 and 768 -> 50265, bf16 and fp32; peak allocation; a chunk_rows sweep; the step kernel alone against its byte floor beside the forward + in-place backward pair', f'{E} 8.30'),
     ('linear_cross_entropy_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2894 device functions before / after the step kernel was added to fewbit_xent.hip as a unit of its own (9 new)', f'{E} 8.30'),
+    ('quant_wgrad_bench.json', 'tools/quant_linear_bench.py --fused: QuantizedLinear forward + backward with use_fused_weight_gradient() off and on, cabi_x.quant_wgrad alone against quant_unpack + torch.mm on the same buffers, the plan, the kernel flop/s and the allocator peak over one backward at 16384 rows, 768 -> 3072 and 3072 -> 768, bf16 and fp16', f'{E} 8.31'),
+    ('quant_wgrad_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2903 device functions before / after fewbit_qgemm.hip was added as a unit of its own (16 new), and the registers and instruction counts of the new kernels', f'{E} 8.31'),
     ('unit_fold_speed*.txt','the launch-bound entry-point arms of quant_linear_bench, dropout_bench, glu_bench and layer_norm_bench from the parent and from the tree with fewbit_unit.h, alternating five times', f'{E} 8.27'),
     ('signed_transform_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1915 device functions before / after the signed pass A was added (228 new)', f'{E} 8.15'),
     ('moments_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1890 device functions before / after fewbit_moments.hip was added (13 new)', f'{E} 8.9'),

@@ -13,6 +13,8 @@ fewbit.memory_usage_hooks (the weight included, which every arm keeps).  Beside 
 gradient against the fp64 product, and of the 'dct' arm's.
 
     python tools/quant_linear_bench.py [--out FILE]        ->  profiles/quant_linear_bench.json
+    python tools/quant_linear_bench.py --fused [--out FILE]  ->  profiles/quant_wgrad_bench.json: the layer with linear.use_fused_weight_gradient() off and
+        on, cabi_x.quant_wgrad alone against quant_unpack + torch.mm on the same buffers, and the allocator's peak over one backward (fused_main)
 """
 import argparse
 import json
@@ -40,12 +42,95 @@ def saved_bytes(f):
     return usage.forward or 0
 
 
+def backward_peak(layer, x, gy, fused):
+    """bytes by which the allocator's peak over ONE backward exceeds what was allocated before it"""
+    prev = fewbit.linear.use_fused_weight_gradient(fused)
+    try:
+        y = layer(x)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        torch.autograd.grad(y, (x, layer.weight, layer.bias), gy)
+        torch.cuda.synchronize()
+        return torch.cuda.max_memory_allocated() - before
+    finally:
+        fewbit.linear.use_fused_weight_gradient(prev)
+
+
+def fused_main(args):
+    """--fused: the weight gradient straight from the codes (cabi_x.quant_wgrad, fewbit_amd/csrc/fewbit_qgemm.hip) beside the default route, bf16 and fp16
+    gradients: the layer forward + backward with linear.use_fused_weight_gradient() off and on, the kernel alone against quant_unpack + torch.mm on
+    the same buffers (at bf16 / 8 bits the fp32 decode, the split and two GEMMs: kept.products' own code), and the allocator's peak over one backward"""
+    from fewbit_amd import kept
+    rows = []
+    for fin, fout in ((768, 3072), (3072, 768)):
+        for dtype in (torch.bfloat16, torch.float16):
+            torch.manual_seed(0)
+            x = torch.randn(ROWS, fin, device=DEV).to(dtype).requires_grad_()
+            gy = torch.randn(ROWS, fout, device=DEV).to(dtype)
+            xd, n = x.detach(), ROWS * fin
+            out = torch.empty(fout, fin, device=DEV, dtype=torch.float32)
+            workspace = torch.empty(max(cabi_x.quant_wgrad_workspace(dtype, ROWS, fin, fout, 4), 16), dtype=torch.uint8, device=DEV)
+            arms, layers, packed = {}, {}, {}
+            for bits in BITS:
+                layer = layers[bits] = fewbit.QuantizedLinear(fin, fout, device=DEV, dtype=dtype, bits=bits)
+                packed[bits] = cabi_x.quant_pack(xd, SEED, bits)
+
+                def step(layer=layer, fused=False):
+                    prev = fewbit.linear.use_fused_weight_gradient(fused)
+                    try:
+                        return torch.autograd.grad(layer(x), (x, layer.weight, layer.bias), gy)
+                    finally:
+                        fewbit.linear.use_fused_weight_gradient(prev)
+                arms[f'layer_{bits}_default'] = (step, args.reps)
+                arms[f'layer_{bits}_fused'] = (lambda step=step: step(fused=True), args.reps)
+                arms[f'route_{bits}_unpack_mm'] = (lambda bits=bits: kept.products((gy, ), (packed[bits], ), (ROWS, fin), bits), args.reps)
+                arms[f'route_{bits}_quant_wgrad'] = (lambda bits=bits: cabi_x.quant_wgrad(gy, packed[bits], fin, bits, torch.float32, out, workspace=workspace), args.reps)
+            runs = {name: [] for name in arms}
+            for f, _ in arms.values():
+                timed(f, reps=10, rounds=1)
+            for _ in range(2):
+                for name, (f, reps) in arms.items():
+                    runs[name].append(round(timed(f, reps=reps), 2))
+            us = {name: min(v) for name, v in runs.items()}
+            exact = gy.double().T @ xd.double()
+            slices = cabi_x.quant_wgrad_slices(ROWS, fin, fout)
+            bm, bn, bk = cabi_x.QUANT_WGRAD_TILE
+            row = {'rows': ROWS, 'in_features': fin, 'out_features': fout, 'dtype': str(dtype).replace('torch.', ''), 'us': us, 'runs_us': runs,
+                   'fused_over_default': {str(bits): {'layer': round(us[f'layer_{bits}_fused'] / us[f'layer_{bits}_default'], 4),
+                                                      'weight_gradient_alone': round(us[f'route_{bits}_quant_wgrad'] / us[f'route_{bits}_unpack_mm'], 4)} for bits in BITS},
+                   'plan': {'tile': [bm, bn, bk], 'tiles': -(-fin // bn) * -(-fout // bm), 'slices': slices,
+                            'workspace_bytes': cabi_x.quant_wgrad_workspace(dtype, ROWS, fin, fout, 4), 'decoded_tensor_bytes': n * x.element_size()},
+                   'kernel_tflops': {str(bits): round(2.0 * ROWS * fin * fout * (2 if kept.decode_in_two_terms(bits, dtype) else 1) / us[f'route_{bits}_quant_wgrad'] / 1e6, 1)
+                                     for bits in BITS},
+                   'backward_peak_bytes': {str(bits): {'default': backward_peak(layers[bits], x, gy, False), 'fused': backward_peak(layers[bits], x, gy, True)} for bits in BITS},
+                   'weight_gradient_relative_error_of_one_call': {
+                       str(bits): {'default': round(float((kept.products((gy, ), (packed[bits], ), (ROWS, fin), bits)[0].double() - exact).norm() / exact.norm()), 5),
+                                   'fused': round(float((cabi_x.quant_wgrad(gy, packed[bits], fin, bits, torch.float32).double() - exact).norm() / exact.norm()), 5)}
+                       for bits in BITS}}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del arms, layers, packed, x, gy, xd, out, workspace, exact
+            torch.cuda.empty_cache()
+    record = {'what': 'python tools/quant_linear_bench.py --fused: QuantizedLinear forward + backward with use_fused_weight_gradient() off and on, and the weight '
+                      'gradient alone (quant_unpack + torch.mm against cabi_x.quant_wgrad on the same buffers); every arm in one process, alternating; us per call; '
+                      'kernel_tflops counts the multiplies the matrix pipe does (two terms at bf16 / 8 bits)',
+              'device': torch.cuda.get_device_name(0), 'torch': torch.__version__, 'rows': rows}
+    with open(args.out, 'w') as f:
+        json.dump(record, f, indent=1)
+        f.write('\n')
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'quant_linear_bench.json'), help='where the record is written')
+    ap.add_argument('--out', default=None, help='where the record is written (default: profiles/quant_linear_bench.json; with --fused profiles/quant_wgrad_bench.json)')
     ap.add_argument('--reps', type=int, default=50, help='back-to-back calls per timed round')
+    ap.add_argument('--fused', action='store_true', help='measure the fused weight gradient (cabi_x.quant_wgrad) beside the default route instead')
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, 'profiles', 'quant_wgrad_bench.json' if args.fused else 'quant_linear_bench.json')
     assert torch.cuda.is_available(), 'a measurement needs the GPU'
+    if args.fused:
+        return fused_main(args)
     rows = []
     for fin, fout, dtype in CASES:
         torch.manual_seed(0)
