@@ -80,7 +80,7 @@ from . import functional  # noqa: E402,F401
 from . import modules  # noqa: E402,F401
 from . import approx, cli, compat, fft, glu, linear, norm, variance, xent  # noqa: E402,F401
 from .modules import *  # noqa: E402,F401,F403
-from .linear import LinearCRS, LinearGRP, QuantizedLinear, RandomizedLinear  # noqa: E402,F401
+from .linear import LinearCRS, LinearGRP, MXLinear, QuantizedLinear, RandomizedLinear  # noqa: E402,F401
 from .dropout import Dropout, dropout, dropout_add  # noqa: E402,F401  (fewbit_amd.dropout is the function from here on; the module: sys.modules['fewbit_amd.dropout'])
 from .norm import (DropoutAddLayerNorm, DropoutAddRMSNorm, QuantizedLayerNorm, QuantizedRMSNorm, dropout_add_layer_norm_quantized,  # noqa: E402,F401
                    dropout_add_rms_norm_quantized, layer_norm_quantized, rms_norm_quantized)

@@ -3,7 +3,7 @@ of ``libfewbit_hip.so`` was frozen at version 5 (``cabi.SYMBOLS`` stays that lis
 torch's current stream on the tensors' device, no fallback -- a missing library or an unsupported shape raises.  What it binds: the sampled
 Fourier transform, the zero-extended and sign-flipped sampled transforms, the column sampling of LinearCRS, the moments of the variance
 estimator, the dropout of a seed, the packed form of a seed, the layer norm and the RMS norm that keep the normalized rows of a seed, and the
-same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed, with the backward that also rebuilds that product from the state, and the cross entropy of a row that keeps the logits as given and one float per row, and the weight gradient of a layer straight from the packed form of its input.
+same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed, with the backward that also rebuilds that product from the state, and the cross entropy of a row that keeps the logits as given and one float per row, and the weight gradient of a layer straight from the packed form of its input, and the row blocks of a seed: a matrix kept as MXFP4 / 6 / 8 cells down its columns and the weight gradient from two such buffers on the scaled matrix instruction.
 """
 import ctypes
 import os
@@ -23,7 +23,8 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'add_rms_norm_forward', 'add_rms_norm_backward', 'GLU_ACTIVATIONS', 'glu_state_bytes', 'glu_state_host', 'glu_forward', 'glu_backward',
            'glu_backward_product', 'CROSS_ENTROPY_MAX_GROUPS', 'cross_entropy_host', 'cross_entropy_forward', 'cross_entropy_backward',
            'CROSS_ENTROPY_STEP_STAGED_BYTES', 'cross_entropy_step', 'QUANT_WGRAD_TILE', 'quant_wgrad_serves', 'quant_wgrad_slices', 'quant_wgrad_workspace',
-           'quant_wgrad']
+           'quant_wgrad', 'MX_FORMATS', 'MX_WGRAD_TILE', 'mx_bytes', 'mx_pack_host', 'mx_unpack_host', 'mx_pack', 'mx_unpack', 'mx_wgrad_serves', 'mx_wgrad_slices',
+           'mx_wgrad_workspace', 'mx_wgrad']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -98,6 +99,14 @@ _SIGNATURES = {
     # the weight gradient from the packed form (the decode fused into the product): inside revision 2 as well, recognised by its symbols
     'fewbit_hipx_quant_wgrad_workspace': (_sz, [_i32, _sz, _sz, _sz, _i32]),
     'fewbit_hipx_quant_wgrad': (_i32, [_i32, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _i32, _i32, _vp, _vp, _sz, _vp]),
+    # the row blocks of a seed (MX cells down the columns, the weight gradient on the scaled MFMA): inside revision 2 as well, recognised by its symbols
+    'fewbit_hipx_mx_bytes': (_sz, [_sz, _sz, _i32]),
+    'fewbit_hipx_mx_pack_host': (_i32, [_vp, _sz, _sz, _i32, _i32, _u64, _vp]),
+    'fewbit_hipx_mx_unpack_host': (_i32, [_vp, _sz, _sz, _i32, _vp]),
+    'fewbit_hipx_mx_pack': (_i32, [_i32, _vp, _sz, _sz, _sz, _i32, _i32, _u64, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_mx_unpack': (_i32, [_vp, _sz, _sz, _sz, _i32, _i32, _vp, _vp]),
+    'fewbit_hipx_mx_wgrad_workspace': (_sz, [_sz, _sz, _sz, _i32]),
+    'fewbit_hipx_mx_wgrad': (_i32, [_vp, _sz, _vp, _sz, _i32, _sz, _sz, _sz, _i32, _vp, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -1096,4 +1105,155 @@ def quant_wgrad(grad: torch.Tensor, packed: torch.Tensor, in_features: int, bits
         _check(lib().fewbit_hipx_quant_wgrad(DTYPES[grad.dtype], grad.data_ptr(), ld, packed.data_ptr(), packed.numel(), rows, in_features, out_features, bits,
                                              DTYPES[out_dtype], out.data_ptr(), _ptr(workspace), 0 if workspace is None else workspace.numel(),
                                              _stream(stream, grad.device)))
+    return out
+
+
+# ---- the row blocks of a seed (fewbit_amd/csrc/fewbit_mx.hip): OCP-MX cells down the columns, G^T X^ on v_mfma_scale_f32_32x32x64_f8f6f4 -------------
+MX_FORMATS = {'fp4': 4, 'fp6': 6, 'fp8': 8}     # E2M1, E2M3, E4M3: the library names a format by its bits
+MX_ROLES = {'kept': 0, 'grad': 1}               # Philox domain 9 / 10: the two roundings of one seed are independent
+MX_WGRAD_TILE = (128, 128, 64)                  # (BM out_features, BN in_features, BK rows) of a workgroup's tile and of a step of its K loop
+MX_WGRAD_TARGET = 256                           # workgroups the plan tries to reach by slicing the rows (kTargetGroups in fewbit_mx.hip)
+MX_WGRAD_MAX_WIDTH = 1 << 22
+
+
+def _mx_format(name: str, format: str) -> int:
+    if format not in MX_FORMATS:
+        raise FewbitHipError(f"{name}: format must be 'fp4', 'fp6' or 'fp8' (got {format!r})")
+    return MX_FORMATS[format]
+
+
+def mx_bytes(rows: int, width: int, format: str) -> int:
+    """Bytes of the row blocks of a ``rows x width`` matrix: ``ceil(rows / 32) * width`` scale bytes rounded up to a multiple of 16, then a cell of
+    16 / 24 / 32 bytes per 32 rows of a column; 0 for an unknown format and for extents outside 1 .. (``width`` 2^23, ``rows * width`` 2^36).
+    Evaluated on the host; no GPU needed."""
+    if format not in MX_FORMATS or rows < 0 or width < 0:
+        return 0
+    return lib().fewbit_hipx_mx_bytes(rows, width, MX_FORMATS[format])
+
+
+def _mx_size(name: str, rows: int, width: int, format: str) -> int:
+    need = lib().fewbit_hipx_mx_bytes(rows, width, _mx_format(name, format))
+    if need == 0:
+        raise FewbitHipError(f'{name}: no row blocks for {rows} x {width} elements (1 .. 2^23 wide, 1 .. 2^36 elements are supported)')
+    return need
+
+
+def mx_pack_host(values: torch.Tensor, seed: int, format: str, role: str = 'kept') -> torch.Tensor:
+    """The buffer ``mx_pack`` writes for ``seed``, evaluated on the host: ``values`` (2-D; taken as contiguous fp32) -> a host uint8 tensor of
+    ``mx_bytes(*values.shape, format)`` bytes.  The definition is include/fewbit_hipx.h's ("the row blocks of a seed"); no GPU needed."""
+    x = values.detach().to(device='cpu', dtype=torch.float32).contiguous()
+    if x.dim() != 2:
+        raise FewbitHipError('values must be 2-D')
+    out = torch.empty(_mx_size('mx_pack_host', x.shape[0], x.shape[1], format), dtype=torch.uint8)
+    _check(lib().fewbit_hipx_mx_pack_host(x.data_ptr(), x.shape[0], x.shape[1], MX_FORMATS[format], MX_ROLES[role], seed & 0xffffffffffffffff, out.data_ptr()))
+    return out
+
+
+def mx_unpack_host(packed: torch.Tensor, rows: int, width: int, format: str) -> torch.Tensor:
+    """The fp32 decode of a buffer on the host: a ``rows x width`` float32 tensor (code value times 2^e, exact; a poisoned cell: 32 NaNs)"""
+    _state_to_read(packed, _mx_size('mx_unpack_host', rows, width, format), 'packed', host=True)
+    out = torch.empty((rows, width), dtype=torch.float32)
+    _check(lib().fewbit_hipx_mx_unpack_host(packed.data_ptr(), rows, width, MX_FORMATS[format], out.data_ptr()))
+    return out
+
+
+def mx_pack(x: torch.Tensor, seed, format: str, role: str = 'kept', out: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+    """``x`` (a 2-D fp32 / fp16 / bf16 GPU tensor, unit stride along its width, rows at least a width apart) as MX cells down its columns with
+    unbiased stochastic rounding, in ONE launch: a uint8 tensor of ``mx_bytes(*x.shape, format)`` bytes -- per 32 rows of a column one E8M0 scale
+    byte and 32 fp4 / fp6 / fp8 codes, laid out as the operand fragments of the scaled matrix instruction.  ``seed``: an int, or a one-element
+    int64 tensor on the device of ``x`` that is read when the kernel runs.  ``role``: 'kept' or 'grad', the Philox domain.  ``mx_pack_host``
+    gives the same bytes for the same seed (the up to 15 bytes between the scales and the codes apart: the kernel leaves them alone).  ``out``: a
+    contiguous uint8 tensor of at least that many bytes (16-byte aligned)."""
+    if x.device.type != 'cuda':
+        raise FewbitHipError(f'x must live on the GPU (got {x.device})')
+    if x.dtype not in DTYPES:
+        raise FewbitHipError(f'unsupported dtype {x.dtype}')
+    rows, width, ld = _logits_rows(x, 'x')
+    need = _mx_size('mx_pack', rows, width, format)
+    value, word, others = _seed_arguments(seed)
+    with _on(x.device):
+        out = _state_to_write(out, True, need, x.device, 'out')
+        _same_device(x, out, *others)
+        _check(lib().fewbit_hipx_mx_pack(DTYPES[x.dtype], x.data_ptr(), rows, width, ld, MX_FORMATS[format], MX_ROLES[role], value, word, out.data_ptr(),
+                                         out.numel(), _stream(stream, x.device)))
+    return out
+
+
+def mx_unpack(packed: torch.Tensor, rows: int, width: int, format: str, dtype: torch.dtype, out: Optional[torch.Tensor] = None,
+              stream: Optional[int] = None) -> torch.Tensor:
+    """The decode of an ``mx_pack`` buffer in ONE launch: ``rows x width`` elements of ``dtype`` (fp32 / fp16 / bf16), each the exact value rounded
+    once to ``dtype``; a poisoned cell decodes to NaN.  ``out``: a contiguous ``rows x width`` tensor of ``dtype``."""
+    if packed.device.type != 'cuda':
+        raise FewbitHipError(f'packed must live on the GPU (got {packed.device})')
+    if dtype not in DTYPES:
+        raise FewbitHipError(f'unsupported dtype {dtype}')
+    _state_to_read(packed, _mx_size('mx_unpack', rows, width, format), 'packed')
+    with _on(packed.device):
+        if out is None:
+            out = torch.empty((rows, width), dtype=dtype, device=packed.device)
+        elif tuple(out.shape) != (rows, width) or out.dtype != dtype or not out.is_contiguous():
+            raise FewbitHipError(f'out must be a contiguous {rows} x {width} tensor of {dtype}')
+        _same_device(packed, out)
+        _check(lib().fewbit_hipx_mx_unpack(packed.data_ptr(), packed.numel(), rows, width, MX_FORMATS[format], DTYPES[dtype], out.data_ptr(),
+                                           _stream(stream, packed.device)))
+    return out
+
+
+def mx_wgrad_serves(rows: int, in_features: int, out_features: int, format: str) -> bool:
+    """Whether ``mx_wgrad`` has a kernel for an fp8 gradient of ``rows x out_features`` against ``rows x in_features`` kept at ``format``: 'fp4' or
+    'fp6', every ``rows >= 1``, both widths multiples of 32.  The host predicate the layer asks (``serves`` in fewbit_mx.hip); no GPU needed."""
+    wider = max(in_features, out_features)
+    return (format in ('fp4', 'fp6') and rows >= 1 and min(in_features, out_features) >= 32 and in_features % 32 == 0 and out_features % 32 == 0
+            and wider <= MX_WGRAD_MAX_WIDTH and rows * wider <= 2**36 and in_features * out_features <= 2**36)
+
+
+def mx_wgrad_slices(rows: int, in_features: int, out_features: int) -> int:
+    """K slices of the plan at served extents (``make_plan`` in fewbit_mx.hip, the same arithmetic): as many as bring the workgroups to at most
+    ``MX_WGRAD_TARGET``, never more than keep the workspace within ``rows * in_features * 2`` bytes, none of them empty"""
+    bm, bn, bk = MX_WGRAD_TILE
+    tiles = -(-in_features // bn) * -(-out_features // bm)
+    steps = -(-rows // bk)
+    want = min(MX_WGRAD_TARGET // tiles, rows // (2 * out_features), steps, 65535)
+    if want < 2:
+        return 1
+    per_slice = -(-steps // want)
+    return -(-steps // per_slice)
+
+
+def mx_wgrad_workspace(rows: int, in_features: int, out_features: int, format: str) -> int:
+    """Bytes of scratch ``mx_wgrad`` needs (the library's own answer): the fp32 partial sums of the K slices, 0 with one slice and for a call the
+    kernel does not serve.  Never more than ``rows * in_features * 2``."""
+    if format not in MX_FORMATS or min(rows, in_features, out_features) < 0:
+        return 0
+    return lib().fewbit_hipx_mx_wgrad_workspace(rows, in_features, out_features, MX_FORMATS[format])
+
+
+def mx_wgrad(grad: torch.Tensor, kept: torch.Tensor, rows: int, in_features: int, out_features: int, format: str, out_dtype: torch.dtype = torch.float32,
+             out: Optional[torch.Tensor] = None, stream: Optional[int] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``G^^T X^`` from two ``mx_pack`` buffers with nothing decoded: ``grad`` the 'fp8' buffer of a ``rows x out_features`` gradient, ``kept`` the
+    ``format`` ('fp4' / 'fp6') buffer of a ``rows x in_features`` input -> ``out_features x in_features`` in ``out_dtype`` (the fp32 sums, rounded
+    once for a 16-bit one).  The code bytes are the operands of v_mfma_scale_f32_32x32x64_f8f6f4 as they lie in memory, the scale bytes its scale
+    operands.  The same arguments give the same bits; nothing is read back, the call can be captured.  A call ``mx_wgrad_serves`` denies raises.
+    ``out``, ``workspace`` (uint8, at least ``mx_wgrad_workspace`` bytes): buffers to use."""
+    if grad.device.type != 'cuda' or kept.device.type != 'cuda':
+        raise FewbitHipError(f'grad and kept must live on the GPU (got {grad.device}, {kept.device})')
+    if out_dtype not in DTYPES:
+        raise FewbitHipError(f'unsupported dtype {out_dtype}')
+    for t, what in ((grad, 'grad'), (kept, 'kept')):
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise FewbitHipError(f'{what} must be a contiguous uint8 tensor')
+    fmt = _mx_format('mx_wgrad', format)
+    with _on(grad.device):
+        if out is None:
+            out = torch.empty((out_features, in_features), dtype=out_dtype, device=grad.device)
+        elif out.dtype != out_dtype or tuple(out.shape) != (out_features, in_features) or not out.is_contiguous():
+            raise FewbitHipError(f'out must be a contiguous {out_features} x {in_features} tensor of {out_dtype}')
+        need = mx_wgrad_workspace(rows, in_features, out_features, format)
+        if workspace is None and need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=grad.device)
+        elif workspace is not None and (workspace.dtype != torch.uint8 or not workspace.is_contiguous()):
+            raise FewbitHipError('workspace must be a contiguous uint8 tensor')
+        _same_device(grad, kept, out, *(() if workspace is None else (workspace, )))
+        _check(lib().fewbit_hipx_mx_wgrad(grad.data_ptr(), grad.numel(), kept.data_ptr(), kept.numel(), fmt, rows, in_features, out_features, DTYPES[out_dtype],
+                                          out.data_ptr(), _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream(stream, grad.device)))
     return out

@@ -98,6 +98,18 @@ for bit the kernel's).  Autocast, checkpointing, ``no_grad`` and a frozen weight
 way into the matrix pipe (``cabi_x.quant_wgrad``, ``fewbit_amd/csrc/fewbit_qgemm.hip``): X^ is never written to memory, the two bf16 terms of
 8 bits meet in the same accumulators, and backward allocates nothing of the input's size; served are bf16 / fp16 gradients with ``in_features`` a
 multiple of 64 and ``out_features`` of 8, every other call takes the route above.  Out of scope: 3-bit codes, per-row groups.
+
+The input in a form the matrix pipe reads: ``linear_mx`` / ``MXLinear`` keep the input as OCP-MX cells that run DOWN its columns -- 32 consecutive
+rows of one feature share one E8M0 scale byte and are 32 fp4 (E2M1) or fp6 (E2M3) codes, rounded without bias ("the row blocks of a seed",
+include/fewbit_hipx.h; ``cabi_x.mx_pack``): 0.2656 x (fp4) or 0.3906 x (fp6) of a bf16 input.  For the weight gradient the rows are the K
+dimension, so a cell is one lane's operand of ``v_mfma_scale_f32_32x32x64_f8f6f4``: backward packs G the same way into fp8 (E4M3, a transient of
+0.516 x G's bytes, an independent rounding of the same seed) and ``cabi_x.mx_wgrad`` forms ``G^^T X^`` with nothing decoded.  Both roundings are
+unbiased and independent: ``E[grad_weight] = G^T X``.  Forward is ``F.linear``; ``grad_input`` and ``grad_bias`` are exact.  Served by the product
+kernel: both feature counts multiples of 32; any other width decodes the kept cells (``cabi_x.mx_unpack``) and multiplies the exact G with the
+library GEMM.  Host tensors, float64 and ``use_native_sketch(False)`` evaluate the same definition with the library's host functions
+(``cabi_x.mx_pack_host`` / ``mx_unpack_host`` on an fp32 copy, the seed from the call's generator) and multiply the exact G -- like
+``linear_quantized`` they keep a formulation of the same scheme, here the very same bytes.  Captured into a hipGraph after one eager call the seed
+is a device word; ``no_grad``, a frozen weight and (the module) ``eval()`` keep nothing.
 """
 import contextlib
 import os
@@ -111,7 +123,7 @@ from .fft import dct
 __all__ = ('MATMUL_TYPES', 'projection_dim', 'linear_crs', 'linear_grp', 'linear_randomized', 'LinearCRS', 'LinearGRP',
            'RandomizedLinear', 'use_native_sketch', 'use_row_extension', 'use_sign_flips', 'use_fused_weight_gradient', 'sampled_transform',
            'sampled_transform_path',
-           'QUANT_BITS', 'linear_quantized', 'QuantizedLinear')
+           'QUANT_BITS', 'linear_quantized', 'QuantizedLinear', 'MX_KEPT_FORMATS', 'linear_mx', 'MXLinear')
 
 MATMUL_TYPES = ('dct', 'dft', 'gaussian', 'rademacher')
 
@@ -715,7 +727,7 @@ def linear_crs(input: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
 # ---- every element of the input in 2, 4 or 8 bits --------------------------------------------------------------------------------------
 
 # the code widths: the binding's constant (the import loads no library).  What the node keeps, and how it is decoded and multiplied: ``kept``
-from . import kept  # noqa: E402
+from . import cabi_x, kept  # noqa: E402
 from .cabi import DTYPES as _DTYPES  # noqa: E402
 from .cabi_x import QUANT_BITS  # noqa: E402
 from .kept import decode_in_two_terms as _decode_in_two_terms, two_term_product as _two_term_product  # noqa: E402,F401  (their names here: tests use them)
@@ -900,3 +912,120 @@ class QuantizedLinear(torch.nn.Linear):
 
     def extra_repr(self) -> str:
         return f'{super().extra_repr()}, bits={self.bits}'
+
+
+# ---- the input kept as MX cells down its columns: the weight gradient on the scaled matrix instruction -----------------------------------------
+
+MX_KEPT_FORMATS = ('fp4', 'fp6')
+
+
+def _check_mx_format(format: str) -> None:
+    if format not in MX_KEPT_FORMATS:
+        raise ValueError(f"format should be 'fp4' or 'fp6', but got {format!r}.")
+
+
+class _LinearMX(torch.autograd.Function):
+    """``F.linear`` that keeps its input as the row blocks of a seed (module docstring).  Kept for backward: ONE uint8 buffer of
+    ``cabi_x.mx_bytes(rows, in_features, format)`` bytes, the weight, the seed (an int; a device word while the stream is being captured) and the shape."""
+
+    @staticmethod
+    def forward(ctx, input, weight, bias, format: str, generator):
+        flat = input.detach().reshape(-1, input.shape[-1])
+        ctx.format, ctx.flat_shape = format, tuple(flat.shape)
+        ctx.has_bias = bias is not None
+        ctx.autocast = _autocast_seen(input.device.type)
+        ctx.native = _kernels_take(flat) and cabi_x.mx_bytes(*flat.shape, format) != 0
+        if ctx.native:
+            ctx.seed = _sketch_seed(generator, flat.device)
+            packed = cabi_x.mx_pack(_unit_stride(flat), ctx.seed, format, 'kept')
+        else:
+            ctx.seed = _draw_seed(generator if generator is None or generator.device.type == 'cpu' else None)
+            packed = cabi_x.mx_pack_host(flat, ctx.seed, format, 'kept').to(flat.device)
+        ctx.save_for_backward(packed, weight)
+        return F.linear(input, weight, bias)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        with _autocast_as(ctx.autocast):
+            return _LinearMX._backward(ctx, _dense_rows(grad_output))
+
+    @staticmethod
+    def _backward(ctx, grad_output):
+        packed, weight = ctx.saved_tensors
+        grad_input = grad_weight = grad_bias = None
+        if ctx.needs_input_grad[0]:
+            grad_input = grad_output @ weight
+        flat = grad_output.reshape(-1, grad_output.shape[-1])
+        if ctx.needs_input_grad[1]:
+            rows, fin = ctx.flat_shape
+            fout = flat.shape[1]
+            if not ctx.native:
+                decoded = cabi_x.mx_unpack_host(packed.cpu(), rows, fin, ctx.format).to(device=flat.device, dtype=flat.dtype)
+                grad_weight = flat.T @ decoded
+            elif flat.dtype in _DTYPES and cabi_x.mx_wgrad_serves(rows, fin, fout, ctx.format):
+                # (G as fp8 cells: a transient of 0.516 x its bytes, rounded in the gradient's own Philox domain of the same seed)
+                # (the kernel rounds its fp32 sums once to a 16-bit weight's dtype itself: no fp32 transient of the weight's size)
+                grad_weight = cabi_x.mx_wgrad(cabi_x.mx_pack(flat, ctx.seed, 'fp8', 'grad'), packed, rows, fin, fout, ctx.format,
+                                              weight.dtype if weight.dtype in _DTYPES else torch.float32)
+            else:
+                g2 = flat if flat.dtype in _DTYPES else flat.float()
+                grad_weight = g2.T @ cabi_x.mx_unpack(packed, rows, fin, ctx.format, g2.dtype)
+            grad_weight = grad_weight.to(weight.dtype)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            grad_bias = flat.sum(dim=0)
+        return grad_input, grad_weight, grad_bias, None, None
+
+
+def linear_mx(input: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, format: str = 'fp4',
+              generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """``F.linear(input, weight, bias)`` that keeps its input as MXFP4 (``format='fp4'``) or MXFP6 (``'fp6'``) cells down its columns, rounded without
+    bias, and forms the weight gradient from them and an fp8 rounding of the gradient on the scaled matrix instruction: ``grad_input`` and
+    ``grad_bias`` are exact, ``E[grad_weight] = G^T X`` (module docstring).  ``generator``: the source of the roundings' randomness; without it the
+    host default generator seeds every call."""
+    _check_mx_format(format)
+    if _plain_linear(input, weight):
+        return F.linear(input, weight, bias)
+    return _LinearMX.apply(input, weight, bias, format, generator)
+
+
+class MXLinear(torch.nn.Linear):
+    r"""Drop-in :class:`torch.nn.Linear` that keeps its input as MXFP4 / MXFP6 cells (32 consecutive rows of a feature: one scale byte, 32 codes) and
+    forms the weight gradient from them on the scaled matrix instruction of gfx950; the output, the input gradient and the bias gradient are those
+    of ``nn.Linear``.  In ``eval()`` mode gradients are torch's exact ones and nothing is kept.
+
+    Parameters (after those of ``nn.Linear``)
+    ----------
+    format : {'fp4', 'fp6'}, default='fp4'
+        The element format of the kept input: a bf16 input is kept in 0.2656 or 0.3906 of its bytes.
+    generator : torch.Generator, optional
+        Source of the roundings' randomness, as for :class:`QuantizedLinear`.
+
+    Examples:
+
+        >>> m = fewbit.MXLinear(64, 96, format='fp4')
+        >>> m(torch.randn(128, 64)).size()
+        torch.Size([128, 96])
+        >>> model = fewbit.map_module(model, lambda m, path: fewbit.MXLinear.from_linear(m) if type(m) is torch.nn.Linear else m)
+    """
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=None, format: str = 'fp4',
+                 generator: Optional[torch.Generator] = None) -> None:
+        _check_mx_format(format)
+        super().__init__(in_features, out_features, bias, device, dtype)
+        self.format = format
+        self.generator = generator
+
+    @classmethod
+    def from_linear(cls, module: torch.nn.Linear, format: str = 'fp4', generator: Optional[torch.Generator] = None) -> 'MXLinear':
+        """An ``MXLinear`` that SHARES the parameters of ``module`` (what ``map_module`` needs to swap the linears of a built model)"""
+        new = cls(module.in_features, module.out_features, module.bias is not None, device='meta', format=format, generator=generator)
+        new.weight, new.bias = module.weight, module.bias
+        return new.train(module.training)
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        if not self.training:
+            return F.linear(input, self.weight, self.bias)
+        return linear_mx(input, self.weight, self.bias, self.format, self.generator)
+
+    def extra_repr(self) -> str:
+        return f'{super().extra_repr()}, format={self.format}'

@@ -52,7 +52,9 @@ extern "C" {
  * So was the step of a chunked LM head, the loss and the gradient of a row in one launch (fewbit_hipx_cross_entropy_step): inside revision 2,
  * recognised by the presence of the symbol.
  * So was the weight gradient from the packed form (fewbit_hipx_quant_wgrad_workspace, _quant_wgrad): inside revision 2, recognised by the
- * presence of the symbols. */
+ * presence of the symbols.
+ * So were the row blocks of a seed (fewbit_hipx_mx_bytes, _mx_pack_host, _mx_unpack_host, _mx_pack, _mx_unpack, _mx_wgrad_workspace, _mx_wgrad):
+ * inside revision 2, recognised by the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -633,6 +635,60 @@ int fewbit_hipx_cross_entropy_step(int dtype, void *logits, size_t rows, size_t 
 size_t fewbit_hipx_quant_wgrad_workspace(int dtype, size_t rows, size_t in_features, size_t out_features, int bits);
 int fewbit_hipx_quant_wgrad(int dtype, const void *grad, size_t ld_grad, const uint8_t *packed, size_t packed_bytes, size_t rows, size_t in_features,
                             size_t out_features, int bits, int out_dtype, void *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The row blocks of a seed: a rows x width matrix kept as OCP-MX cells that run DOWN its columns, and the weight gradient of a layer from two such
+ * buffers on v_mfma_scale_f32_32x32x64_f8f6f4 (fewbit_amd/csrc/fewbit_mx.hip; the definition, evaluated alike on host and device:
+ * fewbit_amd/csrc/fewbit_mxdef.h).  For a weight gradient the rows are the K dimension, and the instruction takes one E8M0 scale per 32 values along
+ * K: a cell of this form IS the operand fragment of one lane, so nothing is decoded on the way into the matrix pipe.
+ *   cell (b, j)   rows 32 b .. 32 b + 31 of column j (rows >= `rows` count as +0): one scale byte and 32 codes
+ *   format        4: fp4 = E2M1 (largest value 6), 6: fp6 = E2M3 (7.5), 8: fp8 = E4M3 (448).  E3M2 and E5M2 are not offered.
+ *   scale         e = the smallest integer with amax * 2^-e <= the largest value, clamped to -127 .. 127, read from the exponent and the significand
+ *                 bits of amax; the byte is e + 127.  NOT the OCP recipe floor(log2 amax) - emax, which clips the top of every binade (6 < t < 8 at
+ *                 fp4) and so biases the estimate.  amax = 0: byte 0, every code +0.
+ *   poison        a cell that holds a NaN or an infinity has scale byte 0xFF (E8M0's NaN) and decodes to 32 NaNs; no other cell is touched.  Its
+ *                 codes are 0 (fp4, fp6) or 0x7F, the format's NaN (fp8).
+ *   code          t = |v| 2^-e (exact; evaluated in integers), lo <= t <= hi the neighbouring magnitudes of the format: hi's code where
+ *                 floor((t - lo) / (hi - lo) + U) >= 1, else lo's, with the sign of v.  U = 16 Philox bits / 65536: E[decode] = v to 2^-16 of a step.
+ *                 The decision only needs floor(65536 (t - lo) / (hi - lo)), so elements far below amax need no denormal product: their code is +-0.
+ *   Philox        counter (q low, q high, 0, domain), q = 4 (b * width + j) + (row % 32) / 8: one call per eight consecutive rows of a column,
+ *                 element row % 8 (the 16-bit halves as in "the mask of a seed").  domain 9: role 0, a kept input; domain 10: role 1, a gradient.
+ *   layout        scales [ceil(rows / 32)][width] bytes; from the next multiple of 16 the codes [ceil(rows / 32)][width][cell], a cell 16 / 24 / 32
+ *                 bytes; element r of a cell is bits [format * r, format * (r + 1)) of the cell as one little-endian number (fp4: low nibble
+ *                 first; fp6: a bit stream over 6 dwords; fp8: one byte each).  At fp4 and fp6 that is the order of 32 consecutive K values in one
+ *                 lane of the instruction; an 8-bit operand is held in halves of 16 K values, so the kernel reads an fp8 cell as two 16-byte halves.
+ *                 The bytes between the scales and the codes are written by the host function (0) and left alone by the kernel.
+ *   decode        magnitude * 2^e, exact in fp32; beyond FLT_MAX (amax within a step of it) it is an infinity.
+ * fewbit_hipx_mx_bytes: the size of a buffer, 0 for an unknown format, no elements, width > 2^23 or rows * width > 2^36.  A bf16 matrix is kept in
+ * 0.2656 (fp4), 0.3906 (fp6) or 0.5156 (fp8) of its bytes.
+ * fewbit_hipx_mx_pack_host / _unpack_host: the definition on the host, contiguous fp32 (ld = width).
+ * fewbit_hipx_mx_pack: ONE launch; src of `dtype`, unit stride along the width, row stride ld >= width, aligned to its element (16-byte pieces are
+ * loaded where src and ld allow, the same bytes come out either way); out 16-byte aligned, out_bytes >= fewbit_hipx_mx_bytes.  seed_device: as for
+ * fewbit_hipx_quant_pack (an 8-byte aligned device word read when the kernel runs, or NULL).
+ * fewbit_hipx_mx_unpack: ONE launch; the decode rounded once to out_dtype as a contiguous rows x width tensor.
+ * fewbit_hipx_mx_wgrad: out[o][i] = sum over r < rows of G^[r][o] * X^[r][i], G^ the decode of `grad` (an fp8 buffer of rows x out_features), X^ that of
+ * `kept` (`format` 4 or 6, rows x in_features); out: out_features x in_features, contiguous, of out_dtype (the fp32 sums, rounded once for a 16-bit
+ * one).  The instruction does not add the 64 products of a K step in fp32: it aligns them to the largest and cuts off, towards zero, what lies below
+ * 2^-13 of that one's binade (measured).  Entry by entry the result is within sum over K steps of 64 * 2^-13 * max |G^| * max |X^| (over the step's
+ * rows) + 2 (steps + slices + 2) 2^-24 sum |G^| |X^| of the exact sum; on N(0, 1) data the measured error is about 2^-20 of sum |G^| |X^|.
+ * A poisoned cell of X^ makes column i of out NaN, one of G^ row o.
+ * Served: format 4 or 6, rows >= 1, in_features and out_features multiples of 32 up to 2^22, rows * either and their product up to 2^36; anything
+ * else of known format is FEWBIT_ERR_UNSUPPORTED and fewbit_hipx_mx_wgrad_workspace returns 0 for it.  The plan is a pure function of the
+ * extents: workgroups of 256 lanes own 128 x 128 of out and walk the rows in steps of 64; where the tiles are fewer than 256 the steps are cut
+ * into slices whose fp32 partial sums go to the workspace and are added by a second launch in slice order (no atomics: the same arguments give
+ * the same bits).  The workspace -- slices * out_features * in_features * 4 bytes, 0 with one slice -- never exceeds rows * in_features * 2.
+ * Refused before anything is launched (FEWBIT_ERR_INVALID_ARGUMENT): an unknown dtype, format or role, width > 2^23, rows * width > 2^36, ld < width,
+ * rows = 0 (mx_wgrad; the others return at once), null or misaligned pointers (grad, kept, out and the workspace of mx_wgrad: 16 bytes), buffers
+ * too small.  Nothing is read back, no host synchronisation: every call can be captured into a hipGraph. */
+size_t fewbit_hipx_mx_bytes(size_t rows, size_t width, int format);
+int fewbit_hipx_mx_pack_host(const float *x_host, size_t rows, size_t width, int format, int role, uint64_t seed, uint8_t *out_host);
+int fewbit_hipx_mx_unpack_host(const uint8_t *packed_host, size_t rows, size_t width, int format, float *out_host);
+int fewbit_hipx_mx_pack(int dtype, const void *src, size_t rows, size_t width, size_t ld, int format, int role, uint64_t seed, const uint64_t *seed_device,
+                        uint8_t *out, size_t out_bytes, void *stream);
+int fewbit_hipx_mx_unpack(const uint8_t *packed, size_t packed_bytes, size_t rows, size_t width, int format, int out_dtype, void *out, void *stream);
+size_t fewbit_hipx_mx_wgrad_workspace(size_t rows, size_t in_features, size_t out_features, int format);
+int fewbit_hipx_mx_wgrad(const uint8_t *grad, size_t grad_bytes, const uint8_t *kept, size_t kept_bytes, int format, size_t rows, size_t in_features,
+                         size_t out_features, int out_dtype, void *out, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -72,6 +72,8 @@ ROWS = [
     ('linear_cross_entropy_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2894 device functions before / after the step kernel was added to fewbit_xent.hip as a unit of its own (9 new)', f'{E} 8.30'),
     ('quant_wgrad_bench.json', 'tools/quant_linear_bench.py --fused: QuantizedLinear forward + backward with use_fused_weight_gradient() off and on, cabi_x.quant_wgrad alone against quant_unpack + torch.mm on the same buffers, the plan, the kernel flop/s and the allocator peak over one backward at 16384 rows, 768 -> 3072 and 3072 -> 768, bf16 and fp16', f'{E} 8.31'),
     ('quant_wgrad_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2903 device functions before / after fewbit_qgemm.hip was added as a unit of its own (16 new), and the registers and instruction counts of the new kernels', f'{E} 8.31'),
+    ('mx_linear_bench.json', 'tools/mx_linear_bench.py: cabi_x.mx_wgrad alone, with and without the pack of G, beside torch.mm, mx_unpack + mm, quant_unpack + mm and quant_wgrad at 4 bits; cabi_x.mx_pack against its byte floor; MXLinear forward + backward beside nn.Linear and QuantizedLinear(bits=4); bytes saved, the allocator peak over one backward and the weight-gradient error at 16384 rows, 768 -> 3072, 3072 -> 768 and 4096 -> 11008, bf16 and fp16', f'{E} 8.32'),
+    ('mx_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2919 device functions before / after fewbit_mx.hip was added as a unit of its own (27 new), and the registers and instruction counts of the new kernels', f'{E} 8.32'),
     ('unit_fold_speed*.txt','the launch-bound entry-point arms of quant_linear_bench, dropout_bench, glu_bench and layer_norm_bench from the parent and from the tree with fewbit_unit.h, alternating five times', f'{E} 8.27'),
     ('signed_transform_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1915 device functions before / after the signed pass A was added (228 new)', f'{E} 8.15'),
     ('moments_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1890 device functions before / after fewbit_moments.hip was added (13 new)', f'{E} 8.9'),
