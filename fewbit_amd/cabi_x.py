@@ -3,7 +3,7 @@ of ``libfewbit_hip.so`` was frozen at version 5 (``cabi.SYMBOLS`` stays that lis
 torch's current stream on the tensors' device, no fallback -- a missing library or an unsupported shape raises.  What it binds: the sampled
 Fourier transform, the zero-extended and sign-flipped sampled transforms, the column sampling of LinearCRS, the moments of the variance
 estimator, the dropout of a seed, the packed form of a seed, the layer norm and the RMS norm that keep the normalized rows of a seed, and the
-same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed, with the backward that also rebuilds that product from the state, and the cross entropy of a row that keeps the logits as given and one float per row, and the weight gradient of a layer straight from the packed form of its input, and the row blocks of a seed: a matrix kept as MXFP4 / 6 / 8 cells down its columns and the weight gradient from two such buffers on the scaled matrix instruction.
+same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed, with the backward that also rebuilds that product from the state, and the cross entropy of a row that keeps the logits as given and one float per row, and the weight gradient of a layer straight from the packed form of its input, and the row blocks of a seed: a matrix kept as MXFP4 / 6 / 8 cells down its columns and the weight gradient from two such buffers on the scaled matrix instruction, and the gated product whose gate and up are kept as such cells, with the backward that writes the operands of all three weight gradients.
 """
 import ctypes
 import os
@@ -24,7 +24,7 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'glu_backward_product', 'CROSS_ENTROPY_MAX_GROUPS', 'cross_entropy_host', 'cross_entropy_forward', 'cross_entropy_backward',
            'CROSS_ENTROPY_STEP_STAGED_BYTES', 'cross_entropy_step', 'QUANT_WGRAD_TILE', 'quant_wgrad_serves', 'quant_wgrad_slices', 'quant_wgrad_workspace',
            'quant_wgrad', 'MX_FORMATS', 'MX_WGRAD_TILE', 'mx_bytes', 'mx_pack_host', 'mx_unpack_host', 'mx_pack', 'mx_unpack', 'mx_wgrad_serves', 'mx_wgrad_slices',
-           'mx_wgrad_workspace', 'mx_wgrad']
+           'mx_wgrad_workspace', 'mx_wgrad', 'mx_glu_state_bytes', 'mx_glu_forward', 'mx_glu_backward']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -107,6 +107,10 @@ _SIGNATURES = {
     'fewbit_hipx_mx_unpack': (_i32, [_vp, _sz, _sz, _sz, _i32, _i32, _vp, _vp]),
     'fewbit_hipx_mx_wgrad_workspace': (_sz, [_sz, _sz, _sz, _i32]),
     'fewbit_hipx_mx_wgrad': (_i32, [_vp, _sz, _vp, _sz, _i32, _sz, _sz, _sz, _i32, _vp, _vp, _sz, _vp]),
+    # the gate and the up as row blocks (the gated product on MX cells, all three weight gradients on the scaled MFMA): inside revision 2 as well
+    'fewbit_hipx_mx_glu_state_bytes': (_sz, [_sz, _sz, _i32]),
+    'fewbit_hipx_mx_glu_forward': (_i32, [_i32, _i32, _vp, _sz, _vp, _sz, _sz, _sz, _i32, _u64, _u64, _vp, _vp, _sz, _vp, _sz, _vp]),
+    'fewbit_hipx_mx_glu_backward': (_i32, [_i32, _i32, _vp, _sz, _vp, _sz, _sz, _sz, _i32, _u64, _u64, _u64, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -1257,3 +1261,85 @@ def mx_wgrad(grad: torch.Tensor, kept: torch.Tensor, rows: int, in_features: int
         _check(lib().fewbit_hipx_mx_wgrad(grad.data_ptr(), grad.numel(), kept.data_ptr(), kept.numel(), fmt, rows, in_features, out_features, DTYPES[out_dtype],
                                           out.data_ptr(), _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream(stream, grad.device)))
     return out
+
+
+# ---- the gate and the up as row blocks (fewbit_amd/csrc/fewbit_mxglu.hip): the gated product on MX cells, the operands of three mx_wgrad calls ------------
+def mx_glu_state_bytes(rows: int, width: int, format: str) -> int:
+    """Bytes of the state of ``mx_glu_forward``: two ``mx_pack`` buffers of ``format`` ('fp4' / 'fp6'), gate's at byte 0 and up's at half the size
+    (``mx_bytes`` filled up to a multiple of 16); 0 where ``mx_bytes`` is.  Evaluated on the host; no GPU needed."""
+    if format not in ('fp4', 'fp6') or rows < 0 or width < 0:
+        return 0
+    return lib().fewbit_hipx_mx_glu_state_bytes(rows, width, MX_FORMATS[format])
+
+
+def _mx_glu_call(name: str, like: torch.Tensor, format: str, seeds, count: int):
+    """What both launches take from their arguments: (rows, width, ld of ``like``, bytes of the state, seed values, device words, tensors of the seeds).
+    ``seeds``: ``count`` ints, or ONE int64 tensor of ``count`` words on the device that is read when the kernel runs."""
+    rows, width, ld = _glu_rows(like, name)
+    if format not in ('fp4', 'fp6'):
+        raise FewbitHipError(f"{name}: format must be 'fp4' or 'fp6' (got {format!r})")
+    need = mx_glu_state_bytes(rows, width, format)
+    if need == 0:
+        raise FewbitHipError(f'{name}: no row blocks for {rows} x {width} elements (1 .. 2^23 wide, 1 .. 2^36 elements are supported)')
+    if isinstance(seeds, torch.Tensor):
+        if seeds.device != like.device or seeds.dtype != torch.int64 or seeds.numel() != count or not seeds.is_contiguous():
+            raise FewbitHipError(f'{name}: seeds on the device must be {count} contiguous int64 words')
+        return rows, width, ld, need, (0, ) * count, seeds.data_ptr(), (seeds, )
+    if len(seeds) != count or len(set(s & 0xffffffffffffffff for s in seeds)) != count:
+        raise FewbitHipError(f'{name}: {count} different seeds are needed, one per rounded tensor')
+    return rows, width, ld, need, tuple(s & 0xffffffffffffffff for s in seeds), None, ()
+
+
+def _mx_glu_out(t: Optional[torch.Tensor], like: torch.Tensor, what: str) -> torch.Tensor:
+    if t is None:
+        return torch.empty(tuple(like.shape), dtype=like.dtype, device=like.device)
+    if t.dtype != like.dtype or t.shape != like.shape:
+        raise FewbitHipError(f'{what} must be a {like.shape[0]} x {like.shape[1]} tensor of {like.dtype}')
+    return t
+
+
+def mx_glu_forward(gate: torch.Tensor, up: torch.Tensor, activation: str, format: str, seeds, y: Optional[torch.Tensor] = None,
+                   state: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """``act(gate) * up`` in ONE launch -> ``(y, state)``.  ``gate``, ``up``: as for ``glu_forward`` (2-D, one shape and dtype, unit stride along the
+    width, any row stride); ``y`` has the bytes of ``glu_forward``'s.  ``state``: ``mx_glu_state_bytes`` bytes, its two halves bit for bit
+    ``mx_pack(gate, seeds[0], format, 'kept')`` and ``mx_pack(up, seeds[1], format, 'kept')``.  ``seeds``: two different ints (equal ones would round
+    both tensors with the same uniforms), or one int64 tensor of two words on the device.  ``y`` (any row stride), ``state``: buffers to write into."""
+    rows, width, ld_gate, need, values, words, others = _mx_glu_call('mx_glu_forward', gate, format, seeds, 2)
+    if up.shape != gate.shape or up.dtype != gate.dtype:
+        raise FewbitHipError('up must have the shape and dtype of gate')
+    ld_up = _glu_rows(up, 'up')[2]
+    act = _glu_activation(activation)
+    with _on(gate.device):
+        y = _mx_glu_out(y, gate, 'y')
+        ld_y = _glu_rows(y, 'y')[2]
+        state = _state_to_write(state, True, need, gate.device)
+        _same_device(gate, up, y, state, *others)
+        _check(lib().fewbit_hipx_mx_glu_forward(DTYPES[gate.dtype], act, gate.data_ptr(), ld_gate, up.data_ptr(), ld_up, rows, width, MX_FORMATS[format], *values,
+                                                words, y.data_ptr(), ld_y, state.data_ptr(), state.numel(), _stream(stream, gate.device)))
+    return y, state
+
+
+def mx_glu_backward(gy: torch.Tensor, state: torch.Tensor, activation: str, format: str, seeds, want=(True, True, True, True, True),
+                    d_gate: Optional[torch.Tensor] = None, d_up: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """The backward of ``mx_glu_forward`` in ONE launch -> ``(d_gate, d_up, d_gate_cells, d_up_cells, product_cells)``: the two gradients in the dtype of
+    ``gy`` with ``glu_backward_product``'s expressions on the decodes of the state, and three ``mx_pack`` buffers, bit for bit
+    ``mx_pack(d_gate, seeds[0], 'fp8', 'grad')``, ``mx_pack(d_up, seeds[1], 'fp8', 'grad')`` and ``mx_pack(y^, seeds[2], format, 'kept')`` with
+    ``y^ = act(g^) * u^`` rounded once to that dtype and never written itself: the operands of ``mx_wgrad`` for all three weights of a gated MLP.
+    Where ``want`` is False the output is None and is not written.  ``gy``, ``d_gate``, ``d_up``: 2-D, unit stride along the width, any row stride (the
+    halves of one ``rows x 2 width`` tensor).  ``seeds``: three different ints, or one int64 tensor of three words on the device."""
+    rows, width, ld_gy, need, values, words, others = _mx_glu_call('mx_glu_backward', gy, format, seeds, 3)
+    want = tuple(bool(w) for w in want)
+    if len(want) != 5:
+        raise FewbitHipError('want must name five outputs (d_gate, d_up, d_gate_cells, d_up_cells, product_cells)')
+    act = _glu_activation(activation)
+    _state_to_read(state, need)
+    with _on(gy.device):
+        d_gate = _mx_glu_out(d_gate, gy, 'd_gate') if want[0] else None
+        d_up = _mx_glu_out(d_up, gy, 'd_up') if want[1] else None
+        ld_dgate, ld_dup = (0 if t is None else _glu_rows(t, what)[2] for t, what in ((d_gate, 'd_gate'), (d_up, 'd_up')))
+        # (the entry point takes no sizes for the cell buffers: they are made here, of the library's own size)
+        cells = [torch.empty(mx_bytes(rows, width, f), dtype=torch.uint8, device=gy.device) if w else None for f, w in zip(('fp8', 'fp8', format), want[2:])]
+        _same_device(gy, state, *others, *(t for t in (d_gate, d_up, *cells) if t is not None))
+        _check(lib().fewbit_hipx_mx_glu_backward(DTYPES[gy.dtype], act, gy.data_ptr(), ld_gy, state.data_ptr(), state.numel(), rows, width, MX_FORMATS[format], *values,
+                                                 words, _ptr(d_gate), ld_dgate, _ptr(d_up), ld_dup, *(_ptr(t) for t in cells), _stream(stream, gy.device)))
+    return (d_gate, d_up, *cells)

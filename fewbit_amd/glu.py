@@ -27,6 +27,10 @@ bytes of the two bf16 inputs, a tenth of what torch keeps.  The few-bit activati
   default one (``generator=None`` included): checkpoint restores only those, and the recomputation must draw the forward's seed again.
 * A group of 64 elements of either input that holds a NaN or an infinity makes both gradients NaN on those 64 elements; ``y`` is the exact forward.
 * Not differentiable twice (``once_differentiable``).
+
+:func:`gated_mlp_mx` / :class:`MXGatedMLP` are the same MLP as one node on the OTHER kept form of this package, the row blocks of a seed (MXFP4 / MXFP6
+cells down the columns, ``cabi_x.mx_pack``): ``x``, ``gate`` and ``up`` are kept as cells, and all three weight gradients are formed from cells on the
+scaled matrix instruction of gfx950 (``cabi_x.mx_wgrad``); see there.
 """
 import math
 from typing import Optional, Tuple
@@ -38,7 +42,7 @@ from torch.autograd.function import once_differentiable
 from . import cabi_x, kept, linear
 from .cabi import DTYPES
 
-__all__ = ('glu_quantized', 'gated_mlp_quantized', 'QuantizedGLU', 'QuantizedGatedMLP')
+__all__ = ('glu_quantized', 'gated_mlp_quantized', 'gated_mlp_mx', 'QuantizedGLU', 'QuantizedGatedMLP', 'MXGatedMLP')
 
 ACTIVATIONS = cabi_x.GLU_ACTIVATIONS
 
@@ -408,4 +412,221 @@ class QuantizedGatedMLP(torch.nn.Module):
         activation = _activation_of(module.act_fn)
         new = cls(1, 1, activation=activation, bits=bits, generator=generator, device='meta', fused=fused)
         new.gate_proj, new.up_proj, new.down_proj = module.gate_proj, module.up_proj, module.down_proj
+        return new.train(module.training)
+
+
+# ---- the same MLP on the row blocks of a seed: x, gate and up kept as MX cells, all three weight gradients on the scaled matrix instruction -----------
+
+# the tensors one call rounds, in the order of their seeds: seed i is the call's ONE draw plus i.  No two share a seed: two tensors of one role
+# ('kept': x, gate, up, product; 'grad': the others) with one seed would meet the same uniforms at equal cells
+MX_SEEDS = ('x', 'gate', 'up', 'd_gate', 'd_up', 'product', 'grad_output')
+
+
+def _mx_seeds(base):
+    """The seeds of a call from its one draw -> ``at(i, j)``: seeds i .. j - 1 as ints, or as a view of ``len(MX_SEEDS)`` words on the device while
+    the stream is being captured (``base`` is then the device word of ``linear._sketch_seed``)"""
+    if isinstance(base, torch.Tensor):
+        words = base + torch.arange(len(MX_SEEDS), dtype=torch.int64, device=base.device)
+        return lambda i, j: words[i:j]
+    return lambda i, j: tuple((base + k) & 0xffffffffffffffff for k in range(i, j))
+
+
+def _mx_keep(t: torch.Tensor, seed, format: str, role: str = 'kept') -> torch.Tensor:
+    """the 2-D ``t`` as the row blocks of ``seed`` on its device: the kernel where it takes ``t``, the host form otherwise"""
+    seed = seed[0] if isinstance(seed, tuple) else seed
+    if linear._kernels_take(t):
+        return cabi_x.mx_pack(linear._unit_stride(t), seed, format, role)
+    return cabi_x.mx_pack_host(t, seed, format, role).to(t.device)
+
+
+def _mx_decoded(packed: torch.Tensor, shape, format: str, dtype: torch.dtype) -> torch.Tensor:
+    if packed.device.type == 'cuda' and dtype in DTYPES:
+        return cabi_x.mx_unpack(packed, *shape, format, dtype)
+    return cabi_x.mx_unpack_host(packed.cpu(), *shape, format).to(device=packed.device, dtype=dtype)
+
+
+class _GatedMLPMX(torch.autograd.Function):
+    """``down(act(gate(x)) * up(x))`` as ONE node (:func:`gated_mlp_mx`).  Kept for backward: ``x`` as the row blocks of a seed (one uint8 buffer; only
+    while ``gate_weight`` or ``up_weight`` requires grad), ``gate`` and ``up`` as two such buffers (one uint8 tensor on the kernels, two on the composed
+    route; only while something other than ``down_bias`` requires grad) and the three weights.  On ``ctx``: ``seeds`` (:func:`_mx_seeds`; None where
+    nothing is rounded), ``served`` (whether the kernels of fewbit_mxglu.hip and ``mx_wgrad`` run).  Nothing of the shape of ``x``, ``gate``, ``up`` or
+    ``y`` in a float dtype."""
+
+    @staticmethod
+    def forward(ctx, x, gate_weight, up_weight, down_weight, gate_bias, up_bias, down_bias, activation: str, format: str, generator):
+        needs = ctx.needs_input_grad
+        ctx.activation, ctx.format, ctx.input_shape, ctx.input_dtype = activation, format, tuple(x.shape), x.dtype
+        ctx.autocast = linear._autocast_seen(x.device.type)
+        keeps_x, keeps_gate_up = needs[1] or needs[2], any(needs[:6])
+        flat = x.detach().reshape(-1, x.shape[-1])
+        gate, up = F.linear(x, gate_weight, gate_bias), F.linear(x, up_weight, up_bias)
+        lead, width = gate.shape[:-1], gate.shape[-1]
+        gate, up = gate.reshape(-1, width), up.reshape(-1, width)
+        rows, hidden = flat.shape
+        ctx.flat_shape, ctx.width = (rows, hidden), width
+        ctx.served = (_kernel_applies(gate, up) and flat.dtype == gate.dtype and gate.dtype != torch.float32 and linear._kernels_take(flat)
+                      and cabi_x.mx_wgrad_serves(rows, hidden, width, format) and cabi_x.mx_wgrad_serves(rows, width, hidden, format))
+        ctx.seeds = None
+        if keeps_gate_up:
+            on_device = linear._kernels_take(gate)
+            ctx.seeds = _mx_seeds(linear._sketch_seed(generator, gate.device) if on_device else
+                                  linear._draw_seed(generator if generator is None or generator.device.type == 'cpu' else None))
+        x_kept = (_mx_keep(flat, ctx.seeds(0, 1), format), ) if keeps_x else ()
+        if ctx.served:
+            # (with nothing to keep: the product kernel of the other form, which writes the same y)
+            y, state = (cabi_x.mx_glu_forward(gate, up, activation, format, ctx.seeds(1, 3)) if keeps_gate_up
+                        else cabi_x.glu_forward(gate, up, activation, keep=False))
+            gate_up_kept = (state, ) if keeps_gate_up else ()
+        else:
+            gate_up_kept = (_mx_keep(gate, ctx.seeds(1, 2), format), _mx_keep(up, ctx.seeds(2, 3), format)) if keeps_gate_up else ()
+            y = _torch_product(gate, up, activation)
+        ctx.layout = (len(x_kept), len(gate_up_kept))
+        ctx.save_for_backward(*x_kept, *gate_up_kept, gate_weight, up_weight, down_weight)
+        return F.linear(y.view(*lead, width), down_weight, down_bias)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        with linear._autocast_as(ctx.autocast):
+            return _GatedMLPMX._backward(ctx, linear._dense_rows(grad_output))
+
+    @staticmethod
+    def _backward(ctx, grad_output):
+        saved = ctx.saved_tensors                           # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
+        of_x, of_gate_up = ctx.layout
+        x_kept, gate_up_kept, (gate_weight, up_weight, down_weight) = saved[:of_x], saved[of_x:of_x + of_gate_up], saved[of_x + of_gate_up:]
+        needs, format, seeds = ctx.needs_input_grad, ctx.format, ctx.seeds
+        (rows, hidden), width = ctx.flat_shape, ctx.width
+        G = grad_output.reshape(-1, grad_output.shape[-1])
+        if ctx.served and G.dtype not in DTYPES:
+            G = G.float()
+        # d_gate and d_up as tensors (dx and the bias sums read them), then the operands of the three weight gradients
+        want = (needs[0] or needs[4], needs[0] or needs[5], needs[1], needs[2], needs[3])
+        gy = G @ down_weight if any(want[:4]) else None
+        d_gate = d_up = by_gate = by_up = by_down = None
+        if ctx.served and any(want):
+            if gy is None:
+                gy = torch.zeros((rows, width), dtype=G.dtype, device=G.device)      # (only d down_weight is wanted: y^ does not depend on gy)
+            elif gy.dtype not in DTYPES:
+                gy = gy.float()
+            if want[0] and want[1]:
+                # [d_gate | d_up] in ONE buffer: the launch writes its two halves where they lie (row stride 2 width)
+                both = torch.empty((rows, 2 * width), dtype=gy.dtype, device=gy.device)
+                d_gate, d_up = both[:, :width], both[:, width:]
+            d_gate, d_up, gate_cells, up_cells, product_cells = cabi_x.mx_glu_backward(gy, gate_up_kept[0], ctx.activation, format, seeds(3, 6), want, d_gate, d_up)
+            to = lambda weight: weight.dtype if weight.dtype in DTYPES else torch.float32
+            if needs[1]:
+                by_gate = cabi_x.mx_wgrad(gate_cells, x_kept[0], rows, hidden, width, format, to(gate_weight))
+            if needs[2]:
+                by_up = cabi_x.mx_wgrad(up_cells, x_kept[0], rows, hidden, width, format, to(up_weight))
+            if needs[3]:
+                # (the one stand-alone pack of backward: grad_output, of the hidden width)
+                by_down = cabi_x.mx_wgrad(_mx_keep(G, seeds(6, 7), 'fp8', 'grad'), product_cells, rows, width, hidden, format, to(down_weight))
+        elif any(want):
+            # the composed route: the same mathematics from mx_pack / mx_unpack (or their host forms) and torch's formulas, with the EXACT gradients --
+            # nothing is rounded to fp8 here
+            work = G.dtype if gy is None else gy.dtype
+            g, u = (_mx_decoded(t, (rows, width), format, work) for t in gate_up_kept)
+            nan = torch.full((), float('nan'), dtype=work, device=G.device)
+            poisoned = torch.isnan(g) | torch.isnan(u)
+            act = F.silu(g) if ctx.activation == 'silu' else F.gelu(g)
+            if want[0] or want[2]:
+                d_gate = torch.where(poisoned, nan, gy * u * _slope(g, ctx.activation))
+            if want[1] or want[3]:
+                d_up = torch.where(poisoned, nan, gy * act)
+            if needs[1] or needs[2]:
+                x_hat = _mx_decoded(x_kept[0], (rows, hidden), format, work)
+                by_gate, by_up = d_gate.T @ x_hat if needs[1] else None, d_up.T @ x_hat if needs[2] else None
+            if needs[3]:
+                product = torch.where(poisoned, nan, act * u)
+                by_down = G.T @ _mx_decoded(_mx_keep(product, seeds(5, 6), format), (rows, width), format, G.dtype)
+        grads = [None] * 10
+        for i, (by, weight) in enumerate(((by_gate, gate_weight), (by_up, up_weight), (by_down, down_weight)), start=1):
+            if needs[i]:
+                grads[i] = by.to(weight.dtype)
+        if needs[4]:
+            grads[4] = d_gate.sum(dim=0)
+        if needs[5]:
+            grads[5] = d_up.sum(dim=0)
+        if needs[6]:
+            grads[6] = G.sum(dim=0)
+        if needs[0]:
+            # (two products into one sum: the weights are never concatenated)
+            grads[0] = torch.addmm(d_gate @ gate_weight, d_up, up_weight).view(ctx.input_shape).to(ctx.input_dtype)
+        return tuple(grads)
+
+
+def gated_mlp_mx(x: torch.Tensor, gate_weight: torch.Tensor, up_weight: torch.Tensor, down_weight: torch.Tensor,
+                 gate_bias: Optional[torch.Tensor] = None, up_bias: Optional[torch.Tensor] = None, down_bias: Optional[torch.Tensor] = None,
+                 activation: str = 'silu', format: str = 'fp6', generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """``F.linear(act(F.linear(x, gate_weight, gate_bias)) * F.linear(x, up_weight, up_bias), down_weight, down_bias)``, the gated MLP of the Llama
+    family, as ONE node that keeps ``x``, ``gate`` and ``up`` as MXFP4 (``format='fp4'``) or MXFP6 (``'fp6'``) cells down their columns
+    (:func:`linear_mx` keeps its input so) and nothing of the product: per token of H = 4096, I = 11008 in bf16, 0.2656 (fp4) or 0.3906 (fp6) of the
+    bytes of ``x``, ``gate`` and ``up``, where torch keeps those three, ``act(gate)`` and the product.
+
+    * Forward: ``x^ = mx_pack(x)``, the two projections of torch, ONE launch (``cabi_x.mx_glu_forward``) that writes ``y`` -- the bytes of the product
+      kernel of :func:`gated_mlp_quantized` -- and both inputs as cells, the down projection of torch.
+    * Backward: ``gy = G @ down_weight``; ONE launch (``cabi_x.mx_glu_backward``) decodes ``g^``, ``u^``, writes ``d_gate`` and ``d_up`` and, while it
+      holds them, the same two as fp8 cells and ``y^ = act(g^) * u^`` as cells only; then ``d gate_weight = mx_wgrad(d_gate cells, x^)``,
+      ``d up_weight = mx_wgrad(d_up cells, x^)``, ``d down_weight = mx_wgrad(mx_pack(G, 'fp8'), y^ cells)``: all three on the scaled matrix instruction,
+      nothing decoded.  ``dx = d_gate @ gate_weight + d_up @ up_weight`` and the bias gradients (column sums) use the unrounded ``d_gate``, ``d_up``, ``G``.
+    * What is rounded twice: ``y^`` is rebuilt from the rounded ``g^``, ``u^`` and then rounded into cells; ``d_gate`` and ``d_up`` are formed from
+      ``g^``, ``u^`` and then rounded to fp8 cells for the weight gradients.  Every rounding is unbiased given its input, but ``act`` is not linear:
+      ``d_gate``, ``d_up`` and ``d down_weight`` carry the bias of second order in the step that :func:`gated_mlp_quantized` states for the integer form.
+    * Seeds: ONE draw from ``linear._sketch_seed`` per call (none where only ``down_bias`` requires grad); the seven rounded tensors (``MX_SEEDS``)
+      take it plus 0 .. 6, so no two tensors share a seed.  While the stream is being captured the draw is a device word and so are the seven.
+    * Served on the kernels: fp16 / bf16 GPU tensors whose hidden and intermediate widths are multiples of 32 (``cabi_x.mx_wgrad_serves``) while
+      ``linear.use_native_sketch()`` is on.  Every other call -- host tensors, fp32, float64, other widths -- composes the same mathematics from
+      ``mx_pack`` / ``mx_unpack`` or their host forms and torch's formulas with the EXACT gradients (no fp8 rounding), as :func:`linear_mx` does.
+    * Only what a requested gradient can need is kept or written.  Grad mode off, or nothing that requires grad: the plain forward of
+      :func:`gated_mlp_quantized` -- no seed is drawn, nothing is kept, the same bytes.
+    * Backward runs under the autocast state the forward saw; not differentiable twice; inside ``torch.utils.checkpoint`` ``generator`` must be a
+      default one (``None`` included)."""
+    linear._check_mx_format(format)
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation should be 'silu' or 'gelu', but got {activation!r}.")
+    tensors = (x, gate_weight, up_weight, down_weight, gate_bias, up_bias, down_bias)
+    if not kept.trains(*tensors) or x.numel() == 0:
+        if x.numel() == 0:
+            return F.linear(_torch_product(F.linear(x, gate_weight, gate_bias), F.linear(x, up_weight, up_bias), activation), down_weight, down_bias)
+        return _plain_gated_mlp(*(None if t is None else t.detach() for t in tensors), activation)
+    return _GatedMLPMX.apply(*tensors, activation, format, generator)
+
+
+class MXGatedMLP(torch.nn.Module):
+    r"""``down_proj(act(gate_proj(x)) * up_proj(x))`` as ONE node that keeps ``x``, ``gate`` and ``up`` as MXFP4 / MXFP6 cells and forms all three weight
+    gradients on the scaled matrix instruction of gfx950 (:func:`gated_mlp_mx`).  The projections are plain ``nn.Linear`` layers named as in the Llama
+    family.  Parameters: ``in_features``, ``intermediate``, ``bias`` (default False), ``activation`` (``'silu'`` or ``'gelu'``), ``format`` (``'fp4'`` or
+    ``'fp6'``, the default), ``generator``, ``device``, ``dtype``.  In ``eval()`` mode gradients that are asked for are torch's exact ones.
+
+        >>> swap = lambda m, path: fewbit.MXGatedMLP.from_mlp(m, format='fp6') if type(m).__name__.endswith('MLP') else m
+        >>> model = fewbit.map_module(model, swap)
+    """
+
+    def __init__(self, in_features: int, intermediate: int, bias: bool = False, activation: str = 'silu', format: str = 'fp6',
+                 generator: Optional[torch.Generator] = None, device=None, dtype=None) -> None:
+        linear._check_mx_format(format)
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation should be 'silu' or 'gelu', but got {activation!r}.")
+        super().__init__()
+        self.activation, self.format, self.generator = activation, format, generator
+        self.gate_proj = torch.nn.Linear(in_features, intermediate, bias, device, dtype)
+        self.up_proj = torch.nn.Linear(in_features, intermediate, bias, device, dtype)
+        self.down_proj = torch.nn.Linear(intermediate, in_features, bias, device, dtype)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        gate, up, down = self.gate_proj, self.up_proj, self.down_proj
+        if kept.exact_in_eval(self, x, *self.parameters()):
+            return down(_torch_product(gate(x), up(x), self.activation))
+        return gated_mlp_mx(x, gate.weight, up.weight, down.weight, gate.bias, up.bias, down.bias, self.activation, self.format, self.generator)
+
+    def extra_repr(self) -> str:
+        return f'activation={self.activation!r}, format={self.format!r}'
+
+    @classmethod
+    def from_mlp(cls, module: torch.nn.Module, format: str = 'fp6', generator: Optional[torch.Generator] = None) -> 'MXGatedMLP':
+        """An ``MXGatedMLP`` that SHARES the three projections of ``module`` and reads its ``act_fn``, exactly as ``QuantizedGatedMLP.from_mlp`` does"""
+        shared = QuantizedGatedMLP.from_mlp(module)
+        new = cls(1, 1, activation=shared.glu.activation, format=format, generator=generator, device='meta')
+        new.gate_proj, new.up_proj, new.down_proj = shared.gate_proj, shared.up_proj, shared.down_proj
         return new.train(module.training)

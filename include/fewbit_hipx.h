@@ -54,7 +54,9 @@ extern "C" {
  * So was the weight gradient from the packed form (fewbit_hipx_quant_wgrad_workspace, _quant_wgrad): inside revision 2, recognised by the
  * presence of the symbols.
  * So were the row blocks of a seed (fewbit_hipx_mx_bytes, _mx_pack_host, _mx_unpack_host, _mx_pack, _mx_unpack, _mx_wgrad_workspace, _mx_wgrad):
- * inside revision 2, recognised by the presence of the symbols. */
+ * inside revision 2, recognised by the presence of the symbols.
+ * So were the gate and the up as row blocks (fewbit_hipx_mx_glu_state_bytes, _mx_glu_forward, _mx_glu_backward): inside revision 2, recognised by the
+ * presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -689,6 +691,34 @@ int fewbit_hipx_mx_unpack(const uint8_t *packed, size_t packed_bytes, size_t row
 size_t fewbit_hipx_mx_wgrad_workspace(size_t rows, size_t in_features, size_t out_features, int format);
 int fewbit_hipx_mx_wgrad(const uint8_t *grad, size_t grad_bytes, const uint8_t *kept, size_t kept_bytes, int format, size_t rows, size_t in_features,
                          size_t out_features, int out_dtype, void *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The gate and the up as row blocks: the product of a gated MLP, y = act(gate) * up, whose two inputs are kept as the row blocks of two seeds, and its
+ * backward, which hands all three weight gradients of the MLP to fewbit_hipx_mx_wgrad (fewbit_amd/csrc/fewbit_mxglu.hip).  Nothing new is defined:
+ * every buffer below is bit for bit what fewbit_hipx_mx_pack writes from the named tensor, and every value is that of the gate and the up of a seed.
+ *   state     two buffers of `format` (4 or 6), role 0: fewbit_hipx_mx_pack(gate, seed_gate) at byte 0 and fewbit_hipx_mx_pack(up, seed_up) at
+ *             fewbit_hipx_mx_glu_state_bytes / 2, which is fewbit_hipx_mx_bytes filled up to a multiple of 16 (the filling is left alone).
+ * fewbit_hipx_mx_glu_forward: ONE launch.  gate, up, y: rows x width of `dtype`, unit stride along the width, row strides ld_* >= width (the halves of one
+ * [gate | up] tensor as they lie), aligned to their element; y has the bytes of fewbit_hipx_glu_forward.  state: 16-byte aligned.
+ * fewbit_hipx_mx_glu_backward: ONE launch.  g^, u^: the decodes of the state.  d_up = round(gy * act(g^)), d_gate = round((gy * u^) * act'(g^)),
+ * y^ = round(act(g^) * u^), each in fp32 and rounded once to `dtype`, the expressions of fewbit_hipx_glu_backward_product.  Written: d_gate and d_up
+ * (row strides ld_*), and three buffers of rows x width, 16-byte aligned, of fewbit_hipx_mx_bytes bytes each:
+ *   d_gate_cells   = fewbit_hipx_mx_pack(d_gate, format 8, role 1, seed_dgate)          d_up_cells = the same of d_up with seed_dup
+ *   product_cells  = fewbit_hipx_mx_pack(y^, `format`, role 0, seed_product); y^ itself is never written
+ * Any of the five outputs may be NULL: it is not written.  A state cell with scale byte 0xFF of EITHER input makes d_gate, d_up and y^ NaN on its 32
+ * rows of that column, and the cells written from them are poisoned by the rule of the pack.
+ * seed_device: NULL, or the seeds in device memory in the order of the seed arguments (two words forward, three backward; 8-byte aligned), read
+ * when the kernel runs.  Five tensors are rounded and no two of them may share a seed: two of one role would meet the same uniforms at equal cells.
+ * Refused before anything is launched (FEWBIT_ERR_INVALID_ARGUMENT): an unknown dtype or activation, a format other than 4 and 6, a misaligned seed
+ * word, width > 2^23, rows * width > 2^36, null gate, up, y, gy or state, ld < width, misaligned pointers, a state that is too small.  rows * width
+ * = 0: FEWBIT_OK, nothing is launched.  No atomics, no workspace: the same arguments give the same bytes; every call can be captured. */
+size_t fewbit_hipx_mx_glu_state_bytes(size_t rows, size_t width, int format);
+int fewbit_hipx_mx_glu_forward(int dtype, int act, const void *gate, size_t ld_gate, const void *up, size_t ld_up, size_t rows, size_t width, int format,
+                               uint64_t seed_gate, uint64_t seed_up, const uint64_t *seed_device, void *y, size_t ld_y, uint8_t *state, size_t state_bytes,
+                               void *stream);
+int fewbit_hipx_mx_glu_backward(int dtype, int act, const void *gy, size_t ld_gy, const uint8_t *state, size_t state_bytes, size_t rows, size_t width, int format,
+                                uint64_t seed_dgate, uint64_t seed_dup, uint64_t seed_product, const uint64_t *seed_device, void *d_gate, size_t ld_dgate,
+                                void *d_up, size_t ld_dup, uint8_t *d_gate_cells, uint8_t *d_up_cells, uint8_t *product_cells, void *stream);
 
 #ifdef __cplusplus
 }

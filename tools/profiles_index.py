@@ -74,6 +74,8 @@ ROWS = [
     ('quant_wgrad_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2903 device functions before / after fewbit_qgemm.hip was added as a unit of its own (16 new), and the registers and instruction counts of the new kernels', f'{E} 8.31'),
     ('mx_linear_bench.json', 'tools/mx_linear_bench.py: cabi_x.mx_wgrad alone, with and without the pack of G, beside torch.mm, mx_unpack + mm, quant_unpack + mm and quant_wgrad at 4 bits; cabi_x.mx_pack against its byte floor; MXLinear forward + backward beside nn.Linear and QuantizedLinear(bits=4); bytes saved, the allocator peak over one backward and the weight-gradient error at 16384 rows, 768 -> 3072, 3072 -> 768 and 4096 -> 11008, bf16 and fp16', f'{E} 8.32'),
     ('mx_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2919 device functions before / after fewbit_mx.hip was added as a unit of its own (27 new), and the registers and instruction counts of the new kernels', f'{E} 8.32'),
+    ('mx_gated_mlp_bench.json', 'tools/mx_gated_mlp_bench.py: MXGatedMLP (fp4, fp6) forward + backward beside QuantizedGatedMLP(fused=True, bits=4) and the torch MLP at 16384 tokens, 4096 -> 11008 and 768 -> 3072, bf16 and fp16: times, bytes saved per token, allocator peak over one backward, weight-gradient errors; cabi_x.mx_glu_forward / mx_glu_backward alone against their byte floors', f'{E} 8.33'),
+    ('mxglu_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2946 device functions before / after the activation text of fewbit_glu.hip moved to fewbit_gluact.h and fewbit_mxglu.hip was added as a unit of its own (24 new), and the registers and instruction counts of the new kernels', f'{E} 8.33'),
     ('unit_fold_speed*.txt','the launch-bound entry-point arms of quant_linear_bench, dropout_bench, glu_bench and layer_norm_bench from the parent and from the tree with fewbit_unit.h, alternating five times', f'{E} 8.27'),
     ('signed_transform_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1915 device functions before / after the signed pass A was added (228 new)', f'{E} 8.15'),
     ('moments_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1890 device functions before / after fewbit_moments.hip was added (13 new)', f'{E} 8.9'),
