@@ -3,7 +3,7 @@ of ``libfewbit_hip.so`` was frozen at version 5 (``cabi.SYMBOLS`` stays that lis
 torch's current stream on the tensors' device, no fallback -- a missing library or an unsupported shape raises.  What it binds: the sampled
 Fourier transform, the zero-extended and sign-flipped sampled transforms, the column sampling of LinearCRS, the moments of the variance
 estimator, the dropout of a seed, the packed form of a seed, the layer norm and the RMS norm that keep the normalized rows of a seed, and the
-same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed, with the backward that also rebuilds that product from the state, and the cross entropy of a row that keeps the logits as given and one float per row, and the weight gradient of a layer straight from the packed form of its input, and the row blocks of a seed: a matrix kept as MXFP4 / 6 / 8 cells down its columns and the weight gradient from two such buffers on the scaled matrix instruction, and the gated product whose gate and up are kept as such cells, with the backward that writes the operands of all three weight gradients.
+same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed, with the backward that also rebuilds that product from the state, and the cross entropy of a row that keeps the logits as given and one float per row, and the weight gradient of a layer straight from the packed form of its input, and the row blocks of a seed: a matrix kept as MXFP4 / 6 / 8 cells down its columns and the weight gradient from two such buffers on the scaled matrix instruction, and the gated product whose gate and up are kept as such cells, with the backward that writes the operands of all three weight gradients, and the RMS norm that keeps its normalized rows as such cells for its own backward and for the weight gradients of the linears behind it.
 """
 import ctypes
 import os
@@ -24,7 +24,8 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'glu_backward_product', 'CROSS_ENTROPY_MAX_GROUPS', 'cross_entropy_host', 'cross_entropy_forward', 'cross_entropy_backward',
            'CROSS_ENTROPY_STEP_STAGED_BYTES', 'cross_entropy_step', 'QUANT_WGRAD_TILE', 'quant_wgrad_serves', 'quant_wgrad_slices', 'quant_wgrad_workspace',
            'quant_wgrad', 'MX_FORMATS', 'MX_WGRAD_TILE', 'mx_bytes', 'mx_pack_host', 'mx_unpack_host', 'mx_pack', 'mx_unpack', 'mx_wgrad_serves', 'mx_wgrad_slices',
-           'mx_wgrad_workspace', 'mx_wgrad', 'mx_glu_state_bytes', 'mx_glu_forward', 'mx_glu_backward']
+           'mx_wgrad_workspace', 'mx_wgrad', 'mx_glu_state_bytes', 'mx_glu_forward', 'mx_glu_backward', 'MX_NORM_MAX_WIDTH', 'MX_NORM_PLAN_WIDTHS', 'MX_NORM_MAX_GRID',
+           'mx_rms_norm_workspace', 'mx_rms_norm_host', 'mx_rms_norm_backward_host', 'mx_rms_norm_forward', 'mx_rms_norm_backward']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -111,6 +112,10 @@ _SIGNATURES = {
     'fewbit_hipx_mx_glu_state_bytes': (_sz, [_sz, _sz, _i32]),
     'fewbit_hipx_mx_glu_forward': (_i32, [_i32, _i32, _vp, _sz, _vp, _sz, _sz, _sz, _i32, _u64, _u64, _vp, _vp, _sz, _vp, _sz, _vp]),
     'fewbit_hipx_mx_glu_backward': (_i32, [_i32, _i32, _vp, _sz, _vp, _sz, _sz, _sz, _i32, _u64, _u64, _u64, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    # the normalized rows as row blocks: inside revision 2 as well, recognised by their symbols
+    'fewbit_hipx_mx_rms_norm_workspace': (_sz, [_sz, _sz]),
+    'fewbit_hipx_mx_rms_norm_forward': (_i32, [_i32, _vp, _sz, _sz, _sz, _vp, ctypes.c_float, _i32, _u64, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_mx_rms_norm_backward': (_i32, [_i32, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _sz, _i32, _vp, _sz, _vp, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -1343,3 +1348,105 @@ def mx_glu_backward(gy: torch.Tensor, state: torch.Tensor, activation: str, form
         _check(lib().fewbit_hipx_mx_glu_backward(DTYPES[gy.dtype], act, gy.data_ptr(), ld_gy, state.data_ptr(), state.numel(), rows, width, MX_FORMATS[format], *values,
                                                  words, _ptr(d_gate), ld_dgate, _ptr(d_up), ld_dup, *(_ptr(t) for t in cells), _stream(stream, gy.device)))
     return (d_gate, d_up, *cells)
+
+
+# ---- the normalized rows as row blocks (fewbit_amd/csrc/fewbit_mxnorm.hip): the RMS norm whose x^ is ONE mx_pack buffer ---------------------------------
+MX_NORM_MAX_WIDTH = 8192
+MX_NORM_PLAN_WIDTHS = ()                        # the widths at which the forward kernel changes its plan: none, x is read again at every width
+MX_NORM_MAX_GRID = 512                          # workgroups of the backward kernel, rows of its workspace (kMaxGridBackward in fewbit_mxnorm.hip)
+
+
+def mx_rms_norm_workspace(rows: int, width: int) -> int:
+    """Bytes of scratch ``mx_rms_norm_backward`` needs for ``dgamma`` (the library's own answer): one fp32 row of ``width`` per workgroup, of which
+    there are ``min(ceil(rows / 32), MX_NORM_MAX_GRID)``; 0 for extents the kernels refuse.  Evaluated on the host; no GPU needed."""
+    if rows < 0 or width < 0:
+        return 0
+    return lib().fewbit_hipx_mx_rms_norm_workspace(rows, width)
+
+
+def _work_dtype(t: torch.Tensor) -> torch.dtype:
+    return torch.float64 if t.dtype == torch.float64 else torch.float32
+
+
+def mx_rms_norm_host(x: torch.Tensor, gamma: torch.Tensor, eps: float, format: str, seed: int, rstd: Optional[torch.Tensor] = None):
+    """``mx_rms_norm_forward`` evaluated with plain torch and ``mx_pack_host`` -> ``(y, cells, rstd)`` on the device of ``x``: ``rstd = 1 /
+    sqrt(mean(x^2) + eps)`` (or the given one: with the kernel's rstd, ``y`` and ``cells`` are the kernel's bytes), ``x^ = x * rstd`` in fp32,
+    ``y = x^ * gamma`` rounded once, ``cells = mx_pack_host(x^, seed, format, 'kept')``.  A float64 ``x`` is normalized in float64; its cells
+    are those of the fp32 rounding of x^.  No GPU needed."""
+    work = x.detach().to(_work_dtype(x))
+    if rstd is None:
+        rstd = 1.0 / torch.sqrt(work.pow(2).sum(dim=1) / x.shape[1] + eps)
+    xhat = work * rstd.to(work.dtype)[:, None]
+    y = (xhat * gamma.detach().to(work.dtype)).to(x.dtype)
+    return y, mx_pack_host(xhat, seed, format, 'kept').to(x.device), rstd.to(torch.float32)
+
+
+def mx_rms_norm_backward_host(gy: torch.Tensor, cells: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, format: str):
+    """``mx_rms_norm_backward`` evaluated with plain torch and ``mx_unpack_host`` -> ``(dx, dgamma)``: ``dx`` in the dtype of ``gy``, ``dgamma``
+    in fp32 (float64 for a float64 ``gy``).  No GPU needed."""
+    rows, width = gy.shape
+    work = gy.detach().to(_work_dtype(gy))
+    xq = mx_unpack_host(cells.cpu(), rows, width, format).to(device=gy.device, dtype=work.dtype)
+    ghat = work * gamma.detach().to(work.dtype)
+    c = (ghat * xq).sum(dim=1, keepdim=True) / width
+    dx = rstd.to(work.dtype)[:, None] * (ghat - xq * c)
+    return dx.to(gy.dtype), (work * xq).sum(dim=0)
+
+
+def _mx_norm_call(name: str, like: torch.Tensor, gamma: torch.Tensor, format: str):
+    rows, width, ld = _glu_rows(like, name)
+    if format not in ('fp4', 'fp6'):
+        raise FewbitHipError(f"{name}: format must be 'fp4' or 'fp6' (got {format!r})")
+    if rows < 1 or not 1 <= width <= MX_NORM_MAX_WIDTH:
+        raise FewbitHipError(f'{name}: no kernel for {rows} x {width} elements (rows >= 1, width 1 .. {MX_NORM_MAX_WIDTH})')
+    if _norm_vector(gamma, like, 'gamma') is None:
+        raise FewbitHipError(f'{name}: gamma is needed')
+    return rows, width, ld, _mx_size(name, rows, width, format)
+
+
+def mx_rms_norm_forward(x: torch.Tensor, gamma: torch.Tensor, eps: float, format: str, seed, y: Optional[torch.Tensor] = None,
+                        rstd: Optional[torch.Tensor] = None, cells: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """The RMS norm of the rows of ``x`` (2-D, fp32 / fp16 / bf16, unit stride along the width, any row stride, 1 .. 8192 wide) in ONE launch ->
+    ``(y, cells, rstd)``: ``y = x^ * gamma`` rounded once to the dtype of ``x``; ``rstd`` one fp32 per row; ``cells`` the FP32 ``x^ = x * rstd``
+    as ``mx_bytes(rows, width, format)`` bytes, bit for bit ``mx_pack_host(x.float() * rstd[:, None], seed, format, 'kept')`` -- the buffer
+    ``mx_rms_norm_backward`` and ``mx_wgrad`` read.  ``seed``: an int, or a one-element int64 tensor on the device of ``x`` that is read when the
+    kernel runs.  ``y`` (any row stride), ``rstd``, ``cells``: buffers to write into."""
+    rows, width, ld_x, need = _mx_norm_call('mx_rms_norm_forward', x, gamma, format)
+    value, word, others = _seed_arguments(seed)
+    with _on(x.device):
+        y = _mx_glu_out(y, x, 'y')
+        ld_y = _glu_rows(y, 'y')[2]
+        rstd = _norm_out(rstd, (rows, ), torch.float32, x.device, 'rstd')
+        cells = _state_to_write(cells, True, need, x.device, 'cells')
+        _same_device(x, gamma, y, rstd, cells, *others)
+        _check(lib().fewbit_hipx_mx_rms_norm_forward(DTYPES[x.dtype], x.data_ptr(), ld_x, rows, width, gamma.data_ptr(), float(eps), MX_FORMATS[format], value,
+                                                     word, y.data_ptr(), ld_y, rstd.data_ptr(), cells.data_ptr(), cells.numel(), _stream(stream, x.device)))
+    return y, cells, rstd
+
+
+def mx_rms_norm_backward(gy: torch.Tensor, cells: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, format: str, want=(True, True),
+                         dx: Optional[torch.Tensor] = None, dgamma: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                         stream: Optional[int] = None):
+    """The gradients of ``mx_rms_norm_forward`` from its cells, its rstd and ``gy`` (2-D, any row stride) -> ``(dx, dgamma)``: with ``x^q`` the
+    decode of the cells and ``g^ = gy * gamma``, ``dx = rstd * (g^ - x^q * mean(g^ * x^q))`` in the dtype of ``gy`` and ``dgamma = sum_r gy * x^q``
+    as fp32 of ``width`` elements -- ``rms_norm_backward``'s expressions.  Where ``want`` is False the output is None and is neither computed nor
+    written.  One launch, and a small second one for ``dgamma``; every sum in a fixed order: the same arguments give the same bits.  ``dx`` (any
+    row stride), ``dgamma``, ``workspace`` (uint8, at least ``mx_rms_norm_workspace`` bytes): buffers to use."""
+    rows, width, ld_gy, need = _mx_norm_call('mx_rms_norm_backward', gy, gamma, format)
+    want_dx, want_dgamma = (bool(w) for w in want)
+    _state_to_read(cells, need, 'cells')
+    if rstd.dtype != torch.float32 or rstd.numel() != rows or not rstd.is_contiguous():
+        raise FewbitHipError(f'rstd must be a contiguous float32 tensor of {rows} elements')
+    with _on(gy.device):
+        dx = _mx_glu_out(dx, gy, 'dx') if want_dx else None
+        ld_dx = 0 if dx is None else _glu_rows(dx, 'dx')[2]
+        dgamma = _norm_out(dgamma, (width, ), torch.float32, gy.device, 'dgamma') if want_dgamma else None
+        if want_dgamma and workspace is None:
+            workspace = torch.empty(mx_rms_norm_workspace(rows, width), dtype=torch.uint8, device=gy.device)
+        elif workspace is not None and (workspace.dtype != torch.uint8 or not workspace.is_contiguous()):
+            raise FewbitHipError('workspace must be a contiguous uint8 tensor')
+        _same_device(gy, cells, rstd, gamma, *(t for t in (dx, dgamma, workspace) if t is not None))
+        _check(lib().fewbit_hipx_mx_rms_norm_backward(DTYPES[gy.dtype], gy.data_ptr(), ld_gy, cells.data_ptr(), cells.numel(), rstd.data_ptr(), gamma.data_ptr(),
+                                                      rows, width, MX_FORMATS[format], _ptr(dx), ld_dx, _ptr(dgamma), _ptr(workspace),
+                                                      0 if workspace is None else workspace.numel(), _stream(stream, gy.device)))
+    return dx, dgamma

@@ -1,0 +1,450 @@
+// fewbit_mxnorm.hip -- the RMS norm in front of linear layers that keep their input as OCP-MX cells: the norm keeps its normalized rows x^ as ONE
+// mx_pack buffer and one fp32 rstd per row, which serve its own backward and, because y = x^ * gamma, every weight gradient behind it
+// (dW = (G^T x^) * gamma by columns, mx_wgrad on the cells as they lie), on gfx950; part of the companion library libfewbit_hipx.so
+// (include/fewbit_hipx.h, "The normalized rows as row blocks"):
+//
+//     mx_rms_norm_forward    x, gamma -> y, rstd and the cells of the FP32 x^ = x * rstd                                               ONE launch
+//     mx_rms_norm_backward   gy, the cells, rstd, gamma -> dx, and the workgroups' column sums of gy * x^q -> dgamma      ONE launch and a small one
+//
+// The format is fewbit_mxdef.h's (scale_of_amax, octet_words, octet_codes, decode, used as they are); the formulas are those of fewbit_norm.hip's RMS
+// kind.  What is new is the walk.  The norm kernels hold a row in the registers of one row of lanes; a cell needs 32 rows of a column together.  So:
+//   workgroup  1024 lanes own ONE row block b (32 rows) and walk on by the grid's width.  Ownership of whole row blocks is what lets one kernel
+//              know a row's statistic before it rounds the row, with no flag or atomic between workgroups.
+//   forward A  wave w takes rows w and w + 16 of the block: a lane sums the squares of its 8-element pieces (piece l, l + 64, ..) in index order,
+//              then the DPP / readlane order of norm::row_sum<64>.  rstd -> LDS and the output.
+//   forward B  the block's 32 x 64 tiles, FOUR in flight, each on its own group of 256 lanes, with the two roles of mx::pack_kernel:
+//              load role   lane u: row u / 8, columns 8 (u % 8) .. + 7: x again (from L2 by now: 32 * width * itemsize <= 512 KiB a workgroup),
+//                          x^ = x * rstd, y = round(x^ * gamma) stored, the fp32 x^ into the group's LDS tile.
+//              round role  lane u: column u % 64, row octet u / 64 (wave-uniform): eight values down the column, the four octets' amax meet
+//                          through LDS, one Philox call, eight codes -> the LDS image of the cells.
+//              store       whole cells in 8-byte pieces, consecutive lanes consecutive pieces; the scale bytes from the first wave of a group.
+//              3 barriers a round of four tiles.  x is NOT held in LDS between the phases at any width: ONE plan, no thresholds
+//              (cabi_x.MX_NORM_PLAN_WIDTHS is empty).  32 rows fit 160 KiB of LDS only up to 1280 elements of fp32; a block that small is read the
+//              second time from L2 anyway, and the LDS it would take costs the second workgroup of a compute unit.
+//   backward A (only where dx is wanted) the tiles in the same groups: cell images and scale bytes come into LDS by 8-byte pieces, alternating
+//              between two images so that ONE barrier a round suffices; the lane decodes its eight x^q (mxglu's code_at + mx::decode), loads gy and
+//              gamma and adds g^ x^q to its row's partial sum in index order.  The partial sums of a row meet in a fixed order: the eight lanes by
+//              DPP (^1, ^2, the other quad), then the four groups in ascending order through LDS.  c = sum / width.
+//   backward B the tiles again: dx = round(rstd * (g^ - x^q c)) stored; gy * x^q -> the group's LDS tile, whose 32 rows one wave adds in ascending
+//              row order into the workgroup's row of the workspace [workgroups][width] (the same lane owns a column at every row block the
+//              workgroup walks: a plain read-add-write of its own).  2 barriers a round.
+//   column sums  a second launch adds the workgroups' rows in ascending order, associated by sixteenths -> dgamma.  At most kMaxGridBackward workgroups.
+// Rows beyond `rows` count as +0 (their rstd is taken as 0), columns beyond `width` are neither rounded into a stored cell nor stored.
+// Roofline class: memory (forward reads x once from memory and once from L2, writes y and 0.27 / 0.39 of it in cells).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "fewbit_hipx.h"
+#include "fewbit_mxdef.h"
+
+#pragma clang fp contract(off)
+
+namespace fewbit_hip {
+namespace quant {
+namespace mxnorm {
+
+constexpr int kRows = mx::kCellRows, kOctets = mx::kOctets, kTileCols = 64;                   // the tile of mx::pack_kernel
+constexpr int kGroupThreads = 256, kGroups = 4, kThreads = kGroups * kGroupThreads, kWaves = kThreads / 64;
+constexpr size_t kMaxWidth = 8192;
+constexpr size_t kMaxGridForward = size_t{1} << 16, kMaxGridBackward = 512;
+constexpr int kMirrorSixteen = 0x140;       // row_mirror
+
+inline bool known_shape(size_t rows, size_t width) { return rows >= 1 && width >= 1 && width <= kMaxWidth && rows <= kMaxCount / width; }
+inline size_t backward_grid(size_t rows) { const size_t blocks = mx::blocks_of(rows); return blocks < kMaxGridBackward ? blocks : kMaxGridBackward; }
+inline size_t workspace_of(size_t rows, size_t width) { return known_shape(rows, width) ? backward_grid(rows) * width * sizeof(float) : 0; }
+
+struct ForwardArgs {
+    const void *x;
+    size_t ld_x, rows, width;
+    const void *gamma;
+    float eps;
+    Key key;
+    const Key *device;                      // nullptr, or the key in device memory
+    void *y;
+    size_t ld_y;
+    float *rstd;
+    uint8_t *cells;
+    size_t blocks;
+    bool vec_x, vec_y, vec_gamma;
+};
+struct BackwardArgs {
+    const void *gy;
+    size_t ld_gy;
+    const uint8_t *cells;
+    const float *rstd;
+    const void *gamma;
+    size_t rows, width;
+    void *dx;                               // may be absent, and so may partials: what is absent is not written
+    size_t ld_dx;
+    float *partials;
+    size_t blocks;
+    bool vec_gy, vec_dx, vec_gamma;
+};
+
+__device__ __forceinline__ float sqrt_rn(float v) { return __fsqrt_rn(v); }
+template <int CTRL> __device__ __forceinline__ float sum_step(float v) {
+    return add_rn(v, __builtin_bit_cast(float, lane_move<CTRL>(__builtin_bit_cast(int, v))));
+}
+__device__ __forceinline__ float lane_value(float v, int lane) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane)); }
+// the sum of v over the eight lanes of a row of a tile (lane ^ 1, lane ^ 2, the other quad), the same bits in each of them
+__device__ __forceinline__ float eight_sum(float v) {
+    v = sum_step<kSwapPairs>(v);
+    v = sum_step<kSwapHalves>(v);
+    return sum_step<kMirrorEight>(v);
+}
+// the sum of v over a wave, the order of norm::row_sum<64>
+__device__ __forceinline__ float wave_sum(float v) {
+    v = sum_step<kMirrorSixteen>(eight_sum(v));
+    return add_rn(add_rn(lane_value(v, 0), lane_value(v, 16)), add_rn(lane_value(v, 32), lane_value(v, 48)));
+}
+
+// ---- the load role: eight consecutive columns of one row (the text of mxglu::load_piece / store_piece) -------------------------------------------
+template <int DT>
+__device__ __forceinline__ void load_piece(const typename Elem<DT>::type *src, size_t ld, bool vec, size_t r, size_t col, size_t rows, size_t width,
+                                           typename Elem<DT>::type (&raw)[kBlock]) {
+    using T = typename Elem<DT>::type;
+    if (vec && r < rows && col + kBlock <= width) {
+        load8<DT>(src + r * ld + col, raw);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kBlock; ++k) raw[k] = r < rows && col + k < width ? src[r * ld + col + k] : T{0};
+    }
+}
+template <int DT>
+__device__ __forceinline__ void store_piece(typename Elem<DT>::type *dst, size_t ld, bool vec, size_t r, size_t col, size_t rows, size_t width,
+                                            const typename Elem<DT>::type (&raw)[kBlock]) {
+    if (r >= rows) return;
+    if (vec && col + kBlock <= width) {
+        store8<DT>(dst + r * ld + col, raw);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kBlock; ++k)
+            if (col + k < width) dst[r * ld + col + k] = raw[k];
+    }
+}
+
+// ---- the rounding role of mx::pack_kernel on one LDS tile of fp32 bits, in its two halves: the caller's barrier lies between them ---------------
+__device__ __forceinline__ void column_amax(const uint32_t (&tile)[kRows][kTileCols], int c, int o, uint32_t (&v)[kBlock], uint32_t (&amax_s)[kOctets][kTileCols]) {
+    uint32_t amax = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock; ++k) {
+        v[k] = tile[kBlock * o + k][c];
+        const uint32_t m = v[k] & 0x7fffffffu;
+        amax = m > amax ? m : amax;
+    }
+    amax_s[o][c] = amax;
+}
+// -> the octet's codes in the LDS image of the tile's cells, the scale byte of column `col` of block b into `out` (the buffer)
+template <int FMT>
+__device__ __forceinline__ void column_codes(const uint32_t (&v)[kBlock], const uint32_t (&amax_s)[kOctets][kTileCols], int c, int o, size_t b, size_t col, size_t width,
+                                             Key key, uint64_t *image, uint8_t *out) {
+    uint32_t amax = 0;
+#pragma unroll
+    for (int k = 0; k < kOctets; ++k) amax = amax_s[k][c] > amax ? amax_s[k][c] : amax;
+    const bool bad = amax >= 0x7f800000u;
+    const int e = bad ? 128 : mx::scale_of_amax<FMT>(amax);
+    uint32_t w[4];
+    mx::octet_words(b, col, width, o, mx::kKeptDomain, key, w);
+    const uint64_t word = mx::octet_codes<FMT>(v, e, bad, w);
+    if constexpr (FMT == 4) reinterpret_cast<uint32_t *>(image)[kOctets * c + o] = static_cast<uint32_t>(word);
+    else {
+        uint16_t *at = reinterpret_cast<uint16_t *>(image) + 12 * c + 3 * o;
+        at[0] = static_cast<uint16_t>(word), at[1] = static_cast<uint16_t>(word >> 16), at[2] = static_cast<uint16_t>(word >> 32);
+    }
+    if (o == 0 && col < width) out[b * width + col] = static_cast<uint8_t>(e + 127);
+}
+// the tile's cells, `cols` of them, between the buffer and LDS: 8-byte pieces, consecutive lanes consecutive pieces (u: the lane of the group)
+template <int FMT> __device__ __forceinline__ void store_cells(const uint64_t *image, uint8_t *codes, size_t b, size_t j0, size_t width, size_t cols, int u) {
+    if (8 * static_cast<size_t>(u) < cols * mx::cell_bytes(FMT)) reinterpret_cast<uint64_t *>(codes + (b * width + j0) * mx::cell_bytes(FMT))[u] = image[u];
+}
+template <int FMT> __device__ __forceinline__ void load_cells(uint64_t *image, const uint8_t *codes, size_t b, size_t j0, size_t width, size_t cols, int u) {
+    if (8 * static_cast<size_t>(u) < cols * mx::cell_bytes(FMT)) image[u] = reinterpret_cast<const uint64_t *>(codes + (b * width + j0) * mx::cell_bytes(FMT))[u];
+}
+// element `row` of the cell of tile column `c` in an LDS image, as mx::unpack_kernel reads it
+template <int FMT> __device__ __forceinline__ uint32_t code_at(const uint64_t *image, int c, int row) {
+    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(image);
+    const size_t bit = mx::cell_bytes(FMT) * 8 * c + FMT * row;
+    uint32_t two = bytes[bit / 8];
+    if (bit % 8 + FMT > 8) two |= static_cast<uint32_t>(bytes[bit / 8 + 1]) << 8;                  // (fp6 only, and never for a cell's last code)
+    return (two >> (bit % 8)) & ((1u << FMT) - 1u);
+}
+
+template <int DT, int FMT>
+__global__ __launch_bounds__(kThreads) void forward_kernel(ForwardArgs a) {
+    using T = typename Elem<DT>::type;
+    constexpr size_t kCell = mx::cell_bytes(FMT);
+    __shared__ float rstd_s[kRows];
+    __shared__ uint32_t tile[kGroups][kRows][kTileCols];                        // the fp32 bits of x^
+    __shared__ uint32_t amax_s[kGroups][kOctets][kTileCols];
+    __shared__ uint64_t image[kGroups][kTileCols * kCell / 8];
+    const T *x = static_cast<const T *>(a.x), *gamma = static_cast<const T *>(a.gamma);
+    T *y = static_cast<T *>(a.y);
+    Key key = a.key;
+    if (a.device != nullptr) key = *a.device;
+    const size_t rows = a.rows, width = a.width;
+    uint8_t *codes = a.cells + mx::codes_offset(rows, width);
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int grp = t >> 8, u = t & (kGroupThreads - 1);
+    const int lrow = u >> 3, lcol = 8 * (u & 7);          // the load role
+    const int c = u & (kTileCols - 1), o = u >> 6;        // the rounding role: column c, row octet o
+    const size_t across = (width + kTileCols - 1) / kTileCols, rounds = (across + kGroups - 1) / kGroups, pieces = (width + kBlock - 1) / kBlock;
+    const float count = static_cast<float>(width);
+    for (size_t b = blockIdx.x; b < a.blocks; b += gridDim.x) {
+        // ---- phase A: the statistic of the block's rows, a wave per row ----
+        for (int lr = wave; lr < kRows; lr += kWaves) {
+            const size_t r = kRows * b + lr;
+            float s = 0.0f;
+            if (r < rows) {
+                for (size_t p = lane; p < pieces; p += 64) {
+                    T raw[kBlock];
+                    load_piece<DT>(x, a.ld_x, a.vec_x, r, kBlock * p, rows, width, raw);
+#pragma unroll
+                    for (int k = 0; k < kBlock; ++k) {
+                        const float v = float_of_bits(widen<DT>(raw[k]));
+                        s = add_rn(s, mul_rn(v, v));                            // (a missing element: +0)
+                    }
+                }
+            }
+            s = wave_sum(s);
+            const float rstd = div_rn(1.0f, sqrt_rn(add_rn(div_rn(s, count), a.eps)));
+            if (lane == 0) {
+                rstd_s[lr] = r < rows ? rstd : 0.0f;
+                if (r < rows) a.rstd[r] = rstd;
+            }
+        }
+        __syncthreads();
+        // ---- phase B: the block's tiles, four in flight ----
+        for (size_t round = 0; round < rounds; ++round) {
+            const size_t tl = round * kGroups + grp, j0 = tl * kTileCols;
+            const bool have = tl < across;                                      // (the same for every lane of a group; the barriers are outside)
+            const size_t cols = !have ? 0 : width - j0 < static_cast<size_t>(kTileCols) ? width - j0 : kTileCols;
+            if (have) {
+                const size_t r = kRows * b + lrow, col = j0 + lcol;
+                T rx[kBlock], rg[kBlock], ry[kBlock];
+                load_piece<DT>(x, a.ld_x, a.vec_x, r, col, rows, width, rx);
+                load_piece<DT>(gamma, 0, a.vec_gamma, 0, col, 1, width, rg);
+                const float rstd = rstd_s[lrow];
+#pragma unroll
+                for (int k = 0; k < kBlock; ++k) {
+                    const float xhat = mul_rn(float_of_bits(widen<DT>(rx[k])), rstd);
+                    ry[k] = narrow<DT>(mul_rn(xhat, float_of_bits(widen<DT>(rg[k]))));
+                    tile[grp][lrow][lcol + k] = bits_of_float(xhat);
+                }
+                store_piece<DT>(y, a.ld_y, a.vec_y, r, col, rows, width, ry);
+            }
+            __syncthreads();
+            uint32_t v[kBlock];
+            if (have) column_amax(tile[grp], c, o, v, amax_s[grp]);
+            __syncthreads();
+            if (have) column_codes<FMT>(v, amax_s[grp], c, o, b, j0 + c, width, key, image[grp], a.cells);
+            __syncthreads();
+            store_cells<FMT>(image[grp], codes, b, j0, width, cols, u);
+            // (the next round writes `tile` behind this round's second barrier's reads, `amax_s` and `image` behind its third, and the next block
+            // writes rstd_s behind the reads in front of this round's first: no barrier here)
+        }
+    }
+}
+
+template <int DT, int FMT>
+__global__ __launch_bounds__(kThreads) void backward_kernel(BackwardArgs a) {
+    using T = typename Elem<DT>::type;
+    constexpr size_t kCell = mx::cell_bytes(FMT);
+    __shared__ uint64_t image[2][kGroups][kTileCols * kCell / 8];
+    __shared__ uint8_t scale_s[2][kGroups][kTileCols];
+    __shared__ float tile[kGroups][kRows][kTileCols];                           // gy * x^q
+    __shared__ float part_s[kGroups][kRows], c_s[kRows];
+    const T *gy = static_cast<const T *>(a.gy), *gamma = static_cast<const T *>(a.gamma);
+    T *dx = static_cast<T *>(a.dx);
+    const size_t rows = a.rows, width = a.width;
+    const uint8_t *codes = a.cells + mx::codes_offset(rows, width);
+    float *mine = a.partials != nullptr ? a.partials + static_cast<size_t>(blockIdx.x) * width : nullptr;
+    const int t = threadIdx.x;
+    const int grp = t >> 8, u = t & (kGroupThreads - 1);
+    const int lrow = u >> 3, lcol = 8 * (u & 7);          // the load role
+    const size_t across = (width + kTileCols - 1) / kTileCols, rounds = (across + kGroups - 1) / kGroups;
+    const float count = static_cast<float>(width);
+    // the eight x^q, gy and g^ of the lane's piece of tile (b, j0) from the LDS image `par`
+    auto piece = [&](int par, size_t b, size_t j0, size_t cols, float (&xq)[kBlock], float (&up)[kBlock], float (&gh)[kBlock]) {
+        const size_t r = kRows * b + lrow, col = j0 + lcol;
+        T rgy[kBlock], rg[kBlock];
+        load_piece<DT>(gy, a.ld_gy, a.vec_gy, r, col, rows, width, rgy);
+        load_piece<DT>(gamma, 0, a.vec_gamma, 0, col, 1, width, rg);
+#pragma unroll
+        for (int k = 0; k < kBlock; ++k) {
+            const bool inside = r < rows && lcol + k < static_cast<int>(cols);
+            xq[k] = inside ? mx::decode<FMT>(code_at<FMT>(image[par][grp], lcol + k, lrow), scale_s[par][grp][lcol + k]) : 0.0f;
+            up[k] = float_of_bits(widen<DT>(rgy[k]));                           // (outside: +0)
+            gh[k] = mul_rn(up[k], float_of_bits(widen<DT>(rg[k])));
+        }
+    };
+    bool first = true;                                                          // of this workgroup's row blocks: its row of the workspace is written, not added to
+    for (size_t b = blockIdx.x; b < a.blocks; b += gridDim.x, first = false) {
+        if (dx != nullptr) {
+            // ---- phase A: c = sum_j(g^ x^q) / width of the block's rows ----
+            float s = 0.0f;
+            for (size_t round = 0; round < rounds; ++round) {
+                const size_t tl = round * kGroups + grp, j0 = tl * kTileCols;
+                const bool have = tl < across;
+                const size_t cols = !have ? 0 : width - j0 < static_cast<size_t>(kTileCols) ? width - j0 : kTileCols;
+                const int par = static_cast<int>(round & 1);
+                load_cells<FMT>(image[par][grp], codes, b, j0, width, cols, u);
+                if (static_cast<size_t>(u) < cols) scale_s[par][grp][u] = a.cells[b * width + j0 + u];
+                __syncthreads();                       // (round i + 1 writes the other image, last read in round i - 1: in front of this barrier)
+                if (have) {
+                    float xq[kBlock], up[kBlock], gh[kBlock];
+                    piece(par, b, j0, cols, xq, up, gh);
+#pragma unroll
+                    for (int k = 0; k < kBlock; ++k) s = add_rn(s, mul_rn(gh[k], xq[k]));
+                }
+            }
+            s = eight_sum(s);
+            if ((u & 7) == 0) part_s[grp][lrow] = s;
+            __syncthreads();
+            if (t < kRows) c_s[t] = div_rn(add_rn(add_rn(add_rn(part_s[0][t], part_s[1][t]), part_s[2][t]), part_s[3][t]), count);
+            __syncthreads();
+        }
+        // ---- phase B: dx, and the column sums of gy * x^q down the block ----
+        const size_t r = kRows * b + lrow;
+        const float rstd = dx != nullptr && r < rows ? a.rstd[r] : 0.0f, cr = dx != nullptr ? c_s[lrow] : 0.0f;
+        for (size_t round = 0; round < rounds; ++round) {
+            const size_t tl = round * kGroups + grp, j0 = tl * kTileCols;
+            const bool have = tl < across;
+            const size_t cols = !have ? 0 : width - j0 < static_cast<size_t>(kTileCols) ? width - j0 : kTileCols;
+            load_cells<FMT>(image[0][grp], codes, b, j0, width, cols, u);
+            if (static_cast<size_t>(u) < cols) scale_s[0][grp][u] = a.cells[b * width + j0 + u];
+            __syncthreads();
+            if (have) {
+                float xq[kBlock], up[kBlock], gh[kBlock];
+                piece(0, b, j0, cols, xq, up, gh);
+                if (dx != nullptr) {
+                    T rdx[kBlock];
+#pragma unroll
+                    for (int k = 0; k < kBlock; ++k) rdx[k] = narrow<DT>(mul_rn(rstd, sub_rn(gh[k], mul_rn(xq[k], cr))));
+                    store_piece<DT>(dx, a.ld_dx, a.vec_dx, r, j0 + lcol, rows, width, rdx);
+                }
+                if (mine != nullptr) {
+#pragma unroll
+                    for (int k = 0; k < kBlock; ++k) tile[grp][lrow][lcol + k] = mul_rn(up[k], xq[k]);
+                }
+            }
+            __syncthreads();
+            if (mine != nullptr && u < kTileCols && static_cast<size_t>(u) < cols) {
+                float sum = tile[grp][0][u];
+#pragma unroll 8
+                for (int k = 1; k < kRows; ++k) sum = add_rn(sum, tile[grp][k][u]);
+                mine[j0 + u] = first ? sum : add_rn(mine[j0 + u], sum);
+            }
+            // (the next round writes the image behind this round's second barrier, and `tile` behind its own first: no barrier here)
+        }
+    }
+}
+
+// dgamma[c] = the workgroups' sums of column c.  A workgroup of 16 waves takes 64 columns: wave w adds the rows [w per, (w + 1) per) of the workspace in
+// ascending order, per = ceil(parts / 16), and the waves' results are added in ascending order -- the rows in ascending order, associated by
+// sixteenths, so that 16 loads of a column are in flight and not one.
+__global__ __launch_bounds__(kThreads) void column_sums_kernel(const float *__restrict__ partials, size_t parts, size_t width, float *__restrict__ dgamma) {
+    __shared__ float waves[kWaves][kTileCols];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t c = static_cast<size_t>(blockIdx.x) * kTileCols + lane;
+    const size_t per = (parts + kWaves - 1) / kWaves, from = wave * per, to = from + per < parts ? from + per : parts;
+    float sum = 0.0f;
+    if (c < width && from < parts) {
+        sum = partials[from * width + c];
+#pragma unroll 8
+        for (size_t p = from + 1; p < to; ++p) sum = add_rn(sum, partials[p * width + c]);
+    }
+    waves[wave][lane] = sum;
+    __syncthreads();
+    if (wave == 0 && c < width) {
+        float total = waves[0][lane];
+        for (size_t w = 1; w < static_cast<size_t>(kWaves) && w * per < parts; ++w) total = add_rn(total, waves[w][lane]);
+        dgamma[c] = total;
+    }
+}
+
+// what both entry points refuse alike, in the order of mxglu::check_call
+inline int check_call(const char *name, int dtype, int format, const void *seed_device, size_t rows, size_t width) {
+    if (const int rc = check_dtype(name, dtype)) return rc;
+    if (format != 4 && format != 6) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: format = %d is not 4 (fp4) or 6 (fp6)", name, format);
+    if (const int rc = check_seed_word(name, seed_device)) return rc;
+    if (rows == 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: rows = 0", name);
+    if (width == 0 || width > kMaxWidth) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: width = %zu is not in 1 .. %zu", name, width, kMaxWidth);
+    if (rows > kMaxCount / width) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: rows * width = %zu * %zu is beyond 2^36", name, rows, width);
+    return FEWBIT_OK;
+}
+inline int check_aligned16(const char *name, const char *what, const void *p) {
+    return !misaligned(p, 16) ? FEWBIT_OK : fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: %s must be 16-byte aligned", name, what);
+}
+// whether 16-byte pieces serve a tensor (an absent one: they would)
+inline bool wide(const void *p, size_t ld, int dtype) { return !misaligned(p, 16) && ld * size_of(dtype) % 16 == 0; }
+
+template <class F> void pick_kernel(int dtype, int format, F &&f) {
+    pick_dtype(dtype, [&](auto dt) { pick<4, 6>(format, [&](auto fmt) { f(dt, fmt); }); });
+}
+
+}  // namespace mxnorm
+}  // namespace quant
+}  // namespace fewbit_hip
+
+using namespace fewbit_hip::quant;
+using fewbit_hip::sketch::key_of;
+
+extern "C" {
+
+size_t fewbit_hipx_mx_rms_norm_workspace(size_t rows, size_t width) { return mxnorm::workspace_of(rows, width); }
+
+int fewbit_hipx_mx_rms_norm_forward(int dtype, const void *x, size_t ld_x, size_t rows, size_t width, const void *gamma, float eps, int format, uint64_t seed,
+                                    const uint64_t *seed_device, void *y, size_t ld_y, float *rstd, uint8_t *cells, size_t cells_bytes, void *stream) {
+    using namespace mxnorm;
+    const char *name = "mx_rms_norm_forward";
+    if (const int rc = check_call(name, dtype, format, seed_device, rows, width)) return rc;
+    if (x == nullptr || gamma == nullptr || y == nullptr || rstd == nullptr || cells == nullptr) return refuse_null(name);
+    if (ld_x < width || ld_y < width)
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: a row stride ld (%zu, %zu) must be at least width = %zu", name, ld_x, ld_y, width);
+    const size_t item = size_of(dtype);
+    if (misaligned(x, item) || misaligned(y, item) || misaligned(gamma, item) || misaligned(rstd, sizeof(float)))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: x, y, gamma and rstd must be aligned to their element size", name);
+    if (const int rc = check_aligned16(name, "cells", cells)) return rc;
+    if (const int rc = check_bytes(name, "cells", cells_bytes, fewbit_hip::mx::bytes_of(rows, width, format))) return rc;
+    const size_t blocks = fewbit_hip::mx::blocks_of(rows);
+    const ForwardArgs a{x, ld_x, rows, width, gamma, eps, key_of(seed), reinterpret_cast<const Key *>(seed_device), y, ld_y, rstd, cells, blocks,
+                        wide(x, ld_x, dtype), wide(y, ld_y, dtype), wide(gamma, 0, dtype)};
+    const unsigned grid = static_cast<unsigned>(blocks < kMaxGridForward ? blocks : kMaxGridForward);
+    pick_kernel(dtype, format, [&](auto dt, auto fmt) {
+        hipLaunchKernelGGL((forward_kernel<dt(), fmt()>), dim3(grid), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    });
+    return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
+}
+
+int fewbit_hipx_mx_rms_norm_backward(int dtype, const void *gy, size_t ld_gy, const uint8_t *cells, size_t cells_bytes, const float *rstd, const void *gamma,
+                                     size_t rows, size_t width, int format, void *dx, size_t ld_dx, float *dgamma, void *workspace, size_t workspace_bytes,
+                                     void *stream) {
+    using namespace mxnorm;
+    const char *name = "mx_rms_norm_backward";
+    if (const int rc = check_call(name, dtype, format, nullptr, rows, width)) return rc;
+    if (gy == nullptr || cells == nullptr || rstd == nullptr || gamma == nullptr || (dgamma != nullptr && workspace == nullptr)) return refuse_null(name);
+    if (ld_gy < width || (dx != nullptr && ld_dx < width))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: a row stride ld (%zu, %zu) must be at least width = %zu", name, ld_gy, ld_dx, width);
+    const size_t item = size_of(dtype);
+    if (misaligned(gy, item) || misaligned(dx, item) || misaligned(gamma, item) || misaligned(rstd, sizeof(float)) || misaligned(dgamma, sizeof(float)) ||
+        misaligned(workspace, sizeof(float)))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: gy, dx, gamma, rstd, dgamma and the workspace must be aligned to their element size", name);
+    if (const int rc = check_aligned16(name, "cells", cells)) return rc;
+    if (const int rc = check_bytes(name, "cells", cells_bytes, fewbit_hip::mx::bytes_of(rows, width, format))) return rc;
+    if (dgamma != nullptr)
+        if (const int rc = check_bytes(name, "the workspace", workspace_bytes, workspace_of(rows, width))) return rc;
+    if (dx == nullptr && dgamma == nullptr) return FEWBIT_OK;
+    const size_t grid = backward_grid(rows);
+    const BackwardArgs a{gy, ld_gy, cells, rstd, gamma, rows, width, dx, ld_dx, dgamma != nullptr ? static_cast<float *>(workspace) : nullptr,
+                         fewbit_hip::mx::blocks_of(rows), wide(gy, ld_gy, dtype), wide(dx, ld_dx, dtype), wide(gamma, 0, dtype)};
+    pick_kernel(dtype, format, [&](auto dt, auto fmt) {
+        hipLaunchKernelGGL((backward_kernel<dt(), fmt()>), dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    });
+    if (dgamma != nullptr)
+        hipLaunchKernelGGL(column_sums_kernel, dim3(static_cast<unsigned>((width + kTileCols - 1) / kTileCols)), dim3(kThreads), 0,
+                           static_cast<hipStream_t>(stream), static_cast<const float *>(workspace), grid, width, dgamma);
+    return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
+}
+
+}  // extern "C"

@@ -57,7 +57,7 @@ from .cabi import DTYPES
 from .dropout import _check_p, dropout_add
 
 __all__ = ('layer_norm_quantized', 'QuantizedLayerNorm', 'rms_norm_quantized', 'QuantizedRMSNorm', 'dropout_add_layer_norm_quantized', 'DropoutAddLayerNorm',
-           'dropout_add_rms_norm_quantized', 'DropoutAddRMSNorm')
+           'dropout_add_rms_norm_quantized', 'DropoutAddRMSNorm', 'rms_norm_linear_mx', 'MXNormLinear')
 
 # Everything below takes the kind as ``centred``: True for the layer norm, False for the RMS norm (the un-centred statistic, backward without the mean
 # term, no beta: ``bias`` is None throughout).
@@ -488,3 +488,170 @@ class DropoutAddRMSNorm(_DropoutAddNorm, QuantizedRMSNorm):
                       generator: Optional[torch.Generator] = None) -> 'DropoutAddRMSNorm':
         """A ``DropoutAddRMSNorm`` that SHARES the weight of ``module`` (what :meth:`QuantizedRMSNorm.from_rms_norm` accepts)"""
         return super().from_rms_norm(module, bits, generator)._configure(p, prenorm)
+
+
+# ---- the RMS norm and the linears behind it on ONE set of MX cells: x^ kept once, for the norm's backward and for every weight gradient ------------------
+
+def _seed_plus(seed, k: int):
+    """seed + k of a call's one draw: an int, or a new device word while the stream is being captured"""
+    return seed + k if isinstance(seed, torch.Tensor) else (seed + k) & 0xffffffffffffffff
+
+
+def _fp32_product(g: torch.Tensor, xq: torch.Tensor) -> torch.Tensor:
+    """``g^T xq`` with fp32 sums that are not rounded to a 16-bit dtype on the way (the caller scales the columns first and rounds once)"""
+    if g.is_cuda and g.dtype != torch.float32:
+        with torch.autocast('cuda', enabled=False):
+            return torch.mm(g.T, xq, out_dtype=torch.float32)
+    return g.T @ xq
+
+
+class _RMSNormLinearMX(torch.autograd.Function):
+    """``tuple(F.linear(F.rms_norm(input, gamma), W_i, b_i))`` as ONE node (:func:`rms_norm_linear_mx`).  Kept for backward: ONE uint8 buffer of
+    ``cabi_x.mx_bytes(rows, width, format)`` bytes (the cells of the fp32 ``x^``), ``rstd`` (fp32 per row), gamma and the weights; ``y`` is not.  On
+    ``ctx``: the call's ONE seed draw (an int; a device word while the stream is being captured): seed + 0 rounds the cells, seed + 1 + i the fp8
+    pack of ``G_i``, so that no two roundings share a seed."""
+
+    @staticmethod
+    def forward(ctx, input, gamma, eps: float, format: str, generator, count: int, *parameters):
+        weights, biases = parameters[:count], parameters[count:]
+        flat = input.detach().reshape(-1, input.shape[-1])
+        ctx.format, ctx.flat_shape, ctx.input_shape, ctx.input_dtype, ctx.count = format, tuple(flat.shape), input.shape, input.dtype, count
+        ctx.has_bias = tuple(b is not None for b in biases)
+        ctx.autocast = linear._autocast_seen(input.device.type)
+        ctx.set_materialize_grads(False)
+        ctx.native = (linear._kernels_take(flat) and 1 <= flat.shape[1] <= cabi_x.MX_NORM_MAX_WIDTH and gamma.device == flat.device
+                      and gamma.dtype in DTYPES)
+        if ctx.native:
+            ctx.seed = linear._sketch_seed(generator, flat.device)
+            y, cells, rstd = cabi_x.mx_rms_norm_forward(linear._unit_stride(flat), _as(gamma, flat.dtype), eps, format, _seed_plus(ctx.seed, 0))
+        else:
+            ctx.seed = linear._draw_seed(generator if generator is None or generator.device.type == 'cpu' else None)
+            y, cells, rstd = cabi_x.mx_rms_norm_host(flat, gamma, eps, format, ctx.seed)
+        ctx.save_for_backward(cells, rstd, gamma, *weights)
+        y = y.view(input.shape)
+        return tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grad_outputs):
+        with linear._autocast_as(ctx.autocast):
+            return _RMSNormLinearMX._backward(ctx, grad_outputs)
+
+    @staticmethod
+    def _backward(ctx, grad_outputs):
+        cells, rstd, gamma, *weights = ctx.saved_tensors        # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
+        (rows, width), count, format, needs = ctx.flat_shape, ctx.count, ctx.format, ctx.needs_input_grad
+        grads = [None if g is None else linear._dense_rows(g).reshape(rows, -1) for g in grad_outputs]
+        grad_weights, grad_biases, gy, decoded = [None] * count, [None] * count, None, {}
+
+        def xq(dtype):                                          # the decode route: x^q ONCE per dtype, a transient of the input's size
+            if dtype not in decoded:
+                decoded[dtype] = (cabi_x.mx_unpack(cells, rows, width, format, dtype) if ctx.native else
+                                  cabi_x.mx_unpack_host(cells.cpu(), rows, width, format).to(device=cells.device, dtype=dtype))
+            return decoded[dtype]
+
+        for i, (g, weight) in enumerate(zip(grads, weights)):
+            if g is None:
+                continue
+            if needs[0] or needs[1]:                            # gy = sum_i G_i W_i in ONE buffer
+                w = weight if weight.dtype == g.dtype else weight.to(g.dtype)      # (under autocast: the cast autocast makes itself)
+                gy = g @ w if gy is None else gy.addmm_(g, w)
+            if needs[6 + i]:
+                fout = g.shape[1]
+                if ctx.native and g.dtype in DTYPES and cabi_x.mx_wgrad_serves(rows, width, fout, format):
+                    packed = cabi_x.mx_pack(linear._unit_stride(g), _seed_plus(ctx.seed, 1 + i), 'fp8', 'grad')
+                    product = cabi_x.mx_wgrad(packed, cells, rows, width, fout, format, torch.float32)
+                else:
+                    g2 = g if ctx.native and g.dtype in DTYPES else g.to(cabi_x._work_dtype(g))
+                    product = _fp32_product(g2, xq(g2.dtype))
+                # dW = (G^T x^q) * gamma by columns: the fp32 product is a transient of the WEIGHT's size, rounded once
+                grad_weights[i] = (product * gamma.detach().to(product.dtype)[None, :]).to(weight.dtype)
+            if ctx.has_bias[i] and needs[6 + count + i]:
+                grad_biases[i] = g.sum(dim=0)
+        grad_input = grad_gamma = None
+        if gy is not None:
+            want = (needs[0], needs[1])
+            if ctx.native:
+                gy = gy if gy.dtype in DTYPES else gy.float()
+                dx, dgamma = cabi_x.mx_rms_norm_backward(gy, cells, rstd, _as(gamma, gy.dtype), format, want)
+            else:
+                dx, dgamma = cabi_x.mx_rms_norm_backward_host(gy, cells, rstd, gamma, format)
+            grad_input = dx.to(ctx.input_dtype).view(ctx.input_shape) if want[0] else None
+            grad_gamma = dgamma.to(gamma.dtype).view(gamma.shape) if want[1] else None
+        return (grad_input, grad_gamma, None, None, None, None, *grad_weights, *grad_biases)
+
+
+def rms_norm_linear_mx(input: torch.Tensor, norm_weight: torch.Tensor, weights: Sequence[torch.Tensor], biases: Optional[Sequence[Optional[torch.Tensor]]] = None,
+                       eps: Optional[float] = None, format: str = 'fp4', generator: Optional[torch.Generator] = None) -> tuple:
+    """``tuple(F.linear(F.rms_norm(input, (width, ), norm_weight, eps), W, b) for W, b in zip(weights, biases))`` as ONE node that keeps ONE buffer for
+    all of it: the normalized rows ``x^ = x * rstd`` as MXFP4 (``format='fp4'``) or MXFP6 (``'fp6'``) cells down their columns, one fp32 ``rstd``
+    per row, ``norm_weight`` and the weights -- at width 4096 and fp4 2180 bytes a token, where ``QuantizedRMSNorm(bits=4)`` in front of three
+    ``MXLinear`` keeps 9088.  The output of the norm is not kept: because ``y = x^ * gamma``, ``dW_i = G_i^T y = (G_i^T x^) * gamma`` by columns.
+
+    * Forward: one kernel (``cabi_x.mx_rms_norm_forward``) writes ``y``, ``rstd`` and the cells of the FP32 ``x^``; then ``F.linear`` per weight.
+    * Backward: ``gy = sum_i G_i W_i`` in one buffer; ``dW_i`` from ``cabi_x.mx_wgrad`` on the fp8 cells of ``G_i`` and the kept cells (where
+      ``cabi_x.mx_wgrad_serves`` denies -- widths that are no multiples of 32 -- a decode and a GEMM), as fp32 sums that are scaled by
+      ``norm_weight`` and rounded once: an fp32 transient of the weight's size, not of the tokens'.  ``db_i`` is exact.  ``dx`` and the gradient
+      of ``norm_weight`` come from ``cabi_x.mx_rms_norm_backward`` on the decoded cells: ``E[x^q] = x^``, so ``E[dW_i] = G_i^T y``; ``dx`` is
+      not linear in ``x^q`` and carries a bias of second order in the rounding, as the quantized norms' does.
+    * Seeds: ONE draw from ``linear._sketch_seed`` per call; the cells take it plus 0, the fp8 rounding of ``G_i`` plus 1 + i.
+    * Widths above 8192, host tensors and float64 take the host route: the same definitions on ``cabi_x.mx_pack_host``.
+    * Grad mode off, or nothing that requires grad: plain ``F.rms_norm`` and ``F.linear``; no seed is drawn, nothing is kept.
+    * ``eps=None`` means ``torch.finfo(input.dtype).eps``, as in :func:`rms_norm_quantized`.  Under ``torch.autocast`` the norm runs in the input's
+      dtype and the linears as autocast casts them; backward runs under the state the forward saw."""
+    linear._check_mx_format(format)
+    weights = tuple(weights)
+    biases = (None, ) * len(weights) if biases is None else tuple(biases)
+    if len(biases) != len(weights) or not weights:
+        raise ValueError(f'{len(weights)} weights and {len(biases)} biases: one bias (or None) per weight is needed, and at least one weight')
+    eps = float(torch.finfo(input.dtype).eps if eps is None else eps)
+    if not kept.trains(input, norm_weight, *weights, *biases) or input.numel() == 0:
+        y = F.rms_norm(input, (input.shape[-1], ), norm_weight, eps)
+        return tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
+    return _RMSNormLinearMX.apply(input, norm_weight, eps, format, generator, len(weights), *weights, *biases)
+
+
+class MXNormLinear(torch.nn.Module):
+    r"""An RMS norm and the linear layers that read its output -- q / k / v behind the norm at the head of an attention block -- as one module that
+    keeps ONE set of MXFP4 / MXFP6 cells for all of them (:func:`rms_norm_linear_mx`); ``forward`` returns the tuple of the linears' outputs.  The
+    linears are plain ``nn.Linear`` layers in ``self.linears``, the norm's weight is ``self.weight``.  In ``eval()`` mode gradients are torch's exact
+    ones and nothing is kept.
+
+        >>> m = fewbit.MXNormLinear(64, [(64, 96, False), (64, 32, False), (64, 32, False)], eps=1e-6)
+        >>> q, k, v = m(torch.randn(128, 64))
+        >>> m = fewbit.MXNormLinear.from_modules(block.input_layernorm, [attn.q_proj, attn.k_proj, attn.v_proj], format='fp4')
+    """
+
+    def __init__(self, norm_weight_shape, linears, eps: Optional[float] = None, format: str = 'fp4', generator: Optional[torch.Generator] = None,
+                 device=None, dtype=None) -> None:
+        linear._check_mx_format(format)
+        super().__init__()
+        width = norm_weight_shape if isinstance(norm_weight_shape, int) else math.prod(norm_weight_shape)
+        self.weight = torch.nn.Parameter(torch.ones(width, device=device, dtype=dtype))
+        self.linears = torch.nn.ModuleList(torch.nn.Linear(fin, fout, bias, device=device, dtype=dtype) for fin, fout, bias in linears)
+        if any(m.in_features != width for m in self.linears):
+            raise ValueError(f'every linear must read the {width} features of the norm')
+        self.eps, self.format, self.generator = eps, format, generator
+
+    @classmethod
+    def from_modules(cls, norm: torch.nn.Module, linears: Sequence[torch.nn.Linear], format: str = 'fp4',
+                     generator: Optional[torch.Generator] = None) -> 'MXNormLinear':
+        """An ``MXNormLinear`` that SHARES the weight of ``norm`` -- a ``torch.nn.RMSNorm``, or any module with a 1-D ``weight`` and a float
+        ``variance_epsilon`` or ``eps`` -- and the given ``nn.Linear`` modules themselves"""
+        weight, eps = getattr(norm, 'weight', None), getattr(norm, 'variance_epsilon', getattr(norm, 'eps', None))
+        if not isinstance(weight, torch.Tensor) or weight.dim() != 1 or not (eps is None or isinstance(eps, float)):
+            raise TypeError(f'{type(norm).__name__} has no 1-D weight with a float variance_epsilon or eps')
+        new = cls(weight.numel(), [], eps, format, generator, device='meta')
+        new.weight, new.linears = weight, torch.nn.ModuleList(linears)
+        return new.train(norm.training)
+
+    def forward(self, input: torch.Tensor) -> tuple:
+        weights, biases = [m.weight for m in self.linears], [m.bias for m in self.linears]
+        if not self.training:
+            eps = float(torch.finfo(input.dtype).eps if self.eps is None else self.eps)
+            y = F.rms_norm(input, (input.shape[-1], ), self.weight, eps)
+            return tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
+        return rms_norm_linear_mx(input, self.weight, weights, biases, self.eps, self.format, self.generator)
+
+    def extra_repr(self) -> str:
+        return f'{self.weight.numel()}, eps={self.eps}, format={self.format}'

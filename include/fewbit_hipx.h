@@ -56,7 +56,9 @@ extern "C" {
  * So were the row blocks of a seed (fewbit_hipx_mx_bytes, _mx_pack_host, _mx_unpack_host, _mx_pack, _mx_unpack, _mx_wgrad_workspace, _mx_wgrad):
  * inside revision 2, recognised by the presence of the symbols.
  * So were the gate and the up as row blocks (fewbit_hipx_mx_glu_state_bytes, _mx_glu_forward, _mx_glu_backward): inside revision 2, recognised by the
- * presence of the symbols. */
+ * presence of the symbols.
+ * So were the normalized rows as row blocks (fewbit_hipx_mx_rms_norm_workspace, _mx_rms_norm_forward, _mx_rms_norm_backward): inside revision 2,
+ * recognised by the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -719,6 +721,34 @@ int fewbit_hipx_mx_glu_forward(int dtype, int act, const void *gate, size_t ld_g
 int fewbit_hipx_mx_glu_backward(int dtype, int act, const void *gy, size_t ld_gy, const uint8_t *state, size_t state_bytes, size_t rows, size_t width, int format,
                                 uint64_t seed_dgate, uint64_t seed_dup, uint64_t seed_product, const uint64_t *seed_device, void *d_gate, size_t ld_dgate,
                                 void *d_up, size_t ld_dup, uint8_t *d_gate_cells, uint8_t *d_up_cells, uint8_t *product_cells, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The normalized rows as row blocks: the RMS norm in front of linear layers whose weight gradients come from fewbit_hipx_mx_wgrad.  The norm keeps
+ * its normalized rows x^ as ONE fewbit_hipx_mx_pack buffer and one fp32 rstd per row; with y = x^ * gamma the input of the linears,
+ * dW = G^T y = (G^T x^) * gamma by columns, so that buffer serves the norm's own backward and every weight gradient behind it
+ * (fewbit_amd/csrc/fewbit_mxnorm.hip).  All arithmetic is fp32, each operation rounded once:
+ *   rstd[r]   = 1 / sqrt(sum_j x[r][j]^2 / width + eps), the sum in a fixed order of the kernel's own
+ *   x^[r][j]  = float(x[r][j]) * rstd[r]                          y[r][j] = round(x^[r][j] * float(gamma[j])) to `dtype`
+ *   cells     = fewbit_hipx_mx_pack of the FP32 matrix x^ (not of its rounding to `dtype`), `format` 4 or 6, role 0, the call's seed: given the
+ *               rstd that was written, the cells and y are functions of host fp32 arithmetic (fewbit_hipx_mx_pack_host of x * rstd)
+ * fewbit_hipx_mx_rms_norm_forward: ONE launch.  x, y: rows x width of `dtype`, unit stride along the width, row strides ld_* >= width, aligned to
+ * their element; gamma: width elements of `dtype`; rstd: rows floats; cells: fewbit_hipx_mx_bytes(rows, width, format) bytes, 16-byte aligned.
+ * fewbit_hipx_mx_rms_norm_backward: x^q the decode of the cells, g^ = gy * gamma, c[r] = sum_j(g^ x^q) / width:
+ *   dx[r][j] = round(rstd[r] * (g^[r][j] - x^q[r][j] * c[r]))     dgamma[j] = sum_r gy[r][j] * x^q[r][j]  (fp32, width floats)
+ * the expressions of fewbit_hipx_rms_norm_backward; every sum in a fixed order.  One launch, and a second small one where dgamma is wanted, which
+ * needs a workspace of fewbit_hipx_mx_rms_norm_workspace(rows, width) bytes (4-byte aligned; 0 for extents that are refused).  dx or dgamma may
+ * be NULL: it is not written.  A poisoned cell (scale byte 0xFF) makes dx NaN on its 32 rows and dgamma NaN in its column.
+ * seed_device: NULL, or the seed in device memory (8-byte aligned), read when the kernel runs.
+ * Refused before anything is launched (FEWBIT_ERR_INVALID_ARGUMENT): an unknown dtype, a format other than 4 and 6, a misaligned seed word,
+ * rows = 0, width outside 1 .. 8192, rows * width > 2^36, a null pointer other than dx and dgamma, ld < width, misaligned pointers, cells or a
+ * workspace that are too small.  No atomics and no flags between workgroups: the same arguments give the same bytes; every call can be captured. */
+size_t fewbit_hipx_mx_rms_norm_workspace(size_t rows, size_t width);
+int fewbit_hipx_mx_rms_norm_forward(int dtype, const void *x, size_t ld_x, size_t rows, size_t width, const void *gamma, float eps, int format,
+                                    uint64_t seed, const uint64_t *seed_device, void *y, size_t ld_y, float *rstd, uint8_t *cells, size_t cells_bytes,
+                                    void *stream);
+int fewbit_hipx_mx_rms_norm_backward(int dtype, const void *gy, size_t ld_gy, const uint8_t *cells, size_t cells_bytes, const float *rstd,
+                                     const void *gamma, size_t rows, size_t width, int format, void *dx, size_t ld_dx, float *dgamma, void *workspace,
+                                     size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -76,6 +76,8 @@ ROWS = [
     ('mx_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2919 device functions before / after fewbit_mx.hip was added as a unit of its own (27 new), and the registers and instruction counts of the new kernels', f'{E} 8.32'),
     ('mx_gated_mlp_bench.json', 'tools/mx_gated_mlp_bench.py: MXGatedMLP (fp4, fp6) forward + backward beside QuantizedGatedMLP(fused=True, bits=4) and the torch MLP at 16384 tokens, 4096 -> 11008 and 768 -> 3072, bf16 and fp16: times, bytes saved per token, allocator peak over one backward, weight-gradient errors; cabi_x.mx_glu_forward / mx_glu_backward alone against their byte floors', f'{E} 8.33'),
     ('mxglu_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2946 device functions before / after the activation text of fewbit_glu.hip moved to fewbit_gluact.h and fewbit_mxglu.hip was added as a unit of its own (24 new), and the registers and instruction counts of the new kernels', f'{E} 8.33'),
+    ('mx_norm_linear_bench.json', 'tools/mx_norm_linear_bench.py: MXNormLinear (fp4, fp6) forward + backward beside QuantizedRMSNorm(bits=4) + three MXLinear and torch RMSNorm + three nn.Linear at 16384 tokens, 4096 -> (4096, 1024, 1024) and 768 -> 3 x 768, bf16 and fp16: times, bytes saved per token, allocator peak over one backward; cabi_x.mx_rms_norm_forward / mx_rms_norm_backward alone against their byte floors and beside rms_norm_forward + mx_pack / rms_norm_backward', f'{E} 8.34'),
+    ('mxnorm_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2970 device functions before / after fewbit_mxnorm.hip was added as a unit of its own (13 new), and the registers, scratch and LDS of the new kernels', f'{E} 8.34'),
     ('unit_fold_speed*.txt','the launch-bound entry-point arms of quant_linear_bench, dropout_bench, glu_bench and layer_norm_bench from the parent and from the tree with fewbit_unit.h, alternating five times', f'{E} 8.27'),
     ('signed_transform_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1915 device functions before / after the signed pass A was added (228 new)', f'{E} 8.15'),
     ('moments_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1890 device functions before / after fewbit_moments.hip was added (13 new)', f'{E} 8.9'),
