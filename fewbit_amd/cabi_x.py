@@ -3,7 +3,7 @@ of ``libfewbit_hip.so`` was frozen at version 5 (``cabi.SYMBOLS`` stays that lis
 torch's current stream on the tensors' device, no fallback -- a missing library or an unsupported shape raises.  What it binds: the sampled
 Fourier transform, the zero-extended and sign-flipped sampled transforms, the column sampling of LinearCRS, the moments of the variance
 estimator, the dropout of a seed, the packed form of a seed, the layer norm and the RMS norm that keep the normalized rows of a seed, and the
-same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed, with the backward that also rebuilds that product from the state, and the cross entropy of a row that keeps the logits as given and one float per row, and the weight gradient of a layer straight from the packed form of its input, and the row blocks of a seed: a matrix kept as MXFP4 / 6 / 8 cells down its columns and the weight gradient from two such buffers on the scaled matrix instruction, and the gated product whose gate and up are kept as such cells, with the backward that writes the operands of all three weight gradients, and the RMS norm that keeps its normalized rows as such cells for its own backward and for the weight gradients of the linears behind it.
+same two norms with ``residual + dropout(x)`` fused in front, and the product of a gated MLP that keeps the gate and the up of a seed, with the backward that also rebuilds that product from the state, and the cross entropy of a row that keeps the logits as given and one float per row, and the weight gradient of a layer straight from the packed form of its input, and the row blocks of a seed: a matrix kept as MXFP4 / 6 / 8 cells down its columns and the weight gradient from two such buffers on the scaled matrix instruction, and the gated product whose gate and up are kept as such cells, with the backward that writes the operands of all three weight gradients, and the RMS norm that keeps its normalized rows as such cells for its own backward and for the weight gradients of the linears behind it, and the layer norm on the same form, whose weight gradients take one rank-one term in beta more.
 """
 import ctypes
 import os
@@ -25,7 +25,8 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'CROSS_ENTROPY_STEP_STAGED_BYTES', 'cross_entropy_step', 'QUANT_WGRAD_TILE', 'quant_wgrad_serves', 'quant_wgrad_slices', 'quant_wgrad_workspace',
            'quant_wgrad', 'MX_FORMATS', 'MX_WGRAD_TILE', 'mx_bytes', 'mx_pack_host', 'mx_unpack_host', 'mx_pack', 'mx_unpack', 'mx_wgrad_serves', 'mx_wgrad_slices',
            'mx_wgrad_workspace', 'mx_wgrad', 'mx_glu_state_bytes', 'mx_glu_forward', 'mx_glu_backward', 'MX_NORM_MAX_WIDTH', 'MX_NORM_PLAN_WIDTHS', 'MX_NORM_MAX_GRID',
-           'mx_rms_norm_workspace', 'mx_rms_norm_host', 'mx_rms_norm_backward_host', 'mx_rms_norm_forward', 'mx_rms_norm_backward']
+           'mx_rms_norm_workspace', 'mx_rms_norm_host', 'mx_rms_norm_backward_host', 'mx_rms_norm_forward', 'mx_rms_norm_backward',
+           'mx_layer_norm_workspace', 'mx_layer_norm_host', 'mx_layer_norm_backward_host', 'mx_layer_norm_forward', 'mx_layer_norm_backward']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -116,6 +117,10 @@ _SIGNATURES = {
     'fewbit_hipx_mx_rms_norm_workspace': (_sz, [_sz, _sz]),
     'fewbit_hipx_mx_rms_norm_forward': (_i32, [_i32, _vp, _sz, _sz, _sz, _vp, ctypes.c_float, _i32, _u64, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
     'fewbit_hipx_mx_rms_norm_backward': (_i32, [_i32, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _sz, _i32, _vp, _sz, _vp, _vp, _sz, _vp]),
+    # the centred normalized rows as row blocks: inside revision 2 as well, recognised by their symbols
+    'fewbit_hipx_mx_layer_norm_workspace': (_sz, [_sz, _sz]),
+    'fewbit_hipx_mx_layer_norm_forward': (_i32, [_i32, _vp, _sz, _sz, _sz, _vp, _vp, ctypes.c_float, _i32, _u64, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_mx_layer_norm_backward': (_i32, [_i32, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _sz, _i32, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -1450,3 +1455,97 @@ def mx_rms_norm_backward(gy: torch.Tensor, cells: torch.Tensor, rstd: torch.Tens
                                                       rows, width, MX_FORMATS[format], _ptr(dx), ld_dx, _ptr(dgamma), _ptr(workspace),
                                                       0 if workspace is None else workspace.numel(), _stream(stream, gy.device)))
     return dx, dgamma
+
+
+# ---- the centred normalized rows as row blocks (fewbit_amd/csrc/fewbit_mxlnorm.hip): the layer norm whose x^ is ONE mx_pack buffer ------------------------
+def mx_layer_norm_workspace(rows: int, width: int) -> int:
+    """Bytes of scratch ``mx_layer_norm_backward`` needs for ``dgamma`` and ``dbeta`` (the library's own answer): two fp32 rows of ``width`` per
+    workgroup, of which there are ``min(ceil(rows / 32), MX_NORM_MAX_GRID)``; 0 for extents the kernels refuse.  Evaluated on the host."""
+    if rows < 0 or width < 0:
+        return 0
+    return lib().fewbit_hipx_mx_layer_norm_workspace(rows, width)
+
+
+def mx_layer_norm_host(x: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor], eps: float, format: str, seed: int,
+                       mean: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None):
+    """``mx_layer_norm_forward`` evaluated with plain torch and ``mx_pack_host`` -> ``(y, cells, rstd, mean)`` on the device of ``x``: ``mean`` the
+    row mean and ``rstd = 1 / sqrt(mean((x - mean)^2) + eps)`` (or the given ones: with the kernel's, ``y`` and ``cells`` are the kernel's bytes),
+    ``x^ = (x - mean) * rstd`` in fp32, ``y = x^ * gamma + beta`` rounded once, ``cells = mx_pack_host(x^, seed, format, 'kept')``.  A float64
+    ``x`` is normalized in float64; its cells are those of the fp32 rounding of x^.  No GPU needed."""
+    work = x.detach().to(_work_dtype(x))
+    if mean is None:
+        mean = work.sum(dim=1) / x.shape[1]
+    centred = work - mean.to(work.dtype)[:, None]
+    if rstd is None:
+        rstd = 1.0 / torch.sqrt(centred.pow(2).sum(dim=1) / x.shape[1] + eps)
+    xhat = centred * rstd.to(work.dtype)[:, None]
+    y = xhat * gamma.detach().to(work.dtype)
+    if beta is not None:
+        y = y + beta.detach().to(work.dtype)
+    return y.to(x.dtype), mx_pack_host(xhat, seed, format, 'kept').to(x.device), rstd.to(torch.float32), mean.to(torch.float32)
+
+
+def mx_layer_norm_backward_host(gy: torch.Tensor, cells: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, format: str):
+    """``mx_layer_norm_backward`` evaluated with plain torch and ``mx_unpack_host`` -> ``(dx, dgamma, dbeta)``: ``dx`` in the dtype of ``gy``, the
+    two sums in fp32 (float64 for a float64 ``gy``).  No GPU needed."""
+    rows, width = gy.shape
+    work = gy.detach().to(_work_dtype(gy))
+    xq = mx_unpack_host(cells.cpu(), rows, width, format).to(device=gy.device, dtype=work.dtype)
+    ghat = work * gamma.detach().to(work.dtype)
+    c1, c2 = ghat.sum(dim=1, keepdim=True) / width, (ghat * xq).sum(dim=1, keepdim=True) / width
+    dx = rstd.to(work.dtype)[:, None] * ((ghat - c1) - xq * c2)
+    return dx.to(gy.dtype), (work * xq).sum(dim=0), work.sum(dim=0)
+
+
+def mx_layer_norm_forward(x: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor], eps: float, format: str, seed,
+                          y: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None,
+                          cells: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """The layer norm of the rows of ``x`` (2-D, fp32 / fp16 / bf16, unit stride along the width, any row stride, 1 .. 8192 wide) in ONE launch ->
+    ``(y, cells, rstd, mean)``: ``y = x^ * gamma + beta`` rounded once to the dtype of ``x`` (``beta=None``: nothing is added); ``mean`` and ``rstd``
+    one fp32 per row each (the two-pass variance); ``cells`` the FP32 ``x^ = (x - mean) * rstd`` as ``mx_bytes(rows, width, format)`` bytes, bit for
+    bit ``mx_pack_host((x.float() - mean[:, None]) * rstd[:, None], seed, format, 'kept')`` -- the buffer ``mx_layer_norm_backward`` and
+    ``mx_wgrad`` read.  ``seed``: an int, or a one-element int64 tensor on the device of ``x`` that is read when the kernel runs.  ``y`` (any row
+    stride), ``mean``, ``rstd``, ``cells``: buffers to write into."""
+    rows, width, ld_x, need = _mx_norm_call('mx_layer_norm_forward', x, gamma, format)
+    value, word, others = _seed_arguments(seed)
+    with _on(x.device):
+        y = _mx_glu_out(y, x, 'y')
+        ld_y = _glu_rows(y, 'y')[2]
+        mean = _norm_out(mean, (rows, ), torch.float32, x.device, 'mean')
+        rstd = _norm_out(rstd, (rows, ), torch.float32, x.device, 'rstd')
+        cells = _state_to_write(cells, True, need, x.device, 'cells')
+        _same_device(x, gamma, y, mean, rstd, cells, *others, *(() if beta is None else (beta, )))
+        _check(lib().fewbit_hipx_mx_layer_norm_forward(DTYPES[x.dtype], x.data_ptr(), ld_x, rows, width, gamma.data_ptr(), _norm_vector(beta, x, 'beta'),
+                                                       float(eps), MX_FORMATS[format], value, word, y.data_ptr(), ld_y, mean.data_ptr(), rstd.data_ptr(),
+                                                       cells.data_ptr(), cells.numel(), _stream(stream, x.device)))
+    return y, cells, rstd, mean
+
+
+def mx_layer_norm_backward(gy: torch.Tensor, cells: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, format: str, want=(True, True, True),
+                           dx: Optional[torch.Tensor] = None, dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None,
+                           workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """The gradients of ``mx_layer_norm_forward`` from its cells, its rstd and ``gy`` (2-D, any row stride) -> ``(dx, dgamma, dbeta)``: with ``x^q``
+    the decode of the cells and ``g^ = gy * gamma``, ``dx = rstd * ((g^ - mean(g^)) - x^q * mean(g^ * x^q))`` in the dtype of ``gy``, ``dgamma =
+    sum_r gy * x^q`` and ``dbeta = sum_r gy`` as fp32 of ``width`` elements -- ``layer_norm_backward``'s expressions.  Where ``want`` is False the
+    output is None and is neither computed nor written.  One launch, and a small second one for the two sums; every sum in a fixed order: the same
+    arguments give the same bits.  ``dx`` (any row stride), ``dgamma``, ``dbeta``, ``workspace`` (uint8, at least ``mx_layer_norm_workspace``
+    bytes): buffers to use."""
+    rows, width, ld_gy, need = _mx_norm_call('mx_layer_norm_backward', gy, gamma, format)
+    want_dx, want_dgamma, want_dbeta = (bool(w) for w in want)
+    _state_to_read(cells, need, 'cells')
+    if rstd.dtype != torch.float32 or rstd.numel() != rows or not rstd.is_contiguous():
+        raise FewbitHipError(f'rstd must be a contiguous float32 tensor of {rows} elements')
+    with _on(gy.device):
+        dx = _mx_glu_out(dx, gy, 'dx') if want_dx else None
+        ld_dx = 0 if dx is None else _glu_rows(dx, 'dx')[2]
+        dgamma = _norm_out(dgamma, (width, ), torch.float32, gy.device, 'dgamma') if want_dgamma else None
+        dbeta = _norm_out(dbeta, (width, ), torch.float32, gy.device, 'dbeta') if want_dbeta else None
+        if (want_dgamma or want_dbeta) and workspace is None:
+            workspace = torch.empty(mx_layer_norm_workspace(rows, width), dtype=torch.uint8, device=gy.device)
+        elif workspace is not None and (workspace.dtype != torch.uint8 or not workspace.is_contiguous()):
+            raise FewbitHipError('workspace must be a contiguous uint8 tensor')
+        _same_device(gy, cells, rstd, gamma, *(t for t in (dx, dgamma, dbeta, workspace) if t is not None))
+        _check(lib().fewbit_hipx_mx_layer_norm_backward(DTYPES[gy.dtype], gy.data_ptr(), ld_gy, cells.data_ptr(), cells.numel(), rstd.data_ptr(),
+                                                        gamma.data_ptr(), rows, width, MX_FORMATS[format], _ptr(dx), ld_dx, _ptr(dgamma), _ptr(dbeta),
+                                                        _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream(stream, gy.device)))
+    return dx, dgamma, dbeta

@@ -37,6 +37,7 @@
 
 #include "fewbit_hipx.h"
 #include "fewbit_mxdef.h"
+#include "fewbit_mxrows.h"
 
 #pragma clang fp contract(off)
 
@@ -44,14 +45,8 @@ namespace fewbit_hip {
 namespace quant {
 namespace mxnorm {
 
-constexpr int kRows = mx::kCellRows, kOctets = mx::kOctets, kTileCols = 64;                   // the tile of mx::pack_kernel
-constexpr int kGroupThreads = 256, kGroups = 4, kThreads = kGroups * kGroupThreads, kWaves = kThreads / 64;
-constexpr size_t kMaxWidth = 8192;
-constexpr size_t kMaxGridForward = size_t{1} << 16, kMaxGridBackward = 512;
-constexpr int kMirrorSixteen = 0x140;       // row_mirror
+using namespace mxrows;            // the geometry, the lane sums, the two roles of a tile and the refusals: fewbit_mxrows.h
 
-inline bool known_shape(size_t rows, size_t width) { return rows >= 1 && width >= 1 && width <= kMaxWidth && rows <= kMaxCount / width; }
-inline size_t backward_grid(size_t rows) { const size_t blocks = mx::blocks_of(rows); return blocks < kMaxGridBackward ? blocks : kMaxGridBackward; }
 inline size_t workspace_of(size_t rows, size_t width) { return known_shape(rows, width) ? backward_grid(rows) * width * sizeof(float) : 0; }
 
 struct ForwardArgs {
@@ -81,94 +76,6 @@ struct BackwardArgs {
     size_t blocks;
     bool vec_gy, vec_dx, vec_gamma;
 };
-
-__device__ __forceinline__ float sqrt_rn(float v) { return __fsqrt_rn(v); }
-template <int CTRL> __device__ __forceinline__ float sum_step(float v) {
-    return add_rn(v, __builtin_bit_cast(float, lane_move<CTRL>(__builtin_bit_cast(int, v))));
-}
-__device__ __forceinline__ float lane_value(float v, int lane) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane)); }
-// the sum of v over the eight lanes of a row of a tile (lane ^ 1, lane ^ 2, the other quad), the same bits in each of them
-__device__ __forceinline__ float eight_sum(float v) {
-    v = sum_step<kSwapPairs>(v);
-    v = sum_step<kSwapHalves>(v);
-    return sum_step<kMirrorEight>(v);
-}
-// the sum of v over a wave, the order of norm::row_sum<64>
-__device__ __forceinline__ float wave_sum(float v) {
-    v = sum_step<kMirrorSixteen>(eight_sum(v));
-    return add_rn(add_rn(lane_value(v, 0), lane_value(v, 16)), add_rn(lane_value(v, 32), lane_value(v, 48)));
-}
-
-// ---- the load role: eight consecutive columns of one row (the text of mxglu::load_piece / store_piece) -------------------------------------------
-template <int DT>
-__device__ __forceinline__ void load_piece(const typename Elem<DT>::type *src, size_t ld, bool vec, size_t r, size_t col, size_t rows, size_t width,
-                                           typename Elem<DT>::type (&raw)[kBlock]) {
-    using T = typename Elem<DT>::type;
-    if (vec && r < rows && col + kBlock <= width) {
-        load8<DT>(src + r * ld + col, raw);
-    } else {
-#pragma unroll
-        for (int k = 0; k < kBlock; ++k) raw[k] = r < rows && col + k < width ? src[r * ld + col + k] : T{0};
-    }
-}
-template <int DT>
-__device__ __forceinline__ void store_piece(typename Elem<DT>::type *dst, size_t ld, bool vec, size_t r, size_t col, size_t rows, size_t width,
-                                            const typename Elem<DT>::type (&raw)[kBlock]) {
-    if (r >= rows) return;
-    if (vec && col + kBlock <= width) {
-        store8<DT>(dst + r * ld + col, raw);
-    } else {
-#pragma unroll
-        for (int k = 0; k < kBlock; ++k)
-            if (col + k < width) dst[r * ld + col + k] = raw[k];
-    }
-}
-
-// ---- the rounding role of mx::pack_kernel on one LDS tile of fp32 bits, in its two halves: the caller's barrier lies between them ---------------
-__device__ __forceinline__ void column_amax(const uint32_t (&tile)[kRows][kTileCols], int c, int o, uint32_t (&v)[kBlock], uint32_t (&amax_s)[kOctets][kTileCols]) {
-    uint32_t amax = 0;
-#pragma unroll
-    for (int k = 0; k < kBlock; ++k) {
-        v[k] = tile[kBlock * o + k][c];
-        const uint32_t m = v[k] & 0x7fffffffu;
-        amax = m > amax ? m : amax;
-    }
-    amax_s[o][c] = amax;
-}
-// -> the octet's codes in the LDS image of the tile's cells, the scale byte of column `col` of block b into `out` (the buffer)
-template <int FMT>
-__device__ __forceinline__ void column_codes(const uint32_t (&v)[kBlock], const uint32_t (&amax_s)[kOctets][kTileCols], int c, int o, size_t b, size_t col, size_t width,
-                                             Key key, uint64_t *image, uint8_t *out) {
-    uint32_t amax = 0;
-#pragma unroll
-    for (int k = 0; k < kOctets; ++k) amax = amax_s[k][c] > amax ? amax_s[k][c] : amax;
-    const bool bad = amax >= 0x7f800000u;
-    const int e = bad ? 128 : mx::scale_of_amax<FMT>(amax);
-    uint32_t w[4];
-    mx::octet_words(b, col, width, o, mx::kKeptDomain, key, w);
-    const uint64_t word = mx::octet_codes<FMT>(v, e, bad, w);
-    if constexpr (FMT == 4) reinterpret_cast<uint32_t *>(image)[kOctets * c + o] = static_cast<uint32_t>(word);
-    else {
-        uint16_t *at = reinterpret_cast<uint16_t *>(image) + 12 * c + 3 * o;
-        at[0] = static_cast<uint16_t>(word), at[1] = static_cast<uint16_t>(word >> 16), at[2] = static_cast<uint16_t>(word >> 32);
-    }
-    if (o == 0 && col < width) out[b * width + col] = static_cast<uint8_t>(e + 127);
-}
-// the tile's cells, `cols` of them, between the buffer and LDS: 8-byte pieces, consecutive lanes consecutive pieces (u: the lane of the group)
-template <int FMT> __device__ __forceinline__ void store_cells(const uint64_t *image, uint8_t *codes, size_t b, size_t j0, size_t width, size_t cols, int u) {
-    if (8 * static_cast<size_t>(u) < cols * mx::cell_bytes(FMT)) reinterpret_cast<uint64_t *>(codes + (b * width + j0) * mx::cell_bytes(FMT))[u] = image[u];
-}
-template <int FMT> __device__ __forceinline__ void load_cells(uint64_t *image, const uint8_t *codes, size_t b, size_t j0, size_t width, size_t cols, int u) {
-    if (8 * static_cast<size_t>(u) < cols * mx::cell_bytes(FMT)) image[u] = reinterpret_cast<const uint64_t *>(codes + (b * width + j0) * mx::cell_bytes(FMT))[u];
-}
-// element `row` of the cell of tile column `c` in an LDS image, as mx::unpack_kernel reads it
-template <int FMT> __device__ __forceinline__ uint32_t code_at(const uint64_t *image, int c, int row) {
-    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(image);
-    const size_t bit = mx::cell_bytes(FMT) * 8 * c + FMT * row;
-    uint32_t two = bytes[bit / 8];
-    if (bit % 8 + FMT > 8) two |= static_cast<uint32_t>(bytes[bit / 8 + 1]) << 8;                  // (fp6 only, and never for a cell's last code)
-    return (two >> (bit % 8)) & ((1u << FMT) - 1u);
-}
 
 template <int DT, int FMT>
 __global__ __launch_bounds__(kThreads) void forward_kernel(ForwardArgs a) {
@@ -340,48 +247,12 @@ __global__ __launch_bounds__(kThreads) void backward_kernel(BackwardArgs a) {
     }
 }
 
-// dgamma[c] = the workgroups' sums of column c.  A workgroup of 16 waves takes 64 columns: wave w adds the rows [w per, (w + 1) per) of the workspace in
-// ascending order, per = ceil(parts / 16), and the waves' results are added in ascending order -- the rows in ascending order, associated by
-// sixteenths, so that 16 loads of a column are in flight and not one.
+// dgamma[c] = the workgroups' sums of column c: the rows of the workspace in ascending order, associated by sixteenths (mxrows::add_partials)
 __global__ __launch_bounds__(kThreads) void column_sums_kernel(const float *__restrict__ partials, size_t parts, size_t width, float *__restrict__ dgamma) {
     __shared__ float waves[kWaves][kTileCols];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t c = static_cast<size_t>(blockIdx.x) * kTileCols + lane;
-    const size_t per = (parts + kWaves - 1) / kWaves, from = wave * per, to = from + per < parts ? from + per : parts;
-    float sum = 0.0f;
-    if (c < width && from < parts) {
-        sum = partials[from * width + c];
-#pragma unroll 8
-        for (size_t p = from + 1; p < to; ++p) sum = add_rn(sum, partials[p * width + c]);
-    }
-    waves[wave][lane] = sum;
-    __syncthreads();
-    if (wave == 0 && c < width) {
-        float total = waves[0][lane];
-        for (size_t w = 1; w < static_cast<size_t>(kWaves) && w * per < parts; ++w) total = add_rn(total, waves[w][lane]);
-        dgamma[c] = total;
-    }
+    add_partials(partials, parts, width, width, blockIdx.x, dgamma, waves);
 }
 
-// what both entry points refuse alike, in the order of mxglu::check_call
-inline int check_call(const char *name, int dtype, int format, const void *seed_device, size_t rows, size_t width) {
-    if (const int rc = check_dtype(name, dtype)) return rc;
-    if (format != 4 && format != 6) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: format = %d is not 4 (fp4) or 6 (fp6)", name, format);
-    if (const int rc = check_seed_word(name, seed_device)) return rc;
-    if (rows == 0) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: rows = 0", name);
-    if (width == 0 || width > kMaxWidth) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: width = %zu is not in 1 .. %zu", name, width, kMaxWidth);
-    if (rows > kMaxCount / width) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: rows * width = %zu * %zu is beyond 2^36", name, rows, width);
-    return FEWBIT_OK;
-}
-inline int check_aligned16(const char *name, const char *what, const void *p) {
-    return !misaligned(p, 16) ? FEWBIT_OK : fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: %s must be 16-byte aligned", name, what);
-}
-// whether 16-byte pieces serve a tensor (an absent one: they would)
-inline bool wide(const void *p, size_t ld, int dtype) { return !misaligned(p, 16) && ld * size_of(dtype) % 16 == 0; }
-
-template <class F> void pick_kernel(int dtype, int format, F &&f) {
-    pick_dtype(dtype, [&](auto dt) { pick<4, 6>(format, [&](auto fmt) { f(dt, fmt); }); });
-}
 
 }  // namespace mxnorm
 }  // namespace quant

@@ -57,7 +57,7 @@ from .cabi import DTYPES
 from .dropout import _check_p, dropout_add
 
 __all__ = ('layer_norm_quantized', 'QuantizedLayerNorm', 'rms_norm_quantized', 'QuantizedRMSNorm', 'dropout_add_layer_norm_quantized', 'DropoutAddLayerNorm',
-           'dropout_add_rms_norm_quantized', 'DropoutAddRMSNorm', 'rms_norm_linear_mx', 'MXNormLinear')
+           'dropout_add_rms_norm_quantized', 'DropoutAddRMSNorm', 'rms_norm_linear_mx', 'MXNormLinear', 'layer_norm_linear_mx', 'MXLayerNormLinear')
 
 # Everything below takes the kind as ``centred``: True for the layer norm, False for the RMS norm (the un-centred statistic, backward without the mean
 # term, no beta: ``bias`` is None throughout).
@@ -505,6 +505,51 @@ def _fp32_product(g: torch.Tensor, xq: torch.Tensor) -> torch.Tensor:
     return g.T @ xq
 
 
+def _linears_backward(ctx, cells, gamma, beta, weights, grads, need_gy: bool, first: int):
+    """What the linears behind a norm on MX cells hand back, for both nodes below -> ``(gy, grad_weights, grad_biases)``: ``gy = sum_i G_i W_i`` in ONE
+    buffer (None where ``need_gy`` is False or no gradient arrived), ``dW_i = (G_i^T x^q) * gamma`` by columns, plus ``(sum_rows G_i) (x) beta`` where
+    the norm has a ``beta`` (the layer norm: ``y = x^ * gamma + beta``), formed in fp32 and rounded once; ``db_i = sum_rows G_i``, exact.  ``first``:
+    the index of the first weight among the node's inputs."""
+    (rows, width), count, format, needs = ctx.flat_shape, ctx.count, ctx.format, ctx.needs_input_grad
+    grad_weights, grad_biases, gy, decoded = [None] * count, [None] * count, None, {}
+
+    def xq(dtype):                                              # the decode route: x^q ONCE per dtype, a transient of the input's size
+        if dtype not in decoded:
+            decoded[dtype] = (cabi_x.mx_unpack(cells, rows, width, format, dtype) if ctx.native else
+                              cabi_x.mx_unpack_host(cells.cpu(), rows, width, format).to(device=cells.device, dtype=dtype))
+        return decoded[dtype]
+
+    for i, (g, weight) in enumerate(zip(grads, weights)):
+        if g is None:
+            continue
+        if need_gy:                                             # gy = sum_i G_i W_i in ONE buffer
+            w = weight if weight.dtype == g.dtype else weight.to(g.dtype)          # (under autocast: the cast autocast makes itself)
+            gy = g @ w if gy is None else gy.addmm_(g, w)
+        want_bias = ctx.has_bias[i] and needs[first + count + i]
+        if beta is None:
+            if want_bias:
+                grad_biases[i] = g.sum(dim=0)
+            column_sum = None
+        elif want_bias or needs[first + i]:                     # s = sum_rows G_i in fp32: db_i, and the rank-one term of dW_i
+            column_sum = g.sum(dim=0, dtype=cabi_x._work_dtype(g))
+            if want_bias:
+                grad_biases[i] = column_sum.to(g.dtype)
+        if needs[first + i]:
+            fout = g.shape[1]
+            if ctx.native and g.dtype in DTYPES and cabi_x.mx_wgrad_serves(rows, width, fout, format):
+                packed = cabi_x.mx_pack(linear._unit_stride(g), _seed_plus(ctx.seed, 1 + i), 'fp8', 'grad')
+                product = cabi_x.mx_wgrad(packed, cells, rows, width, fout, format, torch.float32)
+            else:
+                g2 = g if ctx.native and g.dtype in DTYPES else g.to(cabi_x._work_dtype(g))
+                product = _fp32_product(g2, xq(g2.dtype))
+            # dW = (G^T x^q) * gamma by columns: the fp32 product is a transient of the WEIGHT's size, rounded once
+            product = product * gamma.detach().to(product.dtype)[None, :]
+            if column_sum is not None:
+                product = torch.addr(product, column_sum.to(product.dtype), beta.detach().to(product.dtype))
+            grad_weights[i] = product.to(weight.dtype)
+    return gy, grad_weights, grad_biases
+
+
 class _RMSNormLinearMX(torch.autograd.Function):
     """``tuple(F.linear(F.rms_norm(input, gamma), W_i, b_i))`` as ONE node (:func:`rms_norm_linear_mx`).  Kept for backward: ONE uint8 buffer of
     ``cabi_x.mx_bytes(rows, width, format)`` bytes (the cells of the fp32 ``x^``), ``rstd`` (fp32 per row), gamma and the weights; ``y`` is not.  On
@@ -542,32 +587,7 @@ class _RMSNormLinearMX(torch.autograd.Function):
         cells, rstd, gamma, *weights = ctx.saved_tensors        # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
         (rows, width), count, format, needs = ctx.flat_shape, ctx.count, ctx.format, ctx.needs_input_grad
         grads = [None if g is None else linear._dense_rows(g).reshape(rows, -1) for g in grad_outputs]
-        grad_weights, grad_biases, gy, decoded = [None] * count, [None] * count, None, {}
-
-        def xq(dtype):                                          # the decode route: x^q ONCE per dtype, a transient of the input's size
-            if dtype not in decoded:
-                decoded[dtype] = (cabi_x.mx_unpack(cells, rows, width, format, dtype) if ctx.native else
-                                  cabi_x.mx_unpack_host(cells.cpu(), rows, width, format).to(device=cells.device, dtype=dtype))
-            return decoded[dtype]
-
-        for i, (g, weight) in enumerate(zip(grads, weights)):
-            if g is None:
-                continue
-            if needs[0] or needs[1]:                            # gy = sum_i G_i W_i in ONE buffer
-                w = weight if weight.dtype == g.dtype else weight.to(g.dtype)      # (under autocast: the cast autocast makes itself)
-                gy = g @ w if gy is None else gy.addmm_(g, w)
-            if needs[6 + i]:
-                fout = g.shape[1]
-                if ctx.native and g.dtype in DTYPES and cabi_x.mx_wgrad_serves(rows, width, fout, format):
-                    packed = cabi_x.mx_pack(linear._unit_stride(g), _seed_plus(ctx.seed, 1 + i), 'fp8', 'grad')
-                    product = cabi_x.mx_wgrad(packed, cells, rows, width, fout, format, torch.float32)
-                else:
-                    g2 = g if ctx.native and g.dtype in DTYPES else g.to(cabi_x._work_dtype(g))
-                    product = _fp32_product(g2, xq(g2.dtype))
-                # dW = (G^T x^q) * gamma by columns: the fp32 product is a transient of the WEIGHT's size, rounded once
-                grad_weights[i] = (product * gamma.detach().to(product.dtype)[None, :]).to(weight.dtype)
-            if ctx.has_bias[i] and needs[6 + count + i]:
-                grad_biases[i] = g.sum(dim=0)
+        gy, grad_weights, grad_biases = _linears_backward(ctx, cells, gamma, None, weights, grads, needs[0] or needs[1], 6)
         grad_input = grad_gamma = None
         if gy is not None:
             want = (needs[0], needs[1])
@@ -655,3 +675,143 @@ class MXNormLinear(torch.nn.Module):
 
     def extra_repr(self) -> str:
         return f'{self.weight.numel()}, eps={self.eps}, format={self.format}'
+
+
+# ---- the LAYER norm and the linears behind it on ONE set of MX cells: y = x^ * gamma + beta, so dW_i takes one rank-one term in beta more -----------------
+
+class _LayerNormLinearMX(torch.autograd.Function):
+    """``tuple(F.linear(F.layer_norm(input, gamma, beta), W_i, b_i))`` as ONE node (:func:`layer_norm_linear_mx`), with the norm's output in front where
+    ``return_normed``.  Kept for backward: ONE uint8 buffer of ``cabi_x.mx_bytes(rows, width, format)`` bytes (the cells of the fp32 ``x^``), ``rstd``
+    (fp32 per row), gamma, beta and the weights; ``y``, the mean and the input are not.  Seeds as in :class:`_RMSNormLinearMX`."""
+
+    @staticmethod
+    def forward(ctx, input, gamma, beta, eps: float, format: str, generator, return_normed: bool, count: int, *parameters):
+        weights, biases = parameters[:count], parameters[count:]
+        flat = input.detach().reshape(-1, input.shape[-1])
+        ctx.format, ctx.flat_shape, ctx.input_shape, ctx.input_dtype, ctx.count = format, tuple(flat.shape), input.shape, input.dtype, count
+        ctx.has_bias, ctx.has_beta, ctx.return_normed = tuple(b is not None for b in biases), beta is not None, return_normed
+        ctx.autocast = linear._autocast_seen(input.device.type)
+        ctx.set_materialize_grads(False)
+        ctx.native = (linear._kernels_take(flat) and 1 <= flat.shape[1] <= cabi_x.MX_NORM_MAX_WIDTH and gamma.dtype in DTYPES
+                      and all(p.device == flat.device for p in (gamma, beta) if p is not None) and (beta is None or beta.dtype in DTYPES))
+        if ctx.native:
+            ctx.seed = linear._sketch_seed(generator, flat.device)
+            y, cells, rstd, _ = cabi_x.mx_layer_norm_forward(linear._unit_stride(flat), _as(gamma, flat.dtype), _as(beta, flat.dtype), eps, format,
+                                                             _seed_plus(ctx.seed, 0))
+        else:
+            ctx.seed = linear._draw_seed(generator if generator is None or generator.device.type == 'cpu' else None)
+            y, cells, rstd, _ = cabi_x.mx_layer_norm_host(flat, gamma, beta, eps, format, ctx.seed)
+        ctx.save_for_backward(cells, rstd, gamma, *(() if beta is None else (beta, )), *weights)
+        y = y.view(input.shape)
+        outputs = tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
+        return (y, *outputs) if return_normed else outputs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grad_outputs):
+        with linear._autocast_as(ctx.autocast):
+            return _LayerNormLinearMX._backward(ctx, grad_outputs)
+
+    @staticmethod
+    def _backward(ctx, grad_outputs):
+        cells, rstd, gamma, *rest = ctx.saved_tensors           # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
+        beta, weights = (rest[0], rest[1:]) if ctx.has_beta else (None, rest)
+        (rows, width), count, format, needs = ctx.flat_shape, ctx.count, ctx.format, ctx.needs_input_grad
+        grads = [None if g is None else linear._dense_rows(g).reshape(rows, -1) for g in grad_outputs]
+        at_y = grads.pop(0) if ctx.return_normed else None      # the gradient that arrives at the norm's own output
+        gy, grad_weights, grad_biases = _linears_backward(ctx, cells, gamma, beta, weights, grads, any(needs[:3]), 8)
+        if at_y is not None and any(needs[:3]):
+            gy = at_y if gy is None else gy.add_(at_y) if gy.dtype == at_y.dtype else gy + at_y
+        grad_input = grad_gamma = grad_beta = None
+        if gy is not None:
+            want = (needs[0], needs[1], ctx.has_beta and needs[2])
+            if ctx.native:
+                gy = gy if gy.dtype in DTYPES else gy.float()
+                dx, dgamma, dbeta = cabi_x.mx_layer_norm_backward(linear._unit_stride(gy), cells, rstd, _as(gamma, gy.dtype), format, want)
+            else:
+                dx, dgamma, dbeta = cabi_x.mx_layer_norm_backward_host(gy, cells, rstd, gamma, format)
+            grad_input = dx.to(ctx.input_dtype).view(ctx.input_shape) if want[0] else None
+            grad_gamma = dgamma.to(gamma.dtype).view(gamma.shape) if want[1] else None
+            grad_beta = dbeta.to(beta.dtype).view(beta.shape) if want[2] else None
+        return (grad_input, grad_gamma, grad_beta, None, None, None, None, None, *grad_weights, *grad_biases)
+
+
+def layer_norm_linear_mx(input: torch.Tensor, norm_weight: torch.Tensor, norm_bias: Optional[torch.Tensor], weights: Sequence[torch.Tensor],
+                         biases: Optional[Sequence[Optional[torch.Tensor]]] = None, eps: float = 1e-5, format: str = 'fp4',
+                         generator: Optional[torch.Generator] = None, return_normed: bool = False) -> tuple:
+    """``tuple(F.linear(F.layer_norm(input, (width, ), norm_weight, norm_bias, eps), W, b) for W, b in zip(weights, biases))`` as ONE node that keeps
+    ONE buffer for all of it: the normalized rows ``x^ = (x - mean) * rstd`` as MXFP4 (``format='fp4'``) or MXFP6 (``'fp6'``) cells down their columns,
+    one fp32 ``rstd`` per row, ``norm_weight``, ``norm_bias`` and the weights.  Neither the norm's output, nor the mean, nor the input is kept: because
+    ``y = x^ * gamma + beta``, ``dW_i = G_i^T y = (G_i^T x^) * gamma`` by columns ``+ (sum_rows G_i) (x) beta``, and ``sum_rows G_i`` is ``db_i``.
+
+    * ``return_normed=True`` puts ``y`` itself in front of the tuple (the post-norm case: in BERT / RoBERTa a LayerNorm output feeds the next linears
+      AND the next residual); the gradient that arrives at it is added into ``gy = sum_i G_i W_i`` before the norm's backward.
+    * Forward: one kernel (``cabi_x.mx_layer_norm_forward``) writes ``y``, ``rstd`` and the cells of the FP32 ``x^``; then ``F.linear`` per weight.
+    * Backward: ``dW_i`` from ``cabi_x.mx_wgrad`` on the fp8 cells of ``G_i`` and the kept cells (where ``cabi_x.mx_wgrad_serves`` denies -- widths
+      that are no multiples of 32 -- a decode and a GEMM), scaled by ``norm_weight``, plus ``s (x) norm_bias`` with ``s = G_i.sum(0)`` in fp32 (absent
+      where ``norm_bias`` is None), formed in fp32 and rounded once.  ``db_i = s`` is exact.  ``dx`` and the gradients of ``norm_weight`` and
+      ``norm_bias`` come from ``cabi_x.mx_layer_norm_backward``: ``E[x^q] = x^``, so ``E[dW_i] = G_i^T y``; the gradient of ``norm_bias`` does
+      not read the cells; ``dx`` carries a bias of second order in the rounding, as the quantized norms' does.
+    * Seeds: ONE draw from ``linear._sketch_seed`` per call; the cells take it plus 0, the fp8 rounding of ``G_i`` plus 1 + i.
+    * Widths above 8192, host tensors and float64 take the host route: the same definitions on ``cabi_x.mx_pack_host``.
+    * Grad mode off, or nothing that requires grad: plain ``F.layer_norm`` and ``F.linear``; no seed is drawn, nothing is kept.
+    * Under ``torch.autocast`` the norm runs in the input's dtype and the linears as autocast casts them; backward runs under the state the forward
+      saw."""
+    linear._check_mx_format(format)
+    weights = tuple(weights)
+    biases = (None, ) * len(weights) if biases is None else tuple(biases)
+    if len(biases) != len(weights) or not weights:
+        raise ValueError(f'{len(weights)} weights and {len(biases)} biases: one bias (or None) per weight is needed, and at least one weight')
+    if not kept.trains(input, norm_weight, norm_bias, *weights, *biases) or input.numel() == 0:
+        y = F.layer_norm(input, (input.shape[-1], ), norm_weight, norm_bias, float(eps))
+        outputs = tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
+        return (y, *outputs) if return_normed else outputs
+    return _LayerNormLinearMX.apply(input, norm_weight, norm_bias, float(eps), format, generator, bool(return_normed), len(weights), *weights, *biases)
+
+
+class MXLayerNormLinear(torch.nn.Module):
+    r"""A LayerNorm and the linear layers that read its output -- q / k / v of a BERT / RoBERTa / GPT-2 / ViT block, or the intermediate dense behind
+    the attention output's LayerNorm -- as one module that keeps ONE set of MXFP4 / MXFP6 cells for all of them (:func:`layer_norm_linear_mx`);
+    ``forward`` returns the tuple of the linears' outputs, with the norm's own output in front where ``return_normed`` (it also feeds the next
+    residual there).  The linears are plain ``nn.Linear`` layers in ``self.linears``, the norm's parameters ``self.weight`` and ``self.bias``.  In
+    ``eval()`` mode gradients are torch's exact ones and nothing is kept.
+
+        >>> m = fewbit.MXLayerNormLinear(768, [(768, 768, True)] * 3)
+        >>> q, k, v = m(torch.randn(128, 768))
+        >>> m = fewbit.MXLayerNormLinear.from_modules(layer.attention.output.LayerNorm, [layer.intermediate.dense], return_normed=True)
+        >>> y, h = m(hidden)
+    """
+
+    def __init__(self, width: int, linears, eps: float = 1e-5, bias: bool = True, format: str = 'fp4', generator: Optional[torch.Generator] = None,
+                 return_normed: bool = False, device=None, dtype=None) -> None:
+        linear._check_mx_format(format)
+        super().__init__()
+        self.weight = torch.nn.Parameter(torch.ones(width, device=device, dtype=dtype))
+        self.register_parameter('bias', torch.nn.Parameter(torch.zeros(width, device=device, dtype=dtype)) if bias else None)
+        self.linears = torch.nn.ModuleList(torch.nn.Linear(fin, fout, b, device=device, dtype=dtype) for fin, fout, b in linears)
+        if any(m.in_features != width for m in self.linears):
+            raise ValueError(f'every linear must read the {width} features of the norm')
+        self.eps, self.format, self.generator, self.return_normed = eps, format, generator, return_normed
+
+    @classmethod
+    def from_modules(cls, norm: torch.nn.LayerNorm, linears: Sequence[torch.nn.Linear], format: str = 'fp4', generator: Optional[torch.Generator] = None,
+                     return_normed: bool = False) -> 'MXLayerNormLinear':
+        """An ``MXLayerNormLinear`` that SHARES the weight and the bias of ``norm`` -- a ``torch.nn.LayerNorm`` over the last dimension with affine
+        parameters -- and the given ``nn.Linear`` modules themselves"""
+        weight, bias = getattr(norm, 'weight', None), getattr(norm, 'bias', None)
+        if not isinstance(weight, torch.Tensor) or weight.dim() != 1 or not isinstance(getattr(norm, 'eps', None), float):
+            raise TypeError(f'{type(norm).__name__} has no 1-D weight with a float eps')
+        new = cls(weight.numel(), [], norm.eps, False, format, generator, return_normed, device='meta')
+        new.weight, new.bias, new.linears = weight, bias, torch.nn.ModuleList(linears)
+        return new.train(norm.training)
+
+    def forward(self, input: torch.Tensor) -> tuple:
+        weights, biases = [m.weight for m in self.linears], [m.bias for m in self.linears]
+        if not self.training:
+            y = F.layer_norm(input, (input.shape[-1], ), self.weight, self.bias, self.eps)
+            outputs = tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
+            return (y, *outputs) if self.return_normed else outputs
+        return layer_norm_linear_mx(input, self.weight, self.bias, weights, biases, self.eps, self.format, self.generator, self.return_normed)
+
+    def extra_repr(self) -> str:
+        return f'{self.weight.numel()}, eps={self.eps}, format={self.format}, return_normed={self.return_normed}'

@@ -58,7 +58,9 @@ extern "C" {
  * So were the gate and the up as row blocks (fewbit_hipx_mx_glu_state_bytes, _mx_glu_forward, _mx_glu_backward): inside revision 2, recognised by the
  * presence of the symbols.
  * So were the normalized rows as row blocks (fewbit_hipx_mx_rms_norm_workspace, _mx_rms_norm_forward, _mx_rms_norm_backward): inside revision 2,
- * recognised by the presence of the symbols. */
+ * recognised by the presence of the symbols.
+ * So were the centred normalized rows as row blocks (fewbit_hipx_mx_layer_norm_workspace, _mx_layer_norm_forward, _mx_layer_norm_backward): inside
+ * revision 2, recognised by the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -749,6 +751,43 @@ int fewbit_hipx_mx_rms_norm_forward(int dtype, const void *x, size_t ld_x, size_
 int fewbit_hipx_mx_rms_norm_backward(int dtype, const void *gy, size_t ld_gy, const uint8_t *cells, size_t cells_bytes, const float *rstd,
                                      const void *gamma, size_t rows, size_t width, int format, void *dx, size_t ld_dx, float *dgamma, void *workspace,
                                      size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The centred normalized rows as row blocks: the LAYER norm in front of linear layers whose weight gradients come from fewbit_hipx_mx_wgrad.  The
+ * norm keeps x^ = (x - mean) * rstd as ONE fewbit_hipx_mx_pack buffer and one fp32 rstd per row; with y = x^ * gamma + beta the input of the linears,
+ * dW = G^T y = (G^T x^) * gamma by columns + (sum_rows G) (x) beta, and sum_rows G is the linear's bias gradient: that buffer serves the norm's own
+ * backward and every weight gradient behind it (fewbit_amd/csrc/fewbit_mxlnorm.hip).  All arithmetic is fp32, each operation rounded once:
+ *   mean[r]   = sum_j x[r][j] / width                             rstd[r] = 1 / sqrt(sum_j (x[r][j] - mean[r])^2 / width + eps)
+ *               (the two-pass variance; both sums in a fixed order of the kernel's own, over the same elements in the same order)
+ *   x^[r][j]  = (float(x[r][j]) - mean[r]) * rstd[r]              y[r][j] = round(x^[r][j] * float(gamma[j]) + float(beta[j])) to `dtype`
+ *               (beta NULL: y = round(x^ * gamma), nothing is added)
+ *   cells     = fewbit_hipx_mx_pack of the FP32 matrix x^, `format` 4 or 6, role 0, the call's seed: given the mean and the rstd that were written,
+ *               the cells and y are functions of host fp32 arithmetic (fewbit_hipx_mx_pack_host of (x - mean) * rstd).  Rows beyond `rows` count +0.
+ *   The value edges are those of fewbit_hipx_layer_norm_forward: a non-finite element makes its row NaN (and poisons the cells it lies in); a
+ *   finite row whose centred squares overflow gives rstd = 0, x^ = +-0 and y = beta; a constant row has x^ = 0, so a cell that holds nothing else
+ *   has scale byte 0 and codes 0.
+ * fewbit_hipx_mx_layer_norm_forward: ONE launch.  x, y: rows x width of `dtype`, unit stride along the width, row strides ld_* >= width, aligned to
+ * their element; gamma, beta: width elements of `dtype`; mean, rstd: rows floats each (the backward needs rstd only; mean lets a caller reproduce
+ * x^ bit for bit); cells: fewbit_hipx_mx_bytes(rows, width, format) bytes, 16-byte aligned.
+ * fewbit_hipx_mx_layer_norm_backward: x^q the decode of the cells, g^ = gy * gamma, c1[r] = sum_j(g^) / width, c2[r] = sum_j(g^ x^q) / width:
+ *   dx[r][j] = round(rstd[r] * ((g^[r][j] - c1[r]) - x^q[r][j] * c2[r]))
+ *   dgamma[j] = sum_r gy[r][j] * x^q[r][j]                        dbeta[j] = sum_r gy[r][j]                        (fp32, width floats each)
+ * the expressions of fewbit_hipx_layer_norm_backward; every sum in an order fixed by the shape alone.  One launch, and a second small one where
+ * dgamma or dbeta is wanted, which needs a workspace of fewbit_hipx_mx_layer_norm_workspace(rows, width) bytes: [workgroups][2][width] floats,
+ * workgroups = min(ceil(rows / 32), 512) (4-byte aligned; 0 for extents that are refused).  dx, dgamma and dbeta may each be NULL: what is NULL is
+ * not written.  A poisoned cell (scale byte 0xFF) makes dx NaN on its 32 rows and dgamma NaN in its column; dbeta does not read the cells.
+ * seed_device: NULL, or the seed in device memory (8-byte aligned), read when the kernel runs.
+ * Refused before anything is launched (FEWBIT_ERR_INVALID_ARGUMENT), in the order of the RMS entry points: an unknown dtype, a format other than 4
+ * and 6, a misaligned seed word, rows = 0, width outside 1 .. 8192, rows * width > 2^36, a null pointer other than beta, dx, dgamma and dbeta,
+ * ld < width, misaligned pointers, cells or a workspace that are too small.  No atomics and no flags between workgroups: the same arguments give
+ * the same bytes; every call can be captured. */
+size_t fewbit_hipx_mx_layer_norm_workspace(size_t rows, size_t width);
+int fewbit_hipx_mx_layer_norm_forward(int dtype, const void *x, size_t ld_x, size_t rows, size_t width, const void *gamma, const void *beta, float eps,
+                                      int format, uint64_t seed, const uint64_t *seed_device, void *y, size_t ld_y, float *mean, float *rstd,
+                                      uint8_t *cells, size_t cells_bytes, void *stream);
+int fewbit_hipx_mx_layer_norm_backward(int dtype, const void *gy, size_t ld_gy, const uint8_t *cells, size_t cells_bytes, const float *rstd,
+                                       const void *gamma, size_t rows, size_t width, int format, void *dx, size_t ld_dx, float *dgamma, float *dbeta,
+                                       void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
