@@ -78,13 +78,14 @@ else:
 
 from . import functional  # noqa: E402,F401
 from . import modules  # noqa: E402,F401
-from . import approx, cli, compat, fft, glu, linear, norm, variance, xent  # noqa: E402,F401
+from . import approx, cli, compat, fft, glu, linear, mlp, norm, variance, xent  # noqa: E402,F401
 from .modules import *  # noqa: E402,F401,F403
 from .linear import LinearCRS, LinearGRP, MXLinear, QuantizedLinear, RandomizedLinear  # noqa: E402,F401
 from .dropout import Dropout, dropout, dropout_add  # noqa: E402,F401  (fewbit_amd.dropout is the function from here on; the module: sys.modules['fewbit_amd.dropout'])
 from .norm import (DropoutAddLayerNorm, DropoutAddRMSNorm, MXLayerNormLinear, MXNormLinear, QuantizedLayerNorm, QuantizedRMSNorm, dropout_add_layer_norm_quantized,  # noqa: E402,F401
                    dropout_add_rms_norm_quantized, layer_norm_linear_mx, layer_norm_quantized, rms_norm_linear_mx, rms_norm_quantized)
 from .glu import MXGatedMLP, QuantizedGatedMLP, QuantizedGLU, gated_mlp_mx, gated_mlp_quantized, glu_quantized  # noqa: E402,F401
+from .mlp import MXMLP, mlp_mx  # noqa: E402,F401
 from .xent import CrossEntropyLoss, LinearCrossEntropyLoss, cross_entropy, linear_cross_entropy  # noqa: E402,F401
 from .util import map_module, memory_usage_hooks  # noqa: E402,F401
 

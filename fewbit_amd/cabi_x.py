@@ -24,7 +24,7 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'glu_backward_product', 'CROSS_ENTROPY_MAX_GROUPS', 'cross_entropy_host', 'cross_entropy_forward', 'cross_entropy_backward',
            'CROSS_ENTROPY_STEP_STAGED_BYTES', 'cross_entropy_step', 'QUANT_WGRAD_TILE', 'quant_wgrad_serves', 'quant_wgrad_slices', 'quant_wgrad_workspace',
            'quant_wgrad', 'MX_FORMATS', 'MX_WGRAD_TILE', 'mx_bytes', 'mx_pack_host', 'mx_unpack_host', 'mx_pack', 'mx_unpack', 'mx_wgrad_serves', 'mx_wgrad_slices',
-           'mx_wgrad_workspace', 'mx_wgrad', 'mx_glu_state_bytes', 'mx_glu_forward', 'mx_glu_backward', 'MX_NORM_MAX_WIDTH', 'MX_NORM_PLAN_WIDTHS', 'MX_NORM_MAX_GRID',
+           'mx_wgrad_workspace', 'mx_wgrad', 'mx_glu_state_bytes', 'mx_glu_forward', 'mx_glu_backward', 'MX_ACTIVATIONS', 'mx_act_forward', 'mx_act_backward', 'MX_NORM_MAX_WIDTH', 'MX_NORM_PLAN_WIDTHS', 'MX_NORM_MAX_GRID',
            'mx_rms_norm_workspace', 'mx_rms_norm_host', 'mx_rms_norm_backward_host', 'mx_rms_norm_forward', 'mx_rms_norm_backward',
            'mx_layer_norm_workspace', 'mx_layer_norm_host', 'mx_layer_norm_backward_host', 'mx_layer_norm_forward', 'mx_layer_norm_backward']
 
@@ -113,6 +113,9 @@ _SIGNATURES = {
     'fewbit_hipx_mx_glu_state_bytes': (_sz, [_sz, _sz, _i32]),
     'fewbit_hipx_mx_glu_forward': (_i32, [_i32, _i32, _vp, _sz, _vp, _sz, _sz, _sz, _i32, _u64, _u64, _vp, _vp, _sz, _vp, _sz, _vp]),
     'fewbit_hipx_mx_glu_backward': (_i32, [_i32, _i32, _vp, _sz, _vp, _sz, _sz, _sz, _i32, _u64, _u64, _u64, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    # the pre-activation as row blocks (the activation of a plain MLP on MX cells): inside revision 2 as well, recognised by their symbols
+    'fewbit_hipx_mx_act_forward': (_i32, [_i32, _i32, _vp, _sz, _sz, _sz, _i32, _u64, _vp, _vp, _sz, _vp, _sz, _vp]),
+    'fewbit_hipx_mx_act_backward': (_i32, [_i32, _i32, _vp, _sz, _vp, _sz, _sz, _sz, _i32, _u64, _u64, _vp, _vp, _sz, _vp, _vp, _vp]),
     # the normalized rows as row blocks: inside revision 2 as well, recognised by their symbols
     'fewbit_hipx_mx_rms_norm_workspace': (_sz, [_sz, _sz]),
     'fewbit_hipx_mx_rms_norm_forward': (_i32, [_i32, _vp, _sz, _sz, _sz, _vp, ctypes.c_float, _i32, _u64, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
@@ -1353,6 +1356,62 @@ def mx_glu_backward(gy: torch.Tensor, state: torch.Tensor, activation: str, form
         _check(lib().fewbit_hipx_mx_glu_backward(DTYPES[gy.dtype], act, gy.data_ptr(), ld_gy, state.data_ptr(), state.numel(), rows, width, MX_FORMATS[format], *values,
                                                  words, _ptr(d_gate), ld_dgate, _ptr(d_up), ld_dup, *(_ptr(t) for t in cells), _stream(stream, gy.device)))
     return (d_gate, d_up, *cells)
+
+
+# ---- the pre-activation as row blocks (fewbit_amd/csrc/fewbit_mxact.hip): the activation of a plain MLP on MX cells, the operands of two mx_wgrad calls ----
+MX_ACTIVATIONS = ('gelu', 'gelu_tanh', 'relu', 'silu')          # enum fewbit_mxact; gelu: the erf form
+
+
+def _mx_act_call(name: str, like: torch.Tensor, activation: str, format: str, seeds, count: int):
+    """(enum of the activation, then what ``_mx_glu_call`` gives with the bytes of ONE buffer); ``seeds`` may also be one int where ``count`` is 1"""
+    if activation not in MX_ACTIVATIONS:
+        raise FewbitHipError(f"{name}: activation must be one of {', '.join(map(repr, MX_ACTIVATIONS))} (got {activation!r})")
+    seeds = (seeds, ) if isinstance(seeds, int) else seeds
+    rows, width, ld, _, values, words, others = _mx_glu_call(name, like, format, seeds, count)
+    return MX_ACTIVATIONS.index(activation), rows, width, ld, mx_bytes(rows, width, format), values, words, others
+
+
+def mx_act_forward(u: torch.Tensor, activation: str, format: str = 'fp6', seeds=0, keep: bool = True, h: Optional[torch.Tensor] = None,
+                   state: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """``act(u)`` in ONE launch -> ``(h, state)``.  ``u``: 2-D fp32 / fp16 / bf16 on the GPU, unit stride along the width, any row stride.  ``h``:
+    ``act`` in fp32 rounded once to the dtype (``activation``: 'gelu' the erf form, 'gelu_tanh', 'relu', 'silu'; silu and gelu have the bytes of
+    ``glu_forward(u, ones, ...)``).  ``state``: bit for bit ``mx_pack(u, seed, format, 'kept')``, ``mx_bytes`` bytes; with ``keep=False`` it is None, no
+    seed is read and ``h`` has the same bytes.  ``seeds``: one int, or one int64 word on the device.  ``h`` (any row stride), ``state``: buffers to write into."""
+    act, rows, width, ld_u, need, values, words, others = _mx_act_call('mx_act_forward', u, activation, format, seeds if keep else 0, 1)
+    with _on(u.device):
+        h = _mx_glu_out(h, u, 'h')
+        ld_h = _glu_rows(h, 'h')[2]
+        state = _state_to_write(state, keep, need, u.device)
+        _same_device(u, h, *others, *(() if state is None else (state, )))
+        _check(lib().fewbit_hipx_mx_act_forward(DTYPES[u.dtype], act, u.data_ptr(), ld_u, rows, width, MX_FORMATS[format], *values, words, h.data_ptr(), ld_h,
+                                                _ptr(state), 0 if state is None else state.numel(), _stream(stream, u.device)))
+    return h, state
+
+
+def mx_act_backward(gh: torch.Tensor, state: torch.Tensor, activation: str, format: str, seeds, want=(True, True, True), du: Optional[torch.Tensor] = None,
+                    du_cells: Optional[torch.Tensor] = None, product_cells: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """The backward of ``mx_act_forward`` in ONE launch -> ``(du, du_cells, product_cells)``: ``du = gh * act'(u^)`` in the dtype of ``gh`` on the decode
+    ``u^`` of the state, and two ``mx_pack`` buffers, bit for bit ``mx_pack(du, seeds[0], 'fp8', 'grad')`` and ``mx_pack(h^, seeds[1], format, 'kept')``
+    with ``h^ = act(u^)`` rounded once to that dtype and never written itself: the operands of ``mx_wgrad`` for both weights of a plain MLP.  Where
+    ``want`` is False the output is None and nothing is written for it.  ``gh``, ``du``: 2-D, unit stride along the width, any row stride.  ``seeds``:
+    two different ints, or one int64 tensor of two words on the device.  ``du``, ``du_cells``, ``product_cells``: buffers to write into."""
+    act, rows, width, ld_gh, need, values, words, others = _mx_act_call('mx_act_backward', gh, activation, format, seeds, 2)
+    want = tuple(bool(w) for w in want)
+    if len(want) != 3:
+        raise FewbitHipError('want must name three outputs (du, du_cells, product_cells)')
+    _state_to_read(state, need)
+    with _on(gh.device):
+        du = _mx_glu_out(du, gh, 'du') if want[0] else None
+        ld_du = 0 if du is None else _glu_rows(du, 'du')[2]
+        cells = [_state_to_write(t, w, mx_bytes(rows, width, f), gh.device, what) for t, w, f, what in
+                 ((du_cells, want[1], 'fp8', 'du_cells'), (product_cells, want[2], format, 'product_cells'))]
+        for t, f in zip(cells, ('fp8', format)):
+            if t is not None:
+                _state_to_read(t, mx_bytes(rows, width, f), 'a cell buffer')
+        _same_device(gh, state, *others, *(t for t in (du, *cells) if t is not None))
+        _check(lib().fewbit_hipx_mx_act_backward(DTYPES[gh.dtype], act, gh.data_ptr(), ld_gh, state.data_ptr(), state.numel(), rows, width, MX_FORMATS[format], *values,
+                                                 words, _ptr(du), ld_du, *(_ptr(t) for t in cells), _stream(stream, gh.device)))
+    return (du, *cells)
 
 
 # ---- the normalized rows as row blocks (fewbit_amd/csrc/fewbit_mxnorm.hip): the RMS norm whose x^ is ONE mx_pack buffer ---------------------------------

@@ -60,7 +60,9 @@ extern "C" {
  * So were the normalized rows as row blocks (fewbit_hipx_mx_rms_norm_workspace, _mx_rms_norm_forward, _mx_rms_norm_backward): inside revision 2,
  * recognised by the presence of the symbols.
  * So were the centred normalized rows as row blocks (fewbit_hipx_mx_layer_norm_workspace, _mx_layer_norm_forward, _mx_layer_norm_backward): inside
- * revision 2, recognised by the presence of the symbols. */
+ * revision 2, recognised by the presence of the symbols.
+ * So was the pre-activation as row blocks (fewbit_hipx_mx_act_forward, _mx_act_backward): inside revision 2, recognised by the presence of the
+ * symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -788,6 +790,36 @@ int fewbit_hipx_mx_layer_norm_forward(int dtype, const void *x, size_t ld_x, siz
 int fewbit_hipx_mx_layer_norm_backward(int dtype, const void *gy, size_t ld_gy, const uint8_t *cells, size_t cells_bytes, const float *rstd,
                                        const void *gamma, size_t rows, size_t width, int format, void *dx, size_t ld_dx, float *dgamma, float *dbeta,
                                        void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The pre-activation as row blocks: the activation between the two linears of a plain MLP, h = act(u), whose input is kept as the row blocks of a
+ * seed, and its backward, which hands both weight gradients of the MLP to fewbit_hipx_mx_wgrad (fewbit_amd/csrc/fewbit_mxact.hip).  Nothing new is
+ * defined: every buffer below is bit for bit what fewbit_hipx_mx_pack writes from the named tensor.
+ *   act       an enum of these entry points' own (FEWBIT_RELU and FEWBIT_LOGSIGMOID of fewbit_hip.h share the value 4):
+ *             FEWBIT_MXACT_GELU  u Phi(u), the erf form     FEWBIT_MXACT_GELU_TANH  u sigmoid(2 sqrt(2 / pi) (u + 0.044715 u^3)), which is
+ *             u / 2 (1 + tanh(..)) without its cancellation     FEWBIT_MXACT_RELU  max(u, 0), slope 0 at 0     FEWBIT_MXACT_SILU  u sigmoid(u)
+ *             silu and the erf form have the arithmetic of the gate and the up of a seed (the bytes of fewbit_hipx_glu_forward with up = 1).
+ * fewbit_hipx_mx_act_forward: ONE launch.  u, h: rows x width of `dtype`, unit stride along the width, row strides ld_* >= width, aligned to their
+ * element; h = round(act(u)), act in fp32, rounded once.  state = fewbit_hipx_mx_pack(u, `format` 4 or 6, role 0, seed), fewbit_hipx_mx_bytes bytes,
+ * 16-byte aligned; NULL: h alone, the same bytes, no seed is read.
+ * fewbit_hipx_mx_act_backward: ONE launch.  u^: the decode of the state.  du = round(gh * act'(u^)), h^ = round(act(u^)), each in fp32 and rounded
+ * once to `dtype`.  Written: du (row stride ld_du) and two buffers of rows x width, 16-byte aligned, of fewbit_hipx_mx_bytes bytes each:
+ *   du_cells       = fewbit_hipx_mx_pack(du, format 8, role 1, seed_du)
+ *   product_cells  = fewbit_hipx_mx_pack(h^, `format`, role 0, seed_product); h^ itself is never written
+ * Any of the three outputs may be NULL: it is not written.  A state cell with scale byte 0xFF makes du and h^ NaN on its 32 rows of that column, and
+ * the cells written from them are poisoned by the rule of the pack.  Rows and columns outside the matrix count as +0.
+ * seed_device: NULL, or the seeds in device memory in the order of the seed arguments (one word forward, two backward; 8-byte aligned), read when
+ * the kernel runs.  Three tensors are rounded and no two of one role may share a seed.
+ * Refused before anything is launched (FEWBIT_ERR_INVALID_ARGUMENT), in the order of fewbit_hipx_mx_glu_*: an unknown dtype or activation, a format
+ * other than 4 and 6, a misaligned seed word, width > 2^23, rows * width > 2^36, null u, h, gh or (backward) state, ld < width, misaligned
+ * pointers, a state that is too small.  rows * width = 0: FEWBIT_OK, nothing is launched.  No atomics, no workspace: the same arguments give the
+ * same bytes; every call can be captured. */
+enum fewbit_mxact { FEWBIT_MXACT_GELU = 0, FEWBIT_MXACT_GELU_TANH = 1, FEWBIT_MXACT_RELU = 2, FEWBIT_MXACT_SILU = 3 };
+int fewbit_hipx_mx_act_forward(int dtype, int act, const void *u, size_t ld_u, size_t rows, size_t width, int format, uint64_t seed, const uint64_t *seed_device,
+                               void *h, size_t ld_h, uint8_t *state, size_t state_bytes, void *stream);
+int fewbit_hipx_mx_act_backward(int dtype, int act, const void *gh, size_t ld_gh, const uint8_t *state, size_t state_bytes, size_t rows, size_t width, int format,
+                                uint64_t seed_du, uint64_t seed_product, const uint64_t *seed_device, void *du, size_t ld_du, uint8_t *du_cells,
+                                uint8_t *product_cells, void *stream);
 
 #ifdef __cplusplus
 }
