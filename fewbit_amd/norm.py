@@ -601,8 +601,65 @@ class _RMSNormLinearMX(torch.autograd.Function):
         return (grad_input, grad_gamma, None, None, None, None, *grad_weights, *grad_biases)
 
 
+def _mx_kernels_take(flat: torch.Tensor, gamma: torch.Tensor) -> bool:
+    """whether the kernels of fewbit_mxnorm.hip serve the rows of ``flat`` with ``gamma``"""
+    return linear._kernels_take(flat) and 1 <= flat.shape[1] <= cabi_x.MX_NORM_MAX_WIDTH and gamma.device == flat.device and gamma.dtype in DTYPES
+
+
+class _AddRMSNormLinearMX(torch.autograd.Function):
+    """``tuple(F.linear(F.rms_norm(residual + dropout(input), gamma), W_i, b_i))`` as ONE node, with ``h = residual + dropout(input)`` behind the
+    tuple where ``prenorm``.  Kept for backward: what :class:`_RMSNormLinearMX` keeps -- the cells, ``rstd``, gamma and the weights; neither a mask nor
+    ``h``.  On ``ctx``: the call's ONE seed draw and ``p``: seed + 0 rounds the cells, seed + 1 + i the fp8 pack of ``G_i``, seed + 1 + count draws
+    the mask."""
+
+    @staticmethod
+    def forward(ctx, input, residual, gamma, eps: float, format: str, generator, p: float, prenorm: bool, count: int, *parameters):
+        weights, biases = parameters[:count], parameters[count:]
+        flat, res = input.detach().reshape(-1, input.shape[-1]), residual.detach().reshape(-1, input.shape[-1])
+        ctx.format, ctx.flat_shape, ctx.input_shape, ctx.input_dtype, ctx.count = format, tuple(flat.shape), input.shape, input.dtype, count
+        ctx.has_bias, ctx.p, ctx.prenorm = tuple(b is not None for b in biases), p, prenorm
+        ctx.autocast = linear._autocast_seen(input.device.type)
+        ctx.set_materialize_grads(False)
+        ctx.native = True                                       # (the caller has made sure that the kernels serve the call: rms_norm_linear_mx)
+        ctx.seed = linear._sketch_seed(generator, flat.device)
+        seeds = (_seed_plus(ctx.seed, 0), _seed_plus(ctx.seed, 1 + count))
+        seeds = torch.cat(seeds) if isinstance(ctx.seed, torch.Tensor) else seeds           # (while capturing: the two device words side by side)
+        y, cells, rstd, h = cabi_x.mx_add_rms_norm_forward(linear._unit_stride(flat), linear._unit_stride(res), _as(gamma, flat.dtype), eps, format, seeds, p, prenorm)
+        ctx.save_for_backward(cells, rstd, gamma, *weights)
+        y = y.view(input.shape)
+        outputs = tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
+        return (*outputs, h.view(input.shape)) if prenorm else outputs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grad_outputs):
+        with linear._autocast_as(ctx.autocast):
+            return _AddRMSNormLinearMX._backward(ctx, grad_outputs)
+
+    @staticmethod
+    def _backward(ctx, grad_outputs):
+        cells, rstd, gamma, *weights = ctx.saved_tensors        # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
+        (rows, width), count, format, needs = ctx.flat_shape, ctx.count, ctx.format, ctx.needs_input_grad
+        grads = [None if g is None else linear._dense_rows(g).reshape(rows, -1) for g in grad_outputs]
+        at_h = grads.pop() if ctx.prenorm else None             # the gradient that arrives at the sum: it goes into the kernel as gh
+        gy, grad_weights, grad_biases = _linears_backward(ctx, cells, gamma, None, weights, grads, any(needs[:3]), 9)
+        if gy is None and at_h is not None and (needs[0] or needs[1]):
+            gy = torch.zeros_like(at_h)                         # (nothing arrived at a linear: the norm hands on 0, to which at_h is added and masked)
+        grad_input = grad_residual = grad_gamma = None
+        if gy is not None:
+            want = (needs[1], needs[0], needs[2])               # (dres: the residual's gradient; dbranch: the input's)
+            gy = gy if gy.dtype in DTYPES else gy.float()
+            gy = gy if at_h is None or at_h.dtype == gy.dtype else gy.to(at_h.dtype)        # (under autocast: h has the input's dtype)
+            dres, dbranch, dgamma = cabi_x.mx_add_rms_norm_backward(gy, cells, rstd, _as(gamma, gy.dtype), format, _seed_plus(ctx.seed, 1 + count), ctx.p, at_h, want)
+            grad_input = dbranch.to(ctx.input_dtype).view(ctx.input_shape) if want[1] else None
+            grad_residual = dres.to(ctx.input_dtype).view(ctx.input_shape) if want[0] else None
+            grad_gamma = dgamma.to(gamma.dtype).view(gamma.shape) if want[2] else None
+        return (grad_input, grad_residual, grad_gamma, None, None, None, None, None, None, *grad_weights, *grad_biases)
+
+
 def rms_norm_linear_mx(input: torch.Tensor, norm_weight: torch.Tensor, weights: Sequence[torch.Tensor], biases: Optional[Sequence[Optional[torch.Tensor]]] = None,
-                       eps: Optional[float] = None, format: str = 'fp4', generator: Optional[torch.Generator] = None) -> tuple:
+                       eps: Optional[float] = None, format: str = 'fp4', generator: Optional[torch.Generator] = None,
+                       residual: Optional[torch.Tensor] = None, p: float = 0.0, training: bool = True, prenorm: bool = False) -> tuple:
     """``tuple(F.linear(F.rms_norm(input, (width, ), norm_weight, eps), W, b) for W, b in zip(weights, biases))`` as ONE node that keeps ONE buffer for
     all of it: the normalized rows ``x^ = x * rstd`` as MXFP4 (``format='fp4'``) or MXFP6 (``'fp6'``) cells down their columns, one fp32 ``rstd``
     per row, ``norm_weight`` and the weights -- at width 4096 and fp4 2180 bytes a token, where ``QuantizedRMSNorm(bits=4)`` in front of three
@@ -618,34 +675,58 @@ def rms_norm_linear_mx(input: torch.Tensor, norm_weight: torch.Tensor, weights: 
     * Widths above 8192, host tensors and float64 take the host route: the same definitions on ``cabi_x.mx_pack_host``.
     * Grad mode off, or nothing that requires grad: plain ``F.rms_norm`` and ``F.linear``; no seed is drawn, nothing is kept.
     * ``eps=None`` means ``torch.finfo(input.dtype).eps``, as in :func:`rms_norm_quantized`.  Under ``torch.autocast`` the norm runs in the input's
-      dtype and the linears as autocast casts them; backward runs under the state the forward saw."""
+      dtype and the linears as autocast casts them; backward runs under the state the forward saw.
+    * ``residual`` (of the input's shape): the norm reads ``h = residual + dropout(input, p, training)``, a sublayer's entry, still as ONE node with
+      ONE seed draw (the mask takes it plus 1 + the number of weights) on one launch forward (``cabi_x.mx_add_rms_norm_forward``); backward adds
+      the gradient arriving at ``h`` and applies the mask inside the norm's kernel.  Kept: the same tensors -- no mask and not ``h``.  With
+      ``prenorm=True`` ``h`` is the LAST element of the returned tuple (the residual stream that goes on).  The values are bit for bit those of
+      :func:`fewbit.functional.dropout_add` followed by this function.  A mask at a width that is no multiple of 8, widths above 8192, host
+      tensors, float64, a residual of another dtype or device and ``use_native_sketch(False)`` ARE that composition (two nodes, two seeds)."""
     linear._check_mx_format(format)
     weights = tuple(weights)
     biases = (None, ) * len(weights) if biases is None else tuple(biases)
     if len(biases) != len(weights) or not weights:
         raise ValueError(f'{len(weights)} weights and {len(biases)} biases: one bias (or None) per weight is needed, and at least one weight')
     eps = float(torch.finfo(input.dtype).eps if eps is None else eps)
-    if not kept.trains(input, norm_weight, *weights, *biases) or input.numel() == 0:
-        y = F.rms_norm(input, (input.shape[-1], ), norm_weight, eps)
-        return tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
-    return _RMSNormLinearMX.apply(input, norm_weight, eps, format, generator, len(weights), *weights, *biases)
+    if residual is None:
+        if not kept.trains(input, norm_weight, *weights, *biases) or input.numel() == 0:
+            y = F.rms_norm(input, (input.shape[-1], ), norm_weight, eps)
+            return tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
+        return _RMSNormLinearMX.apply(input, norm_weight, eps, format, generator, len(weights), *weights, *biases)
+    _check_p(p)
+    if tuple(residual.shape) != tuple(input.shape):
+        raise ValueError(f'residual should have the shape of input, {tuple(input.shape)}, but got {tuple(residual.shape)}.')
+    p = float(p) if training else 0.0
+    trains = kept.trains(input, residual, norm_weight, *weights, *biases) and input.numel() != 0
+    flat = input.detach().reshape(-1, input.shape[-1]) if trains else None
+    if (not trains or not _mx_kernels_take(flat, norm_weight) or residual.dtype != input.dtype or residual.device != input.device
+            or (cabi_x.dropout_threshold(p) > 0 and flat.shape[1] % 8 != 0)):
+        # nothing trains (plain torch behind the sum), or the kernels do not serve the call: the composition, whose second half is the call without a residual
+        h = dropout_add(input, residual, p, training, generator)
+        outputs = rms_norm_linear_mx(h, norm_weight, weights, biases, eps, format, generator)
+        return (*outputs, h) if prenorm else outputs
+    return _AddRMSNormLinearMX.apply(input, residual, norm_weight, eps, format, generator, p, bool(prenorm), len(weights), *weights, *biases)
 
 
 class MXNormLinear(torch.nn.Module):
     r"""An RMS norm and the linear layers that read its output -- q / k / v behind the norm at the head of an attention block -- as one module that
     keeps ONE set of MXFP4 / MXFP6 cells for all of them (:func:`rms_norm_linear_mx`); ``forward`` returns the tuple of the linears' outputs.  The
     linears are plain ``nn.Linear`` layers in ``self.linears``, the norm's weight is ``self.weight``.  In ``eval()`` mode gradients are torch's exact
-    ones and nothing is kept.
+    ones and nothing is kept.  ``forward(input, residual)`` normalizes ``residual + dropout(input, p)`` in the same node (``p``, ``prenorm``: as in
+    :func:`rms_norm_linear_mx`; with ``prenorm=True`` the sum is the last element of the tuple).
 
         >>> m = fewbit.MXNormLinear(64, [(64, 96, False), (64, 32, False), (64, 32, False)], eps=1e-6)
         >>> q, k, v = m(torch.randn(128, 64))
+        >>> q, k, v, stream = fewbit.MXNormLinear(64, [(64, 64, False)] * 3, p=0.1, prenorm=True)(mlp_output, stream)
         >>> m = fewbit.MXNormLinear.from_modules(block.input_layernorm, [attn.q_proj, attn.k_proj, attn.v_proj], format='fp4')
     """
 
     def __init__(self, norm_weight_shape, linears, eps: Optional[float] = None, format: str = 'fp4', generator: Optional[torch.Generator] = None,
-                 device=None, dtype=None) -> None:
+                 device=None, dtype=None, p: float = 0.0, prenorm: bool = False) -> None:
         linear._check_mx_format(format)
+        _check_p(p)
         super().__init__()
+        self.p, self.prenorm = float(p), bool(prenorm)
         width = norm_weight_shape if isinstance(norm_weight_shape, int) else math.prod(norm_weight_shape)
         self.weight = torch.nn.Parameter(torch.ones(width, device=device, dtype=dtype))
         self.linears = torch.nn.ModuleList(torch.nn.Linear(fin, fout, bias, device=device, dtype=dtype) for fin, fout, bias in linears)
@@ -655,26 +736,28 @@ class MXNormLinear(torch.nn.Module):
 
     @classmethod
     def from_modules(cls, norm: torch.nn.Module, linears: Sequence[torch.nn.Linear], format: str = 'fp4',
-                     generator: Optional[torch.Generator] = None) -> 'MXNormLinear':
+                     generator: Optional[torch.Generator] = None, p: float = 0.0, prenorm: bool = False) -> 'MXNormLinear':
         """An ``MXNormLinear`` that SHARES the weight of ``norm`` -- a ``torch.nn.RMSNorm``, or any module with a 1-D ``weight`` and a float
         ``variance_epsilon`` or ``eps`` -- and the given ``nn.Linear`` modules themselves"""
         weight, eps = getattr(norm, 'weight', None), getattr(norm, 'variance_epsilon', getattr(norm, 'eps', None))
         if not isinstance(weight, torch.Tensor) or weight.dim() != 1 or not (eps is None or isinstance(eps, float)):
             raise TypeError(f'{type(norm).__name__} has no 1-D weight with a float variance_epsilon or eps')
-        new = cls(weight.numel(), [], eps, format, generator, device='meta')
+        new = cls(weight.numel(), [], eps, format, generator, device='meta', p=p, prenorm=prenorm)
         new.weight, new.linears = weight, torch.nn.ModuleList(linears)
         return new.train(norm.training)
 
-    def forward(self, input: torch.Tensor) -> tuple:
+    def forward(self, input: torch.Tensor, residual: Optional[torch.Tensor] = None) -> tuple:
         weights, biases = [m.weight for m in self.linears], [m.bias for m in self.linears]
-        if not self.training:
+        if not self.training:                                   # (eval: the dropout is off, torch's exact gradients on residual + input)
             eps = float(torch.finfo(input.dtype).eps if self.eps is None else self.eps)
-            y = F.rms_norm(input, (input.shape[-1], ), self.weight, eps)
-            return tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
-        return rms_norm_linear_mx(input, self.weight, weights, biases, self.eps, self.format, self.generator)
+            h = input if residual is None else residual + input
+            y = F.rms_norm(h, (h.shape[-1], ), self.weight, eps)
+            outputs = tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
+            return (*outputs, h) if residual is not None and self.prenorm else outputs
+        return rms_norm_linear_mx(input, self.weight, weights, biases, self.eps, self.format, self.generator, residual, self.p, True, self.prenorm)
 
     def extra_repr(self) -> str:
-        return f'{self.weight.numel()}, eps={self.eps}, format={self.format}'
+        return f'{self.weight.numel()}, eps={self.eps}, format={self.format}' + (f', p={self.p}, prenorm={self.prenorm}' if self.p or self.prenorm else '')
 
 
 # ---- the LAYER norm and the linears behind it on ONE set of MX cells: y = x^ * gamma + beta, so dW_i takes one rank-one term in beta more -----------------

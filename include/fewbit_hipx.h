@@ -62,7 +62,9 @@ extern "C" {
  * So were the centred normalized rows as row blocks (fewbit_hipx_mx_layer_norm_workspace, _mx_layer_norm_forward, _mx_layer_norm_backward): inside
  * revision 2, recognised by the presence of the symbols.
  * So was the pre-activation as row blocks (fewbit_hipx_mx_act_forward, _mx_act_backward): inside revision 2, recognised by the presence of the
- * symbols. */
+ * symbols.
+ * So was the sum of a seed in front of the normalized rows (fewbit_hipx_mx_add_rms_norm_forward, _mx_add_rms_norm_backward): inside revision 2,
+ * recognised by the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -753,6 +755,39 @@ int fewbit_hipx_mx_rms_norm_forward(int dtype, const void *x, size_t ld_x, size_
 int fewbit_hipx_mx_rms_norm_backward(int dtype, const void *gy, size_t ld_gy, const uint8_t *cells, size_t cells_bytes, const float *rstd,
                                      const void *gamma, size_t rows, size_t width, int format, void *dx, size_t ld_dx, float *dgamma, void *workspace,
                                      size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The sum of a seed in front of the normalized rows: a sublayer's entry on MX cells, y = rms_norm(residual + dropout(x)), as ONE launch forward and
+ * ONE (and the small one of dgamma) backward, in the same unit.  Nothing new is defined: every output is bit for bit what fewbit_hipx_dropout
+ * followed by the plain entry point above gives.
+ *     T = threshold (0 .. 65536, in units of 2^-16: fewbit_hipx_dropout_threshold), scale = float32(65536 / (65536 - T)), 0 for T = 65536
+ *     keep(i) = the mask of seed_mask at flat index i = r * width + c of the contiguous rows x width index (first = 0), whatever the row strides
+ *   forward:
+ *     h       = keep ? round_to_dtype(float(x) * scale + float(residual)) : residual (its bits)        T = 0: every element is kept, nothing is drawn
+ *     y, rstd, cells: those of fewbit_hipx_mx_rms_norm_forward on h AS ROUNDED with `seed` (the row sums in its order)
+ *     h_out   NULL, or rows x width of `dtype` (row stride ld_h) that receive h (post-norm: nobody else reads the sum, so it never exists in memory)
+ *   backward:
+ *     dx      = what fewbit_hipx_mx_rms_norm_backward writes, rounded to `dtype` as it rounds it
+ *     dres    = gh != NULL ? round_to_dtype(float(dx) + float(gh)) : dx          gh: NULL, or the gradient arriving at h (row stride ld_gh)
+ *     dbranch = keep ? round_to_dtype(float(dres) * scale) : +0                  fewbit_hipx_dropout of dres, no addend
+ *     dres is the gradient of the residual, dbranch that of x.  With T = 0 they are the same values: dbranch must be NULL then.
+ *     dgamma: that of the plain backward (the same partial sums in the same workspace of fewbit_hipx_mx_rms_norm_workspace bytes, the same second launch).
+ *   dres, dbranch and dgamma may each be NULL: that output is skipped and nothing of it is written.
+ * The mask is drawn on blocks of eight FLAT elements and a lane holds eight elements of a ROW: with T > 0 the width must be a multiple of 8
+ * (anything else: FEWBIT_ERR_UNSUPPORTED; compose the two calls).  With T = 0 every width 1 .. 8192 is served.
+ * seed_device: NULL, or the seeds in device memory in the order of the seed arguments (forward: two words, the cells' and the mask's; backward: the
+ * mask's one word; 8-byte aligned), read when the kernel runs.  No output may overlap an input or another output.
+ * Refused before anything is launched, in the order of the plain pair: what it refuses, and on top a threshold beyond 65536, a mask at a width that
+ * is no multiple of 8, a NULL residual, ld_residual / ld_h / ld_gh / ld_dres / ld_dbranch < width, residual / h_out / gh / dres / dbranch not
+ * aligned to their element, dbranch with T = 0. */
+int fewbit_hipx_mx_add_rms_norm_forward(int dtype, const void *x, size_t ld_x, const void *residual, size_t ld_residual, size_t rows, size_t width,
+                                        const void *gamma, float eps, int format, uint64_t seed, uint64_t seed_mask, const uint64_t *seed_device,
+                                        uint32_t threshold, void *y, size_t ld_y, void *h_out, size_t ld_h, float *rstd, uint8_t *cells, size_t cells_bytes,
+                                        void *stream);
+int fewbit_hipx_mx_add_rms_norm_backward(int dtype, const void *gy, size_t ld_gy, const void *gh, size_t ld_gh, const uint8_t *cells, size_t cells_bytes,
+                                         const float *rstd, const void *gamma, size_t rows, size_t width, int format, uint64_t seed_mask,
+                                         const uint64_t *seed_device, uint32_t threshold, void *dres, size_t ld_dres, void *dbranch, size_t ld_dbranch,
+                                         float *dgamma, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * The centred normalized rows as row blocks: the LAYER norm in front of linear layers whose weight gradients come from fewbit_hipx_mx_wgrad.  The
