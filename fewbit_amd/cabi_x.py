@@ -27,7 +27,8 @@ __all__ = ['LIB_PATH', 'ABI_VERSION', 'REVISION', 'SYMBOLS', 'lib', 'sampled_dft
            'mx_wgrad_workspace', 'mx_wgrad', 'mx_glu_state_bytes', 'mx_glu_forward', 'mx_glu_backward', 'MX_ACTIVATIONS', 'mx_act_forward', 'mx_act_backward', 'MX_NORM_MAX_WIDTH', 'MX_NORM_PLAN_WIDTHS', 'MX_NORM_MAX_GRID',
            'mx_rms_norm_workspace', 'mx_rms_norm_host', 'mx_rms_norm_backward_host', 'mx_rms_norm_forward', 'mx_rms_norm_backward',
            'mx_layer_norm_workspace', 'mx_layer_norm_host', 'mx_layer_norm_backward_host', 'mx_layer_norm_forward', 'mx_layer_norm_backward',
-           'mx_add_rms_norm_host', 'mx_add_rms_norm_backward_host', 'mx_add_rms_norm_forward', 'mx_add_rms_norm_backward']
+           'mx_add_rms_norm_host', 'mx_add_rms_norm_backward_host', 'mx_add_rms_norm_forward', 'mx_add_rms_norm_backward',
+           'mx_add_layer_norm_host', 'mx_add_layer_norm_backward_host', 'mx_add_layer_norm_forward', 'mx_add_layer_norm_backward']
 
 LIB_PATH = Path(os.environ.get('FEWBIT_HIPX_LIB') or Path(__file__).resolve().with_name('libfewbit_hipx.so'))
 ABI_VERSION = 1                                # FEWBIT_HIPX_ABI_VERSION this binding was written against
@@ -130,6 +131,11 @@ _SIGNATURES = {
                                                    _vp, _sz, _vp]),
     'fewbit_hipx_mx_add_rms_norm_backward': (_i32, [_i32, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _sz, _i32, _u64, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _vp, _sz,
                                                     _vp]),
+    # the sum of a seed in front of the centred normalized rows (the same fusion on the layer norm's pair): inside revision 2 as well
+    'fewbit_hipx_mx_add_layer_norm_forward': (_i32, [_i32, _vp, _sz, _vp, _sz, _sz, _sz, _vp, _vp, ctypes.c_float, _i32, _u64, _u64, _vp, _u32, _vp, _sz, _vp, _sz,
+                                                     _vp, _vp, _vp, _sz, _vp]),
+    'fewbit_hipx_mx_add_layer_norm_backward': (_i32, [_i32, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _sz, _i32, _u64, _vp, _u32, _vp, _sz, _vp, _sz,
+                                                      _vp, _vp, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -1721,3 +1727,108 @@ def mx_layer_norm_backward(gy: torch.Tensor, cells: torch.Tensor, rstd: torch.Te
                                                         gamma.data_ptr(), rows, width, MX_FORMATS[format], _ptr(dx), ld_dx, _ptr(dgamma), _ptr(dbeta),
                                                         _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream(stream, gy.device)))
     return dx, dgamma, dbeta
+
+
+# ---- the sum of a seed in front of the centred normalized rows (fewbit_amd/csrc/fewbit_mxlnorm.hip): layer_norm(residual + dropout(x)) on the same cells ----
+def mx_add_layer_norm_host(x: torch.Tensor, residual: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor], eps: float, format: str, seeds,
+                           p: float = 0.0, mean: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None):
+    """``mx_add_layer_norm_forward`` evaluated with plain torch -> ``(y, cells, rstd, h, mean)``: ``h = where(keep, x * scale + residual, residual)`` in
+    fp32 (float64 for a float64 ``x``) rounded once, with ``keep = dropout_keep(seeds[1], rows * width, p)``, then ``mx_layer_norm_host(h, ...,
+    seeds[0])``.  No GPU needed."""
+    keep, scale = _mask_and_scale(seeds[1], x.shape, p, x)
+    work = _work_dtype(x)
+    h = (x.detach().to(work) * scale + residual.detach().to(work)).to(x.dtype)
+    if keep is not None:
+        h = torch.where(keep, h, residual.detach())
+    y, cells, rstd, mean = mx_layer_norm_host(h, gamma, beta, eps, format, seeds[0], mean, rstd)
+    return y, cells, rstd, h, mean
+
+
+def mx_add_layer_norm_backward_host(gy: torch.Tensor, cells: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, format: str, seed: int = 0,
+                                    p: float = 0.0, gh: Optional[torch.Tensor] = None, gy_add: Optional[torch.Tensor] = None):
+    """``mx_add_layer_norm_backward`` evaluated with plain torch -> ``(dres, dbranch, dgamma, dbeta)``: ``mx_layer_norm_backward_host`` of ``gy +
+    gy_add`` as torch adds them, then ``dres = dx + gh``, then ``dbranch = where(keep, dres * scale, 0)`` for the mask of ``seed`` (``dres`` itself
+    where ``p`` keeps everything)."""
+    g = gy.detach() if gy_add is None else gy.detach() + gy_add.detach().to(gy.dtype)
+    dx, dgamma, dbeta = mx_layer_norm_backward_host(g, cells, rstd, gamma, format)
+    dres = dx if gh is None else dx + gh.detach().to(dx.dtype)
+    keep, scale = _mask_and_scale(seed, gy.shape, p, gy)
+    if keep is None:
+        return dres, dres, dgamma, dbeta
+    return dres, torch.where(keep, (dres.to(_work_dtype(gy)) * scale).to(dres.dtype), torch.zeros((), dtype=dres.dtype, device=dres.device)), dgamma, dbeta
+
+
+def mx_add_layer_norm_forward(x: torch.Tensor, residual: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor], eps: float, format: str, seeds,
+                              p: float = 0.0, want_h: bool = False, y: Optional[torch.Tensor] = None, h: Optional[torch.Tensor] = None,
+                              rstd: Optional[torch.Tensor] = None, cells: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None,
+                              stream: Optional[int] = None):
+    """``mx_layer_norm_forward`` of ``h = residual + dropout(x)`` in ONE launch -> ``(y, cells, rstd, h, mean)``, every output bit for bit what
+    ``dropout_apply(x, seeds[1], p, addend=residual)`` followed by ``mx_layer_norm_forward(h, ..., seeds[0])`` gives.  ``x``, ``residual``: 2-D of
+    one shape and dtype, unit stride along the width, any row strides.  ``h`` is None unless ``want_h`` (post-norm the sum is never in memory).
+    ``seeds``: two different ints (the cells', the mask's), or one int64 tensor of two words on the device.  With a mask (``dropout_threshold(p) >
+    0``) the width must be a multiple of 8.  ``y``, ``h`` (any row stride), ``rstd``, ``cells``, ``mean``: buffers to write into."""
+    name = 'mx_add_layer_norm_forward'
+    rows, width, ld_x, need = _mx_norm_call(name, x, gamma, format)
+    values, words, others = _mx_glu_call(name, x, format, seeds, 2)[4:]
+    if residual.shape != x.shape or residual.dtype != x.dtype:
+        raise FewbitHipError('residual must have the shape and dtype of x')
+    ld_res = _glu_rows(residual, 'residual')[2]
+    with _on(x.device):
+        y = _mx_glu_out(y, x, 'y')
+        h = _mx_glu_out(h, x, 'h') if want_h else None
+        ld_y, ld_h = _glu_rows(y, 'y')[2], 0 if h is None else _glu_rows(h, 'h')[2]
+        mean = _norm_out(mean, (rows, ), torch.float32, x.device, 'mean')
+        rstd = _norm_out(rstd, (rows, ), torch.float32, x.device, 'rstd')
+        cells = _state_to_write(cells, True, need, x.device, 'cells')
+        _same_device(x, residual, gamma, y, mean, rstd, cells, *others, *(t for t in (beta, h) if t is not None))
+        _check(lib().fewbit_hipx_mx_add_layer_norm_forward(DTYPES[x.dtype], x.data_ptr(), ld_x, residual.data_ptr(), ld_res, rows, width, gamma.data_ptr(),
+                                                           _norm_vector(beta, x, 'beta'), float(eps), MX_FORMATS[format], *values, words, dropout_threshold(p),
+                                                           y.data_ptr(), ld_y, _ptr(h), ld_h, mean.data_ptr(), rstd.data_ptr(), cells.data_ptr(),
+                                                           cells.numel(), _stream(stream, x.device)))
+    return y, cells, rstd, h, mean
+
+
+def mx_add_layer_norm_backward(gy: torch.Tensor, cells: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, format: str, seed=0, p: float = 0.0,
+                               gh: Optional[torch.Tensor] = None, want=(True, True, True, True), gy_add: Optional[torch.Tensor] = None,
+                               dres: Optional[torch.Tensor] = None, dbranch: Optional[torch.Tensor] = None, dgamma: Optional[torch.Tensor] = None,
+                               dbeta: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+    """The gradients of ``mx_add_layer_norm_forward`` in one launch (and the small one of the two sums) -> ``(dres, dbranch, dgamma, dbeta)``: with
+    ``g = gy + gy_add`` as torch adds them (``gy_add``: None, or the gradient arriving at the norm's own output) and ``dx``, ``dgamma``, ``dbeta``
+    what ``mx_layer_norm_backward`` makes of ``g``, ``dres = dx + gh`` (``gh``: None, or the gradient arriving at ``h``) is the gradient of the
+    residual and ``dbranch = dropout_apply(dres, seed, p)`` that of ``x``.  ``gy_add``, ``gh``: of the shape and dtype of ``gy``, any row stride.
+    ``seed``: the mask's (an int or one int64 word on the device).  Where ``p`` keeps everything ``dbranch`` IS ``dres`` (the same tensor; it is
+    made if either is wanted).  Where ``want`` is False the output is None and is not written."""
+    name = 'mx_add_layer_norm_backward'
+    rows, width, ld_gy, need = _mx_norm_call(name, gy, gamma, format)
+    want_dres, want_dbranch, want_dgamma, want_dbeta = (bool(w) for w in want)
+    threshold = dropout_threshold(p)
+    if threshold == 0:
+        want_dres, want_dbranch = want_dres or want_dbranch, False
+    value, word, others = _seed_arguments(seed)
+    _state_to_read(cells, need, 'cells')
+    if rstd.dtype != torch.float32 or rstd.numel() != rows or not rstd.is_contiguous():
+        raise FewbitHipError(f'rstd must be a contiguous float32 tensor of {rows} elements')
+    for t, what in ((gh, 'gh'), (gy_add, 'gy_add')):
+        if t is not None and (t.shape != gy.shape or t.dtype != gy.dtype):
+            raise FewbitHipError(f'{what} must have the shape and dtype of gy')
+    ld_gh, ld_add = (0 if t is None else _glu_rows(t, what)[2] for t, what in ((gh, 'gh'), (gy_add, 'gy_add')))
+    with _on(gy.device):
+        dres = _mx_glu_out(dres, gy, 'dres') if want_dres else None
+        dbranch = _mx_glu_out(dbranch, gy, 'dbranch') if want_dbranch else None
+        ld_dres, ld_dbranch = (0 if t is None else _glu_rows(t, what)[2] for t, what in ((dres, 'dres'), (dbranch, 'dbranch')))
+        dgamma = _norm_out(dgamma, (width, ), torch.float32, gy.device, 'dgamma') if want_dgamma else None
+        dbeta = _norm_out(dbeta, (width, ), torch.float32, gy.device, 'dbeta') if want_dbeta else None
+        if (want_dgamma or want_dbeta) and workspace is None:
+            workspace = torch.empty(mx_layer_norm_workspace(rows, width), dtype=torch.uint8, device=gy.device)
+        elif workspace is not None and (workspace.dtype != torch.uint8 or not workspace.is_contiguous()):
+            raise FewbitHipError('workspace must be a contiguous uint8 tensor')
+        _same_device(gy, cells, rstd, gamma, *others, *(t for t in (gy_add, gh, dres, dbranch, dgamma, dbeta, workspace) if t is not None))
+        _check(lib().fewbit_hipx_mx_add_layer_norm_backward(DTYPES[gy.dtype], gy.data_ptr(), ld_gy, _ptr(gy_add), ld_add, _ptr(gh), ld_gh, cells.data_ptr(),
+                                                            cells.numel(), rstd.data_ptr(), gamma.data_ptr(), rows, width, MX_FORMATS[format], value, word,
+                                                            threshold, _ptr(dres), ld_dres, _ptr(dbranch), ld_dbranch, _ptr(dgamma), _ptr(dbeta),
+                                                            _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream(stream, gy.device)))
+    if threshold == 0 and bool(want[1]):
+        dbranch = dres
+    if threshold == 0 and not bool(want[0]):
+        dres = None
+    return dres, dbranch, dgamma, dbeta

@@ -42,6 +42,28 @@
 // block of 8192 columns is 32 tiles a lane), and phase B keeps its two barriers a round.
 // Rows beyond `rows` count as +0 (their mean and rstd are taken as 0), columns beyond `width` are neither rounded into a stored cell nor stored.
 // Roofline class: memory (forward reads x once from memory and twice from L2, writes y and 0.27 / 0.39 of it in cells).
+//
+// The sum of a seed in front of it (include/fewbit_hipx.h, "The sum of a seed in front of the centred normalized rows"): h = residual + dropout(x)
+// normalized in the same launch, and the gradients of both behind the norm's backward:
+//
+//     mx_add_layer_norm_forward    x, residual, gamma, beta -> y, mean, rstd, the cells of h^ and, where asked for, h                      ONE launch
+//     mx_add_layer_norm_backward   gy, [gy_add], [gh], the cells, rstd, gamma -> dres, dbranch, the column sums -> dgamma, dbeta
+//                                                                                                              ONE launch and a small one
+//
+// Two kernels of their own (add_forward_kernel, add_backward_kernel) beside the plain pair, whose text and code stay as they were; the walk, the
+// roles, the barriers and every sum's order are the plain kernels', so that every output is bit for bit fewbit_hipx_dropout with the residual as
+// addend, the plain entry point, and torch's addition of two tensors.  What the fusion had to settle:
+//   h thrice   the centred statistic takes two passes over a row and the tiles a third; each forms h = narrow(x scale + residual) from x, the
+//              residual and the mask (mxrows::sum_piece: two 16-byte loads and one Philox call per eight elements), and because h is ROUNDED to the
+//              dtype before anything reads it the three agree bit for bit.  x and the residual come from memory once and from L2 twice.  Nothing of
+//              a row is held between the passes and h is never read back: ONE plan at every width, with or without h_out, which the tile pass
+//              stores (its lanes hold the piece they store anyway; phase A's waves would write the same lines a second way).
+//   the mask   is drawn on blocks of eight FLAT elements; with width % 8 == 0 a lane's piece in the load role is one flat block in all three
+//              walks.  threshold = 0 draws nothing and serves every width; a mask at another width is refused.
+//   gy_add     the gradient that arrives at the norm's own output (y feeds the next residual, post-norm) is added where a piece of gy is
+//              loaded, in BOTH phases, rounded to the dtype as torch's gy.add_ rounds it: the row sums, dx and both column sums see the same g.
+//   backward   phase B rounds dx as the plain kernel does, adds gh as torch adds two tensors -> dres, and draws the piece's mask for
+//              dbranch = keep ? narrow(dres scale) : +0.  With threshold = 0 dbranch is dres and must be absent.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -323,6 +345,280 @@ __global__ __launch_bounds__(kThreads) void column_sums_kernel(const float *__re
     add_partials(partials + blockIdx.y * width, parts, kSums * width, width, blockIdx.x, dst, waves);
 }
 
+// ---- the sum of a seed in front of the norm: h = residual + dropout(x), and the gradients of the two behind the norm's backward -------------------
+struct AddForwardArgs {
+    const void *x, *residual;
+    size_t ld_x, ld_res, rows, width;
+    const void *gamma, *beta;               // beta may be absent: it counts as 0 and nothing is added
+    float eps;
+    Key key, mask_key;
+    const Key *device;                      // nullptr, or the two keys in device memory: the cells', then the mask's
+    uint32_t threshold;
+    float scale;
+    void *y, *h;                            // h may be absent: it is then not written
+    size_t ld_y, ld_h;
+    float *mean, *rstd;                     // mean may be absent
+    uint8_t *cells;
+    size_t blocks;
+    bool vec_x, vec_res, vec_y, vec_h, vec_gamma, vec_beta;
+};
+struct AddBackwardArgs {
+    const void *gy, *gy_add, *gh;           // gy_add and gh may each be absent: nothing is added
+    size_t ld_gy, ld_add, ld_gh;
+    const uint8_t *cells;
+    const float *rstd;
+    const void *gamma;
+    size_t rows, width;
+    Key mask_key;
+    const Key *device;                      // nullptr, or the mask's key in device memory
+    uint32_t threshold;
+    float scale;
+    void *dres, *dbranch;                   // may each be absent, and so may partials: what is absent is not written
+    size_t ld_dres, ld_dbranch;
+    float *partials;
+    size_t blocks;
+    bool vec_in, vec_out, vec_gamma;        // 16-byte pieces serve every gradient that is read (gy, gy_add, gh) / every one that is written
+};
+
+// v, as a value the compiler knows nothing about: what is computed from it is computed where it is used
+__device__ __forceinline__ int fresh(int v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+// forward_kernel with h = residual + dropout(x) in the place of x: formed in registers by each of the three passes (mxrows::sum_piece), stored by
+// the last where h is wanted
+template <int DT, int FMT>
+__global__ __launch_bounds__(kThreads) void add_forward_kernel(AddForwardArgs a) {
+    using T = typename Elem<DT>::type;
+    constexpr size_t kCell = mx::cell_bytes(FMT);
+    __shared__ float mean_s[kRows], rstd_s[kRows];
+    __shared__ uint32_t tile[kGroups][kRows][kTileCols];                        // the fp32 bits of h^
+    __shared__ uint32_t amax_s[kGroups][kOctets][kTileCols];
+    __shared__ uint64_t image[kGroups][kTileCols * kCell / 8];
+    const T *gamma = static_cast<const T *>(a.gamma), *beta = static_cast<const T *>(a.beta);
+    T *y = static_cast<T *>(a.y), *h_out = static_cast<T *>(a.h);
+    Key key = a.key, mask_key = a.mask_key;
+    if (a.device != nullptr) key = a.device[0], mask_key = a.device[1];
+    const size_t rows = a.rows, width = a.width;
+    uint8_t *codes = a.cells + mx::codes_offset(rows, width);
+    const size_t across = (width + kTileCols - 1) / kTileCols, rounds = (across + kGroups - 1) / kGroups, pieces = (width + kBlock - 1) / kBlock;
+    const float count = static_cast<float>(width);
+    for (size_t b = blockIdx.x; b < a.blocks; b += gridDim.x) {
+        // (each phase takes the lane's number afresh: what a phase derives from it -- indices, addresses, conditions -- is then not carried in
+        // registers through the other phase, which is what keeps this kernel within its 128 registers without scratch)
+        // ---- phase A: the two statistics of the block's rows of h, a wave per row, two passes that each form the row's h ----
+        const int wave = fresh(threadIdx.x) >> 6, lane = threadIdx.x & 63;
+        for (int lr = wave; lr < kRows; lr += kWaves) {
+            const size_t r = kRows * b + lr;
+            float s = 0.0f;
+            if (r < rows) {
+                for (size_t p = lane; p < pieces; p += 64) {
+                    T rh[kBlock];
+                    sum_piece<DT>(a, mask_key, r, kBlock * p, rh);
+#pragma unroll
+                    for (int k = 0; k < kBlock; ++k) s = add_rn(s, float_of_bits(widen<DT>(rh[k])));       // (a missing element: +0)
+                }
+            }
+            const float mean = div_rn(wave_sum(s), count);
+            float ss = 0.0f;
+            if (r < rows) {
+                for (size_t p = lane; p < pieces; p += 64) {
+                    T rh[kBlock];
+                    sum_piece<DT>(a, mask_key, r, kBlock * p, rh);
+#pragma unroll
+                    for (int k = 0; k < kBlock; ++k) {
+                        const float d = kBlock * p + k < width ? sub_rn(float_of_bits(widen<DT>(rh[k])), mean) : 0.0f;
+                        ss = add_rn(ss, mul_rn(d, d));
+                    }
+                }
+            }
+            const float rstd = div_rn(1.0f, sqrt_rn(add_rn(div_rn(wave_sum(ss), count), a.eps)));
+            if (lane == 0) {
+                mean_s[lr] = r < rows ? mean : 0.0f;
+                rstd_s[lr] = r < rows ? rstd : 0.0f;
+                if (r < rows) {
+                    a.rstd[r] = rstd;
+                    if (a.mean != nullptr) a.mean[r] = mean;
+                }
+            }
+        }
+        __syncthreads();
+        // ---- phase B: the block's tiles, four in flight ----
+        const int t = fresh(threadIdx.x), grp = t >> 8, u = t & (kGroupThreads - 1);
+        const int lrow = u >> 3, lcol = 8 * (u & 7);          // the load role
+        const int c = u & (kTileCols - 1), o = u >> 6;        // the rounding role: column c, row octet o
+        for (size_t round = 0; round < rounds; ++round) {
+            const size_t tl = round * kGroups + grp, j0 = tl * kTileCols;
+            const bool have = tl < across;                                      // (the same for every lane of a group; the barriers are outside)
+            const size_t cols = !have ? 0 : width - j0 < static_cast<size_t>(kTileCols) ? width - j0 : kTileCols;
+            if (have) {
+                const size_t r = kRows * b + lrow, col = j0 + lcol;
+                T rh[kBlock], rg[kBlock], rb[kBlock], ry[kBlock];
+                sum_piece<DT>(a, mask_key, r, col, rh);
+                if (h_out != nullptr) store_piece<DT>(h_out, a.ld_h, a.vec_h, r, col, rows, width, rh);
+                load_piece<DT>(gamma, 0, a.vec_gamma, 0, col, 1, width, rg);
+                if (beta != nullptr) load_piece<DT>(beta, 0, a.vec_beta, 0, col, 1, width, rb);
+                const float mean = mean_s[lrow], rstd = rstd_s[lrow];
+#pragma unroll
+                for (int k = 0; k < kBlock; ++k) {
+                    const float xhat = mul_rn(sub_rn(float_of_bits(widen<DT>(rh[k])), mean), rstd);
+                    const float scaled = mul_rn(xhat, float_of_bits(widen<DT>(rg[k])));
+                    ry[k] = narrow<DT>(beta != nullptr ? add_rn(scaled, float_of_bits(widen<DT>(rb[k]))) : scaled);
+                    tile[grp][lrow][lcol + k] = bits_of_float(xhat);
+                }
+                store_piece<DT>(y, a.ld_y, a.vec_y, r, col, rows, width, ry);
+            }
+            __syncthreads();
+            uint32_t v[kBlock];
+            if (have) column_amax(tile[grp], c, o, v, amax_s[grp]);
+            __syncthreads();
+            if (have) column_codes<FMT>(v, amax_s[grp], c, o, b, j0 + c, width, key, image[grp], a.cells);
+            __syncthreads();
+            store_cells<FMT>(image[grp], codes, b, j0, width, cols, u);
+            // (no barrier here: forward_kernel)
+        }
+    }
+}
+
+// backward_kernel with g = gy + gy_add in the place of gy, and dres = dx + gh and dbranch = the dropout's gradient of dres in the place of dx
+template <int DT, int FMT>
+__global__ __launch_bounds__(kThreads) void add_backward_kernel(AddBackwardArgs a) {
+    using T = typename Elem<DT>::type;
+    __shared__ uint32_t image[2][kGroups][image_words<FMT>()];
+    __shared__ uint64_t scale_s[2][kGroups][kTileCols / 8];
+    __shared__ float tile[kGroups][kSums][kTileFloats];                         // g * x^q, g
+    __shared__ float part_s[kSums][kGroups][kRows], c_s[kSums][kRows];
+    const T *gy = static_cast<const T *>(a.gy), *gy_add = static_cast<const T *>(a.gy_add), *gh = static_cast<const T *>(a.gh);
+    const T *gamma = static_cast<const T *>(a.gamma);
+    T *dres = static_cast<T *>(a.dres), *dbranch = static_cast<T *>(a.dbranch);
+    Key mask_key = a.mask_key;
+    if (a.device != nullptr) mask_key = *a.device;
+    const bool wanted = dres != nullptr || dbranch != nullptr;
+    const size_t rows = a.rows, width = a.width;
+    const uint8_t *codes = a.cells + mx::codes_offset(rows, width);
+    float *mine = a.partials != nullptr ? a.partials + static_cast<size_t>(blockIdx.x) * kSums * width : nullptr;
+    int t, grp, u, lrow, lcol;                            // the load role, taken afresh by each phase (add_forward_kernel)
+    auto take = [&] { t = fresh(threadIdx.x), grp = t >> 8, u = t & (kGroupThreads - 1), lrow = u >> 3, lcol = 8 * (u & 7); };
+    const size_t across = (width + kTileCols - 1) / kTileCols, rounds = (across + kGroups - 1) / kGroups;
+    const float count = static_cast<float>(width);
+    auto fetch = [&](int par, size_t b, size_t j0, size_t cols) {
+        load_image<FMT>(image[par][grp], codes, b, j0, width, cols, u);
+        if (static_cast<size_t>(u) < cols) reinterpret_cast<uint8_t *>(scale_s[par][grp])[u] = a.cells[b * width + j0 + u];
+    };
+    // the eight x^q, g = gy + gy_add as rounded to the dtype, and g^ of the lane's piece of tile (b, j0) from the LDS image `par`
+    auto piece = [&](int par, size_t b, size_t j0, size_t cols, float (&xq)[kBlock], float (&up)[kBlock], float (&ghat)[kBlock]) {
+        const size_t r = kRows * b + lrow, col = j0 + lcol;
+        T rgy[kBlock], rg[kBlock];
+        load_piece<DT>(gy, a.ld_gy, a.vec_in, r, col, rows, width, rgy);
+        if (gy_add != nullptr) {
+            T ra[kBlock];
+            load_piece<DT>(gy_add, a.ld_add, a.vec_in, r, col, rows, width, ra);
+#pragma unroll
+            for (int k = 0; k < kBlock; ++k) rgy[k] = added<DT>(rgy[k], ra[k]);
+        }
+        load_piece<DT>(gamma, 0, a.vec_gamma, 0, col, 1, width, rg);
+        const uint64_t scales = scale_s[par][grp][u & 7];
+#pragma unroll
+        for (int k = 0; k < kBlock; ++k) {
+            const bool inside = r < rows && lcol + k < static_cast<int>(cols);
+            xq[k] = inside ? mx::decode<FMT>(image_code<FMT>(image[par][grp], lcol + k, lrow), static_cast<uint32_t>(scales >> (8 * k)) & 0xFFu) : 0.0f;
+            up[k] = float_of_bits(widen<DT>(rgy[k]));                           // (outside: +0)
+            ghat[k] = mul_rn(up[k], float_of_bits(widen<DT>(rg[k])));
+        }
+    };
+    bool first = true;                                                          // of this workgroup's row blocks: its rows of the workspace are written, not added to
+    for (size_t b = blockIdx.x; b < a.blocks; b += gridDim.x, first = false) {
+        if (wanted) {
+            // ---- phase A: c1 = sum_j(g^) / width and c2 = sum_j(g^ x^q) / width of the block's rows, ONE sweep ----
+            take();
+            float s1 = 0.0f, s2 = 0.0f;
+            for (size_t round = 0; round < rounds; ++round) {
+                const size_t tl = round * kGroups + grp, j0 = tl * kTileCols;
+                const bool have = tl < across;
+                const size_t cols = !have ? 0 : width - j0 < static_cast<size_t>(kTileCols) ? width - j0 : kTileCols;
+                const int par = static_cast<int>(round & 1);
+                fetch(par, b, j0, cols);
+                __syncthreads();                       // (round i + 1 writes the other image, last read in round i - 1: in front of this barrier)
+                if (have) {
+                    float xq[kBlock], up[kBlock], ghat[kBlock];
+                    piece(par, b, j0, cols, xq, up, ghat);
+#pragma unroll
+                    for (int k = 0; k < kBlock; ++k) {
+                        s1 = add_rn(s1, ghat[k]);
+                        s2 = add_rn(s2, mul_rn(ghat[k], xq[k]));
+                    }
+                }
+            }
+            s1 = eight_sum(s1), s2 = eight_sum(s2);
+            if ((u & 7) == 0) part_s[0][grp][lrow] = s1, part_s[1][grp][lrow] = s2;
+            __syncthreads();
+            if (t < kSums * kRows) {
+                const int q = t >> 5, row = t & (kRows - 1);
+                c_s[q][row] = div_rn(add_rn(add_rn(add_rn(part_s[q][0][row], part_s[q][1][row]), part_s[q][2][row]), part_s[q][3][row]), count);
+            }
+            __syncthreads();
+        }
+        // ---- phase B: dres and dbranch, and the column sums of g * x^q and of g down the block ----
+        take();
+        const int which = (u >> 6) & 1, half = (u >> 5) & 1, ccol = 32 * (u >> 7) + (u & 31);   // the adding role: quantity, half of the rows, column
+        const size_t r = kRows * b + lrow;
+        const float rstd = wanted && r < rows ? a.rstd[r] : 0.0f;
+        const float c1 = wanted ? c_s[0][lrow] : 0.0f, c2 = wanted ? c_s[1][lrow] : 0.0f;
+        for (size_t round = 0; round < rounds; ++round) {
+            const size_t tl = round * kGroups + grp, j0 = tl * kTileCols;
+            const bool have = tl < across;
+            const size_t cols = !have ? 0 : width - j0 < static_cast<size_t>(kTileCols) ? width - j0 : kTileCols;
+            fetch(0, b, j0, cols);
+            __syncthreads();
+            if (have) {
+                float xq[kBlock], up[kBlock], ghat[kBlock];
+                piece(0, b, j0, cols, xq, up, ghat);
+                if (mine != nullptr) {
+#pragma unroll
+                    for (int k = 0; k < kBlock; ++k) {
+                        tile[grp][0][tile_at(lrow, lcol + k)] = mul_rn(up[k], xq[k]);
+                        tile[grp][1][tile_at(lrow, lcol + k)] = up[k];
+                    }
+                }
+                if (wanted) {
+                    const size_t col = j0 + lcol;
+                    T rd[kBlock];
+#pragma unroll
+                    for (int k = 0; k < kBlock; ++k) rd[k] = narrow<DT>(mul_rn(rstd, sub_rn(sub_rn(ghat[k], c1), mul_rn(xq[k], c2))));      // dx, as the plain kernel rounds it
+                    if (gh != nullptr) {
+                        T ra[kBlock];
+                        load_piece<DT>(gh, a.ld_gh, a.vec_in, r, col, rows, width, ra);
+#pragma unroll
+                        for (int k = 0; k < kBlock; ++k) rd[k] = added<DT>(rd[k], ra[k]);
+                    }
+                    if (dres != nullptr) store_piece<DT>(dres, a.ld_dres, a.vec_out, r, col, rows, width, rd);
+                    if (dbranch != nullptr) {
+                        uint32_t w[4];
+                        piece_mask(r, col, width, mask_key, a.threshold, w);
+#pragma unroll
+                        for (int k = 0; k < kBlock; ++k) rd[k] = dropped_gradient<DT>(rd[k], mask_bits(w, k) >= a.threshold, a.scale);
+                        store_piece<DT>(dbranch, a.ld_dbranch, a.vec_out, r, col, rows, width, rd);
+                    }
+                }
+            }
+            __syncthreads();
+            if (mine != nullptr) {                                              // (the whole workgroup alike: the exchange below takes every lane of a wave)
+                const float *from = tile[grp][which];
+                float sum = from[tile_at(kHalfRows * half, ccol)];
+#pragma unroll 5
+                for (int k = 1; k < kHalfRows; ++k) sum = add_rn(sum, from[tile_at(kHalfRows * half + k, ccol)]);
+                const float other = __shfl_xor(sum, 32);                        // lanes 0 .. 31: rows 16 .. 31 of the same column
+                if (half == 0 && static_cast<size_t>(ccol) < cols) {
+                    const float total = add_rn(sum, other);
+                    float *at = mine + which * width + j0 + ccol;
+                    *at = first ? total : add_rn(*at, total);
+                }
+            }
+            // (no barrier here: backward_kernel)
+        }
+    }
+}
+
 }  // namespace mxlnorm
 }  // namespace quant
 }  // namespace fewbit_hip
@@ -383,6 +679,81 @@ int fewbit_hipx_mx_layer_norm_backward(int dtype, const void *gy, size_t ld_gy, 
                          fewbit_hip::mx::blocks_of(rows), wide(gy, ld_gy, dtype), wide(dx, ld_dx, dtype), wide(gamma, 0, dtype)};
     pick_kernel(dtype, format, [&](auto dt, auto fmt) {
         hipLaunchKernelGGL((backward_kernel<dt(), fmt()>), dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    });
+    if (sums)
+        hipLaunchKernelGGL(column_sums_kernel, dim3(static_cast<unsigned>((width + kTileCols - 1) / kTileCols), kSums), dim3(kThreads), 0,
+                           static_cast<hipStream_t>(stream), static_cast<const float *>(workspace), grid, width, dgamma, dbeta);
+    return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
+}
+
+int fewbit_hipx_mx_add_layer_norm_forward(int dtype, const void *x, size_t ld_x, const void *residual, size_t ld_residual, size_t rows, size_t width,
+                                          const void *gamma, const void *beta, float eps, int format, uint64_t seed, uint64_t seed_mask,
+                                          const uint64_t *seed_device, uint32_t threshold, void *y, size_t ld_y, void *h_out, size_t ld_h, float *mean,
+                                          float *rstd, uint8_t *cells, size_t cells_bytes, void *stream) {
+    using namespace mxlnorm;
+    const char *name = "mx_add_layer_norm_forward";
+    if (const int rc = check_call(name, dtype, format, seed_device, rows, width)) return rc;
+    if (const int rc = check_mask(name, threshold, width)) return rc;
+    if (residual == nullptr) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: null pointer (residual)", name);
+    if (x == nullptr || gamma == nullptr || y == nullptr || rstd == nullptr || cells == nullptr) return refuse_null(name);
+    if (ld_x < width || ld_residual < width || ld_y < width || (h_out != nullptr && ld_h < width))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: a row stride ld (%zu, %zu, %zu, %zu) must be at least width = %zu", name, ld_x, ld_residual, ld_y, ld_h, width);
+    const size_t item = size_of(dtype);
+    if (misaligned(x, item) || misaligned(residual, item) || misaligned(y, item) || misaligned(h_out, item) || misaligned(gamma, item) ||
+        misaligned(beta, item) || misaligned(mean, sizeof(float)) || misaligned(rstd, sizeof(float)))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: x, residual, y, h_out, gamma, beta, mean and rstd must be aligned to their element size", name);
+    if (const int rc = check_aligned16(name, "cells", cells)) return rc;
+    if (const int rc = check_bytes(name, "cells", cells_bytes, fewbit_hip::mx::bytes_of(rows, width, format))) return rc;
+    if (matrices_meet(y, ld_y, h_out, ld_h, rows, width, item)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: y and h_out overlap", name);
+    const size_t blocks = fewbit_hip::mx::blocks_of(rows);
+    const AddForwardArgs a{x, residual, ld_x, ld_residual, rows, width, gamma, beta, eps, key_of(seed), key_of(seed_mask),
+                           reinterpret_cast<const Key *>(seed_device), threshold, fewbit_hip::unit::scale_of(threshold), y, h_out, ld_y, ld_h, mean, rstd,
+                           cells, blocks, wide(x, ld_x, dtype), wide(residual, ld_residual, dtype), wide(y, ld_y, dtype), wide(h_out, ld_h, dtype),
+                           wide(gamma, 0, dtype), wide(beta, 0, dtype)};
+    const unsigned grid = static_cast<unsigned>(blocks < kMaxGridForward ? blocks : kMaxGridForward);
+    pick_kernel(dtype, format, [&](auto dt, auto fmt) {
+        hipLaunchKernelGGL((add_forward_kernel<dt(), fmt()>), dim3(grid), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    });
+    return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
+}
+
+int fewbit_hipx_mx_add_layer_norm_backward(int dtype, const void *gy, size_t ld_gy, const void *gy_add, size_t ld_gy_add, const void *gh, size_t ld_gh,
+                                           const uint8_t *cells, size_t cells_bytes, const float *rstd, const void *gamma, size_t rows, size_t width,
+                                           int format, uint64_t seed_mask, const uint64_t *seed_device, uint32_t threshold, void *dres, size_t ld_dres,
+                                           void *dbranch, size_t ld_dbranch, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                                           void *stream) {
+    using namespace mxlnorm;
+    const char *name = "mx_add_layer_norm_backward";
+    const bool sums = dgamma != nullptr || dbeta != nullptr;
+    if (const int rc = check_call(name, dtype, format, seed_device, rows, width)) return rc;
+    if (const int rc = check_mask(name, threshold, width)) return rc;
+    if (dbranch != nullptr && threshold == 0)
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: with threshold = 0 dbranch is dres: pass dbranch = NULL", name);
+    if (gy == nullptr || cells == nullptr || rstd == nullptr || gamma == nullptr || (sums && workspace == nullptr)) return refuse_null(name);
+    if (ld_gy < width || (gy_add != nullptr && ld_gy_add < width) || (gh != nullptr && ld_gh < width) || (dres != nullptr && ld_dres < width) ||
+        (dbranch != nullptr && ld_dbranch < width))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: a row stride ld (%zu, %zu, %zu, %zu, %zu) must be at least width = %zu", name, ld_gy, ld_gy_add, ld_gh,
+                    ld_dres, ld_dbranch, width);
+    const size_t item = size_of(dtype);
+    if (misaligned(gy, item) || misaligned(gy_add, item) || misaligned(gh, item) || misaligned(dres, item) || misaligned(dbranch, item) ||
+        misaligned(gamma, item) || misaligned(rstd, sizeof(float)) || misaligned(dgamma, sizeof(float)) || misaligned(dbeta, sizeof(float)) ||
+        misaligned(workspace, sizeof(float)))
+        return fail(FEWBIT_ERR_INVALID_ARGUMENT,
+                    "%s: gy, gy_add, gh, dres, dbranch, gamma, rstd, dgamma, dbeta and the workspace must be aligned to their element size", name);
+    if (const int rc = check_aligned16(name, "cells", cells)) return rc;
+    if (const int rc = check_bytes(name, "cells", cells_bytes, fewbit_hip::mx::bytes_of(rows, width, format))) return rc;
+    if (sums)
+        if (const int rc = check_bytes(name, "the workspace", workspace_bytes, workspace_of(rows, width))) return rc;
+    if (matrices_meet(dres, ld_dres, dbranch, ld_dbranch, rows, width, item)) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: dres and dbranch overlap", name);
+    if (dres == nullptr && dbranch == nullptr && !sums) return FEWBIT_OK;
+    const size_t grid = backward_grid(rows);
+    const AddBackwardArgs a{gy, gy_add, gh, ld_gy, ld_gy_add, ld_gh, cells, rstd, gamma, rows, width, key_of(seed_mask),
+                            reinterpret_cast<const Key *>(seed_device), threshold, fewbit_hip::unit::scale_of(threshold), dres, dbranch, ld_dres, ld_dbranch,
+                            sums ? static_cast<float *>(workspace) : nullptr, fewbit_hip::mx::blocks_of(rows),
+                            wide(gy, ld_gy, dtype) && wide(gy_add, ld_gy_add, dtype) && wide(gh, ld_gh, dtype),
+                            wide(dres, ld_dres, dtype) && wide(dbranch, ld_dbranch, dtype), wide(gamma, 0, dtype)};
+    pick_kernel(dtype, format, [&](auto dt, auto fmt) {
+        hipLaunchKernelGGL((add_backward_kernel<dt(), fmt()>), dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
     });
     if (sums)
         hipLaunchKernelGGL(column_sums_kernel, dim3(static_cast<unsigned>((width + kTileCols - 1) / kTileCols), kSums), dim3(kThreads), 0,

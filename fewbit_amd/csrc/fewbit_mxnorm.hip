@@ -311,37 +311,7 @@ struct AddBackwardArgs {
     bool vec_gy, vec_gh, vec_dres, vec_dbranch, vec_gamma;
 };
 
-// the 16 mask bits of the eight elements of the piece (r, col .. col + 7), flat block (r width + col) / 8 where width % 8 == 0; threshold 0 keeps
-// everything and draws nothing (the text of norm::mask_words)
-__device__ __forceinline__ void piece_mask(size_t r, size_t col, size_t width, Key key, uint32_t threshold, uint32_t (&w)[4]) {
-    w[0] = w[1] = w[2] = w[3] = ~0u;
-    if (threshold != 0) block_words<kMaskDomain>((static_cast<uint64_t>(r) * width + col) / kBlock, key, w);
-}
-// h = keep ? narrow(widen(x) scale + widen(res)) : res, and dbranch = keep ? narrow(widen(dres) scale) : +0 -- `one<DT, true>` and `one<DT, false>`
-// of fewbit_dropout.hip as fewbit_norm.hip writes them on widen / narrow: the product and the sum are fp32 values of their own (an fp16 operand's
-// conversion, the arithmetic and the rounding must not meet in one v_fma_mix*, which is one step off at the ties)
-template <int DT> __device__ __forceinline__ typename Elem<DT>::type dropped_sum(typename Elem<DT>::type x, typename Elem<DT>::type res, bool keep, float scale) {
-    float v = mul_rn(float_of_bits(widen<DT>(x)), scale);
-    if constexpr (DT == FEWBIT_F16) asm("" : "+v"(v));
-    v = add_rn(v, float_of_bits(widen<DT>(res)));
-    return keep ? narrow<DT>(v) : res;
-}
-template <int DT> __device__ __forceinline__ typename Elem<DT>::type dropped_gradient(typename Elem<DT>::type dres, bool keep, float scale) {
-    const float v = mul_rn(float_of_bits(widen<DT>(dres)), scale);
-    return keep ? narrow<DT>(v) : typename Elem<DT>::type{0};
-}
-// the eight h of the piece (r, col .. col + 7) as rounded to the dtype: two loads and one draw (outside the matrix: +0)
-template <int DT>
-__device__ __forceinline__ void sum_piece(const AddForwardArgs &a, Key mask_key, size_t r, size_t col, typename Elem<DT>::type (&h)[kBlock]) {
-    using T = typename Elem<DT>::type;
-    T rx[kBlock], rr[kBlock];
-    load_piece<DT>(static_cast<const T *>(a.x), a.ld_x, a.vec_x, r, col, a.rows, a.width, rx);
-    load_piece<DT>(static_cast<const T *>(a.residual), a.ld_res, a.vec_res, r, col, a.rows, a.width, rr);
-    uint32_t w[4];
-    piece_mask(r, col, a.width, mask_key, a.threshold, w);
-#pragma unroll
-    for (int k = 0; k < kBlock; ++k) h[k] = dropped_sum<DT>(rx[k], rr[k], mask_bits(w, k) >= a.threshold, a.scale);
-}
+// (piece_mask, dropped_sum, dropped_gradient and sum_piece: fewbit_mxrows.h, shared with the layer norm's fused pair)
 
 // forward_kernel with h = residual + dropout(x) in the place of x: formed in phase A (and stored where h is wanted), formed AGAIN in phase B
 template <int DT, int FMT>
@@ -595,14 +565,6 @@ int fewbit_hipx_mx_rms_norm_backward(int dtype, const void *gy, size_t ld_gy, co
         hipLaunchKernelGGL(column_sums_kernel, dim3(static_cast<unsigned>((width + kTileCols - 1) / kTileCols)), dim3(kThreads), 0,
                            static_cast<hipStream_t>(stream), static_cast<const float *>(workspace), grid, width, dgamma);
     return hipGetLastError() == hipSuccess ? FEWBIT_OK : fail(FEWBIT_ERR_LAUNCH, "%s: the launch failed", name);
-}
-
-// what the fused pair refuses on top: a threshold beyond 65536, and a mask where a lane's piece is no mask block
-static int check_mask(const char *name, uint32_t threshold, size_t width) {
-    if (threshold > kOne) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: threshold = %u is beyond 65536", name, threshold);
-    if (threshold != 0 && width % kBlock != 0)
-        return fail(FEWBIT_ERR_UNSUPPORTED, "%s: a mask (threshold = %u) needs a width that is a multiple of 8, not %zu", name, threshold, width);
-    return FEWBIT_OK;
 }
 
 int fewbit_hipx_mx_add_rms_norm_forward(int dtype, const void *x, size_t ld_x, const void *residual, size_t ld_residual, size_t rows, size_t width,

@@ -1,11 +1,13 @@
 // fewbit_mxrows.h -- what the norms that keep their normalized rows as OCP-MX cells share (fewbit_mxnorm.hip: the RMS norm; fewbit_mxlnorm.hip: the
 // layer norm): the geometry of a workgroup that owns whole row blocks, the fixed-order lane sums, the load role (eight consecutive columns of one
-// row) and the rounding role of mx::pack_kernel on one LDS tile, the cells between the buffer and LDS, and what their entry points refuse alike.
+// row) and the rounding role of mx::pack_kernel on one LDS tile, the cells between the buffer and LDS, what their entry points refuse alike, and
+// the mask and the sum of the pairs that take residual + dropout(x) in front of the norm.
 // Every device function here is inlined into its kernel; the text is the one fewbit_mxnorm.hip had, moved as it was.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <utility>
 
 #include "fewbit_hipx.h"
 #include "fewbit_mxdef.h"
@@ -65,6 +67,43 @@ __device__ __forceinline__ void store_piece(typename Elem<DT>::type *dst, size_t
         for (int k = 0; k < kBlock; ++k)
             if (col + k < width) dst[r * ld + col + k] = raw[k];
     }
+}
+
+// ---- the sum of a seed in front of a norm, h = residual + dropout(x), in the load role (the fused pairs of both units) -------------------------------
+// the 16 mask bits of the eight elements of the piece (r, col .. col + 7), flat block (r width + col) / 8 where width % 8 == 0; threshold 0 keeps
+// everything and draws nothing (the text of norm::mask_words)
+__device__ __forceinline__ void piece_mask(size_t r, size_t col, size_t width, Key key, uint32_t threshold, uint32_t (&w)[4]) {
+    w[0] = w[1] = w[2] = w[3] = ~0u;
+    if (threshold != 0) block_words<kMaskDomain>((static_cast<uint64_t>(r) * width + col) / kBlock, key, w);
+}
+// h = keep ? narrow(widen(x) scale + widen(res)) : res, and dbranch = keep ? narrow(widen(dres) scale) : +0 -- `one<DT, true>` and `one<DT, false>`
+// of fewbit_dropout.hip as fewbit_norm.hip writes them on widen / narrow: the product and the sum are fp32 values of their own (an fp16 operand's
+// conversion, the arithmetic and the rounding must not meet in one v_fma_mix*, which is one step off at the ties)
+template <int DT> __device__ __forceinline__ typename Elem<DT>::type dropped_sum(typename Elem<DT>::type x, typename Elem<DT>::type res, bool keep, float scale) {
+    float v = mul_rn(float_of_bits(widen<DT>(x)), scale);
+    if constexpr (DT == FEWBIT_F16) asm("" : "+v"(v));
+    v = add_rn(v, float_of_bits(widen<DT>(res)));
+    return keep ? narrow<DT>(v) : res;
+}
+template <int DT> __device__ __forceinline__ typename Elem<DT>::type dropped_gradient(typename Elem<DT>::type dres, bool keep, float scale) {
+    const float v = mul_rn(float_of_bits(widen<DT>(dres)), scale);
+    return keep ? narrow<DT>(v) : typename Elem<DT>::type{0};
+}
+// the eight h of the piece (r, col .. col + 7) as rounded to the dtype: two loads and one draw (outside the matrix: +0).  Args: a unit's AddForwardArgs
+template <int DT, class Args>
+__device__ __forceinline__ void sum_piece(const Args &a, Key mask_key, size_t r, size_t col, typename Elem<DT>::type (&h)[kBlock]) {
+    using T = typename Elem<DT>::type;
+    T rx[kBlock], rr[kBlock];
+    load_piece<DT>(static_cast<const T *>(a.x), a.ld_x, a.vec_x, r, col, a.rows, a.width, rx);
+    load_piece<DT>(static_cast<const T *>(a.residual), a.ld_res, a.vec_res, r, col, a.rows, a.width, rr);
+    uint32_t w[4];
+    piece_mask(r, col, a.width, mask_key, a.threshold, w);
+#pragma unroll
+    for (int k = 0; k < kBlock; ++k) h[k] = dropped_sum<DT>(rx[k], rr[k], mask_bits(w, k) >= a.threshold, a.scale);
+}
+// a + b as torch adds two tensors of the dtype: both widened, the fp32 sum rounded once
+template <int DT> __device__ __forceinline__ typename Elem<DT>::type added(typename Elem<DT>::type a, typename Elem<DT>::type b) {
+    return narrow<DT>(add_rn(float_of_bits(widen<DT>(a)), float_of_bits(widen<DT>(b))));
 }
 
 // ---- the rounding role of mx::pack_kernel on one LDS tile of fp32 bits, in its two halves: the caller's barrier lies between them ---------------
@@ -148,6 +187,24 @@ inline int check_call(const char *name, int dtype, int format, const void *seed_
 }
 inline int check_aligned16(const char *name, const char *what, const void *p) {
     return !misaligned(p, 16) ? FEWBIT_OK : fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: %s must be 16-byte aligned", name, what);
+}
+// what the fused pairs refuse on top: a threshold beyond 65536, and a mask where a lane's piece is no mask block
+inline int check_mask(const char *name, uint32_t threshold, size_t width) {
+    if (threshold > kOne) return fail(FEWBIT_ERR_INVALID_ARGUMENT, "%s: threshold = %u is beyond 65536", name, threshold);
+    if (threshold != 0 && width % kBlock != 0)
+        return fail(FEWBIT_ERR_UNSUPPORTED, "%s: a mask (threshold = %u) needs a width that is a multiple of 8, not %zu", name, threshold, width);
+    return FEWBIT_OK;
+}
+// whether two rows x width matrices of `item`-byte elements (either may be absent) share a byte.  Exact where the row strides agree (column
+// blocks of one buffer do not meet); with different strides every meeting of the two spans counts.
+inline bool matrices_meet(const void *p, size_t ld_p, const void *q, size_t ld_q, size_t rows, size_t width, size_t item) {
+    if (p == nullptr || q == nullptr) return false;
+    uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    if (a > b) std::swap(a, b), std::swap(ld_p, ld_q);
+    if (a + ((rows - 1) * ld_p + width) * item <= b) return false;
+    if (ld_p != ld_q) return true;
+    const size_t pitch = ld_p * item, row = width * item, off = (b - a) % pitch;
+    return off < row || off + row > pitch;
 }
 // whether 16-byte pieces serve a tensor (an absent one: they would)
 inline bool wide(const void *p, size_t ld, int dtype) { return !misaligned(p, 16) && ld * size_of(dtype) % 16 == 0; }

@@ -819,9 +819,77 @@ class _LayerNormLinearMX(torch.autograd.Function):
         return (grad_input, grad_gamma, grad_beta, None, None, None, None, None, *grad_weights, *grad_biases)
 
 
+class _AddLayerNormLinearMX(torch.autograd.Function):
+    """``tuple(F.linear(F.layer_norm(residual + dropout(input), gamma, beta), W_i, b_i))`` as ONE node, with the norm's output in front where
+    ``return_normed`` and ``h = residual + dropout(input)`` behind the tuple where ``prenorm``.  Kept for backward: what :class:`_LayerNormLinearMX`
+    keeps -- the cells, ``rstd``, gamma, beta and the weights; neither a mask nor ``h`` nor ``y``.  On ``ctx``: the call's ONE seed draw and ``p``:
+    seed + 0 rounds the cells, seed + 1 + i the fp8 pack of ``G_i``, seed + 1 + count draws the mask."""
+
+    @staticmethod
+    def forward(ctx, input, residual, gamma, beta, eps: float, format: str, generator, return_normed: bool, p: float, prenorm: bool, count: int, *parameters):
+        weights, biases = parameters[:count], parameters[count:]
+        flat, res = input.detach().reshape(-1, input.shape[-1]), residual.detach().reshape(-1, input.shape[-1])
+        ctx.format, ctx.flat_shape, ctx.input_shape, ctx.input_dtype, ctx.count = format, tuple(flat.shape), input.shape, input.dtype, count
+        ctx.has_bias, ctx.has_beta, ctx.return_normed = tuple(b is not None for b in biases), beta is not None, return_normed
+        ctx.p, ctx.prenorm = p, prenorm
+        ctx.autocast = linear._autocast_seen(input.device.type)
+        ctx.set_materialize_grads(False)
+        ctx.native = True                                       # (the caller has made sure that the kernels serve the call: layer_norm_linear_mx)
+        ctx.seed = linear._sketch_seed(generator, flat.device)
+        seeds = (_seed_plus(ctx.seed, 0), _seed_plus(ctx.seed, 1 + count))
+        seeds = torch.cat(seeds) if isinstance(ctx.seed, torch.Tensor) else seeds           # (while capturing: the two device words side by side)
+        y, cells, rstd, h, _ = cabi_x.mx_add_layer_norm_forward(linear._unit_stride(flat), linear._unit_stride(res), _as(gamma, flat.dtype),
+                                                                _as(beta, flat.dtype), eps, format, seeds, p, prenorm)
+        ctx.save_for_backward(cells, rstd, gamma, *(() if beta is None else (beta, )), *weights)
+        y = y.view(input.shape)
+        outputs = tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
+        return (*((y, ) if return_normed else ()), *outputs, *((h.view(input.shape), ) if prenorm else ()))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grad_outputs):
+        with linear._autocast_as(ctx.autocast):
+            return _AddLayerNormLinearMX._backward(ctx, grad_outputs)
+
+    @staticmethod
+    def _backward(ctx, grad_outputs):
+        cells, rstd, gamma, *rest = ctx.saved_tensors           # read once: a non-re-entrant checkpoint unpacks a saved tensor one time only
+        beta, weights = (rest[0], rest[1:]) if ctx.has_beta else (None, rest)
+        (rows, width), count, format, needs = ctx.flat_shape, ctx.count, ctx.format, ctx.needs_input_grad
+        grads = [None if g is None else linear._dense_rows(g).reshape(rows, -1) for g in grad_outputs]
+        at_y = grads.pop(0) if ctx.return_normed else None      # the gradient that arrives at the norm's own output: into the kernel as gy_add
+        at_h = grads.pop() if ctx.prenorm else None             # the gradient that arrives at the sum: into the kernel as gh
+        gy, grad_weights, grad_biases = _linears_backward(ctx, cells, gamma, beta, weights, grads, any(needs[:4]), 11)
+        if not any(needs[:4]):
+            at_y = at_h = None
+        if gy is None and at_y is not None:
+            gy, at_y = at_y, None                               # (nothing arrived at a linear: what arrived at y is gy itself)
+        if gy is None and at_h is not None and (needs[0] or needs[1]):
+            gy = torch.zeros_like(at_h)                         # (nothing arrived at the norm: it hands on 0, to which at_h is added and masked)
+        grad_input = grad_residual = grad_gamma = grad_beta = None
+        if gy is not None:
+            want = (needs[1], needs[0], needs[2], ctx.has_beta and needs[3])        # (dres: the residual's gradient; dbranch: the input's)
+            gy = gy if gy.dtype in DTYPES else gy.float()
+            other = at_y if at_y is not None else at_h
+            gy = gy if other is None or other.dtype == gy.dtype else gy.to(other.dtype)     # (under autocast: y and h have the input's dtype)
+            dres, dbranch, dgamma, dbeta = cabi_x.mx_add_layer_norm_backward(linear._unit_stride(gy), cells, rstd, _as(gamma, gy.dtype), format,
+                                                                             _seed_plus(ctx.seed, 1 + count), ctx.p, at_h, want, at_y)
+            grad_input = dbranch.to(ctx.input_dtype).view(ctx.input_shape) if want[1] else None
+            grad_residual = dres.to(ctx.input_dtype).view(ctx.input_shape) if want[0] else None
+            grad_gamma = dgamma.to(gamma.dtype).view(gamma.shape) if want[2] else None
+            grad_beta = dbeta.to(beta.dtype).view(beta.shape) if want[3] else None
+        return (grad_input, grad_residual, grad_gamma, grad_beta, None, None, None, None, None, None, None, *grad_weights, *grad_biases)
+
+
+def _layer_norm_kernels_take(flat: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor]) -> bool:
+    """whether the kernels of fewbit_mxlnorm.hip serve the rows of ``flat`` with ``gamma`` and ``beta`` (what makes :class:`_LayerNormLinearMX` native)"""
+    return (_mx_kernels_take(flat, gamma) and (beta is None or (beta.device == flat.device and beta.dtype in DTYPES)))
+
+
 def layer_norm_linear_mx(input: torch.Tensor, norm_weight: torch.Tensor, norm_bias: Optional[torch.Tensor], weights: Sequence[torch.Tensor],
                          biases: Optional[Sequence[Optional[torch.Tensor]]] = None, eps: float = 1e-5, format: str = 'fp4',
-                         generator: Optional[torch.Generator] = None, return_normed: bool = False) -> tuple:
+                         generator: Optional[torch.Generator] = None, return_normed: bool = False,
+                         residual: Optional[torch.Tensor] = None, p: float = 0.0, training: bool = True, prenorm: bool = False) -> tuple:
     """``tuple(F.linear(F.layer_norm(input, (width, ), norm_weight, norm_bias, eps), W, b) for W, b in zip(weights, biases))`` as ONE node that keeps
     ONE buffer for all of it: the normalized rows ``x^ = (x - mean) * rstd`` as MXFP4 (``format='fp4'``) or MXFP6 (``'fp6'``) cells down their columns,
     one fp32 ``rstd`` per row, ``norm_weight``, ``norm_bias`` and the weights.  Neither the norm's output, nor the mean, nor the input is kept: because
@@ -839,17 +907,40 @@ def layer_norm_linear_mx(input: torch.Tensor, norm_weight: torch.Tensor, norm_bi
     * Widths above 8192, host tensors and float64 take the host route: the same definitions on ``cabi_x.mx_pack_host``.
     * Grad mode off, or nothing that requires grad: plain ``F.layer_norm`` and ``F.linear``; no seed is drawn, nothing is kept.
     * Under ``torch.autocast`` the norm runs in the input's dtype and the linears as autocast casts them; backward runs under the state the forward
-      saw."""
+      saw.
+    * ``residual`` (of the input's shape): the norm reads ``h = residual + dropout(input, p, training)`` -- every BERT / RoBERTa sublayer's end,
+      ``LayerNorm(dropout(dense(x)) + input)`` -- still as ONE node with ONE seed draw (the mask takes it plus 1 + the number of weights) on one
+      launch forward (``cabi_x.mx_add_layer_norm_forward``); backward adds the gradients arriving at ``y`` and at ``h`` and applies the mask inside
+      the norm's kernel.  Kept: the same tensors -- no mask, not ``h``, not ``y``.  With ``prenorm=True`` ``h`` is the LAST element of the returned
+      tuple (GPT-2 / ViT / OPT: the residual stream that goes on): ``(y if return_normed, *outputs, h if prenorm)``.  The values are bit for bit
+      those of :func:`fewbit.functional.dropout_add` followed by this function.  A mask at a width that is no multiple of 8, widths above 8192,
+      host tensors, float64, a residual of another dtype or device, ``use_native_sketch(False)`` and a call in which nothing trains ARE that
+      composition (two nodes, two seeds)."""
     linear._check_mx_format(format)
     weights = tuple(weights)
     biases = (None, ) * len(weights) if biases is None else tuple(biases)
     if len(biases) != len(weights) or not weights:
         raise ValueError(f'{len(weights)} weights and {len(biases)} biases: one bias (or None) per weight is needed, and at least one weight')
-    if not kept.trains(input, norm_weight, norm_bias, *weights, *biases) or input.numel() == 0:
-        y = F.layer_norm(input, (input.shape[-1], ), norm_weight, norm_bias, float(eps))
-        outputs = tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
-        return (y, *outputs) if return_normed else outputs
-    return _LayerNormLinearMX.apply(input, norm_weight, norm_bias, float(eps), format, generator, bool(return_normed), len(weights), *weights, *biases)
+    if residual is None:
+        if not kept.trains(input, norm_weight, norm_bias, *weights, *biases) or input.numel() == 0:
+            y = F.layer_norm(input, (input.shape[-1], ), norm_weight, norm_bias, float(eps))
+            outputs = tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
+            return (y, *outputs) if return_normed else outputs
+        return _LayerNormLinearMX.apply(input, norm_weight, norm_bias, float(eps), format, generator, bool(return_normed), len(weights), *weights, *biases)
+    _check_p(p)
+    if tuple(residual.shape) != tuple(input.shape):
+        raise ValueError(f'residual should have the shape of input, {tuple(input.shape)}, but got {tuple(residual.shape)}.')
+    p = float(p) if training else 0.0
+    trains = kept.trains(input, residual, norm_weight, norm_bias, *weights, *biases) and input.numel() != 0
+    flat = input.detach().reshape(-1, input.shape[-1]) if trains else None
+    if (not trains or not _layer_norm_kernels_take(flat, norm_weight, norm_bias) or residual.dtype != input.dtype or residual.device != input.device
+            or (cabi_x.dropout_threshold(p) > 0 and flat.shape[1] % 8 != 0)):
+        # nothing trains (plain torch behind the sum), or the kernels do not serve the call: the composition, whose second half is the call without a residual
+        h = dropout_add(input, residual, p, training, generator)
+        outputs = layer_norm_linear_mx(h, norm_weight, norm_bias, weights, biases, eps, format, generator, return_normed)
+        return (*outputs, h) if prenorm else outputs
+    return _AddLayerNormLinearMX.apply(input, residual, norm_weight, norm_bias, float(eps), format, generator, bool(return_normed), p, bool(prenorm),
+                                       len(weights), *weights, *biases)
 
 
 class MXLayerNormLinear(torch.nn.Module):
@@ -857,18 +948,23 @@ class MXLayerNormLinear(torch.nn.Module):
     the attention output's LayerNorm -- as one module that keeps ONE set of MXFP4 / MXFP6 cells for all of them (:func:`layer_norm_linear_mx`);
     ``forward`` returns the tuple of the linears' outputs, with the norm's own output in front where ``return_normed`` (it also feeds the next
     residual there).  The linears are plain ``nn.Linear`` layers in ``self.linears``, the norm's parameters ``self.weight`` and ``self.bias``.  In
-    ``eval()`` mode gradients are torch's exact ones and nothing is kept.
+    ``eval()`` mode gradients are torch's exact ones and nothing is kept.  ``forward(input, residual)`` normalizes ``residual + dropout(input, p)`` in
+    the same node (``p``, ``prenorm``: as in :func:`layer_norm_linear_mx`; with ``prenorm=True`` the sum is the last element of the tuple).
 
         >>> m = fewbit.MXLayerNormLinear(768, [(768, 768, True)] * 3)
         >>> q, k, v = m(torch.randn(128, 768))
         >>> m = fewbit.MXLayerNormLinear.from_modules(layer.attention.output.LayerNorm, [layer.intermediate.dense], return_normed=True)
         >>> y, h = m(hidden)
+        >>> m = fewbit.MXLayerNormLinear.from_modules(layer.attention.output.LayerNorm, [layer.intermediate.dense], return_normed=True, p=0.1)
+        >>> y, h = m(layer.attention.output.dense(context), hidden)            # LayerNorm(dropout(dense(context)) + hidden) and the dense behind it
     """
 
     def __init__(self, width: int, linears, eps: float = 1e-5, bias: bool = True, format: str = 'fp4', generator: Optional[torch.Generator] = None,
-                 return_normed: bool = False, device=None, dtype=None) -> None:
+                 return_normed: bool = False, device=None, dtype=None, p: float = 0.0, prenorm: bool = False) -> None:
         linear._check_mx_format(format)
+        _check_p(p)
         super().__init__()
+        self.p, self.prenorm = float(p), bool(prenorm)
         self.weight = torch.nn.Parameter(torch.ones(width, device=device, dtype=dtype))
         self.register_parameter('bias', torch.nn.Parameter(torch.zeros(width, device=device, dtype=dtype)) if bias else None)
         self.linears = torch.nn.ModuleList(torch.nn.Linear(fin, fout, b, device=device, dtype=dtype) for fin, fout, b in linears)
@@ -878,23 +974,27 @@ class MXLayerNormLinear(torch.nn.Module):
 
     @classmethod
     def from_modules(cls, norm: torch.nn.LayerNorm, linears: Sequence[torch.nn.Linear], format: str = 'fp4', generator: Optional[torch.Generator] = None,
-                     return_normed: bool = False) -> 'MXLayerNormLinear':
+                     return_normed: bool = False, p: float = 0.0, prenorm: bool = False) -> 'MXLayerNormLinear':
         """An ``MXLayerNormLinear`` that SHARES the weight and the bias of ``norm`` -- a ``torch.nn.LayerNorm`` over the last dimension with affine
         parameters -- and the given ``nn.Linear`` modules themselves"""
         weight, bias = getattr(norm, 'weight', None), getattr(norm, 'bias', None)
         if not isinstance(weight, torch.Tensor) or weight.dim() != 1 or not isinstance(getattr(norm, 'eps', None), float):
             raise TypeError(f'{type(norm).__name__} has no 1-D weight with a float eps')
-        new = cls(weight.numel(), [], norm.eps, False, format, generator, return_normed, device='meta')
+        new = cls(weight.numel(), [], norm.eps, False, format, generator, return_normed, device='meta', p=p, prenorm=prenorm)
         new.weight, new.bias, new.linears = weight, bias, torch.nn.ModuleList(linears)
         return new.train(norm.training)
 
-    def forward(self, input: torch.Tensor) -> tuple:
+    def forward(self, input: torch.Tensor, residual: Optional[torch.Tensor] = None) -> tuple:
         weights, biases = [m.weight for m in self.linears], [m.bias for m in self.linears]
-        if not self.training:
-            y = F.layer_norm(input, (input.shape[-1], ), self.weight, self.bias, self.eps)
+        if not self.training:                                   # (eval: the dropout is off, torch's exact gradients on residual + input)
+            h = input if residual is None else residual + input
+            y = F.layer_norm(h, (h.shape[-1], ), self.weight, self.bias, self.eps)
             outputs = tuple(F.linear(y, w, b) for w, b in zip(weights, biases))
-            return (y, *outputs) if self.return_normed else outputs
-        return layer_norm_linear_mx(input, self.weight, self.bias, weights, biases, self.eps, self.format, self.generator, self.return_normed)
+            outputs = (y, *outputs) if self.return_normed else outputs
+            return (*outputs, h) if residual is not None and self.prenorm else outputs
+        return layer_norm_linear_mx(input, self.weight, self.bias, weights, biases, self.eps, self.format, self.generator, self.return_normed, residual,
+                                    self.p, True, self.prenorm)
 
     def extra_repr(self) -> str:
-        return f'{self.weight.numel()}, eps={self.eps}, format={self.format}, return_normed={self.return_normed}'
+        return (f'{self.weight.numel()}, eps={self.eps}, format={self.format}, return_normed={self.return_normed}'
+                + (f', p={self.p}, prenorm={self.prenorm}' if self.p or self.prenorm else ''))

@@ -64,7 +64,9 @@ extern "C" {
  * So was the pre-activation as row blocks (fewbit_hipx_mx_act_forward, _mx_act_backward): inside revision 2, recognised by the presence of the
  * symbols.
  * So was the sum of a seed in front of the normalized rows (fewbit_hipx_mx_add_rms_norm_forward, _mx_add_rms_norm_backward): inside revision 2,
- * recognised by the presence of the symbols. */
+ * recognised by the presence of the symbols.
+ * So was the sum of a seed in front of the centred normalized rows (fewbit_hipx_mx_add_layer_norm_forward, _mx_add_layer_norm_backward): inside
+ * revision 2, recognised by the presence of the symbols. */
 #define FEWBIT_HIPX_ABI_VERSION 1
 #define FEWBIT_HIPX_REVISION 2
 
@@ -825,6 +827,41 @@ int fewbit_hipx_mx_layer_norm_forward(int dtype, const void *x, size_t ld_x, siz
 int fewbit_hipx_mx_layer_norm_backward(int dtype, const void *gy, size_t ld_gy, const uint8_t *cells, size_t cells_bytes, const float *rstd,
                                        const void *gamma, size_t rows, size_t width, int format, void *dx, size_t ld_dx, float *dgamma, float *dbeta,
                                        void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The sum of a seed in front of the centred normalized rows: a BERT / RoBERTa sublayer's end (and a GPT-2 / ViT sublayer's entry) on MX cells,
+ * y = layer_norm(residual + dropout(x)), as ONE launch forward and ONE (and the small one of dgamma and dbeta) backward, in the layer norm's unit.
+ * Nothing new is defined.  T, scale, keep(i) and its flat index, h, h_out, dres and dbranch are those of "The sum of a seed in front of the
+ * normalized rows" above; what is normalized is defined by "The centred normalized rows as row blocks":
+ *   forward:
+ *     h       = keep ? round_to_dtype(float(x) * scale + float(residual)) : residual          formed in registers by each of the kernel's three passes
+ *     y, mean, rstd, cells: those of fewbit_hipx_mx_layer_norm_forward on h AS ROUNDED with `seed` (both row sums in its order); mean may be NULL
+ *     h_out   NULL, or rows x width of `dtype` (row stride ld_h) that receive h, stored by the pass that writes y
+ *   backward:
+ *     g       = gy_add != NULL ? round_to_dtype(float(gy) + float(gy_add)) : gy     gy_add: NULL, or the gradient arriving at the norm's own output y
+ *               (row stride ld_gy_add); g stands in the place of gy in every expression of fewbit_hipx_mx_layer_norm_backward
+ *     dx      = what fewbit_hipx_mx_layer_norm_backward writes for g, rounded to `dtype` as it rounds it
+ *     dres    = gh != NULL ? round_to_dtype(float(dx) + float(gh)) : dx             dbranch = keep ? round_to_dtype(float(dres) * scale) : +0
+ *     dgamma, dbeta: those of the plain backward for g (the same partial sums in the same workspace of fewbit_hipx_mx_layer_norm_workspace bytes,
+ *     the same second launch).  dres, dbranch, dgamma and dbeta may each be NULL: that output is skipped and nothing of it is written.  With T = 0
+ *     dbranch must be NULL.
+ * Every output is bit for bit what fewbit_hipx_dropout (residual as addend), the plain entry point, and an addition of two tensors of `dtype` give.
+ * With T > 0 the width must be a multiple of 8 (anything else: FEWBIT_ERR_UNSUPPORTED; compose the calls).  With T = 0 every width 1 .. 8192 is served.
+ * seed_device: NULL, or the seeds in device memory in the order of the seed arguments (forward: two words, the cells' and the mask's; backward: the
+ * mask's one word; 8-byte aligned), read when the kernel runs.
+ * Refused before anything is launched, in the order of the plain pair: what it refuses (mean may be NULL here), and on top a threshold beyond
+ * 65536, a mask at a width that is no multiple of 8, a NULL residual, ld_residual / ld_h / ld_gy_add / ld_gh / ld_dres / ld_dbranch < width,
+ * residual / h_out / gy_add / gh / dres / dbranch not aligned to their element, dbranch with T = 0, and y and h_out, or dres and dbranch, that
+ * share a byte (with equal row strides column blocks of one buffer do not; with different ones any meeting of the two spans counts). */
+int fewbit_hipx_mx_add_layer_norm_forward(int dtype, const void *x, size_t ld_x, const void *residual, size_t ld_residual, size_t rows, size_t width,
+                                          const void *gamma, const void *beta, float eps, int format, uint64_t seed, uint64_t seed_mask,
+                                          const uint64_t *seed_device, uint32_t threshold, void *y, size_t ld_y, void *h_out, size_t ld_h, float *mean,
+                                          float *rstd, uint8_t *cells, size_t cells_bytes, void *stream);
+int fewbit_hipx_mx_add_layer_norm_backward(int dtype, const void *gy, size_t ld_gy, const void *gy_add, size_t ld_gy_add, const void *gh, size_t ld_gh,
+                                           const uint8_t *cells, size_t cells_bytes, const float *rstd, const void *gamma, size_t rows, size_t width,
+                                           int format, uint64_t seed_mask, const uint64_t *seed_device, uint32_t threshold, void *dres, size_t ld_dres,
+                                           void *dbranch, size_t ld_dbranch, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                                           void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * The pre-activation as row blocks: the activation between the two linears of a plain MLP, h = act(u), whose input is kept as the row blocks of a

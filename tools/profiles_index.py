@@ -82,6 +82,8 @@ ROWS = [
     ('mxlnorm_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 2983 device functions before / after fewbit_mxlnorm.hip was added as a unit of its own (13 new) and the text it shares with fewbit_mxnorm.hip moved to fewbit_mxrows.h, and the registers, scratch, occupancy and LDS of the new kernels', f'{E} 8.35'),
     ('mx_mlp_bench.json', 'tools/mx_mlp_bench.py: MXMLP (fp4, fp6) forward + backward beside MXLinear -> GELU(bits=3) -> MXLinear and the torch MLP at 16384 tokens, 768 -> 3072 -> 768 and 1024 -> 4096 -> 1024, bf16 and fp16, gelu: times, bytes saved per token, allocator peak over one backward; cabi_x.mx_act_forward / mx_act_backward alone against their byte floors, the forward beside mx_pack + F.gelu, the backward beside mx_glu_backward per byte moved (the column pair in a lane against the tile walk)', f'{E} 8.36'),
     ('mx_add_norm_bench.json', 'tools/mx_add_norm_bench.py: rms_norm_linear_mx with a residual (p = 0 with prenorm, p = 0.1 post-norm; fp4, fp6) forward + backward beside dropout_add + rms_norm_linear_mx at 16384 tokens, 4096 -> (4096, 1024, 1024) and 768 -> 3 x 768, bf16 and fp16: times and the allocator peak over one backward; cabi_x.mx_add_rms_norm_forward / mx_add_rms_norm_backward alone beside the kernels they replace', f'{E} 8.37'),
+    ('mx_add_layer_norm_bench.json', 'tools/mx_add_layer_norm_bench.py: layer_norm_linear_mx with a residual (p = 0 and 0.1, post-norm with return_normed and pre-norm; fp4) forward + backward beside dropout_add + layer_norm_linear_mx and beside torch at 16384 tokens, 4096 -> (4096, 1024, 1024) and 768 -> 3072, bf16 and fp16: times, the allocator peak over one backward, bytes kept per token; cabi_x.mx_add_layer_norm_forward / mx_add_layer_norm_backward alone beside the kernels they replace', f'{E} 8.38'),
+    ('mx_add_layer_norm_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 3068 device functions before / after the fused pair was added to fewbit_mxlnorm.hip (12 new; one function differs by a line of padding behind its s_endpgm), and the registers, scratch and LDS of the new kernels', f'{E} 8.38'),
     ('unit_fold_speed*.txt','the launch-bound entry-point arms of quant_linear_bench, dropout_bench, glu_bench and layer_norm_bench from the parent and from the tree with fewbit_unit.h, alternating five times', f'{E} 8.27'),
     ('signed_transform_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1915 device functions before / after the signed pass A was added (228 new)', f'{E} 8.15'),
     ('moments_isa_identity.txt', 'tools/isa_digest.py --diff: machine code of all 1890 device functions before / after fewbit_moments.hip was added (13 new)', f'{E} 8.9'),
